@@ -8,13 +8,16 @@ volumes, inputs resident in HBM.  With N GPUs the calibration set is vols*N volu
 (data-parallel, Gram / statistics all-reduced over RCCL) => weak scaling; value = total volumes / s.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--vols V] [--size S] [--levels L]
+                    [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 starts its own N ranks (``python -m torch.distributed.run --nproc-per-node N``,
 one rank per GPU over RCCL) when it was not itself started by a launcher (WORLD_SIZE unset); under a
 launcher (WORLD_SIZE set) it is one of the ranks.  The parent process never touches the GPU.
 ``--config``: 2 = BraTS net, 4/4 levels, 16 volumes per GPU (default, the headline); 3 = BraTS net,
 16/16 levels, 8 volumes per GPU (8-way: 64 volumes); 4 = LiTS net, 4/4 levels, 8 volumes 1x160^3 per GPU
-(4-way: 32 volumes).  Prints ONE JSON line on rank 0 (progress goes to stderr).
+(4-way: 32 volumes).  Prints ONE JSON line on rank 0 (progress goes to stderr); its `ms_per_step` is the wall clock of
+one timed step.  ``--dump-outputs DIR`` writes rank 0's results of the last timed step as .npy files (see dump_outputs);
+the inputs are seeded, so the same flags give the same inputs on every run.
 """
 import argparse
 import json
@@ -49,7 +52,11 @@ def parse_args(argv=None):
                     help="evaluate every per-iteration loss on the f32 matrix cores (no exact-integer path)")
     ap.add_argument("--spawn-check", action="store_true",
                     help="only start the ranks, run one all-reduce and report the rank count (no calibration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args(argv)
+    if a.steps < 1 and not a.spawn_check:
+        ap.error("--steps must be at least 1")
     preset = CONFIGS[a.config]
     for k, v in preset.items():
         if getattr(a, k) is None:
@@ -450,6 +457,73 @@ def cpu_baseline(levels, vols, size):
                        "(favours the CPU)")
 
 
+DUMP_SAMPLE = 1 << 20            # elements kept of a network output larger than this (fixed, seeded index set)
+DUMP_PARAM_SAMPLE = 1 << 23      # the same for a concatenated parameter array (BraTS net: 6.0 M weights, kept whole)
+DUMP_BUDGET = 64 << 20           # bytes of all dumped arrays together
+
+
+def _dump_counts(sizes, caps, itemsize, budget=DUMP_BUDGET):
+    """Elements kept per array: min(size, cap), and when those still exceed `budget` bytes together, the budget shared out
+    smallest first (an array below its even share keeps what it has, the rest split what is left evenly).  Depends on the
+    sizes only, so the same shapes give the same counts on every run."""
+    want = [min(n, c) for n, c in zip(sizes, caps)]
+    if sum(w * b for w, b in zip(want, itemsize)) <= budget:
+        return want
+    keep, left = list(want), budget
+    order = sorted(range(len(want)), key=lambda i: want[i] * itemsize[i])
+    for k, i in enumerate(order):
+        keep[i] = min(want[i], left // (len(order) - k) // itemsize[i])
+        left -= keep[i] * itemsize[i]
+    return keep
+
+
+def dump_outputs(out_dir, res, model):
+    """--dump-outputs DIR: what the last timed calibration handed its caller, as DIR/<name>.npy (float32 / float64):
+    the network outputs (FP and quantised) and the attention weight map, the per-layer losses, the class voxel counts,
+    and the calibrated parameters of every conv of the model (weights, biases, weight and activation scales), each kind
+    concatenated in state_dict order.  The mask pyramid is left out on purpose: calibrate_model derives it from
+    output_fp and the inputs.  An array above its cap (DUMP_SAMPLE for an output, DUMP_PARAM_SAMPLE for a parameter
+    array; less if all of them would exceed DUMP_BUDGET) is kept at a seeded set of flat indices, the same on every
+    run of the same shapes, and written as <name>_sample.npy.  The BraTS net's parameters are written whole; the LiTS
+    net's 22.8 M weights are sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    entries = []                    # (name, flat tensor, cap, numpy dtype)
+
+    def tensors(prefix, v):
+        if torch.is_tensor(v):
+            yield prefix, v
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                yield from tensors(f"{prefix}_{i}", x)
+
+    for key in ("output_fp", "output_q", "weight_map"):
+        for name, t in tensors(key, res[key]):
+            entries.append((name, t.detach().reshape(-1), DUMP_SAMPLE, np.float32))
+    entries.append(("layer_loss", torch.tensor([float(s.rsplit(":", 1)[1]) for s in res["layer_loss"]],
+                                               dtype=torch.float64), DUMP_SAMPLE, np.float64))
+    entries.append(("class_nums", torch.tensor([float(n) for n in res["nums"]], dtype=torch.float64),
+                    DUMP_SAMPLE, np.float64))
+    sd = model.state_dict()
+    for kind in ("weight", "bias", "alpha_w", "alpha_act"):
+        parts = [v.detach().reshape(-1).float() for k, v in sd.items() if k.rsplit(".", 1)[-1] == kind]
+        if parts:
+            entries.append((f"calibrated_{kind}", torch.cat([p.to(parts[0].device) for p in parts]),
+                            DUMP_PARAM_SAMPLE, np.float32))
+    counts = _dump_counts([e[1].numel() for e in entries], [e[2] for e in entries],
+                          [np.dtype(e[3]).itemsize for e in entries])
+    total = 0
+    for (name, flat, _, dt), k in zip(entries, counts):
+        if k < flat.numel():
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), k))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            name += "_sample"
+        arr = flat.cpu().numpy().astype(dt, copy=False)
+        total += arr.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"[rank 0] dumped {len(entries)} arrays ({total / 2 ** 20:.1f} MB) to {out_dir}")
+
+
 def spawn_check(a, world, rank, local):
     """--spawn-check: the launch path only (ranks start, rendezvous, one all-reduce), no calibration."""
     use_gpu = torch.cuda.is_available()
@@ -567,6 +641,8 @@ def main():
     coll_per_step = _SR.calls / max(1, a.steps)
     unwrap()
     timer.collect_library()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res, model)        # before the sub-runs below recalibrate the model
     tmax = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
     if world > 1 and comm is not None:
         comm.all_reduce_max_(tmax)

@@ -21,3 +21,17 @@ def load_gold(name):
 @pytest.fixture(scope="session")
 def gold():
     return load_gold
+
+
+# the goldens were made with this many intra-op CPU threads (tests/golden/make_goldens.py); CPU reductions round
+# differently with the thread count, so the tests that reproduce them bit for bit pin it instead of taking the host's
+GOLDEN_THREADS = 8
+
+
+@pytest.fixture
+def golden_threads():
+    import torch
+    before = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield GOLDEN_THREADS
+    torch.set_num_threads(before)

@@ -245,6 +245,7 @@ def _run_tiny(task, fname, gold, monkeypatch):
     return g, model, res
 
 
+@pytest.mark.usefixtures("golden_threads")       # the whole-net run amplifies last-ulp differences layer by layer
 @pytest.mark.parametrize("task,fname", [("brats", "g6_tiny_brats_L4.npz"), ("brats", "g6c_tiny_brats_L4.npz")])
 def test_whole_calibration_on_oracle_backend_matches_reference(gold, monkeypatch, task, fname):
     g, model, res = _run_tiny(task, fname, gold, monkeypatch)
@@ -330,45 +331,45 @@ def test_data_parallel_two_ranks_gloo_matches_single_rank(tmp_path):
     assert np.all(np.abs(a - b) <= 1e-3 * b), (a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="needs the reference checkout (build container only)")
-def test_reference_side_registration_shim_satisfies_the_reference_orchestrator():
+def test_registration_shim_with_a_foreign_base_keeps_the_hip_calibrator():
     """the two-line class a maintainer adds to the reference tree - the HIP calibrator with the
-    reference's own PTQConv as a second base - is what makes the reference's ptqer helpers (isinstance(module, (PTQConv,
-    PTQBlock)), ptqer.py:17-80) see the layers.  Built here against the REAL reference classes (in a child process: the
-    reference's package names must not leak into this test session): construction through the product's UResQ factory,
-    MRO, the reference's mode / name / mask broadcasters, state_dict keys."""
-    code = r'''
-import sys, types
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference/src")
-nib = types.ModuleType("nibabel")
-nib.Nifti1Image, nib.load = (lambda *a, **k: None), (lambda f: None)
-sys.modules["nibabel"] = nib                       # the one dependency of ptqer that this image lacks (SURVEY appendix A)
-from models.PTQConv import PTQConv as RefPTQConv
-import ptqer
-sys.path.insert(0, sys.argv[1])
-from efficientq_amd.qconv import EfficientQConvHIP as Hip
-from efficientq_amd import config as Cf
-class EfficientQConvHIP(Hip, RefPTQConv):          # the shim of INTEGRATION.md
-    pass
-assert [c.__module__.split(".")[0] for c in EfficientQConvHIP.__mro__[1:4]] == ["efficientq_amd", "efficientq_amd", "models"]
-args = Cf.make_args(Cf.TINY_NET, 4, 4)
-_, _, kwQ = Cf.get_conv_class(args)
-model = Cf.get_model_cube(args, EfficientQConvHIP, kwQ)[0]["model"]
-q = [m for m in model.modules() if isinstance(m, RefPTQConv)]
-assert len(q) == 10 and all(isinstance(m, Hip) for m in q)
-ptqer.set_name(model); ptqer.set_mask(model, ["m"]); ptqer.set_quantizing(model)
-assert q[0].name == "conv0.conv" and q[0].mask_pyramid == ["m"] and q[0]._quantizing and not q[0]._fp
-ptqer.set_quantized(model)
-assert all(m._quantized for m in q)
-keys = set(model.state_dict())
-assert {"conv0.conv.weight", "conv0.conv.alpha_act", "conv0.conv.alpha_w"} <= keys
-assert type(q[0]).ptq is Hip.ptq                   # the HIP calibrator, not the reference's NotImplementedError
-print("ok")
-'''
-    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-3000:]
+    reference's own PTQConv as a second base - is what makes the reference's helpers (isinstance(module, PTQConv))
+    see the layers.  The foreign base here is a stand-in nn.Conv3d subclass with a broadcaster that finds layers by
+    isinstance, as the reference's do: construction through the product's UResQ factory, MRO, the foreign and the
+    product's mode / name / mask broadcasters, state_dict keys, and the HIP `ptq` winning the method lookup."""
+    from efficientq_amd import calibrate as K, config as Cf
+    from efficientq_amd.qconv import EfficientQConvHIP as Hip
+
+    class ForeignPTQConv(nn.Conv3d):
+        def ptq(self, *a, **kw):
+            raise NotImplementedError
+
+    def foreign_set_anything(model, attr, value):
+        for m in model.modules():
+            if isinstance(m, ForeignPTQConv):
+                setattr(m, attr, value)
+
+    class EfficientQConvHIP(Hip, ForeignPTQConv):      # the shim of INTEGRATION.md
+        pass
+
+    mods = [c.__module__.split(".")[0] for c in EfficientQConvHIP.__mro__[1:4]]
+    assert mods == ["efficientq_amd", "efficientq_amd", __name__.split(".")[0]], mods
+    assert EfficientQConvHIP.__mro__.index(ForeignPTQConv) < EfficientQConvHIP.__mro__.index(nn.Conv3d)
+    args = Cf.make_args(Cf.TINY_NET, 4, 4)
+    _, _, kwQ = Cf.get_conv_class(args)
+    model = Cf.get_model_cube(args, EfficientQConvHIP, kwQ)[0]["model"]
+    q = [m for m in model.modules() if isinstance(m, ForeignPTQConv)]
+    assert len(q) == 10 and all(isinstance(m, Hip) for m in q)
+    assert q == [m for m in model.modules() if isinstance(m, Hip)]
+    K.set_name(model)
+    foreign_set_anything(model, "mask_pyramid", ["m"])
+    K.set_quantizing(model)
+    assert q[0].name == "conv0.conv" and q[0].mask_pyramid == ["m"] and q[0]._quantizing and not q[0]._fp
+    K.set_quantized(model)
+    assert all(m._quantized for m in q)
+    keys = set(model.state_dict())
+    assert {"conv0.conv.weight", "conv0.conv.alpha_act", "conv0.conv.alpha_w"} <= keys
+    assert type(q[0]).ptq is Hip.ptq                   # the HIP calibrator, not the foreign base's NotImplementedError
 
 
 def _bench(*flags, env=None, timeout=600):
@@ -383,7 +384,7 @@ def test_bench_starts_its_own_ranks_for_gpus_above_one():
     """`python bench.py --gpus N` (the driver's command form) must launch N ranks itself, run a real all-reduce over
     them and relay exactly ONE JSON line; here on gloo / CPU, without any calibration (--spawn-check)."""
     import json
-    r = _bench("--gpus", "2", "--spawn-check")
+    r = _bench("--gpus", "2", "--spawn-check", env={"EFFQ_BENCH_BACKEND": "gloo"})    # whatever GPUs the host has
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -432,3 +433,76 @@ def test_sliding_window_helpers_match_reference(gold, tag, psz, ov):
     d_l = torch.stack([d.float() for d in E.validate_vs_label(logits, torch.from_numpy(g["m_tgt_lits"]), "lits")])
     d_b = torch.stack([d.float() for d in E.validate_vs_label(logits, torch.from_numpy(g["m_tgt_brats"]), "brats")])
     assert torch.equal(d_l, torch.from_numpy(g["m_dice_lits"])) and torch.equal(d_b, torch.from_numpy(g["m_dice_brats"]))
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: every result of the step as a float32 / float64 .npy, large outputs sampled at the same
+    seeded indices on every call, the calibrated parameters whole, at most 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    from efficientq_amd import config as Cf
+    args = Cf.make_args(Cf.TINY_NET, 4, 4)
+    QConv, _, kwQ = Cf.get_conv_class(args)
+    model = Cf.get_model_cube(args, QConv, kwQ)[0]["model"]
+    gen = torch.Generator().manual_seed(0)
+    big = torch.randn(bench.DUMP_SAMPLE + 5, generator=gen)
+    res = dict(output_fp=[torch.randn(2, 3, 4, generator=gen), big], output_q=[big * 2.0], weight_map=torch.ones(7),
+               layer_loss=[f"{'conv0.conv':45s}:0.125", f"{'conv1.conv':45s}:2.5"], nums=[3, 4])
+    bench.dump_outputs(str(tmp_path / "a"), res, model)
+    bench.dump_outputs(str(tmp_path / "b"), res, model)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(["output_fp_0.npy", "output_fp_1_sample.npy", "output_q_0_sample.npy", "weight_map.npy",
+                            "layer_loss.npy", "class_nums.npy", "calibrated_weight.npy", "calibrated_bias.npy",
+                            "calibrated_alpha_w.npy", "calibrated_alpha_act.npy"])
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "output_fp_1_sample.npy").size == bench.DUMP_SAMPLE
+    assert np.array_equal(np.load(tmp_path / "a" / "output_q_0_sample.npy"),
+                          2.0 * np.load(tmp_path / "a" / "output_fp_1_sample.npy"))
+    assert np.load(tmp_path / "a" / "layer_loss.npy").tolist() == [0.125, 2.5]
+    sd = model.state_dict()
+    assert np.load(tmp_path / "a" / "calibrated_weight.npy").size == sum(
+        v.numel() for k, v in sd.items() if k.endswith(".weight"))
+
+
+def test_bench_dump_outputs_samples_the_lits_net_parameters_within_the_size_limit(tmp_path):
+    """The LiTS net (--config 4) holds 22.8 M weights, 91 MB in float32: the dump keeps a seeded sample of them and stays
+    within 64 MB, and so does a dump with more outputs than the per-array caps leave room for."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    _, model = bench.build_model(4, "cpu", "lits")
+    n_w = sum(v.numel() for k, v in model.state_dict().items() if k.endswith(".weight"))
+    assert n_w > bench.DUMP_PARAM_SAMPLE
+    gen = torch.Generator().manual_seed(0)
+    out = torch.randn(2 * bench.DUMP_SAMPLE, generator=gen)
+    res = dict(output_fp=out, output_q=out * 0.5, weight_map=torch.ones(3), layer_loss=[f"{'c':45s}:1.0"] * 28, nums=[1, 2, 3])
+    for tag, r in (("lits", res), ("many", dict(res, output_fp=[out] * 24))):
+        for run in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / tag / run), r, model)
+        files = sorted(p.name for p in (tmp_path / tag / "a").iterdir())
+        total = 0
+        for n in files:
+            x, y = np.load(tmp_path / tag / "a" / n), np.load(tmp_path / tag / "b" / n)
+            assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), (tag, n)
+            total += x.nbytes
+        assert total <= 64 << 20, (tag, total)
+        assert "calibrated_weight_sample.npy" in files and "calibrated_bias.npy" in files
+        assert np.load(tmp_path / tag / "a" / "layer_loss.npy").size == 28
+    assert np.load(tmp_path / "lits" / "a" / "calibrated_weight_sample.npy").size == bench.DUMP_PARAM_SAMPLE
+    assert np.load(tmp_path / "lits" / "a" / "output_fp_sample.npy").size == bench.DUMP_SAMPLE
+
+
+def test_bench_dump_counts_share_the_budget_smallest_first():
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    assert bench._dump_counts([10, 5], [8, 8], [4, 8], budget=1000) == [8, 5]
+    # 40 + 400 + 4000 bytes wanted, 1000 allowed: the arrays below their even share whole, the last one what is left
+    assert bench._dump_counts([10, 100, 1000], [10 ** 6] * 3, [4, 4, 4], budget=1000) == [10, 100, 140]
+    assert bench._dump_counts([10, 100, 1000], [10 ** 6] * 3, [4, 4, 4], budget=400) == [10, 45, 45]

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 from oracle import effq_oracle as O
 
 T = torch.from_numpy
+pytestmark = pytest.mark.usefixtures("golden_threads")     # the goldens' CPU thread count (conftest.py)
 
 
 def test_g1_discretize_bit_exact(gold):
