@@ -70,7 +70,8 @@ class AdmmRunArgs(C.Structure):
                 ("stream_main", C.c_void_p), ("stream_loss", C.c_void_p), ("stream_side", C.c_void_p),
                 ("stream_side2", C.c_void_p), ("inv_ws_side2", C.c_void_p), ("inv_ws_side2_bytes", C.c_size_t),
                 ("loss_Au", C.c_void_p), ("loss_Bu", C.c_void_p), ("loss_syy", C.c_void_p),
-                ("loss_planes", C.c_void_p), ("loss_nplanes", C.c_int32), ("res_ring", C.c_void_p)]
+                ("loss_planes", C.c_void_p), ("loss_nplanes", C.c_int32), ("res_ring", C.c_void_p),
+                ("channel_wise", C.c_int32), ("alpha_ring", C.c_void_p), ("w_iters_ring", C.c_void_p)]
 
 
 class ProfRecord(C.Structure):
@@ -114,6 +115,10 @@ SIGNATURES = {
     "effq_fixed_point_bucket_rec": (_I, [_P, _P, _P, _SZ, _I, _D, _D, _D, _I, _P, _P, _SZ, _P, _P]),
     "effq_fixed_point_coop_rec": (_I, [_P, _P, _P, _SZ, _I, _D, _D, _D, _I, _P, _P, _P, _P]),
     "effq_fp_check": (_I, [_P, _P, _P]),
+    "effq_fp_channels_max_row": (_I, []),
+    "effq_fixed_point_channels": (_I, [_P, _P, _P, _I, _I, _I, _D, _I, _P, _P, _P, _P]),
+    "effq_fixed_point_channels_proj": (_I, [_P, _P, _P, _I, _I, _I, _D, _I, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _D,
+                                            _D, _P]),
     "effq_gram_packed_elems": (_SZ, [_I, _I]),
     "effq_gram_pack": (_I, [_P, _P, _I, _I, _P, _P]),
     "effq_gram_unpack": (_I, [_P, _I, _I, _P, _P, _P]),

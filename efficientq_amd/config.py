@@ -67,6 +67,8 @@ def build_parser():
     p.add_argument('--lwq_batchsz', type=int, default=1)
     p.add_argument('--lwq_patchsz')
     p.add_argument('--lwq_verbose', action='store_true')
+    # new in this build: one weight scale per output channel (the reference's alpha_w is one scalar per layer)
+    p.add_argument('--lwq_channel_wise', action='store_true')
     p.add_argument('--save_nii', action='store_true')
     # new in this build: synthetic calibration volumes (no dataset is shipped with either repo)
     p.add_argument('--synthetic', action='store_true', help='calibrate on seeded synthetic volumes')

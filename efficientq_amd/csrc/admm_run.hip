@@ -38,6 +38,11 @@ int effq_fixed_point_traj_parts(const float* part, int nsplit, int ldp, int c2, 
                                 float* wstar_out, float* bstar_out, float* v_out, int levels, double lo, double hi, double tol,
                                 int max_iter, effq_fp_state* state_dev, void* pred_dev, void* ws, size_t ws_bytes,
                                 void* stream);                                          // fixed_point_traj.hip
+int effq_fixed_point_channels_proj(const float* wstar, float* dual, float* v_out, int c2, int nwrow, int levels,
+                                   double tol, int max_iter, double* alpha_out, int32_t* iters_out, int32_t* err_flag_dev,
+                                   float* G, float dual_div, float* Bm, const float* B0, const float* W0, int n, int ldb,
+                                   double rho_next, double eta, void* stream);   // fixed_point_channels.hip
+int effq_fp_channels_max_row(void);
 int effq_project_dual_checked(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
                               float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
                               void* stream);   // quant_reduce.hip (internal)
@@ -245,6 +250,13 @@ int effq_admm_run(const effq_admm_run_args* a) {
   const int c2 = a->c2, n = a->n, has_b = a->has_bias ? 1 : 0;
   const size_t nw = (size_t)c2 * (size_t)(n - has_b);
   EFFQ_CHECK_ARG(nw == (size_t)a->geom.C2 * a->geom.C1 * a->geom.KD * a->geom.KH * a->geom.KW);
+  // channel mode: one scale per output row (effq_fixed_point_channels_proj).  The integer loss paths fold ONE scalar scale
+  // into their arithmetic (conv3d_i8*.hip epilogues, effq_gram_loss_i8's integer Q): only the losses that take G as fp32
+  // values are accepted
+  const bool chan = a->channel_wise != 0;
+  if (chan)
+    EFFQ_CHECK_ARG((a->loss_kind == 0 || a->loss_kind == 4) && a->alpha_ring != nullptr &&
+                   n - has_b <= effq_fp_channels_max_row());
   if (nw > effq_fp_coop_max()) {
     set_error("admm_run: %zu weights exceed the single-launch fixed points", nw);
     return EFFQ_ERR_ARG;
@@ -255,7 +267,7 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // kernels win at every size)
   static const size_t bucket_max = getenv("EFFQ_FP_BUCKET_MAX") ? (size_t)atoll(getenv("EFFQ_FP_BUCKET_MAX"))
                                                                 : ((size_t)1 << 19);          // tuning aid
-  const bool bucket = a->fp_ws != nullptr && a->w_levels <= 16 && nw > 4096 && nw <= bucket_max;
+  const bool bucket = !chan && a->fp_ws != nullptr && a->w_levels <= 16 && nw > 4096 && nw <= bucket_max;
   if (bucket && a->fp_ws_bytes < effq_fp_bucket_ws_bytes(nw)) {
     set_error("admm_run: fixed-point workspace %zu < %zu", a->fp_ws_bytes, effq_fp_bucket_ws_bytes(nw));
     return EFFQ_ERR_WORKSPACE;
@@ -273,7 +285,7 @@ int effq_admm_run(const effq_admm_run_args* a) {
   static const int traj_after_env = getenv("EFFQ_FP_TRAJ_AFTER") ? atoi(getenv("EFFQ_FP_TRAJ_AFTER")) : 12;
   static const int traj_after_big = getenv("EFFQ_FP_TRAJ_AFTER_BIG") ? atoi(getenv("EFFQ_FP_TRAJ_AFTER_BIG")) : 30;
   const int traj_after = (nw > ((size_t)1 << 20)) ? traj_after_big : traj_after_env;
-  const bool traj = a->fp_pred != nullptr && a->fp_traj_ws != nullptr && effq_admm_uses_traj(nw, a->w_levels) != 0;
+  const bool traj = !chan && a->fp_pred != nullptr && a->fp_traj_ws != nullptr && effq_admm_uses_traj(nw, a->w_levels) != 0;
   if (traj && a->fp_traj_ws_bytes < effq_fp_traj_ws_bytes(nw)) {
     set_error("admm_run: trajectory fixed-point workspace %zu < %zu", a->fp_traj_ws_bytes, effq_fp_traj_ws_bytes(nw));
     return EFFQ_ERR_WORKSPACE;
@@ -515,7 +527,15 @@ int effq_admm_run(const effq_admm_run_args* a) {
       }
     }
     void* rec = traj ? a->fp_pred : nullptr;
-    if (use_traj && parts != nullptr) {
+    if (chan) {
+      // every row's fixed point, projection, dual update and the next Bm in one launch (no per-tensor kernel runs)
+      ADMM_RC(effq_fixed_point_channels_proj(a->wstar, a->dual, a->v, c2, n - has_b, a->w_levels, a->tol, 100 * a->w_levels,
+                                             a->alpha_ring + (size_t)i * c2,
+                                             a->w_iters_ring ? a->w_iters_ring + (size_t)i * c2 : nullptr, a->err_flag, G,
+                                             dual_div, next_rhs ? bm : nullptr, a->B0, a->W0, n, bm_ld, rho_next, a->eta,
+                                             s_main));
+      fuse_proj = true;
+    } else if (use_traj && parts != nullptr) {
       fuse_proj = false;
       ADMM_RC(effq_fixed_point_traj_parts(parts, parts_n, parts_ld, c2, n - has_b, has_b ? 1 : 0, a->dual, a->wstar, bstar,
                                           a->v, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels, st, a->fp_pred,

@@ -41,8 +41,22 @@ struct ProjNext {
   float rho, eta;
 };
 
-// Four consecutive weights: 16-byte accesses, one (row, column) split with 32-bit arithmetic, and the level index from the
-// fp32 evaluation of level_accum (the reference's fp64 arithmetic decides within 2e-4 of a rounding boundary: exact).
+// Level index of one value at scale alpha: the fp32 evaluation of level_accum, with the reference's fp64 arithmetic
+// deciding within 2e-4 of a rounding boundary (exact).
+__device__ __forceinline__ float proj_level(float v, double alpha, const LevelConsts& lc, double d) {
+  float u = __builtin_fmaf(v, lc.c1, lc.c0);
+  u = fminf(fmaxf(u, 0.0f), lc.lmax);
+  float rf = rintf(u);
+  if (!(fabsf(u - rf) < 0.4998f)) {
+    double r;
+    disc64((double)v, alpha, -1.0, 1.0, d, &r);
+    rf = (float)r;
+  }
+  return rf;
+}
+
+// Four consecutive weights: 16-byte accesses, one (row, column) split with 32-bit arithmetic, and the level index from
+// proj_level.
 __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const float* wstar, double alpha, float alpha32,
                                             const LevelConsts& lc, double d, float* G, float* dual, float dual_div,
                                             int8_t* Gq, int lm1, const ProjNext& nx) {
@@ -54,14 +68,7 @@ __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const fl
   int ri[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float u = __builtin_fmaf(ve[e], lc.c1, lc.c0);
-    u = fminf(fmaxf(u, 0.0f), lc.lmax);
-    float rf = rintf(u);
-    if (!(fabsf(u - rf) < 0.4998f)) {
-      double r;
-      disc64((double)ve[e], alpha, -1.0, 1.0, d, &r);
-      rf = (float)r;
-    }
+    const float rf = proj_level(ve[e], alpha, lc, d);
     ri[e] = (int)rf;
     const float b = (float)((double)rf * d + -1.0);       // disc64's r * d + lo
     ge[e] = alpha32 * b;
@@ -94,6 +101,26 @@ __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const fl
       be[e] = t + nx.rho * (ge[e] - du[e]);
     }
     *reinterpret_cast<float4*>(nx.Bm + (size_t)r * (size_t)nx.ldb + k) = make_float4(be[0], be[1], be[2], be[3]);
+  }
+}
+
+// One weight (element i = r * nwrow + k, from registers) with proj4_apply's arithmetic, for rows of any length (the
+// per-output-channel fixed point, fixed_point_channels.hip).  zero_row: G = 0 (a row with sum |v| = 0 has scale 0).
+__device__ __forceinline__ void proj1_apply(size_t i, unsigned r, unsigned k, float v, double alpha, float alpha32,
+                                            const LevelConsts& lc, double d, bool zero_row, const float* wstar, float* G,
+                                            float* dual, float dual_div, const ProjNext& nx) {
+  float g = 0.0f;
+  if (!zero_row) {
+    const float b = (float)((double)proj_level(v, alpha, lc, d) * d + -1.0);
+    g = alpha32 * b;
+  }
+  float t = (wstar[i] - g) + dual[i];                     // EfficientQConv.py:111
+  if (dual_div != 1.0f) t = t / dual_div;
+  G[i] = g;
+  dual[i] = t;
+  if (nx.Bm != nullptr) {
+    float bv = nx.B0[(size_t)r * (size_t)nx.n + k] + nx.eta * nx.W0[i];
+    nx.Bm[(size_t)r * (size_t)nx.ldb + k] = bv + nx.rho * (g - t);
   }
 }
 

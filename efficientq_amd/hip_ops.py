@@ -661,14 +661,16 @@ class HipOps:
     # -- the whole ADMM loop of a layer in one binding call ---------------------------------------------
     def admm_run(self, A0, B0, W0, b0, geom: Geom, y_ndhwc, *, xq=None, xidx=None, act_alpha=None, act_levels: int = 0,
                  loss_kind: int = 0, rho: float, rho_max: float, eta: float, iters: int, period: int, levels: int,
-                 overlap: bool = True, loss_gram=None, residuals: bool = False):
+                 overlap: bool = True, loss_gram=None, residuals: bool = False, channel_wise: bool = False):
         """effq_admm_run: enqueue `iters` ADMM iterations (chain on the current stream, per-iteration loss on the
         loss stream, later inverses on the side stream).  Returns a handle with the rings and `hist` (iters x 2
         device doubles, sums of squared errors); no host synchronisation.
         Memory: every iterate is kept until the best one is picked after the loop (G_ring: iters x nw floats, plus an
         int8 copy where the loss is an integer conv): 1.75 GB for a 256 -> 256 3^3 layer, 7 GB for LiTS' 512 -> 512,
         linear in `iters` (200 in the reference, a constructor constant there) - of 288 GB; the reference keeps one
-        best iterate but synchronises with the host every iteration to do so."""
+        best iterate but synchronises with the host every iteration to do so.
+        channel_wise: one weight scale per output channel (effq_fixed_point_channels_proj); the run then carries
+        `alpha_ring` (iters x c2 doubles) and `w_iters_ring` (iters x c2 int32).  Loss kinds 0 and 4 only."""
         from types import SimpleNamespace
         c2, n = (int(i) for i in B0.shape)
         has_b = b0 is not None
@@ -686,6 +688,8 @@ class HipOps:
             loss_gram = loss_gram[:3]
         elif loss_gram is not None:
             loss_kind = 4                         # (Au, Bu, syy): losses from the unweighted Gram system
+        if channel_wise and loss_kind not in (0, 4):
+            raise _lib.EffqError(f"admm_run: channel mode takes loss kinds 0 and 4, not {loss_kind}")
         _check_shapes(geom, xq if loss_kind in (0, 4, 5) else xidx, W0, b0, y)
         if tuple(A0.shape) != (n, n) or nw != c2 * (n - int(has_b)):
             raise _lib.EffqError("admm_run: A0/B0/W0 shapes do not match")
@@ -694,7 +698,7 @@ class HipOps:
             raise _lib.EffqError("admm_run: bad rho schedule")
         dev, f32 = self.device, torch.float32
         ld = self.lib.effq_ainv_ld(n)
-        r = SimpleNamespace(iters=int(iters), nw=nw, c2=c2, has_b=has_b)
+        r = SimpleNamespace(iters=int(iters), nw=nw, c2=c2, has_b=has_b, channel_wise=bool(channel_wise))
         r.ainv = torch.empty(n_inv, n, ld, dtype=f32, device=dev)
         r.dual = torch.empty(nw, dtype=f32, device=dev)
         r.wstar = torch.empty(nw, dtype=f32, device=dev)
@@ -706,6 +710,8 @@ class HipOps:
         r.hist = torch.zeros(iters, 2, dtype=torch.float64, device=dev)
         r.err = torch.zeros(1, dtype=torch.int32, device=dev)
         r.res = torch.zeros(iters, 2, dtype=torch.float64, device=dev) if residuals else None     # lwq_verbose
+        r.alpha_ring = torch.zeros(iters, c2, dtype=torch.float64, device=dev) if channel_wise else None
+        r.w_iters_ring = torch.zeros(iters, c2, dtype=torch.int32, device=dev) if channel_wise else None
         main = torch.cuda.current_stream(dev)
         loss_s = self.loss_stream() if overlap else None
         side_s = self.side_stream()
@@ -718,9 +724,10 @@ class HipOps:
         inv_side2 = (self._workspace("inv_side2", self.lib.effq_spd_inverse_ws_bytes(n))
                      if n_inv > 2 and SIDE2_STREAM and SIDE_STREAM else None)
         fpw = (self._workspace("fp_bucket", self.lib.effq_fp_bucket_ws_bytes(nw))
-               if nw <= self.lib.effq_fp_bucket_max() and BUCKET_FIXED_POINT else None)
+               if nw <= self.lib.effq_fp_bucket_max() and BUCKET_FIXED_POINT and not channel_wise else None)
         # weight projection from the previous iteration's iterates (effq_fixed_point_traj)
-        traj = TRAJ_FIXED_POINT and bool(self.lib.effq_admm_uses_traj(nw, int(levels)))   # the library's own decision
+        traj = (TRAJ_FIXED_POINT and not channel_wise and
+                bool(self.lib.effq_admm_uses_traj(nw, int(levels))))   # the library's own decision
         tws = self._workspace("fp_traj", self.lib.effq_fp_traj_ws_bytes(nw)) if traj else None
         r.fp_pred = torch.zeros(self.lib.effq_fp_traj_pred_bytes(), dtype=torch.uint8, device=dev) if traj else None
         if loss_kind == 5:
@@ -759,6 +766,7 @@ class HipOps:
         a.G_ring, a.Gq_ring, a.b_ring = p(r.G_ring), p(r.Gq_ring), p(r.b_ring)
         a.state_ring, a.hist, a.err_flag = p(r.state_ring), p(r.hist), p(r.err)
         a.res_ring = p(r.res)
+        a.channel_wise, a.alpha_ring, a.w_iters_ring = int(bool(channel_wise)), p(r.alpha_ring), p(r.w_iters_ring)
         a.ainv_pool, a.n_ainv = p(r.ainv), n_inv
         a.prox_ws, a.prox_ws_bytes = p(prox), prox.numel()
         a.red_ws = p(self._red_ws)
@@ -794,6 +802,8 @@ class HipOps:
         err = run.err.to(torch.float64)
         if getattr(run, "loss_planes", None) is not None:       # effq_gram_loss_i8_prepare's flag: 1000 x (1 | 2)
             err = err + 1000.0 * run.loss_planes._effq_err.to(torch.float64)
+        if getattr(run, "channel_wise", False):
+            return HipOps._admm_read_channels(run, best, err, extra)
         parts = [run.hist[:, 0], best, run.state_ring[-1, :1], run.state_ring[:, 4], err]
         if extra is not None:
             parts.append(extra.to(torch.float64).reshape(-1))
@@ -803,6 +813,51 @@ class HipOps:
         return dict(hist=pack[:it].tolist(), best=pack[it:it + 2].tolist(), alpha_w=float(pack[it + 2]),
                     w_iters=w_iters, err=int(pack[2 * it + 3]),
                     extra=pack[2 * it + 4:].tolist() if extra is not None else None)
+
+    @staticmethod
+    def channel_alpha_best(run, best):
+        """Channel mode: the BEST iterate's per-row scales (device-side index of the scale ring, no host read)."""
+        return run.alpha_ring.index_select(0, best[1:2].to(torch.long)).reshape(-1)
+
+    @staticmethod
+    def _admm_read_channels(run, best, err, extra):
+        """admm_read of a channel-mode run: alpha_w = the best iterate's scale vector, w_iters = the per-iteration maximum
+        over the rows, w_iters_rows = the row that took it."""
+        it, c2 = run.iters, run.c2
+        wmax, wrow = run.w_iters_ring.max(dim=1)
+        parts = [run.hist[:, 0], best, HipOps.channel_alpha_best(run, best), wmax.to(torch.float64),
+                 wrow.to(torch.float64), err]
+        if extra is not None:
+            parts.append(extra.to(torch.float64).reshape(-1))
+        pack = torch.cat(parts).cpu()
+        o = it + 2
+        a_w = pack[o:o + c2].tolist()
+        o += c2
+        w_iters = [int(v) for v in pack[o:o + it].tolist()]
+        w_rows = [int(v) for v in pack[o + it:o + 2 * it].tolist()]
+        o += 2 * it
+        return dict(hist=pack[:it].tolist(), best=pack[it:it + 2].tolist(), alpha_w=a_w, w_iters=w_iters,
+                    w_iters_rows=w_rows, err=int(pack[o]), extra=pack[o + 1:].tolist() if extra is not None else None)
+
+    def fixed_point_channels(self, a, b, v, levels: int, alpha, iters=None, err_flag=None, proj=None):
+        """effq_fixed_point_channels[_proj]: one scale per output row of a ([c2, ...]).  alpha: c2 device doubles; iters:
+        c2 int32 (optional).  proj = dict(G, dual_div[, Bm, B0, W0, ldb, rho_next, eta]) runs the projection epilogue
+        (then b is the dual, updated in place)."""
+        c2 = int(a.shape[0])
+        nwrow = a.numel() // c2
+        tol, cap = ADMM_TOL, 100 * int(levels)
+        if proj is None:
+            check(self.lib.effq_fixed_point_channels(_ptr(a), _ptr(b), _ptr(v), c2, nwrow, int(levels), tol, cap,
+                                                     _ptr(alpha), _ptr(iters), _ptr(err_flag), self.stream),
+                  "effq_fixed_point_channels")
+            return
+        Bm = proj.get("Bm")
+        B0 = proj.get("B0")
+        check(self.lib.effq_fixed_point_channels_proj(
+            _ptr(a), _ptr(b), _ptr(v), c2, nwrow, int(levels), tol, cap, _ptr(alpha), _ptr(iters), _ptr(err_flag),
+            _ptr(proj["G"]), float(proj["dual_div"]), _ptr(Bm), _ptr(B0), _ptr(proj.get("W0")),
+            int(B0.shape[1]) if B0 is not None else 0, int(proj.get("ldb", 0)), float(proj.get("rho_next", 0.0)),
+            float(proj.get("eta", 0.0)), self.stream), "effq_fixed_point_channels_proj")
 
     def shift_terms(self, rho: float, eta: float, rho_inv: float) -> int:
         d = rho_inv - rho

@@ -145,7 +145,9 @@ class PTQConv(nn.Conv3d):
         self.qlvl_w, self.qlvl_act = qlvl, qlvl_act
         self.kwQ = kwQ
         self.alpha_act = nn.Parameter(torch.tensor(1.))
-        self.alpha_w = nn.Parameter(torch.tensor(1.))
+        # lwq_channel_wise (not in the reference): one weight scale per output channel, alpha_w of shape (c2, 1, 1, 1)
+        self.channel_wise = bool(kwQ.get('lwq_channel_wise', False))
+        self.alpha_w = nn.Parameter(torch.ones(out_channels, 1, 1, 1) if self.channel_wise else torch.tensor(1.))
         self.output_fp = None            # FP target, set by the forward hook
         self.name = None
         self.snap_dir = kwQ.get('snap_dir', None)
@@ -246,19 +248,44 @@ class PTQConv(nn.Conv3d):
     # ---- storage formats (PTQConv.py:125-152) -----------------------------------------------
     def store_int_weight(self):
         """Level ids as uint8 (<=256 levels) / int32, for storage only.  Uses the saved alpha_w,
-        which is the LAST iterate's scale while weight is the BEST iterate's (quirk Q6)."""
+        which is the LAST iterate's scale while weight is the BEST iterate's (quirk Q6).
+        Channel mode: alpha_w (c2, 1, 1, 1) is the best iterate's, so the ids are exact; a row with scale 0 stores
+        level (L-1)//2."""
         a = self.alpha_w.data
-        b = self.weight.data / a
         delta = 2 / (self.qlvl_w - 1)
-        w_int = torch.round((b + 1) / delta)
+        if self.channel_wise:
+            w_int = self._channel_ids(self.weight.data, a, self.qlvl_w)
+        else:
+            b = self.weight.data / a
+            w_int = torch.round((b + 1) / delta)
         w_int = w_int.to(torch.uint8) if self.qlvl_w <= 256 else w_int.to(torch.int32)
         self.weight.requires_grad = False
         self.weight.data = w_int.data.cpu()
 
     def restore_fp_weight(self):
         delta = 2 / (self.qlvl_w - 1)
+        if self.channel_wise:
+            self.weight.data = self._channel_weight(self.weight.data, self.alpha_w.data, self.qlvl_w)
+            return
         b = self.weight.data.float() * delta - 1
         self.weight.data = self.alpha_w.data * b
+
+    @staticmethod
+    def _channel_ids(w, a, levels):
+        """Level ids of weights on per-row grids alpha_c * (2 j / (L-1) - 1); rows with alpha_c = 0 -> (L-1)//2."""
+        a = a.to(w.device).reshape(-1, *([1] * (w.dim() - 1)))
+        delta = 2 / (levels - 1)
+        zero = a == 0
+        ids = torch.round((w / torch.where(zero, torch.ones_like(a), a) + 1) / delta)
+        return torch.where(zero, torch.full_like(ids, float((levels - 1) // 2)), ids)
+
+    @staticmethod
+    def _channel_weight(ids, a, levels):
+        """Inverse of _channel_ids with the calibrator's arithmetic: b = fp32(id * d - 1 in fp64), w = fp32(alpha_c) * b
+        (the same bits as the calibrated weights); rows with alpha_c = 0 -> +0."""
+        a = a.to(ids.device).reshape(-1, *([1] * (ids.dim() - 1))).float()
+        b = (ids.double() * (2 / (levels - 1)) - 1).float()
+        return torch.where(a == 0, torch.zeros_like(b), a * b)
 
     # ---- bit-packed storage (row f2; the reference keeps one uint8 per weight) ------------------
     def export_packed_weight(self):
@@ -266,6 +293,13 @@ class PTQConv(nn.Conv3d):
         Same level ids as store_int_weight(); the module is left untouched."""
         ops = get_ops(self.weight.device)
         delta = 2 / (self.qlvl_w - 1)
+        if self.channel_wise:         # alpha_w travels as a list of c2 scales, flagged channel_wise=True
+            ids = self._channel_ids(self.weight.data, self.alpha_w.data, self.qlvl_w)
+            ids = ids.to(torch.uint8).contiguous().reshape(-1)
+            bits = ops.storage_bits(self.qlvl_w)
+            return dict(data=ops.pack_levels(ids, bits).cpu(), n=int(ids.numel()), bits=bits,
+                        shape=tuple(self.weight.shape), alpha_w=self.alpha_w.data.reshape(-1).tolist(),
+                        levels=int(self.qlvl_w), channel_wise=True)
         ids = torch.round((self.weight.data / self.alpha_w.data + 1) / delta).to(torch.uint8).contiguous().reshape(-1)
         bits = ops.storage_bits(self.qlvl_w)
         return dict(data=ops.pack_levels(ids, bits).cpu(), n=int(ids.numel()), bits=bits,
@@ -275,6 +309,11 @@ class PTQConv(nn.Conv3d):
         """Inverse of export_packed_weight(): weight = alpha_w * (2*id/(L-1) - 1), like restore_fp_weight()."""
         ops = get_ops(self.weight.device)
         ids = ops.unpack_levels(blob["data"].to(self.weight.device), blob["n"], blob["bits"])
+        if blob.get("channel_wise", False):
+            a = torch.tensor(blob["alpha_w"], dtype=self.weight.dtype, device=self.weight.device)
+            self.alpha_w.data = a.reshape(-1, 1, 1, 1)
+            self.weight.data = self._channel_weight(ids.reshape(blob["shape"]), a, blob["levels"])
+            return
         delta = 2 / (blob["levels"] - 1)
         self.alpha_w.data = torch.tensor(blob["alpha_w"], dtype=self.weight.dtype, device=self.weight.device)
         self.weight.data = (self.alpha_w.data * (ids.float() * delta - 1)).reshape(blob["shape"])
@@ -300,7 +339,15 @@ class PTQConv(nn.Conv3d):
 
 
 class EfficientQConvHIP(PTQConv):
-    """Layer-wise ADMM calibrator (EfficientQConv.py:13-166) on the HIP library."""
+    """Layer-wise ADMM calibrator (EfficientQConv.py:13-166) on the HIP library.
+
+    ``lwq_channel_wise=True`` (not in the reference) fits one weight scale per output channel: the projection of every
+    ADMM iteration runs project_by_iter on each output row of w* + dual (effq_fixed_point_channels_proj); prox solve,
+    dual update and the loss from the fp32 conv (or the fp64 Gram system) are unchanged.  The integer conv losses and
+    the i8 forward, which fold one scalar scale into their arithmetic, are not used.  ``alpha_w`` is then a
+    (c2, 1, 1, 1) parameter holding the BEST iterate's scales - unlike the per-tensor quirk Q6, which keeps the last
+    iterate's scale - so the saved weights lie exactly on their rows' grids.  A row whose values are all zero gets
+    scale 0 and weights 0."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, q_weight=True, qlvl=8, q_act=True, qlvl_act=8, **kwQ):
@@ -380,6 +427,11 @@ class EfficientQConvHIP(PTQConv):
         # ... and of the Gram system (exact integer sums, weights applied per attention class)
         use_gi8 = bool(self.q_act and not self._act_inited and self.lwq_exact_int and
                        getattr(ops, "gram_i8_supported", lambda *a: False)(geom, self.qlvl_act))
+        # channel mode: the integer conv losses and the i8 forward fold ONE weight scale into their arithmetic - off; the
+        # integer Gram accumulation and the fp64 Gram loss (kind 4) take G as fp32 values and stay
+        chan = self.channel_wise
+        if chan:
+            use_i8 = use_i8s = int_conv = False
         att_cls = ops.att_classes(att) if use_gi8 else None
         use_gi8 = att_cls is not None
         if self.q_act:                                                     # (:64-72)
@@ -407,7 +459,7 @@ class EfficientQConvHIP(PTQConv):
                       yn.numel() // c2 >= 8 * n_sys)
         # ... and on the wide layers (n above GRAM_LOSS_MAX_N: the fp64 evaluation would cost more than the conv pass) with
         # the quadratic form on the i8 matrix cores: both of its factors are small integers there (effq_gram_loss_i8)
-        use_gl8 = bool(use_gi8 and GRAM_LOSS_DEFAULT and GRAM_LOSS_I8 and not use_gl and
+        use_gl8 = bool(use_gi8 and GRAM_LOSS_DEFAULT and GRAM_LOSS_I8 and not use_gl and not chan and
                        GRAM_LOSS_MAX_N < n_sys <= GRAM_LOSS_I8_MAX_N and
                        getattr(ops, "gram_loss_i8_supported", lambda *a: False)(c2, n_sys, has_b, self.qlvl_w))
         if use_gi8 and (use_gl or use_gl8):
@@ -444,6 +496,8 @@ class EfficientQConvHIP(PTQConv):
         t_loop0 = _time.perf_counter()
         loss_kind = 1 if use_i8 else (2 if use_i8s else 0)
         kw = dict(loss_gram=loss_gram) if loss_gram is not None else {}
+        if chan:
+            kw['channel_wise'] = True     # effq_fixed_point_channels_proj: one scale per output row
         if self.lwq_verbose:
             kw['residuals'] = True        # the per-iteration residual norms of the reference's progress line (:114-127)
         run = ops.admm_run(A0, B0, W0, b0, geom, yn, xq=xq, xidx=xidx, act_alpha=self.alpha_act.data,
@@ -461,7 +515,7 @@ class EfficientQConvHIP(PTQConv):
         # ... on the i8 matrix cores where the level ids of the input are at hand and the shape has a kernel (32 -> 32 and
         # 64 -> 64 channels at 3^3: the layers with the most voxels): an exact integer contraction + one multiply-add per
         # output, HBM-bound, instead of the f32 conv (2.6 -> 0.3 ms at 16 x 64^3 voxels)
-        fwd_i8 = bool(FORWARD_I8 and fuse and xidx is not None and self.lwq_exact_int and
+        fwd_i8 = bool(FORWARD_I8 and fuse and xidx is not None and self.lwq_exact_int and not chan and
                       getattr(ops, "conv_i8_out_supported", lambda *a: False)(geom, self.qlvl_act, self.qlvl_w))
         if fwd_i8:
             st_best = run.state_ring.index_select(0, best[1:2].to(torch.long)).reshape(-1)    # the best iterate's scale
@@ -493,7 +547,12 @@ class EfficientQConvHIP(PTQConv):
                                f'expects (flag {info["err"] // 1000})')
         if info["err"] != 0:                                               # layer_helper.py:62-64
             if info["err"] == 2:
-                raise RuntimeWarning(f'Exceed maximum iteration ({100 * self.qlvl_w}) for alpha optimization')
+                where = ''
+                if chan:
+                    i_cap = next((i for i, w in enumerate(w_iters) if w >= 100 * self.qlvl_w), None)
+                    if i_cap is not None:
+                        where = f' (output channel {info["w_iters_rows"][i_cap]}, ADMM iteration {i_cap})'
+                raise RuntimeWarning(f'Exceed maximum iteration ({100 * self.qlvl_w}) for alpha optimization{where}')
             # state 3 = the grid barrier of the cooperative fixed point timed out (its workgroups were not co-resident):
             # its barrier words in the reduction workspace are left non-zero - clear them before reporting
             if hasattr(ops, "_red_ws"):
@@ -505,7 +564,12 @@ class EfficientQConvHIP(PTQConv):
         self.weight.data = best_G.reshape(self.weight.shape)               # (:147-158)
         if has_b:
             self.bias.data = best_b
-        self.alpha_w.data = torch.tensor(a_w, dtype=x.dtype, device=dev)   # LAST iterate's scale (quirk Q6)
+        if chan:
+            # the BEST iterate's scales (not the last iterate's as in the per-tensor quirk Q6): the saved weights then lie
+            # exactly on alpha_w's grids, and store_int_weight is exact
+            self.alpha_w.data = torch.tensor(a_w, dtype=x.dtype, device=dev).reshape(c2, 1, 1, 1)
+        else:
+            self.alpha_w.data = torch.tensor(a_w, dtype=x.dtype, device=dev)   # LAST iterate's scale (quirk Q6)
         fin_h = info["extra"]
         numel = y_dim * 1.0
         lossf = (fin_h[1] if att is not None else fin_h[0]) / numel
@@ -515,7 +579,8 @@ class EfficientQConvHIP(PTQConv):
                                final_mse=fin_h[0] / numel, layer_loss=lossf, act_iters=act_iters,
                                w_iters=w_iters, alpha_w=a_w, loss_history=[h / numel for h in hist],
                                exact_int=int_conv or loss_gram is not None, exact_gram=use_gi8,
-                               gram_loss=loss_gram is not None, host_enqueue_s=t_enq, admm_loop_s=t_loop)
+                               gram_loss=loss_gram is not None, host_enqueue_s=t_enq, admm_loop_s=t_loop,
+                               channel_wise=chan)
 
     def compute_quant_error(self, output_fp, Qw, Qact):
         """EfficientQConv.py:168-172."""

@@ -210,6 +210,22 @@ int effq_fp_bracket_import(const void* ws_src, size_t n_src, const long long* pa
 /* after state.done = 4: clears it and makes the rank's OWN workspace start its next pass from the base (its list and
  * tallies belong to a bracket the iterates have moved on from while the imported fit ran) */
 int effq_fp_bracket_rebase(effq_fp_state* state_dev, void* ws, size_t n, void* stream);
+/* Per-output-channel scales (fixed_point_channels.hip): project_by_iter on every row of v = a + b ([c2][nwrow], b may be
+ * NULL; v is written to v_out when given, required if b != NULL) on its own, weight grid lo = -1, hi = 1: a0 = mean|v_c|,
+ * then the fixed point until |d alpha| <= tol or max_iter.  alpha_out[c2] (fp64), iters_out[c2] (may be NULL),
+ * *err_flag_dev = 2 (sticky; may be NULL) when a row hit max_iter.  A row with sum|v_c| = 0 gets alpha 0, 0 iterations,
+ * converged.  One workgroup per row, no grid barrier; deterministic.  nwrow <= effq_fp_channels_max_row().
+ * _proj: with a = wstar, b = dual, the ADMM projection + dual update of every row in the same launch: G = alpha_c b
+ * (0 on a zero row), dual <- (wstar - G + dual) / dual_div, and, with Bm != NULL, the next prox right-hand side
+ * Bm[r][k] = (B0[r][k] + eta W0) + rho_next (G - dual) (rows of B0 n long, of Bm ldb long), as effq_project_dual_next. */
+int effq_fp_channels_max_row(void);
+int effq_fixed_point_channels(const float* a, const float* b, float* v_out, int c2, int nwrow, int levels, double tol,
+                              int max_iter, double* alpha_out, int32_t* iters_out, int32_t* err_flag_dev, void* stream);
+int effq_fixed_point_channels_proj(const float* wstar, float* dual, float* v_out, int c2, int nwrow, int levels,
+                                   double tol, int max_iter, double* alpha_out, int32_t* iters_out, int32_t* err_flag_dev,
+                                   float* G, float dual_div, float* Bm, const float* B0, const float* W0, int n, int ldb,
+                                   double rho_next, double eta, void* stream);
+
 /* Sticky device-side check used by stream-resident loops: *err_flag_dev = 2 (cap hit; the reference
  * raises, layer_helper.py:62-64) or 3 (not finished) unless state.done == 1. */
 int effq_fp_check(const effq_fp_state* state_dev, int32_t* err_flag_dev, void* stream);
@@ -460,6 +476,12 @@ typedef struct effq_admm_run_args {
    * iteration (the primal residual is the root of the first, the dual residual rho times the root of the second); NULL: not
    * computed (one small launch per iteration) */
   double* res_ring;
+  /* channel mode (lwq_channel_wise: one weight scale per output channel): channel_wise != 0 runs the weight projection
+   * through effq_fixed_point_channels_proj instead of the per-tensor fixed points; alpha_ring [iters][c2] device doubles
+   * receive every iteration's scales, w_iters_ring [iters][c2] int32 the per-row fixed-point iteration counts.
+   * state_ring is then not written.  Only loss_kind 0 and 4 (they take G as fp32 values); 1, 2, 5 -> EFFQ_ERR_ARG. */
+  int32_t channel_wise;
+  double* alpha_ring; int32_t* w_iters_ring;
 } effq_admm_run_args;
 /* 1 if effq_admm_run takes the trajectory weight projection (effq_fixed_point_traj) for a layer of nw weights at
  * w_levels levels - the caller then passes fp_pred (effq_fp_traj_pred_bytes(), zero-filled) and fp_traj_ws
