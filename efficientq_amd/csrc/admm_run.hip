@@ -19,9 +19,6 @@ extern "C" {
 int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
                                  double tol, int max_iter, effq_fp_state* state_dev, const effq::ProjFused* pf_in,
                                  void* stream);   // quant_reduce.hip (internal)
-int effq_fixed_point_bucket_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
-                                  double tol, int max_iter, effq_fp_state* state_dev, void* ws, size_t ws_bytes,
-                                  void* pred_dev, const effq::ProjFused* pf_in, int* fused_out, void* stream);   // fixed_point_bucket.hip (internal)
 int effq_project_dual_next(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
                            float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev, float* Bm,
                            const float* B0, const float* W0, int nwrow, int nb0, int ldb, double rho_next, double eta,
@@ -218,10 +215,9 @@ extern "C" {
 // whether effq_admm_run would use effq_fixed_point_traj for a layer of nw weights at w_levels levels (the caller then
 // provides fp_pred / fp_traj_ws; otherwise both may be NULL)
 int effq_admm_uses_traj(size_t nw, int w_levels) {
-  static const bool traj_on = !(getenv("EFFQ_FP_TRAJ") && atoi(getenv("EFFQ_FP_TRAJ")) == 0);
-  static const int traj_levels = getenv("EFFQ_FP_TRAJ_LEVELS") ? atoi(getenv("EFFQ_FP_TRAJ_LEVELS")) : 4;
-  static const size_t traj_min = getenv("EFFQ_FP_TRAJ_MIN") ? (size_t)atoll(getenv("EFFQ_FP_TRAJ_MIN")) : 65536;
-  return (traj_on && w_levels <= traj_levels && nw >= traj_min && nw <= effq_fp_traj_max()) ? 1 : 0;
+  constexpr int traj_levels = 4;          // see the measurements in effq_admm_run
+  constexpr size_t traj_min = 65536;
+  return (w_levels <= traj_levels && nw >= traj_min && nw <= effq_fp_traj_max()) ? 1 : 0;
 }
 
 int effq_admm_num_inverses(double rho, double rho_max, int iters, int period) {
@@ -265,8 +261,7 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // all-values kernel / bucketed: 2048 values 16 / 22; 8192 36 / 28; 27648 84 / 37; 110592 125 / 51; 442368 143 / 65;
   // 1.77 M 171 / 163 alone but slower inside the loop (1261 vs 1224 ms per calibration); at 256 levels the all-values
   // kernels win at every size)
-  static const size_t bucket_max = getenv("EFFQ_FP_BUCKET_MAX") ? (size_t)atoll(getenv("EFFQ_FP_BUCKET_MAX"))
-                                                                : ((size_t)1 << 19);          // tuning aid
+  constexpr size_t bucket_max = (size_t)1 << 19;
   const bool bucket = !chan && a->fp_ws != nullptr && a->w_levels <= 16 && nw > 4096 && nw <= bucket_max;
   if (bucket && a->fp_ws_bytes < effq_fp_bucket_ws_bytes(nw)) {
     set_error("admm_run: fixed-point workspace %zu < %zu", a->fp_ws_bytes, effq_fp_bucket_ws_bytes(nw));
@@ -278,13 +273,10 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // (ms per calibration, all on one box: older kernels only 715; trajectory kernel from the third iteration of a layer on
   // 743; from 5 / 10 / 15 iterations after a change of rho, layers of 65 536 ... 2^20 weights only: 702 / 703 / 699; and
   // for larger layers from 30 iterations after: 698).  The iterations in between run the kernels above, which leave
-  // their iterates behind.  EFFQ_FP_TRAJ=0, EFFQ_FP_TRAJ_AFTER[_BIG], EFFQ_FP_TRAJ_MIN, EFFQ_FP_TRAJ_LEVELS: A/B switches
-  static const bool traj_rho_old = !(getenv("EFFQ_FP_TRAJ_RHO") && atoi(getenv("EFFQ_FP_TRAJ_RHO")) == 0);
-  // (at 16 levels the fixed point takes ~50 iterations: the one hull slot for everything past the seventh keeps a third
-  // of the values on the list, and the older kernels are faster - measured, scripts/prof_fp_traj.py)
-  static const int traj_after_env = getenv("EFFQ_FP_TRAJ_AFTER") ? atoi(getenv("EFFQ_FP_TRAJ_AFTER")) : 12;
-  static const int traj_after_big = getenv("EFFQ_FP_TRAJ_AFTER_BIG") ? atoi(getenv("EFFQ_FP_TRAJ_AFTER_BIG")) : 30;
-  const int traj_after = (nw > ((size_t)1 << 20)) ? traj_after_big : traj_after_env;
+  // their iterates behind.  (At 16 levels the fixed point takes ~50 iterations: the one hull slot for everything past the
+  // seventh keeps a third of the values on the list, and the older kernels are faster - measured, scripts/prof_fp_traj.py;
+  // hence at most 4 levels, effq_admm_uses_traj.)
+  const int traj_after = (nw > ((size_t)1 << 20)) ? 30 : 12;
   const bool traj = !chan && a->fp_pred != nullptr && a->fp_traj_ws != nullptr && effq_admm_uses_traj(nw, a->w_levels) != 0;
   if (traj && a->fp_traj_ws_bytes < effq_fp_traj_ws_bytes(nw)) {
     set_error("admm_run: trajectory fixed-point workspace %zu < %zu", a->fp_traj_ws_bytes, effq_fp_traj_ws_bytes(nw));
@@ -356,16 +348,8 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // the inverse the first iterations need, on the main stream; the later ones on the side stream, which starts at once,
   // beside the first inverse (all of them only read A0): with n = 13825 an inverse takes longer than the 50 iterations it has
   // to be ready after, and the chain waited for each of the three later ones in turn (LiTS: 3.08 -> 3.03 s per calibration;
-  // BraTS 900 -> 893 ms).  EFFQ_SIDE_EARLY_N = smallest n that does so (tuning aid).
-  static const int early_n = getenv("EFFQ_SIDE_EARLY_N") ? atoi(getenv("EFFQ_SIDE_EARLY_N")) : 0;
-  // ... unless the later inverses are quick enough to be ready in time when they start AFTER the first one (n below
-  // EFFQ_SIDE_SERIAL_BELOW): beside two other sweeps the first inverse - which the whole chain waits for - took 2 x as
-  // long as alone (n = 3457: 7.3 against 3.6 ms, 1729: 3.1 against 1.5), and the later ones then run one after the other
-  // on ONE side stream, the one that is needed next always first.
-  static const int serial_below = getenv("EFFQ_SIDE_SERIAL_BELOW") ? atoi(getenv("EFFQ_SIDE_SERIAL_BELOW")) : 0;
-  const bool side_serial = fork_side && n_inv > 1 && n < serial_below;
-  const bool side_early = fork_side && n_inv > 1 && n >= early_n;
-  if (side_early && !side_serial) {
+  // BraTS 900 -> 893 ms).
+  if (fork_side && n_inv > 1) {
     ADMM_HIP(new_event(&ev_fork));
     ADMM_HIP(hipEventRecord(ev_fork, s_main));         // A0 (and everything before the call) is ready
     ADMM_HIP(hipStreamWaitEvent(s_side, ev_fork, 0));
@@ -376,11 +360,6 @@ int effq_admm_run(const effq_admm_run_args* a) {
     ADMM_RC(effq_spd_inverse(a->A0, n, has_b, plan.rho[first], a->eta, a->ainv_pool, a->inv_ws, a->inv_ws_bytes, s_main));
     ps.close();
   }
-  if (side_serial) {
-    ADMM_HIP(new_event(&ev_fork));
-    ADMM_HIP(hipEventRecord(ev_fork, s_main));         // the first inverse has finished
-    ADMM_HIP(hipStreamWaitEvent(s_side, ev_fork, 0));
-  }
   // The later inverses (side stream) are ENQUEUED a few iterations into the loop, not here: their ~30 - 650 launches take
   // the host 0.2 - 2.6 ms, during which the main stream - done with its own inverse on the small layers - had nothing queued
   // (under a profiler, at 3 x the launch cost, 6 ms per layer).  The side stream still starts from the fork event recorded
@@ -388,19 +367,9 @@ int effq_admm_run(const effq_admm_run_args* a) {
   bool side_enqueued = (n_inv <= 1);
   auto enqueue_side_inverses = [&]() -> int {
     side_enqueued = true;
-    if (fork_side && !side_early && !side_serial) {
-      hipError_t e1 = new_event(&ev_fork);
-      if (e1 == hipSuccess) e1 = hipEventRecord(ev_fork, s_main);       // A0 (and everything before the call) is ready
-      if (e1 == hipSuccess) e1 = hipStreamWaitEvent(s_side, ev_fork, 0);
-      if (e1 == hipSuccess && two_sides) e1 = hipStreamWaitEvent(s_side2, ev_fork, 0);
-      if (e1 != hipSuccess) {
-        effq::set_error("admm_run: side-stream fork -> %s", hipGetErrorString(e1));
-        return EFFQ_ERR_HIP;
-      }
-    }
     for (int r = first + 1; r < plan.count; ++r) {
       float* dst = a->ainv_pool + (size_t)(r - first) * ainv_elems;
-      const bool on2 = two_sides && !side_serial && ((r - first) % 2 == 0);   // first later inverse on side 1, the next on side 2 ...
+      const bool on2 = two_sides && ((r - first) % 2 == 0);   // first later inverse on side 1, the next on side 2 ...
       hipStream_t sr = on2 ? s_side2 : s_side;
       void* ws = !fork_side ? a->inv_ws : (on2 ? a->inv_ws_side2 : a->inv_ws_side);
       const size_t wsb = !fork_side ? a->inv_ws_bytes : (on2 ? a->inv_ws_side2_bytes : a->inv_ws_side_bytes);
@@ -427,18 +396,17 @@ int effq_admm_run(const effq_admm_run_args* a) {
 
   double rho = a->rho;
   int cur = -1;     // index into plan.rho of the inverse in use
-  static const bool fuse_off = getenv("EFFQ_FUSE_BUILD") != nullptr && atoi(getenv("EFFQ_FUSE_BUILD")) == 0;   // A/B switch
-  const bool fuse_build = !fuse_off;
   int bm_ld = 0;
   float* bm = effq_prox_bm(a->prox_ws, c2, n, &bm_ld);
   bool bm_ready = false;
   const float* Ainv = nullptr;
   // group size: the last group is evaluated after the chain has finished (it delays the join by one group of losses), so
-  // the cheap losses from the Gram system travel in larger groups than the conv passes.  EFFQ_LOSS_GROUP[_CONV]: A/B switches
+  // the cheap losses from the Gram system travel in larger groups than the conv passes.  EFFQ_LOSS_GROUP overrides the
+  // Gram group (bench.py's model reads it too)
   static const int group_gram = getenv("EFFQ_LOSS_GROUP") ? atoi(getenv("EFFQ_LOSS_GROUP")) : 8;
-  static const int group_conv = getenv("EFFQ_LOSS_GROUP_CONV") ? atoi(getenv("EFFQ_LOSS_GROUP_CONV")) : 4;
-  const int group_env = (a->loss_kind == 4 || a->loss_kind == 5) ? group_gram : group_conv;
-  const int loss_group = (fork_loss && group_env > 1) ? group_env : 1;
+  constexpr int group_conv = 4;
+  const int group_size = (a->loss_kind == 4 || a->loss_kind == 5) ? group_gram : group_conv;
+  const int loss_group = (fork_loss && group_size > 1) ? group_size : 1;
   int loss_next = 0;
   bool rho_changed_last = false;
   int rho_changed_at = 0;          // first iteration that ran with the current rho
@@ -470,15 +438,14 @@ int effq_admm_run(const effq_admm_run_args* a) {
     // (iterations since rho last changed: the drift from call to call - and with it the length of the lists the
     // trajectory kernel's single last workgroup has to scan - is largest right after a change)
     const int since_rho = i - rho_changed_at;
-    const bool use_traj = traj && i > 1 && !(traj_rho_old && after_rho) && since_rho >= traj_after;
+    const bool use_traj = traj && i > 1 && !after_rho && since_rho >= traj_after;
     // ... and then the trajectory kernel adds the K slices of the product up in its prologue: one launch less
-    static const bool fuse_reduce = !(getenv("EFFQ_FUSE_REDUCE") && atoi(getenv("EFFQ_FUSE_REDUCE")) == 0);   // A/B switch
     const float* parts = nullptr;
     int parts_n = 1, parts_ld = 0;
     // ---- the chain (main stream) ----
     const bool prof = g_prof_every > 0 && !use_shift && (i % g_prof_every) == g_prof_every / 2;
     ProfScope p_prox(prof, PROF_PROX, i, a, s_main);
-    if (!use_shift && bm_ready && use_traj && fuse_reduce && c2 <= 512)
+    if (!use_shift && bm_ready && use_traj && c2 <= 512)
       ADMM_RC(effq_prox_solve_prebuilt_parts(a->B0, Ainv, a->W0, a->b0, G_prev, a->dual, c2, n, has_b, rho, a->eta, a->wstar,
                                              bstar, a->prox_ws, a->prox_ws_bytes, s_main, &parts, &parts_n, &parts_ld));
     else if (use_shift)
@@ -498,7 +465,7 @@ int effq_admm_run(const effq_admm_run_args* a) {
     // workspace; the first solve of the layer builds Bm itself (bias column, padding).
     double rho_next = rho;
     if (i % a->rho_period == 0) rho_next = (rho * 2 <= a->rho_max) ? rho * 2 : a->rho_max;
-    const bool next_rhs = fuse_build && i + 1 < a->iters;
+    const bool next_rhs = i + 1 < a->iters;
     ProjFused pf;
     memset(&pf, 0, sizeof(pf));
     bool fuse_proj = false;
@@ -512,10 +479,7 @@ int effq_admm_run(const effq_admm_run_args* a) {
       // measured (us per iteration, fused against fixed point + projection): 2048 weights 13.8 against 12.2 + 7.1, 3456 at
       // 256 levels 231.8 against 229.3 + 8.3 - but 27648 weights on the bucketed kernel 56.3 against 33.6 + 7.1: only the
       // 256 threads of its iteration phase are left for the epilogue.  So: the all-values kernel's layers only
-      // (EFFQ_FUSE_PROJ=2 also fuses the bucketed single-workgroup kernel: A/B switch)
-      static const int fuse_proj_mode = getenv("EFFQ_FUSE_PROJ") ? atoi(getenv("EFFQ_FUSE_PROJ")) : 1;
-      const bool one_wg = (bucket && nw <= 32768 && fuse_proj_mode >= 2) || (!bucket && nw <= effq_fp_small_max());
-      if (vec_ok && one_wg && fuse_proj_mode != 0) {
+      if (vec_ok && !bucket && nw <= effq_fp_small_max()) {
         fuse_proj = true;
         pf.wstar = a->wstar; pf.G = G; pf.dual = a->dual; pf.Gq = Gq; pf.err_flag = a->err_flag;
         pf.d = 2.0 / (double)(a->w_levels - 1); pf.dual_div = dual_div; pf.lm1 = a->w_levels - 1;
@@ -545,11 +509,8 @@ int effq_admm_run(const effq_admm_run_args* a) {
       ADMM_RC(effq_fixed_point_traj(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels, st,
                                     a->fp_pred, a->fp_traj_ws, a->fp_traj_ws_bytes, s_main));
     } else if (bucket) {
-      int fused = 0;
-      ADMM_RC(effq_fixed_point_bucket_fused(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol,
-                                            100 * a->w_levels, st, a->fp_ws, a->fp_ws_bytes, rec,
-                                            fuse_proj ? &pf : nullptr, &fused, s_main));
-      fuse_proj = fused != 0;
+      ADMM_RC(effq_fixed_point_bucket_rec(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels,
+                                          st, a->fp_ws, a->fp_ws_bytes, rec, s_main));
     } else if (nw <= effq_fp_small_max()) {
       ADMM_RC(effq_fixed_point_small_fused(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol,
                                            100 * a->w_levels, st, fuse_proj ? &pf : nullptr, s_main));

@@ -472,36 +472,30 @@ int conv_direct_launch(int kind, DirectParams& p, size_t max_blocks, hipStream_t
     return EFFQ_OK;
   }
   if (kind == 1 && p.SD == p.SH && p.SH == p.SW && (p.SD == 1 || p.SD == 2)) {
-    static const int use_lds = getenv("EFFQ_C4_LDS") ? atoi(getenv("EFFQ_C4_LDS")) : 1;      // tuning aid
-    if (use_lds) {
-      const int td = (p.OD + C4_TD - 1) / C4_TD, th = (p.OH + C4_TH - 1) / C4_TH, tw = (p.OW + C4_TW - 1) / C4_TW;
-      const long long nt = (long long)p.N * td * th * tw;
-      if (nt < (1ll << 30)) {
-        static const size_t cap = getenv("EFFQ_C4_GRID") ? (size_t)atoi(getenv("EFFQ_C4_GRID")) : 512;   // 2 workgroups per CU
-        size_t grid = (size_t)nt < cap ? (size_t)nt : cap;
-        if (grid > max_blocks) grid = max_blocks;
-        if (p.SD == 2)
-          hipLaunchKernelGGL(k_conv3d_c4h<2>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-        else
-          hipLaunchKernelGGL(k_conv3d_c4h<1>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-        return EFFQ_OK;
-      }
+    const int td = (p.OD + C4_TD - 1) / C4_TD, th = (p.OH + C4_TH - 1) / C4_TH, tw = (p.OW + C4_TW - 1) / C4_TW;
+    const long long nt = (long long)p.N * td * th * tw;
+    if (nt < (1ll << 30)) {
+      size_t grid = (size_t)nt < 512 ? (size_t)nt : 512;   // 2 workgroups per CU
+      if (grid > max_blocks) grid = max_blocks;
+      if (p.SD == 2)
+        hipLaunchKernelGGL(k_conv3d_c4h<2>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
+      else
+        hipLaunchKernelGGL(k_conv3d_c4h<1>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
+      return EFFQ_OK;
     }
   }
   if (kind == 1) {
     size_t grid = ((size_t)p.ntiles + 3) / 4;
-    static const size_t cap = getenv("EFFQ_C4_GRID") ? (size_t)atoi(getenv("EFFQ_C4_GRID")) : 512;   // tuning aid
     // 2 workgroups per CU (3 are 5 % faster alone): the 164-VGPR waves then leave room for the scale fixed point
     // of the next ADMM iteration to run beside this kernel instead of queueing behind it (first-conv layer 135 -> 122 ms)
-    if (grid > cap) grid = cap;
+    if (grid > 512) grid = 512;
     if (grid > max_blocks) grid = max_blocks;
     hipLaunchKernelGGL(k_conv3d_c4, dim3((unsigned)grid), dim3(256), 0, st, p);
     return EFFQ_OK;
   }
-  static const size_t cap1 = getenv("EFFQ_C1_GRID") ? (size_t)atoi(getenv("EFFQ_C1_GRID")) : 1024;   // tuning aid
   const size_t nbody4 = (size_t)((p.V + 63) / 64);
   size_t grid = (nbody4 + 3) / 4;
-  if (grid > cap1) grid = cap1;
+  if (grid > 1024) grid = 1024;
   if (grid > max_blocks) grid = max_blocks;
   if (grid < 1) grid = 1;
   switch (p.C1) {

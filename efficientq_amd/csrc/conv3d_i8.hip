@@ -1092,10 +1092,6 @@ struct I8Plan {
   size_t nblk, wq_bytes;
 };
 
-static bool i8_stream64() {
-  static const int on = getenv("EFFQ_I8G64") ? atoi(getenv("EFFQ_I8G64")) : 0;
-  return on != 0;
-}
 static bool i8_two_plane(const effq_geom* g) { return g->C1 == 32; }
 
 static int i8_plan(const effq_geom* g, I8Plan* pl) {
@@ -1118,27 +1114,19 @@ static int i8_plan(const effq_geom* g, I8Plan* pl) {
   EFFQ_CHECK_ARG(nt < (1ll << 30));
   p.ntiles = (int)nt;
   const int ny = (g->C1 == 512) ? p.C2 / 64 : p.C2 / 32;
-  static const int wpc128 = getenv("EFFQ_I8_WPC128") ? atoi(getenv("EFFQ_I8_WPC128")) : 2;   // tuning aid
-  static const int wpc64 = getenv("EFFQ_I8_WPC64") ? atoi(getenv("EFFQ_I8_WPC64")) : 2;      // tuning aid
-  const int wg_per_cu = (g->C1 == 32) ? 2 : (g->C1 == 128) ? wpc128
-                        : (g->C1 == 64 && i8_stream64()) ? wpc64 : 1;
+  const int wg_per_cu = (g->C1 == 32 || g->C1 == 128) ? 2 : 1;
   int gx = (256 * wg_per_cu + ny - 1) / ny;
   if (gx < 32) gx = 32;
   // The persistent grid leaves a few workgroup slots empty: the chain kernels of the NEXT iterate (prox GEMM, scale fixed
   // point, projection) run beside this kernel and otherwise find no room until the persistent workgroups retire - chain
   // and loss then serialise (32-channel layers: 0.104 ms per prox solve in situ against 0.046 with 15 slots free (grid 497; 482 workgroups measured worse again),
-  // 1222 -> 1190 ms per calibration).  The grid is trimmed to equal runs of tiles.  EFFQ_I8_RESERVE overrides (tuning aid).
-  static const int reserve = getenv("EFFQ_I8_RESERVE") ? atoi(getenv("EFFQ_I8_RESERVE")) : 15;
-  static const int reserve_wide = getenv("EFFQ_I8_RESERVE_WIDE") ? atoi(getenv("EFFQ_I8_RESERVE_WIDE")) : -1;   // tuning aid
-  const int rsv = (g->C1 >= 128 && reserve_wide >= 0) ? reserve_wide : reserve;
-  if (rsv > 0 && gx * ny > 2 * rsv) {
+  // 1222 -> 1190 ms per calibration).  The grid is trimmed to equal runs of tiles.
+  constexpr int rsv = 15;
+  if (gx * ny > 2 * rsv) {
     int g0 = gx - (rsv + ny - 1) / ny;
     const int per = (p.ntiles + g0 - 1) / g0;
     gx = (p.ntiles + per - 1) / per;
   }
-  // EFFQ_I8_TPW = tiles per workgroup: > 0 launches ntiles / TPW short-lived workgroups instead of a persistent grid
-  static const int tpw = getenv("EFFQ_I8_TPW") ? atoi(getenv("EFFQ_I8_TPW")) : 0;          // tuning aid
-  if (tpw > 0) gx = (p.ntiles + tpw - 1) / tpw;
   if (gx > p.ntiles) gx = p.ntiles;
   pl->grid = dim3((unsigned)gx, (unsigned)ny, 1);
   pl->nblk = (size_t)gx * ny;
@@ -1170,15 +1158,18 @@ size_t effq_conv_i8_ws_bytes(const effq_geom* g) {
   return 256 + pl.nblk * 2 * sizeof(double) + pl.wq_bytes + 256;
 }
 
+// 32 -> 32 layers whose output tiles evenly: k_conv3d_i8l2e
+static bool i8_l2e(const ConvI8Params& p) {
+  return p.C1 == 32 && p.C2 == 32 && p.OD % L2_TD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0;
+}
+// 64 -> 64 layers whose output tiles evenly: k_conv3d_i8w
+static bool i8_w64(const ConvI8Params& p) {
+  return p.C1 == 64 && p.C2 == 64 && p.OD % ITD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0;
+}
+
 // which of the kernels that can also store their output serves the shape: 1 = k_conv3d_i8l2e (32 -> 32), 2 = k_conv3d_i8w
 // (64 -> 64), 0 = none
-static int i8_out_kernel(const ConvI8Params& p) {
-  static const bool fast_off = getenv("EFFQ_I8L2E") != nullptr && atoi(getenv("EFFQ_I8L2E")) == 0;
-  static const bool w64_off = getenv("EFFQ_I8W") != nullptr && atoi(getenv("EFFQ_I8W")) == 0;
-  if (p.C1 == 32 && p.C2 == 32 && !fast_off && p.OD % L2_TD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0) return 1;
-  if (p.C1 == 64 && p.C2 == 64 && !w64_off && !i8_stream64() && p.OD % ITD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0) return 2;
-  return 0;
-}
+static int i8_out_kernel(const ConvI8Params& p) { return i8_l2e(p) ? 1 : i8_w64(p) ? 2 : 0; }
 
 int effq_conv_i8_out_supported(const effq_geom* g, int act_levels, int w_levels) {
   if (g == nullptr || !effq_conv_i8_supported(g, act_levels, w_levels)) return 0;
@@ -1226,8 +1217,7 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
   hipStream_t st = as_stream(stream);
   // (the ticket of the last-block reduction is left at zero by the kernel that used it: the caller zero-fills
   //  the workspace once, effq_hip.h)
-  static const bool w64_off = getenv("EFFQ_I8W") != nullptr && atoi(getenv("EFFQ_I8W")) == 0;      // A/B switch
-  if (p.C1 == 64 && p.C2 == 64 && !w64_off && !i8_stream64() && p.OD % ITD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0) {
+  if (i8_w64(p)) {
     size_t nb = (pl.wq_bytes + 255) / 256;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_pack_weight_i8g<4>, dim3((unsigned)((p.c2p + 3) / 4)), dim3(256), (size_t)4 * p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
@@ -1253,28 +1243,21 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
   {
     size_t nb = (pl.wq_bytes + 255) / 256;
     if (nb > 2048) nb = 2048;
-    if (p.C1 < 64 || (p.C1 == 64 && !i8_stream64()))
+    if (p.C1 <= 64)
       hipLaunchKernelGGL(k_pack_weight_i8, dim3((unsigned)nb), dim3(256), 0, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
-    else {
-      // the pack sits on the loss stream beside the ADMM chain: one output channel per workgroup (128 - 512 workgroups
-      // instead of 32 - 128) shortens it.  EFFQ_I8_PACK_RPW=4: the 4-channel form (A/B switch)
-      static const int rpw = getenv("EFFQ_I8_PACK_RPW") ? atoi(getenv("EFFQ_I8_PACK_RPW")) : 1;
-      if (rpw == 4)
-        hipLaunchKernelGGL(k_pack_weight_i8g<4>, dim3((unsigned)((p.c2p + 3) / 4)), dim3(256), (size_t)4 * p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
-      else
-        hipLaunchKernelGGL(k_pack_weight_i8g<1>, dim3((unsigned)p.c2p), dim3(256), (size_t)p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
-    }
+    else   // the pack sits on the loss stream beside the ADMM chain: one output channel per workgroup (128 - 512
+           // workgroups instead of 32 - 128 with four channels each) shortens it
+      hipLaunchKernelGGL(k_pack_weight_i8g<1>, dim3((unsigned)p.c2p), dim3(256), (size_t)p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
     EFFQ_LAUNCH_CHECK();
   }
   if (p.C1 == 32) {
-    static const bool fast_off = getenv("EFFQ_I8L2E") != nullptr && atoi(getenv("EFFQ_I8L2E")) == 0;   // A/B switch
     if (out != nullptr)
       hipLaunchKernelGGL(k_conv3d_i8l2e<true>, pl.grid, dim3(256), 0, st, p);
-    else if (!fast_off && p.C2 == 32 && p.OD % L2_TD == 0 && p.OH % ITH == 0 && p.OW % ITW == 0)
+    else if (i8_l2e(p))
       hipLaunchKernelGGL(k_conv3d_i8l2e<false>, pl.grid, dim3(256), 0, st, p);
     else
       hipLaunchKernelGGL(k_conv3d_i8l2, pl.grid, dim3(256), 0, st, p);
-  } else if (p.C1 == 64 && !i8_stream64()) {
+  } else if (p.C1 == 64) {
     hipLaunchKernelGGL(k_conv3d_i8<2>, pl.grid, dim3(256), 0, st, p);
   } else {
     const int cg = p.C1 / 32;
@@ -1286,10 +1269,6 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
       EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g2<16>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
       hipLaunchKernelGGL(k_conv3d_i8g2<16>, pl.grid, dim3(256), lds2, st, p);
-    } else if (cg == 2) {
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g<2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_conv3d_i8g<2>, pl.grid, dim3(256), lds, st, p);
     } else if (cg == 4) {
       EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g<4>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -314,9 +314,8 @@ static int i8s_plan(const effq_geom* g, int act_levels, int w_levels, I8sPlan* p
   EFFQ_CHECK_ARG((double)p.K * 255.0 * 255.0 * 2.0 < 2147483647.0);
   // persistent: every workgroup pays a prologue (B operands, tap table) and one same-address ticket atomic (~12 ns
   // each, serialised): a few workgroups per CU with several tiles per wave, not one tile per wave
-  static const int cap = getenv("EFFQ_I8S_GRID") ? atoi(getenv("EFFQ_I8S_GRID")) : 512;      // tuning aid
   int grid = (p.ntiles + 3) / 4;
-  if (grid > cap) grid = cap;
+  if (grid > 512) grid = 512;
   pl->grid = grid;
   pl->wq_bytes = (size_t)p.NJ * p.CT * 2 * 32 * 16;
   pl->su_bytes = (w_levels > 128) ? (size_t)p.V * sizeof(int) : 0;

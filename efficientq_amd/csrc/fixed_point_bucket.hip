@@ -814,30 +814,12 @@ size_t effq_fp_bucket_max(void) { return (size_t)1 << 23; }
 
 size_t effq_fp_bucket_ws_bytes(size_t n) { return n <= (size_t)FPS2_MAXN ? 256 : fpg_ws_bytes(n); }
 
-int effq_fixed_point_bucket_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
-                                  double tol, int max_iter, effq_fp_state* state_dev, void* ws, size_t ws_bytes,
-                                  void* pred_dev, const ProjFused* pf_in, int* fused_out, void* stream);
-
 int effq_fixed_point_bucket_rec(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
                                 double tol, int max_iter, effq_fp_state* state_dev, void* ws, size_t ws_bytes,
                                 void* pred_dev, void* stream) {
-  return effq_fixed_point_bucket_fused(a, b, v_out, n, levels, lo, hi, tol, max_iter, state_dev, ws, ws_bytes, pred_dev,
-                                       nullptr, nullptr, stream);
-}
-
-// internal (admm_run.hip): pf_in != NULL and n <= 32768 (one workgroup): the projection of the ADMM iteration runs as the
-// kernel's epilogue and *fused_out = 1; larger tensors ignore pf_in (*fused_out = 0: the caller launches the projection)
-int effq_fixed_point_bucket_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
-                                  double tol, int max_iter, effq_fp_state* state_dev, void* ws, size_t ws_bytes,
-                                  void* pred_dev, const ProjFused* pf_in, int* fused_out, void* stream) {
   FptPred* pred = reinterpret_cast<FptPred*>(pred_dev);
-  ProjFused pf;
+  ProjFused pf;                  // k_fps's projection epilogue stays off (measured slower, admm_run.hip)
   memset(&pf, 0, sizeof(pf));
-  if (fused_out != nullptr) *fused_out = 0;
-  if (pf_in != nullptr && n <= (size_t)FPS2_MAXN && v_out != nullptr) {
-    pf = *pf_in;
-    if (fused_out != nullptr) *fused_out = 1;
-  }
   EFFQ_CHECK_ARG(a && state_dev && n > 0 && levels >= 2 && levels <= 256 && hi > lo && max_iter > 0);
   EFFQ_CHECK_ARG(n <= effq_fp_bucket_max());
   EFFQ_CHECK_ARG(b == nullptr || v_out != nullptr);

@@ -420,8 +420,7 @@ static int gram_i8_plan(const effq_geom* g, int ncls, long long n_list, GramI8Pa
   p.nchunks = (int)nchunks;
   p.ncls = ncls;
   // splits: ~1536 workgroups, at least 4 chunks each, at most GI_MAX_CPS (int32 accumulator range)
-  static const int wgs = getenv("EFFQ_GI8_WGS") ? atoi(getenv("EFFQ_GI8_WGS")) : 3072;   // tuning aid
-  long long want = (wgs + p.npairs - 1) / p.npairs;
+  long long want = (3072 + p.npairs - 1) / p.npairs;
   if (want > nchunks / 4) want = nchunks / 4;
   if (want < 1) want = 1;
   long long cps = (nchunks + want - 1) / want;

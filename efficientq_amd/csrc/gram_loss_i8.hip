@@ -41,8 +41,8 @@ struct Gl8Params {
   int P, nwp, nw, ncols, c2, mt, nt, ntiles;
 };
 
-// One tile of the product per call; the launch is a PERSISTENT grid of far fewer workgroups than CUs (EFFQ_GL8_WGS,
-// default 64) that draw tiles from a ticket: the losses only rank iterates that the chain has long left behind (a group of
+// One tile of the product per call; the launch is a PERSISTENT grid of far fewer workgroups than CUs (64) that
+// draw tiles from a ticket: the losses only rank iterates that the chain has long left behind (a group of
 // 8 iterates has 1 - 3 ms of chain time to finish in), and a grid that fills the chip keeps the 256-row prox GEMM of the
 // chain (one workgroup per CU, 147 KB of LDS) waiting for CUs: 0.20 -> 0.42 ms per solve with 648 resident-at-will
 // workgroups.
@@ -336,8 +336,7 @@ int effq_gram_loss_i8(const int8_t* planes, int nplanes, const double* Au, const
   p.mt = p.nwp / G8_TM; p.nt = (p.ncols + G8_TN - 1) / G8_TN;
   p.ntiles = p.mt * p.P * p.nt;
   p.ticket = tile_ticket;
-  static const int wgs_env = getenv("EFFQ_GL8_WGS") ? atoi(getenv("EFFQ_GL8_WGS")) : 64;
-  int wgs = wgs_env < 1 ? 1 : wgs_env;
+  int wgs = 64;
   if (wgs > p.ntiles) wgs = p.ntiles;
   static bool attr_set = false;
   const int lds = 4 * G8_TILE;

@@ -876,12 +876,8 @@ int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, s
   const double d = (hi - lo) / (double)(levels - 1);
   {
     // threads: 256 up to 2048 elements, 512 up to 16384 (few waves: the barrier is cheap and the element loop stays
-    // short; measured best on MI355X, scripts/exp_fp256.py), else 1024; slots per thread rounded up to a power of 2.  EFFQ_FPS_T overrides (tuning aid).
-    static const int force_t = getenv("EFFQ_FPS_T") ? atoi(getenv("EFFQ_FPS_T")) : 0;
-    int T = (n <= 2048) ? 256 : (n <= 16384) ? 512 : FPS_T;
-    if (force_t == 256 && n <= 8192) T = 256;
-    if (force_t == 512 && n <= 16384) T = 512;
-    if (force_t == 1024) T = 1024;
+    // short; measured best on MI355X, scripts/exp_fp256.py), else 1024; slots per thread rounded up to a power of 2
+    const int T = (n <= 2048) ? 256 : (n <= 16384) ? 512 : FPS_T;
     int per = (int)((n + T - 1) / T), pp = 1;
     while (pp < per) pp <<= 1;
     hipStream_t st = as_stream(stream);

@@ -1092,7 +1092,7 @@ __global__ __launch_bounds__(256) void k_prox_reduce(const float* __restrict__ p
 }
 
 // workgroup tile variant and K split of the prox GEMM: ~440 workgroups, >= 6 K tiles per slice (measured
-// best on MI355X for the BraTS sizes: scripts/prof_prox.py with EFFQ_PROX_SPLIT).  The 256-row variant holds 3
+// best on MI355X for the BraTS sizes: scripts/prof_prox.py, forcing the split).  The 256-row variant holds 3
 // workgroups per CU (104 VGPR + 64 AGPR, 45 KB LDS): ~760 workgroups fill the 768 slots evenly - with 545 some CUs
 // carried 3 and others 2 (c2 = 256, n = 6913: 325 -> 266 us per solve).
 struct ProxPlan { int variant, gx, gy, nsplit, c2p, ldb; };
@@ -1100,38 +1100,30 @@ static ProxPlan prox_plan(int c2, int n) {
   ProxPlan p;
   p.c2p = (c2 > 128) ? round_up(c2, 256) : (c2 > 64) ? 128 : round_up(c2, 32);
   p.ldb = round_up(n, 32);
-  static const int wide = getenv("EFFQ_PROX_WIDE") ? atoi(getenv("EFFQ_PROX_WIDE")) : 0;   // tuning aid
-  // A/B switch of the bf16 x 3 kernel: bit 0 = rows > 128, bit 1 = the 128-row layers too (0 = f32 matrix cores)
-  static const int b3 = getenv("EFFQ_PROX_B3") ? atoi(getenv("EFFQ_PROX_B3")) : 3;
-  if (b3 && (p.c2p >= 256 || (p.c2p == 128 && (b3 & 2))) && n >= 1024) {
-    // 256 (128) x 256 tiles on the bf16 matrix cores (k_prox_gemm_b3), one workgroup of 8 waves per CU: K split so that
-    // the grid is about one round of the 256 CUs, at least 16 K tiles per slice
-    p.variant = (p.c2p >= 256) ? 5 : 6; p.gx = (n + 255) / 256; p.gy = (p.c2p >= 256) ? p.c2p / 256 : 1;
+  if (p.c2p >= 128 && n >= 1024) {
+    // 256 x 256 tiles on the bf16 matrix cores (k_prox_gemm_b3), one workgroup of 8 waves per CU: K split so that the
+    // grid is about one round of the 256 CUs, at least 16 K tiles per slice
+    p.variant = 5; p.gx = (n + 255) / 256; p.gy = p.c2p / 256;
     // 128 rows: 128 x 128 tiles (28 column tiles x 9 K slices at n = 3457: half the partial slabs of the 128 x 256 tiling,
-    // two workgroups per CU): 37.7 against 43.1 us alone, 35.8 against 44.3 in situ.  EFFQ_PROX_B3_128=0: A/B switch
-    static const int b3_128 = getenv("EFFQ_PROX_B3_128") ? atoi(getenv("EFFQ_PROX_B3_128")) : 1;
-    if (p.variant == 6 && b3_128) { p.variant = 7; p.gx = (n + 127) / 128; }
+    // two workgroups per CU): 37.7 against 43.1 us alone, 35.8 against 44.3 in situ
+    if (p.c2p == 128) { p.variant = 7; p.gx = (n + 127) / 128; p.gy = 1; }
     const int tiles5 = p.gx * p.gy, nkt5 = p.ldb / B3_K;
     int s5 = (256 + tiles5 / 2) / tiles5;
     if (s5 > nkt5 / 16) s5 = nkt5 / 16;
     if (s5 < 1) s5 = 1;
-    static const int force5 = getenv("EFFQ_PROX_SPLIT") ? atoi(getenv("EFFQ_PROX_SPLIT")) : 0;   // tuning aid
-    if (force5 > 0 && force5 <= nkt5) s5 = force5;
     p.nsplit = s5;
     return p;
   }
-  if (p.c2p >= 256 && wide) { p.variant = 4; p.gx = (n + 127) / 128; p.gy = p.c2p / 256; }   // 256x128, waves 64x128
-  else if (p.c2p >= 256) { p.variant = 0; p.gx = (n + 63) / 64; p.gy = p.c2p / 256; }        // 256x64, waves 64x64
+  if (p.c2p >= 256) { p.variant = 0; p.gx = (n + 63) / 64; p.gy = p.c2p / 256; }             // 256x64, waves 64x64
   else if (p.c2p == 128) { p.variant = 1; p.gx = (n + 63) / 64; p.gy = 1; }             // 128x64, waves 32x64
   else if (p.c2p == 64) { p.variant = 2; p.gx = (n + 63) / 64; p.gy = 1; }              // 64x64, waves 32x32
   else { p.variant = 3; p.gx = (n + 127) / 128; p.gy = 1; }                             // 32x128, waves 32x32
   const int tiles = p.gx * p.gy, nkt = p.ldb / PBK;
-  static const int target_env = getenv("EFFQ_PROX_WGS") ? atoi(getenv("EFFQ_PROX_WGS")) : 0;   // tuning aid
-  int s = ((target_env > 0 ? target_env : 440) + tiles - 1) / tiles;
+  int s = (440 + tiles - 1) / tiles;
   if (s > nkt / 6) s = nkt / 6;
   if (s > 16) s = 16;
   if (s < 1) s = 1;
-  if (p.variant == 0 && target_env == 0) {
+  if (p.variant == 0) {
     // fill the 768 slots (3 workgroups per CU) in whole rounds: the split with the best fill, smaller splits preferred
     const int smax = s > 1 ? 16 : 1;
     double best = -1.0;
@@ -1141,8 +1133,6 @@ static ProxPlan prox_plan(int c2, int n) {
       if (score > best) { best = score; s = c; }
     }
   }
-  static const int force = getenv("EFFQ_PROX_SPLIT") ? atoi(getenv("EFFQ_PROX_SPLIT")) : 0;   // tuning aid
-  if (force > 0 && force <= nkt) s = force;
   p.nsplit = s;
   return p;
 }
@@ -1156,21 +1146,17 @@ extern "C" {
 // workspace of the rank-64 sweep on an npad x npad matrix that is already in place: XT [64][npad], NZ [npad][64], 2 Dinv
 static size_t gj64_aux_doubles(size_t npad) { return 2 * (size_t)NBK * npad + 2 * NBK * NBK; }
 
-// the wide sweep (pivot blocks of 256) from this many 64-blocks on; EFFQ_GJ_WIDE=0: the rank-64 sweep everywhere (A/B)
-static int gj_wide_min_blocks() {
-  static const int off = getenv("EFFQ_GJ_WIDE") != nullptr && atoi(getenv("EFFQ_GJ_WIDE")) == 0;
-  // measured inside the calibration (ms per calibration, one box): rank-64 sweep everywhere 689.6; 256-row pivot blocks
-  // from n = 6400 on 671.0; 256-row (or 128-row, fused pivot launch) blocks for every n >= 512: 683.5 / 681.8 - below
-  // n ~ 5000 an inverse is a chain of dependent launches either way, and the rank-64 sweep has the shortest one
-  static const int mn = getenv("EFFQ_GJ_WIDE_MIN") ? atoi(getenv("EFFQ_GJ_WIDE_MIN")) : 100;
-  return off ? (1 << 30) : mn;
-}
+// the wide sweep (pivot blocks of 256) from this many 64-blocks on.  Measured inside the calibration (ms per calibration,
+// one box): rank-64 sweep everywhere 689.6; 256-row pivot blocks from n = 6400 on 671.0; 256-row (or 128-row, fused pivot
+// launch) blocks for every n >= 512: 683.5 / 681.8 - below n ~ 5000 an inverse is a chain of dependent launches either
+// way, and the rank-64 sweep has the shortest one
+constexpr int GJ_WIDE_MIN_BLOCKS = 100;
 
 size_t effq_spd_inverse_ws_bytes(int n) {
   if (n <= 0) return 0;
   const size_t npad = (size_t)round_up(n, NBK);
   size_t d = npad * npad + gj64_aux_doubles(npad);
-  if ((int)(npad / NBK) >= gj_wide_min_blocks()) {
+  if ((int)(npad / NBK) >= GJ_WIDE_MIN_BLOCKS) {
     const size_t ldx = (size_t)round_up((int)npad, BG_T);
     d = npad * npad + 2 * (size_t)WK * ldx + (size_t)WK * WK + gj64_aux_doubles(WK);
   }
@@ -1188,16 +1174,15 @@ static int gj64_sweep(double* A64, int npad, double* aux, hipStream_t st) {
   const size_t lds = (size_t)(NBK * LDA_S + NBK * LDB_S) * sizeof(double);
   // The trailing update of step k also forms the inverse of the NEXT pivot block (look-ahead workgroup, see
   // k_gj_trail_sym): only step 0 needs the stand-alone k_gj_diag.  Dinv is double-buffered by step parity.
-  static const bool ahead_off = getenv("EFFQ_GJ_AHEAD") != nullptr && atoi(getenv("EFFQ_GJ_AHEAD")) == 0;   // A/B switch
   for (int k = 0; k < nblk; ++k) {
     const int kb = k * NBK;
     double* Dk = Dinv + (size_t)(k & 1) * NBK * NBK;
     double* Dn = Dinv + (size_t)((k + 1) & 1) * NBK * NBK;
-    if (k == 0 || ahead_off) hipLaunchKernelGGL(k_gj_diag, dim3(1), dim3(GJD_T), 0, st, A64, npad, kb, Dk);
+    if (k == 0) hipLaunchKernelGGL(k_gj_diag, dim3(1), dim3(GJD_T), 0, st, A64, npad, kb, Dk);
     hipLaunchKernelGGL(k_gj_panel, dim3(nblk), dim3(256), lds, st, A64, npad, kb, Dk, NZ, XT);
     if (nblk > 1)
       hipLaunchKernelGGL(k_gj_trail_sym, dim3((nblk + GJ_CT - 1) / GJ_CT, nblk + 1), dim3(256), 0, st, A64, npad, kb, NZ,
-                         XT, ahead_off ? (double*)nullptr : Dn);
+                         XT, Dn);
     EFFQ_LAUNCH_CHECK();
   }
   return EFFQ_OK;
@@ -1234,19 +1219,18 @@ static int gj_wide_ctx(hipStream_t caller, GjWideCtx** out) {
 
 static int gj_wide_sweep(double* A64, int npad, double* aux, hipStream_t st) {
   const int nblk = npad / NBK;
-  // pivot blocks of 128 rows (next pivot block by ONE fused launch) below EFFQ_GJ_WB4_MIN 64-blocks, of 256 rows from there
-  // on (the triangle no longer fits the Infinity Cache: the rank-256 update halves the bytes per flop once more)
-  static const int wb4_min = getenv("EFFQ_GJ_WB4_MIN") ? atoi(getenv("EFFQ_GJ_WB4_MIN")) : 100;
-  const int WB = (nblk >= wb4_min) ? effq::WB : 2;
+  // pivot blocks of 128 rows (next pivot block by ONE fused launch) below 100 64-blocks, of 256 rows from there on (the
+  // triangle no longer fits the Infinity Cache: the rank-256 update halves the bytes per flop once more).  The wide sweep
+  // itself starts at GJ_WIDE_MIN_BLOCKS = 100, so every sweep takes 256-row blocks (128-row form measured slower)
+  const int WB = (nblk >= 100) ? effq::WB : 2;
   const size_t ldx = (size_t)round_up(npad, BG_T);
   double* NZT = aux;                               // [256][ldx]
   double* XTW = NZT + (size_t)WK * ldx;            // [256][ldx]
   double* Dw = XTW + (size_t)WK * ldx;             // [64 m][64 m]: the pivot block, then its inverse
   double* aux64 = Dw + (size_t)WK * WK;
   const int nK = (nblk + WB - 1) / WB, nm = (nblk + 1) / 2;
-  static const bool overlap_on = !(getenv("EFFQ_GJ_OVERLAP") != nullptr && atoi(getenv("EFFQ_GJ_OVERLAP")) == 0);   // A/B
   GjWideCtx* ctx = nullptr;
-  if (overlap_on && nK > 1) {
+  if (nK > 1) {
     const int rc = gj_wide_ctx(st, &ctx);
     if (rc != EFFQ_OK) return rc;
   }
@@ -1352,7 +1336,7 @@ int effq_spd_inverse(const float* A0, int n, int has_bias, double rho, double et
                                  (int)((2 * NBK * PF_LD + 2 * (NBK + 1)) * sizeof(double))));
     attr_set = true;
   }
-  const int rc = (npad / NBK >= gj_wide_min_blocks()) ? gj_wide_sweep(A64, npad, aux, st) : gj64_sweep(A64, npad, aux, st);
+  const int rc = (npad / NBK >= GJ_WIDE_MIN_BLOCKS) ? gj_wide_sweep(A64, npad, aux, st) : gj64_sweep(A64, npad, aux, st);
   if (rc != EFFQ_OK) return rc;
   {
     const int lda = effq_ainv_ld(n);
@@ -1407,9 +1391,8 @@ static int prox_solve_impl(const float* B0, const float* Ainv, const float* W0, 
 #define EFFQ_PROX_LAUNCH(MT, WM, WN, NTN)                                                                              \
   hipLaunchKernelGGL((k_prox_gemm<MT, WM, WN, NTN>), grid, dim3(256), 0, st, Bm, ldb, Ainv, lda, n, c2, has_bias ? 1 : 0, \
                      wstar, bstar, part, ldb)
-    if (pl.variant == 5 || pl.variant == 6 || pl.variant == 7) {
+    if (pl.variant == 5 || pl.variant == 7) {
       const size_t lds5 = (size_t)2 * 3 * (256 + 256) * B3_LD * sizeof(__bf16);      // two stages
-      const size_t lds6 = (size_t)2 * 3 * (128 + 256) * B3_LD * sizeof(__bf16);
       const size_t lds7 = (size_t)2 * 3 * (128 + 128) * B3_LD * sizeof(__bf16);
       static bool attr5[64] = {};
       int dev5 = 0;
@@ -1418,8 +1401,6 @@ static int prox_solve_impl(const float* B0, const float* Ainv, const float* W0, 
       if (!attr5[dev5]) {
         EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prox_gemm_b3<256, 256, 4, 2>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
-        EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prox_gemm_b3<128, 256, 2, 4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6));
         EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prox_gemm_b3<128, 128, 2, 4>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7));
         attr5[dev5] = true;
@@ -1427,16 +1408,12 @@ static int prox_solve_impl(const float* B0, const float* Ainv, const float* W0, 
       if (pl.variant == 5)
         hipLaunchKernelGGL((k_prox_gemm_b3<256, 256, 4, 2>), grid, dim3(512), lds5, st, Bm, ldb, Ainv, lda, n, c2,
                            has_bias ? 1 : 0, wstar, bstar, part, ldb);
-      else if (pl.variant == 6)
-        hipLaunchKernelGGL((k_prox_gemm_b3<128, 256, 2, 4>), grid, dim3(512), lds6, st, Bm, ldb, Ainv, lda, n, c2,
-                           has_bias ? 1 : 0, wstar, bstar, part, ldb);
       else
         hipLaunchKernelGGL((k_prox_gemm_b3<128, 128, 2, 4>), grid, dim3(512), lds7, st, Bm, ldb, Ainv, lda, n, c2,
                            has_bias ? 1 : 0, wstar, bstar, part, ldb);
     } else
     switch (pl.variant) {
       case 0: EFFQ_PROX_LAUNCH(2, 4, 1, 2); break;
-      case 4: EFFQ_PROX_LAUNCH(2, 4, 1, 4); break;
       case 1: EFFQ_PROX_LAUNCH(1, 4, 1, 2); break;
       case 2: EFFQ_PROX_LAUNCH(1, 2, 2, 1); break;
       default: EFFQ_PROX_LAUNCH(1, 1, 4, 1); break;

@@ -16,19 +16,12 @@ from ._lib import Geom, check
 
 ADMM_TOL = 1e-5   # layer_helper.py:55
 # tensors from this size on are fitted by the bracketed fixed point (effq_fp_bracket_*)
-import os as _os
-FP_BRACKET_MIN = int(_os.environ.get("EFFQ_FP_BRACKET_MIN", 1 << 18))
-COOP_FIXED_POINT = _os.environ.get("EFFQ_COOP_FP", "1") != "0"
+FP_BRACKET_MIN = 1 << 18
 # data-parallel activation fit: after DP_GATHER_AFTER all-reduced iterations the ranks exchange their tallies and undecided
 # lists once and finish on their own (effq_fp_bracket_export / _import); lists longer than DP_GATHER_MAX_BYTES in all: more
-# all-reduced iterations first.  EFFQ_DP_GATHER_FIT=0: one all-reduce per iteration (A/B)
-DP_GATHER_FIT = _os.environ.get("EFFQ_DP_GATHER_FIT", "1") != "0"
-DP_GATHER_AFTER = int(_os.environ.get("EFFQ_DP_GATHER_AFTER", "4"))
-DP_GATHER_MAX_BYTES = int(_os.environ.get("EFFQ_DP_GATHER_MAX_BYTES", str(128 << 20)))
-BUCKET_FIXED_POINT = _os.environ.get("EFFQ_BUCKET_FP", "1") != "0"
-TRAJ_FIXED_POINT = _os.environ.get("EFFQ_FP_TRAJ", "1") != "0"
-SIDE2_STREAM = _os.environ.get("EFFQ_SIDE2", "1") != "0"
-SIDE_STREAM = _os.environ.get("EFFQ_SIDE", "1") != "0"      # 0: every inverse on the main stream, ahead of the loop (diagnostic)
+# all-reduced iterations first
+DP_GATHER_AFTER = 4
+DP_GATHER_MAX_BYTES = 128 << 20
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -136,11 +129,8 @@ class HipOps:
         main = torch.cuda.current_stream(self.device)
         # which streams get their helper, in which order, is empirical (per calibration with a 1-rank RCCL group, one box: none
         # 693 ms, main / loss / side / side2 675, main / side / side2 - the order of a run without a communicator - 691; plain
-        # run 657; GPU_MAX_HW_QUEUES = 6 / 8: 766 / 753).  EFFQ_WARM_ORDER = 0 / 1 / 2 selects them (tuning aid)
-        order = _os.environ.get("EFFQ_WARM_ORDER", "1")
-        loss, side, side2 = self.loss_stream(), self.side_stream(), self.side_stream2()
-        sts = () if order == "0" else (main, loss, side, side2) if order == "1" else (main, side, side2)
-        for st in sts:
+        # run 657; GPU_MAX_HW_QUEUES = 6 / 8: 766 / 753)
+        for st in (main, self.loss_stream(), self.side_stream(), self.side_stream2()):
             check(self.lib.effq_spd_inverse_prepare(st.cuda_stream), "effq_spd_inverse_prepare")
         self._warm = True
 
@@ -276,7 +266,7 @@ class HipOps:
         # unsigned quantiser = post-ReLU input: the first pass already drops the exact zeros
         check(self.lib.effq_fp_bracket_init(_ptr(st), _ptr(s0), n, levels, int(lo == 0.0), _ptr(ws), ws.numel(),
                                             self.stream), "effq_fp_bracket_init")
-        gather = (reducer is not None and DP_GATHER_FIT and lo == 0.0 and hasattr(reducer, "all_gather"))
+        gather = (reducer is not None and lo == 0.0 and hasattr(reducer, "all_gather"))
         dp_iters = DP_GATHER_AFTER
         while True:
             if reducer is None:
@@ -365,7 +355,7 @@ class HipOps:
             check(self.lib.effq_fixed_point_small(_ptr(wstar), _ptr(dual), _ptr(v), n, levels, -1.0, 1.0, ADMM_TOL,
                                                   100 * levels, _ptr(state), self.stream), "effq_fixed_point_small")
             return None
-        if n <= self.lib.effq_fp_coop_max() and COOP_FIXED_POINT:
+        if n <= self.lib.effq_fp_coop_max():
             check(self.lib.effq_fixed_point_coop(_ptr(wstar), _ptr(dual), _ptr(v), n, levels, -1.0, 1.0, ADMM_TOL,
                                                  100 * levels, _ptr(state), _ptr(self._red_ws), self.stream),
                   "effq_fixed_point_coop")
@@ -720,14 +710,13 @@ class HipOps:
         prox = self._workspace("prox", self.lib.effq_prox_ws_bytes(c2, n))
         inv = self._workspace("inv", self.lib.effq_spd_inverse_ws_bytes(n))
         inv_side = (self._workspace("inv_side", self.lib.effq_spd_inverse_ws_bytes(n))
-                    if n_inv > 1 and SIDE_STREAM else None)
+                    if n_inv > 1 else None)
         inv_side2 = (self._workspace("inv_side2", self.lib.effq_spd_inverse_ws_bytes(n))
-                     if n_inv > 2 and SIDE2_STREAM and SIDE_STREAM else None)
+                     if n_inv > 2 else None)
         fpw = (self._workspace("fp_bucket", self.lib.effq_fp_bucket_ws_bytes(nw))
-               if nw <= self.lib.effq_fp_bucket_max() and BUCKET_FIXED_POINT and not channel_wise else None)
+               if nw <= self.lib.effq_fp_bucket_max() and not channel_wise else None)
         # weight projection from the previous iteration's iterates (effq_fixed_point_traj)
-        traj = (TRAJ_FIXED_POINT and not channel_wise and
-                bool(self.lib.effq_admm_uses_traj(nw, int(levels))))   # the library's own decision
+        traj = not channel_wise and bool(self.lib.effq_admm_uses_traj(nw, int(levels)))   # the library's own decision
         tws = self._workspace("fp_traj", self.lib.effq_fp_traj_ws_bytes(nw)) if traj else None
         r.fp_pred = torch.zeros(self.lib.effq_fp_traj_pred_bytes(), dtype=torch.uint8, device=dev) if traj else None
         if loss_kind == 5:

@@ -25,17 +25,14 @@ from .hip_ops import from_ndhwc, make_geom, to_ndhwc
 LWQ_ITER, LWQ_RHO, LWQ_RHO_MAX, LWQ_ETA, RHO_PERIOD = 200, 10.0, 1000.0, 1.0, 50
 import os as _os
 EXACT_INT_DEFAULT = _os.environ.get("EFFQ_EXACT_INT", "1") != "0"
-# evaluate the loss of iteration i on a second stream while the chain computes iteration i+1
-OVERLAP_LOSS_DEFAULT = _os.environ.get("EFFQ_OVERLAP_LOSS", "1") != "0"
 # per-iteration losses from the unweighted Gram system (effq_gram_loss) for layers with n = k^3 c1 + 1 up to this size
 GRAM_LOSS_DEFAULT = _os.environ.get("EFFQ_GRAM_LOSS", "1") != "0"
-GRAM_LOSS_MAX_N = int(_os.environ.get("EFFQ_GRAM_LOSS_MAX_N", "1729"))
-FORWARD_I8 = _os.environ.get("EFFQ_FORWARD_I8", "1") != "0"       # the calibrated layer's forward + final loss on the i8 cores
-GRAM_LOSS_I8 = _os.environ.get("EFFQ_GRAM_LOSS_I8", "1") != "0"     # wide layers: the quadratic form on the i8 matrix cores
-# ... up to this system size: measured per calibration, BraTS (n = 3457, 6913) 674 -> 657 ms with it; LiTS with its
-# 512-channel layers (n = 13825) included 2110 -> 2169 ms (5.4 ms per group of 8 iterates beside a chain that is itself
-# slowed by three concurrent 57 ms inverses), so those keep the integer conv pass
-GRAM_LOSS_I8_MAX_N = int(_os.environ.get("EFFQ_GRAM_LOSS_I8_MAX_N", "8000"))
+GRAM_LOSS_MAX_N = 1729
+# wide layers: the quadratic form on the i8 matrix cores up to this system size: measured per calibration, BraTS
+# (n = 3457, 6913) 674 -> 657 ms with it; LiTS with its 512-channel layers (n = 13825) included 2110 -> 2169 ms (5.4 ms
+# per group of 8 iterates beside a chain that is itself slowed by three concurrent 57 ms inverses), so those keep the
+# integer conv pass
+GRAM_LOSS_I8_MAX_N = 8000
 
 
 def get_ops(device):
@@ -362,7 +359,8 @@ class EfficientQConvHIP(PTQConv):
         self.lwq_trace = kwQ.get('lwq_trace', False)   # record the per-iteration loss (one host sync each)
         # evaluate the per-iteration losses on the i8 matrix cores (exact int32 accumulation) where supported
         self.lwq_exact_int = kwQ.get('lwq_exact_int', EXACT_INT_DEFAULT)
-        self.lwq_overlap_loss = kwQ.get('lwq_overlap_loss', OVERLAP_LOSS_DEFAULT)
+        # evaluate the loss of iteration i on a second stream while the chain computes iteration i+1
+        self.lwq_overlap_loss = kwQ.get('lwq_overlap_loss', True)
 
     @staticmethod
     def _std(m: torch.Tensor) -> float:
@@ -459,7 +457,7 @@ class EfficientQConvHIP(PTQConv):
                       yn.numel() // c2 >= 8 * n_sys)
         # ... and on the wide layers (n above GRAM_LOSS_MAX_N: the fp64 evaluation would cost more than the conv pass) with
         # the quadratic form on the i8 matrix cores: both of its factors are small integers there (effq_gram_loss_i8)
-        use_gl8 = bool(use_gi8 and GRAM_LOSS_DEFAULT and GRAM_LOSS_I8 and not use_gl and not chan and
+        use_gl8 = bool(use_gi8 and GRAM_LOSS_DEFAULT and not use_gl and not chan and
                        GRAM_LOSS_MAX_N < n_sys <= GRAM_LOSS_I8_MAX_N and
                        getattr(ops, "gram_loss_i8_supported", lambda *a: False)(c2, n_sys, has_b, self.qlvl_w))
         if use_gi8 and (use_gl or use_gl8):
@@ -515,7 +513,7 @@ class EfficientQConvHIP(PTQConv):
         # ... on the i8 matrix cores where the level ids of the input are at hand and the shape has a kernel (32 -> 32 and
         # 64 -> 64 channels at 3^3: the layers with the most voxels): an exact integer contraction + one multiply-add per
         # output, HBM-bound, instead of the f32 conv (2.6 -> 0.3 ms at 16 x 64^3 voxels)
-        fwd_i8 = bool(FORWARD_I8 and fuse and xidx is not None and self.lwq_exact_int and not chan and
+        fwd_i8 = bool(fuse and xidx is not None and self.lwq_exact_int and not chan and
                       getattr(ops, "conv_i8_out_supported", lambda *a: False)(geom, self.qlvl_act, self.qlvl_w))
         if fwd_i8:
             st_best = run.state_ring.index_select(0, best[1:2].to(torch.long)).reshape(-1)    # the best iterate's scale
@@ -529,8 +527,6 @@ class EfficientQConvHIP(PTQConv):
         red(fin)
         info = ops.admm_read(run, best, extra=fin)                         # ONE host sync for the loop and the final loss
         t_loop = _time.perf_counter() - t_loop0
-        if _os.environ.get("EFFQ_FP_TRAJ_STATS") and getattr(run, "fp_pred", None) is not None:     # diagnostic
-            print(f"[fp_traj] {getattr(self, 'name', '?')}: {ops.read_fp_pred(run.fp_pred)}", flush=True)
         a_w, w_iters, hist, best_h = info["alpha_w"], info["w_iters"], info["hist"], info["best"]
         if self.lwq_verbose and getattr(run, "res", None) is not None:
             # "print every 10 admm iters" (EfficientQConv.py:124-127), after the loop: the iterations are enqueued as a whole

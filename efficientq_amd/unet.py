@@ -36,16 +36,12 @@ class TrilinearUp(nn.Upsample):
         plain = (x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and len(sc) == 3 and
                  all(v in (1, 2) for v in sc) and
                  tuple(float(v) for v in (sf if isinstance(sf, (tuple, list)) else (sf,) * 3)) == tuple(float(v) for v in sc)
-                 and not (torch.is_grad_enabled() and x.requires_grad) and FAST_UPSAMPLE)
+                 and not (torch.is_grad_enabled() and x.requires_grad))
         if not plain:
             return super().forward(x)
         from .hip_ops import get_ops
         from .qconv import from_ndhwc, to_ndhwc
         return from_ndhwc(get_ops(x.device).upsample_trilinear(to_ndhwc(x), sc))
-
-
-import os as _os
-FAST_UPSAMPLE = _os.environ.get("EFFQ_FAST_UPSAMPLE", "1") != "0"
 
 
 class ConvUnit(nn.Module):

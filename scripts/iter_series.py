@@ -1,6 +1,6 @@
 """Time of the chain ops of the widest layers against the ADMM iteration (diagnostic, GPU): shows what the side-stream
 inverses and the loss stream cost the chain kernels that run beside them.
-    python scripts/iter_series.py [volumes] [every]      (EFFQ_SIDE=0 / EFFQ_OVERLAP_LOSS=0 for the comparison runs)"""
+    python scripts/iter_series.py [volumes] [every]"""
 import ctypes as C
 import os
 import sys
