@@ -13,37 +13,8 @@
 #include <stdlib.h>
 #include <vector>
 #include "common.h"
+#include "internal.h"
 #include "project_dual.h"
-
-extern "C" {
-int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
-                                 double tol, int max_iter, effq_fp_state* state_dev, const effq::ProjFused* pf_in,
-                                 void* stream);   // quant_reduce.hip (internal)
-int effq_project_dual_next(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
-                           float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev, float* Bm,
-                           const float* B0, const float* W0, int nwrow, int nb0, int ldb, double rho_next, double eta,
-                           void* stream);
-float* effq_prox_bm(void* ws, int c2, int n, int* ldb);
-int effq_prox_solve_prebuilt(const float* B0, const float* Ainv, const float* W0, const float* b0, const float* G,
-                             const float* dual, int c2, int n, int has_bias, double rho, double eta, float* wstar,
-                             float* bstar, void* ws, size_t ws_bytes, void* stream);
-int effq_prox_solve_prebuilt_parts(const float* B0, const float* Ainv, const float* W0, const float* b0, const float* G,
-                                   const float* dual, int c2, int n, int has_bias, double rho, double eta, float* wstar,
-                                   float* bstar, void* ws, size_t ws_bytes, void* stream, const float** part_out,
-                                   int* nsplit_out, int* ldp_out);                      // solve.hip
-int effq_fixed_point_traj_parts(const float* part, int nsplit, int ldp, int c2, int nwrow, int has_bias, const float* dual,
-                                float* wstar_out, float* bstar_out, float* v_out, int levels, double lo, double hi, double tol,
-                                int max_iter, effq_fp_state* state_dev, void* pred_dev, void* ws, size_t ws_bytes,
-                                void* stream);                                          // fixed_point_traj.hip
-int effq_fixed_point_channels_proj(const float* wstar, float* dual, float* v_out, int c2, int nwrow, int levels,
-                                   double tol, int max_iter, double* alpha_out, int32_t* iters_out, int32_t* err_flag_dev,
-                                   float* G, float dual_div, float* Bm, const float* B0, const float* W0, int n, int ldb,
-                                   double rho_next, double eta, void* stream);   // fixed_point_channels.hip
-int effq_fp_channels_max_row(void);
-int effq_project_dual_checked(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
-                              float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
-                              void* stream);   // quant_reduce.hip (internal)
-}
 
 namespace effq {
 

@@ -32,6 +32,26 @@ void set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Raises KERNEL's dynamic-LDS limit on the current device to at least `bytes`.  The attribute belongs to the device, so
+// the record of what was set is kept per device (hipGetDevice): a fixed size is set once per device, a varying one again
+// only when a launch needs more than was set.  Use as EFFQ_HIP(raise_lds_limit<kernel>(bytes)).
+template <auto KERNEL>
+static inline hipError_t raise_lds_limit(size_t bytes) {
+  constexpr int MAX_DEV = 64;
+  static size_t set[MAX_DEV] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= MAX_DEV) return hipErrorInvalidDevice;
+  if (bytes > set[dev]) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)bytes);
+    if (e != hipSuccess) return e;
+    set[dev] = bytes;
+  }
+  return hipSuccess;
+}
+
 // Profiling ablations ("run the kernel without its MFMA loop / its loads ...") exist only in builds made with
 // -DEFFQ_ABLATE (make ABLATE=1): in the shipped library EFFQ_DBG(p) is the constant 0 and the branches fold away, and no
 // environment variable is read on a launch path.

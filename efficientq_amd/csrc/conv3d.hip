@@ -713,9 +713,7 @@ int conv3d_quant_calib_step(const float* xq_ndhwc, const float* G, const float* 
   const bool has_y = y_fp != nullptr, vec = (p.C1 & 3) == 0;
 #define EFFQ_LAUNCH_K(KERN)                                                                                    \
   do {                                                                                                         \
-    if (lds > 64 * 1024)                                                                                       \
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds));                                                                 \
+    if (lds > 64 * 1024) EFFQ_HIP(raise_lds_limit<KERN>(lds));                                                 \
     hipLaunchKernelGGL(KERN, pl.grid, dim3(256), lds, st, p);                                                  \
   } while (0)
   if (pl.fast) {

@@ -1222,14 +1222,8 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_pack_weight_i8g<4>, dim3((unsigned)((p.c2p + 3) / 4)), dim3(256), (size_t)4 * p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
     const size_t lds = (size_t)W64_WLB + W64_HALOB;
-    static bool attr_set = false;
-    if (!attr_set) {
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8w<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8w<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_set = true;
-    }
+    EFFQ_HIP(raise_lds_limit<k_conv3d_i8w<false>>(lds));
+    EFFQ_HIP(raise_lds_limit<k_conv3d_i8w<true>>(lds));
     int gx = 256;                           // one workgroup per CU (LDS); pl.nblk = 256 partial slots
     if (gx > p.ntiles) gx = p.ntiles;
     if ((size_t)gx > pl.nblk) gx = (int)pl.nblk;
@@ -1266,16 +1260,13 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
     if (cg == 16) {
       const size_t lds2 = (size_t)((G2_NH * (32 * 16 + 16) + G2_HD * I_HH * halo_row_pad(16) + 15) / 16) * 16 +
                           (size_t)64 * G2_TS * sizeof(float);
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g2<16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+      EFFQ_HIP(raise_lds_limit<k_conv3d_i8g2<16>>(lds2));
       hipLaunchKernelGGL(k_conv3d_i8g2<16>, pl.grid, dim3(256), lds2, st, p);
     } else if (cg == 4) {
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g<4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      EFFQ_HIP(raise_lds_limit<k_conv3d_i8g<4>>(lds));
       hipLaunchKernelGGL(k_conv3d_i8g<4>, pl.grid, dim3(256), lds, st, p);
     } else {
-      EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3d_i8g<8>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      EFFQ_HIP(raise_lds_limit<k_conv3d_i8g<8>>(lds));
       hipLaunchKernelGGL(k_conv3d_i8g<8>, pl.grid, dim3(256), lds, st, p);
     }
   }

@@ -32,6 +32,7 @@
 // between the two halves of the finish step (effq_fp_bracket_stats / effq_fp_bracket_update).
 #include <math.h>
 #include "common.h"
+#include "fp_level.h"
 
 namespace effq {
 
@@ -112,34 +113,6 @@ static FbrWs fbr_carve(void* ws, size_t n) {
   return w;
 }
 
-// level index of the reference (layer_helper.py:25-37 in fp64), screened in fp32 exactly as level_accum of
-// quant_reduce.hip: u = (v / a - lo) / d evaluated in fp32 is off by <= 3e-5 at 256 levels and accepted unless it lies
-// within 2e-4 of a rounding boundary, where the reference's own arithmetic decides
-struct FbrLevel {
-  float c1, c0, lmax;
-  double a;
-};
-__device__ __forceinline__ FbrLevel fbr_level_consts(double a, double lo, double hi, double d) {
-  FbrLevel c;
-  const double rd = 1.0 / d;
-  c.c1 = (float)((1.0 / a) * rd);
-  c.c0 = (float)(-lo * rd);
-  c.lmax = (float)rint((hi - lo) * rd);
-  c.a = a;
-  return c;
-}
-__device__ __forceinline__ int fbr_level(float v, const FbrLevel& c, double lo, double hi, double d) {
-  float u = __builtin_fmaf(v, c.c1, c.c0);
-  u = fminf(fmaxf(u, 0.0f), c.lmax);
-  float rf = rintf(u);
-  if (!(fabsf(u - rf) < 0.4998f)) {
-    double t = (double)v / c.a;
-    t = fmin(fmax(t, lo), hi);
-    rf = (float)rint((t - lo) / d);
-  }
-  return (int)rf;
-}
-
 __device__ __forceinline__ long long wave_sum_i64(long long v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -167,9 +140,9 @@ __global__ __launch_bounds__(FBR_T) void k_fbr_iter(const float* __restrict__ x,
   }
   const bool narrow = h.narrow != 0;
   float* __restrict__ dst = w.L[narrow ? h.dst - 1 : 0] + (size_t)wg * per;
-  const FbrLevel la = fbr_level_consts(st->alpha, lo, hi, d);
-  const FbrLevel ll = fbr_level_consts(narrow ? h.nlo : st->alpha, lo, hi, d);
-  const FbrLevel lh = fbr_level_consts(narrow ? h.nhi : st->alpha, lo, hi, d);
+  // levels at the scale and at the ends of the new bracket (fp_level.h)
+  const double aa = st->alpha, al = narrow ? h.nlo : aa, ah = narrow ? h.nhi : aa;
+  const LevelConsts la = level_consts(aa, lo, hi, d), ll = level_consts(al, lo, hi, d), lh = level_consts(ah, lo, hi, d);
   const double inv_q = h.inv_q;
   if (tid == 0) s_out = 0u;
   __syncthreads();
@@ -177,10 +150,10 @@ __global__ __launch_bounds__(FBR_T) void k_fbr_iter(const float* __restrict__ x,
   long long D0 = 0, D1 = 0, D2 = 0, D3 = 0, U0 = 0, U1 = 0, U2 = 0, U3 = 0;
   // one value: tallies; returns whether it stays undecided under the new bracket
   auto tally = [&](float v, bool valid) -> bool {
-    const int r = fbr_level(v, la, lo, hi, d);
+    const int r = (int)fp_level_f(v, la, aa, lo, hi, d);
     const long long u = __double2ll_rn((double)v * inv_q);
     bool und = true;
-    if (narrow) und = fbr_level(v, ll, lo, hi, d) != fbr_level(v, lh, lo, hi, d);
+    if (narrow) und = (int)fp_level_f(v, ll, al, lo, hi, d) != (int)fp_level_f(v, lh, ah, lo, hi, d);
     const long long ru = (long long)r * u, r1 = valid ? (long long)r : 0ll, r2 = valid ? (long long)(r * r) : 0ll;
     const long long ruv = valid ? ru : 0ll, uv = valid ? u : 0ll;
     if (und) {
@@ -411,11 +384,8 @@ __global__ __launch_bounds__(FBR_FT) void k_fbr_finish(FbrWs w, effq_fp_state* s
     const int it = st->iters + 1;
     st->iters = it;
     int done = 0;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
-    else if (!(a_new >= h->guard_lo && a_new <= h->guard_hi))
+    fp_stop(it, max_iter, a_new, alpha, tol, done);
+    if (done == 0 && !(a_new >= h->guard_lo && a_new <= h->guard_hi))
       done = 4;                                  // left the bracket an imported fit is valid under: the caller falls back
     st->done = done;
     if (done == 0) fbr_plan(h, a_new, alpha, a_pp, it, n);

@@ -12,7 +12,7 @@
 // and its k-th boundary sits at t_k = a*(lo + (k-0.5)*d) up to a few fp64 roundings: |error| <= ~4 ulp64 * |t_k| plus
 // a * 2^-52 from the subtraction of lo (the boundary at v = 0: 1 - |v/a| rounds to 1 for tiny negative v).  Values
 // outside the guard band t_k -+ max(|t_k| * 2^-20, a * 2^-30) are therefore classified by comparison; values INSIDE it
-// (a 1e-6 relative sliver) by the reference's own arithmetic (fpb_level: IEEE fp64 divisions, round-half-even).  The
+// (a 1e-6 relative sliver) by the reference's own arithmetic (level_exact of fp_level.h: IEEE fp64 divisions, round-half-even).  The
 // level counts are exactly the reference's; the sums are fp64 sums of the same products in another order, built from
 // integer partial sums (exact, order-independent: run-to-run and rank-to-rank deterministic), i.e. alpha agrees to
 // ~1e-14 relative and the iteration count is the same.  Tested against the reference goldens (G2), the oracle, the
@@ -36,13 +36,6 @@ __device__ long long g_fpb_trace[1024];
 constexpr int FPB_SHIFT = 36;    // integer sums carry (v - origin) in units of bucket_width * 2^-36
 constexpr int FPB_TI = 256;      // threads of the iteration phase
 constexpr int FPB_CR = 4;        // boundary-bucket values cached in registers per lane
-
-__device__ __forceinline__ int fpb_level(double x, double alpha, double lo, double hi, double d) {
-  // layer_helper.py:25-37 in fp64, exactly as disc64 in quant_reduce.hip
-  double t = x / alpha;
-  t = fmin(fmax(t, lo), hi);
-  return (int)rint((t - lo) / d);
-}
 
 struct FpbGeo {
   float R, scale;        // bucket(v) = clamp(floor((v + R) * scale), 0, B-1)   (fp32 arithmetic: monotone in v)
@@ -188,7 +181,7 @@ __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, cons
 #pragma unroll
         for (int r = 0; r < FPB_CR; ++r) {
           const float v = cv[r];
-          if (v > vlo && v < vhi && fpb_level((double)v, alpha, lo, hi, d) < k) {
+          if (v > vlo && v < vhi && (int)level_exact((double)v, alpha, lo, hi, d) < k) {
             ++cnt;
             qs += cq[r];
           }
@@ -198,7 +191,7 @@ __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, cons
         for (unsigned i = c_seg0 + (unsigned)gl + (unsigned)(FPB_CR * gs); i < c_seg1; i += (unsigned)gs) {
           const float v = vals[i];
           bool below = (v <= vlo);
-          if (!below && v < vhi) below = fpb_level((double)v, alpha, lo, hi, d) < k;
+          if (!below && v < vhi) below = (int)level_exact((double)v, alpha, lo, hi, d) < k;
           if (below) {
             ++cnt;
             qs += fpb_units(v, jlo, g);
@@ -261,27 +254,13 @@ __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, cons
     FPB_TRACE(19 + 4 * it);
     const double a_new = t0 / t1;
     ++it;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
+    fp_stop(it, max_iter, a_new, alpha, tol, done);
     alpha_prev = alpha;
     alpha = a_new;
     last0 = t0;
     last1 = t1;
   }
-  if (tid == 0) {
-    st->alpha = alpha;
-    st->alpha_prev = alpha_prev;
-    st->sums[0] = last0;
-    st->sums[1] = last1;
-    st->iters = it;
-    st->done = done;
-    if (pred != nullptr) {
-      for (int j = 0; j < FPT_SLOTS; ++j) fpt_finish_slot(pred, j, it, alpha);
-      fpt_finish_head(pred, it, tot_abs, levels);
-    }
-  }
+  if (tid == 0) fp_state_finish(st, pred, alpha, alpha_prev, last0, last1, it, done, tot_abs, levels);
   if (alpha_out != nullptr) *alpha_out = alpha;      // (every thread of the iteration phase holds the same values)
   if (done_out != nullptr) *done_out = done;
 }
@@ -839,12 +818,8 @@ int effq_fixed_point_bucket_rec(const float* a, const float* b, float* v_out, si
     const float* src = (v_out != nullptr) ? v_out : a;
     hipLaunchKernelGGL(k_fpg_sum, dim3((unsigned)blocks), dim3(FPG_T), 0, st, a, b, v_out, n, w);
     {
-      static bool attr_set2 = false;
       const int lds = (int)((sizeof(unsigned long long) + sizeof(unsigned)) * FPG_B);
-      if (!attr_set2) {
-        EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fpg_count), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set2 = true;
-      }
+      EFFQ_HIP(raise_lds_limit<k_fpg_count>(lds));
       const size_t cblocks = (n + FPG_SLICE - 1) / FPG_SLICE;
       hipLaunchKernelGGL(k_fpg_count, dim3((unsigned)cblocks), dim3(FPG_CT), lds, st, src, n, w);
     }
@@ -854,14 +829,10 @@ int effq_fixed_point_bucket_rec(const float* a, const float* b, float* v_out, si
     EFFQ_LAUNCH_CHECK();
     return EFFQ_OK;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    const int lim = (int)fps_lds_bytes(FPS2_MAXN);
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps<8>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps<16>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    attr_set = true;
-  }
+  const size_t lim = fps_lds_bytes(FPS2_MAXN);
+  EFFQ_HIP(raise_lds_limit<k_fps<8>>(lim));
+  EFFQ_HIP(raise_lds_limit<k_fps<16>>(lim));
+  EFFQ_HIP(raise_lds_limit<k_fps<32>>(lim));
   const size_t lds = fps_lds_bytes(n);
   const int per = (int)((n + FPS2_T - 1) / FPS2_T);
   if (per <= 8)

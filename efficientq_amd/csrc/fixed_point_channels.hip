@@ -77,24 +77,16 @@ __global__ __launch_bounds__(T) void k_fp_channels(const float* __restrict__ a, 
   double ralpha = zero_row ? 0.0 : n / tot;
   int it = 0, done = zero_row ? 1 : 0;
   const double rd = 1.0 / d;
-  const float c0 = (float)(-lo * rd), lmax = (float)rint((hi - lo) * rd);
-  const double lo_sv = lo * sv, lo2n = lo * lo * n, d2 = d * d, dlo2 = 2.0 * d * lo;
+  LevelConsts lc = level_grid(lo, hi, d);
   while (!done) {
     const int par = (it + 1) & 1;          // parity 0 carried the prologue sums
-    const float c1 = (float)(ralpha * rd);
+    lc.c1 = (float)(ralpha * rd);
     double arv = 0.0;
     int sr = 0, sr2 = 0;                   // <= 64 slots x 255^2 per thread
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const float vf = vr[k];
-      float u = __builtin_fmaf(vf, c1, c0);
-      u = fminf(fmaxf(u, 0.0f), lmax);
-      float rf = rintf(u);
-      if (!(fabsf(u - rf) < 0.4998f)) {    // within 2e-4 of a rounding boundary (or NaN): exact arithmetic decides
-        double r;
-        disc64((double)vf, alpha, lo, hi, d, &r);
-        rf = (float)r;
-      }
+      const float rf = fp_level_f(vf, lc, alpha, lo, hi, d);
       const int ri = (tid + k * T < nwrow) ? (int)rf : 0;     // absent elements must not count
       sr += ri;
       sr2 += ri * ri;
@@ -120,15 +112,12 @@ __global__ __launch_bounds__(T) void k_fp_channels(const float* __restrict__ a, 
         tr2 += part[par][2][w];
       }
     }
-    const double t0 = d * trv + lo_sv;                         // sum b v
-    const double t1 = (d2 * tr2 + dlo2 * tr) + lo2n;           // sum b^2
+    const double t0 = level_sum_bv(trv, sv, lo, d);   // sum b v
+    const double t1 = level_sum_bb(tr2, tr, n, lo, d);   // sum b^2
     const double a_new = t0 / t1;
     const double ra_new = t1 / t0;
     ++it;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
+    fp_stop(it, max_iter, a_new, alpha, tol, done);
     alpha = a_new;
     ralpha = ra_new;
   }
@@ -139,12 +128,12 @@ __global__ __launch_bounds__(T) void k_fp_channels(const float* __restrict__ a, 
   }
   if (pf.G != nullptr) {                   // this row's projection + dual update (+ Bm of the next prox solve)
     const float alpha32 = (float)alpha;
-    const LevelConsts lc = level_consts(zero_row ? 1.0 : alpha, -1.0, 1.0, pf.d);
+    const LevelConsts plc = level_consts(zero_row ? 1.0 : alpha, -1.0, 1.0, pf.d);
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int c = tid + k * T;
       if (c < nwrow)
-        proj1_apply(base + c, (unsigned)row, (unsigned)c, vr[k], alpha, alpha32, lc, pf.d, zero_row, pf.wstar, pf.G,
+        proj1_apply(base + c, (unsigned)row, (unsigned)c, vr[k], alpha, alpha32, plc, pf.d, zero_row, pf.wstar, pf.G,
                     pf.dual, pf.dual_div, pf.nx);
     }
   }

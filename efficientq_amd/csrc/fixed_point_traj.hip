@@ -24,6 +24,7 @@
 #include "common.h"
 #include "fp_level.h"
 #include "fp_traj.h"
+#include "internal.h"
 
 namespace effq {
 

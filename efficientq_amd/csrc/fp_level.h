@@ -1,39 +1,86 @@
-// Level index of the reference quantiser (layer_helper.py:25-37 evaluated in fp64) with an fp32 screen, shared by the
-// fixed points that classify values at several scales per pass (fixed_point_bracket.hip, fixed_point_traj.hip).
+// The quantiser arithmetic every fixed-point family must agree on bit for bit: the level index of the reference
+// (layer_helper.py:25-37 evaluated in fp64) with its fp32 screen, the scale sums from integer level tallies, the stop
+// rule of project_by_iter (layer_helper.py:55-64) and the final state store.  The kernels (quant_reduce.hip,
+// project_dual.h, fixed_point_{bucket,bracket,channels}.hip, fp_traj.h) keep their own loops and reductions around them.
 #pragma once
 #include <math.h>
+#include "common.h"
 
 namespace effq {
 
-// u = (v / a - lo) / d evaluated in fp32 is off by <= 3e-5 at 256 levels; it is accepted unless it lies within 2e-4 of a
-// rounding boundary, where the reference's own arithmetic (IEEE fp64 divisions, round-half-even) decides: the level is
-// exactly the reference's (the screen of level_accum in quant_reduce.hip).
-struct FpLevel {
+// Exact level index of x at scale a: the reference's own arithmetic (IEEE fp64 divisions, round-half-even).
+__device__ __forceinline__ double level_exact(double x, double a, double lo, double hi, double d) {
+  double t = x / a;
+  t = fmin(fmax(t, lo), hi);
+  return rint((t - lo) / d);
+}
+// (not inlined: the fallback of the screen is taken for ~4 values in 10 000, and its two IEEE divisions are ~100
+// instructions that would otherwise be copied into every unrolled call site)
+__device__ __attribute__((noinline)) inline int fp_level_exact(float v, double a, double lo, double hi, double d) {
+  return (int)level_exact((double)v, a, lo, hi, d);
+}
+
+// Screen constants: u = v c1 + c0 is (v / a - lo) / d in fp32, clamped to [0, lmax].  level_consts derives c1 from 1/a;
+// kernels that derive it otherwise (from sum b^2 / sum bv, or per bracket end) start from level_grid and set c1.
+struct LevelConsts {
   float c1, c0, lmax;
-  double a;
 };
-__device__ __forceinline__ FpLevel fp_level_consts(double a, double lo, double hi, double d) {
-  FpLevel c;
+__device__ __forceinline__ LevelConsts level_consts(double a, double lo, double hi, double d) {
+  LevelConsts c;
   const double rd = 1.0 / d;
   c.c1 = (float)((1.0 / a) * rd);
   c.c0 = (float)(-lo * rd);
   c.lmax = (float)rint((hi - lo) * rd);
-  c.a = a;
   return c;
 }
-// (not inlined: the fallback is taken for ~4 values in 10 000, and its two IEEE divisions are ~100 instructions that
-// would otherwise be copied into every unrolled call site)
-__device__ __attribute__((noinline)) inline int fp_level_exact(float v, double a, double lo, double hi, double d) {
-  double t = (double)v / a;
-  t = fmin(fmax(t, lo), hi);
-  return (int)rint((t - lo) / d);
+__device__ __forceinline__ LevelConsts level_grid(double lo, double hi, double d) {
+  LevelConsts c;
+  const double rd = 1.0 / d;
+  c.c1 = 0.0f;
+  c.c0 = (float)(-lo * rd);
+  c.lmax = (float)rint((hi - lo) * rd);
+  return c;
 }
-__device__ __forceinline__ int fp_level(float v, const FpLevel& c, double lo, double hi, double d) {
+
+// The fp32 screen: u is off by <= 3e-5 at 256 levels, so rint(u) is the exact level unless u lies within 2e-4 of a
+// rounding boundary (or is NaN).  Returns false there: the caller's exact arithmetic decides.
+__device__ __forceinline__ bool level_screen(float v, const LevelConsts& c, float& rf) {
   float u = __builtin_fmaf(v, c.c1, c.c0);
   u = fminf(fmaxf(u, 0.0f), c.lmax);
-  const float rf = rintf(u);
-  if (!(fabsf(u - rf) < 0.4998f)) return fp_level_exact(v, c.a, lo, hi, d);
+  rf = rintf(u);
+  return fabsf(u - rf) < 0.4998f;
+}
+// Screened level of v at scale a (the scale c was built for), the exact fallback inline ...
+__device__ __forceinline__ float fp_level_f(float v, const LevelConsts& c, double a, double lo, double hi, double d) {
+  float rf;
+  if (!level_screen(v, c, rf)) rf = (float)level_exact((double)v, a, lo, hi, d);
+  return rf;
+}
+// ... or out of line (fp_level_exact)
+__device__ __forceinline__ int fp_level(float v, const LevelConsts& c, double a, double lo, double hi, double d) {
+  float rf;
+  if (!level_screen(v, c, rf)) return fp_level_exact(v, a, lo, hi, d);
   return (int)rf;
+}
+
+// Scale sums of n values from their level tallies: b = r d + lo depends on the level r alone, so
+//   sum b v = d sum(r v) + lo sum(v),   sum b^2 = d^2 sum(r^2) + 2 d lo sum(r) + lo^2 n
+// with sum(r), sum(r^2) exact integers and r v exact in fp64.
+__device__ __forceinline__ double level_sum_bv(double srv, double sv, double lo, double d) { return d * srv + lo * sv; }
+template <class N>   // (the count in its caller's type: converted where the formula uses it)
+__device__ __forceinline__ double level_sum_bb(double sr2, double sr, N n, double lo, double d) {
+  const double lo2n = lo * lo * (double)n;
+  return (d * d * sr2 + 2.0 * d * lo * sr) + lo2n;
+}
+
+// Stop rule of project_by_iter after step `it` (counted from 1) moved the scale from alpha to a_new: done = 2 at the cap
+// (the reference raises whenever c == max_iter, even if that last step converged: layer_helper.py:62-64), else done = 1
+// once |a_new - alpha| <= tol (or is NaN); otherwise done is left as it is (0 while iterating).
+__device__ __forceinline__ void fp_stop(int it, int max_iter, double a_new, double alpha, double tol, int& done) {
+  if (it >= max_iter)
+    done = 2;
+  else if (!(fabs(a_new - alpha) > tol))
+    done = 1;
 }
 
 // ---- prediction of a fixed point's iterates from the previous call on (nearly) the same tensor -----------------------
@@ -106,6 +153,27 @@ __device__ __forceinline__ void fpt_finish_head(FptPred* p, int iters, double su
   p->e = e;
   p->e_valid = ok ? 1 : 0;
   p->calls += 1;
+}
+
+// Final state of a fixed point that ran on chip (one thread) ...
+__device__ __forceinline__ void fp_state_store(effq_fp_state* st, double alpha, double alpha_prev, double sbv,
+                                               double sbb, int iters, int done) {
+  st->alpha = alpha;
+  st->alpha_prev = alpha_prev;
+  st->sums[0] = sbv;
+  st->sums[1] = sbb;
+  st->iters = iters;
+  st->done = done;
+}
+// ... and with the recorder's finish by the same thread (sum_abs: sum |v| of the call)
+__device__ __forceinline__ void fp_state_finish(effq_fp_state* st, FptPred* pred, double alpha, double alpha_prev,
+                                                double sbv, double sbb, int iters, int done, double sum_abs,
+                                                int levels) {
+  fp_state_store(st, alpha, alpha_prev, sbv, sbb, iters, done);
+  if (pred != nullptr) {
+    for (int j = 0; j < FPT_SLOTS; ++j) fpt_finish_slot(pred, j, iters, alpha);
+    fpt_finish_head(pred, iters, sum_abs, levels);
+  }
 }
 
 }  // namespace effq

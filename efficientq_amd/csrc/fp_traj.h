@@ -127,7 +127,7 @@ __device__ __forceinline__ void fpt_phase1(FptSmem& sm, const float (&vv)[EPT], 
   const bool warm = K > 0 && e_valid != 0;
   const double inv_q = ldexp(1.0, e_units);
   const double rd = 1.0 / d;
-  const float c0 = (float)(-lo * rd), lmax = (float)rint((hi - lo) * rd);
+  const LevelConsts grid = level_grid(lo, hi, d);
   if (warm && tid < 4 * K) {
     const int c = tid & 3;
     const double ew = p_eps, en = fmin(p_epsn, ew);
@@ -149,11 +149,9 @@ __device__ __forceinline__ void fpt_phase1(FptSmem& sm, const float (&vv)[EPT], 
     sm.c1[FPT_NE + tid] = (float)((1.0 / h) * rd);
   }
   auto level_end = [&](float v, int g) -> int {
-    float u = __builtin_fmaf(v, sm.c1[g], c0);
-    u = fminf(fmaxf(u, 0.0f), lmax);
-    const float rf = rintf(u);
-    if (!(fabsf(u - rf) < 0.4998f)) return fp_level_exact(v, sm.end[g], lo, hi, d);
-    return (int)rf;
+    LevelConsts c = grid;
+    c.c1 = sm.c1[g];
+    return fp_level(v, c, sm.end[g], lo, hi, d);
   };
 
   double sabs = 0.0, sv = 0.0;
@@ -408,14 +406,14 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
         const int j = (it < K) ? it : K - 1;
         if (!(alpha >= sm.end[4 * j + 1] && alpha <= sm.end[4 * j + 2])) break;
         if (lane == 0) fpt_note(pred, it, alpha);
-        const FpLevel lc = fp_level_consts(alpha, lo, hi, d);
+        const LevelConsts lc = level_consts(alpha, lo, hi, d);
         const unsigned long long want = 1ull << (32 + j);
         long long ru = 0, ct = 0;
 #pragma unroll
         for (int c = 0; c < FC; ++c) {
           if (c < nfc && (fcr[c] & want)) {
             const float v = __uint_as_float((unsigned)fcr[c]);
-            const int r = fp_level(v, lc, lo, hi, d);
+            const int r = fp_level(v, lc, alpha, lo, hi, d);
             ru += (long long)r * __double2ll_rn((double)v * inv_q);
             ct += fpt_pack(r);
           }
@@ -423,15 +421,12 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
         const long long Sru = fpt_wave_sum(ru) + sm.T[0] + sm.T[2 + 4 * j] + sm.T[2 + 4 * j + 2];
         const long long Sct = fpt_wave_sum(ct) + sm.T[1] + sm.T[2 + 4 * j + 1] + sm.T[2 + 4 * j + 3];
         const double Sr = (double)(Sct & 0xffffffffll), Sr2 = (double)(Sct >> 32);
-        const double t0 = d * (q_tally * (double)Sru) + lo * tot_v;                          // sum b v
-        const double t1 = (d * d * Sr2 + 2.0 * d * lo * Sr) + lo * lo * (double)n;            // sum b^2
+        const double t0 = level_sum_bv(q_tally * (double)Sru, tot_v, lo, d);   // sum b v
+        const double t1 = level_sum_bb(Sr2, Sr, n, lo, d);   // sum b^2
         const double a_new = t0 / t1;
         ++it;
         ++n_warm;
-        if (it >= max_iter)
-          done = 2;
-        else if (!(fabs(a_new - alpha) > tol))
-          done = 1;
+        fp_stop(it, max_iter, a_new, alpha, tol, done);
         alpha_prev = alpha;
         alpha = a_new;
         last0 = t0;
@@ -466,7 +461,7 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
     const int j = (it < K) ? it : K - 1;
     const bool in_w = tallies_ok && alpha >= sm.end[4 * j] && alpha <= sm.end[4 * j + 3];
     const bool in_n = in_w && alpha >= sm.end[4 * j + 1] && alpha <= sm.end[4 * j + 2];
-    const FpLevel lc = fp_level_consts(alpha, lo, hi, d);
+    const LevelConsts lc = level_consts(alpha, lo, hi, d);
     long long ru = 0, ct = 0;
     if (in_w) {
       // bits of an entry that matter: narrow bit j always; ring bit j too when the iterate missed the narrow bracket
@@ -474,7 +469,7 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
       auto entry = [&](unsigned long long en) {
         if (en & want) {
           const float v = __uint_as_float((unsigned)en);
-          const int r = fp_level(v, lc, lo, hi, d);
+          const int r = fp_level(v, lc, alpha, lo, hi, d);
           ru += (long long)r * __double2ll_rn((double)v * inv_q);
           ct += fpt_pack(r);
         }
@@ -502,7 +497,7 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
       }
     } else {
       auto one = [&](float v) {
-        const int r = fp_level(v, lc, lo, hi, d);
+        const int r = fp_level(v, lc, alpha, lo, hi, d);
         ru += (long long)r * __double2ll_rn((double)v * inv_qf);
         ct += fpt_pack(r);
       };
@@ -551,28 +546,18 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
       q_used = q_tally;
     }
     const double Sr = (double)(Sct & 0xffffffffll), Sr2 = (double)(Sct >> 32);
-    const double t0 = d * (q_used * (double)Sru) + lo * tot_v;                            // sum b v
-    const double t1 = (d * d * Sr2 + 2.0 * d * lo * Sr) + lo * lo * (double)n;              // sum b^2
+    const double t0 = level_sum_bv(q_used * (double)Sru, tot_v, lo, d);   // sum b v
+    const double t1 = level_sum_bb(Sr2, Sr, n, lo, d);   // sum b^2
     const double a_new = t0 / t1;
     ++it;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
+    fp_stop(it, max_iter, a_new, alpha, tol, done);
     alpha_prev = alpha;
     alpha = a_new;
     last0 = t0;
     last1 = t1;
   }
   const long long tr3 = wall_clock64();
-  if (tid == 0) {
-    st->alpha = alpha;
-    st->alpha_prev = alpha_prev;
-    st->sums[0] = last0;
-    st->sums[1] = last1;
-    st->iters = it;
-    st->done = done;
-  }
+  if (tid == 0) fp_state_store(st, alpha, alpha_prev, last0, last1, it, done);
   if (tid < FPT_SLOTS) fpt_finish_slot(pred, tid, it, alpha);
   __syncthreads();
   if (tid == 0) {

@@ -510,12 +510,7 @@ int effq_gram_accum_i8_unw(const uint8_t* xidx_ndhwc, const float* y_ndhwc, cons
     hipLaunchKernelGGL(k_gi_voxtable, dim3((unsigned)nt), dim3(256), 0, st, p, vtab);
     EFFQ_LAUNCH_CHECK();
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram_i8), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GI_LDS));
-    attr_set = true;
-  }
+  EFFQ_HIP(raise_lds_limit<k_gram_i8>(GI_LDS));
   hipLaunchKernelGGL(k_gram_i8, dim3((unsigned)p.npairs, (unsigned)p.nsplit), dim3(GI_T), GI_LDS, st, p);
   EFFQ_LAUNCH_CHECK();
   const int n = p.RX + (has_bias ? 1 : 0);

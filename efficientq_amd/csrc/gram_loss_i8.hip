@@ -338,12 +338,8 @@ int effq_gram_loss_i8(const int8_t* planes, int nplanes, const double* Au, const
   p.ticket = tile_ticket;
   int wgs = 64;
   if (wgs > p.ntiles) wgs = p.ntiles;
-  static bool attr_set = false;
   const int lds = 4 * G8_TILE;
-  if (!attr_set) {
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gl8), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set = true;
-  }
+  EFFQ_HIP(raise_lds_limit<k_gl8>(lds));
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(k_gl8, dim3((unsigned)wgs), dim3(G8_T), lds, st, p);
   EFFQ_LAUNCH_CHECK();

@@ -3,32 +3,9 @@
 // (k_fp_small, k_fps: one launch per iteration less on the layers whose weights fit one workgroup).
 #pragma once
 #include "common.h"
+#include "fp_level.h"
 
 namespace effq {
-
-__device__ __forceinline__ double disc64(double x, double alpha, double lo, double hi, double d, double* idx) {
-  double t = x / alpha;
-  t = fmin(fmax(t, lo), hi);
-  double r = rint((t - lo) / d);
-  *idx = r;
-  return r * d + lo;
-}
-
-struct LevelConsts {
-  float c1, c0, lmax;
-  double alpha, lo, hi, d;
-  bool need_sx;
-};
-__device__ __forceinline__ LevelConsts level_consts(double alpha, double lo, double hi, double d) {
-  LevelConsts c;
-  const double rd = 1.0 / d;
-  c.c1 = (float)((1.0 / alpha) * rd);
-  c.c0 = (float)(-lo * rd);
-  c.lmax = (float)rint((hi - lo) * rd);
-  c.alpha = alpha; c.lo = lo; c.hi = hi; c.d = d;
-  c.need_sx = lo != 0.0;
-  return c;
-}
 
 // Optional extra output of the projection: Bm = B0 + eta [W0|b0] + rho (G - dual) for the next iteration's prox solve,
 // element for element what k_build_b4 (solve.hip) computes - one launch per ADMM iteration less.  The bias column and the
@@ -41,22 +18,8 @@ struct ProjNext {
   float rho, eta;
 };
 
-// Level index of one value at scale alpha: the fp32 evaluation of level_accum, with the reference's fp64 arithmetic
-// deciding within 2e-4 of a rounding boundary (exact).
-__device__ __forceinline__ float proj_level(float v, double alpha, const LevelConsts& lc, double d) {
-  float u = __builtin_fmaf(v, lc.c1, lc.c0);
-  u = fminf(fmaxf(u, 0.0f), lc.lmax);
-  float rf = rintf(u);
-  if (!(fabsf(u - rf) < 0.4998f)) {
-    double r;
-    disc64((double)v, alpha, -1.0, 1.0, d, &r);
-    rf = (float)r;
-  }
-  return rf;
-}
-
 // Four consecutive weights: 16-byte accesses, one (row, column) split with 32-bit arithmetic, and the level index from
-// proj_level.
+// the screen of fp_level.h (levels on [-1, 1]).
 __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const float* wstar, double alpha, float alpha32,
                                             const LevelConsts& lc, double d, float* G, float* dual, float dual_div,
                                             int8_t* Gq, int lm1, const ProjNext& nx) {
@@ -68,9 +31,9 @@ __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const fl
   int ri[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const float rf = proj_level(ve[e], alpha, lc, d);
+    const float rf = fp_level_f(ve[e], lc, alpha, -1.0, 1.0, d);
     ri[e] = (int)rf;
-    const float b = (float)((double)rf * d + -1.0);       // disc64's r * d + lo
+    const float b = (float)((double)rf * d + -1.0);       // r * d + lo
     ge[e] = alpha32 * b;
     float t = (we[e] - ge[e]) + de[e];                    // EfficientQConv.py:111
     if (dual_div != 1.0f) t = t / dual_div;               // "dual /= 2" or "dual /= rho_m/rho" (:131-136)
@@ -111,7 +74,7 @@ __device__ __forceinline__ void proj1_apply(size_t i, unsigned r, unsigned k, fl
                                             float* dual, float dual_div, const ProjNext& nx) {
   float g = 0.0f;
   if (!zero_row) {
-    const float b = (float)((double)proj_level(v, alpha, lc, d) * d + -1.0);
+    const float b = (float)((double)fp_level_f(v, lc, alpha, -1.0, 1.0, d) * d + -1.0);
     g = alpha32 * b;
   }
   float t = (wstar[i] - g) + dual[i];                     // EfficientQConv.py:111

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "fp_level.h"
+#include "internal.h"
 #include "project_dual.h"
 
 namespace effq {
@@ -38,6 +39,13 @@ __device__ __forceinline__ float qd32(float x, float alpha, float lo, float hi, 
   return (r * d + lo) * alpha;
 }
 
+// discretize (layer_helper.py:25-37) in fp64: the exact level of fp_level.h and its value r d + lo
+__device__ __forceinline__ double disc64(double x, double alpha, double lo, double hi, double d, double* idx) {
+  const double r = level_exact(x, alpha, lo, hi, d);
+  *idx = r;
+  return r * d + lo;
+}
+
 // Same level index as disc64 (bit-exact), without the two IEEE fp64 divisions on the common path: the
 // quotient is formed with reciprocals (a few ulp off) and accepted only when it is provably on the same
 // side of every rounding boundary as the exact one; otherwise the exact divisions are redone.
@@ -57,11 +65,8 @@ __device__ __forceinline__ double disc64_fast(double x, double alpha, double ral
   return disc64(x, alpha, lo, hi, d, idx);
 }
 
-// Statistics of one fixed-point pass without per-value fp64 arithmetic beyond one multiply-add: b = r d + lo depends on
-// the level index r alone, so  sum b x = d sum(r x) + lo sum(x)  and  sum b^2 = d^2 sum(r^2) + 2 d lo sum(r) + lo^2 n,
-// with sum(r), sum(r^2) exact integers and r x exact in fp64.  r comes from an fp32 evaluation of u = (x/alpha - lo)/d
-// (error <= 3e-5 at 256 levels), accepted unless u lies within 2e-4 of a rounding boundary, where the reference's own
-// fp64 arithmetic (disc64) decides: the level indices are exactly the reference's.
+// Statistics of one fixed-point pass without per-value fp64 arithmetic beyond one multiply-add: the level index r from the
+// fp32 screen (fp_level.h), exactly the reference's, and integer tallies from which level_sum_bv / _bb form sum b x, sum b^2.
 // four doubles of scratch in the tail of the reduction workspace (after the ticket and the cooperative kernel's two
 // counter words at +64 / +68): the raw totals of a level-statistics pass before level_finish
 __device__ __forceinline__ double* level_scratch(double* partials) {
@@ -71,25 +76,26 @@ struct LevelStats {
   double arx, sx;          // sum r x, sum x (sx only when lo != 0)
   long long sr, sr2;       // sum r, sum r^2
 };
-__device__ __forceinline__ void level_accum(float xf, const LevelConsts& c, LevelStats& a) {
-  float u = __builtin_fmaf(xf, c.c1, c.c0);
-  u = fminf(fmaxf(u, 0.0f), c.lmax);
-  float rf = rintf(u);
-  if (!(fabsf(u - rf) < 0.4998f)) {
-    double r;
-    disc64((double)xf, c.alpha, c.lo, c.hi, c.d, &r);
-    rf = (float)r;
-  }
+struct LevelPass {         // the scale and the level grid of a pass
+  LevelConsts c;
+  double alpha, lo, hi, d;
+  bool need_sx;
+};
+__device__ __forceinline__ LevelPass level_pass(double alpha, double lo, double hi, double d) {
+  return {level_consts(alpha, lo, hi, d), alpha, lo, hi, d, lo != 0.0};
+}
+__device__ __forceinline__ void level_accum(float xf, const LevelPass& p, LevelStats& a) {
+  const float rf = fp_level_f(xf, p.c, p.alpha, p.lo, p.hi, p.d);
   const int ri = (int)rf;
   a.sr += ri;
   a.sr2 += ri * ri;
   a.arx = __builtin_fma((double)rf, (double)xf, a.arx);
-  if (c.need_sx) a.sx += (double)xf;
+  if (p.need_sx) a.sx += (double)xf;
 }
 // [sum r x, sum r, sum r^2, sum x] over n values -> [sum b x, sum b b]
 __device__ __forceinline__ void level_finish(const double* t4, size_t n, double lo, double d, double* out2) {
-  out2[0] = d * t4[0] + lo * t4[3];
-  out2[1] = (d * d * t4[2] + 2.0 * d * lo * t4[1]) + lo * lo * (double)n;
+  out2[0] = level_sum_bv(t4[0], t4[3], lo, d);
+  out2[1] = level_sum_bb(t4[2], t4[1], n, lo, d);
 }
 
 __global__ __launch_bounds__(TPB) void k_quant_dequant_f32(const float* __restrict__ x,
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(TPB) void k_reduce(const float* __restrict__ x, siz
 #pragma unroll
   for (int s = 0; s < NS; ++s) acc[s] = 0.0;
   LevelStats ls = {0.0, 0.0, 0, 0};
-  LevelConsts lc = level_consts((MODE == 2) ? *alpha_dev : 1.0, lo, hi, (MODE == 2) ? d : 1.0);
+  const LevelPass lp = level_pass((MODE == 2) ? *alpha_dev : 1.0, lo, hi, (MODE == 2) ? d : 1.0);
   const size_t nv = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   auto body = [&](float xf) {
@@ -183,7 +189,7 @@ __global__ __launch_bounds__(TPB) void k_reduce(const float* __restrict__ x, siz
       acc[0] += v;
       acc[1] += v * v;
     } else {
-      level_accum(xf, lc, ls);
+      level_accum(xf, lp, ls);
     }
   };
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
@@ -216,18 +222,19 @@ __global__ __launch_bounds__(TPB) void k_fp_iter(const float* __restrict__ x, si
   __shared__ int s_last;
   if (st->done != 0) return;  // uniform across the grid
   const double alpha = st->alpha;
-  const LevelConsts lc = level_consts(alpha, lo, hi, d);
+  const LevelPass lp = level_pass(alpha, lo, hi, d);
   LevelStats ls = {0.0, 0.0, 0, 0};
   const size_t nv = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
-    level_accum(v.x, lc, ls);
-    level_accum(v.y, lc, ls);
-    level_accum(v.z, lc, ls);
-    level_accum(v.w, lc, ls);
+    level_accum(v.x, lp, ls);
+    level_accum(v.y, lp, ls);
+    level_accum(v.z, lp, ls);
+    level_accum(v.w, lp, ls);
   }
-  for (size_t i = nv * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) level_accum(x[i], lc, ls);
+  for (size_t i = nv * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    level_accum(x[i], lp, ls);
   double acc[4] = {ls.arx, (double)ls.sr, (double)ls.sr2, ls.sx};
   double* t4 = level_scratch(partials);
   grid_sum_finish<4>(acc, partials, ticket, t4, smem, &s_last);
@@ -239,10 +246,7 @@ __global__ __launch_bounds__(TPB) void k_fp_iter(const float* __restrict__ x, si
     st->alpha = a_new;
     const int it = st->iters + 1;
     st->iters = it;
-    if (it >= max_iter)
-      st->done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      st->done = 1;
+    fp_stop(it, max_iter, a_new, alpha, tol, st->done);
   }
 }
 
@@ -256,13 +260,10 @@ constexpr int FPS_T = 1024;
 // runs ~300 iterations per ADMM iteration: the per-iteration latency (2.2 us with three barriers) is what counts.
 // PER = register slots per thread (compile time, so the element loop is branch-free and the fp64 chains of the
 // slots interleave).
-// Arithmetic per value: b = r d + lo is a function of the level index r alone, so
-//   sum b v = d sum(r v) + lo sum(v),   sum b^2 = d^2 sum(r^2) + 2 d lo sum(r) + lo^2 n
-// with sum(r), sum(r^2) exact integers and r v exact in fp64: per value ONE fp64 multiply-add instead of the ~16 fp64
-// operations of disc64_fast + two accumulations (fp64 min/max/rint/floor issue at a fraction of the fp32 rate; at 256
-// levels the first conv's weight scale takes ~290 iterations per ADMM iteration).  r comes from an fp32 evaluation of
-// u = (v/alpha - lo)/d (error <= 3e-5 at 256 levels) and is accepted when u is not within 2e-4 of a rounding boundary;
-// otherwise (2e-4 of the values) the reference's own fp64 arithmetic (disc64) decides: the level indices are exact.
+// Arithmetic per value: the level index r from the fp32 screen (fp_level.h: exact), integer tallies of r and r^2 and
+// sum(r v), exact in fp64, from which level_sum_bv / _bb form sum b v and sum b^2: per value ONE fp64 multiply-add instead of
+// the ~16 fp64 operations of disc64_fast + two accumulations (fp64 min/max/rint/floor issue at a fraction of the fp32
+// rate; at 256 levels the first conv's weight scale takes ~290 iterations per ADMM iteration).
 template <int T, int PER>
 __global__ __launch_bounds__(T) void k_fp_small(const float* __restrict__ a, const float* b2, float* v_out, size_t n,
                                                 effq_fp_state* st, double lo, double hi, double d, double tol,
@@ -308,11 +309,10 @@ __global__ __launch_bounds__(T) void k_fp_small(const float* __restrict__ a, con
   double last0 = 0.0, last1 = 0.0;
   int it = 0, done = 0;
   const double rd = 1.0 / d;
-  const float c0 = (float)(-lo * rd), lmax = (float)rint((hi - lo) * rd);
-  const double lo_sv = lo * sv, lo2n = lo * lo * (double)n, d2 = d * d, dlo2 = 2.0 * d * lo;
+  LevelConsts lc = level_grid(lo, hi, d);
   while (!done) {
     const int par = (it + 1) & 1;            // parity 0 carried the prologue sums
-    const float c1 = (float)(ralpha * rd);
+    lc.c1 = (float)(ralpha * rd);
     double arv = 0.0;
     int sr = 0, sr2 = 0;                     // <= 32 slots x 255^2 per thread
 #pragma unroll
@@ -321,14 +321,7 @@ __global__ __launch_bounds__(T) void k_fp_small(const float* __restrict__ a, con
       // (uniform) branch per slot; (a branch-free common path with the exact fallback hoisted out measured slower)
       if (T < 1024 || k < kmax) {
         const float vf = vr[k];
-        float u = __builtin_fmaf(vf, c1, c0);
-        u = fminf(fmaxf(u, 0.0f), lmax);
-        float rf = rintf(u);
-        if (!(fabsf(u - rf) < 0.4998f)) {    // within 2e-4 of a rounding boundary (or NaN): exact arithmetic decides
-          double r;
-          disc64((double)vf, alpha, lo, hi, d, &r);
-          rf = (float)r;
-        }
+        const float rf = fp_level_f(vf, lc, alpha, lo, hi, d);
         const int ri = ((live >> k) & 1u) ? (int)rf : 0;      // dead slots hold v = 0: they must not count
         sr += ri;
         sr2 += ri * ri;
@@ -350,29 +343,19 @@ __global__ __launch_bounds__(T) void k_fp_small(const float* __restrict__ a, con
       tr += part[par][1][w];
       tr2 += part[par][2][w];
     }
-    const double t0 = d * trv + lo_sv;                         // sum b v
-    const double t1 = (d2 * tr2 + dlo2 * tr) + lo2n;           // sum b^2
+    const double t0 = level_sum_bv(trv, sv, lo, d);   // sum b v
+    const double t1 = level_sum_bb(tr2, tr, n, lo, d);   // sum b^2
     const double a_new = t0 / t1;
     const double ra_new = t1 / t0;           // independent of the division above (pipelines with it)
     ++it;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
+    fp_stop(it, max_iter, a_new, alpha, tol, done);
     alpha_prev = alpha;
     alpha = a_new;
     ralpha = ra_new;
     last0 = t0;
     last1 = t1;
   }
-  if (tid == 0) {
-    st->alpha = alpha;
-    st->alpha_prev = alpha_prev;
-    st->sums[0] = last0;
-    st->sums[1] = last1;
-    st->iters = it;
-    st->done = done;
-  }
+  if (tid == 0) fp_state_store(st, alpha, alpha_prev, last0, last1, it, done);
   if (pf.G != nullptr) {                       // the projection + dual update of this ADMM iteration, same launch
     __syncthreads();                           // v_out of every thread is in place
     proj_fused_epilogue(pf, v_out, alpha, done, tid, T);
@@ -530,27 +513,18 @@ __global__ __launch_bounds__(T) void k_fp_coop(const float* __restrict__ a, cons
   double alpha = tot / (double)n, alpha_prev = -999.0;
   int it = 0, done = 0;
   double last0 = 0.0, last1 = 0.0;
-  // per value: level index r from an fp32 evaluation (exact fp64 arithmetic within 2e-4 of a rounding boundary), then
-  // sum b v = d sum(r v) + lo sum(v), sum b^2 = d^2 sum(r^2) + 2 d lo sum(r) + lo^2 n (see k_fp_small)
+  // per value: level index r from the fp32 screen, then sum b v and sum b^2 from the tallies (see k_fp_small)
   const double rd = 1.0 / d;
-  const float c0 = (float)(-lo * rd), lmax = (float)rint((hi - lo) * rd);
-  const double lo_sv = lo * sv, lo2n = lo * lo * (double)n, d2 = d * d, dlo2 = 2.0 * d * lo;
+  LevelConsts lc = level_grid(lo, hi, d);
   while (!done) {
     const int par = (it + 1) & 1;          // parity 0 was used by the abs-sum epoch
     if (wg == 0 && tid == 0) fpt_note(pred, it, alpha);      // (seeds the next call's predictions: fixed_point_traj.hip)
-    const float c1 = (float)((1.0 / alpha) * rd);
+    lc.c1 = (float)((1.0 / alpha) * rd);
     double arv = 0.0;
     long long sr = 0, sr2 = 0;
     for (int i = tid; i < cnt; i += T) {
       const float vf = vs[i];
-      float u = __builtin_fmaf(vf, c1, c0);
-      u = fminf(fmaxf(u, 0.0f), lmax);
-      float rf = rintf(u);
-      if (!(fabsf(u - rf) < 0.4998f)) {
-        double r;
-        disc64((double)vf, alpha, lo, hi, d, &r);
-        rf = (float)r;
-      }
+      const float rf = fp_level_f(vf, lc, alpha, lo, hi, d);
       const int ri = (int)rf;
       sr += ri;
       sr2 += ri * ri;
@@ -569,31 +543,17 @@ __global__ __launch_bounds__(T) void k_fp_coop(const float* __restrict__ a, cons
     }
     double trv = 0.0, tr = 0.0, tr2 = 0.0;
     combine(par, trv, tr, tr2);
-    const double t0 = d * trv + lo_sv;                         // sum b v
-    const double t1 = (d2 * tr2 + dlo2 * tr) + lo2n;           // sum b^2
+    const double t0 = level_sum_bv(trv, sv, lo, d);   // sum b v
+    const double t1 = level_sum_bb(tr2, tr, n, lo, d);   // sum b^2
     const double a_new = t0 / t1;
     alpha_prev = alpha;
     ++it;
-    if (it >= max_iter)
-      done = 2;
-    else if (!(fabs(a_new - alpha) > tol))
-      done = 1;
+    fp_stop(it, max_iter, a_new, alpha_prev, tol, done);
     alpha = a_new;
     last0 = t0;
     last1 = t1;
   }
-  if (wg == 0 && tid == 0) {
-    st->alpha = alpha;
-    st->alpha_prev = alpha_prev;
-    st->sums[0] = last0;
-    st->sums[1] = last1;
-    st->iters = it;
-    st->done = done;
-    if (pred != nullptr) {
-      for (int j = 0; j < FPT_SLOTS; ++j) fpt_finish_slot(pred, j, it, alpha);
-      fpt_finish_head(pred, it, tot, levels);
-    }
-  }
+  if (wg == 0 && tid == 0) fp_state_finish(st, pred, alpha, alpha_prev, last0, last1, it, done, tot, levels);
   // leave the barrier counter at zero for the next launch: every workgroup is past its last poll when it gets
   // here, so the last one to check out (counter[1]) resets both words - no memset command per call.  (After a
   // barrier time-out the early returns above skip this; the host then sees done = 3 and raises.)
@@ -626,11 +586,7 @@ __global__ void k_fp_update(effq_fp_state* st, double tol, int max_iter) {
   st->alpha_prev = st->alpha;
   st->alpha = a_new;
   st->iters += 1;
-  // the reference raises whenever c == max_iter, even if that last step converged (:62-64)
-  if (st->iters >= max_iter)
-    st->done = 2;
-  else if (!(fabs(st->alpha - st->alpha_prev) > tol))
-    st->done = 1;
+  fp_stop(st->iters, max_iter, st->alpha, st->alpha_prev, tol, st->done);
 }
 
 __global__ __launch_bounds__(TPB) void k_presum(const float* __restrict__ a, const float* __restrict__ b,
@@ -672,8 +628,8 @@ __global__ __launch_bounds__(TPB) void k_project_dual(const float* __restrict__ 
 }
 
 // Four consecutive weights per thread (weight rows that are a multiple of 4 long: every layer of the shipped nets): 16-byte
-// accesses, one (row, column) split per thread with 32-bit arithmetic, and the level index from the fp32 evaluation of
-// level_accum (the reference's fp64 arithmetic decides within 2e-4 of a rounding boundary: indices are exact).
+// accesses, one (row, column) split per thread with 32-bit arithmetic, and the level index from the fp32 screen of
+// fp_level.h (the reference's fp64 arithmetic decides within 2e-4 of a rounding boundary: indices are exact).
 __global__ __launch_bounds__(TPB) void k_project_dual4(const float* __restrict__ v, const float* __restrict__ wstar,
                                                        const effq_fp_state* __restrict__ st, double d,
                                                        float* __restrict__ G, float* __restrict__ dual,
@@ -855,8 +811,6 @@ int effq_alpha_fixed_point(const float* x, size_t n, int levels, double lo, doub
 }
 
 size_t effq_fp_small_max(void) { return (size_t)1 << 15; }
-int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
-                                 double tol, int max_iter, effq_fp_state* state_dev, const ProjFused* pf_in, void* stream);
 
 int effq_fixed_point_small(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
                            double tol, int max_iter, effq_fp_state* state_dev, void* stream) {
@@ -949,8 +903,7 @@ int effq_fixed_point_coop_rec(const float* a, const float* b, float* v_out, size
   static bool known[64] = {};
   static int resident_max[64];
   if (!known[dev]) {
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fp_coop<FPC_T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(FPC_SLICE * sizeof(float))));
+    EFFQ_HIP(raise_lds_limit<k_fp_coop<FPC_T>>(FPC_SLICE * sizeof(float)));
     int ncu = 0, per_cu = 0;
     EFFQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     EFFQ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fp_coop<FPC_T>, FPC_T, FPC_SLICE * sizeof(float)));

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 #include "common.h"
+#include "internal.h"
 
 namespace effq {
 
@@ -1328,14 +1329,9 @@ int effq_spd_inverse(const float* A0, int n, int has_bias, double rho, double et
     EFFQ_LAUNCH_CHECK();
   }
   const size_t lds = (size_t)(NBK * LDA_S + NBK * LDB_S) * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gj_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gj_panel_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gj_pivot_fused), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)((2 * NBK * PF_LD + 2 * (NBK + 1)) * sizeof(double))));
-    attr_set = true;
-  }
+  EFFQ_HIP(raise_lds_limit<k_gj_panel>(lds));
+  EFFQ_HIP(raise_lds_limit<k_gj_panel_w>(lds));
+  EFFQ_HIP(raise_lds_limit<k_gj_pivot_fused>((2 * NBK * PF_LD + 2 * (NBK + 1)) * sizeof(double)));
   const int rc = (npad / NBK >= GJ_WIDE_MIN_BLOCKS) ? gj_wide_sweep(A64, npad, aux, st) : gj64_sweep(A64, npad, aux, st);
   if (rc != EFFQ_OK) return rc;
   {
@@ -1394,17 +1390,8 @@ static int prox_solve_impl(const float* B0, const float* Ainv, const float* W0, 
     if (pl.variant == 5 || pl.variant == 7) {
       const size_t lds5 = (size_t)2 * 3 * (256 + 256) * B3_LD * sizeof(__bf16);      // two stages
       const size_t lds7 = (size_t)2 * 3 * (128 + 128) * B3_LD * sizeof(__bf16);
-      static bool attr5[64] = {};
-      int dev5 = 0;
-      EFFQ_HIP(hipGetDevice(&dev5));
-      EFFQ_CHECK_ARG(dev5 >= 0 && dev5 < 64);
-      if (!attr5[dev5]) {
-        EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prox_gemm_b3<256, 256, 4, 2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
-        EFFQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prox_gemm_b3<128, 128, 2, 4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7));
-        attr5[dev5] = true;
-      }
+      EFFQ_HIP((raise_lds_limit<k_prox_gemm_b3<256, 256, 4, 2>>(lds5)));
+      EFFQ_HIP((raise_lds_limit<k_prox_gemm_b3<128, 128, 2, 4>>(lds7)));
       if (pl.variant == 5)
         hipLaunchKernelGGL((k_prox_gemm_b3<256, 256, 4, 2>), grid, dim3(512), lds5, st, Bm, ldb, Ainv, lda, n, c2,
                            has_bias ? 1 : 0, wstar, bstar, part, ldb);
@@ -1480,9 +1467,5 @@ int effq_prox_solve_shifted(const float* B0, const float* Ainv, const float* W0,
   return prox_solve_impl(B0, Ainv, W0, b0, G, dual, c2, n, has_bias, rho, eta, rho_inv - rho, nterms, wstar, bstar, ws,
                          ws_bytes, stream);
 }
-
-int effq_project_dual_checked(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
-                              float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
-                              void* stream);   // quant_reduce.hip (internal to the library)
 
 }  // extern "C"
