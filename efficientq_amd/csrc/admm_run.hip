@@ -11,6 +11,7 @@
 // the best iterate is picked AFTER the loop (effq_admm_select_best), which is what lets a data-parallel caller
 // all-reduce the whole history with one collective per layer instead of one per iteration.
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 #include "common.h"
 #include "internal.h"
@@ -178,27 +179,23 @@ __global__ __launch_bounds__(256) void k_admm_residuals(const float* __restrict_
   if (threadIdx.x < 2) atomicAdd(res + threadIdx.x, (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]));
 }
 
-}  // namespace effq
-using namespace effq;
-
-extern "C" {
-
-// whether effq_admm_run would use effq_fixed_point_traj for a layer of nw weights at w_levels levels (the caller then
-// provides fp_pred / fp_traj_ws; otherwise both may be NULL)
-int effq_admm_uses_traj(size_t nw, int w_levels) {
-  constexpr int traj_levels = 4;          // see the measurements in effq_admm_run
-  constexpr size_t traj_min = 65536;
-  return (w_levels <= traj_levels && nw >= traj_min && nw <= effq_fp_traj_max()) ? 1 : 0;
-}
-
-int effq_admm_num_inverses(double rho, double rho_max, int iters, int period) {
-  if (!(rho > 0.0) || iters <= 0 || period <= 0) return -1;
-  const RhoPlan p = plan_rhos(rho, rho_max, iters, period);
-  if (p.overflow) return -1;
-  return p.count - (p.shifted_first ? 1 : 0);
-}
-
-int effq_admm_run(const effq_admm_run_args* a) {
+struct AdmmPlan {                  // what effq_admm_run decides once per layer
+  int c2, n, has_b;
+  size_t nw;                       // weights, c2 x (n - has_b)
+  RhoPlan rhos;
+  int first, n_inv;                // the n_inv inverses in ainv_pool are those of rhos.rho[first ...]
+  size_t ainv_elems;               // floats per inverse
+  bool chan, bucket, traj;         // channel mode; whether the bucketed / the trajectory fixed point may run
+  int traj_after;                  // iterations after a change of rho before the trajectory fixed point
+  hipStream_t s_main, s_loss, s_side, s_side2;
+  bool fork_loss, fork_side, two_sides;
+  int side_iter;                   // the iteration that enqueues the later inverses first (-1: there are none)
+  int loss_group;                  // iterates the loss stream picks up at a time
+  float* bm;                       // Bm, the right-hand side of the prox solve (start of prox_ws), rows of bm_ld
+  int bm_ld;
+};
+// The argument and workspace checks, then the plan.  No HIP call: a rejected run has enqueued nothing.
+static int admm_plan(const effq_admm_run_args* a, AdmmPlan* p) {
   EFFQ_CHECK_ARG(a != nullptr);
   EFFQ_CHECK_ARG(a->A0 && a->B0 && a->W0 && a->dual && a->wstar && a->v && a->G_ring && a->state_ring && a->hist &&
                  a->err_flag && a->ainv_pool && a->prox_ws && a->red_ws && a->inv_ws && a->conv_ws && a->y_fp);
@@ -214,16 +211,18 @@ int effq_admm_run(const effq_admm_run_args* a) {
   else
     EFFQ_CHECK_ARG(a->loss_kind == 0 ? (a->xq != nullptr) : (a->xidx != nullptr && a->Gq_ring != nullptr &&
                                                             a->act_alpha_dev != nullptr));
-  const int c2 = a->c2, n = a->n, has_b = a->has_bias ? 1 : 0;
-  const size_t nw = (size_t)c2 * (size_t)(n - has_b);
+  p->c2 = a->c2;
+  p->n = a->n;
+  p->has_b = a->has_bias ? 1 : 0;
+  const size_t nw = p->nw = (size_t)p->c2 * (size_t)(p->n - p->has_b);
   EFFQ_CHECK_ARG(nw == (size_t)a->geom.C2 * a->geom.C1 * a->geom.KD * a->geom.KH * a->geom.KW);
   // channel mode: one scale per output row (effq_fixed_point_channels_proj).  The integer loss paths fold ONE scalar scale
   // into their arithmetic (conv3d_i8*.hip epilogues, effq_gram_loss_i8's integer Q): only the losses that take G as fp32
   // values are accepted
-  const bool chan = a->channel_wise != 0;
-  if (chan)
+  p->chan = a->channel_wise != 0;
+  if (p->chan)
     EFFQ_CHECK_ARG((a->loss_kind == 0 || a->loss_kind == 4) && a->alpha_ring != nullptr &&
-                   n - has_b <= effq_fp_channels_max_row());
+                   p->n - p->has_b <= effq_fp_channels_max_row());
   if (nw > effq_fp_coop_max()) {
     set_error("admm_run: %zu weights exceed the single-launch fixed points", nw);
     return EFFQ_ERR_ARG;
@@ -233,8 +232,8 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // 1.77 M 171 / 163 alone but slower inside the loop (1261 vs 1224 ms per calibration); at 256 levels the all-values
   // kernels win at every size)
   constexpr size_t bucket_max = (size_t)1 << 19;
-  const bool bucket = !chan && a->fp_ws != nullptr && a->w_levels <= 16 && nw > 4096 && nw <= bucket_max;
-  if (bucket && a->fp_ws_bytes < effq_fp_bucket_ws_bytes(nw)) {
+  p->bucket = !p->chan && a->fp_ws != nullptr && a->w_levels <= 16 && nw > 4096 && nw <= bucket_max;
+  if (p->bucket && a->fp_ws_bytes < effq_fp_bucket_ws_bytes(nw)) {
     set_error("admm_run: fixed-point workspace %zu < %zu", a->fp_ws_bytes, effq_fp_bucket_ws_bytes(nw));
     return EFFQ_ERR_WORKSPACE;
   }
@@ -247,347 +246,346 @@ int effq_admm_run(const effq_admm_run_args* a) {
   // their iterates behind.  (At 16 levels the fixed point takes ~50 iterations: the one hull slot for everything past the
   // seventh keeps a third of the values on the list, and the older kernels are faster - measured, scripts/prof_fp_traj.py;
   // hence at most 4 levels, effq_admm_uses_traj.)
-  const int traj_after = (nw > ((size_t)1 << 20)) ? 30 : 12;
-  const bool traj = !chan && a->fp_pred != nullptr && a->fp_traj_ws != nullptr && effq_admm_uses_traj(nw, a->w_levels) != 0;
-  if (traj && a->fp_traj_ws_bytes < effq_fp_traj_ws_bytes(nw)) {
+  p->traj_after = (nw > ((size_t)1 << 20)) ? 30 : 12;
+  p->traj = !p->chan && a->fp_pred != nullptr && a->fp_traj_ws != nullptr && effq_admm_uses_traj(nw, a->w_levels) != 0;
+  if (p->traj && a->fp_traj_ws_bytes < effq_fp_traj_ws_bytes(nw)) {
     set_error("admm_run: trajectory fixed-point workspace %zu < %zu", a->fp_traj_ws_bytes, effq_fp_traj_ws_bytes(nw));
     return EFFQ_ERR_WORKSPACE;
   }
-  const RhoPlan plan = plan_rhos(a->rho, a->rho_max, a->iters, a->rho_period);
-  EFFQ_CHECK_ARG(!plan.overflow);
-  const int first = plan.shifted_first ? 1 : 0;
-  const int n_inv = plan.count - first;
-  EFFQ_CHECK_ARG(a->n_ainv >= n_inv);
-  const size_t ainv_elems = (size_t)n * (size_t)effq_ainv_ld(n);
-
-  hipStream_t s_main = as_stream(a->stream_main);
-  hipStream_t s_loss = a->stream_loss ? as_stream(a->stream_loss) : s_main;
-  hipStream_t s_side = (a->stream_side && a->inv_ws_side) ? as_stream(a->stream_side) : s_main;
-  const bool fork_loss = s_loss != s_main, fork_side = s_side != s_main;
+  p->rhos = plan_rhos(a->rho, a->rho_max, a->iters, a->rho_period);
+  EFFQ_CHECK_ARG(!p->rhos.overflow);
+  p->first = p->rhos.shifted_first ? 1 : 0;
+  p->n_inv = p->rhos.count - p->first;
+  EFFQ_CHECK_ARG(a->n_ainv >= p->n_inv);
+  p->ainv_elems = (size_t)p->n * (size_t)effq_ainv_ld(p->n);
+  p->s_main = as_stream(a->stream_main);
+  p->s_loss = a->stream_loss ? as_stream(a->stream_loss) : p->s_main;
+  p->s_side = (a->stream_side && a->inv_ws_side) ? as_stream(a->stream_side) : p->s_main;
+  p->fork_loss = p->s_loss != p->s_main;
+  p->fork_side = p->s_side != p->s_main;
   // a second side stream: the later inverses alternate between the two (a Gauss-Jordan sweep is a chain of ~100 dependent
   // launches with serial pivot phases: two sweeps side by side fill each other's bubbles, and the last inverse of a wide
   // layer is ready before the chain reaches the iteration that needs it)
-  hipStream_t s_side2 = (fork_side && a->stream_side2 && a->inv_ws_side2) ? as_stream(a->stream_side2) : s_side;
-  const bool two_sides = s_side2 != s_side;
+  p->s_side2 = (p->fork_side && a->stream_side2 && a->inv_ws_side2) ? as_stream(a->stream_side2) : p->s_side;
+  p->two_sides = p->s_side2 != p->s_side;
+  // The later inverses (side stream) are ENQUEUED a few iterations into the loop: their ~30 - 650 launches take the host
+  // 0.2 - 2.6 ms, during which the main stream - done with its own inverse on the small layers - had nothing queued (under
+  // a profiler, at 3 x the launch cost, 6 ms per layer); the side stream still starts at the fork.  They are queued before
+  // the iteration that uses the first of them, and at once without a side stream (they then run on the main stream).
+  // (plan_rhos records first_iter only below iters, and first_iter[first + 1] >= 1: side_iter lies in [0, iters - 1], the
+  // first iteration that met the condition the loop tested before, so no enqueue is left for after the loop.)
+  constexpr int SIDE_AFTER_ITERS = 8;
+  p->side_iter = p->n_inv <= 1 ? -1 : !p->fork_side ? 0 : std::min(SIDE_AFTER_ITERS, p->rhos.first_iter[p->first + 1] - 1);
+  // loss group size: the last group is evaluated after the chain has finished (it delays the join by one group of
+  // losses), so the cheap losses from the Gram system travel in larger groups than the conv passes.  EFFQ_LOSS_GROUP
+  // overrides the Gram group (bench.py's model reads it too)
+  static const int group_gram = getenv("EFFQ_LOSS_GROUP") ? atoi(getenv("EFFQ_LOSS_GROUP")) : 8;
+  constexpr int group_conv = 4;
+  const int group_size = (a->loss_kind == 4 || a->loss_kind == 5) ? group_gram : group_conv;
+  p->loss_group = (p->fork_loss && group_size > 1) ? group_size : 1;
+  p->bm = effq_prox_bm(a->prox_ws, p->c2, p->n, &p->bm_ld);
+  return EFFQ_OK;
+}
 
-  // events: one per inverse formed on the side stream, a small pool for main -> loss, one each for the joins.  They
-  // come from a per-thread, per-device pool that is never destroyed (a wait captures the record that precedes it, so
-  // an event may be re-recorded by the next call while an older wait on it is still queued).
-  constexpr int EV_POOL = 4;
-  int dev_id = 0;
-  EFFQ_HIP(hipGetDevice(&dev_id));
-  static thread_local std::vector<std::vector<hipEvent_t>> g_events;
-  if ((int)g_events.size() <= dev_id) g_events.resize(dev_id + 1);
-  std::vector<hipEvent_t>& pool = g_events[dev_id];
-  size_t pool_used = 0;
-  auto new_event = [&](hipEvent_t* e) -> hipError_t {
-    if (pool_used == pool.size()) {
+// The events of one run: the fork, one per inverse formed on a side stream, a few for main -> loss, one per join.  They
+// come from a per-thread, per-device pool that is never destroyed (a wait captures the record that precedes it, so an
+// event may be re-recorded by the next run while an older wait on it is still queued).
+struct EventPool {
+  std::vector<hipEvent_t>* pool = nullptr;
+  size_t used = 0;
+  hipError_t open() {              // the calling thread's pool of the current device
+    static thread_local std::vector<std::vector<hipEvent_t>> per_device;
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && (int)per_device.size() <= dev) per_device.resize(dev + 1);
+    if (e == hipSuccess) pool = &per_device[dev];
+    return e;
+  }
+  hipError_t take(hipEvent_t* ev) {
+    if (used == pool->size()) {
       hipEvent_t fresh;
-      hipError_t rc = hipEventCreateWithFlags(&fresh, hipEventDisableTiming);
-      if (rc != hipSuccess) return rc;
-      pool.push_back(fresh);
+      const hipError_t e = hipEventCreateWithFlags(&fresh, hipEventDisableTiming);
+      if (e != hipSuccess) return e;
+      pool->push_back(fresh);
     }
-    *e = pool[pool_used++];
+    *ev = (*pool)[used++];
     return hipSuccess;
-  };
-  auto destroy_events = [&]() {};
-#define ADMM_HIP(call)                                                                        \
-  do {                                                                                        \
-    hipError_t e_ = (call);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      effq::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_));     \
-      destroy_events();                                                                       \
-      return EFFQ_ERR_HIP;                                                                    \
-    }                                                                                         \
-  } while (0)
-#define ADMM_RC(call)          \
-  do {                         \
-    int rc_ = (call);          \
-    if (rc_ != EFFQ_OK) {      \
-      destroy_events();        \
-      return rc_;              \
-    }                          \
-  } while (0)
+  }
+  // into waits for what is queued on from so far, through ev or, if that is NULL, an event taken from the pool
+  hipError_t hand_over(hipStream_t from, hipStream_t into, hipEvent_t ev = nullptr) {
+    hipError_t e = ev ? hipSuccess : take(&ev);
+    if (e == hipSuccess) e = hipEventRecord(ev, from);
+    return e == hipSuccess ? hipStreamWaitEvent(into, ev, 0) : e;
+  }
+};
 
-  hipEvent_t ev_inv[ADMM_MAX_RHOS] = {};
-  hipEvent_t ev_main[EV_POOL] = {};
-  hipEvent_t ev_fork = nullptr, ev_join_loss = nullptr, ev_join_side = nullptr;
+// The inverses of A(rho) for the later rho values, into ainv_pool; on a side stream each one records ev_inv[r].
+static int enqueue_later_inverses(const effq_admm_run_args* a, const AdmmPlan& p, EventPool& events, hipEvent_t* ev_inv) {
+  for (int r = p.first + 1; r < p.rhos.count; ++r) {
+    float* dst = a->ainv_pool + (size_t)(r - p.first) * p.ainv_elems;
+    const bool on2 = p.two_sides && ((r - p.first) % 2 == 0);   // first later inverse on side 1, the next on side 2 ...
+    hipStream_t sr = on2 ? p.s_side2 : p.s_side;
+    void* ws = !p.fork_side ? a->inv_ws : (on2 ? a->inv_ws_side2 : a->inv_ws_side);
+    const size_t wsb = !p.fork_side ? a->inv_ws_bytes : (on2 ? a->inv_ws_side2_bytes : a->inv_ws_side_bytes);
+    ProfScope ps(g_prof_every > 0, PROF_INVERSE, -1 - r, a, sr);
+    const int rc = effq_spd_inverse(a->A0, p.n, p.has_b, p.rhos.rho[r], a->eta, dst, ws, wsb, sr);
+    if (rc != EFFQ_OK) return rc;
+    ps.close();
+    if (p.fork_side) {
+      EFFQ_HIP(events.take(&ev_inv[r]));
+      EFFQ_HIP(hipEventRecord(ev_inv[r], sr));
+    }
+  }
+  return EFFQ_OK;
+}
 
-  ADMM_HIP(hipMemsetAsync(a->dual, 0, nw * sizeof(float), s_main));                 // dual <- 0 (EfficientQConv.py:40)
-  if (a->res_ring != nullptr) ADMM_HIP(hipMemsetAsync(a->res_ring, 0, 2 * (size_t)a->iters * sizeof(double), s_main));
-  if (traj) ADMM_HIP(hipMemsetAsync(a->fp_pred, 0, effq_fp_traj_pred_bytes(), s_main));   // nothing known about this layer
+struct AdmmIter {                  // iteration i: the rho it runs with and hands on, its slots of the rings
+  int i;
+  double rho, rho_next;
+  float dual_div;                  // the dual's rescale for rho_next
+  bool use_shift, use_traj, prof;  // use_shift: rho[0], solved through the inverse of A(rho[1])
+  bool next_rhs;                   // not the last iteration: the projection leaves the next prox right-hand side in Bm
+  const float* G_prev;
+  float *G, *bstar;
+  int8_t* Gq;
+  effq_fp_state* st;
+  const float* parts;              // set by enqueue_prox where it leaves the K slices of the product for the trajectory
+  int parts_n, parts_ld;           // kernel to add up in its prologue (one launch less); NULL: the product is whole
+};
+static AdmmIter admm_iter(const effq_admm_run_args* a, const AdmmPlan& p, int i, double rho, bool use_traj) {
+  const bool step = i % a->rho_period == 0, doubles = rho * 2 <= a->rho_max;   // rho changes after this iteration
+  const bool use_shift = p.rhos.shifted_first && i == 0;
+  const bool prof = g_prof_every > 0 && !use_shift && (i % g_prof_every) == g_prof_every / 2;
+  return AdmmIter{i, rho, !step ? rho : doubles ? rho * 2 : a->rho_max,
+                  !step ? 1.0f : doubles ? 2.0f : (float)(a->rho_max / rho), use_shift, use_traj, prof, i + 1 < a->iters,
+                  (i == 0) ? a->W0 : a->G_ring + (size_t)(i - 1) * p.nw, a->G_ring + (size_t)i * p.nw,
+                  p.has_b ? a->b_ring + (size_t)i * p.c2 : nullptr, a->Gq_ring ? a->Gq_ring + (size_t)i * p.nw : nullptr,
+                  a->state_ring + i, nullptr, 1, 0};
+}
+
+static int enqueue_prox(const effq_admm_run_args* a, const AdmmPlan& p, AdmmIter* it, const float* Ainv, bool bm_ready) {
+  if (!it->use_shift && bm_ready && it->use_traj && p.c2 <= 512)
+    return effq_prox_solve_prebuilt_parts(a->B0, Ainv, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho,
+                                          a->eta, a->wstar, it->bstar, a->prox_ws, a->prox_ws_bytes, p.s_main,
+                                          &it->parts, &it->parts_n, &it->parts_ld);
+  if (it->use_shift)
+    return effq_prox_solve_shifted(a->B0, a->ainv_pool, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho,
+                                   a->eta, p.rhos.rho[1], shift_terms(it->rho, a->eta, p.rhos.rho[1]), a->wstar, it->bstar,
+                                   a->prox_ws, a->prox_ws_bytes, p.s_main);
+  const auto solve = bm_ready ? effq_prox_solve_prebuilt : effq_prox_solve;   // Bm written by the last projection or not
+  return solve(a->B0, Ainv, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho, a->eta, a->wstar, it->bstar,
+               a->prox_ws, a->prox_ws_bytes, p.s_main);
+}
+
+enum class FpKind { channels, traj, bucket, small, coop };   // the weight-scale fixed point of an iteration
+static FpKind fp_kind(const AdmmPlan& p, bool use_traj) {
+  if (p.chan) return FpKind::channels;
+  if (use_traj) return FpKind::traj;
+  if (p.bucket) return FpKind::bucket;
+  return p.nw <= effq_fp_small_max() ? FpKind::small : FpKind::coop;
+}
+
+// The fixed point, then the projection + dual update, which also leaves the right-hand side of the NEXT prox solve in
+// Bm (the first solve of the layer builds Bm itself: bias column, padding).  *bm_ready: Bm holds it.
+static int enqueue_fixed_point(const effq_admm_run_args* a, const AdmmPlan& p, const AdmmIter& it, bool* bm_ready) {
+  const int nwrow = p.n - p.has_b;
+  const uintptr_t al16 = reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->wstar) |
+                         reinterpret_cast<uintptr_t>(it.G) | reinterpret_cast<uintptr_t>(a->dual) |
+                         (it.next_rhs ? (reinterpret_cast<uintptr_t>(a->W0) | reinterpret_cast<uintptr_t>(p.bm)) : 0);
+  const bool vec_ok = (al16 & 15) == 0 && (reinterpret_cast<uintptr_t>(it.Gq) & 3) == 0 && (p.nw % 4) == 0 &&
+                      (!it.next_rhs || ((nwrow % 4) == 0 && (p.bm_ld % 4) == 0));
+  const FpKind kind = fp_kind(p, it.use_traj);
+  // The projection as the EPILOGUE of a single-workgroup fixed point: one launch per iteration less.  Measured (us per
+  // iteration, fused against fixed point + projection): 2048 weights 13.8 against 12.2 + 7.1, 3456 at 256 levels 231.8
+  // against 229.3 + 8.3 - but 27648 weights on the bucketed kernel 56.3 against 33.6 + 7.1: only the 256 threads of its
+  // iteration phase are left for the epilogue.  So: the small kernel's layers (<= 32768 weights), and the channel kernel.
+  const bool fuse_proj = kind == FpKind::channels || (kind == FpKind::small && vec_ok);
+  ProjFused pf;                    // (the small kernel's epilogue)
+  memset(&pf, 0, sizeof(pf));
+  pf.wstar = a->wstar; pf.G = it.G; pf.dual = a->dual; pf.Gq = it.Gq; pf.err_flag = a->err_flag;
+  pf.d = 2.0 / (double)(a->w_levels - 1); pf.dual_div = it.dual_div; pf.lm1 = a->w_levels - 1;
+  pf.n4 = (unsigned)(p.nw / 4);
+  if (it.next_rhs) {
+    pf.nx.Bm = p.bm; pf.nx.B0 = a->B0; pf.nx.W0 = a->W0; pf.nx.nwrow = nwrow; pf.nx.n = p.n; pf.nx.ldb = p.bm_ld;
+    pf.nx.rho = (float)it.rho_next; pf.nx.eta = (float)a->eta;
+  }
+  void* rec = p.traj ? a->fp_pred : nullptr;
+  const int maxit = 100 * a->w_levels;
+  ProfScope p_fp(it.prof, PROF_FIXED_POINT, it.i, a, p.s_main);
+  int rc;
+  if (kind == FpKind::channels)       // every row's fixed point, projection, dual update and the next Bm in one launch
+    rc = effq_fixed_point_channels_proj(a->wstar, a->dual, a->v, p.c2, nwrow, a->w_levels, a->tol, maxit,
+                                        a->alpha_ring + (size_t)it.i * p.c2,
+                                        a->w_iters_ring ? a->w_iters_ring + (size_t)it.i * p.c2 : nullptr, a->err_flag,
+                                        it.G, it.dual_div, it.next_rhs ? p.bm : nullptr, a->B0, a->W0, p.n, p.bm_ld,
+                                        it.rho_next, a->eta, p.s_main);
+  else if (kind == FpKind::traj && it.parts != nullptr)
+    rc = effq_fixed_point_traj_parts(it.parts, it.parts_n, it.parts_ld, p.c2, nwrow, p.has_b, a->dual, a->wstar, it.bstar,
+                                     a->v, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st, a->fp_pred, a->fp_traj_ws,
+                                     a->fp_traj_ws_bytes, p.s_main);
+  else if (kind == FpKind::traj)
+    rc = effq_fixed_point_traj(a->wstar, a->dual, a->v, p.nw, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st, a->fp_pred,
+                               a->fp_traj_ws, a->fp_traj_ws_bytes, p.s_main);
+  else if (kind == FpKind::bucket)
+    rc = effq_fixed_point_bucket_rec(a->wstar, a->dual, a->v, p.nw, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st, a->fp_ws,
+                                     a->fp_ws_bytes, rec, p.s_main);
+  else if (kind == FpKind::small)
+    rc = effq_fixed_point_small_fused(a->wstar, a->dual, a->v, p.nw, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st,
+                                      fuse_proj ? &pf : nullptr, p.s_main);
+  else
+    rc = effq_fixed_point_coop_rec(a->wstar, a->dual, a->v, p.nw, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st, a->red_ws,
+                                   rec, p.s_main);
+  if (rc != EFFQ_OK) return rc;
+  p_fp.close();
+  *bm_ready = it.next_rhs;
+  if (fuse_proj) return EFFQ_OK;
+  ProfScope p_pr(it.prof, PROF_PROJECT, it.i, a, p.s_main);
+  if (it.next_rhs)
+    rc = effq_project_dual_next(a->v, a->wstar, it.st, a->w_levels, it.G, a->dual, it.dual_div, it.Gq, p.nw, a->err_flag,
+                                p.bm, a->B0, a->W0, nwrow, p.n, p.bm_ld, it.rho_next, a->eta, p.s_main);
+  else
+    rc = effq_project_dual_checked(a->v, a->wstar, it.st, a->w_levels, it.G, a->dual, it.dual_div, it.Gq, p.nw,
+                                   a->err_flag, p.s_main);
+  if (rc != EFFQ_OK) return rc;
+  p_pr.close();
+  return EFFQ_OK;
+}
+
+// The losses of iterates j0 .. i, on the loss stream: kind 5 for up to 16 iterates in one launch pair (the digit planes of
+// the Gram system are read once per group), the other kinds one iterate at a time.
+static int enqueue_losses(const effq_admm_run_args* a, const AdmmPlan& p, int j0, int i) {
+  const int step = a->loss_kind == 5 ? 16 : 1;
+  for (int j = j0; j <= i; j += step) {
+    const int cnt = (i - j + 1 < step) ? (i - j + 1) : step;
+    const float* Gj = a->G_ring + (size_t)j * p.nw;
+    const int8_t* Gqj = a->Gq_ring ? a->Gq_ring + (size_t)j * p.nw : nullptr;
+    const float* bj = p.has_b ? a->b_ring + (size_t)j * p.c2 : nullptr;
+    const effq_fp_state* stj = a->state_ring + j;
+    double* sq = a->hist + 2 * (size_t)j;
+    const bool prof = g_prof_every > 0 && (a->loss_kind == 5 ? (j / p.loss_group) % 2 == 1 :
+                      !(p.rhos.shifted_first && j == 0) && (j % g_prof_every) == g_prof_every / 2);
+    ProfScope p_loss(prof, PROF_LOSS, j, a, p.s_loss);
+    int rc;
+    if (a->loss_kind == 5)
+      rc = effq_gram_loss_i8(a->loss_planes, a->loss_nplanes, a->loss_Au, a->loss_Bu, a->loss_syy, Gqj, bj, stj,
+                             a->act_alpha_dev, a->act_levels, a->w_levels, p.c2, p.n, p.has_b, cnt, sq, a->conv_ws,
+                             a->conv_ws_bytes, p.s_loss);
+    else if (a->loss_kind == 1)
+      rc = conv3d_calib_step_i8(a->xidx, Gqj, bj, a->y_fp, &a->geom, a->act_alpha_dev, a->act_levels, stj, a->w_levels,
+                                sq, a->conv_ws, a->conv_ws_bytes, p.s_loss);
+    else if (a->loss_kind == 2)
+      rc = conv3d_calib_step_i8s(a->xidx, Gqj, bj, a->y_fp, &a->geom, a->act_alpha_dev, a->act_levels, stj, a->w_levels,
+                                 j == 0 ? 1 : 0, sq, a->conv_ws, a->conv_ws_bytes, p.s_loss);
+    else if (a->loss_kind == 4)
+      rc = effq_gram_loss(a->loss_Au, a->loss_Bu, a->loss_syy, Gj, bj, p.c2, p.n, p.has_b, sq, a->conv_ws,
+                          a->conv_ws_bytes, p.s_loss);
+    else
+      rc = conv3d_quant_calib_step(a->xq, Gj, bj, a->y_fp, nullptr, &a->geom, nullptr, 0, sq, nullptr, a->conv_ws,
+                                   a->conv_ws_bytes, p.s_loss);   // unweighted MSE (quirk Q5)
+    if (rc != EFFQ_OK) return rc;
+    p_loss.close();
+  }
+  return EFFQ_OK;
+}
+
+}  // namespace effq
+using namespace effq;
+
+extern "C" {
+
+// whether effq_admm_run would use effq_fixed_point_traj for a layer of nw weights at w_levels levels (the caller then
+// provides fp_pred / fp_traj_ws; otherwise both may be NULL)
+int effq_admm_uses_traj(size_t nw, int w_levels) {
+  constexpr int traj_levels = 4;          // see the measurements in admm_plan
+  constexpr size_t traj_min = 65536;
+  return (w_levels <= traj_levels && nw >= traj_min && nw <= effq_fp_traj_max()) ? 1 : 0;
+}
+
+int effq_admm_num_inverses(double rho, double rho_max, int iters, int period) {
+  if (!(rho > 0.0) || iters <= 0 || period <= 0) return -1;
+  const RhoPlan p = plan_rhos(rho, rho_max, iters, period);
+  if (p.overflow) return -1;
+  return p.count - (p.shifted_first ? 1 : 0);
+}
+
+int effq_admm_run(const effq_admm_run_args* a) {
+  AdmmPlan p;
+  if (const int rc = admm_plan(a, &p); rc != EFFQ_OK) return rc;
+  constexpr int LOSS_EVENTS = 4;
+  EventPool events;
+  EFFQ_HIP(events.open());
+  hipEvent_t ev_inv[ADMM_MAX_RHOS] = {}, ev_loss[LOSS_EVENTS] = {};
+  EFFQ_HIP(hipMemsetAsync(a->dual, 0, p.nw * sizeof(float), p.s_main));               // dual <- 0 (EfficientQConv.py:40)
+  if (a->res_ring != nullptr) EFFQ_HIP(hipMemsetAsync(a->res_ring, 0, 2 * (size_t)a->iters * sizeof(double), p.s_main));
+  if (p.traj) EFFQ_HIP(hipMemsetAsync(a->fp_pred, 0, effq_fp_traj_pred_bytes(), p.s_main));   // nothing known about this layer
   // the inverse the first iterations need, on the main stream; the later ones on the side stream, which starts at once,
   // beside the first inverse (all of them only read A0): with n = 13825 an inverse takes longer than the 50 iterations it has
   // to be ready after, and the chain waited for each of the three later ones in turn (LiTS: 3.08 -> 3.03 s per calibration;
   // BraTS 900 -> 893 ms).
-  if (fork_side && n_inv > 1) {
-    ADMM_HIP(new_event(&ev_fork));
-    ADMM_HIP(hipEventRecord(ev_fork, s_main));         // A0 (and everything before the call) is ready
-    ADMM_HIP(hipStreamWaitEvent(s_side, ev_fork, 0));
-    if (two_sides) ADMM_HIP(hipStreamWaitEvent(s_side2, ev_fork, 0));
+  if (p.fork_side && p.n_inv > 1) {
+    hipEvent_t ev_fork;
+    EFFQ_HIP(events.take(&ev_fork));
+    EFFQ_HIP(hipEventRecord(ev_fork, p.s_main));         // A0 (and everything before the call) is ready
+    EFFQ_HIP(hipStreamWaitEvent(p.s_side, ev_fork, 0));
+    if (p.two_sides) EFFQ_HIP(hipStreamWaitEvent(p.s_side2, ev_fork, 0));
   }
-  {
-    ProfScope ps(g_prof_every > 0, PROF_INVERSE, -1, a, s_main);
-    ADMM_RC(effq_spd_inverse(a->A0, n, has_b, plan.rho[first], a->eta, a->ainv_pool, a->inv_ws, a->inv_ws_bytes, s_main));
-    ps.close();
-  }
-  // The later inverses (side stream) are ENQUEUED a few iterations into the loop, not here: their ~30 - 650 launches take
-  // the host 0.2 - 2.6 ms, during which the main stream - done with its own inverse on the small layers - had nothing queued
-  // (under a profiler, at 3 x the launch cost, 6 ms per layer).  The side stream still starts from the fork event recorded
-  // above, i.e. as early as before.
-  bool side_enqueued = (n_inv <= 1);
-  auto enqueue_side_inverses = [&]() -> int {
-    side_enqueued = true;
-    for (int r = first + 1; r < plan.count; ++r) {
-      float* dst = a->ainv_pool + (size_t)(r - first) * ainv_elems;
-      const bool on2 = two_sides && ((r - first) % 2 == 0);   // first later inverse on side 1, the next on side 2 ...
-      hipStream_t sr = on2 ? s_side2 : s_side;
-      void* ws = !fork_side ? a->inv_ws : (on2 ? a->inv_ws_side2 : a->inv_ws_side);
-      const size_t wsb = !fork_side ? a->inv_ws_bytes : (on2 ? a->inv_ws_side2_bytes : a->inv_ws_side_bytes);
-      ProfScope ps(g_prof_every > 0, PROF_INVERSE, -1 - r, a, sr);
-      const int rc = effq_spd_inverse(a->A0, n, has_b, plan.rho[r], a->eta, dst, ws, wsb, sr);
-      if (rc != EFFQ_OK) return rc;
-      ps.close();
-      if (fork_side) {
-        hipError_t e2 = new_event(&ev_inv[r]);
-        if (e2 == hipSuccess) e2 = hipEventRecord(ev_inv[r], sr);
-        if (e2 != hipSuccess) {
-          effq::set_error("admm_run: side-stream event -> %s", hipGetErrorString(e2));
-          return EFFQ_ERR_HIP;
-        }
-      }
-    }
-    return EFFQ_OK;
-  };
-  // without a side stream the later inverses run on the main stream: they must be queued before the iterations that use them
-  if (!fork_side && !side_enqueued) ADMM_RC(enqueue_side_inverses());
-  constexpr int SIDE_AFTER_ITERS = 8;
-  if (fork_loss)
-    for (int e = 0; e < EV_POOL; ++e) ADMM_HIP(new_event(&ev_main[e]));
-
-  double rho = a->rho;
-  int cur = -1;     // index into plan.rho of the inverse in use
-  int bm_ld = 0;
-  float* bm = effq_prox_bm(a->prox_ws, c2, n, &bm_ld);
+  ProfScope p_inv(g_prof_every > 0, PROF_INVERSE, -1, a, p.s_main);
+  if (const int rc = effq_spd_inverse(a->A0, p.n, p.has_b, p.rhos.rho[p.first], a->eta, a->ainv_pool, a->inv_ws,
+                                      a->inv_ws_bytes, p.s_main); rc != EFFQ_OK)
+    return rc;
+  p_inv.close();
+  if (p.fork_loss)
+    for (int e = 0; e < LOSS_EVENTS; ++e) EFFQ_HIP(events.take(&ev_loss[e]));
   bool bm_ready = false;
   const float* Ainv = nullptr;
-  // group size: the last group is evaluated after the chain has finished (it delays the join by one group of losses), so
-  // the cheap losses from the Gram system travel in larger groups than the conv passes.  EFFQ_LOSS_GROUP overrides the
-  // Gram group (bench.py's model reads it too)
-  static const int group_gram = getenv("EFFQ_LOSS_GROUP") ? atoi(getenv("EFFQ_LOSS_GROUP")) : 8;
-  constexpr int group_conv = 4;
-  const int group_size = (a->loss_kind == 4 || a->loss_kind == 5) ? group_gram : group_conv;
-  const int loss_group = (fork_loss && group_size > 1) ? group_size : 1;
+  int k = 0;                       // p.rhos.rho[k]: this iteration's rho (plan_rhos ran the schedule of EfficientQConv.py)
+  int cur = -1;                    // index into p.rhos.rho of the inverse in use
   int loss_next = 0;
-  bool rho_changed_last = false;
-  int rho_changed_at = 0;          // first iteration that ran with the current rho
   for (int i = 0; i < a->iters; ++i) {
-    const bool use_shift = plan.shifted_first && i == 0;
-    if (!side_enqueued && (i == SIDE_AFTER_ITERS || (first + 1 < plan.count && i + 1 >= plan.first_iter[first + 1])))
-      ADMM_RC(enqueue_side_inverses());
-    if (!use_shift && (cur < 0 || plan.rho[cur] != rho)) {
-      int r = first;
-      while (r < plan.count && plan.rho[r] != rho) ++r;
-      EFFQ_CHECK_ARG(r < plan.count);
-      if (fork_side && ev_inv[r] != nullptr) {
-        ProfScope p_wait(g_prof_every > 0, PROF_WAIT, i, a, s_main);
-        ADMM_HIP(hipStreamWaitEvent(s_main, ev_inv[r], 0));
+    if (k + 1 < p.rhos.count && p.rhos.first_iter[k + 1] == i) ++k;
+    if (i == p.side_iter)
+      if (const int rc = enqueue_later_inverses(a, p, events, ev_inv); rc != EFFQ_OK) return rc;
+    // (iterations since rho last changed: the drift from call to call - and with it the length of the lists the
+    // trajectory kernel's single last workgroup has to scan - is largest right after a change.  traj_after >= 12 also
+    // keeps it off the first two iterations and off the one after a change, whose dual is rescaled.)
+    AdmmIter it = admm_iter(a, p, i, p.rhos.rho[k], p.traj && i - p.rhos.first_iter[k] >= p.traj_after);
+    if (!it.use_shift && cur != k) {
+      EFFQ_CHECK_ARG(p.rhos.rho[k] == p.rhos.rho[k]);   // (a NaN rho, from a NaN rho_max, has no inverse)
+      if (p.fork_side && ev_inv[k] != nullptr) {
+        ProfScope p_wait(g_prof_every > 0, PROF_WAIT, i, a, p.s_main);
+        EFFQ_HIP(hipStreamWaitEvent(p.s_main, ev_inv[k], 0));
         p_wait.close();
       }
-      Ainv = a->ainv_pool + (size_t)(r - first) * ainv_elems;
-      cur = r;
+      Ainv = a->ainv_pool + (size_t)(k - p.first) * p.ainv_elems;
+      cur = k;
     }
-    float dual_div = 1.0f;
-    if (i % a->rho_period == 0) dual_div = (rho * 2 <= a->rho_max) ? 2.0f : (float)(a->rho_max / rho);
-    const float* G_prev = (i == 0) ? a->W0 : a->G_ring + (size_t)(i - 1) * nw;
-    float* G = a->G_ring + (size_t)i * nw;
-    int8_t* Gq = a->Gq_ring ? a->Gq_ring + (size_t)i * nw : nullptr;
-    float* bstar = has_b ? a->b_ring + (size_t)i * c2 : nullptr;
-    effq_fp_state* st = a->state_ring + i;
-    // (rho changes at the end of iterations 0, period, 2 period ...: the iteration after sees a rescaled dual)
-    const bool after_rho = i > 0 && (i - 1) % a->rho_period == 0 && rho_changed_last;
-    // (iterations since rho last changed: the drift from call to call - and with it the length of the lists the
-    // trajectory kernel's single last workgroup has to scan - is largest right after a change)
-    const int since_rho = i - rho_changed_at;
-    const bool use_traj = traj && i > 1 && !after_rho && since_rho >= traj_after;
-    // ... and then the trajectory kernel adds the K slices of the product up in its prologue: one launch less
-    const float* parts = nullptr;
-    int parts_n = 1, parts_ld = 0;
     // ---- the chain (main stream) ----
-    const bool prof = g_prof_every > 0 && !use_shift && (i % g_prof_every) == g_prof_every / 2;
-    ProfScope p_prox(prof, PROF_PROX, i, a, s_main);
-    if (!use_shift && bm_ready && use_traj && c2 <= 512)
-      ADMM_RC(effq_prox_solve_prebuilt_parts(a->B0, Ainv, a->W0, a->b0, G_prev, a->dual, c2, n, has_b, rho, a->eta, a->wstar,
-                                             bstar, a->prox_ws, a->prox_ws_bytes, s_main, &parts, &parts_n, &parts_ld));
-    else if (use_shift)
-      ADMM_RC(effq_prox_solve_shifted(a->B0, a->ainv_pool, a->W0, a->b0, G_prev, a->dual, c2, n, has_b, rho, a->eta,
-                                      plan.rho[1], shift_terms(rho, a->eta, plan.rho[1]), a->wstar, bstar, a->prox_ws,
-                                      a->prox_ws_bytes, s_main));
-    else if (bm_ready)
-      ADMM_RC(effq_prox_solve_prebuilt(a->B0, Ainv, a->W0, a->b0, G_prev, a->dual, c2, n, has_b, rho, a->eta, a->wstar,
-                                       bstar, a->prox_ws, a->prox_ws_bytes, s_main));
-    else
-      ADMM_RC(effq_prox_solve(a->B0, Ainv, a->W0, a->b0, G_prev, a->dual, c2, n, has_b, rho, a->eta, a->wstar, bstar,
-                              a->prox_ws, a->prox_ws_bytes, s_main));
+    ProfScope p_prox(it.prof, PROF_PROX, i, a, p.s_main);
+    if (const int rc = enqueue_prox(a, p, &it, Ainv, bm_ready); rc != EFFQ_OK) return rc;
     p_prox.close();
-    ProfScope p_fp(prof, PROF_FIXED_POINT, i, a, s_main);
-    // The projection + dual update as the EPILOGUE of the fixed point where that is a single workgroup (weights <= 32768):
-    // one launch per iteration less.  The projection also leaves the right-hand side of the NEXT prox solve in the prox
-    // workspace; the first solve of the layer builds Bm itself (bias column, padding).
-    double rho_next = rho;
-    if (i % a->rho_period == 0) rho_next = (rho * 2 <= a->rho_max) ? rho * 2 : a->rho_max;
-    const bool next_rhs = i + 1 < a->iters;
-    ProjFused pf;
-    memset(&pf, 0, sizeof(pf));
-    bool fuse_proj = false;
-    {
-      const int nwrow = n - has_b;
-      const uintptr_t al16 = reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->wstar) |
-                             reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(a->dual) |
-                             (next_rhs ? (reinterpret_cast<uintptr_t>(a->W0) | reinterpret_cast<uintptr_t>(bm)) : 0);
-      const bool vec_ok = (al16 & 15) == 0 && (reinterpret_cast<uintptr_t>(Gq) & 3) == 0 && (nw % 4) == 0 &&
-                          (!next_rhs || ((nwrow % 4) == 0 && (bm_ld % 4) == 0));
-      // measured (us per iteration, fused against fixed point + projection): 2048 weights 13.8 against 12.2 + 7.1, 3456 at
-      // 256 levels 231.8 against 229.3 + 8.3 - but 27648 weights on the bucketed kernel 56.3 against 33.6 + 7.1: only the
-      // 256 threads of its iteration phase are left for the epilogue.  So: the all-values kernel's layers only
-      if (vec_ok && !bucket && nw <= effq_fp_small_max()) {
-        fuse_proj = true;
-        pf.wstar = a->wstar; pf.G = G; pf.dual = a->dual; pf.Gq = Gq; pf.err_flag = a->err_flag;
-        pf.d = 2.0 / (double)(a->w_levels - 1); pf.dual_div = dual_div; pf.lm1 = a->w_levels - 1;
-        pf.n4 = (unsigned)(nw / 4);
-        if (next_rhs) {
-          pf.nx.Bm = bm; pf.nx.B0 = a->B0; pf.nx.W0 = a->W0; pf.nx.nwrow = nwrow; pf.nx.n = n; pf.nx.ldb = bm_ld;
-          pf.nx.rho = (float)rho_next; pf.nx.eta = (float)a->eta;
-        }
-      }
-    }
-    void* rec = traj ? a->fp_pred : nullptr;
-    if (chan) {
-      // every row's fixed point, projection, dual update and the next Bm in one launch (no per-tensor kernel runs)
-      ADMM_RC(effq_fixed_point_channels_proj(a->wstar, a->dual, a->v, c2, n - has_b, a->w_levels, a->tol, 100 * a->w_levels,
-                                             a->alpha_ring + (size_t)i * c2,
-                                             a->w_iters_ring ? a->w_iters_ring + (size_t)i * c2 : nullptr, a->err_flag, G,
-                                             dual_div, next_rhs ? bm : nullptr, a->B0, a->W0, n, bm_ld, rho_next, a->eta,
-                                             s_main));
-      fuse_proj = true;
-    } else if (use_traj && parts != nullptr) {
-      fuse_proj = false;
-      ADMM_RC(effq_fixed_point_traj_parts(parts, parts_n, parts_ld, c2, n - has_b, has_b ? 1 : 0, a->dual, a->wstar, bstar,
-                                          a->v, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels, st, a->fp_pred,
-                                          a->fp_traj_ws, a->fp_traj_ws_bytes, s_main));
-    } else if (use_traj) {
-      fuse_proj = false;
-      ADMM_RC(effq_fixed_point_traj(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels, st,
-                                    a->fp_pred, a->fp_traj_ws, a->fp_traj_ws_bytes, s_main));
-    } else if (bucket) {
-      ADMM_RC(effq_fixed_point_bucket_rec(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels,
-                                          st, a->fp_ws, a->fp_ws_bytes, rec, s_main));
-    } else if (nw <= effq_fp_small_max()) {
-      ADMM_RC(effq_fixed_point_small_fused(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol,
-                                           100 * a->w_levels, st, fuse_proj ? &pf : nullptr, s_main));
-    } else {
-      fuse_proj = false;
-      ADMM_RC(effq_fixed_point_coop_rec(a->wstar, a->dual, a->v, nw, a->w_levels, -1.0, 1.0, a->tol, 100 * a->w_levels,
-                                        st, a->red_ws, rec, s_main));
-    }
-    p_fp.close();
-    if (fuse_proj) {
-      bm_ready = next_rhs;
-    } else {
-      ProfScope p_pr(prof, PROF_PROJECT, i, a, s_main);
-      if (next_rhs) {
-        ADMM_RC(effq_project_dual_next(a->v, a->wstar, st, a->w_levels, G, a->dual, dual_div, Gq, nw, a->err_flag, bm,
-                                       a->B0, a->W0, n - has_b, n, bm_ld, rho_next, a->eta, s_main));
-        bm_ready = true;
-      } else {
-        ADMM_RC(effq_project_dual_checked(a->v, a->wstar, st, a->w_levels, G, a->dual, dual_div, Gq, nw, a->err_flag,
-                                          s_main));
-        bm_ready = false;
-      }
-      p_pr.close();
-    }
+    if (const int rc = enqueue_fixed_point(a, p, it, &bm_ready); rc != EFFQ_OK) return rc;
     if (a->res_ring != nullptr) {                 // lwq_verbose: residuals of this iteration (w* is overwritten by the next)
-      size_t nb = (nw + 1023) / 1024;
-      if (nb > 256) nb = 256;
-      hipLaunchKernelGGL(k_admm_residuals, dim3((unsigned)nb), dim3(256), 0, s_main, a->wstar, G, G_prev, nw,
+      const size_t nb = std::min<size_t>((p.nw + 1023) / 1024, 256);
+      hipLaunchKernelGGL(k_admm_residuals, dim3((unsigned)nb), dim3(256), 0, p.s_main, a->wstar, it.G, it.G_prev, p.nw,
                          a->res_ring + 2 * (size_t)i);
+      EFFQ_LAUNCH_CHECK();
     }
-    // ---- the losses (loss stream), in groups of LOSS_GROUP iterates ----
+    // ---- the losses (loss stream), in groups of loss_group iterates ----
     // An event record is a barrier packet in the main queue: the next chain kernel starts ~7 us later than it would
     // behind a kernel (kernel trace: the only gap of an iteration sat between the projection and the next prox GEMM).
     // The iterates are kept in rings, so the loss stream may as well pick them up a few at a time.
-    if (fork_loss && ((i + 1) % loss_group == 0 || i + 1 == a->iters)) {
-      hipEvent_t e = ev_main[(i / loss_group) % EV_POOL];
-      ADMM_HIP(hipEventRecord(e, s_main));
-      ADMM_HIP(hipStreamWaitEvent(s_loss, e, 0));
-    }
-    if (a->loss_kind == 5 && (!fork_loss || (i + 1) % loss_group == 0 || i + 1 == a->iters)) {
-      // the whole group in one launch pair (the digit planes of the Gram system are read once per group)
-      for (int j = loss_next; j <= i; j += 16) {
-        const int cnt = (i - j + 1 < 16) ? (i - j + 1) : 16;
-        ProfScope p_loss(g_prof_every > 0 && (j / loss_group) % 2 == 1, PROF_LOSS, j, a, s_loss);
-        ADMM_RC(effq_gram_loss_i8(a->loss_planes, a->loss_nplanes, a->loss_Au, a->loss_Bu, a->loss_syy,
-                                  a->Gq_ring + (size_t)j * nw, has_b ? a->b_ring + (size_t)j * c2 : nullptr, a->state_ring + j,
-                                  a->act_alpha_dev, a->act_levels, a->w_levels, c2, n, has_b, cnt, a->hist + 2 * (size_t)j,
-                                  a->conv_ws, a->conv_ws_bytes, s_loss));
-        p_loss.close();
-      }
+    if (!p.fork_loss || (i + 1) % p.loss_group == 0 || i + 1 == a->iters) {
+      if (p.fork_loss) EFFQ_HIP(events.hand_over(p.s_main, p.s_loss, ev_loss[(i / p.loss_group) % LOSS_EVENTS]));
+      if (const int rc = enqueue_losses(a, p, loss_next, i); rc != EFFQ_OK) return rc;
       loss_next = i + 1;
-    } else if (!fork_loss || (i + 1) % loss_group == 0 || i + 1 == a->iters) {
-      for (int j = loss_next; j <= i; ++j) {
-        const float* Gj = a->G_ring + (size_t)j * nw;
-        const int8_t* Gqj = a->Gq_ring ? a->Gq_ring + (size_t)j * nw : nullptr;
-        const float* bj = has_b ? a->b_ring + (size_t)j * c2 : nullptr;
-        const effq_fp_state* stj = a->state_ring + j;
-        double* sq = a->hist + 2 * (size_t)j;
-        const bool profj = g_prof_every > 0 && !(plan.shifted_first && j == 0) && (j % g_prof_every) == g_prof_every / 2;
-        ProfScope p_loss(profj, PROF_LOSS, j, a, s_loss);
-        if (a->loss_kind == 1)
-          ADMM_RC(conv3d_calib_step_i8(a->xidx, Gqj, bj, a->y_fp, &a->geom, a->act_alpha_dev, a->act_levels, stj,
-                                       a->w_levels, sq, a->conv_ws, a->conv_ws_bytes, s_loss));
-        else if (a->loss_kind == 2)
-          ADMM_RC(conv3d_calib_step_i8s(a->xidx, Gqj, bj, a->y_fp, &a->geom, a->act_alpha_dev, a->act_levels, stj,
-                                        a->w_levels, j == 0 ? 1 : 0, sq, a->conv_ws, a->conv_ws_bytes, s_loss));
-        else if (a->loss_kind == 4)
-          ADMM_RC(effq_gram_loss(a->loss_Au, a->loss_Bu, a->loss_syy, Gj, bj, c2, n, has_b, sq, a->conv_ws,
-                                 a->conv_ws_bytes, s_loss));
-        else
-          ADMM_RC(conv3d_quant_calib_step(a->xq, Gj, bj, a->y_fp, nullptr, &a->geom, nullptr, 0, sq, nullptr, a->conv_ws,
-                                          a->conv_ws_bytes, s_loss));   // unweighted MSE (quirk Q5)
-        p_loss.close();
-      }
-      loss_next = i + 1;
-    }
-    if (i % a->rho_period == 0) {
-      const double rho_new = (rho * 2 <= a->rho_max) ? rho * 2 : a->rho_max;
-      rho_changed_last = rho_new != rho;
-      if (rho_changed_last) rho_changed_at = i + 1;
-      rho = rho_new;
     }
   }
-  if (!side_enqueued) ADMM_RC(enqueue_side_inverses());      // (fewer iterations than SIDE_AFTER_ITERS)
   // join: everything the caller reads next (hist, rings) is ordered on the main stream
-  ProfScope p_join(g_prof_every > 0 && (fork_loss || fork_side), PROF_WAIT, a->iters, a, s_main);
-  if (fork_loss) {
-    ADMM_HIP(new_event(&ev_join_loss));
-    ADMM_HIP(hipEventRecord(ev_join_loss, s_loss));
-    ADMM_HIP(hipStreamWaitEvent(s_main, ev_join_loss, 0));
-  }
-  if (fork_side && n_inv > 1) {
-    ADMM_HIP(new_event(&ev_join_side));
-    ADMM_HIP(hipEventRecord(ev_join_side, s_side));
-    ADMM_HIP(hipStreamWaitEvent(s_main, ev_join_side, 0));
-    if (two_sides) {
-      hipEvent_t ev_join_side2 = nullptr;
-      ADMM_HIP(new_event(&ev_join_side2));
-      ADMM_HIP(hipEventRecord(ev_join_side2, s_side2));
-      ADMM_HIP(hipStreamWaitEvent(s_main, ev_join_side2, 0));
-    }
-  }
+  ProfScope p_join(g_prof_every > 0 && (p.fork_loss || p.fork_side), PROF_WAIT, a->iters, a, p.s_main);
+  if (p.fork_loss) EFFQ_HIP(events.hand_over(p.s_loss, p.s_main));
+  if (p.fork_side && p.n_inv > 1) EFFQ_HIP(events.hand_over(p.s_side, p.s_main));
+  if (p.fork_side && p.n_inv > 1 && p.two_sides) EFFQ_HIP(events.hand_over(p.s_side2, p.s_main));
   p_join.close();
-  destroy_events();
-#undef ADMM_HIP
-#undef ADMM_RC
   return EFFQ_OK;
 }
 

@@ -40,6 +40,93 @@ def test_product_path_refuses_cpu_tensors():
         conv(torch.zeros(1, 2, 4, 4, 4))
 
 
+def _admm_args(lib, c2=8, c1=3, k=3, **fields):
+    """An effq_admm_run argument block for a c2 x c1 x k^3 layer with bias that passes every check, then `fields`.
+    The pointers are dummies: every case below is rejected before the run touches a device."""
+    from efficientq_amd import _lib
+    a = _lib.AdmmRunArgs()
+    dummy = 1 << 20
+    for name in ("A0", "B0", "W0", "b0", "xq", "y_fp", "dual", "wstar", "v", "G_ring", "b_ring", "state_ring", "hist",
+                 "err_flag", "ainv_pool", "prox_ws", "red_ws", "inv_ws", "conv_ws"):
+        setattr(a, name, dummy)
+    a.c2, a.n, a.has_bias, a.w_levels = c2, c1 * k ** 3 + 1, 1, 4
+    a.iters, a.rho_period, a.rho, a.rho_max, a.eta, a.tol = 10, 2, 0.5, 4.0, 1e-3, 1e-6
+    a.geom = _lib.Geom(1, c1, c2, 4, 4, 4, k, k, k, 1, 1, 1, k // 2, k // 2, k // 2)
+    a.loss_kind, a.act_levels = 0, 4
+    a.n_ainv = lib.effq_admm_num_inverses(a.rho, a.rho_max, a.iters, a.rho_period)
+    for name, value in fields.items():
+        setattr(a, name, dummy if value is ... else value)   # ... = a dummy pointer
+    return a
+
+
+_ADMM_REJECTS = [   # (case, arguments, expected status, the part of effq_last_error() that names the check)
+    ("null args", None, "EFFQ_ERR_ARG", "a != nullptr"),
+    ("loss kind 3", dict(loss_kind=3), "EFFQ_ERR_ARG", "a->loss_kind == 4 || a->loss_kind == 5"),
+    ("loss kind 4 without its Gram operands", dict(loss_kind=4), "EFFQ_ERR_ARG",
+     "a->loss_Au != nullptr && a->loss_Bu != nullptr && a->loss_syy != nullptr"),
+    ("channel mode with loss kind 1", dict(channel_wise=1, alpha_ring=..., loss_kind=1, xidx=..., Gq_ring=...,
+                                           act_alpha_dev=...), "EFFQ_ERR_ARG",
+     "(a->loss_kind == 0 || a->loss_kind == 4) && a->alpha_ring != nullptr"),
+    ("weights that do not match geom", dict(n=83), "EFFQ_ERR_ARG", "a->geom.C2 * a->geom.C1"),
+    ("weights above effq_fp_coop_max", "coop", "EFFQ_ERR_ARG", "exceed the single-launch fixed points"),
+    ("bucketed fixed-point workspace too small", dict(c2=64, fp_ws=..., fp_ws_bytes=0), "EFFQ_ERR_WORKSPACE",
+     "admm_run: fixed-point workspace 0 <"),
+    ("trajectory workspace too small", dict(c2=810, fp_pred=..., fp_traj_ws=..., fp_traj_ws_bytes=0),
+     "EFFQ_ERR_WORKSPACE", "trajectory fixed-point workspace 0 <"),
+    ("n_ainv below effq_admm_num_inverses", "n_ainv", "EFFQ_ERR_ARG", "a->n_ainv >="),
+]
+
+
+def _admm_rejections():
+    """Child process of admm_rejections: every case of _ADMM_REJECTS, as one JSON line {case: [status, message]}."""
+    import ctypes
+    import json
+    from efficientq_amd import _lib
+    assert torch.cuda.device_count() == 0, "a device is visible: the dummy pointers must never reach one"
+    lib = _lib.load()
+    out = {}
+    for case, args, _, _ in _ADMM_REJECTS:
+        if args is None:
+            rc = lib.effq_admm_run(None)
+        else:
+            if args == "coop":
+                a = _admm_args(lib, c2=lib.effq_fp_coop_max() // 81 + 1, k=1, c1=81)
+                assert a.c2 * (a.n - 1) > lib.effq_fp_coop_max()
+            elif args == "n_ainv":
+                a = _admm_args(lib)
+                a.n_ainv -= 1
+                assert a.n_ainv >= 1
+            else:
+                a = _admm_args(lib, **args)
+            nw = a.c2 * (a.n - 1)
+            if a.fp_ws:               # the case is the bucketed path's ...
+                assert 4096 < nw <= 1 << 19 and lib.effq_fp_bucket_ws_bytes(nw) > 0
+            if a.fp_traj_ws:          # ... and the trajectory path's
+                assert lib.effq_admm_uses_traj(nw, a.w_levels) == 1 and lib.effq_fp_traj_ws_bytes(nw) > 0
+            rc = lib.effq_admm_run(ctypes.byref(a))
+        out[case] = [_lib._ERR_NAMES.get(rc, rc), lib.effq_last_error().decode()]
+    print(json.dumps(out))
+
+
+@pytest.fixture(scope="module")
+def admm_rejections():
+    """Runs the cases in a child process that sees no device: a check that stopped rejecting would fail there with
+    EFFQ_ERR_HIP instead of writing through a dummy pointer on a real card."""
+    import json
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", "from tests.test_host_cpu import _admm_rejections; _admm_rejections()"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.parametrize("case,want,check", [(c, w, m) for c, _, w, m in _ADMM_REJECTS],
+                         ids=[c[0] for c in _ADMM_REJECTS])
+def test_admm_run_rejects_bad_arguments_before_any_device_call(admm_rejections, case, want, check):
+    status, message = admm_rejections[case]
+    assert status == want and check in message, (status, message)
+
+
 # ------------------------------------------------------------------ graph / state_dict / BN fold / masks
 def _tiny(task, L=4, width=None, init_stride=None):
     from efficientq_amd import config as Cf
