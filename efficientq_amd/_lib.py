@@ -176,7 +176,16 @@ SIGNATURES = {
     "effq_conv_ws_bytes": (_SZ, [_GP]),
     "conv3d_quant_calib_step": (_I, [_P, _P, _P, _P, _P, _GP, _P, _I, _P, _P, _P, _SZ, _P]),
     "effq_adam_step": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _I, _SZ, _P]),
+    "effq_window_gather": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
 }
+
+# include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
+SEG_TALLIES_WS_BYTES = 1024 * 3 * 8 * 4
+SEG_TALLIES_MAX_CLASSES = 8
+SEG_ARGMAX, SEG_SIGMOID = 0, 1
+SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 
 _lib = None
 

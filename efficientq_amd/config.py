@@ -38,6 +38,8 @@ def build_parser():
     p.add_argument('--config', type=str)
     p.add_argument('--data_dir')
     p.add_argument('--split_dir')
+    p.add_argument('--access_type', default='npy', choices=['npy', 'npz'])
+    p.add_argument('--merge_type', help='how to merge multiple labels (agg / con)')
     p.add_argument('--round', default='1', type=str)
     p.add_argument('--patch_size')
     p.add_argument('--bin_label')

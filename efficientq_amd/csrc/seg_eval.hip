@@ -1,0 +1,348 @@
+// Validation of a segmentation network on whole volumes (evaluate.validate_seg): the overlapped windows of a volume
+// gathered into one channels-last batch, the per-window logits stitched back to the volume, and the per-class confusion
+// counts of the stitched logits against the label.  All three stream HBM once and do no arithmetic to speak of.
+//
+// Windows: along each axis the starts are  min(i * (patch - overlap), size - patch)  for i = 0 .. n-1 with
+// n = ceil((size - patch) / (patch - overlap)) + 1, i.e. evaluate.window_starts: steps while a whole patch ends strictly
+// before the border, then one patch flush with it.  Windows are numbered in (d, h, w) raster order.
+//
+// Stitch: one thread per output voxel adds the covering windows in raster order onto 0.0f and divides once by their
+// count - the addends, the order and the rounding of evaluate.patch_to_image3d, so the result is the same bits.
+// Tallies: wave reductions into per-block partials, summed in block order by a second launch; integer counts only.
+#include "common.h"
+
+namespace effq {
+
+struct WinAxes {
+  int D, H, W;        // volume extent
+  int pd, ph, pw;     // window extent
+  int sd, sh, sw;     // step = patch - overlap
+  int nd, nh, nw;     // windows per axis
+};
+
+static inline int n_windows(int size, int patch, int step) {
+  return (size - patch + step - 1) / step + 1;
+}
+
+__device__ __forceinline__ int win_start(int i, int size, int patch, int step) {
+  const int s = i * step;
+  return s < size - patch ? s : size - patch;
+}
+
+// ---- gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1 -------------
+template <int VEC>
+__global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ vol, float* __restrict__ out, WinAxes a,
+                                                       int N, int C, int first, uint32_t total) {
+  const size_t plane = (size_t)a.D * a.H * a.W;
+  // 32-bit index arithmetic (the entry point bounds `total`): 64-bit division is a long software sequence on the GPU
+  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    uint32_t r = e;
+    const int x = (int)(r % a.pw); r /= a.pw;
+    const int y = (int)(r % a.ph); r /= a.ph;
+    const int z = (int)(r % a.pd); r /= a.pd;
+    const int n = (int)(r % N);
+    const int win = first + (int)(r / N);
+    const int k = win % a.nw, j = (win / a.nw) % a.nh, i = win / (a.nw * a.nh);
+    const int d = win_start(i, a.D, a.pd, a.sd) + z;
+    const int h = win_start(j, a.H, a.ph, a.sh) + y;
+    const int w = win_start(k, a.W, a.pw, a.sw) + x;
+    // lanes of a wave hold consecutive x: every channel plane is read coalesced, every voxel written as C contiguous floats
+    const float* src = vol + (size_t)n * C * plane + ((size_t)d * a.H + h) * a.W + w;
+    float* dst = out + (size_t)e * C;
+    for (int c = 0; c < C; c += VEC) {
+      if constexpr (VEC == 4) {
+        float4 v;
+        v.x = src[(size_t)c * plane];
+        v.y = src[(size_t)(c + 1) * plane];
+        v.z = src[(size_t)(c + 2) * plane];
+        v.w = src[(size_t)(c + 3) * plane];
+        *reinterpret_cast<float4*>(dst + c) = v;
+      } else {
+        dst[c] = src[(size_t)c * plane];
+      }
+    }
+  }
+}
+
+// ---- stitch: win (nwin, N, pd, ph, pw, C) -> out (N, C, D, H, W) --------------------------------------------------
+constexpr int STITCH_MAX_C = 8;
+
+__global__ __launch_bounds__(256) void k_window_stitch(const float* __restrict__ win, float* __restrict__ out, WinAxes a,
+                                                       int N, int C, uint32_t total) {
+  const size_t plane = (size_t)a.D * a.H * a.W;
+  const size_t wvox = (size_t)a.pd * a.ph * a.pw;
+  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    uint32_t r = e;
+    const int w = (int)(r % a.W); r /= a.W;
+    const int h = (int)(r % a.H); r /= a.H;
+    const int d = (int)(r % a.D);
+    const int n = (int)(r / a.D);
+    float acc[STITCH_MAX_C];
+#pragma unroll
+    for (int c = 0; c < STITCH_MAX_C; ++c) acc[c] = 0.0f;
+    int cnt = 0;
+    for (int i = 0; i < a.nd; ++i) {
+      const int z = d - win_start(i, a.D, a.pd, a.sd);
+      if (z < 0 || z >= a.pd) continue;
+      for (int j = 0; j < a.nh; ++j) {
+        const int y = h - win_start(j, a.H, a.ph, a.sh);
+        if (y < 0 || y >= a.ph) continue;
+        for (int k = 0; k < a.nw; ++k) {
+          const int x = w - win_start(k, a.W, a.pw, a.sw);
+          if (x < 0 || x >= a.pw) continue;
+          const size_t widx = ((size_t)(i * a.nh + j) * a.nw + k) * N + n;
+          const float* src = win + ((widx * wvox) + ((size_t)z * a.ph + y) * a.pw + x) * C;
+#pragma unroll
+          for (int c = 0; c < STITCH_MAX_C; ++c)
+            if (c < C) acc[c] = acc[c] + src[c];
+          ++cnt;
+        }
+      }
+    }
+    const float fc = (float)cnt;
+    float* dst = out + (size_t)n * C * plane + ((size_t)d * a.H + h) * a.W + w;
+#pragma unroll
+    for (int c = 0; c < STITCH_MAX_C; ++c)
+      if (c < C) dst[(size_t)c * plane] = acc[c] / fc;
+  }
+}
+
+// ---- tallies ------------------------------------------------------------------------------------------------------
+// per class three counters: true positives, predicted positives, labelled positives (FP, FN and TN follow from them)
+constexpr int TALLY_THREADS = 256;
+constexpr int TALLY_WAVES = TALLY_THREADS / 64;
+constexpr int TALLY_MAX_BLOCKS = 1024;
+constexpr int TALLY_NCNT = 3 * EFFQ_SEG_TALLIES_MAX_CLASSES;
+static_assert((size_t)TALLY_MAX_BLOCKS * TALLY_NCNT * sizeof(uint32_t) <= EFFQ_SEG_TALLIES_WS_BYTES, "workspace");
+
+struct TallyParams {
+  const float* logits;    // (C, S)
+  const uint8_t* label;   // (S) class ids for argmax, (C, S) 0/1 for multi-label
+  uint32_t* partial;      // (gridDim.x, 3 * C)
+  long long S;
+  int C, mode, fuse;
+  float thresh;
+};
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the decisions of one voxel: pred / gt bit c for class c
+template <int MODE, int C>
+__device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,
+                                       uint32_t& gt) {
+  pred = gt = 0;
+  if constexpr (MODE == EFFQ_SEG_ARGMAX) {
+    // torch.max over the channels: the first maximum wins, NaN counts as the largest value
+    int best = 0;
+    float bv = v[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) {
+      const float x = v[c];
+      if (x > bv || (x != x && bv == bv)) {
+        bv = x;
+        best = c;
+      }
+    }
+    pred = 1u << best;
+    const int l = lab[0];
+    gt = l < C ? (1u << l) : 0u;
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      pred |= (v[c] >= thresh ? 1u : 0u) << c;
+      gt |= (lab[c] != 0 ? 1u : 0u) << c;
+    }
+    if (fuse == EFFQ_SEG_FUSE_AGG) {        // p[i] = any(p[i:])
+      uint32_t f = 0, any = 0;
+#pragma unroll
+      for (int c = C - 1; c >= 0; --c) {
+        any |= (pred >> c) & 1u;
+        f |= any << c;
+      }
+      pred = f;
+    } else if (fuse == EFFQ_SEG_FUSE_CON) { // p[i] = all(p[:i+1])
+      uint32_t f = 0, all = 1;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        all &= (pred >> c) & 1u;
+        f |= all << c;
+      }
+      pred = f;
+    }
+  }
+}
+
+// C classes known at compile time: every per-class loop unrolls and each thread keeps 3 C counters
+template <int MODE, int VEC, int C>
+__global__ __launch_bounds__(TALLY_THREADS) void k_seg_tallies(TallyParams p) {
+  uint32_t cnt[3 * C];
+#pragma unroll
+  for (int q = 0; q < 3 * C; ++q) cnt[q] = 0;
+  const long long groups = p.S / VEC;
+  const long long lab_stride = MODE == EFFQ_SEG_ARGMAX ? 0 : p.S;
+  for (long long g = (long long)blockIdx.x * TALLY_THREADS + threadIdx.x; g < groups;
+       g += (long long)gridDim.x * TALLY_THREADS) {
+    float v[VEC][C];
+    uint8_t lab[VEC][C];
+    constexpr int nlab = MODE == EFFQ_SEG_ARGMAX ? 1 : C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      if constexpr (VEC == 4) {
+        const float4 f = *reinterpret_cast<const float4*>(p.logits + c * p.S + g * 4);
+        v[0][c] = f.x; v[1][c] = f.y; v[2][c] = f.z; v[3][c] = f.w;
+      } else {
+        v[0][c] = p.logits[c * p.S + g];
+      }
+      if (c < nlab) {
+        if constexpr (VEC == 4) {
+          const uchar4 l = *reinterpret_cast<const uchar4*>(p.label + c * lab_stride + g * 4);
+          lab[0][c] = l.x; lab[1][c] = l.y; lab[2][c] = l.z; lab[3][c] = l.w;
+        } else {
+          lab[0][c] = p.label[c * lab_stride + g];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) {
+      uint32_t pred, gt;
+      decide<MODE, C>(v[u], lab[u], p.fuse, p.thresh, pred, gt);
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        cnt[3 * c + 0] += (pred >> c) & (gt >> c) & 1u;
+        cnt[3 * c + 1] += (pred >> c) & 1u;
+        cnt[3 * c + 2] += (gt >> c) & 1u;
+      }
+    }
+  }
+  __shared__ uint32_t red[TALLY_WAVES][3 * C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 3 * C; ++q) {
+    const uint32_t s = wave_sum(cnt[q]);
+    if (lane == 0) red[wave][q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * C) {
+    uint32_t s = 0;
+    for (int w = 0; w < TALLY_WAVES; ++w) s += red[w][threadIdx.x];
+    p.partial[(size_t)blockIdx.x * 3 * C + threadIdx.x] = s;
+  }
+}
+
+// one thread per counter adds the partials in block order; out (C, 4) = TP, FP, FN, TN
+__global__ __launch_bounds__(64) void k_seg_tallies_final(const uint32_t* __restrict__ partial, int nblocks, int C,
+                                                          long long S, long long* __restrict__ out) {
+  __shared__ long long tot[TALLY_NCNT];
+  const int q = threadIdx.x;
+  if (q < 3 * C) {
+    long long s = 0;
+    for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * 3 * C + q];
+    tot[q] = s;
+  }
+  __syncthreads();
+  if (q < C) {
+    const long long tp = tot[3 * q], pp = tot[3 * q + 1], lp = tot[3 * q + 2];
+    out[4 * q + 0] = tp;
+    out[4 * q + 1] = pp - tp;
+    out[4 * q + 2] = lp - tp;
+    out[4 * q + 3] = S - pp - lp + tp;
+  }
+}
+
+template <int C>
+static void launch_tallies(int mode, bool v4, dim3 g, dim3 b, hipStream_t st, const TallyParams& p) {
+  if (mode == EFFQ_SEG_ARGMAX) {
+    if (v4) hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_ARGMAX, 4, C>), g, b, 0, st, p);
+    else hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_ARGMAX, 1, C>), g, b, 0, st, p);
+  } else {
+    if (v4) hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_SIGMOID, 4, C>), g, b, 0, st, p);
+    else hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_SIGMOID, 1, C>), g, b, 0, st, p);
+  }
+}
+
+static bool make_axes(int D, int H, int W, int pd, int ph, int pw, int od, int oh, int ow, WinAxes& a) {
+  if (pd <= 0 || ph <= 0 || pw <= 0 || pd > D || ph > H || pw > W) return false;
+  if (od < 0 || oh < 0 || ow < 0 || od >= pd || oh >= ph || ow >= pw) return false;
+  a.D = D; a.H = H; a.W = W; a.pd = pd; a.ph = ph; a.pw = pw;
+  a.sd = pd - od; a.sh = ph - oh; a.sw = pw - ow;
+  a.nd = n_windows(D, pd, a.sd); a.nh = n_windows(H, ph, a.sh); a.nw = n_windows(W, pw, a.sw);
+  return true;
+}
+
+static unsigned grid_for(size_t items, size_t cap) {
+  size_t nb = (items + 255) / 256;
+  if (nb < 1) nb = 1;
+  return (unsigned)(nb < cap ? nb : cap);
+}
+
+}  // namespace effq
+using namespace effq;
+
+extern "C" {
+
+int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, int first, int count, float* out, void* stream) {
+  EFFQ_CHECK_ARG(vol && out && N > 0 && C > 0 && D > 0 && H > 0 && W > 0);
+  WinAxes a;
+  EFFQ_CHECK_ARG(make_axes(D, H, W, pd, ph, pw, od, oh, ow, a));
+  EFFQ_CHECK_ARG(first >= 0 && count > 0 && (long long)first + count <= (long long)a.nd * a.nh * a.nw);
+  const size_t total = (size_t)count * N * pd * ph * pw;
+  EFFQ_CHECK_ARG(total < (1u << 31));
+  const bool v4 = C % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  if (v4)
+    hipLaunchKernelGGL(k_window_gather<4>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
+                       N, C, first, (uint32_t)total);
+  else
+    hipLaunchKernelGGL(k_window_gather<1>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
+                       N, C, first, (uint32_t)total);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, float* out, void* stream) {
+  EFFQ_CHECK_ARG(win && out && N > 0 && C > 0 && C <= STITCH_MAX_C && D > 0 && H > 0 && W > 0);
+  WinAxes a;
+  EFFQ_CHECK_ARG(make_axes(D, H, W, pd, ph, pw, od, oh, ow, a));
+  const size_t total = (size_t)N * D * H * W;
+  EFFQ_CHECK_ARG(total < (1u << 31));
+  hipLaunchKernelGGL(k_window_stitch, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), win, out, a, N,
+                     C, (uint32_t)total);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
+                     long long* counts, void* ws, size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(logits && label && counts && ws && S > 0 && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
+  EFFQ_CHECK_ARG(mode == EFFQ_SEG_ARGMAX || mode == EFFQ_SEG_SIGMOID);
+  EFFQ_CHECK_ARG(fuse == EFFQ_SEG_FUSE_NONE || fuse == EFFQ_SEG_FUSE_AGG || fuse == EFFQ_SEG_FUSE_CON);
+  EFFQ_CHECK_ARG(ws_bytes >= EFFQ_SEG_TALLIES_WS_BYTES);
+  TallyParams p;
+  p.logits = logits; p.label = label; p.partial = static_cast<uint32_t*>(ws);
+  p.S = S; p.C = C; p.mode = mode; p.fuse = fuse; p.thresh = thresh;
+  const bool v4 = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(logits) & 15) | (reinterpret_cast<uintptr_t>(label) & 3)) == 0;
+  const unsigned nb = grid_for((size_t)(v4 ? S / 4 : S), TALLY_MAX_BLOCKS);
+  const dim3 g(nb), b(TALLY_THREADS);
+  const hipStream_t st = as_stream(stream);
+  switch (C) {
+    case 1: launch_tallies<1>(mode, v4, g, b, st, p); break;
+    case 2: launch_tallies<2>(mode, v4, g, b, st, p); break;
+    case 3: launch_tallies<3>(mode, v4, g, b, st, p); break;
+    case 4: launch_tallies<4>(mode, v4, g, b, st, p); break;
+    case 5: launch_tallies<5>(mode, v4, g, b, st, p); break;
+    case 6: launch_tallies<6>(mode, v4, g, b, st, p); break;
+    case 7: launch_tallies<7>(mode, v4, g, b, st, p); break;
+    default: launch_tallies<8>(mode, v4, g, b, st, p); break;
+  }
+  EFFQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_seg_tallies_final, dim3(1), dim3(64), 0, as_stream(stream), p.partial, (int)nb, C, S, counts);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+}  // extern "C"

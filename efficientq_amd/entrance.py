@@ -4,11 +4,12 @@
     python -m efficientq_amd.entrance ptq --config config/brats_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --pretrain pretrain/brats/round1/mid/state_0500.pkl --synthetic --lwq_batchsz 2 --snap_dir out/
 
-Neither repository ships data, so ``--synthetic`` replaces the reference's data cube by seeded synthetic
-volumes (``synth.py``); without ``--pretrain`` a seeded random-init network stands in for the checkpoint.
-Real data goes through ``calibrate.do_ptq(args, model_cube, data_cube, tester, snap_dir)`` with the
-reference's own ``data_cube`` / ``tester`` objects.  With ``torchrun --nproc-per-node N``
-the calibration volumes are sharded over N GPUs.
+Labelled volumes in the reference's layout are read with ``--data_dir`` / ``--split_dir`` (data.py): the
+calibration takes the train split, and ``--test_fp`` / the default test (unless ``--no_test``) validate the FP and
+the calibrated network on the val split (evaluate.validate_seg), writing ``<snap>/{fp,ptq}/metrics.csv``.
+``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing; without
+``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
+the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
 """
 from __future__ import annotations
 
@@ -21,6 +22,8 @@ import torch
 
 from . import calibrate as K
 from . import config as Cf
+from . import data as D
+from . import evaluate as E
 from . import synth
 
 
@@ -41,6 +44,32 @@ class _SnapshotWriter:
         else:
             torch.save({'state_dict': sd}, path)
         print(f'[entrance] wrote {path}')
+
+
+class _ValidationTester(_SnapshotWriter):
+    """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
+    <root>/<folder>/metrics.csv."""
+
+    def __init__(self, model, root, data_cube, task, rank=0):
+        super().__init__(model, root)
+        self.cube, self.task, self.rank = data_cube, task.lower(), rank
+
+    def test_as_is(self, folder='results', is_save_nii=False):
+        if self.rank != 0:
+            return
+        if self.cube.valloader is None:
+            print('[entrance] no val split: validation skipped')
+            return
+        t0 = time.time()
+        res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
+                             fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn)
+        out = os.path.join(self.root, folder)
+        os.makedirs(out, exist_ok=True)
+        E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
+        means = E.metric_means(res)
+        print(f'[entrance] {folder}: {len(res)} val cases in {time.time() - t0:.2f}s, per-class means:')
+        for c in range(len(means['dsc'])):
+            print(f'  class {c}: ' + ', '.join(f'{m} = {float(means[m][c]):.4f}' for m in E.METRICS))
 
 
 class _SyntheticCube:
@@ -87,7 +116,14 @@ def main(argv=None):
         cube['pretrain'] = args.pretrain
         print(f'[entrance] no --pretrain given: seeded random-init network saved to {args.pretrain}')
     if not args.synthetic:
-        raise SystemExit('no dataset is shipped: pass --synthetic, or call calibrate.do_ptq with your own data_cube')
+        if not (args.data_dir and args.split_dir):
+            raise SystemExit('no dataset is shipped: pass --data_dir and --split_dir, or --synthetic')
+        data_cube = D.get_data_cube(args)
+        with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
+            f.write(' '.join(sys.argv) + '\n')
+        rank = int(os.environ.get('RANK', '0'))
+        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank), snap)
+        return
     size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
     size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
     data_cube = _SyntheticCube(args.task, args.lwq_batchsz, size)

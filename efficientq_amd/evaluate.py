@@ -2,9 +2,10 @@
 
 Mirrors the reference's evaluation path for the calibrated network - ``validate_seg``'s split / per-patch
 forward / stitch (``utils/validate.py:212-264``, ``utils/transforms.py:784-852``) and ``validate_vs_label``
-(``utils/metrics.py:119-148``) - without the NIfTI / data-loader / Dice-table machinery, which stays out of
-scope.  The per-patch forward is the calibrated ``UResQ`` in quantized mode, i.e. every
-conv runs ``conv3d_quant_calib_step`` with the activation quantiser fused (``PTQConv.py:163-167``).
+(``utils/metrics.py:119-148``) - without the NIfTI export.  The per-patch forward is the calibrated ``UResQ`` in
+quantized mode, i.e. every conv runs ``conv3d_quant_calib_step`` with the activation quantiser fused
+(``PTQConv.py:163-167``).  ``validate_seg`` below is the HIP path of the reference's validation on labelled volumes
+(batched windows, stitch and confusion counts: DESIGN.md section 13).
 """
 from __future__ import annotations
 
@@ -118,3 +119,100 @@ def fp_vs_quantised_dice(model_q, images: torch.Tensor, task: str, fp_model=None
     else:
         target = (torch.sigmoid(fp_logits) >= 0.5).int()
     return validate_vs_label(out_q, target, task), out_q, fp_logits
+
+
+# ---- validation on labelled volumes (validate.py:212-264 with metrics.py:21-45): the HIP path -----------------------
+METRICS = ("dsc", "sens", "spec", "acc")
+WINDOW_BATCH_MAX = 16     # windows per forward at most (a BraTS case has 8 of 128^3)
+EPS = 1e-6                # metrics.py
+
+
+def metrics_from_counts(counts: torch.Tensor) -> dict:
+    """dice / sensitivity / specificity / accuracy per class from C x 4 counts (TP, FP, FN, TN), in the fp32
+    arithmetic of metrics.py:21-45 on those same integer sums (eps included)."""
+    counts = counts.to("cpu", torch.int64)
+    tp, fp, fn, tn = counts.unbind(1)
+    n = torch.tensor(float(counts[0].sum()), dtype=torch.float)
+    return {"dsc": (2 * tp.float() + EPS) / ((tp + fp).float() + (tp + fn).float() + EPS),
+            "sens": (tp.float() + EPS) / ((tp + fn).float() + EPS),
+            "spec": (tn.float() + EPS) / ((tn + fp).float() + EPS),
+            "acc": (tp + tn).float() / n}
+
+
+def _last_head(out) -> torch.Tensor:
+    """The last head of a model output: a list of heads, heads stacked in front (UResQ), or one N x C x ... tensor."""
+    if isinstance(out, (list, tuple)):
+        return out[-1]
+    return out[-1] if out.dim() == 6 else out
+
+
+@torch.no_grad()
+def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None):
+    """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
+    ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
+    brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
+    batch, the last head stitched (effq_window_stitch, bit for bit patch_to_image3d) and tallied against the label
+    (effq_seg_tallies).  As in SegMetricMC.evaluate_append the label's form decides the counting, whatever `task`:
+    one 0/1 channel per class (--multi_label) = sigmoid >= 0.5 per channel merged by `fuse`, class ids = argmax.
+    window_batch=None: the first window runs alone and its peak memory sizes the batches, half the free device memory
+    at most WINDOW_BATCH_MAX windows.  Returns one dict per case: name, counts (C x 4: TP, FP, FN, TN) and dsc / sens /
+    spec / acc per class."""
+    from .hip_ops import from_ndhwc, get_ops
+    if task not in ("lits", "brats"):
+        raise RuntimeError(f"Unknown task {task}")
+    dev = next(model.parameters()).device
+    ops = get_ops(dev)
+    p, o = _triple(patch_size), _triple(overlap)
+    bsz = window_batch
+    results = []
+    for images, labels in loader:
+        vol = images.to(dev, torch.float32).contiguous()
+        N = int(vol.shape[0])
+        nwin = 1
+        for n in ops.window_grid(vol.shape[-3:], p, o):
+            nwin *= n
+        buf = None
+        first = 0
+        while first < nwin:
+            cnt = min(bsz or 1, nwin - first)
+            if bsz is None:
+                torch.cuda.synchronize(dev)
+                base = torch.cuda.memory_allocated(dev)
+                torch.cuda.reset_peak_memory_stats(dev)
+            x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
+            last = _last_head(model(x))
+            if buf is None:
+                buf = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+            buf[first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+            if bsz is None:
+                per = max(1, torch.cuda.max_memory_allocated(dev) - base)
+                free, _ = torch.cuda.mem_get_info(dev)
+                bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
+            first += cnt
+        stitched = ops.window_stitch(buf, (N,) + tuple(buf.shape[-1:]) + tuple(vol.shape[-3:]), p, o)
+        lab = labels.to(dev).to(torch.uint8)
+        multi = lab.dim() == vol.dim()          # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append
+        for n in range(N):
+            counts = ops.seg_tallies(stitched[n], lab[n], "brats" if multi else "lits", fuse if multi else None).cpu()
+            i = len(results)
+            res = {"name": names[i] if names is not None else str(i), "counts": counts}
+            res.update(metrics_from_counts(counts))
+            results.append(res)
+    return results
+
+
+def write_metrics_csv(path: str, results) -> None:
+    """One row per subject and class: subject, class, dsc, sens, spec, acc, tp, fp, fn, tn."""
+    import csv
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn"))
+        for r in results:
+            for c in range(r["counts"].shape[0]):
+                wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
+                            [int(v) for v in r["counts"][c]])
+
+
+def metric_means(results) -> dict:
+    """Per-class mean over the cases of each metric."""
+    return {m: torch.stack([r[m] for r in results]).mean(0) for m in METRICS}

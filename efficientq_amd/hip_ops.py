@@ -965,6 +965,105 @@ class HipOps:
                                                self.stream), "conv3d_quant_calib_step")
         return out, sqerr
 
+    # -- validation on whole volumes (evaluate.validate_seg) ----------------------------------------------------
+    @staticmethod
+    def window_grid(dhw, patch, overlap) -> Tuple[int, int, int]:
+        """Windows per axis of evaluate.window_starts; raises on a window larger than the volume or an overlap that
+        is not smaller than the window."""
+        n = []
+        for s, p, o in zip(dhw, _triple(patch), _triple(overlap)):
+            if p <= 0 or p > s:
+                raise _lib.EffqError(f"window extent {p} outside 1..{s}")
+            if o < 0 or o >= p:
+                raise _lib.EffqError(f"overlap {o} must lie in 0..{p - 1}")
+            n.append(len(range(0, s - p, p - o)) + 1)
+        return tuple(n)
+
+    def window_gather(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None):
+        """Windows first .. first+count-1 of the N x C x D x H x W volume as one (count*N, pd, ph, pw, C)
+        channels-last batch, window-major (effq_window_gather)."""
+        x = self._f32(vol)
+        if x.dim() != 5:
+            raise _lib.EffqError(f"window_gather: expected N x C x D x H x W, got {tuple(x.shape)}")
+        N, Cc, D, H, W = (int(i) for i in x.shape)
+        p, o = _triple(patch), _triple(overlap)
+        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        count = nwin - first if count is None else int(count)
+        if first < 0 or count <= 0 or first + count > nwin:
+            raise _lib.EffqError(f"windows {first}..{first + count - 1} of {nwin}")
+        out = torch.empty(count * N, p[0], p[1], p[2], Cc, dtype=torch.float32, device=self.device)
+        check(self.lib.effq_window_gather(_ptr(x), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], int(first), count,
+                                          _ptr(out), self.stream), "effq_window_gather")
+        return out
+
+    def window_stitch(self, win: torch.Tensor, shape, patch, overlap) -> torch.Tensor:
+        """Every window's logits, (nwin*N, pd, ph, pw, C) channels-last and window-major, stitched to the N x C x D x H
+        x W volume `shape` as the mean over the covering windows (effq_window_stitch; evaluate.patch_to_image3d)."""
+        w = self._f32(win)
+        N, Cc, D, H, W = (int(i) for i in shape)
+        p, o = _triple(patch), _triple(overlap)
+        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        if tuple(w.shape) != (nwin * N, p[0], p[1], p[2], Cc):
+            raise _lib.EffqError(f"window_stitch: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
+        if not 0 < Cc <= 8:
+            raise _lib.EffqError(f"window_stitch: {Cc} channels, at most 8")
+        out = torch.empty(N, Cc, D, H, W, dtype=torch.float32, device=self.device)
+        check(self.lib.effq_window_stitch(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], _ptr(out),
+                                          self.stream), "effq_window_stitch")
+        return out
+
+    def sigmoid_threshold(self) -> float:
+        """The least fp32 x at which the framework's fp32 `torch.sigmoid(x) >= 0.5` holds on this device.  Near 0 it is
+        not 0: a small negative logit rounds to exactly 0.5.  Found by bisection over the bit patterns of -x, then
+        checked on the 2^17 floats around it; cached."""
+        if getattr(self, "_sig_thresh", None) is not None:
+            return self._sig_thresh
+
+        def decide(mags):       # magnitudes as int32 bit patterns -> decision of sigmoid(-mag) >= 0.5
+            x = -torch.tensor(mags, dtype=torch.int32).view(torch.float32).to(self.device)
+            return (torch.sigmoid(x) >= 0.5).cpu()
+
+        lo, hi = 0, 0x3F800000            # sigmoid(-0) = 0.5 holds, sigmoid(-1) < 0.5
+        while hi - lo > 1:
+            cand = sorted({lo + (hi - lo) * k // 4097 for k in range(1, 4097)} - {lo, hi})
+            ok = decide(cand)
+            bad = (~ok).nonzero()
+            first_bad = int(bad[0]) if len(bad) else len(cand)
+            lo = cand[first_bad - 1] if first_bad > 0 else lo
+            hi = cand[first_bad] if first_bad < len(cand) else hi
+        dense = list(range(max(0, lo - (1 << 16)), lo + (1 << 16)))
+        if not torch.equal(decide(dense), torch.tensor(dense) <= lo):
+            raise _lib.EffqError("torch.sigmoid(x) >= 0.5 is not monotone around its threshold")
+        self._sig_thresh = float(-torch.tensor([lo], dtype=torch.int32).view(torch.float32).item())
+        return self._sig_thresh
+
+    def seg_tallies(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
+        """TP, FP, FN, TN per class (C x 4 int64) of one case's stitched logits (C x D x H x W) against its label
+        (effq_seg_tallies): lits = argmax over the channels vs class ids (D x H x W); brats = sigmoid >= 0.5 per channel,
+        merged by `fuse` (None / 'agg' / 'con'), vs a C x D x H x W 0/1 label."""
+        x = self._f32(logits)
+        Cc, S = int(x.shape[0]), x[0].numel()
+        if task == "lits":
+            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
+        elif task == "brats":
+            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
+        else:
+            raise _lib.EffqError(f"Unknown task {task}")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
+            raise _lib.EffqError(f"seg_tallies: merge type {fuse!r} for task {task}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_tallies: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
+            raise _lib.EffqError(f"seg_tallies: label {tuple(label.shape)} {label.dtype} on {label.device}, "
+                                 f"needs {lshape} torch.uint8 on {x.device}")
+        lab = label.contiguous()
+        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
+        ws = self._workspace("seg_tallies", _lib.SEG_TALLIES_WS_BYTES)
+        check(self.lib.effq_seg_tallies(_ptr(x), _ptr(lab), Cc, S, mode, _lib.SEG_FUSE[key], thresh, _ptr(counts),
+                                        _ptr(ws), ws.numel(), self.stream), "effq_seg_tallies")
+        return counts
+
 
 _OPS = {}
 

@@ -529,6 +529,31 @@ size_t effq_packed_bytes(size_t n, int bits);
 int effq_pack_levels(const uint8_t* idx, size_t n, int bits, uint8_t* packed, void* stream);
 int effq_unpack_levels(const uint8_t* packed, size_t n, int bits, uint8_t* idx, void* stream);
 
+/* ---- validation on whole volumes (evaluate.validate_seg; utils/validate.py:212-264, utils/transforms.py:784-852,
+ * utils/metrics.py) -------------------------------------------------------------------------------------------------
+ * Windows of extent (pd, ph, pw) and overlap (od, oh, ow) < extent: along each axis the starts step by extent - overlap
+ * while a whole window still ends strictly before the border, then one window lies flush with it; windows are numbered
+ * in (d, h, w) raster order (evaluate.window_starts / image_to_patch3d).
+ *
+ * Gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1, channels-last.
+ * Stitch: win (nwin, N, pd, ph, pw, C) holding every window -> out (N, C, D, H, W): each voxel is the sum of its
+ *   covering windows in raster order over their count, bit for bit evaluate.patch_to_image3d.  C <= 8.
+ * Tallies: logits (C, S) of one case and its label -> counts (C, 4) int64 = TP, FP, FN, TN per class.
+ *   EFFQ_SEG_ARGMAX: label (S) class ids; prediction = the first largest channel (torch.max).
+ *   EFFQ_SEG_SIGMOID: label (C, S) 0/1; channel c predicted when logit >= thresh, where thresh is the least float at
+ *   which the framework's fp32 sigmoid reaches 0.5; then merged across channels by `fuse` (misc.merge_label_basic:
+ *   AGG p[i] = any(p[i:]), CON p[i] = all(p[:i+1])).  ws: EFFQ_SEG_TALLIES_WS_BYTES of scratch. */
+#define EFFQ_SEG_TALLIES_MAX_CLASSES 8
+#define EFFQ_SEG_TALLIES_WS_BYTES (1024 * 3 * EFFQ_SEG_TALLIES_MAX_CLASSES * 4)
+enum { EFFQ_SEG_ARGMAX = 0, EFFQ_SEG_SIGMOID = 1 };
+enum { EFFQ_SEG_FUSE_NONE = 0, EFFQ_SEG_FUSE_AGG = 1, EFFQ_SEG_FUSE_CON = 2 };
+int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, int first, int count, float* out, void* stream);
+int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, float* out, void* stream);
+int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
+                     long long* counts, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
