@@ -907,16 +907,16 @@ class HipOps:
         alpha first); returns (out NDHWC fp32, [sum err^2, sum att err^2] device doubles)."""
         if xidx.dtype != torch.uint8:
             raise _lib.EffqError("conv_forward_i8 wants uint8 level ids")
+        att_f = self._f32(att) if att is not None else None
+        _check_shapes(geom, xidx, G, bias, y_ndhwc, att_f)
         lm1 = int(w_levels) - 1
         a32 = w_state.reshape(-1)[0].to(torch.float32)
         # the integer numerators 2 * level - (Lw - 1) of the weights: G / f32(alpha) is b = level * d - 1 to an ulp
         Gq = (2.0 * torch.round((self._f32(G) / a32 + 1.0) * (0.5 * lm1)) - lm1).to(torch.int8).contiguous()
-        _check_shapes(geom, xidx, Gq, bias, y_ndhwc)
         al = self._f32(act_alpha.reshape(1))
         y = self._f32(y_ndhwc)
         out = torch.empty_like(y)
         sq = torch.zeros(2, dtype=torch.float64, device=self.device)
-        att_f = self._f32(att) if att is not None else None
         st = w_state.to(torch.float64).contiguous()
         ws = self._workspace("conv_i8", self.lib.effq_conv_i8_ws_bytes(C.byref(geom)))
         check(self.lib.conv3d_quant_forward_i8(_ptr(xidx), _ptr(Gq), _ptr(self._f32(bias) if bias is not None else None),
