@@ -179,6 +179,7 @@ SIGNATURES = {
     "effq_window_gather": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
+    "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -186,6 +187,8 @@ SEG_TALLIES_WS_BYTES = 1024 * 3 * 8 * 4
 SEG_TALLIES_MAX_CLASSES = 8
 SEG_ARGMAX, SEG_SIGMOID = 0, 1
 SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
+# include/effq_hip.h: the label rules of effq_seg_labels
+SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}
 
 _lib = None
 

@@ -5,7 +5,8 @@ snapshots.  Differences, all deliberate and MI355X-first:
   * FP targets and masks stay in HBM (the reference parks them on the host, hooks.py:6);
   * with ``torch.distributed`` initialised, ``data_batch`` is this rank's shard of the calibration
     volumes and every volume-summed statistic is all-reduced (RCCL), see qconv.SumReducer;
-  * NIfTI export needs nibabel and is skipped when it is absent (evaluation is out of scope).
+  * the Qseg / FPseg NIfTI maps of the calibration volumes are written with ``--save_nii`` only, by the HIP label
+    kernel and the nibabel-free writer of nifti.py.
 """
 from __future__ import annotations
 
@@ -324,7 +325,8 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
         fid.write(f'{(t2 - t0) / 60:.3f} min.')
     with open(P.join(snap_dir, 'layer_loss.txt'), 'w') as fid:
         fid.write('\n'.join(res['layer_loss']))
-    _save_nifti(res, args.task, snap_dir)
+    if args.save_nii:
+        _save_nifti(res, args.task, snap_dir)
 
     if not args.no_test:
         tester.test_as_is('ptq', args.save_nii)
@@ -336,15 +338,30 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     return res
 
 
+def _volume_offset(n: int) -> int:
+    """Index of this rank's first calibration volume in the whole batch: the volume count of the lower ranks."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return 0
+    sizes = [None] * dist.get_world_size()
+    dist.all_gather_object(sizes, int(n))
+    return sum(sizes[:dist.get_rank()])
+
+
 def _save_nifti(res, task, snap_dir):
-    try:
-        import nibabel as nib
-        import numpy as np
-    except ImportError:
-        return
+    """Qseg{i}.nii.gz / FPseg{i}.nii.gz of the calibration volumes (ptqer.py:372-377, metrics.extract_nii): the last
+    head's class ids for lits, get_pred_brats_con_merge for brats (effq_seg_labels), uint8 with the identity affine.
+    i is the volume's index in the whole calibration batch, so data-parallel ranks write different files."""
+    from .hip_ops import get_ops
+    from .nifti import write_nifti
+    if task not in ('lits', 'brats'):
+        raise RuntimeError(f'Unknown task {task}')
+    rule, fuse = ('argmax', None) if task == 'lits' else ('rank', 'con')
+    first = None
     for tag, out in (('Qseg', res['output_q']), ('FPseg', res['output_fp'])):
         head = out[-1]
-        pred = get_pred_lits(head) if task == 'lits' else get_pred_brats(head)
-        for i in range(pred.shape[0]):
-            nib.Nifti1Image(pred[i].cpu().numpy().astype(np.uint8), np.eye(4)).to_filename(
-                P.join(snap_dir, f'{tag}{i}.nii.gz'))
+        maps = get_ops(head.device).seg_labels(head, rule, fuse).cpu().numpy()
+        if first is None:
+            first = _volume_offset(len(maps))
+        for i, m in enumerate(maps):
+            write_nifti(P.join(snap_dir, f'{tag}{first + i}.nii.gz'), m)

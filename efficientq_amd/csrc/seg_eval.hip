@@ -1,6 +1,7 @@
 // Validation of a segmentation network on whole volumes (evaluate.validate_seg): the overlapped windows of a volume
 // gathered into one channels-last batch, the per-window logits stitched back to the volume, and the per-class confusion
-// counts of the stitched logits against the label.  All three stream HBM once and do no arithmetic to speak of.
+// counts of the stitched logits against the label, and the label maps written for the viewer (--save_nii).  All four
+// stream HBM once and do no arithmetic to speak of.
 //
 // Windows: along each axis the starts are  min(i * (patch - overlap), size - patch)  for i = 0 .. n-1 with
 // n = ceil((size - patch) / (patch - overlap)) + 1, i.e. evaluate.window_starts: steps while a whole patch ends strictly
@@ -253,6 +254,117 @@ __global__ __launch_bounds__(64) void k_seg_tallies_final(const uint32_t* __rest
   }
 }
 
+// ---- label maps ---------------------------------------------------------------------------------------------------
+// The decisions of decide<MODE, C> (the tallies' own, so the maps and the counts cannot disagree) turned into a label
+// per voxel, or into C 0/1 planes.  One thread per VEC voxels, 16-B logit loads per channel, one store per thread and
+// plane; no reductions, no atomics.
+constexpr int LABEL_THREADS = 256;
+constexpr int LABEL_MAX_BLOCKS = 2048;   // per case (gridDim.y = N); grid-stride beyond
+
+struct LabelParams {
+  const float* logits;   // (N, C, S)
+  void* out;             // (N, S) uint8 / uint16, or (N, C, S) uint8 for EFFQ_SEG_LABEL_PLANES
+  long long S;
+  int fuse;
+  float thresh;
+};
+
+template <int RULE, int C>
+__device__ __forceinline__ uint32_t label_of(uint32_t pred) {
+  if constexpr (RULE == EFFQ_SEG_LABEL_ARGMAX) {
+    return 31 - __builtin_clz(pred);                  // pred = 1 << winning class
+  } else if constexpr (RULE == EFFQ_SEG_LABEL_BRATS) {
+    // misc.merge_label_brats, later assignments winning: WT -> 1, WT and not TC -> 2, ET -> 4
+    uint32_t l = 0;
+    if (pred & 1u) l = 1;
+    if ((pred & 3u) == 1u) l = 2;
+    if (pred & 4u) l = 4;
+    return l;
+  } else {                                            // RANK: i + 1 of the highest set channel, 0 when none
+    return pred ? 32 - __builtin_clz(pred) : 0u;
+  }
+}
+
+template <int MODE, int RULE, int VEC, int C, typename T>
+__global__ __launch_bounds__(LABEL_THREADS) void k_seg_labels(LabelParams p) {
+  const long long groups = p.S / VEC;
+  const size_t n = blockIdx.y;
+  const float* x = p.logits + n * C * p.S;
+  const uint8_t nolab[C] = {};                        // decide() wants a label; its gt bits are not used
+  for (long long g = (long long)blockIdx.x * LABEL_THREADS + threadIdx.x; g < groups;
+       g += (long long)gridDim.x * LABEL_THREADS) {
+    float v[VEC][C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      if constexpr (VEC == 4) {
+        const float4 f = *reinterpret_cast<const float4*>(x + c * p.S + g * 4);
+        v[0][c] = f.x; v[1][c] = f.y; v[2][c] = f.z; v[3][c] = f.w;
+      } else {
+        v[0][c] = x[c * p.S + g];
+      }
+    }
+    uint32_t pred[VEC];
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) {
+      uint32_t gt;
+      decide<MODE, C>(v[u], nolab, p.fuse, p.thresh, pred[u], gt);
+    }
+    if constexpr (RULE == EFFQ_SEG_LABEL_PLANES) {
+      uint8_t* o = static_cast<uint8_t*>(p.out) + n * C * p.S;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        if constexpr (VEC == 4) {
+          const uchar4 b = make_uchar4((pred[0] >> c) & 1u, (pred[1] >> c) & 1u, (pred[2] >> c) & 1u,
+                                       (pred[3] >> c) & 1u);
+          *reinterpret_cast<uchar4*>(o + c * p.S + g * 4) = b;
+        } else {
+          o[c * p.S + g] = (pred[0] >> c) & 1u;
+        }
+      }
+    } else {
+      T* o = static_cast<T*>(p.out) + n * p.S;
+      if constexpr (VEC == 4) {
+        const uint32_t l0 = label_of<RULE, C>(pred[0]), l1 = label_of<RULE, C>(pred[1]);
+        const uint32_t l2 = label_of<RULE, C>(pred[2]), l3 = label_of<RULE, C>(pred[3]);
+        if constexpr (sizeof(T) == 1)
+          *reinterpret_cast<uchar4*>(o + g * 4) = make_uchar4(l0, l1, l2, l3);
+        else
+          *reinterpret_cast<ushort4*>(o + g * 4) = make_ushort4(l0, l1, l2, l3);
+      } else {
+        o[g] = (T)label_of<RULE, C>(pred[0]);
+      }
+    }
+  }
+}
+
+template <int RULE, int C, typename T>
+static void launch_labels_t(bool v4, dim3 g, hipStream_t st, const LabelParams& p) {
+  constexpr int MODE = RULE == EFFQ_SEG_LABEL_ARGMAX ? EFFQ_SEG_ARGMAX : EFFQ_SEG_SIGMOID;
+  if (v4) hipLaunchKernelGGL((k_seg_labels<MODE, RULE, 4, C, T>), g, dim3(LABEL_THREADS), 0, st, p);
+  else hipLaunchKernelGGL((k_seg_labels<MODE, RULE, 1, C, T>), g, dim3(LABEL_THREADS), 0, st, p);
+}
+
+template <int C>
+static void launch_labels(int rule, bool u16, bool v4, dim3 g, hipStream_t st, const LabelParams& p) {
+  switch (rule) {
+    case EFFQ_SEG_LABEL_ARGMAX:
+      if (u16) launch_labels_t<EFFQ_SEG_LABEL_ARGMAX, C, uint16_t>(v4, g, st, p);
+      else launch_labels_t<EFFQ_SEG_LABEL_ARGMAX, C, uint8_t>(v4, g, st, p);
+      break;
+    case EFFQ_SEG_LABEL_BRATS:
+      if (u16) launch_labels_t<EFFQ_SEG_LABEL_BRATS, C, uint16_t>(v4, g, st, p);
+      else launch_labels_t<EFFQ_SEG_LABEL_BRATS, C, uint8_t>(v4, g, st, p);
+      break;
+    case EFFQ_SEG_LABEL_RANK:
+      if (u16) launch_labels_t<EFFQ_SEG_LABEL_RANK, C, uint16_t>(v4, g, st, p);
+      else launch_labels_t<EFFQ_SEG_LABEL_RANK, C, uint8_t>(v4, g, st, p);
+      break;
+    default:
+      launch_labels_t<EFFQ_SEG_LABEL_PLANES, C, uint8_t>(v4, g, st, p);
+      break;
+  }
+}
+
 template <int C>
 static void launch_tallies(int mode, bool v4, dim3 g, dim3 b, hipStream_t st, const TallyParams& p) {
   if (mode == EFFQ_SEG_ARGMAX) {
@@ -341,6 +453,36 @@ int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long
   }
   EFFQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_seg_tallies_final, dim3(1), dim3(64), 0, as_stream(stream), p.partial, (int)nb, C, S, counts);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+int effq_seg_labels(const float* logits, int N, int C, long long S, int rule, int fuse, float thresh, int out_bytes,
+                    void* out, void* stream) {
+  EFFQ_CHECK_ARG(logits && out && N > 0 && N <= 65535 && S > 0 && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
+  EFFQ_CHECK_ARG(rule == EFFQ_SEG_LABEL_ARGMAX || rule == EFFQ_SEG_LABEL_BRATS || rule == EFFQ_SEG_LABEL_RANK ||
+                 rule == EFFQ_SEG_LABEL_PLANES);
+  EFFQ_CHECK_ARG(fuse == EFFQ_SEG_FUSE_NONE || fuse == EFFQ_SEG_FUSE_AGG || fuse == EFFQ_SEG_FUSE_CON);
+  EFFQ_CHECK_ARG(rule != EFFQ_SEG_LABEL_ARGMAX || fuse == EFFQ_SEG_FUSE_NONE);
+  EFFQ_CHECK_ARG(rule != EFFQ_SEG_LABEL_BRATS || C >= 3);
+  EFFQ_CHECK_ARG(out_bytes == 1 || (out_bytes == 2 && rule != EFFQ_SEG_LABEL_PLANES));
+  LabelParams p;
+  p.logits = logits; p.out = out; p.S = S; p.fuse = fuse; p.thresh = thresh;
+  const bool v4 = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(logits) & 15) |
+                                 (reinterpret_cast<uintptr_t>(out) & (4 * out_bytes - 1))) == 0;
+  const dim3 g(grid_for((size_t)(v4 ? S / 4 : S), LABEL_MAX_BLOCKS), N);
+  const hipStream_t st = as_stream(stream);
+  const bool u16 = out_bytes == 2;
+  switch (C) {
+    case 1: launch_labels<1>(rule, u16, v4, g, st, p); break;
+    case 2: launch_labels<2>(rule, u16, v4, g, st, p); break;
+    case 3: launch_labels<3>(rule, u16, v4, g, st, p); break;
+    case 4: launch_labels<4>(rule, u16, v4, g, st, p); break;
+    case 5: launch_labels<5>(rule, u16, v4, g, st, p); break;
+    case 6: launch_labels<6>(rule, u16, v4, g, st, p); break;
+    case 7: launch_labels<7>(rule, u16, v4, g, st, p); break;
+    default: launch_labels<8>(rule, u16, v4, g, st, p); break;
+  }
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

@@ -114,6 +114,7 @@ class DataCube:
         mk = lambda names: SegVolumes(data_dir, names, MODALITIES[task], access_type, fn)
         self.trainseqloader = torch.utils.data.DataLoader(mk(self.train_sn), 1, shuffle=False)
         self.valloader = torch.utils.data.DataLoader(mk(self.val_sn), 1, shuffle=False) if self.val_sn else None
+        self.multi_label = multi_label
         self.multilabel_fusetype = merge_type
         self.patch_size = parse_patch(patch_size) if patch_size else PATCH_DEFAULT[task]
         self.overlap = OVERLAP_DEFAULT

@@ -6,7 +6,8 @@
 
 Labelled volumes in the reference's layout are read with ``--data_dir`` / ``--split_dir`` (data.py): the
 calibration takes the train split, and ``--test_fp`` / the default test (unless ``--no_test``) validate the FP and
-the calibrated network on the val split (evaluate.validate_seg), writing ``<snap>/{fp,ptq}/metrics.csv``.
+the calibrated network on the val split (evaluate.validate_seg), writing ``<snap>/{fp,ptq}/metrics.csv``;
+``--save_nii`` adds the predicted label maps ``<snap>/{fp,ptq}/val/<subject>.nii.gz`` and ``<snap>/{Q,FP}seg<i>.nii.gz``.
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
 the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
@@ -48,7 +49,8 @@ class _SnapshotWriter:
 
 class _ValidationTester(_SnapshotWriter):
     """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
-    <root>/<folder>/metrics.csv."""
+    <root>/<folder>/metrics.csv, with is_save_nii also every val subject's predicted map as
+    <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final)."""
 
     def __init__(self, model, root, data_cube, task, rank=0):
         super().__init__(model, root)
@@ -61,9 +63,11 @@ class _ValidationTester(_SnapshotWriter):
             print('[entrance] no val split: validation skipped')
             return
         t0 = time.time()
-        res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
-                             fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn)
         out = os.path.join(self.root, folder)
+        res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
+                             fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
+                             save_dir=os.path.join(out, 'val') if is_save_nii else None,
+                             multi_label=getattr(self.cube, 'multi_label', None))
         os.makedirs(out, exist_ok=True)
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         means = E.metric_means(res)

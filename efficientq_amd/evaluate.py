@@ -2,15 +2,17 @@
 
 Mirrors the reference's evaluation path for the calibrated network - ``validate_seg``'s split / per-patch
 forward / stitch (``utils/validate.py:212-264``, ``utils/transforms.py:784-852``) and ``validate_vs_label``
-(``utils/metrics.py:119-148``) - without the NIfTI export.  The per-patch forward is the calibrated ``UResQ`` in
+(``utils/metrics.py:119-148``).  The per-patch forward is the calibrated ``UResQ`` in
 quantized mode, i.e. every conv runs ``conv3d_quant_calib_step`` with the activation quantiser fused
 (``PTQConv.py:163-167``).  ``validate_seg`` below is the HIP path of the reference's validation on labelled volumes
-(batched windows, stitch and confusion counts: DESIGN.md section 13).
+(batched windows, stitch, confusion counts and, with ``save_dir``, the NIfTI label maps: DESIGN.md section 13).
 """
 from __future__ import annotations
 
+import os
 from typing import List, Sequence
 
+import numpy as np
 import torch
 
 
@@ -146,8 +148,26 @@ def _last_head(out) -> torch.Tensor:
     return out[-1] if out.dim() == 6 else out
 
 
+def label_rule(multi: bool, multi_label=None, task: str = "lits") -> str:
+    """The seg_labels rule of a validation map (validate.py:247-252 with definer.py's merge_label_func): class ids
+    (argmax) without --multi_label, merge_label_brats for --multi_label brats, the merged planes (merge_label_basic)
+    for --multi_label lits.  `multi_label` None with a multi-channel label: the task's own."""
+    if not multi:
+        return "argmax"
+    key = (multi_label or task).lower()
+    if key not in ("brats", "lits"):
+        raise RuntimeError(f"Unknown multi_label {multi_label}")
+    return "brats" if key == "brats" else "planes"
+
+
+def _write_map(path, host, dtype):
+    from .nifti import write_nifti
+    write_nifti(path, np.asarray(host, dtype=dtype))
+
+
 @torch.no_grad()
-def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None):
+def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
+                 save_dir=None, label_dtype=np.uint16, multi_label=None):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -156,7 +176,10 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     one 0/1 channel per class (--multi_label) = sigmoid >= 0.5 per channel merged by `fuse`, class ids = argmax.
     window_batch=None: the first window runs alone and its peak memory sizes the batches, half the free device memory
     at most WINDOW_BATCH_MAX windows.  Returns one dict per case: name, counts (C x 4: TP, FP, FN, TN) and dsc / sens /
-    spec / acc per class."""
+    spec / acc per class.
+    save_dir: also write each case's predicted map, from the same decisions (effq_seg_labels, rule label_rule(...,
+    multi_label, task)), to <save_dir>/<name>.nii.gz as `label_dtype` with the identity affine (validate.py:247-260).
+    The files are written by one background thread while the device goes on; all are written when this returns."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -165,39 +188,62 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     p, o = _triple(patch_size), _triple(overlap)
     bsz = window_batch
     results = []
-    for images, labels in loader:
-        vol = images.to(dev, torch.float32).contiguous()
-        N = int(vol.shape[0])
-        nwin = 1
-        for n in ops.window_grid(vol.shape[-3:], p, o):
-            nwin *= n
-        buf = None
-        first = 0
-        while first < nwin:
-            cnt = min(bsz or 1, nwin - first)
-            if bsz is None:
-                torch.cuda.synchronize(dev)
-                base = torch.cuda.memory_allocated(dev)
-                torch.cuda.reset_peak_memory_stats(dev)
-            x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
-            last = _last_head(model(x))
-            if buf is None:
-                buf = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-            buf[first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
-            if bsz is None:
-                per = max(1, torch.cuda.max_memory_allocated(dev) - base)
-                free, _ = torch.cuda.mem_get_info(dev)
-                bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
-            first += cnt
-        stitched = ops.window_stitch(buf, (N,) + tuple(buf.shape[-1:]) + tuple(vol.shape[-3:]), p, o)
-        lab = labels.to(dev).to(torch.uint8)
-        multi = lab.dim() == vol.dim()          # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append
-        for n in range(N):
-            counts = ops.seg_tallies(stitched[n], lab[n], "brats" if multi else "lits", fuse if multi else None).cpu()
-            i = len(results)
-            res = {"name": names[i] if names is not None else str(i), "counts": counts}
-            res.update(metrics_from_counts(counts))
-            results.append(res)
+    pool, writes = None, []
+    if save_dir is not None:
+        from concurrent.futures import ThreadPoolExecutor
+        map_dtype = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16}.get(np.dtype(label_dtype))
+        if map_dtype is None:
+            raise RuntimeError(f"label maps are written as uint8 or uint16, not {np.dtype(label_dtype)}")
+        os.makedirs(save_dir, exist_ok=True)
+        pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-nifti")
+    try:
+        for images, labels in loader:
+            vol = images.to(dev, torch.float32).contiguous()
+            N = int(vol.shape[0])
+            nwin = 1
+            for n in ops.window_grid(vol.shape[-3:], p, o):
+                nwin *= n
+            buf = None
+            first = 0
+            while first < nwin:
+                cnt = min(bsz or 1, nwin - first)
+                if bsz is None:
+                    torch.cuda.synchronize(dev)
+                    base = torch.cuda.memory_allocated(dev)
+                    torch.cuda.reset_peak_memory_stats(dev)
+                x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
+                last = _last_head(model(x))
+                if buf is None:
+                    buf = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+                buf[first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+                if bsz is None:
+                    per = max(1, torch.cuda.max_memory_allocated(dev) - base)
+                    free, _ = torch.cuda.mem_get_info(dev)
+                    bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
+                first += cnt
+            stitched = ops.window_stitch(buf, (N,) + tuple(buf.shape[-1:]) + tuple(vol.shape[-3:]), p, o)
+            lab = labels.to(dev).to(torch.uint8)
+            multi = lab.dim() == vol.dim()      # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append
+            maps = None
+            if pool is not None:                # the planes are 0/1 uint8 on the device, cast when written
+                rule = label_rule(multi, multi_label, task)
+                maps = ops.seg_labels(stitched, rule, fuse if multi else None,
+                                      torch.uint8 if rule == "planes" else map_dtype).cpu().numpy()
+            for n in range(N):
+                counts = ops.seg_tallies(stitched[n], lab[n], "brats" if multi else "lits",
+                                         fuse if multi else None).cpu()
+                i = len(results)
+                res = {"name": names[i] if names is not None else str(i), "counts": counts}
+                res.update(metrics_from_counts(counts))
+                results.append(res)
+                if maps is not None:
+                    writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
+                                              label_dtype))
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True)
+    for w in writes:
+        w.result()                              # re-raises a failed write
     return results
 
 

@@ -1064,6 +1064,36 @@ class HipOps:
                                         _ptr(ws), ws.numel(), self.stream), "effq_seg_tallies")
         return counts
 
+    def seg_labels(self, logits: torch.Tensor, rule: str, fuse: Optional[str] = None, dtype=torch.uint8):
+        """Label maps of N cases' logits (N x C x spatial, fp32) from the decisions seg_tallies counts
+        (effq_seg_labels).  rule 'argmax': class ids of torch.max (fuse None); 'brats': merge_label_brats of the
+        sigmoid >= 0.5 channels merged by `fuse` (0 / 1 / 2 / 4, C >= 3); 'rank': i + 1 of the highest set merged
+        channel (fuse 'con': get_pred_brats_con_merge); 'planes': the merged 0/1 channels themselves.  Returns
+        N x spatial of `dtype` (torch.uint8 / torch.uint16), or N x C x spatial uint8 for 'planes'."""
+        x = self._f32(logits)
+        if x.dim() < 3:
+            raise _lib.EffqError(f"seg_labels: expected N x C x spatial logits, got {tuple(x.shape)}")
+        N, Cc, S = int(x.shape[0]), int(x.shape[1]), math.prod(x.shape[2:])
+        if rule not in _lib.SEG_LABEL_RULES:
+            raise _lib.EffqError(f"seg_labels: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (rule == "argmax" and key is not None):
+            raise _lib.EffqError(f"seg_labels: merge type {fuse!r} for rule {rule}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_labels: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if rule == "brats" and Cc < 3:
+            raise _lib.EffqError(f"seg_labels: the brats rule needs 3 channels or more, got {Cc}")
+        if dtype not in (torch.uint8, torch.uint16) or (rule == "planes" and dtype != torch.uint8):
+            raise _lib.EffqError(f"seg_labels: output {dtype} for rule {rule}")
+        if N == 0 or S == 0 or N > 65535:
+            raise _lib.EffqError(f"seg_labels: {N} cases of {S} voxels")
+        shape = tuple(x.shape) if rule == "planes" else (N,) + tuple(x.shape[2:])
+        out = torch.empty(shape, dtype=dtype, device=self.device)
+        thresh = 0.0 if rule == "argmax" else self.sigmoid_threshold()
+        check(self.lib.effq_seg_labels(_ptr(x), N, Cc, S, _lib.SEG_LABEL_RULES[rule], _lib.SEG_FUSE[key], thresh,
+                                       out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
+        return out
+
 
 _OPS = {}
 

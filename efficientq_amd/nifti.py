@@ -1,0 +1,112 @@
+"""Single-file NIfTI-1 (``.nii`` / ``.nii.gz``) label maps without nibabel: what ``--save_nii`` writes.
+
+The writer produces the file ``nib.Nifti1Image(array, affine).to_filename(path)`` describes for an integer label map
+(utils/validate.py:247-260, metrics.extract_nii): the 348-byte header, 4 zero extension bytes, the data from byte 352,
+``sform_code`` 2 (aligned) with the affine's rows, ``qform_code`` 0, unit ``pixdim``.  The data block is little-endian
+and in Fortran order (first array axis fastest), so a NIfTI reader gets back ``array`` with the same axes.  ``.gz``
+files carry no name and ``mtime`` 0: the same map always gives the same bytes.
+
+The reader is the inverse for these files (uint8 / uint16 data, either byte order) and rejects anything else.
+"""
+from __future__ import annotations
+
+import gzip
+import struct
+
+import numpy as np
+
+HEADER_BYTES = 348
+VOX_OFFSET = 352
+MAGIC = b"n+1\0"
+DATATYPES = {2: np.dtype(np.uint8), 512: np.dtype(np.uint16)}      # NIfTI datatype code -> dtype
+_CODES = {v: k for k, v in DATATYPES.items()}
+GZIP_LEVEL = 1
+
+# (name, struct format, offset) of the fields used here, NIfTI-1 spec (nifti1.h)
+FIELDS = (("sizeof_hdr", "i", 0), ("dim", "8h", 40), ("datatype", "h", 70), ("bitpix", "h", 72),
+          ("pixdim", "8f", 76), ("vox_offset", "f", 108), ("scl_slope", "f", 112), ("scl_inter", "f", 116),
+          ("qform_code", "h", 252), ("sform_code", "h", 254), ("quatern", "6f", 256), ("srow_x", "4f", 280),
+          ("srow_y", "4f", 296), ("srow_z", "4f", 312), ("magic", "4s", 344))
+
+
+def _header(shape, dtype: np.dtype, affine: np.ndarray) -> bytes:
+    hdr = bytearray(HEADER_BYTES)
+    dim = [len(shape)] + list(shape) + [1] * (7 - len(shape))
+    values = {"sizeof_hdr": (HEADER_BYTES,), "dim": dim, "datatype": (_CODES[dtype],), "bitpix": (8 * dtype.itemsize,),
+              "pixdim": [1.0] * 8, "vox_offset": (float(VOX_OFFSET),), "scl_slope": (0.0,), "scl_inter": (0.0,),
+              "qform_code": (0,), "sform_code": (2,), "quatern": [0.0, 0.0, 0.0] + list(affine[:3, 3]),
+              "srow_x": list(affine[0]), "srow_y": list(affine[1]), "srow_z": list(affine[2]), "magic": (MAGIC,)}
+    for name, fmt, off in FIELDS:
+        struct.pack_into("<" + fmt, hdr, off, *values[name])
+    hdr[38:39] = b"r"                                                  # `regular`, as the ANALYZE readers expect
+    return bytes(hdr)
+
+
+def encode_nifti(array, affine=None) -> bytes:
+    """The uncompressed ``.nii`` bytes of a uint8 / uint16 array of 1 to 7 dimensions."""
+    a = np.asarray(array)
+    if a.dtype.newbyteorder("=") not in _CODES:
+        raise ValueError(f"write_nifti: {a.dtype} data, only uint8 and uint16 are written")
+    if not 1 <= a.ndim <= 7 or a.size == 0 or max(a.shape) > 32767:
+        raise ValueError(f"write_nifti: shape {a.shape} does not fit a NIfTI-1 header")
+    aff = np.eye(4) if affine is None else np.asarray(affine, dtype=np.float64)
+    if aff.shape != (4, 4):
+        raise ValueError(f"write_nifti: affine of shape {aff.shape}, needs 4 x 4")
+    dt = a.dtype.newbyteorder("=")
+    data = np.asarray(a, dtype=dt.newbyteorder("<")).tobytes(order="F")
+    return _header(a.shape, dt, aff) + b"\0" * (VOX_OFFSET - HEADER_BYTES) + data
+
+
+def write_nifti(path: str, array, affine=None) -> None:
+    """Write `array` (uint8 / uint16) to `path` as a single-file NIfTI-1 image with the given 4 x 4 affine (identity by
+    default); a path ending in ``.gz`` is gzip-compressed with no name and mtime 0."""
+    raw = encode_nifti(array, affine)
+    with open(path, "wb") as f:
+        if str(path).endswith(".gz"):
+            with gzip.GzipFile(filename="", mode="wb", compresslevel=GZIP_LEVEL, fileobj=f, mtime=0) as gz:
+                gz.write(raw)
+        else:
+            f.write(raw)
+
+
+def decode_nifti(raw: bytes):
+    """(array, header fields) of the bytes of a single-file NIfTI-1 image; see read_nifti."""
+    if len(raw) < VOX_OFFSET:
+        raise ValueError(f"read_nifti: {len(raw)} bytes, shorter than a NIfTI-1 header")
+    for end in "<>":
+        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
+            break
+    else:
+        raise ValueError(f"read_nifti: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
+    f = {}
+    for name, fmt, off in FIELDS:
+        v = struct.unpack_from(end + fmt, raw, off)
+        f[name] = v[0] if len(v) == 1 else v
+    if f["magic"] != MAGIC:
+        raise ValueError(f"read_nifti: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    if f["datatype"] not in DATATYPES:
+        raise ValueError(f"read_nifti: datatype {f['datatype']}, only uint8 (2) and uint16 (512) are read")
+    dt = DATATYPES[f["datatype"]].newbyteorder(end)
+    if f["bitpix"] != 8 * dt.itemsize:
+        raise ValueError(f"read_nifti: bitpix {f['bitpix']} for datatype {f['datatype']}")
+    ndim = f["dim"][0]
+    if not 1 <= ndim <= 7:
+        raise ValueError(f"read_nifti: dim[0] = {ndim}")
+    shape = tuple(f["dim"][1:1 + ndim])
+    off = int(f["vox_offset"])
+    n = int(np.prod(shape)) * dt.itemsize
+    if min(shape) < 1 or off < VOX_OFFSET or len(raw) < off + n:
+        raise ValueError(f"read_nifti: shape {shape} at offset {off} does not fit {len(raw)} bytes")
+    a = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape)), offset=off).reshape(shape, order="F")
+    f["affine"] = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
+    return np.ascontiguousarray(a, dtype=DATATYPES[f["datatype"]]), f
+
+
+def read_nifti(path: str):
+    """(array, header fields) of a single-file NIfTI-1 image of uint8 / uint16 data (gzip-compressed or not).  The
+    fields are those of FIELDS plus `affine` (the sform rows); raises ValueError on files of another kind."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if raw[:2] == b"\x1f\x8b":
+        raw = gzip.decompress(raw)
+    return decode_nifti(raw)

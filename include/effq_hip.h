@@ -554,6 +554,21 @@ int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int 
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* Labels: logits (N, C, S) of N cases -> one label map (N, S) of out_bytes = 1 (uint8) or 2 (uint16) per voxel, or
+ * for EFFQ_SEG_LABEL_PLANES the C merged 0/1 planes (N, C, S) uint8.  The per-voxel decisions are the tallies': the
+ * ARGMAX rule uses EFFQ_SEG_ARGMAX (fuse must be NONE), every other rule EFFQ_SEG_SIGMOID with `thresh` and `fuse`.
+ *   ARGMAX: the class id (metrics.get_pred_lits).
+ *   BRATS:  misc.merge_label_brats of the merged channels: 0; 1 where ch0; 2 where ch0 and not ch1; 4 where ch2
+ *           (later assignments win).  C >= 3.
+ *   RANK:   i + 1 of the highest set channel, 0 when none (fuse CON: metrics.get_pred_brats_con_merge).
+ *   PLANES: the merged channels themselves (misc.merge_label_basic).  out_bytes = 1. */
+#define EFFQ_SEG_LABEL_ARGMAX 0
+#define EFFQ_SEG_LABEL_BRATS 1
+#define EFFQ_SEG_LABEL_RANK 2
+#define EFFQ_SEG_LABEL_PLANES 3
+int effq_seg_labels(const float* logits, int N, int C, long long S, int rule, int fuse, float thresh, int out_bytes,
+                    void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

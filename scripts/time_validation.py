@@ -1,12 +1,17 @@
 """Validation of one uncropped BraTS-size case (4 x 155 x 240 x 240, windows of 128^3, overlap 16) on the calibrated
 BraTS net (diagnostic, GPU): the three validation kernels alone, and evaluate.validate_seg against the per-window loop
-(evaluate.sliding_window_forward + torch counts), all timed with HIP events.  Prints one JSON line."""
-import json, os, sys
+(evaluate.sliding_window_forward + torch counts), all timed with HIP events.  Prints one JSON line.
+--save-nii adds the label-map kernel (warm, and after 512 MiB of other writes have pushed the logits out of the
+Infinity Cache) and validate_seg over three such cases with and without save_dir, wall time per case."""
+import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efficientq_amd import calibrate as K, config as Cf, evaluate as E, synth
 from efficientq_amd.hip_ops import from_ndhwc, get_ops
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--save-nii", dest="save_nii", action="store_true", help="also time the NIfTI label maps")
+cli = ap.parse_args()
 REPS = int(os.environ.get("REPS", "5"))
 HBM_PEAK = 8.0e12
 dev = "cuda:0"
@@ -73,4 +78,38 @@ res["validate_per_window_ms"] = round(timed(per_window, 3), 2)
 torch.cuda.reset_peak_memory_stats()
 E.validate_seg(model, loader, "brats", p, o)
 res["auto_window_batch_peak_GB"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
+
+if cli.save_nii:
+    nbytes = 3 * vox * 4 + 2 * vox          # logits read, uint16 map written
+    labels = lambda: ops.seg_labels(stitched, "brats", "agg", torch.uint16)
+    ms = timed(labels)
+    res["labels"] = {"ms": round(ms, 4), "bytes": nbytes, "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)}
+    evict = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+    cold = []
+    for _ in range(REPS):
+        evict.fill_(1)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); labels(); b.record(); torch.cuda.synchronize()
+        cold.append(a.elapsed_time(b))
+    ms = sorted(cold)[len(cold) // 2]
+    res["labels_after_evict"] = {"ms": round(ms, 4), "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)}
+    del evict
+    cases = loader * 3
+
+    def wall(save_dir):
+        E.validate_seg(model, cases, "brats", p, o, window_batch=nwin, fuse="agg", save_dir=save_dir,
+                       multi_label="brats")
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            E.validate_seg(model, cases, "brats", p, o, window_batch=nwin, fuse="agg", save_dir=save_dir,
+                           multi_label="brats")
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3 / len(cases))
+        return round(sorted(ms)[1], 2)
+    with tempfile.TemporaryDirectory() as tmp:
+        res["validate_ms_per_case"] = wall(None)
+        res["validate_save_nii_ms_per_case"] = wall(tmp)
+        res["nii_gz_bytes"] = os.path.getsize(os.path.join(tmp, "0.nii.gz"))
 print(json.dumps(res))
