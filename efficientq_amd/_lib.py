@@ -46,6 +46,7 @@ FP_STATE_BYTES = C.sizeof(FpState)
 
 _P, _SZ, _I, _F, _D, _LL = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double, C.c_longlong
 _GP = C.POINTER(Geom)
+_IP = C.POINTER(C.c_int)
 
 
 class AdmmRunArgs(C.Structure):
@@ -160,6 +161,8 @@ SIGNATURES = {
     "effq_gram_loss_i8": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_spd_inverse_ws_bytes": (_SZ, [_I]),
     "effq_spd_inverse": (_I, [_P, _I, _I, _D, _D, _P, _P, _SZ, _P]),
+    "effq_spd_inverse_plan": (_I, [_I, _IP, _IP, _IP]),
+    "effq_prox_plan_query": (_I, [_I, _I, _IP, _IP, _IP, _IP]),
     "effq_prox_ws_bytes": (_SZ, [_I, _I]),
     "effq_prox_solve": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P, _SZ, _P]),
     "effq_prox_solve_shifted": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _I, _P, _P, _P, _SZ, _P]),

@@ -1152,12 +1152,18 @@ static size_t gj64_aux_doubles(size_t npad) { return 2 * (size_t)NBK * npad + 2 
 // launch) blocks for every n >= 512: 683.5 / 681.8 - below n ~ 5000 an inverse is a chain of dependent launches either
 // way, and the rank-64 sweep has the shortest one
 constexpr int GJ_WIDE_MIN_BLOCKS = 100;
+static bool gj_takes_wide(int nblk) { return nblk >= GJ_WIDE_MIN_BLOCKS; }
+// 64-blocks per pivot block of the wide sweep: pivot blocks of 128 rows (next pivot block by ONE fused launch) below 100
+// 64-blocks, of 256 rows from there on (the triangle no longer fits the Infinity Cache: the rank-256 update halves the bytes
+// per flop once more).  The wide sweep itself starts at GJ_WIDE_MIN_BLOCKS = 100, so every sweep takes 256-row blocks
+// (128-row form measured slower)
+static int gj_wide_pivot(int nblk) { return (nblk >= 100) ? effq::WB : 2; }
 
 size_t effq_spd_inverse_ws_bytes(int n) {
   if (n <= 0) return 0;
   const size_t npad = (size_t)round_up(n, NBK);
   size_t d = npad * npad + gj64_aux_doubles(npad);
-  if ((int)(npad / NBK) >= GJ_WIDE_MIN_BLOCKS) {
+  if (gj_takes_wide((int)(npad / NBK))) {
     const size_t ldx = (size_t)round_up((int)npad, BG_T);
     d = npad * npad + 2 * (size_t)WK * ldx + (size_t)WK * WK + gj64_aux_doubles(WK);
   }
@@ -1220,10 +1226,7 @@ static int gj_wide_ctx(hipStream_t caller, GjWideCtx** out) {
 
 static int gj_wide_sweep(double* A64, int npad, double* aux, hipStream_t st) {
   const int nblk = npad / NBK;
-  // pivot blocks of 128 rows (next pivot block by ONE fused launch) below 100 64-blocks, of 256 rows from there on (the
-  // triangle no longer fits the Infinity Cache: the rank-256 update halves the bytes per flop once more).  The wide sweep
-  // itself starts at GJ_WIDE_MIN_BLOCKS = 100, so every sweep takes 256-row blocks (128-row form measured slower)
-  const int WB = (nblk >= 100) ? effq::WB : 2;
+  const int WB = gj_wide_pivot(nblk);
   const size_t ldx = (size_t)round_up(npad, BG_T);
   double* NZT = aux;                               // [256][ldx]
   double* XTW = NZT + (size_t)WK * ldx;            // [256][ldx]
@@ -1332,7 +1335,7 @@ int effq_spd_inverse(const float* A0, int n, int has_bias, double rho, double et
   EFFQ_HIP(raise_lds_limit<k_gj_panel>(lds));
   EFFQ_HIP(raise_lds_limit<k_gj_panel_w>(lds));
   EFFQ_HIP(raise_lds_limit<k_gj_pivot_fused>((2 * NBK * PF_LD + 2 * (NBK + 1)) * sizeof(double)));
-  const int rc = (npad / NBK >= GJ_WIDE_MIN_BLOCKS) ? gj_wide_sweep(A64, npad, aux, st) : gj64_sweep(A64, npad, aux, st);
+  const int rc = gj_takes_wide(npad / NBK) ? gj_wide_sweep(A64, npad, aux, st) : gj64_sweep(A64, npad, aux, st);
   if (rc != EFFQ_OK) return rc;
   {
     const int lda = effq_ainv_ld(n);
@@ -1341,6 +1344,28 @@ int effq_spd_inverse(const float* A0, int n, int has_bias, double rho, double et
     hipLaunchKernelGGL(k_a64_to_f32, dim3((unsigned)nb), dim3(256), 0, st, A64, n, npad, Ainv, lda);
     EFFQ_LAUNCH_CHECK();
   }
+  return EFFQ_OK;
+}
+
+// which sweep effq_spd_inverse takes for n (launches nothing): *wide = the 256-row sweep, *nblk = 64-blocks per side,
+// *pivot_blocks = elimination steps (nblk for the rank-64 sweep, the last one of a wide sweep may be shorter)
+int effq_spd_inverse_plan(int n, int* wide, int* nblk, int* pivot_blocks) {
+  EFFQ_CHECK_ARG(n > 0 && wide && nblk && pivot_blocks);
+  const int nb = round_up(n, NBK) / NBK;
+  *wide = gj_takes_wide(nb) ? 1 : 0;
+  *nblk = nb;
+  *pivot_blocks = *wide ? (nb + gj_wide_pivot(nb) - 1) / gj_wide_pivot(nb) : nb;
+  return EFFQ_OK;
+}
+
+// the kernel variant, grid and K split effq_prox_solve* takes for (c2, n) (launches nothing)
+int effq_prox_plan_query(int c2, int n, int* variant, int* gx, int* gy, int* nsplit) {
+  EFFQ_CHECK_ARG(c2 > 0 && n > 0 && variant && gx && gy && nsplit);
+  const ProxPlan p = prox_plan(c2, n);
+  *variant = p.variant;
+  *gx = p.gx;
+  *gy = p.gy;
+  *nsplit = p.nsplit;
   return EFFQ_OK;
 }
 

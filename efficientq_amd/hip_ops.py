@@ -628,6 +628,19 @@ class HipOps:
                                         self.stream), "effq_spd_inverse")
         return out
 
+    def spd_inverse_plan(self, n: int) -> dict:
+        """The sweep spd_inverse takes for n rows (effq_spd_inverse_plan; launches nothing)."""
+        wide, nblk, piv = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.effq_spd_inverse_plan(int(n), C.byref(wide), C.byref(nblk), C.byref(piv)), "effq_spd_inverse_plan")
+        return dict(wide=bool(wide.value), nblk=nblk.value, pivot_blocks=piv.value)
+
+    def prox_plan(self, c2: int, n: int) -> dict:
+        """The GEMM variant, grid and K split prox_solve takes for a c2 x n system (effq_prox_plan_query; launches nothing)."""
+        v, gx, gy, ns = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.effq_prox_plan_query(int(c2), int(n), C.byref(v), C.byref(gx), C.byref(gy), C.byref(ns)),
+              "effq_prox_plan_query")
+        return dict(variant=v.value, gx=gx.value, gy=gy.value, nsplit=ns.value)
+
     def prox_solve(self, B0, Ainv, W0, b0, G, dual, rho: float, eta: float, wstar, bstar):
         c2, n = B0.shape
         ws = self._workspace("prox", self.lib.effq_prox_ws_bytes(c2, n))

@@ -327,6 +327,10 @@ int effq_ainv_ld(int n);
 size_t effq_spd_inverse_ws_bytes(int n);
 int effq_spd_inverse(const float* A0, int n, int has_bias, double rho, double eta, float* Ainv,
                      void* ws, size_t ws_bytes, void* stream);
+/* Which sweep effq_spd_inverse runs for a system of n rows; launches nothing.  *wide: 1 = the sweep with 256-row pivot
+ * blocks, 0 = the rank-64 sweep; *nblk: 64-blocks per side of the padded matrix; *pivot_blocks: elimination steps (the last
+ * pivot block of a wide sweep holds the remaining 1 .. 4 64-blocks). */
+int effq_spd_inverse_plan(int n, int* wide, int* nblk, int* pivot_blocks);
 
 /* What = (B0 + eta*[W0|b0] + rho*[G-dual|0]) * Ainv ; splits into wstar [c2 x (n-1|n)] and bstar [c2].
  * W0, G, dual, wstar in reference weight layout (contiguous c2 x c1k).  b0/bstar NULL when !has_bias.
@@ -335,6 +339,10 @@ size_t effq_prox_ws_bytes(int c2, int n);
 int effq_prox_solve(const float* B0, const float* Ainv, const float* W0, const float* b0, const float* G,
                     const float* dual, int c2, int n, int has_bias, double rho, double eta, float* wstar,
                     float* bstar, void* ws, size_t ws_bytes, void* stream);
+/* The GEMM the prox solves of a c2 x n system run; launches nothing.  *variant: 0 - 3 = the f32 matrix-core kernel with
+ * 256 / 128 / 64 / 32 rows per workgroup, 5 / 7 = the bf16x3 kernel with 256 / 128 rows; the grid is gx column tiles x gy
+ * row tiles x nsplit K slices (nsplit > 1: partial products, added up in slice order). */
+int effq_prox_plan_query(int c2, int n, int* variant, int* gx, int* gy, int* nsplit);
 
 /* The same solve for A(rho) when only Ainv = A(rho_inv)^-1 is at hand (rho_inv >= rho): A(rho) = A(rho_inv) -
  * d*I' with d = rho_inv - rho, so What = (B + d*[What_w|0]) * Ainv is a contraction with factor

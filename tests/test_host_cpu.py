@@ -30,6 +30,36 @@ def test_library_exports_every_declared_symbol():
     assert lib.effq_reduce_ws_bytes() > 0
 
 
+def test_solver_dispatch_queries_launch_nothing():
+    """effq_prox_plan_query / effq_spd_inverse_plan answer without a device: the classes tests/test_solver_shapes_gpu.py
+    pins its cases to (the same prox_plan and the same block threshold the solver calls)."""
+    import ctypes as C
+    from efficientq_amd import _lib
+    lib = _lib.load()
+
+    def prox(c2, n):
+        out = [C.c_int() for _ in range(4)]
+        assert lib.effq_prox_plan_query(c2, n, *[C.byref(o) for o in out]) == 0
+        return tuple(o.value for o in out)
+
+    def inverse(n):
+        out = [C.c_int() for _ in range(3)]
+        assert lib.effq_spd_inverse_plan(n, *[C.byref(o) for o in out]) == 0
+        return tuple(o.value for o in out)
+
+    # (variant, column tiles, row tiles, K slices): the shipped 1x1x1 layers on variants 0 and 1, the split variant 2,
+    # the two sides of the bf16 switch
+    assert prox(256, 129) == (0, 3, 1, 1) and prox(512, 257) == (0, 5, 2, 1) and prox(256, 513) == (0, 9, 1, 2)
+    assert prox(128, 65) == (1, 2, 1, 1) and prox(64, 1729) == (2, 28, 1, 9) and prox(32, 109) == (3, 1, 1, 1)
+    assert prox(256, 1023)[0] == 0 and prox(256, 1024)[0] == 5 and prox(128, 1023)[0] == 1 and prox(128, 1024)[0] == 7
+    # (wide, 64-blocks, pivot blocks): the wide sweep starts at 100 blocks
+    assert inverse(1) == (0, 1, 1) and inverse(6336) == (0, 99, 99)
+    assert inverse(6337) == (1, 100, 25) and inverse(6401) == (1, 101, 26) and inverse(6592) == (1, 103, 26)
+    v = C.c_int()
+    assert lib.effq_prox_plan_query(0, 5, C.byref(v), C.byref(v), C.byref(v), C.byref(v)) == 1      # EFFQ_ERR_ARG
+    assert lib.effq_spd_inverse_plan(0, C.byref(v), C.byref(v), C.byref(v)) == 1
+
+
 def test_product_path_refuses_cpu_tensors():
     from efficientq_amd import hip_ops, _lib
     with pytest.raises(_lib.EffqError):
