@@ -47,6 +47,7 @@ FP_STATE_BYTES = C.sizeof(FpState)
 _P, _SZ, _I, _F, _D, _LL = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double, C.c_longlong
 _GP = C.POINTER(Geom)
 _IP = C.POINTER(C.c_int)
+_LLP = C.POINTER(C.c_longlong)
 
 
 class AdmmRunArgs(C.Structure):
@@ -134,14 +135,17 @@ SIGNATURES = {
     "effq_admm_select_best": (_I, [_P, _I, _P, _P, _SZ, _SZ, _P, _P, _P, _P]),
     "effq_gram_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_accum": (_I, [_P, _P, _P, _GP, _I, _P, _P, _I, _P, _SZ, _P]),
+    "effq_gram_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP, _LLP, _IP, _IP]),
     "effq_gram_i8_supported": (_I, [_GP, _I]),
     "effq_gram_i8_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_accum_i8": (_I, [_P, _P, _GP, _I, _P, _I, _P, _P, _P, _I, _LL, _P, _P, _I, _P, _SZ, _P]),
     "effq_gram_accum_i8_unw": (_I, [_P, _P, _GP, _I, _P, _I, _P, _P, _P, _I, _LL, _P, _P, _I, _P, _P, _P, _SZ, _P]),
+    "effq_gram_i8_plan_query": (_I, [_GP, _I, _LL, _IP, _IP, _IP, _IP, _IP, _IP]),
     "effq_upsample_trilinear": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_gram_f64_supported": (_I, [_GP, _I]),
     "effq_gram_f64_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_f64": (_I, [_P, _P, _GP, _I, _P, _P, _P, _SZ, _P]),
+    "effq_gram_f64_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP]),
     "effq_gram_loss_ws_bytes": (_SZ, [_I]),
     "effq_gram_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_packed_bytes": (_SZ, [_SZ, _I]),

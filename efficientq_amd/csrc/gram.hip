@@ -384,6 +384,17 @@ static int gram_plan(const effq_geom* g, int has_bias, GramParams* pp) {
   return EFFQ_OK;
 }
 
+// k_gram<true> stages whole 16-byte cells (4 channels of one tap / of y); it needs C1 and C2 to be multiples of 4
+static bool gram_vec(const GramParams& p) { return (p.C1 & 3) == 0 && (p.C2 & 3) == 0; }
+
+// k_gram_finish: one thread per output element up to 8192 workgroups, strided beyond
+static unsigned gram_finish_blocks(const GramParams& p) {
+  const int n = p.RX + p.hb;
+  const size_t tot = (size_t)n * n + (size_t)p.C2 * n;
+  const size_t nb = (tot + 255) / 256;
+  return (unsigned)(nb > 8192 ? 8192 : nb);
+}
+
 }  // namespace effq
 
 using namespace effq;
@@ -413,17 +424,31 @@ int effq_gram_accum(const float* x_ndhwc, const float* att, const float* y_ndhwc
   p.y = y_ndhwc;
   p.slabs = reinterpret_cast<double*>(ws);
   hipStream_t st = as_stream(stream);
-  if ((p.C1 & 3) == 0 && (p.C2 & 3) == 0)
+  if (gram_vec(p))
     hipLaunchKernelGGL(k_gram<true>, dim3((unsigned)p.npairs, (unsigned)p.nsplit), dim3(GT), 0, st, p);
   else
     hipLaunchKernelGGL(k_gram<false>, dim3((unsigned)p.npairs, (unsigned)p.nsplit), dim3(GT), 0, st, p);
   EFFQ_LAUNCH_CHECK();
   const int n = p.RX + p.hb;
-  size_t tot = (size_t)n * n + (size_t)p.C2 * n;
-  size_t nb = (tot + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(k_gram_finish, dim3((unsigned)nb), dim3(256), 0, st, p, n, A0, B0, accumulate);
+  hipLaunchKernelGGL(k_gram_finish, dim3(gram_finish_blocks(p)), dim3(256), 0, st, p, n, A0, B0, accumulate);
   EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+// the launch effq_gram_accum makes for a geometry (launches nothing): the same gram_plan, gram_vec and gram_finish_blocks
+int effq_gram_plan_query(const effq_geom* g, int has_bias, int* vec, int* nb, int* npairs, int* nsplit,
+                         long long* vox_per_split, int* fold, int* finish_blocks) {
+  EFFQ_CHECK_ARG(vec && nb && npairs && nsplit && vox_per_split && fold && finish_blocks);
+  GramParams p;
+  const int rc = gram_plan(g, has_bias, &p);
+  if (rc != EFFQ_OK) return rc;
+  *vec = gram_vec(p) ? 1 : 0;
+  *nb = p.NB;
+  *npairs = p.npairs;
+  *nsplit = p.nsplit;
+  *vox_per_split = p.vox_per_split;
+  *fold = p.fold;
+  *finish_blocks = (int)gram_finish_blocks(p);
   return EFFQ_OK;
 }
 

@@ -197,6 +197,12 @@ static bool gram_f64_plan(const effq_geom* g, int has_bias, GramF64Params* p) {
 // net, 11 % of the fp64 matrix peak)
 static int gram_f64_grid(const GramF64Params& p) { return p.nchunk < 1024 ? p.nchunk : 1024; }
 
+// accumulator tiles per wave the kernel is instantiated for: the smallest of 3 / 6 / 11 / 18 that holds ceil(ntiles / 4)
+static int gram_f64_tpw(const GramF64Params& p) {
+  const int tpw = (p.ntiles + 3) / 4;
+  return tpw <= 3 ? 3 : (tpw <= 6 ? 6 : (tpw <= 11 ? 11 : 18));
+}
+
 }  // namespace effq
 using namespace effq;
 
@@ -231,14 +237,30 @@ int effq_gram_f64(const float* x_ndhwc, const float* y_ndhwc, const effq_geom* g
   p.slab = reinterpret_cast<double*>(ws);
   const int grid = gram_f64_grid(p);
   const size_t lds = (size_t)GF_VC * p.ld * sizeof(double);
-  const int tpw = (p.ntiles + 3) / 4;
   hipStream_t st = as_stream(stream);
 #define EFFQ_GF(TPW_) hipLaunchKernelGGL((k_gram_f64<TPW_>), dim3(grid), dim3(GF_T), lds, st, p)
-  if (tpw <= 3) EFFQ_GF(3); else if (tpw <= 6) EFFQ_GF(6); else if (tpw <= 11) EFFQ_GF(11); else EFFQ_GF(18);
+  switch (gram_f64_tpw(p)) {
+    case 3: EFFQ_GF(3); break;
+    case 6: EFFQ_GF(6); break;
+    case 11: EFFQ_GF(11); break;
+    default: EFFQ_GF(18); break;
+  }
 #undef EFFQ_GF
   EFFQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_gram_f64_reduce, dim3(p.ntiles), dim3(256), 0, st, p, grid, Au, Bu);
   EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+// the launch effq_gram_f64 makes for a geometry (launches nothing): the same gram_f64_plan, _grid and _tpw
+int effq_gram_f64_plan_query(const effq_geom* g, int has_bias, int* nchunk, int* grid, int* ntiles, int* tpw) {
+  EFFQ_CHECK_ARG(g && nchunk && grid && ntiles && tpw);
+  GramF64Params p;
+  EFFQ_CHECK_ARG(gram_f64_plan(g, has_bias, &p));
+  *nchunk = p.nchunk;
+  *grid = gram_f64_grid(p);
+  *ntiles = p.ntiles;
+  *tpw = gram_f64_tpw(p);
   return EFFQ_OK;
 }
 

@@ -523,6 +523,23 @@ int effq_gram_accum_i8_unw(const uint8_t* xidx_ndhwc, const float* y_ndhwc, cons
   return EFFQ_OK;
 }
 
+// the launch effq_gram_accum_i8* makes for a geometry and a voxel list of n_list slots (0: no list, all voxels in order);
+// launches nothing: the same gram_i8_plan
+int effq_gram_i8_plan_query(const effq_geom* g, int ncls, long long n_list, int* nb, int* nbx, int* npairs, int* nchunks,
+                            int* cps, int* nsplit) {
+  EFFQ_CHECK_ARG(nb && nbx && npairs && nchunks && cps && nsplit && n_list >= 0 && (n_list % GI_KC) == 0);
+  GramI8Params p;
+  const int rc = gram_i8_plan(g, ncls, n_list, &p);
+  if (rc != EFFQ_OK) return rc;
+  *nb = p.NB;
+  *nbx = p.NBX;
+  *npairs = p.npairs;
+  *nchunks = p.nchunks;
+  *cps = p.cps;
+  *nsplit = p.nsplit;
+  return EFFQ_OK;
+}
+
 int effq_gram_accum_i8(const uint8_t* xidx_ndhwc, const float* y_ndhwc, const effq_geom* g, int has_bias,
                        const float* act_alpha_dev, int act_levels, const int32_t* vox_list, const int32_t* chunk_cls,
                        const float* cls_w_dev, int ncls, long long n_list, float* A0, float* B0, int accumulate,

@@ -281,11 +281,14 @@ int effq_gram_loss_i8_supported(int c2, int n, int has_bias, int w_levels) {
   return (c2 > 0 && nw > 0 && (c2 % 32) == 0 && (nw % G8_KC) == 0 && nw < 65536 && w_levels >= 2 && w_levels <= 64) ? 1 : 0;
 }
 
+// largest non-negative integer P balanced base-256 digits (-128 .. 127 each) hold: 127 (1 + 256 + ... + 256^(P-1)).  That is
+// BELOW 2^(8P - 1) - 1 from two planes on (32639 < 32767): k_gl8_planes carries out of the top digit in between
+static long long g8_plane_capacity(int P) { return 127ll * (((1ll << (8 * P)) - 1) / 255); }
+
 int effq_gram_loss_i8_num_planes(long long kmax) {
-  // balanced digits: P planes hold |K| < 128 * 256^(P-1) + ... >= 2^(8P - 1) - 1
   int P = 1;
-  while (P < G8_MAXP && kmax > ((1ll << (8 * P - 1)) - 1)) ++P;
-  return (kmax <= ((1ll << (8 * P - 1)) - 1)) ? P : -1;
+  while (P < G8_MAXP && kmax > g8_plane_capacity(P)) ++P;
+  return (kmax <= g8_plane_capacity(P)) ? P : -1;
 }
 
 size_t effq_gram_loss_i8_planes_bytes(int n, int has_bias, int nplanes) {

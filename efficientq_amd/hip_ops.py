@@ -436,6 +436,31 @@ class HipOps:
                                        acc, _ptr(ws), ws.numel(), self.stream), "effq_gram_accum")
         return A0, B0
 
+    def gram_plan(self, geom: Geom, has_bias: bool) -> dict:
+        """The launch gram() makes for a geometry (effq_gram_plan_query; launches nothing)."""
+        vec, nb, npairs, nsplit, fold, fin = (C.c_int() for _ in range(6))
+        vps = C.c_longlong()
+        check(self.lib.effq_gram_plan_query(C.byref(geom), int(has_bias), C.byref(vec), C.byref(nb), C.byref(npairs),
+                                            C.byref(nsplit), C.byref(vps), C.byref(fold), C.byref(fin)),
+              "effq_gram_plan_query")
+        return dict(vec=bool(vec.value), NB=nb.value, npairs=npairs.value, nsplit=nsplit.value, vox_per_split=vps.value,
+                    fold=fold.value, finish_blocks=fin.value)
+
+    def gram_i8_plan(self, geom: Geom, ncls: int = 1, n_list: int = 0) -> dict:
+        """The launch gram_i8() makes for a geometry, ncls classes and a voxel list of n_list slots (0: no list)
+        (effq_gram_i8_plan_query; launches nothing)."""
+        out = [C.c_int() for _ in range(6)]
+        check(self.lib.effq_gram_i8_plan_query(C.byref(geom), int(ncls), int(n_list), *[C.byref(o) for o in out]),
+              "effq_gram_i8_plan_query")
+        return dict(zip(("NB", "NBX", "npairs", "nchunks", "cps", "nsplit"), (o.value for o in out)))
+
+    def gram_f64_plan(self, geom: Geom, has_bias: bool) -> dict:
+        """The launch gram_f64() makes for a supported geometry (effq_gram_f64_plan_query; launches nothing)."""
+        out = [C.c_int() for _ in range(4)]
+        check(self.lib.effq_gram_f64_plan_query(C.byref(geom), int(has_bias), *[C.byref(o) for o in out]),
+              "effq_gram_f64_plan_query")
+        return dict(zip(("nchunk", "grid", "ntiles", "tpw"), (o.value for o in out)))
+
     def gram_i8_supported(self, geom: Geom, act_levels: int) -> bool:
         return bool(self.lib.effq_gram_i8_supported(C.byref(geom), int(act_levels)))
 

@@ -238,6 +238,12 @@ size_t effq_gram_ws_bytes(const effq_geom* g, int has_bias);
 int effq_gram_accum(const float* x_ndhwc, const float* att, const float* y_ndhwc, const effq_geom* g,
                     int has_bias, float* A0, float* B0, int accumulate, void* ws, size_t ws_bytes,
                     void* stream);
+/* The launch effq_gram_accum makes for a geometry; launches nothing.  *vec: 1 = the kernel that stages 16-byte cells
+ * (C1 and C2 multiples of 4), 0 = the row-by-row kernel; the grid is *npairs blocks of the upper block triangle (*nb
+ * 128-row blocks per side) x *nsplit voxel ranges of *vox_per_split voxels; the fp32 accumulators are folded into fp64 every
+ * *fold chunks of 32 voxels; *finish_blocks workgroups add the slabs up (8192 at most, strided beyond). */
+int effq_gram_plan_query(const effq_geom* g, int has_bias, int* vec, int* nb, int* npairs, int* nsplit,
+                         long long* vox_per_split, int* fold, int* finish_blocks);
 
 /* The same A0/B0 for a layer whose input is already quantised (EfficientQConv.py:64-72 ran first), evaluated
  * exactly on the i8 matrix cores: xidx = level ids of the quantised input (uint8, NDHWC, value k means
@@ -261,6 +267,11 @@ int effq_gram_accum_i8_unw(const uint8_t* xidx_ndhwc, const float* y_ndhwc, cons
                            const float* act_alpha_dev, int act_levels, const int32_t* vox_list, const int32_t* chunk_cls,
                            const float* cls_w_dev, int ncls, long long n_list, float* A0, float* B0, int accumulate,
                            double* Au, double* Bu, void* ws, size_t ws_bytes, void* stream);
+/* The launch effq_gram_accum_i8* makes for a geometry and a voxel list of n_list slots (0: no list); launches nothing.
+ * *nb 128-row blocks per side of the extended integer system, the first *nbx of them hold x rows, *npairs block pairs x
+ * *nsplit splits of *cps chunks (128 voxels each, *nchunks in all); a split accumulates in int32 and flushes per class. */
+int effq_gram_i8_plan_query(const effq_geom* g, int ncls, long long n_list, int* nb, int* nbx, int* npairs, int* nchunks,
+                            int* cps, int* nsplit);
 
 /* The unweighted system of a layer whose input is NOT quantised (first conv / classifier, q_first = q_last = "256,-1":
  * definer.py:296-299, model_blk.py:98-107), in fp64 on the matrix cores: Au [n][n] = sum_v xhat xhat^T with
@@ -272,6 +283,9 @@ int effq_gram_f64_supported(const effq_geom* g, int has_bias);
 size_t effq_gram_f64_ws_bytes(const effq_geom* g, int has_bias);
 int effq_gram_f64(const float* x_ndhwc, const float* y_ndhwc, const effq_geom* g, int has_bias, double* Au, double* Bu,
                   void* ws, size_t ws_bytes, void* stream);
+/* The launch effq_gram_f64 makes for a supported geometry; launches nothing.  *grid persistent workgroups (1024 at most)
+ * walk *nchunk chunks of 32 voxels; *ntiles 16 x 16 accumulator tiles, *tpw (3, 6, 11 or 18) of them per wave. */
+int effq_gram_f64_plan_query(const effq_geom* g, int has_bias, int* nchunk, int* grid, int* ntiles, int* tpw);
 
 /* ---- the loss of one iterate from the unweighted Gram system (EfficientQConv.py:118-122 without the pass over the voxels)
  * sum_v,c (conv(Qx, G, b)_v,c - y_v,c)^2 = sum_c g_c^T Au g_c - 2 sum_c g_c . Bu_c + syy with g_c = [G[c,:], b_c], in fp64:
@@ -287,6 +301,7 @@ int effq_gram_loss(const double* Au, const double* Bu, const double* syy_dev, co
  * J = the int8 level numerators of the iterate (Gq ring of effq_admm_run, as for conv3d_calib_step_i8).
  *   effq_gram_loss_i8_supported: c2 % 32 == 0, (n - has_bias) % 64 == 0, w_levels <= 64;
  *   effq_gram_loss_i8_num_planes(kmax): balanced base-256 digit planes for entries up to kmax (<= (La-1)^2 * voxels), -1 if > 6;
+ *     P planes of digits -128 .. 127 hold 0 .. 127 (256^P - 1) / 255 (127, 32639, 8355711, ...);
  *   effq_gram_loss_i8_prepare: planes [P][round_up(n - has_bias, 256)][n - has_bias] int8 from Au (effq_gram_accum_i8_unw),
  *     once per layer; *err_flag_dev is set non-zero if Au is not the integer system it should be;
  *   effq_gram_loss_i8: hist_out[j][0] = hist_out[j][1] = sum (out - y)^2 of iterate j = 0 .. count-1 (count <= 16):

@@ -60,6 +60,95 @@ def test_solver_dispatch_queries_launch_nothing():
     assert lib.effq_spd_inverse_plan(0, C.byref(v), C.byref(v), C.byref(v)) == 1
 
 
+def test_gram_dispatch_queries_launch_nothing():
+    """effq_gram_plan_query / effq_gram_i8_plan_query / effq_gram_f64_plan_query answer without a device: the classes
+    tests/test_gram_shapes_gpu.py pins its cases to (the planners the launches call).  The clamp on the chunks per split of
+    the i8 Gram keeps the int32 partial sums of a split in range at the largest level id, whatever the geometry."""
+    import ctypes as C
+    from efficientq_amd import _lib
+    from efficientq_amd.hip_ops import make_geom
+    lib = _lib.load()
+
+    def gram(shape, c2, k, s, p, bias):
+        g = make_geom(shape, c2, k, s, p)
+        out = [C.c_int() for _ in range(4)]
+        vps, tail = C.c_longlong(), [C.c_int(), C.c_int()]
+        assert lib.effq_gram_plan_query(C.byref(g), bias, *[C.byref(o) for o in out], C.byref(vps),
+                                        *[C.byref(o) for o in tail]) == 0
+        return tuple(o.value for o in out) + (vps.value,) + tuple(o.value for o in tail)
+
+    def gram_i8(shape, c2, k, ncls=1, n_list=0):
+        g = make_geom(shape, c2, k, 1, k // 2)
+        out = [C.c_int() for _ in range(6)]
+        rc = lib.effq_gram_i8_plan_query(C.byref(g), ncls, n_list, *[C.byref(o) for o in out])
+        return (rc,) + tuple(o.value for o in out)
+
+    def gram_f64(shape, c2, k, s, p, bias):
+        g = make_geom(shape, c2, k, s, p)
+        out = [C.c_int() for _ in range(4)]
+        rc = lib.effq_gram_f64_plan_query(C.byref(g), bias, *[C.byref(o) for o in out])
+        return (rc,) + tuple(o.value for o in out)
+
+    # (vec, NB, npairs, nsplit, voxels per split, fold, finish blocks)
+    assert gram((1, 4, 102, 102, 101), 32, 3, 1, 1, 1) == (1, 2, 3, 1314, 800, 4, 61)          # fold 4 from 2^20 voxels
+    assert gram((2, 6, 9, 10, 11), 2, 3, 1, 1, 1) == (0, 2, 3, 7, 288, 1, 106)                 # row-by-row staging
+    assert gram((1, 128, 12, 13, 14), 128, 3, 1, 1, 1) == (1, 29, 435, 8, 288, 1, 8192)        # strided finish
+    assert gram((1, 4, 6, 8, 9), 8, 3, 1, 1, 1)[3] == 1
+    # (rc, NB, NBX, npairs, nchunks, cps, nsplit)
+    assert gram_i8((4, 32, 64, 64, 64), 32, 3) == (0, 8, 7, 35, 8192, 94, 88)
+    assert gram_i8((1, 16, 128, 128, 128), 16, 1) == (0, 1, 1, 1, 16384, 6, 2731)
+    assert gram_i8((1, 32, 8, 8, 8), 32, 3, 16, 1024)[4] == 8                                  # the list sets the chunks
+    longest = 0
+    for c1, c2, k in [(16, 16, 1), (32, 32, 3), (64, 64, 3), (128, 128, 3), (256, 256, 3), (512, 512, 3), (256, 128, 1)]:
+        for nchunks in (1, 4, 4095, 65536, 3072 * 1000, (1 << 24) - 1):
+            rc, _, _, _, got, cps, nsplit = gram_i8((1, c1, 8, 8, 8), c2, k, 1, nchunks * 128)
+            assert rc == 0 and got == nchunks and cps * nsplit >= nchunks and nsplit <= 65535
+            longest = max(longest, cps)
+    assert longest == 1000 and longest * 128 * 127 * 127 < 2 ** 31                             # GI_MAX_CPS, 128 levels
+    assert gram_i8((1, 16, 8, 8, 8), 16, 1, 1, 130)[0] == 1 and gram_i8((1, 16, 8, 8, 8), 16, 1, 17, 0)[0] == 1
+    # (rc, nchunk, grid, ntiles, tiles per wave)
+    assert gram_f64((1, 32, 32, 32, 33), 3, 1, 1, 0, 1) == (0, 1056, 1024, 9, 3)
+    assert gram_f64((3, 2, 60, 60, 41), 16, 3, (2, 2, 1), 0, 1) == (0, 3075, 1024, 14, 6)
+    assert gram_f64((1, 4, 46, 47, 47), 32, 3, 1, 1, 1) == (0, 3176, 1024, 42, 11)
+    assert gram_f64((2, 127, 10, 10, 10), 64, 1, 1, 0, 1) == (0, 63, 63, 68, 18)
+    # both sides of every step of the ladder (1^3 layers without bias: n = C1)
+    for c1, c2, want in [(40, 32, (12, 3)), (64, 16, (14, 6)), (64, 48, (22, 6)), (80, 32, (25, 11)), (128, 16, (44, 11)),
+                         (96, 64, (45, 18)), (128, 64, (68, 18))]:
+        assert gram_f64((1, c1, 4, 4, 4), c2, 1, 1, 0, 0)[3:] == want, (c1, c2)
+    assert gram_f64((1, 32, 8, 8, 8), 32, 3, 1, 1, 1)[0] == 1                                   # n = 865: not supported
+    # digit planes of the i8 loss: P balanced digits hold 127 (256^P - 1) / 255, which is below 2^(8P-1) - 1 from P = 2 on
+    for P in range(1, 7):
+        cap = 127 * ((256 ** P - 1) // 255)
+        assert lib.effq_gram_loss_i8_num_planes(cap) == P
+        assert lib.effq_gram_loss_i8_num_planes(cap + 1) == (P + 1 if P < 6 else -1)
+
+
+def test_gram_test_reference_agrees_with_the_oracle():
+    """The fp64 slab reference of tests/test_gram_shapes_gpu.py (strided views, slab by slab) against the oracle's
+    patch_matrix and ProxSystem at two small shapes - one strided, one without bias - to 1e-12 of the largest entry."""
+    from oracle import effq_oracle as O
+    from tests.test_gram_shapes_gpu import gram_reference
+    for (N, c1, D, H, W), c2, k, s, p, bias in [((2, 3, 7, 8, 9), 5, (3, 3, 3), (2, 2, 1), (1, 1, 1), True),
+                                                ((2, 4, 6, 5, 7), 3, (3, 3, 3), (1, 1, 1), (0, 0, 0), False)]:
+        gen = torch.Generator().manual_seed(c1 + c2)
+        x = torch.randn(N, c1, D, H, W, generator=gen, dtype=torch.float64)
+        w = torch.randn(c2, c1, *k, generator=gen, dtype=torch.float64)
+        b = torch.randn(c2, generator=gen, dtype=torch.float64) if bias else None
+        y = torch.nn.functional.conv3d(x, w, b, s, p) + torch.randn(1, dtype=torch.float64, generator=gen)
+        att = torch.randint(1, 4, y[:, 0].shape, generator=gen).double()
+        ref = gram_reference(x.permute(0, 2, 3, 4, 1), y.permute(0, 2, 3, 4, 1), att, k, s, p, bias, slab=40,
+                             want_patches=True, want_abs=True, G=w, b=b)
+        X = O.patch_matrix(x.numpy(), k, s, p, ones_row=bias, dtype=np.float64)
+        assert np.array_equal(ref["patches"].numpy(), X.T) and ref["V"] == X.shape[1] and ref["n"] == X.shape[0]
+        ps = O.ProxSystem(x, y, k, s, p, w, b, att, dtype=torch.float64)
+        Y = y.permute(1, 0, 2, 3, 4).reshape(c2, -1)
+        for got, want in ((2 * ref["A"], ps.A0), (2 * ref["B"], ps.B0), (ref["Au"], T(X @ X.T)), (ref["Bu"], Y @ T(X).T),
+                          (ref["absA"], T(np.abs(X) @ np.abs(X).T))):
+            assert (got - want).abs().max() <= 1e-12 * want.abs().max()
+        out = torch.nn.functional.conv3d(x, w, b, s, p)
+        assert abs(ref["loss"] - ((out - y) ** 2).sum().item()) <= 1e-12 * ((out - y) ** 2).sum().item()
+
+
 def test_product_path_refuses_cpu_tensors():
     from efficientq_amd import hip_ops, _lib
     with pytest.raises(_lib.EffqError):
