@@ -187,6 +187,9 @@ SIGNATURES = {
     "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
+    "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "effq_seg_lesions": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -196,6 +199,8 @@ SEG_ARGMAX, SEG_SIGMOID = 0, 1
 SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 # include/effq_hip.h: the label rules of effq_seg_labels
 SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}
+# the neighbourhood of the lesion metrics: the full 3 x 3 x 3, the 3-D counterpart of metrics.py's np.ones((3, 3))
+LESION_CONNECTIVITY = 26
 
 _lib = None
 

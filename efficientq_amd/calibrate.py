@@ -309,8 +309,10 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     set_name(model)
     set_snapdir(model, snap_dir)
     set_fp(model)
+    # the lesion switch is passed only when it is set: a tester that knows (folder, is_save_nii) alone keeps working
+    cc = {'is_cc': True} if getattr(args, 'is_cc', False) else {}
     if args.test_fp:
-        tester.test_as_is(folder='fp', is_save_nii=args.save_nii)
+        tester.test_as_is(folder='fp', is_save_nii=args.save_nii, **cc)
 
     res = calibrate_model(model, data_batch, args.task, args.init_stride, verbose=bool(args.lwq_verbose))
     body = (data_batch[:, 0] != 0.0) if args.task == 'brats' else torch.ones_like(data_batch[:, 0]).bool()
@@ -329,7 +331,7 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
         _save_nifti(res, args.task, snap_dir)
 
     if not args.no_test:
-        tester.test_as_is('ptq', args.save_nii)
+        tester.test_as_is('ptq', args.save_nii, **cc)
     model.cpu()
     tester.snapshot('state_in_fp.pkl', compress=False)
     store_int_weight(model)

@@ -72,6 +72,7 @@ def build_parser():
     # new in this build: one weight scale per output channel (the reference's alpha_w is one scalar per layer)
     p.add_argument('--lwq_channel_wise', action='store_true')
     p.add_argument('--save_nii', action='store_true')
+    p.add_argument('--is_cc', action='store_true', help='lesion-level metrics from connected components')
     # new in this build: synthetic calibration volumes (no dataset is shipped with either repo)
     p.add_argument('--synthetic', action='store_true', help='calibrate on seeded synthetic volumes')
     p.add_argument('--snap_dir', default=None)
@@ -158,7 +159,7 @@ TINY_NET = dict(task='lits', model='UResQ', nMod=1, nClass=3, multi_label=None, 
 
 def make_args(net: dict, qlvl_w: int, qlvl_a: int, **over):
     base = dict(pretrain=None, resume=None, device=0, round='1', suffix='', config=None, test_fp=False,
-                no_test=True, save_nii=False, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
+                no_test=True, save_nii=False, is_cc=False, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
                 lwq_verbose=False, qlvl_w=qlvl_w, qlvl_a=qlvl_a)
     base.update(net)
     base.update(over)

@@ -1,0 +1,55 @@
+// The per-voxel decisions of the validation kernels: which classes a voxel is predicted as and labelled as.  One
+// definition for the tallies, the label maps (seg_eval.hip) and the lesion counts (seg_cc.hip), so that they cannot
+// disagree about a voxel.
+#pragma once
+#include "common.h"
+
+namespace effq {
+
+// the decisions of one voxel: pred / gt bit c for class c
+template <int MODE, int C>
+__device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,
+                                       uint32_t& gt) {
+  pred = gt = 0;
+  if constexpr (MODE == EFFQ_SEG_ARGMAX) {
+    // torch.max over the channels: the first maximum wins, NaN counts as the largest value
+    int best = 0;
+    float bv = v[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) {
+      const float x = v[c];
+      if (x > bv || (x != x && bv == bv)) {
+        bv = x;
+        best = c;
+      }
+    }
+    pred = 1u << best;
+    const int l = lab[0];
+    gt = l < C ? (1u << l) : 0u;
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      pred |= (v[c] >= thresh ? 1u : 0u) << c;
+      gt |= (lab[c] != 0 ? 1u : 0u) << c;
+    }
+    if (fuse == EFFQ_SEG_FUSE_AGG) {        // p[i] = any(p[i:])
+      uint32_t f = 0, any = 0;
+#pragma unroll
+      for (int c = C - 1; c >= 0; --c) {
+        any |= (pred >> c) & 1u;
+        f |= any << c;
+      }
+      pred = f;
+    } else if (fuse == EFFQ_SEG_FUSE_CON) { // p[i] = all(p[:i+1])
+      uint32_t f = 0, all = 1;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        all &= (pred >> c) & 1u;
+        f |= all << c;
+      }
+      pred = f;
+    }
+  }
+}
+
+}  // namespace effq

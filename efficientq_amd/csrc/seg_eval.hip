@@ -11,6 +11,7 @@
 // count - the addends, the order and the rounding of evaluate.patch_to_image3d, so the result is the same bits.
 // Tallies: wave reductions into per-block partials, summed in block order by a second launch; integer counts only.
 #include "common.h"
+#include "seg_decide.h"
 
 namespace effq {
 
@@ -129,52 +130,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// the decisions of one voxel: pred / gt bit c for class c
-template <int MODE, int C>
-__device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,
-                                       uint32_t& gt) {
-  pred = gt = 0;
-  if constexpr (MODE == EFFQ_SEG_ARGMAX) {
-    // torch.max over the channels: the first maximum wins, NaN counts as the largest value
-    int best = 0;
-    float bv = v[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) {
-      const float x = v[c];
-      if (x > bv || (x != x && bv == bv)) {
-        bv = x;
-        best = c;
-      }
-    }
-    pred = 1u << best;
-    const int l = lab[0];
-    gt = l < C ? (1u << l) : 0u;
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      pred |= (v[c] >= thresh ? 1u : 0u) << c;
-      gt |= (lab[c] != 0 ? 1u : 0u) << c;
-    }
-    if (fuse == EFFQ_SEG_FUSE_AGG) {        // p[i] = any(p[i:])
-      uint32_t f = 0, any = 0;
-#pragma unroll
-      for (int c = C - 1; c >= 0; --c) {
-        any |= (pred >> c) & 1u;
-        f |= any << c;
-      }
-      pred = f;
-    } else if (fuse == EFFQ_SEG_FUSE_CON) { // p[i] = all(p[:i+1])
-      uint32_t f = 0, all = 1;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        all &= (pred >> c) & 1u;
-        f |= all << c;
-      }
-      pred = f;
-    }
-  }
 }
 
 // C classes known at compile time: every per-class loop unrolls and each thread keeps 3 C counters

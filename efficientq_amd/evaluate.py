@@ -127,6 +127,7 @@ def fp_vs_quantised_dice(model_q, images: torch.Tensor, task: str, fp_model=None
 METRICS = ("dsc", "sens", "spec", "acc")
 WINDOW_BATCH_MAX = 16     # windows per forward at most (a BraTS case has 8 of 128^3)
 EPS = 1e-6                # metrics.py
+LESION_COLUMNS = ("totall", "predl", "fnl", "fpl")     # the columns of "lesions" (hip_ops.seg_lesions)
 
 
 def metrics_from_counts(counts: torch.Tensor) -> dict:
@@ -167,7 +168,7 @@ def _write_map(path, host, dtype):
 
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
-                 save_dir=None, label_dtype=np.uint16, multi_label=None):
+                 save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -179,7 +180,10 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     spec / acc per class.
     save_dir: also write each case's predicted map, from the same decisions (effq_seg_labels, rule label_rule(...,
     multi_label, task)), to <save_dir>/<name>.nii.gz as `label_dtype` with the identity affine (validate.py:247-260).
-    The files are written by one background thread while the device goes on; all are written when this returns."""
+    The files are written by one background thread while the device goes on; all are written when this returns.
+    lesions: each dict also carries "lesions", the C x 4 int64 lesion-level counts LESION_COLUMNS of the same decisions
+    (effq_seg_lesions: connected components with the 3 x 3 x 3 neighbourhood; validate_seg(..., is_cc=True),
+    metrics.py:69-94) - one more call per case after the tallies."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -235,6 +239,9 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                 i = len(results)
                 res = {"name": names[i] if names is not None else str(i), "counts": counts}
                 res.update(metrics_from_counts(counts))
+                if lesions:
+                    res["lesions"] = ops.seg_lesions(stitched[n], lab[n], "brats" if multi else "lits",
+                                                     fuse if multi else None).cpu()
                 results.append(res)
                 if maps is not None:
                     writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
@@ -248,17 +255,24 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
 
 
 def write_metrics_csv(path: str, results) -> None:
-    """One row per subject and class: subject, class, dsc, sens, spec, acc, tp, fp, fn, tn."""
+    """One row per subject and class: subject, class, dsc, sens, spec, acc, tp, fp, fn, tn, and when the results carry
+    "lesions" (validate_seg(..., lesions=True)) also totall, predl, fnl, fpl."""
     import csv
+    cc = any("lesions" in r for r in results)
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn"))
+        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn") + (LESION_COLUMNS if cc else ()))
         for r in results:
             for c in range(r["counts"].shape[0]):
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
-                            [int(v) for v in r["counts"][c]])
+                            [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []))
 
 
 def metric_means(results) -> dict:
     """Per-class mean over the cases of each metric."""
     return {m: torch.stack([r[m] for r in results]).mean(0) for m in METRICS}
+
+
+def lesion_totals(results) -> torch.Tensor:
+    """Per-class sums over the cases of the lesion-level counts (C x 4 int64: LESION_COLUMNS)."""
+    return torch.stack([r["lesions"].to("cpu", torch.int64) for r in results]).sum(0)

@@ -1132,6 +1132,63 @@ class HipOps:
                                        out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
         return out
 
+    def cc_label(self, mask: torch.Tensor, connectivity: int = 26):
+        """Connected components of 0/1 volumes (effq_cc_label; scipy.ndimage.label in metrics.py:69-73): `mask` D x H x W
+        or P x D x H x W uint8, non-zero = foreground.  Returns (labels, ncomp): int32 labels of the mask's shape, 0 for
+        background and 1 + the least linear index of the voxel's component otherwise, and the int64 component count of
+        each mask.  connectivity 26 (3 x 3 x 3 neighbourhood) or 6 (faces)."""
+        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
+            raise _lib.EffqError(f"cc_label: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
+        if mask.device != self.device and not (mask.device.type == "cuda" and
+                                               self.device.index in (None, mask.device.index)):
+            raise _lib.EffqError(f"cc_label: mask on {mask.device}, ops on {self.device}")
+        if connectivity not in (6, 26):
+            raise _lib.EffqError(f"cc_label: connectivity {connectivity}, 6 or 26")
+        m = mask.contiguous()
+        D, H, W = (int(i) for i in m.shape[-3:])
+        P = int(m.shape[0]) if m.dim() == 4 else 1
+        if P > 65535 or m.numel() >= 2 ** 31:
+            raise _lib.EffqError(f"cc_label: {P} masks of {D * H * W} voxels (at most 65535 masks, 2^31 - 1 voxels in all)")
+        labels = torch.empty(m.shape, dtype=torch.int32, device=self.device)
+        ncomp = torch.empty(P, dtype=torch.int64, device=self.device)
+        ws = self._workspace("cc", self.lib.effq_cc_ws_bytes(P, D, H, W))
+        check(self.lib.effq_cc_label(_ptr(m), P, D, H, W, int(connectivity), _ptr(labels), _ptr(ncomp), _ptr(ws),
+                                     ws.numel(), self.stream), "effq_cc_label")
+        return labels, (ncomp if m.dim() == 4 else ncomp[0])
+
+    def seg_lesions(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
+        """The lesion-level columns of one case (C x 4 int64: totall, predl, fnl, fpl - components of the label mask, of
+        the predicted mask, label components without a predicted voxel, predicted components without a labelled voxel;
+        metrics.py:69-94 with the 3 x 3 x 3 neighbourhood) from its stitched logits (C x D x H x W) and its label
+        (effq_seg_lesions).  Arguments and decisions as seg_tallies."""
+        x = self._f32(logits)
+        if x.dim() != 4:
+            raise _lib.EffqError(f"seg_lesions: expected C x D x H x W logits, got {tuple(x.shape)}")
+        Cc, D, H, W = (int(i) for i in x.shape)
+        if task == "lits":
+            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
+        elif task == "brats":
+            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
+        else:
+            raise _lib.EffqError(f"Unknown task {task}")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
+            raise _lib.EffqError(f"seg_lesions: merge type {fuse!r} for task {task}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_lesions: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
+            raise _lib.EffqError(f"seg_lesions: label {tuple(label.shape)} {label.dtype} on {label.device}, "
+                                 f"needs {lshape} torch.uint8 on {x.device}")
+        if D * H * W == 0 or 2 * Cc * D * H * W >= 2 ** 31:
+            raise _lib.EffqError(f"seg_lesions: {2 * Cc} masks of {D * H * W} voxels (2^31 - 1 voxels in all at most)")
+        lab = label.contiguous()
+        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
+        ws = self._workspace("cc", self.lib.effq_cc_ws_bytes(2 * Cc, D, H, W))
+        check(self.lib.effq_seg_lesions(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh,
+                                        _lib.LESION_CONNECTIVITY, _ptr(counts), _ptr(ws), ws.numel(), self.stream),
+              "effq_seg_lesions")
+        return counts
+
 
 _OPS = {}
 

@@ -592,6 +592,34 @@ int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long
 int effq_seg_labels(const float* logits, int N, int C, long long S, int rule, int fuse, float thresh, int out_bytes,
                     void* out, void* stream);
 
+/* ---- connected components of 0/1 volumes and the lesion-level columns of the validation (validate_seg(..., is_cc=True):
+ * utils/validate.py:28-36, utils/metrics.py:69-94: num_component, num_false_positive, num_positive, num_false_negative,
+ * there with scipy.ndimage.label on the host).  Block-based union-find: tiles of 8 x 8 x 32 voxels are labelled in LDS,
+ * the tiles are joined across their faces, edges and corners by a lock-free atomicMin union on the label array, every
+ * voxel is pointed at its root and the roots are counted.  Five launches (with the masks and the zeroing of the flags
+ * of effq_seg_lesions: seven), all on `stream`, no read by the host and no workgroup that waits for another.
+ *
+ * effq_cc_label: masks (P, D, H, W) uint8, non-zero = foreground -> labels (P, D, H, W) int32: 0 for background, for a
+ *   foreground voxel 1 + the least linear index (d*H*W + h*W + w) of any voxel of its component; ncomp (P) = the number
+ *   of components of each mask.  The label does not depend on the order of the unions: equal inputs give equal bits, and
+ *   numbering the distinct labels in raster order gives scipy.ndimage.label's.  connectivity 26 (the full 3 x 3 x 3
+ *   neighbourhood, the 3-D counterpart of the np.ones((3, 3)) of metrics.py) or 6 (faces only, scipy's default).
+ *   P * D*H*W < 2^31, P <= 65535.
+ * effq_seg_lesions: stitched logits (C, D, H, W) of one case and its label, arguments as effq_seg_tallies -> counts
+ *   (C, 4) int64 per class: totall = components of the label mask (num_positive), predl = components of the predicted
+ *   mask, fnl = label components without a predicted voxel (num_false_negative), fpl = predicted components without a
+ *   labelled voxel (num_false_positive).  The masks are the tallies' own decisions (in argmax mode class 0, the
+ *   background, is a class like any other); the 2 C masks are labelled by the same launches.
+ * ws: effq_cc_ws_bytes(P, D, H, W) bytes for either call, P = 2 C for effq_seg_lesions: 4 B of label, 1 B of overlap flag
+ *   per plane and voxel, 2 B of decision bits per voxel and the partial counts (effq_cc_label keeps its labels in
+ *   `labels` and uses the partial counts only).  A BraTS case (3 classes, 155 x 240 x 240): 6 planes x 8.9 M x 4 B =
+ *   214 MB of labels, 286 MB in all. */
+size_t effq_cc_ws_bytes(int P, int D, int H, int W);
+int effq_cc_label(const uint8_t* masks, int P, int D, int H, int W, int connectivity, int32_t* labels,
+                  long long* ncomp, void* ws, size_t ws_bytes, void* stream);
+int effq_seg_lesions(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                     float thresh, int connectivity, long long* counts, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,12 @@
 BraTS net (diagnostic, GPU): the three validation kernels alone, and evaluate.validate_seg against the per-window loop
 (evaluate.sliding_window_forward + torch counts), all timed with HIP events.  Prints one JSON line.
 --save-nii adds the label-map kernel (warm, and after 512 MiB of other writes have pushed the logits out of the
-Infinity Cache) and validate_seg over three such cases with and without save_dir, wall time per case."""
+Infinity Cache) and validate_seg over three such cases with and without save_dir, wall time per case.
+--is-cc adds effq_seg_lesions (the lesion-level columns: connected components of the 2 x 3 masks of the case) on the
+calibrated net's own stitched logits and on random logits (masks of density 0.5: one giant component with holes), with
+validate_seg per case with and without lesions=True, and - where scipy is importable - the reference's way on the same
+masks (device -> host copy + ndimage.label of the label mask and the predicted mask of each class).  The time per phase
+is read from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- python scripts/time_validation.py --is-cc)."""
 import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,6 +16,7 @@ from efficientq_amd.hip_ops import from_ndhwc, get_ops
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--save-nii", dest="save_nii", action="store_true", help="also time the NIfTI label maps")
+ap.add_argument("--is-cc", dest="is_cc", action="store_true", help="also time the lesion-level counts")
 cli = ap.parse_args()
 REPS = int(os.environ.get("REPS", "5"))
 HBM_PEAK = 8.0e12
@@ -112,4 +118,53 @@ if cli.save_nii:
         res["validate_ms_per_case"] = wall(None)
         res["validate_save_nii_ms_per_case"] = wall(tmp)
         res["nii_gz_bytes"] = os.path.getsize(os.path.join(tmp, "0.nii.gz"))
+
+if cli.is_cc:
+    # the calibrated net's own logits of the case, stitched as validate_seg stitches them
+    with torch.no_grad():
+        out = E._last_head(model(from_ndhwc(win)))
+    net_logits = ops.window_stitch(out.permute(0, 2, 3, 4, 1).contiguous(), (1, 3) + shape, p, o)
+    planes = 6
+    # algorithmic bytes: logits and label read, 2 B of decision bits written and read by the tiles and the flatten, 4 B
+    # labels written by the tiles, read by the merge's surface voxels (about half), read and written by the flatten,
+    # read by the count; 1 B flags zeroed and read
+    nbytes = vox * (3 * 5 + 2 * 3) + planes * vox * (4 * 4.5 + 2)
+    for key, lg in (("lesions", net_logits), ("lesions_random_logits", stitched)):
+        ms = timed(lambda: ops.seg_lesions(lg[0], lab8, "brats", "agg"))
+        res[key] = {"ms": round(ms, 4), "bytes": int(nbytes), "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3),
+                    "counts": ops.seg_lesions(lg[0], lab8, "brats", "agg").tolist()}
+    res["cc_ws_MB"] = round(ops.lib.effq_cc_ws_bytes(planes, *shape) / 1e6, 1)
+
+    def wall_cc(lesions):
+        ms = []
+        for i in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            E.validate_seg(model, loader * 3, "brats", p, o, window_batch=nwin, fuse="agg", lesions=lesions)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3 / 3)
+        return round(sorted(ms[1:])[1], 2)
+    res["validate_ms_per_case"] = wall_cc(False)
+    res["validate_lesions_ms_per_case"] = wall_cc(True)
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    res["scipy"] = ndimage is not None
+    if ndimage is not None:
+        import numpy as np
+        pred = ops.seg_labels(net_logits, "planes", "agg")[0]
+
+        def host_way():
+            pm, gm = pred.cpu().numpy(), lab8.cpu().numpy()
+            return [ndimage.label(m[c], np.ones((3, 3, 3)))[1] for c in range(3) for m in (gm, pm)]
+        host_way()
+        ms = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host_way()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        res["scipy_label_ms"] = round(sorted(ms)[1], 1)
+        res["scipy_over_kernel"] = round(res["scipy_label_ms"] / res["lesions"]["ms"], 1)
 print(json.dumps(res))
