@@ -190,6 +190,9 @@ SIGNATURES = {
     "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "effq_seg_lesions": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _SZ, _P]),
+    "effq_surf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "effq_edt_sq": (_I, [_P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "effq_seg_surface": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -201,6 +204,8 @@ SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}
 # the neighbourhood of the lesion metrics: the full 3 x 3 x 3, the 3-D counterpart of metrics.py's np.ones((3, 3))
 LESION_CONNECTIVITY = 26
+# include/effq_hip.h: the longest line of the h and d passes of the distance transform
+EDT_MAX_LINE = 16382
 
 _lib = None
 

@@ -309,8 +309,11 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     set_name(model)
     set_snapdir(model, snap_dir)
     set_fp(model)
-    # the lesion switch is passed only when it is set: a tester that knows (folder, is_save_nii) alone keeps working
+    # the lesion and surface switches are passed only when they are set: a tester that knows (folder, is_save_nii)
+    # alone keeps working
     cc = {'is_cc': True} if getattr(args, 'is_cc', False) else {}
+    if getattr(args, 'surf_dist', False):
+        cc['is_surf'] = True
     if args.test_fp:
         tester.test_as_is(folder='fp', is_save_nii=args.save_nii, **cc)
 

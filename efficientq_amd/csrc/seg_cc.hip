@@ -17,15 +17,14 @@
 // is an older parent in the same component, and only the value an atomicMin returns decides that a union is done.
 #include "common.h"
 #include "seg_decide.h"
+#include "seg_masks.h"
 
 namespace effq {
 
 constexpr int CC_TD = 8, CC_TH = 8, CC_TW = 32;        // tile: 2048 voxels, 8 KB of LDS, rows of 128 B of labels
 constexpr int CC_TVOX = CC_TD * CC_TH * CC_TW;
-constexpr int CC_THREADS = 256;
 constexpr int CC_VPT = CC_TVOX / CC_THREADS;
 constexpr int CC_WAVES = CC_THREADS / 64;
-constexpr int CC_STREAM_BLOCKS = 4096;                 // merge / flatten: blocks per plane at most, grid-stride beyond
 constexpr int CC_COUNT_BLOCKS = 512;                   // count: blocks per plane at most = partials per plane
 static_assert(CC_TW == 32 && CC_THREADS % 64 == 0, "one ballot holds two rows of a tile");
 
@@ -61,68 +60,6 @@ static CcWs cc_ws(void* ws, int P, size_t S) {
   r.flags = reinterpret_cast<uint8_t*>(p + off);    off += align16((size_t)P * S);
   r.bytes = off;
   return r;
-}
-
-// ---- masks ----------------------------------------------------------------------------------------------------------
-struct CcMaskParams {
-  const float* logits;    // (C, S)
-  const uint8_t* label;   // (S) class ids for argmax, (C, S) 0/1 for multi-label
-  uint16_t* bits;         // (S)
-  long long S;
-  int fuse;
-  float thresh;
-};
-
-template <int MODE, int VEC, int C>
-__global__ __launch_bounds__(CC_THREADS) void k_cc_masks(CcMaskParams p) {
-  const long long groups = p.S / VEC;
-  const long long lab_stride = MODE == EFFQ_SEG_ARGMAX ? 0 : p.S;
-  for (long long g = (long long)blockIdx.x * CC_THREADS + threadIdx.x; g < groups;
-       g += (long long)gridDim.x * CC_THREADS) {
-    float v[VEC][C];
-    uint8_t lab[VEC][C];
-    constexpr int nlab = MODE == EFFQ_SEG_ARGMAX ? 1 : C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      if constexpr (VEC == 4) {
-        const float4 f = *reinterpret_cast<const float4*>(p.logits + c * p.S + g * 4);
-        v[0][c] = f.x; v[1][c] = f.y; v[2][c] = f.z; v[3][c] = f.w;
-      } else {
-        v[0][c] = p.logits[c * p.S + g];
-      }
-      if (c < nlab) {
-        if constexpr (VEC == 4) {
-          const uchar4 l = *reinterpret_cast<const uchar4*>(p.label + c * lab_stride + g * 4);
-          lab[0][c] = l.x; lab[1][c] = l.y; lab[2][c] = l.z; lab[3][c] = l.w;
-        } else {
-          lab[0][c] = p.label[c * lab_stride + g];
-        }
-      }
-    }
-    uint16_t b[VEC];
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) {
-      uint32_t pred, gt;
-      decide<MODE, C>(v[u], lab[u], p.fuse, p.thresh, pred, gt);
-      b[u] = (uint16_t)(pred | (gt << 8));
-    }
-    if constexpr (VEC == 4)
-      *reinterpret_cast<ushort4*>(p.bits + g * 4) = make_ushort4(b[0], b[1], b[2], b[3]);
-    else
-      p.bits[g] = b[0];
-  }
-}
-
-template <int C>
-static void launch_masks(int mode, bool v4, dim3 g, hipStream_t st, const CcMaskParams& p) {
-  const dim3 b(CC_THREADS);
-  if (mode == EFFQ_SEG_ARGMAX) {
-    if (v4) hipLaunchKernelGGL((k_cc_masks<EFFQ_SEG_ARGMAX, 4, C>), g, b, 0, st, p);
-    else hipLaunchKernelGGL((k_cc_masks<EFFQ_SEG_ARGMAX, 1, C>), g, b, 0, st, p);
-  } else {
-    if (v4) hipLaunchKernelGGL((k_cc_masks<EFFQ_SEG_SIGMOID, 4, C>), g, b, 0, st, p);
-    else hipLaunchKernelGGL((k_cc_masks<EFFQ_SEG_SIGMOID, 1, C>), g, b, 0, st, p);
-  }
 }
 
 // ---- union-find -----------------------------------------------------------------------------------------------------
@@ -362,12 +299,6 @@ __global__ __launch_bounds__(64) void k_cc_final(const uint32_t* __restrict__ pa
   }
 }
 
-static unsigned cc_grid(size_t items, size_t cap) {
-  size_t nb = (items + CC_THREADS - 1) / CC_THREADS;
-  if (nb < 1) nb = 1;
-  return (unsigned)(nb < cap ? nb : cap);
-}
-
 // the launches after the masks; C == 0: plain labelling (no flags), out = ncomp (P)
 static int cc_run(const CcSrc& src, int P, int D, int H, int W, int conn, int* labels, uint8_t* flags, int C,
                   uint32_t* partial, long long* out, hipStream_t st) {
@@ -436,22 +367,8 @@ int effq_seg_lesions(const float* logits, const uint8_t* label, int C, int D, in
     return EFFQ_ERR_WORKSPACE;
   }
   const hipStream_t st = as_stream(stream);
-  CcMaskParams p;
-  p.logits = logits; p.label = label; p.bits = s.bits; p.S = (long long)S; p.fuse = fuse; p.thresh = thresh;
-  const bool v4 = S % 4 == 0 && ((reinterpret_cast<uintptr_t>(logits) & 15) | (reinterpret_cast<uintptr_t>(label) & 3) |
-                                 (reinterpret_cast<uintptr_t>(s.bits) & 7)) == 0;
-  const dim3 g(cc_grid(v4 ? S / 4 : S, CC_STREAM_BLOCKS));
-  switch (C) {
-    case 1: launch_masks<1>(mode, v4, g, st, p); break;
-    case 2: launch_masks<2>(mode, v4, g, st, p); break;
-    case 3: launch_masks<3>(mode, v4, g, st, p); break;
-    case 4: launch_masks<4>(mode, v4, g, st, p); break;
-    case 5: launch_masks<5>(mode, v4, g, st, p); break;
-    case 6: launch_masks<6>(mode, v4, g, st, p); break;
-    case 7: launch_masks<7>(mode, v4, g, st, p); break;
-    default: launch_masks<8>(mode, v4, g, st, p); break;
-  }
-  EFFQ_LAUNCH_CHECK();
+  const int rc = cc_decision_bits(logits, label, C, S, mode, fuse, thresh, s.bits, st);
+  if (rc != EFFQ_OK) return rc;
   CcSrc src;
   src.masks = nullptr; src.bits = s.bits; src.C = C;
   return cc_run(src, P, D, H, W, connectivity, s.labels, s.flags, C, s.partial, counts, st);

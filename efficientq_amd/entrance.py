@@ -8,7 +8,8 @@ Labelled volumes in the reference's layout are read with ``--data_dir`` / ``--sp
 calibration takes the train split, and ``--test_fp`` / the default test (unless ``--no_test``) validate the FP and
 the calibrated network on the val split (evaluate.validate_seg), writing ``<snap>/{fp,ptq}/metrics.csv``;
 ``--save_nii`` adds the predicted label maps ``<snap>/{fp,ptq}/val/<subject>.nii.gz`` and ``<snap>/{Q,FP}seg<i>.nii.gz``;
-``--is_cc`` adds the lesion-level columns ``totall, predl, fnl, fpl`` (connected components) to ``metrics.csv``.
+``--is_cc`` adds the lesion-level columns ``totall, predl, fnl, fpl`` (connected components) to ``metrics.csv``;
+``--surf_dist`` adds the surface distances ``hd, hd95, assd`` (voxel units) after them.
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
 the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
@@ -51,13 +52,14 @@ class _SnapshotWriter:
 class _ValidationTester(_SnapshotWriter):
     """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
     <root>/<folder>/metrics.csv, with is_save_nii also every val subject's predicted map as
-    <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns."""
+    <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns, with is_surf also the
+    surface distances."""
 
     def __init__(self, model, root, data_cube, task, rank=0):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
 
-    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False):
+    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False):
         if self.rank != 0:
             return
         if self.cube.valloader is None:
@@ -68,16 +70,20 @@ class _ValidationTester(_SnapshotWriter):
         res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
                              fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
                              save_dir=os.path.join(out, 'val') if is_save_nii else None,
-                             multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc)
+                             multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
+                             surface=is_surf)
         os.makedirs(out, exist_ok=True)
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         means = E.metric_means(res)
         print(f'[entrance] {folder}: {len(res)} val cases in {time.time() - t0:.2f}s, per-class means:')
         tot = E.lesion_totals(res) if is_cc else None
+        surf = E.surface_means(res) if is_surf else None
         for c in range(len(means['dsc'])):
             line = f'  class {c}: ' + ', '.join(f'{m} = {float(means[m][c]):.4f}' for m in E.METRICS)
             if is_cc:
                 line += ', ' + ', '.join(f'{k} = {int(tot[c][j])}' for j, k in enumerate(E.LESION_COLUMNS))
+            if is_surf:
+                line += ', ' + ', '.join(f'{k} = {float(surf[c][j]):.3f}' for j, k in enumerate(E.SURFACE_COLUMNS))
             print(line)
 
 

@@ -9,6 +9,7 @@ quantized mode, i.e. every conv runs ``conv3d_quant_calib_step`` with the activa
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Sequence
 
@@ -128,6 +129,7 @@ METRICS = ("dsc", "sens", "spec", "acc")
 WINDOW_BATCH_MAX = 16     # windows per forward at most (a BraTS case has 8 of 128^3)
 EPS = 1e-6                # metrics.py
 LESION_COLUMNS = ("totall", "predl", "fnl", "fpl")     # the columns of "lesions" (hip_ops.seg_lesions)
+SURFACE_COLUMNS = ("hd", "hd95", "assd")               # the columns of "surface" (surface_metrics), voxel units
 
 
 def metrics_from_counts(counts: torch.Tensor) -> dict:
@@ -140,6 +142,32 @@ def metrics_from_counts(counts: torch.Tensor) -> dict:
             "sens": (tp.float() + EPS) / ((tp + fn).float() + EPS),
             "spec": (tn.float() + EPS) / ((tn + fp).float() + EPS),
             "acc": (tp + tn).float() / n}
+
+
+def surface_metrics(counts, sums, shape) -> torch.Tensor:
+    """hd, hd95, assd per class (C x 3 float64, voxel units) of one case of extent `shape` = (D, H, W) from what
+    hip_ops.seg_surface returns: counts C x 6 = nP, nL, maxsq_PL, maxsq_LP, qlo_sq, qhi_sq and sums C x 2.  With the
+    surface voxels S(P), S(L) of the predicted and the label mask and the distances of each to the other surface:
+    hd = the largest of all, hd95 = the 95th percentile of the n = nP + nL pooled distances with linear interpolation
+    between the order statistics (numpy.percentile: 95 (n - 1) = 100 lo + r in integers, v[lo] + (v[min(lo + 1, n - 1)]
+    - v[lo]) r / 100), assd = the mean of the two directed means: medpy's hd, hd95 and assd.  Both surfaces empty: 0;
+    one of them empty: sqrt(D^2 + H^2 + W^2) for all three (the BraTS convention)."""
+    counts = torch.as_tensor(counts).to("cpu", torch.int64)
+    sums = torch.as_tensor(sums).to("cpu", torch.float64)
+    diag = math.sqrt(sum(int(e) ** 2 for e in shape))
+    out = torch.zeros(counts.shape[0], 3, dtype=torch.float64)
+    for c, ((n_p, n_l, max_pl, max_lp, qlo, qhi), (sum_pl, sum_lp)) in enumerate(zip(counts.tolist(), sums.tolist())):
+        if n_p == 0 and n_l == 0:
+            continue
+        if n_p == 0 or n_l == 0:
+            out[c] = diag
+            continue
+        r = 95 * (n_p + n_l - 1) % 100
+        lo, hi = math.sqrt(qlo), math.sqrt(qhi)
+        out[c, 0] = math.sqrt(max(max_pl, max_lp))
+        out[c, 1] = lo + (hi - lo) * r / 100
+        out[c, 2] = (sum_pl / n_p + sum_lp / n_l) / 2
+    return out
 
 
 def _last_head(out) -> torch.Tensor:
@@ -168,7 +196,7 @@ def _write_map(path, host, dtype):
 
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
-                 save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False):
+                 save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -183,7 +211,10 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     The files are written by one background thread while the device goes on; all are written when this returns.
     lesions: each dict also carries "lesions", the C x 4 int64 lesion-level counts LESION_COLUMNS of the same decisions
     (effq_seg_lesions: connected components with the 3 x 3 x 3 neighbourhood; validate_seg(..., is_cc=True),
-    metrics.py:69-94) - one more call per case after the tallies."""
+    metrics.py:69-94) - one more call per case after the tallies.
+    surface: each dict also carries "surface", the C x 3 float64 surface distances SURFACE_COLUMNS of the same decisions
+    in voxel units (surface_metrics), and "surface_counts", the C x 6 int64 they come from (effq_seg_surface: an exact
+    distance transform of the 2 C surfaces on the device) - one more call per case after the tallies."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -242,6 +273,11 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                 if lesions:
                     res["lesions"] = ops.seg_lesions(stitched[n], lab[n], "brats" if multi else "lits",
                                                      fuse if multi else None).cpu()
+                if surface:
+                    sc, ss = ops.seg_surface(stitched[n], lab[n], "brats" if multi else "lits",
+                                             fuse if multi else None)
+                    res["surface_counts"] = sc.cpu()
+                    res["surface"] = surface_metrics(res["surface_counts"], ss, vol.shape[-3:])
                 results.append(res)
                 if maps is not None:
                     writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
@@ -256,16 +292,20 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
 
 def write_metrics_csv(path: str, results) -> None:
     """One row per subject and class: subject, class, dsc, sens, spec, acc, tp, fp, fn, tn, and when the results carry
-    "lesions" (validate_seg(..., lesions=True)) also totall, predl, fnl, fpl."""
+    "lesions" (validate_seg(..., lesions=True)) also totall, predl, fnl, fpl, and when they carry "surface"
+    (validate_seg(..., surface=True)) after those hd, hd95, assd."""
     import csv
     cc = any("lesions" in r for r in results)
+    sd = any("surface" in r for r in results)
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn") + (LESION_COLUMNS if cc else ()))
+        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn") + (LESION_COLUMNS if cc else ()) +
+                    (SURFACE_COLUMNS if sd else ()))
         for r in results:
             for c in range(r["counts"].shape[0]):
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
-                            [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []))
+                            [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []) +
+                            (["%.7g" % float(v) for v in r["surface"][c]] if sd else []))
 
 
 def metric_means(results) -> dict:
@@ -276,3 +316,8 @@ def metric_means(results) -> dict:
 def lesion_totals(results) -> torch.Tensor:
     """Per-class sums over the cases of the lesion-level counts (C x 4 int64: LESION_COLUMNS)."""
     return torch.stack([r["lesions"].to("cpu", torch.int64) for r in results]).sum(0)
+
+
+def surface_means(results) -> torch.Tensor:
+    """Per-class means over the cases of the surface distances (C x 3 float64: SURFACE_COLUMNS)."""
+    return torch.stack([r["surface"].to("cpu", torch.float64) for r in results]).mean(0)

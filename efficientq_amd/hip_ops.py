@@ -1189,6 +1189,63 @@ class HipOps:
               "effq_seg_lesions")
         return counts
 
+    def edt_sq(self, mask: torch.Tensor):
+        """Exact squared Euclidean distance transform (effq_edt_sq): `mask` D x H x W or P x D x H x W uint8, non-zero =
+        site.  Returns an int32 tensor of the mask's shape: the squared distance (voxel units) of every voxel to the
+        nearest site of its own volume, 0 on a site, INT32_MAX throughout a volume without sites.  It is
+        rint(scipy.ndimage.distance_transform_edt(mask == 0) ** 2), voxel for voxel."""
+        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
+            raise _lib.EffqError(f"edt_sq: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
+        if mask.device != self.device and not (mask.device.type == "cuda" and
+                                               self.device.index in (None, mask.device.index)):
+            raise _lib.EffqError(f"edt_sq: mask on {mask.device}, ops on {self.device}")
+        m = mask.contiguous()
+        D, H, W = (int(i) for i in m.shape[-3:])
+        P = int(m.shape[0]) if m.dim() == 4 else 1
+        need = self.lib.effq_surf_ws_bytes(P, D, H, W)
+        if need == 0:
+            raise _lib.EffqError(f"edt_sq: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels in "
+                                 f"all, D^2 + H^2 + W^2 < 2^31, D and H at most {_lib.EDT_MAX_LINE})")
+        sq = torch.empty(m.shape, dtype=torch.int32, device=self.device)
+        ws = self._workspace("surf", need)
+        check(self.lib.effq_edt_sq(_ptr(m), P, D, H, W, _ptr(sq), _ptr(ws), ws.numel(), self.stream), "effq_edt_sq")
+        return sq
+
+    def seg_surface(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
+        """What the surface distances of one case need (effq_seg_surface), from its stitched logits (C x D x H x W) and
+        its label, arguments and decisions as seg_tallies.  Returns (counts, sums): counts C x 6 int64 = nP, nL,
+        maxsq_PL, maxsq_LP, qlo_sq, qhi_sq and sums C x 2 float64 = the sums of the directed distances
+        (include/effq_hip.h); evaluate.surface_metrics turns them into hd, hd95 and assd."""
+        x = self._f32(logits)
+        if x.dim() != 4:
+            raise _lib.EffqError(f"seg_surface: expected C x D x H x W logits, got {tuple(x.shape)}")
+        Cc, D, H, W = (int(i) for i in x.shape)
+        if task == "lits":
+            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
+        elif task == "brats":
+            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
+        else:
+            raise _lib.EffqError(f"Unknown task {task}")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
+            raise _lib.EffqError(f"seg_surface: merge type {fuse!r} for task {task}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_surface: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
+            raise _lib.EffqError(f"seg_surface: label {tuple(label.shape)} {label.dtype} on {label.device}, "
+                                 f"needs {lshape} torch.uint8 on {x.device}")
+        need = self.lib.effq_surf_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
+        if need == 0:
+            raise _lib.EffqError(f"seg_surface: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
+                                 f"most, D^2 + H^2 + W^2 < 2^31, D and H at most {_lib.EDT_MAX_LINE})")
+        lab = label.contiguous()
+        counts = torch.empty(Cc, 6, dtype=torch.int64, device=self.device)
+        sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
+        ws = self._workspace("surf", need)
+        check(self.lib.effq_seg_surface(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh, _ptr(counts),
+                                        _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface")
+        return counts, sums
+
 
 _OPS = {}
 

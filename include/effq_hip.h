@@ -620,6 +620,39 @@ int effq_cc_label(const uint8_t* masks, int P, int D, int H, int W, int connecti
 int effq_seg_lesions(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
                      float thresh, int connectivity, long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- exact Euclidean distance transform of 3-D masks and the surface-distance columns of the validation
+ * (validate_seg(..., surface=True): hd, hd95, assd per class; the reference has no counterpart, the definitions are
+ * DESIGN section 13's).  Voxel units.  Separable and in integers throughout, so the squared distances are exact: along
+ * w the distance to the nearest site of the row (one wave per row, ballots), then along h and along d the lower envelope
+ * min_j (g(j) + (i - j)^2) of every line, a slab of lines staged in LDS and searched outwards from each voxel until
+ * (i - j)^2 reaches the best value so far.  Three launches for effq_edt_sq; effq_seg_surface adds the decision bits, the
+ * surface stencil, the zeroing and the filling of the histograms and their walk: eight, all on `stream`, no read by the
+ * host and no workgroup that waits for another.
+ *
+ * effq_edt_sq: masks (P, D, H, W) uint8, non-zero = site -> sq (P, D, H, W) int32: the squared Euclidean distance of
+ *   every voxel to the nearest site of its own plane (0 on a site), INT32_MAX everywhere in a plane without sites.
+ *   P * D*H*W < 2^31, P <= 65535, D^2 + H^2 + W^2 < 2^31 (every distance fits), D and H <= EFFQ_EDT_MAX_LINE (a line
+ *   of the h and d passes is staged in the LDS of one workgroup).
+ * effq_seg_surface: stitched logits (C, D, H, W) of one case and its label, arguments as effq_seg_tallies.  Per class
+ *   P = the predicted mask, L = the label mask (the tallies' own decisions; in argmax mode class 0 is a class like any
+ *   other), S(M) = the voxels of M with a face neighbour that is background or outside the volume, E_M(v) = the squared
+ *   distance of v to the nearest voxel of S(M).  counts (C, 6) int64 = nP, nL (voxels of S(P), S(L)), maxsq_PL,
+ *   maxsq_LP (the largest E_L over S(P), the largest E_P over S(L); 0 where the set or the target is empty), qlo_sq,
+ *   qhi_sq (the squared distances at ranks lo and min(lo + 1, n - 1) of the n = nP + nL pooled values in ascending
+ *   order, lo = 95 (n - 1) / 100 in integers; 0 when a surface is empty); sums (C, 2) fp64 = the sum of sqrt(E_L) over
+ *   S(P) and of sqrt(E_P) over S(L) (0 where the target is empty), added per bin of a histogram over E in a fixed
+ *   order: equal inputs give equal bits.  hd, hd95 and assd follow on the host (evaluate.surface_metrics).
+ * ws: effq_surf_ws_bytes(P, D, H, W) bytes for either call, P = 2 C for effq_seg_surface: 4 B of squared distance per
+ *   plane and voxel, 2 B of decision bits and 2 B of surface bits per voxel, and per plane a histogram of
+ *   (D-1)^2 + (H-1)^2 + (W-1)^2 + 2 counters (effq_edt_sq writes into `sq` and only checks the size).  A BraTS case
+ *   (3 classes, 155 x 240 x 240): 214 MB of distances, 253 MB in all.  Bad arguments and a short workspace return
+ *   EFFQ_ERR_ARG and launch nothing. */
+#define EFFQ_EDT_MAX_LINE 16382
+size_t effq_surf_ws_bytes(int P, int D, int H, int W);
+int effq_edt_sq(const uint8_t* masks, int P, int D, int H, int W, int32_t* sq, void* ws, size_t ws_bytes, void* stream);
+int effq_seg_surface(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                     float thresh, long long* counts, double* sums, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

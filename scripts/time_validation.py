@@ -7,7 +7,11 @@ Infinity Cache) and validate_seg over three such cases with and without save_dir
 calibrated net's own stitched logits and on random logits (masks of density 0.5: one giant component with holes), with
 validate_seg per case with and without lesions=True, and - where scipy is importable - the reference's way on the same
 masks (device -> host copy + ndimage.label of the label mask and the predicted mask of each class).  The time per phase
-is read from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- python scripts/time_validation.py --is-cc)."""
+is read from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- python scripts/time_validation.py --is-cc).
+--surf-dist adds effq_seg_surface (the surface distances hd, hd95, assd: an exact distance transform of the 2 x 3
+surfaces of the case) in the same way: on the net's own logits and on random logits, validate_seg per case with and
+without surface=True, and with scipy the host way on the same masks (copy + two binary erosions and two
+distance_transform_edt per class)."""
 import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,6 +21,7 @@ from efficientq_amd.hip_ops import from_ndhwc, get_ops
 ap = argparse.ArgumentParser()
 ap.add_argument("--save-nii", dest="save_nii", action="store_true", help="also time the NIfTI label maps")
 ap.add_argument("--is-cc", dest="is_cc", action="store_true", help="also time the lesion-level counts")
+ap.add_argument("--surf-dist", dest="surf_dist", action="store_true", help="also time the surface distances")
 cli = ap.parse_args()
 REPS = int(os.environ.get("REPS", "5"))
 HBM_PEAK = 8.0e12
@@ -167,4 +172,62 @@ if cli.is_cc:
             ms.append((time.perf_counter() - t0) * 1e3)
         res["scipy_label_ms"] = round(sorted(ms)[1], 1)
         res["scipy_over_kernel"] = round(res["scipy_label_ms"] / res["lesions"]["ms"], 1)
+if cli.surf_dist:
+    with torch.no_grad():
+        out = E._last_head(model(from_ndhwc(win)))
+    net_logits = ops.window_stitch(out.permute(0, 2, 3, 4, 1).contiguous(), (1, 3) + shape, p, o)
+    planes = 6
+    # algorithmic bytes: logits and label read, 2 B of decision bits written and read, 2 B of surface bits written and
+    # read by the rows (once per plane) and the histogram; 4 B of squared distance per plane written by the rows, read
+    # and written by each of the two line passes; the histogram's reads of the maps are left out (surface voxels only)
+    nbytes = vox * (3 * 5 + 2 * 2 + 2 * 2) + planes * vox * (2 + 4 * 5)
+    for key, lg in (("surface", net_logits), ("surface_random_logits", stitched)):
+        ms = timed(lambda: ops.seg_surface(lg[0], lab8, "brats", "agg"))
+        cnt, sm = ops.seg_surface(lg[0], lab8, "brats", "agg")
+        res[key] = {"ms": round(ms, 4), "bytes": int(nbytes), "hbm_frac": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3),
+                    "counts": cnt.tolist(), "metrics": E.surface_metrics(cnt, sm, shape).tolist()}
+    res["surf_ws_MB"] = round(ops.lib.effq_surf_ws_bytes(planes, *shape) / 1e6, 1)
+
+    def wall_sd(surface):
+        ms = []
+        for i in range(6):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            E.validate_seg(model, loader * 3, "brats", p, o, window_batch=nwin, fuse="agg", surface=surface)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3 / 3)
+        return round(sorted(ms[1:])[2], 2)
+    res["validate_ms_per_case"] = wall_sd(False)
+    res["validate_surface_ms_per_case"] = wall_sd(True)
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    res["scipy"] = ndimage is not None
+    if ndimage is not None:
+        import numpy as np
+        pred = ops.seg_labels(net_logits, "planes", "agg")[0]
+        six = ndimage.generate_binary_structure(3, 1)
+
+        def host_way():
+            pm, gm = pred.cpu().numpy() != 0, lab8.cpu().numpy() != 0
+            out = []
+            for c in range(3):
+                sp, sl = pm[c] & ~ndimage.binary_erosion(pm[c], six), gm[c] & ~ndimage.binary_erosion(gm[c], six)
+                if not sp.any() or not sl.any():
+                    out.append(None)
+                    continue
+                dpl, dlp = ndimage.distance_transform_edt(~sl)[sp], ndimage.distance_transform_edt(~sp)[sl]
+                pooled = np.hstack([dpl, dlp])
+                out.append((pooled.max(), np.percentile(pooled, 95), (dpl.mean() + dlp.mean()) / 2))
+            return out
+        ms = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host = host_way()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        res["scipy_surface_ms"] = round(min(ms), 1)
+        res["scipy_metrics"] = [None if h is None else [float(v) for v in h] for h in host]
+        res["scipy_over_kernel"] = round(res["scipy_surface_ms"] / res["surface"]["ms"], 1)
 print(json.dumps(res))
