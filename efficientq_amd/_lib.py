@@ -193,6 +193,9 @@ SIGNATURES = {
     "effq_surf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_edt_sq": (_I, [_P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_seg_surface": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
+    "effq_surf_mm_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "effq_edt_sq_mm": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _SZ, _P]),
+    "effq_seg_surface_mm": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -206,6 +209,8 @@ SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}
 LESION_CONNECTIVITY = 26
 # include/effq_hip.h: the longest line of the h and d passes of the distance transform
 EDT_MAX_LINE = 16382
+# include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)
+EDT_MM_MAX_EXTENT = 4096
 
 _lib = None
 

@@ -3,7 +3,7 @@
 // it is integer arithmetic, so the squared distance map is exact by construction:
 //
 //   masks    (effq_seg_surface only) decide<MODE, C> of every voxel -> 16 decision bits per voxel (seg_masks.h)
-//   surface  (effq_seg_surface only) a 6-neighbour stencil on the bits of all 2 C masks at once: a voxel of a mask is a
+//   surface  (effq_seg_surface only, seg_surf.h) a 6-neighbour stencil on the bits of all 2 C masks at once: a voxel of a mask is a
 //            surface voxel when a face neighbour is background or lies outside the volume
 //   rows     along w, one wave per row: the squared distance to the nearest site of the row, from the ballots of the
 //            row's chunks of 64 (a sweep from the right records the next site after every chunk, a sweep from the left
@@ -22,6 +22,7 @@
 #include "common.h"
 #include "seg_decide.h"
 #include "seg_masks.h"
+#include "seg_surf.h"
 
 namespace effq {
 
@@ -29,23 +30,10 @@ constexpr int EDT_INF = INT32_MAX;
 constexpr int EDT_THREADS = 256;
 constexpr int EDT_ROWS = EDT_THREADS / 64;             // rows of one workgroup of the w pass: one per wave
 constexpr int EDT_MAX_CHUNKS = 728;                    // chunks of 64 of the longest row (W^2 < 2^31: W <= 46340)
-constexpr int EDT_LDS_AIM = 32 * 1024;                 // slab of the line passes: narrowed down to this, ...
-constexpr int EDT_LDS_MAX = 64 * 1024;                 // ... a single line may take this
+constexpr int EDT_LDS_MAX = 64 * 1024;                 // the slab is narrowed down to EDT_LDS_AIM (seg_surf.h); a single line may take this
 constexpr int SURF_LOW = 256;                          // squared distances below this are counted in LDS first
 constexpr int SURF_FINAL_THREADS = 1024;
 static_assert(EFFQ_EDT_MAX_LINE == EDT_LDS_MAX / 4 - 2, "one line and its range fit the LDS of a workgroup");
-
-// where the sites of plane q come from: P masks of uint8, or bit cc_plane_bit(q, C) of the surface bits
-struct EdtSrc {
-  const uint8_t* masks;
-  const uint16_t* surf;
-  int C;
-};
-
-__device__ __forceinline__ bool edt_site(const EdtSrc& s, int plane, int S, int idx) {
-  if (s.surf) return (s.surf[idx] >> cc_plane_bit(plane, s.C)) & 1;
-  return s.masks[(size_t)plane * S + idx] != 0;
-}
 
 static inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
@@ -74,28 +62,6 @@ static SurfWs surf_ws(void* ws, int P, int D, int H, int W) {
   r.hist = reinterpret_cast<uint32_t*>(p + off); off += align16(r.hist_bytes);
   r.bytes = off;
   return r;
-}
-
-// ---- surface --------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CC_THREADS) void k_surf_bits(const uint16_t* __restrict__ bits,
-                                                          uint16_t* __restrict__ surf, int D, int H, int W) {
-  const int S = D * H * W, HW = H * W;
-  for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * CC_THREADS) {
-    const int v = (int)i;
-    const uint32_t b = bits[v];
-    uint32_t inner = 0;
-    if (b) {
-      const int w = v % W, q = v / W, h = q % H, d = q / H;
-      inner = b;
-      inner &= w > 0 ? bits[v - 1] : 0u;
-      inner &= w < W - 1 ? bits[v + 1] : 0u;
-      inner &= h > 0 ? bits[v - W] : 0u;
-      inner &= h < H - 1 ? bits[v + W] : 0u;
-      inner &= d > 0 ? bits[v - HW] : 0u;
-      inner &= d < D - 1 ? bits[v + HW] : 0u;
-    }
-    surf[v] = (uint16_t)(b & ~inner);
-  }
 }
 
 // ---- rows -----------------------------------------------------------------------------------------------------------

@@ -1,0 +1,478 @@
+// The distance transform with per-axis weights and the surface distances in millimetres (effq_edt_sq_mm,
+// effq_seg_surface_mm).  The contract - E(v, s) defined in fp32 term by term, the outputs - is in include/effq_hip.h; why
+// the separable passes return the bits of the brute force, how the two pooled ranks are selected and what was measured is
+// in DESIGN section 13 ("Source geometry").  Phases of a call, in launch order:
+//   masks, surface   the decision bits (seg_masks.h) and the 6-neighbour stencil (seg_surf.h), as effq_seg_surface
+//   rows             k_mm_rows: along w, one wave per row, ballots; writes fl(ww dw^2)
+//   lines            k_mm_lines along h, then d: min_j fl(g(j) + fl(wa (i - j)^2)), a slab of lines in LDS, in place
+//   reduce           k_mm_scan, then k_mm_select / k_mm_hist over 8 + 8 + 8 + 8 bits of the pattern, k_mm_next, k_mm_final
+#include <cmath>
+
+#include "common.h"
+#include "seg_decide.h"
+#include "seg_masks.h"
+#include "seg_surf.h"
+
+namespace effq {
+
+constexpr int MM_THREADS = 256;
+constexpr int MM_ROWS = MM_THREADS / 64;               // rows of one workgroup of the w pass: one per wave
+constexpr int MM_MAX_CHUNKS = EFFQ_EDT_MM_MAX_EXTENT / 64;
+constexpr int MM_SCAN_BLOCKS = 1024;                   // blocks of the scans = per-block partials of the fp64 sums
+constexpr int MM_BINS = 256;                           // 8 bits of the pattern per stage of the select
+constexpr int MM_STAGES = 4;
+constexpr int MM_CLASSES = EFFQ_SEG_TALLIES_MAX_CLASSES;
+constexpr int MM_STATE = 8;                            // uint32 per class: the fields below
+constexpr int ST_PREFIX = 0, ST_RANK = 1, ST_POOLED = 2, ST_NEXT = 3, ST_SAME = 4;
+constexpr uint32_t MM_INF_BITS = 0x7f800000u;
+static_assert(MM_CLASSES == 8, "rows of the reduce arrays");
+static_assert((EFFQ_EDT_MM_MAX_EXTENT + 2) * sizeof(float) <= (size_t)EDT_LDS_AIM, "one line and its range fit the slab");
+
+static inline size_t mm_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// the small arrays of the reduce, sized for MM_CLASSES whatever C is
+struct MmRed {
+  uint32_t* hist;                // (MM_STAGES, MM_CLASSES, MM_BINS) pooled over both directions
+  unsigned long long* cnt;       // (2 MM_CLASSES): row 2 c = nP, row 2 c + 1 = nL
+  uint32_t* mx;                  // (2 MM_CLASSES) patterns of the largest finite E
+  uint32_t* state;               // (MM_CLASSES, MM_STATE)
+  double* part;                  // (MM_SCAN_BLOCKS, 2 MM_CLASSES)
+};
+
+struct MmWs {
+  float* sq;                     // (P, S)
+  uint16_t* bits;                // (S)
+  uint16_t* surf;                // (S)
+  char* zeroed;                  // hist, cnt, mx, state: cleared by one memset
+  size_t zeroed_bytes;
+  MmRed red;
+  size_t bytes;
+};
+
+static MmWs mm_ws(void* ws, int P, int D, int H, int W) {
+  MmWs r;
+  const size_t S = (size_t)D * H * W;
+  char* p = static_cast<char*>(ws);
+  size_t off = 0;
+  r.sq = reinterpret_cast<float*>(p + off);      off += mm_align16((size_t)P * S * sizeof(float));
+  r.bits = reinterpret_cast<uint16_t*>(p + off); off += mm_align16(S * sizeof(uint16_t));
+  r.surf = reinterpret_cast<uint16_t*>(p + off); off += mm_align16(S * sizeof(uint16_t));
+  r.zeroed = p + off;
+  r.red.hist = reinterpret_cast<uint32_t*>(p + off); off += (size_t)MM_STAGES * MM_CLASSES * MM_BINS * sizeof(uint32_t);
+  r.red.cnt = reinterpret_cast<unsigned long long*>(p + off); off += 2 * MM_CLASSES * sizeof(unsigned long long);
+  r.red.mx = reinterpret_cast<uint32_t*>(p + off);    off += 2 * MM_CLASSES * sizeof(uint32_t);
+  r.red.state = reinterpret_cast<uint32_t*>(p + off); off += (size_t)MM_CLASSES * MM_STATE * sizeof(uint32_t);
+  r.zeroed_bytes = (size_t)(p + off - r.zeroed);
+  off = mm_align16(off);
+  r.red.part = reinterpret_cast<double*>(p + off); off += (size_t)MM_SCAN_BLOCKS * 2 * MM_CLASSES * sizeof(double);
+  r.bytes = off;
+  return r;
+}
+
+// ---- rows -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MM_THREADS) void k_mm_rows(EdtSrc src, float* __restrict__ sq, int S, int W, int nrows,
+                                                        float ww) {
+  __shared__ int s_next[MM_ROWS][MM_MAX_CHUNKS];       // the first site after chunk k of the wave's row, -1: none
+  const int plane = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = blockIdx.x * MM_ROWS + wave;
+  const bool live = row < nrows;
+  const int base = live ? row * W : 0;
+  const int nchunks = (W + 63) / 64;
+  int next = -1;
+  for (int k = nchunks - 1; k >= 0; --k) {
+    if (lane == 0) s_next[wave][k] = next;
+    const int w = k * 64 + lane;
+    const unsigned long long bal = __ballot(live && w < W && edt_site(src, plane, S, base + w));
+    if (bal) next = k * 64 + __builtin_ctzll(bal);
+  }
+  __syncthreads();
+  if (!live) return;
+  float* out = sq + (size_t)plane * S + base;
+  int last = -1;
+  for (int k = 0; k < nchunks; ++k) {
+    const int w = k * 64 + lane;
+    const unsigned long long bal = __ballot(w < W && edt_site(src, plane, S, base + w));
+    const unsigned long long le = bal & (~0ull >> (63 - lane)), ge = bal & (~0ull << lane);
+    const int lpos = le ? k * 64 + 63 - __builtin_clzll(le) : last;
+    const int rpos = ge ? k * 64 + __builtin_ctzll(ge) : s_next[wave][k];
+    int dist = -1;
+    if (lpos >= 0) dist = w - lpos;
+    if (rpos >= 0 && (dist < 0 || rpos - w < dist)) dist = rpos - w;
+    if (w < W) out[w] = dist < 0 ? INFINITY : ww * (float)(dist * dist);       // dist^2 < 2^24: exact as a float
+    if (bal) last = k * 64 + 63 - __builtin_clzll(bal);
+  }
+}
+
+// ---- lines ----------------------------------------------------------------------------------------------------------
+// Line (o, w) of a plane holds the n voxels o * ostride + i * stride + w, as in seg_surface.hip.  tw = 1 << ltw lines
+// adjacent along w make the slab of a workgroup; dynamic LDS: (n + 2) * tw words.
+__global__ __launch_bounds__(MM_THREADS) void k_mm_lines(float* __restrict__ sq, int S, int W, int n, int stride,
+                                                         int ostride, int ltw, int ntw, float wa) {
+  extern __shared__ float s_g[];
+  const int tw = 1 << ltw, rows = MM_THREADS >> ltw;
+  int* s_lo = reinterpret_cast<int*>(s_g + n * tw);
+  int* s_hi = s_lo + tw;
+  const int lw = threadIdx.x & (tw - 1), r = threadIdx.x >> ltw;
+  const int o = blockIdx.x / ntw, w = (blockIdx.x % ntw) * tw + lw;
+  const bool live = w < W;
+  float* line = sq + (size_t)blockIdx.y * S + (size_t)o * ostride + (live ? w : 0);
+  if (threadIdx.x < tw) {
+    s_lo[threadIdx.x] = n;
+    s_hi[threadIdx.x] = -1;
+  }
+  __syncthreads();
+  int lo = n, hi = -1;
+  for (int i = r; i < n; i += rows) {
+    const float g = live ? line[(size_t)i * stride] : INFINITY;
+    s_g[i * tw + lw] = g;
+    if (g < INFINITY) {
+      lo = min(lo, i);
+      hi = i;
+    }
+  }
+  if (hi >= 0) {
+    atomicMin(&s_lo[lw], lo);
+    atomicMax(&s_hi[lw], hi);
+  }
+  __syncthreads();
+  lo = s_lo[lw];
+  hi = s_hi[lw];
+  if (!live || hi < 0) return;                         // a line without a finite entry stays as it is
+  for (int i = r; i < n; i += rows) {
+    float best = s_g[i * tw + lw];
+    for (int j = min(i - 1, hi); j >= lo; --j) {
+      const float c = wa * (float)((i - j) * (i - j));
+      if (c >= best) break;
+      const float cand = s_g[j * tw + lw] + c;
+      best = cand < best ? cand : best;
+    }
+    for (int j = max(i + 1, lo); j <= hi; ++j) {
+      const float c = wa * (float)((j - i) * (j - i));
+      if (c >= best) break;
+      const float cand = s_g[j * tw + lw] + c;
+      best = cand < best ? cand : best;
+    }
+    line[(size_t)i * stride] = best;
+  }
+}
+
+// ---- reduce ---------------------------------------------------------------------------------------------------------
+// The pattern of E at surface voxel i of row 2 c + dir: dir 0 = E_L over S(P) of class c, dir 1 = E_P over S(L).
+__device__ __forceinline__ uint32_t mm_value(const float* __restrict__ sq, int C, size_t S, int c, int dir, size_t i) {
+  return __float_as_uint(sq[(size_t)(dir ? c : C + c) * S + i]);
+}
+
+template <int C>
+__global__ __launch_bounds__(MM_THREADS) void k_mm_scan(const uint16_t* __restrict__ surf, const float* __restrict__ sq,
+                                                        int S, MmRed r) {
+  constexpr int R = 2 * C;
+  __shared__ uint32_t s_hist[C * MM_BINS];
+  __shared__ double s_sum[MM_ROWS][R];
+  __shared__ uint32_t s_cnt[MM_ROWS][R], s_max[MM_ROWS][R];
+  for (int k = threadIdx.x; k < C * MM_BINS; k += MM_THREADS) s_hist[k] = 0;
+  __syncthreads();
+  double sum[R];
+  uint32_t cnt[R], mx[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    sum[k] = 0.0;
+    cnt[k] = mx[k] = 0;
+  }
+  for (long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * MM_THREADS) {
+    const uint32_t b = surf[i];
+    if (!b) continue;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+#pragma unroll
+      for (int dir = 0; dir < 2; ++dir) {
+        if (!((b >> (dir ? 8 + c : c)) & 1)) continue;
+        const uint32_t e = mm_value(sq, C, (size_t)S, c, dir, (size_t)i);
+        ++cnt[2 * c + dir];
+        atomicAdd(&s_hist[c * MM_BINS + (e >> 24)], 1u);
+        if (e != MM_INF_BITS) {                        // +inf: the target has no surface
+          mx[2 * c + dir] = max(mx[2 * c + dir], e);
+          sum[2 * c + dir] += sqrt((double)__uint_as_float(e));
+        }
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      sum[k] += __shfl_down(sum[k], off);
+      cnt[k] += __shfl_down(cnt[k], off);
+      mx[k] = max(mx[k], __shfl_down(mx[k], off));
+    }
+    if (lane == 0) {
+      s_sum[wave][k] = sum[k];
+      s_cnt[wave][k] = cnt[k];
+      s_max[wave][k] = mx[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < R) {
+    const int k = threadIdx.x;
+    double s = 0.0;
+    unsigned long long n = 0;
+    uint32_t m = 0;
+    for (int v = 0; v < MM_ROWS; ++v) {
+      s += s_sum[v][k];
+      n += s_cnt[v][k];
+      m = max(m, s_max[v][k]);
+    }
+    r.part[(size_t)blockIdx.x * 2 * MM_CLASSES + k] = s;
+    if (n) atomicAdd(&r.cnt[k], n);
+    if (m) atomicMax(&r.mx[k], m);
+  }
+  for (int k = threadIdx.x; k < C * MM_BINS; k += MM_THREADS)
+    if (s_hist[k]) atomicAdd(&r.hist[k], s_hist[k]);   // stage 0: (c, bin) = k
+}
+
+// One workgroup per class, one thread per bin of stage `stage`: the bin that holds the rank still sought extends the
+// prefix by 8 bits.  Stage 0 first places the rank from the counts.
+__global__ __launch_bounds__(MM_BINS) void k_mm_select(MmRed r, int stage) {
+  __shared__ uint32_t s_scan[MM_BINS];
+  __shared__ uint32_t s_rank, s_go;
+  const int c = blockIdx.x, t = threadIdx.x;
+  uint32_t* st = r.state + c * MM_STATE;
+  if (t == 0) {
+    if (stage == 0) {
+      const unsigned long long n_p = r.cnt[2 * c], n_l = r.cnt[2 * c + 1];
+      const bool pooled = n_p > 0 && n_l > 0;
+      st[ST_PREFIX] = 0;
+      st[ST_RANK] = pooled ? (uint32_t)(95ull * (n_p + n_l - 1) / 100ull) : 0u;
+      st[ST_POOLED] = pooled;
+      st[ST_NEXT] = 0xFFFFFFFFu;
+      st[ST_SAME] = 0;
+    }
+    s_rank = st[ST_RANK];
+    s_go = st[ST_POOLED];
+  }
+  __syncthreads();
+  if (!s_go) return;
+  const uint32_t k = r.hist[((size_t)stage * MM_CLASSES + c) * MM_BINS + t];
+  s_scan[t] = k;
+  __syncthreads();
+  for (int off = 1; off < MM_BINS; off <<= 1) {
+    const uint32_t v = t >= off ? s_scan[t - off] : 0u;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  const uint32_t incl = s_scan[t], excl = incl - k, rank = s_rank;
+  if (excl <= rank && rank < incl) {                   // one thread
+    st[ST_PREFIX] |= (uint32_t)t << (24 - 8 * stage);
+    st[ST_RANK] = rank - excl;
+    if (stage == MM_STAGES - 1) st[ST_SAME] = rank - excl + 1 < k;       // rank lo + 1 holds the same value
+  }
+}
+
+// stage 1..3: the values whose leading 8 * stage bits equal the prefix, counted by their next 8 bits
+__global__ __launch_bounds__(MM_THREADS) void k_mm_hist(const uint16_t* __restrict__ surf, const float* __restrict__ sq,
+                                                        int C, int S, MmRed r, int stage) {
+  __shared__ uint32_t s_hist[MM_CLASSES * MM_BINS];
+  __shared__ uint32_t s_pref[MM_CLASSES], s_on[MM_CLASSES];
+  if (threadIdx.x < MM_CLASSES) {
+    const bool on = threadIdx.x < C && r.state[threadIdx.x * MM_STATE + ST_POOLED];
+    s_on[threadIdx.x] = on;
+    s_pref[threadIdx.x] = on ? r.state[threadIdx.x * MM_STATE + ST_PREFIX] : 0u;
+  }
+  for (int k = threadIdx.x; k < C * MM_BINS; k += MM_THREADS) s_hist[k] = 0;
+  __syncthreads();
+  const int shift = 32 - 8 * stage;
+  for (long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * MM_THREADS) {
+    const uint32_t b = surf[i];
+    if (!b) continue;
+    for (int c = 0; c < C; ++c) {
+      if (!s_on[c]) continue;
+#pragma unroll
+      for (int dir = 0; dir < 2; ++dir) {
+        if (!((b >> (dir ? 8 + c : c)) & 1)) continue;
+        const uint32_t e = mm_value(sq, C, (size_t)S, c, dir, (size_t)i);
+        if ((e >> shift) == (s_pref[c] >> shift)) atomicAdd(&s_hist[c * MM_BINS + ((e >> (shift - 8)) & 255u)], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < C * MM_BINS; k += MM_THREADS)
+    if (s_hist[k]) atomicAdd(&r.hist[(size_t)stage * MM_CLASSES * MM_BINS + k], s_hist[k]);
+}
+
+// the smallest pattern above the value of rank lo, for the classes whose rank lo + 1 is not that value again
+__global__ __launch_bounds__(MM_THREADS) void k_mm_next(const uint16_t* __restrict__ surf, const float* __restrict__ sq,
+                                                        int C, int S, MmRed r) {
+  __shared__ uint32_t s_min[MM_CLASSES], s_lo[MM_CLASSES], s_on[MM_CLASSES], s_any;
+  if (threadIdx.x == 0) s_any = 0;
+  __syncthreads();
+  if (threadIdx.x < MM_CLASSES) {
+    const uint32_t* st = r.state + threadIdx.x * MM_STATE;
+    const bool on = threadIdx.x < C && st[ST_POOLED] && !st[ST_SAME];
+    s_on[threadIdx.x] = on;
+    s_lo[threadIdx.x] = on ? st[ST_PREFIX] : 0u;
+    s_min[threadIdx.x] = 0xFFFFFFFFu;
+    if (on) s_any = 1;
+  }
+  __syncthreads();
+  if (!s_any) return;
+  for (long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * MM_THREADS) {
+    const uint32_t b = surf[i];
+    if (!b) continue;
+    for (int c = 0; c < C; ++c) {
+      if (!s_on[c]) continue;
+#pragma unroll
+      for (int dir = 0; dir < 2; ++dir) {
+        if (!((b >> (dir ? 8 + c : c)) & 1)) continue;
+        const uint32_t e = mm_value(sq, C, (size_t)S, c, dir, (size_t)i);
+        if (e > s_lo[c] && e < s_min[c]) atomicMin(&s_min[c], e);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < C && s_min[threadIdx.x] != 0xFFFFFFFFu)
+    atomicMin(&r.state[threadIdx.x * MM_STATE + ST_NEXT], s_min[threadIdx.x]);
+}
+
+// One workgroup per class: the per-block partials of both sums added in block order (thread t takes blocks t, t + 256,
+// ..., then a fixed tree), and the outputs written.
+__global__ __launch_bounds__(MM_THREADS) void k_mm_final(MmRed r, int nblocks, long long* __restrict__ counts,
+                                                         float* __restrict__ sq_out, double* __restrict__ sums) {
+  __shared__ double s_red[MM_THREADS];
+  const int c = blockIdx.x, t = threadIdx.x;
+  for (int dir = 0; dir < 2; ++dir) {
+    const int row = 2 * c + dir;
+    double s = 0.0;
+    for (int b = t; b < nblocks; b += MM_THREADS) s += r.part[(size_t)b * 2 * MM_CLASSES + row];
+    s_red[t] = s;
+    __syncthreads();
+    for (int off = MM_THREADS / 2; off > 0; off >>= 1) {
+      if (t < off) s_red[t] += s_red[t + off];
+      __syncthreads();
+    }
+    if (t == 0) {
+      sums[row] = s_red[0];
+      counts[row] = (long long)r.cnt[row];
+      sq_out[4 * c + dir] = __uint_as_float(r.mx[row]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const uint32_t* st = r.state + c * MM_STATE;
+    const bool pooled = st[ST_POOLED];
+    sq_out[4 * c + 2] = pooled ? __uint_as_float(st[ST_PREFIX]) : 0.0f;
+    sq_out[4 * c + 3] = pooled ? __uint_as_float(st[ST_SAME] ? st[ST_PREFIX] : st[ST_NEXT]) : 0.0f;
+  }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+static bool mm_dims_ok(int P, int D, int H, int W) {
+  return P > 0 && P <= 65535 && D > 0 && H > 0 && W > 0 && D <= EFFQ_EDT_MM_MAX_EXTENT && H <= EFFQ_EDT_MM_MAX_EXTENT &&
+         W <= EFFQ_EDT_MM_MAX_EXTENT && (long long)P * D * H * W < (1ll << 31);
+}
+
+static bool mm_weight_ok(float w) { return std::isfinite(w) && w > 0.0f; }
+
+static int mm_line_pass(float* sq, int P, int S, int W, int n, int stride, int nouter, int ostride, float wa,
+                        hipStream_t st) {
+  if (n == 1) return EFFQ_OK;                          // min over one entry: fl(g + 0) = g
+  int ltw = 6;
+  while (ltw > 0 && (size_t)(n + 2) * sizeof(float) << ltw > (size_t)EDT_LDS_AIM) --ltw;
+  const int tw = 1 << ltw, ntw = (W + tw - 1) / tw;
+  const size_t lds = (size_t)(n + 2) * sizeof(float) << ltw;
+  hipLaunchKernelGGL(k_mm_lines, dim3((unsigned)((size_t)nouter * ntw), P), dim3(MM_THREADS), lds, st, sq, S, W, n,
+                     stride, ostride, ltw, ntw, wa);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+// the three passes of P planes into sq (P, S): w, then h, then d
+static int mm_run(const EdtSrc& src, int P, int D, int H, int W, float wd, float wh, float ww, float* sq,
+                  hipStream_t st) {
+  const int S = D * H * W, nrows = D * H;
+  hipLaunchKernelGGL(k_mm_rows, dim3((nrows + MM_ROWS - 1) / MM_ROWS, P), dim3(MM_THREADS), 0, st, src, sq, S, W, nrows,
+                     ww);
+  EFFQ_LAUNCH_CHECK();
+  const int rc = mm_line_pass(sq, P, S, W, H, W, D, H * W, wh, st);
+  if (rc != EFFQ_OK) return rc;
+  return mm_line_pass(sq, P, S, W, D, H * W, H, W, wd, st);
+}
+
+template <int C>
+static void launch_scan(dim3 g, hipStream_t st, const uint16_t* surf, const float* sq, int S, const MmRed& r) {
+  hipLaunchKernelGGL((k_mm_scan<C>), g, dim3(MM_THREADS), 0, st, surf, sq, S, r);
+}
+
+}  // namespace effq
+using namespace effq;
+
+extern "C" {
+
+size_t effq_surf_mm_ws_bytes(int P, int D, int H, int W) {
+  if (!mm_dims_ok(P, D, H, W)) return 0;
+  return mm_ws(nullptr, P, D, H, W).bytes;
+}
+
+int effq_edt_sq_mm(const uint8_t* masks, int P, int D, int H, int W, float wd, float wh, float ww, float* sq, void* ws,
+                   size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(masks && sq && ws);
+  EFFQ_CHECK_ARG(mm_dims_ok(P, D, H, W));
+  EFFQ_CHECK_ARG(mm_weight_ok(wd) && mm_weight_ok(wh) && mm_weight_ok(ww));
+  EFFQ_CHECK_ARG(ws_bytes >= mm_ws(ws, P, D, H, W).bytes);
+  EdtSrc src;
+  src.masks = masks; src.surf = nullptr; src.C = 0;
+  return mm_run(src, P, D, H, W, wd, wh, ww, sq, as_stream(stream));
+}
+
+int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                        float thresh, float wd, float wh, float ww, long long* counts, float* sq, double* sums, void* ws,
+                        size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(logits && label && counts && sq && sums && ws && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
+  EFFQ_CHECK_ARG(mm_dims_ok(2 * C, D, H, W));
+  EFFQ_CHECK_ARG(mode == EFFQ_SEG_ARGMAX || mode == EFFQ_SEG_SIGMOID);
+  EFFQ_CHECK_ARG(fuse == EFFQ_SEG_FUSE_NONE || fuse == EFFQ_SEG_FUSE_AGG || fuse == EFFQ_SEG_FUSE_CON);
+  EFFQ_CHECK_ARG(mm_weight_ok(wd) && mm_weight_ok(wh) && mm_weight_ok(ww));
+  const int P = 2 * C;
+  const size_t S = (size_t)D * H * W;
+  const MmWs s = mm_ws(ws, P, D, H, W);
+  EFFQ_CHECK_ARG(ws_bytes >= s.bytes);
+  const hipStream_t st = as_stream(stream);
+  EFFQ_HIP(hipMemsetAsync(s.zeroed, 0, s.zeroed_bytes, st));
+  int rc = cc_decision_bits(logits, label, C, S, mode, fuse, thresh, s.bits, st);
+  if (rc != EFFQ_OK) return rc;
+  const dim3 gs(cc_grid(S, CC_STREAM_BLOCKS)), b(CC_THREADS);
+  hipLaunchKernelGGL(k_surf_bits, gs, b, 0, st, s.bits, s.surf, D, H, W);
+  EFFQ_LAUNCH_CHECK();
+  EdtSrc src;
+  src.masks = nullptr; src.surf = s.surf; src.C = C;
+  rc = mm_run(src, P, D, H, W, wd, wh, ww, s.sq, st);
+  if (rc != EFFQ_OK) return rc;
+  const dim3 g(cc_grid(S, MM_SCAN_BLOCKS)), t(MM_THREADS);
+  switch (C) {
+    case 1: launch_scan<1>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 2: launch_scan<2>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 3: launch_scan<3>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 4: launch_scan<4>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 5: launch_scan<5>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 6: launch_scan<6>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 7: launch_scan<7>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    default: launch_scan<8>(g, st, s.surf, s.sq, (int)S, s.red); break;
+  }
+  EFFQ_LAUNCH_CHECK();
+  for (int stage = 0; stage < MM_STAGES; ++stage) {
+    if (stage > 0) {
+      hipLaunchKernelGGL(k_mm_hist, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red, stage);
+      EFFQ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_mm_select, dim3(C), dim3(MM_BINS), 0, st, s.red, stage);
+    EFFQ_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_mm_next, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red);
+  EFFQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mm_final, dim3(C), t, 0, st, s.red, (int)g.x, counts, sq, sums);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+}  // extern "C"

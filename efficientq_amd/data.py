@@ -4,6 +4,11 @@ src/definer.py:get_data_cube):
     data_dir/<modality>/<subject>.npy      (--access_type npy; .npz holds the array under the key arr_0)
     split_dir/round<R>/train.txt, val.txt  (one subject per line)
 
+With ``--src_geom`` two more files of the reference's layout are read (datahub.py:51, definer.py:113-123):
+
+    data_dir/sn_fn.txt                      ``subject,path`` per line: the subject's source NIfTI image
+    data_dir/restore_shape_infokw.pickle    optional: {subject: {pmin, pmax, shape}}, how the arrays were cropped
+
 Modalities are flair, t1, t1ce, t2 for brats and ct for lits; the label is the modality ``seg``.  Subjects are
 taken in sorted order, as the reference's Dataset_SEG loads them.  Images are used as stored: the reference's README
 asks for volumes already standardised to zero mean and unit variance, and no augmentation or random crop is applied.
@@ -13,7 +18,10 @@ subject names ``train_sn`` / ``val_sn``.
 """
 from __future__ import annotations
 
+import math
 import os.path as P
+import pickle
+from zlib import error as zlib_error
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -42,6 +50,95 @@ def load_array(data_dir: str, modality: str, subject: str, access_type: str, dty
     else:
         raise RuntimeError(f"Unknown access type {access_type} (one of {', '.join(ACCESS_TYPES)})")
     return a.astype(dtype, copy=False)
+
+
+# ---- source geometry (--src_geom, --spacing) --------------------------------------------------------------------------
+SN_FN_FILE = "sn_fn.txt"
+RESTORE_FILE = "restore_shape_infokw.pickle"
+
+
+def read_sn_fn(data_dir: str) -> dict:
+    """{subject: path of its source NIfTI image} from data_dir/sn_fn.txt, ``subject,path`` per line (the reference's
+    file_to_dict); a relative path is taken relative to `data_dir`.  Blank lines are ignored."""
+    out = {}
+    with open(P.join(data_dir, SN_FN_FILE), "r") as f:
+        for line in f.read().splitlines():
+            if not line.strip():
+                continue
+            if line.count(",") != 1:
+                raise RuntimeError(f"{SN_FN_FILE}: line {line!r} is not `subject,path`")
+            sn, path = (s.strip() for s in line.split(","))
+            out[sn] = path if P.isabs(path) else P.join(data_dir, path)
+    return out
+
+
+def read_restore_info(data_dir: str) -> Optional[dict]:
+    """{subject: {pmin, pmax, shape}} - the keyword arguments of restore_crop - from
+    data_dir/restore_shape_infokw.pickle, or None when the file does not exist.  Unpickling runs code: this is called
+    under --src_geom only, on the user's own data_dir."""
+    path = P.join(data_dir, RESTORE_FILE)
+    if not P.isfile(path):
+        return None
+    with open(path, "rb") as f:
+        return pickle.load(f)
+
+
+def restore_crop(crop: np.ndarray, pmin, pmax, shape) -> np.ndarray:
+    """`crop` put back into a volume of zeros of extent `shape` at pmin:pmax (misc.restore_crop for three axes)."""
+    out = np.zeros(tuple(int(n) for n in shape), dtype=crop.dtype)
+    out[pmin[0]:pmax[0], pmin[1]:pmax[1], pmin[2]:pmax[2]] = crop
+    return out
+
+
+def array_shape(data_dir: str, modality: str, subject: str, access_type: str) -> tuple:
+    if access_type == "npy":
+        return tuple(np.load(P.join(data_dir, modality, f"{subject}.npy"), mmap_mode="r").shape)
+    return tuple(load_array(data_dir, modality, subject, access_type, np.uint8).shape)
+
+
+def read_source_geometry(data_dir: str, subjects: Sequence[str], access_type: str = "npy") -> List[dict]:
+    """One entry per subject for --src_geom: `affine`, `spacing`, `source_shape` and `header` (nifti.read_geometry of the
+    image sn_fn.txt names) and, when the subject's array is a crop of it, `pmin` / `pmax`.  Every failure names the
+    subject."""
+    from .nifti import read_geometry
+    if not P.isfile(P.join(data_dir, SN_FN_FILE)):
+        raise RuntimeError(f"--src_geom: {P.join(data_dir, SN_FN_FILE)} is missing (needed for {', '.join(subjects)})")
+    sn_fn = read_sn_fn(data_dir)
+    restore = read_restore_info(data_dir) or {}
+    out = []
+    for sn in subjects:
+        if sn not in sn_fn:
+            raise RuntimeError(f"--src_geom: subject {sn} has no line in {SN_FN_FILE}")
+        try:
+            hdr = read_geometry(sn_fn[sn])
+        except (OSError, ValueError, EOFError, zlib_error) as e:
+            raise RuntimeError(f"--src_geom: subject {sn}: cannot read the geometry of {sn_fn[sn]}: {e}") from e
+        src = tuple(hdr["shape"][:3])
+        entry = {"affine": hdr["affine"], "spacing": hdr["spacing"], "source_shape": src, "header": hdr}
+        have = array_shape(data_dir, LABEL_MODALITY, sn, access_type)
+        if have != src:
+            kw = restore.get(sn)
+            ok = kw is not None and tuple(int(n) for n in kw["shape"]) == src and \
+                tuple(int(b) - int(a) for a, b in zip(kw["pmin"], kw["pmax"])) == have
+            if not ok:
+                raise RuntimeError(f"--src_geom: subject {sn}: array of shape {have}, source image of shape {src}"
+                                   + (f", restore entry pmin {tuple(kw['pmin'])} pmax {tuple(kw['pmax'])} shape "
+                                      f"{tuple(kw['shape'])}" if kw is not None else f", no entry in {RESTORE_FILE}"))
+            entry["pmin"] = tuple(int(v) for v in kw["pmin"])
+            entry["pmax"] = tuple(int(v) for v in kw["pmax"])
+        out.append(entry)
+    return out
+
+
+def parse_spacing(s) -> tuple:
+    """--spacing d,h,w: three finite positive numbers (millimetres per voxel along D, H, W)."""
+    try:
+        v = tuple(float(x) for x in (s.split(",") if isinstance(s, str) else s))
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 3 or not all(math.isfinite(x) and x > 0 for x in v):
+        raise RuntimeError(f"--spacing {s!r}: needs three finite positive numbers d,h,w")
+    return v
 
 
 # ---- label transforms (definer.py: --bin_label / --multi_label; misc.split_label_*) -----------------------------------
@@ -103,7 +200,7 @@ class SegVolumes(torch.utils.data.Dataset):
 
 class DataCube:
     def __init__(self, data_dir, split_dir, round_, task, access_type="npy", bin_label=None, multi_label=None,
-                 merge_type=None, patch_size=None):
+                 merge_type=None, patch_size=None, src_geom=False, spacing=None):
         task = task.lower()
         if task not in MODALITIES:
             raise RuntimeError(f"Unknown task: {task}")
@@ -118,6 +215,14 @@ class DataCube:
         self.multilabel_fusetype = merge_type
         self.patch_size = parse_patch(patch_size) if patch_size else PATCH_DEFAULT[task]
         self.overlap = OVERLAP_DEFAULT
+        # where the val subjects lie in space: one entry per subject (--src_geom), or one spacing for all (--spacing)
+        self.geometry = self.spacing = None
+        if src_geom and spacing:
+            raise RuntimeError("--src_geom and --spacing exclude each other: the source images carry their own spacing")
+        if src_geom:
+            self.geometry = read_source_geometry(data_dir, self.val_sn, access_type)
+        elif spacing:
+            self.spacing = parse_spacing(spacing)
 
 
 def parse_patch(s) -> tuple:
@@ -129,7 +234,8 @@ def parse_patch(s) -> tuple:
 
 def get_data_cube(args) -> DataCube:
     """The data cube of `args` (--data_dir, --split_dir, --round, --task, --access_type, --bin_label, --multi_label,
-    --merge_type, --patch_size)."""
+    --merge_type, --patch_size, --src_geom, --spacing)."""
     return DataCube(args.data_dir, args.split_dir, args.round, args.task, getattr(args, "access_type", "npy"),
                     getattr(args, "bin_label", None), getattr(args, "multi_label", None),
-                    getattr(args, "merge_type", None), getattr(args, "patch_size", None))
+                    getattr(args, "merge_type", None), getattr(args, "patch_size", None),
+                    getattr(args, "src_geom", False), getattr(args, "spacing", None))

@@ -9,7 +9,10 @@ calibration takes the train split, and ``--test_fp`` / the default test (unless 
 the calibrated network on the val split (evaluate.validate_seg), writing ``<snap>/{fp,ptq}/metrics.csv``;
 ``--save_nii`` adds the predicted label maps ``<snap>/{fp,ptq}/val/<subject>.nii.gz`` and ``<snap>/{Q,FP}seg<i>.nii.gz``;
 ``--is_cc`` adds the lesion-level columns ``totall, predl, fnl, fpl`` (connected components) to ``metrics.csv``;
-``--surf_dist`` adds the surface distances ``hd, hd95, assd`` (voxel units) after them.
+``--surf_dist`` adds the surface distances ``hd, hd95, assd`` (voxel units) after them;
+``--src_geom`` reads every val subject's source image header (``data_dir/sn_fn.txt``, data.py): the distances become
+``hd_mm, hd95_mm, assd_mm`` in millimetres and the val maps are written on the source grid with the source's geometry;
+``--spacing d,h,w`` gives the distances in millimetres from one spacing for all subjects, without any file.
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
 the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
@@ -59,6 +62,17 @@ class _ValidationTester(_SnapshotWriter):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
 
+    def _geometry(self, is_save_nii, is_surf):
+        """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances
+        and maps), or the one spacing of --spacing (distances only)."""
+        geom = getattr(self.cube, 'geometry', None)
+        if geom is not None and (is_save_nii or is_surf):
+            return {'geometry': geom}
+        spacing = getattr(self.cube, 'spacing', None)
+        if spacing is not None and is_surf:
+            return {'geometry': spacing}
+        return {}
+
     def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False):
         if self.rank != 0:
             return
@@ -71,7 +85,7 @@ class _ValidationTester(_SnapshotWriter):
                              fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
                              save_dir=os.path.join(out, 'val') if is_save_nii else None,
                              multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
-                             surface=is_surf)
+                             surface=is_surf, **self._geometry(is_save_nii, is_surf))
         os.makedirs(out, exist_ok=True)
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         means = E.metric_means(res)
@@ -83,7 +97,8 @@ class _ValidationTester(_SnapshotWriter):
             if is_cc:
                 line += ', ' + ', '.join(f'{k} = {int(tot[c][j])}' for j, k in enumerate(E.LESION_COLUMNS))
             if is_surf:
-                line += ', ' + ', '.join(f'{k} = {float(surf[c][j]):.3f}' for j, k in enumerate(E.SURFACE_COLUMNS))
+                mm = ' mm' if res[0].get('surface_unit') == 'mm' else ''
+                line += ', ' + ', '.join(f'{k} = {float(surf[c][j]):.3f}{mm}' for j, k in enumerate(E.SURFACE_COLUMNS))
             print(line)
 
 
@@ -134,6 +149,11 @@ def main(argv=None):
         if not (args.data_dir and args.split_dir):
             raise SystemExit('no dataset is shipped: pass --data_dir and --split_dir, or --synthetic')
         data_cube = D.get_data_cube(args)
+        if args.save_nii and data_cube.geometry is not None and data_cube.multi_label and \
+                E.label_rule(True, data_cube.multi_label, args.task) == 'planes':
+            raise SystemExit(f'--save_nii --src_geom: the maps of --multi_label {data_cube.multi_label} hold one plane '
+                             f'per class (C x D x H x W) and cannot be written on the source grid of '
+                             f'{", ".join(data_cube.val_sn)}: drop --src_geom (or --save_nii)')
         with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
             f.write(' '.join(sys.argv) + '\n')
         rank = int(os.environ.get('RANK', '0'))

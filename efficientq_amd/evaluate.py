@@ -130,6 +130,7 @@ WINDOW_BATCH_MAX = 16     # windows per forward at most (a BraTS case has 8 of 1
 EPS = 1e-6                # metrics.py
 LESION_COLUMNS = ("totall", "predl", "fnl", "fpl")     # the columns of "lesions" (hip_ops.seg_lesions)
 SURFACE_COLUMNS = ("hd", "hd95", "assd")               # the columns of "surface" (surface_metrics), voxel units
+SURFACE_COLUMNS_MM = ("hd_mm", "hd95_mm", "assd_mm")   # the same in millimetres (surface_metrics_mm)
 
 
 def metrics_from_counts(counts: torch.Tensor) -> dict:
@@ -170,6 +171,42 @@ def surface_metrics(counts, sums, shape) -> torch.Tensor:
     return out
 
 
+def surface_metrics_mm(counts, sq, sums, shape, spacing) -> torch.Tensor:
+    """hd, hd95, assd per class (C x 3 float64, millimetres) of one case of extent `shape` = (D, H, W) on a grid of
+    `spacing` = (d, h, w) mm from what hip_ops.seg_surface_mm returns: counts C x 2 = nP, nL, sq C x 4 fp32 = max_PL,
+    max_LP, qlo, qhi (mm^2) and sums C x 2.  The definitions are surface_metrics': hd = sqrt of the larger maximum,
+    hd95 = the same interpolation between sqrt(qlo) and sqrt(qhi), assd = the mean of the two directed means.  Both
+    surfaces empty: 0; one of them empty: the physical diagonal sqrt(sum_a (extent_a spacing_a)^2) for all three."""
+    counts = torch.as_tensor(counts).to("cpu", torch.int64)
+    sq = torch.as_tensor(sq).to("cpu", torch.float64)
+    sums = torch.as_tensor(sums).to("cpu", torch.float64)
+    diag = math.sqrt(sum((int(e) * float(s)) ** 2 for e, s in zip(shape, spacing)))
+    out = torch.zeros(counts.shape[0], 3, dtype=torch.float64)
+    for c, ((n_p, n_l), (max_pl, max_lp, qlo, qhi), (sum_pl, sum_lp)) in enumerate(
+            zip(counts.tolist(), sq.tolist(), sums.tolist())):
+        if n_p == 0 and n_l == 0:
+            continue
+        if n_p == 0 or n_l == 0:
+            out[c] = diag
+            continue
+        r = 95 * (n_p + n_l - 1) % 100
+        lo, hi = math.sqrt(qlo), math.sqrt(qhi)
+        out[c, 0] = math.sqrt(max(max_pl, max_lp))
+        out[c, 1] = lo + (hi - lo) * r / 100
+        out[c, 2] = (sum_pl / n_p + sum_lp / n_l) / 2
+    return out
+
+
+def _case_geometry(geometry, i):
+    """(spacing, entry) of case i: `geometry` is one spacing (d, h, w) for all cases, or one entry per case (a dict
+    with `spacing` and, for the label maps, `header` / `pmin` / `pmax`: data.read_source_geometry)."""
+    if isinstance(geometry, (list, tuple)) and len(geometry) == 3 and not isinstance(geometry[0], dict):
+        return tuple(float(v) for v in geometry), None
+    if i >= len(geometry):
+        raise RuntimeError(f"validate_seg: {len(geometry)} geometries, case {i} has none")
+    return tuple(float(v) for v in geometry[i]["spacing"]), geometry[i]
+
+
 def _last_head(out) -> torch.Tensor:
     """The last head of a model output: a list of heads, heads stacked in front (UResQ), or one N x C x ... tensor."""
     if isinstance(out, (list, tuple)):
@@ -189,14 +226,26 @@ def label_rule(multi: bool, multi_label=None, task: str = "lits") -> str:
     return "brats" if key == "brats" else "planes"
 
 
-def _write_map(path, host, dtype):
+def _write_map(path, host, dtype, entry=None):
+    """The map of one case; with the entry of its source image (data.read_source_geometry) restored into the source's
+    shape (zeros outside pmin:pmax) and written with the source's geometry."""
     from .nifti import write_nifti
-    write_nifti(path, np.asarray(host, dtype=dtype))
+    a = np.asarray(host, dtype=dtype)
+    if entry is None or "header" not in entry:
+        write_nifti(path, a)
+        return
+    if a.ndim != 3:
+        raise RuntimeError(f"{path}: a map of shape {a.shape} cannot be put on the source grid (three axes needed)")
+    if "pmin" in entry:
+        from .data import restore_crop
+        a = restore_crop(a, entry["pmin"], entry["pmax"], entry["source_shape"])
+    write_nifti(path, a, geometry=entry["header"])
 
 
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
-                 save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False):
+                 save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
+                 geometry=None):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -214,7 +263,14 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     metrics.py:69-94) - one more call per case after the tallies.
     surface: each dict also carries "surface", the C x 3 float64 surface distances SURFACE_COLUMNS of the same decisions
     in voxel units (surface_metrics), and "surface_counts", the C x 6 int64 they come from (effq_seg_surface: an exact
-    distance transform of the 2 C surfaces on the device) - one more call per case after the tallies."""
+    distance transform of the 2 C surfaces on the device) - one more call per case after the tallies.
+    geometry: None, one spacing (d, h, w) in mm for all cases, or one entry per case (data.read_source_geometry).  The
+    surface distances are then measured in millimetres (effq_seg_surface_mm, surface_metrics_mm): "surface" holds mm,
+    "surface_unit" is "mm", and "surface_counts" (C x 2) and "surface_sq" (C x 4 fp32) are what they come from.  A
+    case's entry with the header of its source image also puts its map on the source grid: restored into the source
+    shape and written with the source's affine, codes and pixdim (a RuntimeError naming the case when the maps are the
+    C x D x H x W planes of --multi_label lits, which have no place on a source grid).  Counts and metrics stay those of
+    the given grid."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -262,6 +318,12 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
             maps = None
             if pool is not None:                # the planes are 0/1 uint8 on the device, cast when written
                 rule = label_rule(multi, multi_label, task)
+                if rule == "planes" and geometry is not None:
+                    sn = names[len(results)] if names is not None else str(len(results))
+                    if _case_geometry(geometry, len(results))[1] is not None:
+                        raise RuntimeError(f"validate_seg: case {sn}: the maps of --multi_label lits hold one plane per "
+                                           f"class (C x D x H x W); a NIfTI image has its spatial axes first, so they "
+                                           f"cannot be written on the source grid: save them without --src_geom")
                 maps = ops.seg_labels(stitched, rule, fuse if multi else None,
                                       torch.uint8 if rule == "planes" else map_dtype).cpu().numpy()
             for n in range(N):
@@ -273,15 +335,26 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                 if lesions:
                     res["lesions"] = ops.seg_lesions(stitched[n], lab[n], "brats" if multi else "lits",
                                                      fuse if multi else None).cpu()
-                if surface:
+                spacing, entry = _case_geometry(geometry, i) if geometry is not None else (None, None)
+                if surface and spacing is None:
                     sc, ss = ops.seg_surface(stitched[n], lab[n], "brats" if multi else "lits",
                                              fuse if multi else None)
                     res["surface_counts"] = sc.cpu()
                     res["surface"] = surface_metrics(res["surface_counts"], ss, vol.shape[-3:])
+                elif surface:
+                    sc, sq, ss = ops.seg_surface_mm(stitched[n], lab[n], "brats" if multi else "lits",
+                                                    fuse if multi else None, spacing)
+                    res["surface_counts"], res["surface_sq"] = sc.cpu(), sq.cpu()
+                    res["surface"] = surface_metrics_mm(res["surface_counts"], res["surface_sq"], ss, vol.shape[-3:],
+                                                        spacing)
+                    res["surface_unit"] = "mm"
                 results.append(res)
-                if maps is not None:
+                if maps is not None and entry is None:
                     writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
                                               label_dtype))
+                elif maps is not None:
+                    writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
+                                              label_dtype, entry))
     finally:
         if pool is not None:
             pool.shutdown(wait=True)
@@ -293,14 +366,19 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
 def write_metrics_csv(path: str, results) -> None:
     """One row per subject and class: subject, class, dsc, sens, spec, acc, tp, fp, fn, tn, and when the results carry
     "lesions" (validate_seg(..., lesions=True)) also totall, predl, fnl, fpl, and when they carry "surface"
-    (validate_seg(..., surface=True)) after those hd, hd95, assd."""
+    (validate_seg(..., surface=True)) after those hd, hd95, assd - named hd_mm, hd95_mm, assd_mm when the results are in
+    millimetres ("surface_unit": validate_seg(..., geometry=...)); a file never mixes the two."""
     import csv
     cc = any("lesions" in r for r in results)
     sd = any("surface" in r for r in results)
+    units = {r.get("surface_unit", "voxel") for r in results if "surface" in r}
+    if len(units) > 1:
+        raise RuntimeError("write_metrics_csv: surface distances in voxel units and in mm in one file")
+    sd_cols = SURFACE_COLUMNS_MM if units == {"mm"} else SURFACE_COLUMNS
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
         wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn") + (LESION_COLUMNS if cc else ()) +
-                    (SURFACE_COLUMNS if sd else ()))
+                    (sd_cols if sd else ()))
         for r in results:
             for c in range(r["counts"].shape[0]):
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +

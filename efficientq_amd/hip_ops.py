@@ -1246,6 +1246,86 @@ class HipOps:
                                         _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface")
         return counts, sums
 
+    @staticmethod
+    def _axis_weights(what: str, spacing):
+        """The fp32 weights of the three axes, float32(float64(spacing) ** 2), from a spacing of three finite positive
+        numbers (millimetres per voxel along D, H, W)."""
+        import numpy as np
+        try:
+            sp = [float(v) for v in spacing]
+        except (TypeError, ValueError):
+            sp = []
+        if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+            raise _lib.EffqError(f"{what}: spacing {spacing!r}, needs three finite positive numbers (d, h, w)")
+        w = [float(np.float32(np.float64(v) ** 2)) for v in sp]
+        if not all(math.isfinite(v) and v > 0 for v in w):
+            raise _lib.EffqError(f"{what}: the square of spacing {spacing!r} is not a positive finite float32")
+        return w
+
+    def edt_sq_mm(self, mask: torch.Tensor, spacing):
+        """Squared Euclidean distance transform on a grid of spacing (d, h, w) (effq_edt_sq_mm): `mask` D x H x W or
+        P x D x H x W uint8, non-zero = site.  Returns a float32 tensor of the mask's shape: for every voxel the least
+        fl(fl(fl(ww dw^2) + fl(wh dh^2)) + fl(wd dd^2)) over the sites of its own volume, wa = float32(spacing_a ** 2) -
+        the bits of the brute force in fp32 -, 0 on a site, +inf throughout a volume without sites."""
+        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
+            raise _lib.EffqError(f"edt_sq_mm: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
+        if mask.device != self.device and not (mask.device.type == "cuda" and
+                                               self.device.index in (None, mask.device.index)):
+            raise _lib.EffqError(f"edt_sq_mm: mask on {mask.device}, ops on {self.device}")
+        wd, wh, ww = self._axis_weights("edt_sq_mm", spacing)
+        m = mask.contiguous()
+        D, H, W = (int(i) for i in m.shape[-3:])
+        P = int(m.shape[0]) if m.dim() == 4 else 1
+        need = self.lib.effq_surf_mm_ws_bytes(P, D, H, W)
+        if need == 0:
+            raise _lib.EffqError(f"edt_sq_mm: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels "
+                                 f"in all, every extent at most {_lib.EDT_MM_MAX_EXTENT})")
+        sq = torch.empty(m.shape, dtype=torch.float32, device=self.device)
+        ws = self._workspace("surf_mm", need)
+        check(self.lib.effq_edt_sq_mm(_ptr(m), P, D, H, W, wd, wh, ww, _ptr(sq), _ptr(ws), ws.numel(), self.stream),
+              "effq_edt_sq_mm")
+        return sq
+
+    def seg_surface_mm(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None,
+                       spacing=(1.0, 1.0, 1.0)):
+        """What the surface distances of one case in millimetres need (effq_seg_surface_mm), from its stitched logits
+        (C x D x H x W), its label and the spacing (d, h, w) of its grid; arguments and decisions as seg_surface.
+        Returns (counts, sq, sums): counts C x 2 int64 = nP, nL, sq C x 4 float32 = max_PL, max_LP, qlo, qhi (squared
+        distances in mm^2) and sums C x 2 float64 = the sums of the directed distances in mm (include/effq_hip.h);
+        evaluate.surface_metrics_mm turns them into hd, hd95 and assd."""
+        x = self._f32(logits)
+        if x.dim() != 4:
+            raise _lib.EffqError(f"seg_surface_mm: expected C x D x H x W logits, got {tuple(x.shape)}")
+        Cc, D, H, W = (int(i) for i in x.shape)
+        if task == "lits":
+            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
+        elif task == "brats":
+            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
+        else:
+            raise _lib.EffqError(f"Unknown task {task}")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
+            raise _lib.EffqError(f"seg_surface_mm: merge type {fuse!r} for task {task}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_surface_mm: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
+            raise _lib.EffqError(f"seg_surface_mm: label {tuple(label.shape)} {label.dtype} on {label.device}, "
+                                 f"needs {lshape} torch.uint8 on {x.device}")
+        wd, wh, ww = self._axis_weights("seg_surface_mm", spacing)
+        need = self.lib.effq_surf_mm_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
+        if need == 0:
+            raise _lib.EffqError(f"seg_surface_mm: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
+                                 f"most, every extent at most {_lib.EDT_MM_MAX_EXTENT})")
+        lab = label.contiguous()
+        counts = torch.empty(Cc, 2, dtype=torch.int64, device=self.device)
+        sq = torch.empty(Cc, 4, dtype=torch.float32, device=self.device)
+        sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
+        ws = self._workspace("surf_mm", need)
+        check(self.lib.effq_seg_surface_mm(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh, wd, wh, ww,
+                                           _ptr(counts), _ptr(sq), _ptr(sums), _ptr(ws), ws.numel(), self.stream),
+              "effq_seg_surface_mm")
+        return counts, sq, sums
+
 
 _OPS = {}
 

@@ -7,11 +7,17 @@ and in Fortran order (first array axis fastest), so a NIfTI reader gets back ``a
 files carry no name and ``mtime`` 0: the same map always gives the same bytes.
 
 The reader is the inverse for these files (uint8 / uint16 data, either byte order) and rejects anything else.
+
+``read_geometry`` reads only the header of an image of any datatype: where the voxels of a scan lie in space.  With
+``--src_geom`` the label maps are written with the geometry of the scan they belong to (``write_nifti(..., geometry=)``:
+the source's sform and qform fields, codes and ``pixdim``), so that a viewer overlays them, and the surface distances
+are measured with the source's spacing.
 """
 from __future__ import annotations
 
 import gzip
 import struct
+import zlib
 
 import numpy as np
 
@@ -25,25 +31,32 @@ GZIP_LEVEL = 1
 # (name, struct format, offset) of the fields used here, NIfTI-1 spec (nifti1.h)
 FIELDS = (("sizeof_hdr", "i", 0), ("dim", "8h", 40), ("datatype", "h", 70), ("bitpix", "h", 72),
           ("pixdim", "8f", 76), ("vox_offset", "f", 108), ("scl_slope", "f", 112), ("scl_inter", "f", 116),
+          ("xyzt_units", "B", 123),
           ("qform_code", "h", 252), ("sform_code", "h", 254), ("quatern", "6f", 256), ("srow_x", "4f", 280),
           ("srow_y", "4f", 296), ("srow_z", "4f", 312), ("magic", "4s", 344))
 
 
-def _header(shape, dtype: np.dtype, affine: np.ndarray) -> bytes:
+def _header(shape, dtype: np.dtype, affine: np.ndarray, geometry=None) -> bytes:
     hdr = bytearray(HEADER_BYTES)
     dim = [len(shape)] + list(shape) + [1] * (7 - len(shape))
     values = {"sizeof_hdr": (HEADER_BYTES,), "dim": dim, "datatype": (_CODES[dtype],), "bitpix": (8 * dtype.itemsize,),
               "pixdim": [1.0] * 8, "vox_offset": (float(VOX_OFFSET),), "scl_slope": (0.0,), "scl_inter": (0.0,),
-              "qform_code": (0,), "sform_code": (2,), "quatern": [0.0, 0.0, 0.0] + list(affine[:3, 3]),
+              "xyzt_units": (0,), "qform_code": (0,), "sform_code": (2,), "quatern": [0.0, 0.0, 0.0] + list(affine[:3, 3]),
               "srow_x": list(affine[0]), "srow_y": list(affine[1]), "srow_z": list(affine[2]), "magic": (MAGIC,)}
+    if geometry is not None:                                           # the source's own fields, value for value
+        values.update({"pixdim": list(geometry["pixdim"]),
+                       "xyzt_units": (int(geometry.get("xyzt_units", 0)),), "qform_code": (int(geometry["qform_code"]),),
+                       "sform_code": (int(geometry["sform_code"]),), "quatern": list(geometry["quatern"]),
+                       "srow_x": list(geometry["srow_x"]), "srow_y": list(geometry["srow_y"]),
+                       "srow_z": list(geometry["srow_z"])})
     for name, fmt, off in FIELDS:
         struct.pack_into("<" + fmt, hdr, off, *values[name])
     hdr[38:39] = b"r"                                                  # `regular`, as the ANALYZE readers expect
     return bytes(hdr)
 
 
-def encode_nifti(array, affine=None) -> bytes:
-    """The uncompressed ``.nii`` bytes of a uint8 / uint16 array of 1 to 7 dimensions."""
+def encode_nifti(array, affine=None, geometry=None) -> bytes:
+    """The uncompressed ``.nii`` bytes of a uint8 / uint16 array of 1 to 7 dimensions; see write_nifti."""
     a = np.asarray(array)
     if a.dtype.newbyteorder("=") not in _CODES:
         raise ValueError(f"write_nifti: {a.dtype} data, only uint8 and uint16 are written")
@@ -52,15 +65,24 @@ def encode_nifti(array, affine=None) -> bytes:
     aff = np.eye(4) if affine is None else np.asarray(affine, dtype=np.float64)
     if aff.shape != (4, 4):
         raise ValueError(f"write_nifti: affine of shape {aff.shape}, needs 4 x 4")
+    if geometry is not None:
+        if affine is not None:
+            raise ValueError("write_nifti: give an affine or a geometry, not both")
+        if tuple(geometry["shape"][:3]) != tuple(a.shape[:3]):
+            raise ValueError(f"write_nifti: array of shape {a.shape} for a geometry of shape {tuple(geometry['shape'])}")
     dt = a.dtype.newbyteorder("=")
     data = np.asarray(a, dtype=dt.newbyteorder("<")).tobytes(order="F")
-    return _header(a.shape, dt, aff) + b"\0" * (VOX_OFFSET - HEADER_BYTES) + data
+    return _header(a.shape, dt, aff, geometry) + b"\0" * (VOX_OFFSET - HEADER_BYTES) + data
 
 
-def write_nifti(path: str, array, affine=None) -> None:
+def write_nifti(path: str, array, affine=None, geometry=None) -> None:
     """Write `array` (uint8 / uint16) to `path` as a single-file NIfTI-1 image with the given 4 x 4 affine (identity by
-    default); a path ending in ``.gz`` is gzip-compressed with no name and mtime 0."""
-    raw = encode_nifti(array, affine)
+    default); a path ending in ``.gz`` is gzip-compressed with no name and mtime 0.  With `geometry` (what read_geometry
+    returned for the scan the map belongs to) the header carries that image's sform and qform fields, both codes, its
+    ``pixdim`` and its ``xyzt_units`` (what unit the pixdim are in) instead; the other fields of the source header
+    (descrip, intent, cal_min / cal_max, slice timing) are not copied.  The array's first three axes are the image's i,
+    j, k and must have the source's extents."""
+    raw = encode_nifti(array, affine, geometry)
     with open(path, "wb") as f:
         if str(path).endswith(".gz"):
             with gzip.GzipFile(filename="", mode="wb", compresslevel=GZIP_LEVEL, fileobj=f, mtime=0) as gz:
@@ -110,3 +132,76 @@ def read_nifti(path: str):
     if raw[:2] == b"\x1f\x8b":
         raw = gzip.decompress(raw)
     return decode_nifti(raw)
+
+
+# ---- geometry --------------------------------------------------------------------------------------------------------
+def _read_head(path: str, nbytes: int) -> bytes:
+    """The first `nbytes` bytes of a file, or of what a gzip file holds (no more than that is inflated)."""
+    with open(path, "rb") as fh:
+        head = fh.read(2)
+        if head != b"\x1f\x8b":
+            return head + fh.read(nbytes - 2)
+        z = zlib.decompressobj(wbits=31)
+        out, chunk = b"", head + fh.read(1022)
+        while chunk and len(out) < nbytes:
+            out += z.decompress(chunk, nbytes - len(out))
+            while z.unconsumed_tail and len(out) < nbytes:
+                out += z.decompress(z.unconsumed_tail, nbytes - len(out))
+            chunk = fh.read(1024)
+        return out
+
+
+def qform_affine(quatern, pixdim) -> np.ndarray:
+    """The 4 x 4 affine of the qform fields (nifti1.h, "METHOD 2"): quaternion (b, c, d) with a = sqrt(1 - b^2 - c^2 -
+    d^2), voxel sizes pixdim[1..3], qfac = -1 when pixdim[0] < 0 (the third column is flipped) and the offsets."""
+    b, c, d, qx, qy, qz = (float(v) for v in quatern)
+    a2 = 1.0 - (b * b + c * c + d * d)
+    a = np.sqrt(a2) if a2 > 0.0 else 0.0
+    rot = np.array([[a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c)],
+                    [2 * (b * c + a * d), a * a + c * c - b * b - d * d, 2 * (c * d - a * b)],
+                    [2 * (b * d - a * c), 2 * (c * d + a * b), a * a + d * d - b * b - c * c]], dtype=np.float64)
+    qfac = -1.0 if float(pixdim[0]) < 0.0 else 1.0
+    aff = np.eye(4)
+    aff[:3, :3] = rot * np.array([float(pixdim[1]), float(pixdim[2]), float(pixdim[3]) * qfac])
+    aff[:3, 3] = (qx, qy, qz)
+    return aff
+
+
+def read_geometry(path: str) -> dict:
+    """Where the voxels of a single-file NIfTI-1 image (``.nii`` / ``.nii.gz``, either byte order, any datatype) lie,
+    from its header alone.  Returns `shape`, `pixdim` (8 values), `qform_code`, `sform_code`, `quatern` (b, c, d and the
+    three offsets), `srow_x` / `srow_y` / `srow_z`, `xyzt_units`, `datatype`, and
+    affine   the sform rows when sform_code > 0, else the qform (qform_affine) when qform_code > 0, else
+             diag(pixdim[1..3]) - the order in which NIfTI readers choose;
+    spacing  the Euclidean norm of each of the first three columns of that affine: millimetres per step along array
+             axis 0, 1, 2.
+    Raises ValueError on anything that is not such a file."""
+    raw = _read_head(path, VOX_OFFSET)
+    if len(raw) < HEADER_BYTES:
+        raise ValueError(f"read_geometry: {path}: {len(raw)} bytes, shorter than a NIfTI-1 header")
+    for end in "<>":
+        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
+            break
+    else:
+        raise ValueError(f"read_geometry: {path}: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
+    f = {}
+    for name, fmt, off in FIELDS:
+        v = struct.unpack_from(end + fmt, raw, off)
+        f[name] = v[0] if len(v) == 1 else v
+    if f["magic"] != MAGIC:
+        raise ValueError(f"read_geometry: {path}: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    ndim = f["dim"][0]
+    if not 3 <= ndim <= 7 or min(f["dim"][1:1 + ndim]) < 1:
+        raise ValueError(f"read_geometry: {path}: dim = {f['dim']}, needs three axes or more")
+    g = {k: f[k] for k in ("pixdim", "xyzt_units", "qform_code", "sform_code", "quatern", "srow_x", "srow_y", "srow_z",
+                           "datatype")}
+    g["shape"] = tuple(int(n) for n in f["dim"][1:1 + ndim])
+    if f["sform_code"] > 0:
+        aff = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
+    elif f["qform_code"] > 0:
+        aff = qform_affine(f["quatern"], f["pixdim"])
+    else:
+        aff = np.diag([float(f["pixdim"][1]), float(f["pixdim"][2]), float(f["pixdim"][3]), 1.0])
+    g["affine"] = aff
+    g["spacing"] = tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
+    return g

@@ -653,6 +653,39 @@ int effq_edt_sq(const uint8_t* masks, int P, int D, int H, int W, int32_t* sq, v
 int effq_seg_surface(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
                      float thresh, long long* counts, double* sums, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the distance transform with per-axis weights and the surface distances in millimetres (validate_seg(...,
+ * surface=True, geometry=...): the voxels of a scan are rarely cubes).  The squared distance of voxel v to site s is
+ * defined in fp32, term by term:
+ *     E(v, s) = fl( fl( fl(ww dw^2) + fl(wh dh^2) ) + fl(wd dd^2) ),   (dd, dh, dw) = v - s,
+ * every fl one correctly rounded fp32 operation, no fused multiply-add, fp32 denormals kept.  The separable transform
+ * (w, then h, then d) returns the bits of the brute force over all sites (DESIGN section 13 has the argument).  The
+ * contract holds for the build of csrc/Makefile only: a recipe without -ffp-contract=off, or one that flushes fp32
+ * denormals (-fgpu-flush-denormals-to-zero), may fuse or flush and then returns other bits.
+ * wd, wh, ww: the squared spacing of the axes, float32(float64(spacing) ** 2); finite and > 0.
+ *
+ * effq_edt_sq_mm: masks (P, D, H, W) uint8, non-zero = site -> sq (P, D, H, W) fp32 = min over the sites s of the
+ *   voxel's own plane of E(v, s); +inf everywhere in a plane without sites.  P * D*H*W < 2^31, P <= 65535, every extent
+ *   <= EFFQ_EDT_MM_MAX_EXTENT ((i - j)^2 < 2^24 is exact in fp32).  Three launches.
+ * effq_seg_surface_mm: arguments, decisions, P, L and S(M) as effq_seg_surface.  counts (C, 2) int64 = nP, nL; sq (C, 4)
+ *   fp32 = the largest E_L over S(P), the largest E_P over S(L) (0 where the set or the target is empty) and the values
+ *   at ranks lo and min(lo + 1, n - 1) of the n = nP + nL pooled values in ascending order, lo = 95 (n - 1) / 100 in
+ *   integers (0 where a surface is empty); sums (C, 2) fp64 = the sum of sqrt((double)E_L) over S(P) and of
+ *   sqrt((double)E_P) over S(L) (0 where the target is empty).  Integer counts select the two ranks and the
+ *   sums are added in a fixed order: equal inputs give equal bits.  A fixed number of launches on `stream`, no read by
+ *   the host and no workgroup that waits for another.  hd, hd95 and assd follow on the host (evaluate.surface_metrics_mm).
+ * ws: effq_surf_mm_ws_bytes(P, D, H, W) bytes for either call, P = 2 C for effq_seg_surface_mm: 4 B of squared distance
+ *   per plane and voxel, 2 B of decision bits and 2 B of surface bits per voxel and 161 KiB of counters and partial sums
+ *   (effq_edt_sq_mm writes into `sq` and only checks the size); 0 for dimensions out of range.  A BraTS case (3 classes,
+ *   155 x 240 x 240): 214 MB of distances, 250 MB in all.  Bad arguments (a weight that is 0, negative, NaN or infinite
+ *   among them) and a short workspace return EFFQ_ERR_ARG and launch nothing. */
+#define EFFQ_EDT_MM_MAX_EXTENT 4096
+size_t effq_surf_mm_ws_bytes(int P, int D, int H, int W);
+int effq_edt_sq_mm(const uint8_t* masks, int P, int D, int H, int W, float wd, float wh, float ww, float* sq, void* ws,
+                   size_t ws_bytes, void* stream);
+int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                        float thresh, float wd, float wh, float ww, long long* counts, float* sq, double* sums, void* ws,
+                        size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

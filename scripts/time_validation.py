@@ -11,7 +11,10 @@ is read from a kernel trace of this script (rocprofv3 --kernel-trace --stats -- 
 --surf-dist adds effq_seg_surface (the surface distances hd, hd95, assd: an exact distance transform of the 2 x 3
 surfaces of the case) in the same way: on the net's own logits and on random logits, validate_seg per case with and
 without surface=True, and with scipy the host way on the same masks (copy + two binary erosions and two
-distance_transform_edt per class)."""
+distance_transform_edt per class).
+--surf-dist --spacing d,h,w times effq_seg_surface_mm (the same distances in millimetres on a grid of that spacing: the
+weighted transform and the radix select) the same way, next to the integer path measured in the same run, and
+validate_seg per case with geometry=spacing."""
 import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,6 +25,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--save-nii", dest="save_nii", action="store_true", help="also time the NIfTI label maps")
 ap.add_argument("--is-cc", dest="is_cc", action="store_true", help="also time the lesion-level counts")
 ap.add_argument("--surf-dist", dest="surf_dist", action="store_true", help="also time the surface distances")
+ap.add_argument("--spacing", default=None, help="d,h,w in mm: with --surf-dist also time the distances in mm")
 cli = ap.parse_args()
 REPS = int(os.environ.get("REPS", "5"))
 HBM_PEAK = 8.0e12
@@ -199,12 +203,37 @@ if cli.surf_dist:
         return round(sorted(ms[1:])[2], 2)
     res["validate_ms_per_case"] = wall_sd(False)
     res["validate_surface_ms_per_case"] = wall_sd(True)
+    if cli.spacing:
+        spacing = tuple(float(v) for v in cli.spacing.split(","))
+        # the same traffic as the integer path (fp32 maps for int32 ones); the select reads the surface bits four more
+        # times (2 B per voxel each) and the maps at the surface voxels only
+        nbytes_mm = nbytes + 4 * vox * 2
+        for key, lg in (("surface_mm", net_logits), ("surface_mm_random_logits", stitched)):
+            ms = timed(lambda: ops.seg_surface_mm(lg[0], lab8, "brats", "agg", spacing))
+            cnt, sq, sm = ops.seg_surface_mm(lg[0], lab8, "brats", "agg", spacing)
+            res[key] = {"ms": round(ms, 4), "bytes": int(nbytes_mm),
+                        "hbm_frac": round(nbytes_mm / (ms * 1e-3) / HBM_PEAK, 3), "counts": cnt.tolist(),
+                        "metrics_mm": E.surface_metrics_mm(cnt, sq, sm, shape, spacing).tolist()}
+            res[key]["over_integer_path"] = round(ms / res[key.replace("_mm", "")]["ms"], 2)
+        res["surf_mm_ws_MB"] = round(ops.lib.effq_surf_mm_ws_bytes(planes, *shape) / 1e6, 1)
+
+        def wall_mm():
+            ms = []
+            for i in range(6):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                E.validate_seg(model, loader * 3, "brats", p, o, window_batch=nwin, fuse="agg", surface=True,
+                               geometry=spacing)
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3 / 3)
+            return round(sorted(ms[1:])[2], 2)
+        res["validate_surface_mm_ms_per_case"] = wall_mm()
     try:
         from scipy import ndimage
     except ImportError:
         ndimage = None
     res["scipy"] = ndimage is not None
-    if ndimage is not None:
+    if ndimage is not None and not cli.spacing:
         import numpy as np
         pred = ops.seg_labels(net_logits, "planes", "agg")[0]
         six = ndimage.generate_binary_structure(3, 1)
