@@ -1,17 +1,11 @@
 // The exact Euclidean distance transform of 3-D masks and the surface-distance columns of the validation
 // (validate_seg(..., surface=True): hd, hd95, assd per class, in voxel units).  The transform is separable and all of
-// it is integer arithmetic, so the squared distance map is exact by construction:
+// it is integer arithmetic, so the squared distance map is exact by construction.  Phases of a call:
 //
 //   masks    (effq_seg_surface only) decide<MODE, C> of every voxel -> 16 decision bits per voxel (seg_masks.h)
 //   surface  (effq_seg_surface only, seg_surf.h) a 6-neighbour stencil on the bits of all 2 C masks at once: a voxel of a mask is a
 //            surface voxel when a face neighbour is background or lies outside the volume
-//   rows     along w, one wave per row: the squared distance to the nearest site of the row, from the ballots of the
-//            row's chunks of 64 (a sweep from the right records the next site after every chunk, a sweep from the left
-//            writes each voxel once)
-//   lines    along h, then along d: the lower envelope min_j (g(j) + (i - j)^2) of every line.  A slab of `tw` lines
-//            adjacent along w is staged in LDS (every global access is a run of tw consecutive ints), the first and last
-//            finite entry of each line are noted, and every voxel searches outwards from itself inside that range until
-//            (i - j)^2 reaches its best value so far.  In place: a workgroup owns its lines.
+//   rows, lines   the three separable passes of seg_surf.h with the metric EdtVox: squared distances in int32
 //   reduce   (effq_seg_surface only) every surface voxel of one mask reads the other mask's map: integer atomicAdd on a
 //            histogram over squared distance per class and direction (the crowded bins first in LDS), then one
 //            workgroup per class walks its two histograms in ascending order for the counts, the maxima, the fp64 sums
@@ -26,10 +20,6 @@
 
 namespace effq {
 
-constexpr int EDT_INF = INT32_MAX;
-constexpr int EDT_THREADS = 256;
-constexpr int EDT_ROWS = EDT_THREADS / 64;             // rows of one workgroup of the w pass: one per wave
-constexpr int EDT_MAX_CHUNKS = 728;                    // chunks of 64 of the longest row (W^2 < 2^31: W <= 46340)
 constexpr int EDT_LDS_MAX = 64 * 1024;                 // the slab is narrowed down to EDT_LDS_AIM (seg_surf.h); a single line may take this
 constexpr int SURF_LOW = 256;                          // squared distances below this are counted in LDS first
 constexpr int SURF_FINAL_THREADS = 1024;
@@ -62,92 +52,6 @@ static SurfWs surf_ws(void* ws, int P, int D, int H, int W) {
   r.hist = reinterpret_cast<uint32_t*>(p + off); off += align16(r.hist_bytes);
   r.bytes = off;
   return r;
-}
-
-// ---- rows -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(EDT_THREADS) void k_edt_rows(EdtSrc src, int* __restrict__ sq, int S, int W, int nrows) {
-  __shared__ int s_next[EDT_ROWS][EDT_MAX_CHUNKS];     // the first site after chunk k of the wave's row, -1: none
-  const int plane = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x * EDT_ROWS + wave;
-  const bool live = row < nrows;
-  const int base = live ? row * W : 0;
-  const int nchunks = (W + 63) / 64;
-  int next = -1;
-  for (int k = nchunks - 1; k >= 0; --k) {
-    if (lane == 0) s_next[wave][k] = next;
-    const int w = k * 64 + lane;
-    const unsigned long long bal = __ballot(live && w < W && edt_site(src, plane, S, base + w));
-    if (bal) next = k * 64 + __builtin_ctzll(bal);
-  }
-  __syncthreads();
-  if (!live) return;
-  int* out = sq + (size_t)plane * S + base;
-  int last = -1;
-  for (int k = 0; k < nchunks; ++k) {
-    const int w = k * 64 + lane;
-    const unsigned long long bal = __ballot(w < W && edt_site(src, plane, S, base + w));
-    const unsigned long long le = bal & (~0ull >> (63 - lane)), ge = bal & (~0ull << lane);
-    const int lpos = le ? k * 64 + 63 - __builtin_clzll(le) : last;
-    const int rpos = ge ? k * 64 + __builtin_ctzll(ge) : s_next[wave][k];
-    int dist = -1;                                     // W <= 46340: dist * dist < 2^31
-    if (lpos >= 0) dist = w - lpos;
-    if (rpos >= 0 && (dist < 0 || rpos - w < dist)) dist = rpos - w;
-    if (w < W) out[w] = dist < 0 ? EDT_INF : dist * dist;
-    if (bal) last = k * 64 + 63 - __builtin_clzll(bal);
-  }
-}
-
-// ---- lines ----------------------------------------------------------------------------------------------------------
-// Line (o, w) of a plane holds the n voxels o * ostride + i * stride + w.  h pass: o = d, ostride = H W, stride = W,
-// n = H; d pass: o = h, ostride = W, stride = H W, n = D.  tw = 1 << ltw lines adjacent along w make the slab of a
-// workgroup; dynamic LDS: (n + 2) * tw ints.  A candidate is formed in uint32: EDT_INF + (i - j)^2 < 2^32.
-__global__ __launch_bounds__(EDT_THREADS) void k_edt_lines(int* __restrict__ sq, int S, int W, int n, int stride,
-                                                           int ostride, int ltw, int ntw) {
-  extern __shared__ int s_g[];
-  const int tw = 1 << ltw, rows = EDT_THREADS >> ltw;
-  int* s_lo = s_g + n * tw;
-  int* s_hi = s_lo + tw;
-  const int lw = threadIdx.x & (tw - 1), r = threadIdx.x >> ltw;
-  const int o = blockIdx.x / ntw, w = (blockIdx.x % ntw) * tw + lw;
-  const bool live = w < W;
-  int* line = sq + (size_t)blockIdx.y * S + (size_t)o * ostride + (live ? w : 0);
-  if (threadIdx.x < tw) {
-    s_lo[threadIdx.x] = n;
-    s_hi[threadIdx.x] = -1;
-  }
-  __syncthreads();
-  int lo = n, hi = -1;
-  for (int i = r; i < n; i += rows) {
-    const int g = live ? line[(size_t)i * stride] : EDT_INF;
-    s_g[i * tw + lw] = g;
-    if (g != EDT_INF) {
-      lo = min(lo, i);
-      hi = i;
-    }
-  }
-  if (hi >= 0) {
-    atomicMin(&s_lo[lw], lo);
-    atomicMax(&s_hi[lw], hi);
-  }
-  __syncthreads();
-  lo = s_lo[lw];
-  hi = s_hi[lw];
-  if (!live || hi < 0) return;                         // a line without a finite entry stays as it is
-  for (int i = r; i < n; i += rows) {
-    uint32_t best = (uint32_t)s_g[i * tw + lw];
-    for (int j = min(i - 1, hi); j >= lo; --j) {
-      const uint32_t dd = (uint32_t)((i - j) * (i - j));
-      if (dd >= best) break;
-      best = min(best, (uint32_t)s_g[j * tw + lw] + dd);
-    }
-    for (int j = max(i + 1, lo); j <= hi; ++j) {
-      const uint32_t dd = (uint32_t)((j - i) * (j - i));
-      if (dd >= best) break;
-      best = min(best, (uint32_t)s_g[j * tw + lw] + dd);
-    }
-    line[(size_t)i * stride] = (int)best;
-  }
 }
 
 // ---- reduce ---------------------------------------------------------------------------------------------------------
@@ -275,29 +179,6 @@ static bool edt_dims_ok(int P, int D, int H, int W) {
          H <= EFFQ_EDT_MAX_LINE;
 }
 
-static int edt_line_pass(int* sq, int P, int S, int W, int n, int stride, int nouter, int ostride, hipStream_t st) {
-  if (n == 1) return EFFQ_OK;                          // min over one entry
-  int ltw = 6;
-  while (ltw > 0 && (size_t)(n + 2) * sizeof(int) << ltw > (size_t)EDT_LDS_AIM) --ltw;
-  const int tw = 1 << ltw, ntw = (W + tw - 1) / tw;
-  const size_t lds = (size_t)(n + 2) * sizeof(int) << ltw;
-  hipLaunchKernelGGL(k_edt_lines, dim3((unsigned)((size_t)nouter * ntw), P), dim3(EDT_THREADS), lds, st, sq, S, W, n,
-                     stride, ostride, ltw, ntw);
-  EFFQ_LAUNCH_CHECK();
-  return EFFQ_OK;
-}
-
-// the three passes of P planes into sq (P, S)
-static int edt_run(const EdtSrc& src, int P, int D, int H, int W, int* sq, hipStream_t st) {
-  const int S = D * H * W, nrows = D * H;
-  hipLaunchKernelGGL(k_edt_rows, dim3((nrows + EDT_ROWS - 1) / EDT_ROWS, P), dim3(EDT_THREADS), 0, st, src, sq, S, W,
-                     nrows);
-  EFFQ_LAUNCH_CHECK();
-  const int rc = edt_line_pass(sq, P, S, W, H, W, D, H * W, st);
-  if (rc != EFFQ_OK) return rc;
-  return edt_line_pass(sq, P, S, W, D, H * W, H, W, st);
-}
-
 }  // namespace effq
 using namespace effq;
 
@@ -315,7 +196,7 @@ int effq_edt_sq(const uint8_t* masks, int P, int D, int H, int W, int32_t* sq, v
   EFFQ_CHECK_ARG(ws_bytes >= surf_ws(ws, P, D, H, W).bytes);
   EdtSrc src;
   src.masks = masks; src.surf = nullptr; src.C = 0;
-  return edt_run(src, P, D, H, W, sq, as_stream(stream));
+  return edt_run<EdtVox>(src, P, D, H, W, EdtUnit{}, EdtUnit{}, EdtUnit{}, sq, as_stream(stream));
 }
 
 int effq_seg_surface(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
@@ -338,7 +219,7 @@ int effq_seg_surface(const float* logits, const uint8_t* label, int C, int D, in
   EFFQ_LAUNCH_CHECK();
   EdtSrc src;
   src.masks = nullptr; src.surf = s.surf; src.C = C;
-  rc = edt_run(src, P, D, H, W, s.sq, st);
+  rc = edt_run<EdtVox>(src, P, D, H, W, EdtUnit{}, EdtUnit{}, EdtUnit{}, s.sq, st);
   if (rc != EFFQ_OK) return rc;
   hipLaunchKernelGGL(k_surf_hist, gs, b, (size_t)P * (SURF_LOW + 1) * sizeof(uint32_t), st, s.surf, s.sq, C, (int)S, nbins,
                      s.hist);

@@ -3,8 +3,7 @@
 // the separable passes return the bits of the brute force, how the two pooled ranks are selected and what was measured is
 // in DESIGN section 13 ("Source geometry").  Phases of a call, in launch order:
 //   masks, surface   the decision bits (seg_masks.h) and the 6-neighbour stencil (seg_surf.h), as effq_seg_surface
-//   rows             k_mm_rows: along w, one wave per row, ballots; writes fl(ww dw^2)
-//   lines            k_mm_lines along h, then d: min_j fl(g(j) + fl(wa (i - j)^2)), a slab of lines in LDS, in place
+//   rows, lines      the three separable passes of seg_surf.h with the metric EdtMm: fl(g(j) + fl(wa (i - j)^2)) in fp32
 //   reduce           k_mm_scan, then k_mm_select / k_mm_hist over 8 + 8 + 8 + 8 bits of the pattern, k_mm_next, k_mm_final
 #include <cmath>
 
@@ -16,8 +15,7 @@
 namespace effq {
 
 constexpr int MM_THREADS = 256;
-constexpr int MM_ROWS = MM_THREADS / 64;               // rows of one workgroup of the w pass: one per wave
-constexpr int MM_MAX_CHUNKS = EFFQ_EDT_MM_MAX_EXTENT / 64;
+constexpr int MM_ROWS = MM_THREADS / 64;               // waves of a workgroup of the scan
 constexpr int MM_SCAN_BLOCKS = 1024;                   // blocks of the scans = per-block partials of the fp64 sums
 constexpr int MM_BINS = 256;                           // 8 bits of the pattern per stage of the select
 constexpr int MM_STAGES = 4;
@@ -67,94 +65,6 @@ static MmWs mm_ws(void* ws, int P, int D, int H, int W) {
   r.red.part = reinterpret_cast<double*>(p + off); off += (size_t)MM_SCAN_BLOCKS * 2 * MM_CLASSES * sizeof(double);
   r.bytes = off;
   return r;
-}
-
-// ---- rows -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MM_THREADS) void k_mm_rows(EdtSrc src, float* __restrict__ sq, int S, int W, int nrows,
-                                                        float ww) {
-  __shared__ int s_next[MM_ROWS][MM_MAX_CHUNKS];       // the first site after chunk k of the wave's row, -1: none
-  const int plane = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x * MM_ROWS + wave;
-  const bool live = row < nrows;
-  const int base = live ? row * W : 0;
-  const int nchunks = (W + 63) / 64;
-  int next = -1;
-  for (int k = nchunks - 1; k >= 0; --k) {
-    if (lane == 0) s_next[wave][k] = next;
-    const int w = k * 64 + lane;
-    const unsigned long long bal = __ballot(live && w < W && edt_site(src, plane, S, base + w));
-    if (bal) next = k * 64 + __builtin_ctzll(bal);
-  }
-  __syncthreads();
-  if (!live) return;
-  float* out = sq + (size_t)plane * S + base;
-  int last = -1;
-  for (int k = 0; k < nchunks; ++k) {
-    const int w = k * 64 + lane;
-    const unsigned long long bal = __ballot(w < W && edt_site(src, plane, S, base + w));
-    const unsigned long long le = bal & (~0ull >> (63 - lane)), ge = bal & (~0ull << lane);
-    const int lpos = le ? k * 64 + 63 - __builtin_clzll(le) : last;
-    const int rpos = ge ? k * 64 + __builtin_ctzll(ge) : s_next[wave][k];
-    int dist = -1;
-    if (lpos >= 0) dist = w - lpos;
-    if (rpos >= 0 && (dist < 0 || rpos - w < dist)) dist = rpos - w;
-    if (w < W) out[w] = dist < 0 ? INFINITY : ww * (float)(dist * dist);       // dist^2 < 2^24: exact as a float
-    if (bal) last = k * 64 + 63 - __builtin_clzll(bal);
-  }
-}
-
-// ---- lines ----------------------------------------------------------------------------------------------------------
-// Line (o, w) of a plane holds the n voxels o * ostride + i * stride + w, as in seg_surface.hip.  tw = 1 << ltw lines
-// adjacent along w make the slab of a workgroup; dynamic LDS: (n + 2) * tw words.
-__global__ __launch_bounds__(MM_THREADS) void k_mm_lines(float* __restrict__ sq, int S, int W, int n, int stride,
-                                                         int ostride, int ltw, int ntw, float wa) {
-  extern __shared__ float s_g[];
-  const int tw = 1 << ltw, rows = MM_THREADS >> ltw;
-  int* s_lo = reinterpret_cast<int*>(s_g + n * tw);
-  int* s_hi = s_lo + tw;
-  const int lw = threadIdx.x & (tw - 1), r = threadIdx.x >> ltw;
-  const int o = blockIdx.x / ntw, w = (blockIdx.x % ntw) * tw + lw;
-  const bool live = w < W;
-  float* line = sq + (size_t)blockIdx.y * S + (size_t)o * ostride + (live ? w : 0);
-  if (threadIdx.x < tw) {
-    s_lo[threadIdx.x] = n;
-    s_hi[threadIdx.x] = -1;
-  }
-  __syncthreads();
-  int lo = n, hi = -1;
-  for (int i = r; i < n; i += rows) {
-    const float g = live ? line[(size_t)i * stride] : INFINITY;
-    s_g[i * tw + lw] = g;
-    if (g < INFINITY) {
-      lo = min(lo, i);
-      hi = i;
-    }
-  }
-  if (hi >= 0) {
-    atomicMin(&s_lo[lw], lo);
-    atomicMax(&s_hi[lw], hi);
-  }
-  __syncthreads();
-  lo = s_lo[lw];
-  hi = s_hi[lw];
-  if (!live || hi < 0) return;                         // a line without a finite entry stays as it is
-  for (int i = r; i < n; i += rows) {
-    float best = s_g[i * tw + lw];
-    for (int j = min(i - 1, hi); j >= lo; --j) {
-      const float c = wa * (float)((i - j) * (i - j));
-      if (c >= best) break;
-      const float cand = s_g[j * tw + lw] + c;
-      best = cand < best ? cand : best;
-    }
-    for (int j = max(i + 1, lo); j <= hi; ++j) {
-      const float c = wa * (float)((j - i) * (j - i));
-      if (c >= best) break;
-      const float cand = s_g[j * tw + lw] + c;
-      best = cand < best ? cand : best;
-    }
-    line[(size_t)i * stride] = best;
-  }
 }
 
 // ---- reduce ---------------------------------------------------------------------------------------------------------
@@ -374,31 +284,6 @@ static bool mm_dims_ok(int P, int D, int H, int W) {
 
 static bool mm_weight_ok(float w) { return std::isfinite(w) && w > 0.0f; }
 
-static int mm_line_pass(float* sq, int P, int S, int W, int n, int stride, int nouter, int ostride, float wa,
-                        hipStream_t st) {
-  if (n == 1) return EFFQ_OK;                          // min over one entry: fl(g + 0) = g
-  int ltw = 6;
-  while (ltw > 0 && (size_t)(n + 2) * sizeof(float) << ltw > (size_t)EDT_LDS_AIM) --ltw;
-  const int tw = 1 << ltw, ntw = (W + tw - 1) / tw;
-  const size_t lds = (size_t)(n + 2) * sizeof(float) << ltw;
-  hipLaunchKernelGGL(k_mm_lines, dim3((unsigned)((size_t)nouter * ntw), P), dim3(MM_THREADS), lds, st, sq, S, W, n,
-                     stride, ostride, ltw, ntw, wa);
-  EFFQ_LAUNCH_CHECK();
-  return EFFQ_OK;
-}
-
-// the three passes of P planes into sq (P, S): w, then h, then d
-static int mm_run(const EdtSrc& src, int P, int D, int H, int W, float wd, float wh, float ww, float* sq,
-                  hipStream_t st) {
-  const int S = D * H * W, nrows = D * H;
-  hipLaunchKernelGGL(k_mm_rows, dim3((nrows + MM_ROWS - 1) / MM_ROWS, P), dim3(MM_THREADS), 0, st, src, sq, S, W, nrows,
-                     ww);
-  EFFQ_LAUNCH_CHECK();
-  const int rc = mm_line_pass(sq, P, S, W, H, W, D, H * W, wh, st);
-  if (rc != EFFQ_OK) return rc;
-  return mm_line_pass(sq, P, S, W, D, H * W, H, W, wd, st);
-}
-
 template <int C>
 static void launch_scan(dim3 g, hipStream_t st, const uint16_t* surf, const float* sq, int S, const MmRed& r) {
   hipLaunchKernelGGL((k_mm_scan<C>), g, dim3(MM_THREADS), 0, st, surf, sq, S, r);
@@ -422,7 +307,7 @@ int effq_edt_sq_mm(const uint8_t* masks, int P, int D, int H, int W, float wd, f
   EFFQ_CHECK_ARG(ws_bytes >= mm_ws(ws, P, D, H, W).bytes);
   EdtSrc src;
   src.masks = masks; src.surf = nullptr; src.C = 0;
-  return mm_run(src, P, D, H, W, wd, wh, ww, sq, as_stream(stream));
+  return edt_run<EdtMm>(src, P, D, H, W, wd, wh, ww, sq, as_stream(stream));
 }
 
 int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
@@ -446,7 +331,7 @@ int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D,
   EFFQ_LAUNCH_CHECK();
   EdtSrc src;
   src.masks = nullptr; src.surf = s.surf; src.C = C;
-  rc = mm_run(src, P, D, H, W, wd, wh, ww, s.sq, st);
+  rc = edt_run<EdtMm>(src, P, D, H, W, wd, wh, ww, s.sq, st);
   if (rc != EFFQ_OK) return rc;
   const dim3 g(cc_grid(S, MM_SCAN_BLOCKS)), t(MM_THREADS);
   switch (C) {

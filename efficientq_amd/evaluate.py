@@ -145,6 +145,25 @@ def metrics_from_counts(counts: torch.Tensor) -> dict:
             "acc": (tp + tn).float() / n}
 
 
+def _surface_rows(rows, diag: float) -> torch.Tensor:
+    """hd, hd95, assd per class (C x 3 float64) from one (n_p, n_l, max_sq, qlo_sq, qhi_sq, sum_pl, sum_lp) per class -
+    the two surface counts, the largest squared distance, the two pooled order statistics squared and the two directed
+    sums - and the diagonal that stands for a distance to an empty surface: the formulas of surface_metrics."""
+    out = torch.zeros(len(rows), 3, dtype=torch.float64)
+    for c, (n_p, n_l, max_sq, qlo, qhi, sum_pl, sum_lp) in enumerate(rows):
+        if n_p == 0 and n_l == 0:
+            continue
+        if n_p == 0 or n_l == 0:
+            out[c] = diag
+            continue
+        r = 95 * (n_p + n_l - 1) % 100
+        lo, hi = math.sqrt(qlo), math.sqrt(qhi)
+        out[c, 0] = math.sqrt(max_sq)
+        out[c, 1] = lo + (hi - lo) * r / 100
+        out[c, 2] = (sum_pl / n_p + sum_lp / n_l) / 2
+    return out
+
+
 def surface_metrics(counts, sums, shape) -> torch.Tensor:
     """hd, hd95, assd per class (C x 3 float64, voxel units) of one case of extent `shape` = (D, H, W) from what
     hip_ops.seg_surface returns: counts C x 6 = nP, nL, maxsq_PL, maxsq_LP, qlo_sq, qhi_sq and sums C x 2.  With the
@@ -156,19 +175,9 @@ def surface_metrics(counts, sums, shape) -> torch.Tensor:
     counts = torch.as_tensor(counts).to("cpu", torch.int64)
     sums = torch.as_tensor(sums).to("cpu", torch.float64)
     diag = math.sqrt(sum(int(e) ** 2 for e in shape))
-    out = torch.zeros(counts.shape[0], 3, dtype=torch.float64)
-    for c, ((n_p, n_l, max_pl, max_lp, qlo, qhi), (sum_pl, sum_lp)) in enumerate(zip(counts.tolist(), sums.tolist())):
-        if n_p == 0 and n_l == 0:
-            continue
-        if n_p == 0 or n_l == 0:
-            out[c] = diag
-            continue
-        r = 95 * (n_p + n_l - 1) % 100
-        lo, hi = math.sqrt(qlo), math.sqrt(qhi)
-        out[c, 0] = math.sqrt(max(max_pl, max_lp))
-        out[c, 1] = lo + (hi - lo) * r / 100
-        out[c, 2] = (sum_pl / n_p + sum_lp / n_l) / 2
-    return out
+    rows = [(n_p, n_l, max(max_pl, max_lp), qlo, qhi, *s)                   # the squares stay Python ints: sqrt is exact
+            for (n_p, n_l, max_pl, max_lp, qlo, qhi), s in zip(counts.tolist(), sums.tolist())]
+    return _surface_rows(rows, diag)
 
 
 def surface_metrics_mm(counts, sq, sums, shape, spacing) -> torch.Tensor:
@@ -181,20 +190,9 @@ def surface_metrics_mm(counts, sq, sums, shape, spacing) -> torch.Tensor:
     sq = torch.as_tensor(sq).to("cpu", torch.float64)
     sums = torch.as_tensor(sums).to("cpu", torch.float64)
     diag = math.sqrt(sum((int(e) * float(s)) ** 2 for e, s in zip(shape, spacing)))
-    out = torch.zeros(counts.shape[0], 3, dtype=torch.float64)
-    for c, ((n_p, n_l), (max_pl, max_lp, qlo, qhi), (sum_pl, sum_lp)) in enumerate(
-            zip(counts.tolist(), sq.tolist(), sums.tolist())):
-        if n_p == 0 and n_l == 0:
-            continue
-        if n_p == 0 or n_l == 0:
-            out[c] = diag
-            continue
-        r = 95 * (n_p + n_l - 1) % 100
-        lo, hi = math.sqrt(qlo), math.sqrt(qhi)
-        out[c, 0] = math.sqrt(max(max_pl, max_lp))
-        out[c, 1] = lo + (hi - lo) * r / 100
-        out[c, 2] = (sum_pl / n_p + sum_lp / n_l) / 2
-    return out
+    rows = [(*n, max(max_pl, max_lp), qlo, qhi, *s)
+            for n, (max_pl, max_lp, qlo, qhi), s in zip(counts.tolist(), sq.tolist(), sums.tolist())]
+    return _surface_rows(rows, diag)
 
 
 def _case_geometry(geometry, i):

@@ -1075,12 +1075,15 @@ class HipOps:
         self._sig_thresh = float(-torch.tensor([lo], dtype=torch.int32).view(torch.float32).item())
         return self._sig_thresh
 
-    def seg_tallies(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
-        """TP, FP, FN, TN per class (C x 4 int64) of one case's stitched logits (C x D x H x W) against its label
-        (effq_seg_tallies): lits = argmax over the channels vs class ids (D x H x W); brats = sigmoid >= 0.5 per channel,
-        merged by `fuse` (None / 'agg' / 'con'), vs a C x D x H x W 0/1 label."""
+    def _seg_case(self, what: str, logits: torch.Tensor, label: torch.Tensor, task: str, fuse, spatial: bool):
+        """The arguments of one case that seg_tallies, seg_lesions, seg_surface and seg_surface_mm share, checked:
+        returns (x, lab, Cc, extents, mode, fuse code, thresh) - the fp32 logits, the contiguous label, the class count,
+        (D, H, W) when `spatial` requires C x D x H x W logits and the voxel count S otherwise, and the decision."""
         x = self._f32(logits)
-        Cc, S = int(x.shape[0]), x[0].numel()
+        if spatial and x.dim() != 4:
+            raise _lib.EffqError(f"{what}: expected C x D x H x W logits, got {tuple(x.shape)}")
+        Cc = int(x.shape[0])
+        extents = tuple(int(i) for i in x.shape[1:]) if spatial else x[0].numel()
         if task == "lits":
             mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
         elif task == "brats":
@@ -1089,17 +1092,35 @@ class HipOps:
             raise _lib.EffqError(f"Unknown task {task}")
         key = fuse.lower() if isinstance(fuse, str) else fuse
         if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
-            raise _lib.EffqError(f"seg_tallies: merge type {fuse!r} for task {task}")
+            raise _lib.EffqError(f"{what}: merge type {fuse!r} for task {task}")
         if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_tallies: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+            raise _lib.EffqError(f"{what}: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
         if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
-            raise _lib.EffqError(f"seg_tallies: label {tuple(label.shape)} {label.dtype} on {label.device}, "
+            raise _lib.EffqError(f"{what}: label {tuple(label.shape)} {label.dtype} on {label.device}, "
                                  f"needs {lshape} torch.uint8 on {x.device}")
-        lab = label.contiguous()
+        return x, label.contiguous(), Cc, extents, mode, _lib.SEG_FUSE[key], thresh
+
+    def _mask_planes(self, what: str, mask: torch.Tensor):
+        """(m, P, D, H, W) of the masks cc_label, edt_sq and edt_sq_mm take: D x H x W or P x D x H x W uint8, not empty,
+        on the device of the ops; m is contiguous."""
+        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
+            raise _lib.EffqError(f"{what}: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
+        if mask.device != self.device and not (mask.device.type == "cuda" and
+                                               self.device.index in (None, mask.device.index)):
+            raise _lib.EffqError(f"{what}: mask on {mask.device}, ops on {self.device}")
+        m = mask.contiguous()
+        D, H, W = (int(i) for i in m.shape[-3:])
+        return m, (int(m.shape[0]) if m.dim() == 4 else 1), D, H, W
+
+    def seg_tallies(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
+        """TP, FP, FN, TN per class (C x 4 int64) of one case's stitched logits (C x D x H x W) against its label
+        (effq_seg_tallies): lits = argmax over the channels vs class ids (D x H x W); brats = sigmoid >= 0.5 per channel,
+        merged by `fuse` (None / 'agg' / 'con'), vs a C x D x H x W 0/1 label."""
+        x, lab, Cc, S, mode, fcode, thresh = self._seg_case("seg_tallies", logits, label, task, fuse, False)
         counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
         ws = self._workspace("seg_tallies", _lib.SEG_TALLIES_WS_BYTES)
-        check(self.lib.effq_seg_tallies(_ptr(x), _ptr(lab), Cc, S, mode, _lib.SEG_FUSE[key], thresh, _ptr(counts),
-                                        _ptr(ws), ws.numel(), self.stream), "effq_seg_tallies")
+        check(self.lib.effq_seg_tallies(_ptr(x), _ptr(lab), Cc, S, mode, fcode, thresh, _ptr(counts), _ptr(ws), ws.numel(),
+                                        self.stream), "effq_seg_tallies")
         return counts
 
     def seg_labels(self, logits: torch.Tensor, rule: str, fuse: Optional[str] = None, dtype=torch.uint8):
@@ -1137,16 +1158,9 @@ class HipOps:
         or P x D x H x W uint8, non-zero = foreground.  Returns (labels, ncomp): int32 labels of the mask's shape, 0 for
         background and 1 + the least linear index of the voxel's component otherwise, and the int64 component count of
         each mask.  connectivity 26 (3 x 3 x 3 neighbourhood) or 6 (faces)."""
-        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
-            raise _lib.EffqError(f"cc_label: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
-        if mask.device != self.device and not (mask.device.type == "cuda" and
-                                               self.device.index in (None, mask.device.index)):
-            raise _lib.EffqError(f"cc_label: mask on {mask.device}, ops on {self.device}")
+        m, P, D, H, W = self._mask_planes("cc_label", mask)
         if connectivity not in (6, 26):
             raise _lib.EffqError(f"cc_label: connectivity {connectivity}, 6 or 26")
-        m = mask.contiguous()
-        D, H, W = (int(i) for i in m.shape[-3:])
-        P = int(m.shape[0]) if m.dim() == 4 else 1
         if P > 65535 or m.numel() >= 2 ** 31:
             raise _lib.EffqError(f"cc_label: {P} masks of {D * H * W} voxels (at most 65535 masks, 2^31 - 1 voxels in all)")
         labels = torch.empty(m.shape, dtype=torch.int32, device=self.device)
@@ -1161,32 +1175,13 @@ class HipOps:
         the predicted mask, label components without a predicted voxel, predicted components without a labelled voxel;
         metrics.py:69-94 with the 3 x 3 x 3 neighbourhood) from its stitched logits (C x D x H x W) and its label
         (effq_seg_lesions).  Arguments and decisions as seg_tallies."""
-        x = self._f32(logits)
-        if x.dim() != 4:
-            raise _lib.EffqError(f"seg_lesions: expected C x D x H x W logits, got {tuple(x.shape)}")
-        Cc, D, H, W = (int(i) for i in x.shape)
-        if task == "lits":
-            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
-        elif task == "brats":
-            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
-        else:
-            raise _lib.EffqError(f"Unknown task {task}")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
-            raise _lib.EffqError(f"seg_lesions: merge type {fuse!r} for task {task}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_lesions: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
-            raise _lib.EffqError(f"seg_lesions: label {tuple(label.shape)} {label.dtype} on {label.device}, "
-                                 f"needs {lshape} torch.uint8 on {x.device}")
+        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_lesions", logits, label, task, fuse, True)
         if D * H * W == 0 or 2 * Cc * D * H * W >= 2 ** 31:
             raise _lib.EffqError(f"seg_lesions: {2 * Cc} masks of {D * H * W} voxels (2^31 - 1 voxels in all at most)")
-        lab = label.contiguous()
         counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
         ws = self._workspace("cc", self.lib.effq_cc_ws_bytes(2 * Cc, D, H, W))
-        check(self.lib.effq_seg_lesions(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh,
-                                        _lib.LESION_CONNECTIVITY, _ptr(counts), _ptr(ws), ws.numel(), self.stream),
-              "effq_seg_lesions")
+        check(self.lib.effq_seg_lesions(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, _lib.LESION_CONNECTIVITY,
+                                        _ptr(counts), _ptr(ws), ws.numel(), self.stream), "effq_seg_lesions")
         return counts
 
     def edt_sq(self, mask: torch.Tensor):
@@ -1194,14 +1189,7 @@ class HipOps:
         site.  Returns an int32 tensor of the mask's shape: the squared distance (voxel units) of every voxel to the
         nearest site of its own volume, 0 on a site, INT32_MAX throughout a volume without sites.  It is
         rint(scipy.ndimage.distance_transform_edt(mask == 0) ** 2), voxel for voxel."""
-        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
-            raise _lib.EffqError(f"edt_sq: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
-        if mask.device != self.device and not (mask.device.type == "cuda" and
-                                               self.device.index in (None, mask.device.index)):
-            raise _lib.EffqError(f"edt_sq: mask on {mask.device}, ops on {self.device}")
-        m = mask.contiguous()
-        D, H, W = (int(i) for i in m.shape[-3:])
-        P = int(m.shape[0]) if m.dim() == 4 else 1
+        m, P, D, H, W = self._mask_planes("edt_sq", mask)
         need = self.lib.effq_surf_ws_bytes(P, D, H, W)
         if need == 0:
             raise _lib.EffqError(f"edt_sq: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels in "
@@ -1216,34 +1204,16 @@ class HipOps:
         its label, arguments and decisions as seg_tallies.  Returns (counts, sums): counts C x 6 int64 = nP, nL,
         maxsq_PL, maxsq_LP, qlo_sq, qhi_sq and sums C x 2 float64 = the sums of the directed distances
         (include/effq_hip.h); evaluate.surface_metrics turns them into hd, hd95 and assd."""
-        x = self._f32(logits)
-        if x.dim() != 4:
-            raise _lib.EffqError(f"seg_surface: expected C x D x H x W logits, got {tuple(x.shape)}")
-        Cc, D, H, W = (int(i) for i in x.shape)
-        if task == "lits":
-            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
-        elif task == "brats":
-            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
-        else:
-            raise _lib.EffqError(f"Unknown task {task}")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
-            raise _lib.EffqError(f"seg_surface: merge type {fuse!r} for task {task}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_surface: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
-            raise _lib.EffqError(f"seg_surface: label {tuple(label.shape)} {label.dtype} on {label.device}, "
-                                 f"needs {lshape} torch.uint8 on {x.device}")
+        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_surface", logits, label, task, fuse, True)
         need = self.lib.effq_surf_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
         if need == 0:
             raise _lib.EffqError(f"seg_surface: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
                                  f"most, D^2 + H^2 + W^2 < 2^31, D and H at most {_lib.EDT_MAX_LINE})")
-        lab = label.contiguous()
         counts = torch.empty(Cc, 6, dtype=torch.int64, device=self.device)
         sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
         ws = self._workspace("surf", need)
-        check(self.lib.effq_seg_surface(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh, _ptr(counts),
-                                        _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface")
+        check(self.lib.effq_seg_surface(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, _ptr(counts), _ptr(sums),
+                                        _ptr(ws), ws.numel(), self.stream), "effq_seg_surface")
         return counts, sums
 
     @staticmethod
@@ -1267,15 +1237,8 @@ class HipOps:
         P x D x H x W uint8, non-zero = site.  Returns a float32 tensor of the mask's shape: for every voxel the least
         fl(fl(fl(ww dw^2) + fl(wh dh^2)) + fl(wd dd^2)) over the sites of its own volume, wa = float32(spacing_a ** 2) -
         the bits of the brute force in fp32 -, 0 on a site, +inf throughout a volume without sites."""
-        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
-            raise _lib.EffqError(f"edt_sq_mm: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
-        if mask.device != self.device and not (mask.device.type == "cuda" and
-                                               self.device.index in (None, mask.device.index)):
-            raise _lib.EffqError(f"edt_sq_mm: mask on {mask.device}, ops on {self.device}")
+        m, P, D, H, W = self._mask_planes("edt_sq_mm", mask)
         wd, wh, ww = self._axis_weights("edt_sq_mm", spacing)
-        m = mask.contiguous()
-        D, H, W = (int(i) for i in m.shape[-3:])
-        P = int(m.shape[0]) if m.dim() == 4 else 1
         need = self.lib.effq_surf_mm_ws_bytes(P, D, H, W)
         if need == 0:
             raise _lib.EffqError(f"edt_sq_mm: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels "
@@ -1293,37 +1256,19 @@ class HipOps:
         Returns (counts, sq, sums): counts C x 2 int64 = nP, nL, sq C x 4 float32 = max_PL, max_LP, qlo, qhi (squared
         distances in mm^2) and sums C x 2 float64 = the sums of the directed distances in mm (include/effq_hip.h);
         evaluate.surface_metrics_mm turns them into hd, hd95 and assd."""
-        x = self._f32(logits)
-        if x.dim() != 4:
-            raise _lib.EffqError(f"seg_surface_mm: expected C x D x H x W logits, got {tuple(x.shape)}")
-        Cc, D, H, W = (int(i) for i in x.shape)
-        if task == "lits":
-            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
-        elif task == "brats":
-            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
-        else:
-            raise _lib.EffqError(f"Unknown task {task}")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
-            raise _lib.EffqError(f"seg_surface_mm: merge type {fuse!r} for task {task}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_surface_mm: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
-            raise _lib.EffqError(f"seg_surface_mm: label {tuple(label.shape)} {label.dtype} on {label.device}, "
-                                 f"needs {lshape} torch.uint8 on {x.device}")
+        case = self._seg_case("seg_surface_mm", logits, label, task, fuse, True)
+        x, lab, Cc, (D, H, W), mode, fcode, thresh = case
         wd, wh, ww = self._axis_weights("seg_surface_mm", spacing)
         need = self.lib.effq_surf_mm_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
         if need == 0:
             raise _lib.EffqError(f"seg_surface_mm: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
                                  f"most, every extent at most {_lib.EDT_MM_MAX_EXTENT})")
-        lab = label.contiguous()
         counts = torch.empty(Cc, 2, dtype=torch.int64, device=self.device)
         sq = torch.empty(Cc, 4, dtype=torch.float32, device=self.device)
         sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
         ws = self._workspace("surf_mm", need)
-        check(self.lib.effq_seg_surface_mm(_ptr(x), _ptr(lab), Cc, D, H, W, mode, _lib.SEG_FUSE[key], thresh, wd, wh, ww,
-                                           _ptr(counts), _ptr(sq), _ptr(sums), _ptr(ws), ws.numel(), self.stream),
-              "effq_seg_surface_mm")
+        check(self.lib.effq_seg_surface_mm(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, wd, wh, ww, _ptr(counts),
+                                           _ptr(sq), _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface_mm")
         return counts, sq, sums
 
 

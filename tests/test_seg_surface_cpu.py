@@ -269,8 +269,13 @@ def test_surface_kernels_take_their_decisions_from_the_shared_header():
     assert "void decide(" not in open(os.path.join(csrc, "seg_masks.h")).read()
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "seg_surface.hip" in mk and "seg_masks.h" in mk
-    assert not re.search(r"\b(float|double)\b", text[text.index("// ---- rows"):text.index("// ---- reduce")]), \
-        "no float enters the squared distance map"
+    # the passes live in seg_surf.h, written over a metric: the integer file takes EdtVox only, and neither EdtVox nor
+    # the shared passes name a floating type
+    shared = open(os.path.join(csrc, "seg_surf.h")).read()
+    assert "edt_run<EdtVox>" in text and "EdtMm" not in text and "seg_surf.h" in mk
+    vox = shared[shared.index("struct EdtVox"):shared.index("struct EdtMm")]
+    for part in (vox[:vox.rindex("};")], shared[shared.index("// ---- rows"):]):
+        assert not re.search(r"\b(float|double)\b", part), "no float enters the squared distance map"
 
 
 # ---- metrics.csv --------------------------------------------------------------------------------------------------
