@@ -190,6 +190,9 @@ SIGNATURES = {
     "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "effq_seg_lesions": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _SZ, _P]),
+    "effq_cc_table_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "effq_cc_table": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "effq_seg_lesion_table": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "effq_surf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_edt_sq": (_I, [_P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_seg_surface": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
@@ -207,6 +210,10 @@ SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}
 # the neighbourhood of the lesion metrics: the full 3 x 3 x 3, the 3-D counterpart of metrics.py's np.ones((3, 3))
 LESION_CONNECTIVITY = 26
+# include/effq_hip.h (EFFQ_CC_TABLE_CHUNK): the voxels of one chunk of the rank scan of effq_cc_table
+CC_TABLE_CHUNK = 2048
+# rows per plane that cc_table / seg_lesion_table ask for first; a plane with more components costs one more call
+LESION_TABLE_ROWS = 4096
 # include/effq_hip.h: the longest line of the h and d passes of the distance transform
 EDT_MAX_LINE = 16382
 # include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)

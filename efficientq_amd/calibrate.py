@@ -314,6 +314,8 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     cc = {'is_cc': True} if getattr(args, 'is_cc', False) else {}
     if getattr(args, 'surf_dist', False):
         cc['is_surf'] = True
+    if getattr(args, 'lesion_table', False):
+        cc['is_table'] = True
     if args.test_fp:
         tester.test_as_is(folder='fp', is_save_nii=args.save_nii, **cc)
 

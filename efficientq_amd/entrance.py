@@ -10,6 +10,8 @@ the calibrated network on the val split (evaluate.validate_seg), writing ``<snap
 ``--save_nii`` adds the predicted label maps ``<snap>/{fp,ptq}/val/<subject>.nii.gz`` and ``<snap>/{Q,FP}seg<i>.nii.gz``;
 ``--is_cc`` adds the lesion-level columns ``totall, predl, fnl, fpl`` (connected components) to ``metrics.csv``;
 ``--surf_dist`` adds the surface distances ``hd, hd95, assd`` (voxel units) after them;
+``--lesion_table`` writes ``<snap>/{fp,ptq}/lesions.csv``, one row per label lesion and per predicted lesion (first
+voxel, size, overlap; ``vol_mm3`` with ``--src_geom`` / ``--spacing``), and prints the detected lesions per size bin;
 ``--src_geom`` reads every val subject's source image header (``data_dir/sn_fn.txt``, data.py): the distances become
 ``hd_mm, hd95_mm, assd_mm`` in millimetres and the val maps are written on the source grid with the source's geometry;
 ``--spacing d,h,w`` gives the distances in millimetres from one spacing for all subjects, without any file.
@@ -56,24 +58,24 @@ class _ValidationTester(_SnapshotWriter):
     """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
     <root>/<folder>/metrics.csv, with is_save_nii also every val subject's predicted map as
     <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns, with is_surf also the
-    surface distances."""
+    surface distances, with is_table also <root>/<folder>/lesions.csv."""
 
     def __init__(self, model, root, data_cube, task, rank=0):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
 
-    def _geometry(self, is_save_nii, is_surf):
-        """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances
-        and maps), or the one spacing of --spacing (distances only)."""
+    def _geometry(self, is_save_nii, is_surf, is_table=False):
+        """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances,
+        lesion volumes and maps), or the one spacing of --spacing (distances and lesion volumes only)."""
         geom = getattr(self.cube, 'geometry', None)
-        if geom is not None and (is_save_nii or is_surf):
+        if geom is not None and (is_save_nii or is_surf or is_table):
             return {'geometry': geom}
         spacing = getattr(self.cube, 'spacing', None)
-        if spacing is not None and is_surf:
+        if spacing is not None and (is_surf or is_table):
             return {'geometry': spacing}
         return {}
 
-    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False):
+    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False, is_table=False):
         if self.rank != 0:
             return
         if self.cube.valloader is None:
@@ -85,9 +87,12 @@ class _ValidationTester(_SnapshotWriter):
                              fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
                              save_dir=os.path.join(out, 'val') if is_save_nii else None,
                              multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
-                             surface=is_surf, **self._geometry(is_save_nii, is_surf))
+                             surface=is_surf, **({'lesion_table': True} if is_table else {}),
+                             **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
+        if is_table:
+            E.write_lesions_csv(os.path.join(out, 'lesions.csv'), res)
         means = E.metric_means(res)
         print(f'[entrance] {folder}: {len(res)} val cases in {time.time() - t0:.2f}s, per-class means:')
         tot = E.lesion_totals(res) if is_cc else None
@@ -100,6 +105,12 @@ class _ValidationTester(_SnapshotWriter):
                 mm = ' mm' if res[0].get('surface_unit') == 'mm' else ''
                 line += ', ' + ', '.join(f'{k} = {float(surf[c][j]):.3f}{mm}' for j, k in enumerate(E.SURFACE_COLUMNS))
             print(line)
+        if is_table:
+            bins = E.lesion_size_summary(res)
+            names = [f'{lo}-{hi}' if hi is not None else f'>= {lo}' for lo, hi in E.LESION_SIZE_BINS]
+            print(f'[entrance] {folder}: label lesions detected / all, by size in voxels:')
+            for c in range(bins.shape[0]):
+                print(f'  class {c}: ' + ', '.join(f'{n}: {int(k[1])} / {int(k[0])}' for n, k in zip(names, bins[c])))
 
 
 class _SyntheticCube:

@@ -129,6 +129,8 @@ METRICS = ("dsc", "sens", "spec", "acc")
 WINDOW_BATCH_MAX = 16     # windows per forward at most (a BraTS case has 8 of 128^3)
 EPS = 1e-6                # metrics.py
 LESION_COLUMNS = ("totall", "predl", "fnl", "fpl")     # the columns of "lesions" (hip_ops.seg_lesions)
+LESION_TABLE_COLUMNS = ("d", "h", "w", "size", "overlap")   # the columns of "lesion_table" (hip_ops.seg_lesion_table)
+LESION_SIZE_BINS = ((1, 9), (10, 99), (100, 999), (1000, None))    # lesion_size_summary: voxels, both ends included
 SURFACE_COLUMNS = ("hd", "hd95", "assd")               # the columns of "surface" (surface_metrics), voxel units
 SURFACE_COLUMNS_MM = ("hd_mm", "hd95_mm", "assd_mm")   # the same in millimetres (surface_metrics_mm)
 
@@ -205,6 +207,13 @@ def _case_geometry(geometry, i):
     return tuple(float(v) for v in geometry[i]["spacing"]), geometry[i]
 
 
+def _lesion_rows(rows, shape) -> np.ndarray:
+    """n x 3 rows (first voxel as a linear index, size, overlap) -> n x 5 int64: d, h, w, size, overlap."""
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    d, h, w = np.unravel_index(r[:, 0], tuple(int(e) for e in shape))
+    return np.stack([d, h, w, r[:, 1], r[:, 2]], axis=1).astype(np.int64)
+
+
 def _last_head(out) -> torch.Tensor:
     """The last head of a model output: a list of heads, heads stacked in front (UResQ), or one N x C x ... tensor."""
     if isinstance(out, (list, tuple)):
@@ -243,7 +252,7 @@ def _write_map(path, host, dtype, entry=None):
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
-                 geometry=None):
+                 geometry=None, lesion_table=False):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -268,7 +277,12 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     case's entry with the header of its source image also puts its map on the source grid: restored into the source
     shape and written with the source's affine, codes and pixdim (a RuntimeError naming the case when the maps are the
     C x D x H x W planes of --multi_label lits, which have no place on a source grid).  Counts and metrics stay those of
-    the given grid."""
+    the given grid.
+    lesion_table: each dict also carries "lesion_table", per class a pair (label lesions, predicted lesions) of int64
+    arrays n x LESION_TABLE_COLUMNS = first voxel as d, h, w, size in voxels, overlap (the voxels the other mask of the
+    class holds too; 0 = a missed / an invented lesion), in raster order of the first voxel (effq_seg_lesion_table: the
+    launches of the lesion counts and four more), and with a geometry "spacing", the (d, h, w) mm of the case.  With
+    lesions=True as well "lesions" comes from the same call: the case is labelled once."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -330,10 +344,20 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                 i = len(results)
                 res = {"name": names[i] if names is not None else str(i), "counts": counts}
                 res.update(metrics_from_counts(counts))
-                if lesions:
+                spacing, entry = _case_geometry(geometry, i) if geometry is not None else (None, None)
+                if lesion_table:
+                    cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], "brats" if multi else "lits",
+                                                        fuse if multi else None)
+                    ncls = int(cnt.shape[0])
+                    res["lesion_table"] = [(_lesion_rows(rows[ncls + c], vol.shape[-3:]),
+                                            _lesion_rows(rows[c], vol.shape[-3:])) for c in range(ncls)]
+                    if spacing is not None:
+                        res["spacing"] = spacing
+                    if lesions:
+                        res["lesions"] = cnt
+                elif lesions:
                     res["lesions"] = ops.seg_lesions(stitched[n], lab[n], "brats" if multi else "lits",
                                                      fuse if multi else None).cpu()
-                spacing, entry = _case_geometry(geometry, i) if geometry is not None else (None, None)
                 if surface and spacing is None:
                     sc, ss = ops.seg_surface(stitched[n], lab[n], "brats" if multi else "lits",
                                              fuse if multi else None)
@@ -382,6 +406,45 @@ def write_metrics_csv(path: str, results) -> None:
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
                             [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []) +
                             (["%.7g" % float(v) for v in r["surface"][c]] if sd else []))
+
+
+def write_lesions_csv(path: str, results) -> None:
+    """One row per lesion of results that carry "lesion_table" (validate_seg(..., lesion_table=True)): subject, class,
+    kind (label | pred), lesion (1-based, in raster order of the first voxel: scipy.ndimage.label's number), d, h, w of
+    the first voxel, size in voxels, overlap; per subject and class the label lesions first.  When the results carry a
+    "spacing" a last column vol_mm3 = size x voxel volume; a file never mixes rows with and without it."""
+    import csv
+    res = [r for r in results if "lesion_table" in r]
+    mm = {"spacing" in r for r in res}
+    if len(mm) > 1:
+        raise RuntimeError("write_lesions_csv: cases with and without a spacing in one file")
+    mm = mm == {True}
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(("subject", "class", "kind", "lesion") + LESION_TABLE_COLUMNS + (("vol_mm3",) if mm else ()))
+        for r in res:
+            vox = float(np.prod([float(v) for v in r["spacing"]])) if mm else None
+            for c, pair in enumerate(r["lesion_table"]):
+                for kind, rows in zip(("label", "pred"), pair):
+                    for k, row in enumerate(np.asarray(rows, dtype=np.int64).reshape(-1, 5)):
+                        wr.writerow([r["name"], c, kind, k + 1] + [int(v) for v in row] +
+                                    (["%.7g" % (int(row[3]) * vox)] if mm else []))
+
+
+def lesion_size_summary(results) -> np.ndarray:
+    """The label lesions of results that carry "lesion_table" per class and size bin (LESION_SIZE_BINS: 1-9, 10-99,
+    100-999, >= 1000 voxels): C x 4 x 2 int64 = the lesions of the bin over all cases, and how many of them were
+    detected (overlap > 0)."""
+    res = [r for r in results if "lesion_table" in r]
+    out = np.zeros((max((len(r["lesion_table"]) for r in res), default=0), len(LESION_SIZE_BINS), 2), np.int64)
+    for r in res:
+        for c, (label_rows, _) in enumerate(r["lesion_table"]):
+            rows = np.asarray(label_rows, dtype=np.int64).reshape(-1, 5)
+            for b, (lo, hi) in enumerate(LESION_SIZE_BINS):
+                sel = (rows[:, 3] >= lo) & ((rows[:, 3] <= hi) if hi is not None else True)
+                out[c, b, 0] += int(sel.sum())
+                out[c, b, 1] += int((sel & (rows[:, 4] > 0)).sum())
+    return out
 
 
 def metric_means(results) -> dict:

@@ -1184,6 +1184,69 @@ class HipOps:
                                         _ptr(counts), _ptr(ws), ws.numel(), self.stream), "effq_seg_lesions")
         return counts
 
+    def _table_call(self, what: str, P: int, head: int, width: int, max_rows, call):
+        """The calls of cc_table and seg_lesion_table: one int32 buffer holds `head` int64 words (the counts), the P
+        int64 row counts and the P x capacity x width table, so one copy brings all of it to the host.  `call(cap, head
+        pointer, nrows pointer, rows pointer)` launches.  A plane with more components than the capacity: once more with
+        the capacity the row counts give.  Returns (head int64, nrows int64 (P), [rows of plane p, int32 n_p x width]),
+        all on the host."""
+        cap = _lib.LESION_TABLE_ROWS if max_rows is None else int(max_rows)
+        if cap <= 0:
+            raise _lib.EffqError(f"{what}: max_rows {max_rows}, needs a positive capacity")
+        while True:
+            if P * cap * width >= 2 ** 31:
+                raise _lib.EffqError(f"{what}: a table of {P} x {cap} rows")
+            front = 2 * (head + P)
+            buf = torch.empty(front + P * cap * width, dtype=torch.int32, device=self.device)
+            base = buf.data_ptr()
+            call(cap, C.c_void_p(base), C.c_void_p(base + 8 * head), C.c_void_p(base + 4 * front))
+            host = buf.cpu()
+            words = host[:front].view(torch.int64)
+            nrows = words[head:]
+            most = int(nrows.max())
+            if most <= cap:
+                table = host[front:].view(P, cap, width)
+                return words[:head], nrows, [table[q, :int(nrows[q])] for q in range(P)]
+            cap = most
+
+    def cc_table(self, mask: torch.Tensor, connectivity: int = 26, max_rows: Optional[int] = None):
+        """One record per connected component of 0/1 volumes (effq_cc_table; scipy.ndimage.label + numpy.bincount):
+        `mask` as cc_label.  Returns (rows, nrows) on the host: int32 rows n x 2 = first voxel (linear index), size in
+        voxels, in ascending order of the first voxel (row k is scipy's component k + 1) - one tensor for a D x H x W
+        mask, a list of P for P x D x H x W - and the int64 component count(s).  max_rows: the rows per mask asked for
+        first (default _lib.LESION_TABLE_ROWS); a mask with more components costs one more call, all rows are returned."""
+        m, P, D, H, W = self._mask_planes("cc_table", mask)
+        if connectivity not in (6, 26):
+            raise _lib.EffqError(f"cc_table: connectivity {connectivity}, 6 or 26")
+        if P > 65535 or m.numel() >= 2 ** 31:
+            raise _lib.EffqError(f"cc_table: {P} masks of {D * H * W} voxels (at most 65535 masks, 2^31 - 1 voxels in all)")
+
+        def call(cap, _head, nrows, rows):
+            ws = self._workspace("cc", self.lib.effq_cc_table_ws_bytes(P, D, H, W, cap))
+            check(self.lib.effq_cc_table(_ptr(m), P, D, H, W, int(connectivity), cap, rows, nrows, _ptr(ws), ws.numel(),
+                                         self.stream), "effq_cc_table")
+        _, nrows, rows = self._table_call("cc_table", P, 0, 2, max_rows, call)
+        return (rows, nrows) if m.dim() == 4 else (rows[0], nrows[0])
+
+    def seg_lesion_table(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None,
+                         max_rows: Optional[int] = None):
+        """The lesions of one case one by one (effq_seg_lesion_table), arguments and decisions as seg_lesions.  Returns
+        (counts, nrows, rows) on the host: counts C x 4 int64, bit for bit seg_lesions'; nrows (2 C) int64, the components
+        of plane q - the predicted mask of class q for q < C, the label mask of class q - C otherwise; rows, a list of
+        2 C int32 tensors n_q x 3 = first voxel (linear index), size, overlap (the voxels that the other mask of the
+        class holds too), in ascending order of the first voxel.  max_rows as cc_table."""
+        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_lesion_table", logits, label, task, fuse, True)
+        if D * H * W == 0 or 2 * Cc * D * H * W >= 2 ** 31:
+            raise _lib.EffqError(f"seg_lesion_table: {2 * Cc} masks of {D * H * W} voxels (2^31 - 1 voxels in all at most)")
+
+        def call(cap, counts, nrows, rows):
+            ws = self._workspace("cc", self.lib.effq_cc_table_ws_bytes(2 * Cc, D, H, W, cap))
+            check(self.lib.effq_seg_lesion_table(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh,
+                                                 _lib.LESION_CONNECTIVITY, cap, counts, nrows, rows, _ptr(ws), ws.numel(),
+                                                 self.stream), "effq_seg_lesion_table")
+        counts, nrows, rows = self._table_call("seg_lesion_table", 2 * Cc, 4 * Cc, 3, max_rows, call)
+        return counts.view(Cc, 4), nrows, rows
+
     def edt_sq(self, mask: torch.Tensor):
         """Exact squared Euclidean distance transform (effq_edt_sq): `mask` D x H x W or P x D x H x W uint8, non-zero =
         site.  Returns an int32 tensor of the mask's shape: the squared distance (voxel units) of every voxel to the

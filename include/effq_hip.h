@@ -620,6 +620,37 @@ int effq_cc_label(const uint8_t* masks, int P, int D, int H, int W, int connecti
 int effq_seg_lesions(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
                      float thresh, int connectivity, long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- one record per connected component (validate_seg(..., lesion_table=True): which lesions were missed or invented,
+ * and how big; the reference carries sizeL / sizeP, utils/metrics.py:48-52, but only ever sums them over a mask).  After
+ * the five launches of effq_cc_label (seven of effq_seg_lesions) four more, on the same labels: the roots of every chunk
+ * of EFFQ_CC_TABLE_CHUNK consecutive voxels are counted, the chunk counts of each plane are scanned, every chunk is
+ * walked again to give its roots their rows, and every foreground voxel adds itself to its component's row (equal rows
+ * of a wave combined, the sums of a workgroup kept in LDS).  All on `stream`, no read by the host and no workgroup that
+ * waits for another; integer adds only, so equal inputs give equal bits.
+ *
+ * Order: row k of a plane is the component whose first voxel (least linear index d*H*W + h*W + w) is the k-th smallest -
+ *   component k + 1 of scipy.ndimage.label.
+ * effq_cc_table: masks as effq_cc_label -> rows (P, max_rows, 2) int32 = first voxel, size (voxels); nrows (P) = the
+ *   number of components of each mask.
+ * effq_seg_lesion_table: arguments as effq_seg_lesions -> counts (C, 4), bit for bit effq_seg_lesions'; nrows (2 C) and
+ *   rows (2 C, max_rows, 3) int32 = first voxel, size, overlap.  Plane q < C is the predicted mask of class q, plane
+ *   C + q its label mask; overlap = the voxels of the component that the other mask of its class holds too (0: a false
+ *   positive lesion in a predicted plane, a missed lesion in a label plane).
+ * Truncation: nrows is always the true count.  Of a plane with nrows > max_rows the first max_rows rows are written,
+ *   complete; of a plane with fewer, rows nrows .. max_rows - 1 are left as they were.  Nothing is written past the table.
+ * ws: effq_cc_table_ws_bytes(P, D, H, W, max_rows) bytes, P = 2 C for effq_seg_lesion_table: effq_cc_ws_bytes(P, D, H, W)
+ *   (effq_cc_table keeps its labels there) and one counter per plane and chunk - 105 KB more for a BraTS case; nothing
+ *   grows with max_rows today.  0 for dimensions out of range or max_rows <= 0.  Bad arguments (a null pointer,
+ *   max_rows <= 0, a connectivity other than 6 or 26, dimensions out of range) return EFFQ_ERR_ARG, a short workspace
+ *   EFFQ_ERR_WORKSPACE; both launch nothing. */
+#define EFFQ_CC_TABLE_CHUNK 2048
+size_t effq_cc_table_ws_bytes(int P, int D, int H, int W, int max_rows);
+int effq_cc_table(const uint8_t* masks, int P, int D, int H, int W, int connectivity, int max_rows, int32_t* rows,
+                  long long* nrows, void* ws, size_t ws_bytes, void* stream);
+int effq_seg_lesion_table(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                          float thresh, int connectivity, int max_rows, long long* counts, long long* nrows,
+                          int32_t* rows, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- exact Euclidean distance transform of 3-D masks and the surface-distance columns of the validation
  * (validate_seg(..., surface=True): hd, hd95, assd per class; the reference has no counterpart, the definitions are
  * DESIGN section 13's).  Voxel units.  Separable and in integers throughout, so the squared distances are exact: along

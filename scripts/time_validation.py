@@ -14,7 +14,12 @@ without surface=True, and with scipy the host way on the same masks (copy + two 
 distance_transform_edt per class).
 --surf-dist --spacing d,h,w times effq_seg_surface_mm (the same distances in millimetres on a grid of that spacing: the
 weighted transform and the radix select) the same way, next to the integer path measured in the same run, and
-validate_seg per case with geometry=spacing."""
+validate_seg per case with geometry=spacing.
+--lesion-table adds effq_seg_lesion_table (one record per lesion: the launches of --is-cc and four more) on the net's own
+logits and on random logits, called as the library is (a table of 2^18 rows per plane, no host read), next to
+effq_seg_lesions in the same run, validate_seg per case with lesion_table=True, and with scipy the host way on the same
+masks (copy + ndimage.label + numpy.bincount of both masks of each class).  The time per phase is read from a kernel
+trace (rocprofv3 --kernel-trace --stats -- python scripts/time_validation.py --lesion-table)."""
 import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +30,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--save-nii", dest="save_nii", action="store_true", help="also time the NIfTI label maps")
 ap.add_argument("--is-cc", dest="is_cc", action="store_true", help="also time the lesion-level counts")
 ap.add_argument("--surf-dist", dest="surf_dist", action="store_true", help="also time the surface distances")
+ap.add_argument("--lesion-table", dest="lesion_table", action="store_true", help="also time the per-lesion table")
 ap.add_argument("--spacing", default=None, help="d,h,w in mm: with --surf-dist also time the distances in mm")
 cli = ap.parse_args()
 REPS = int(os.environ.get("REPS", "5"))
@@ -176,6 +182,74 @@ if cli.is_cc:
             ms.append((time.perf_counter() - t0) * 1e3)
         res["scipy_label_ms"] = round(sorted(ms)[1], 1)
         res["scipy_over_kernel"] = round(res["scipy_label_ms"] / res["lesions"]["ms"], 1)
+if cli.lesion_table:
+    import ctypes as C
+    from efficientq_amd import _lib
+    with torch.no_grad():
+        out = E._last_head(model(from_ndhwc(win)))
+    net_logits = ops.window_stitch(out.permute(0, 2, 3, 4, 1).contiguous(), (1, 3) + shape, p, o)
+    planes, cap = 6, 1 << 18
+    counts = torch.empty(3, 4, dtype=torch.int64, device=dev)
+    nrows = torch.empty(planes, dtype=torch.int64, device=dev)
+    rows = torch.empty(planes, cap, 3, dtype=torch.int32, device=dev)
+    need = ops.lib.effq_cc_table_ws_bytes(planes, *shape, cap)
+    ws = ops._workspace("cc", need)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    thresh = ops.sigmoid_threshold()
+
+    def table(lg):
+        _lib.check(ops.lib.effq_seg_lesion_table(ptr(lg), ptr(lab8), 3, *shape, _lib.SEG_SIGMOID, _lib.SEG_FUSE["agg"],
+                                                 thresh, _lib.LESION_CONNECTIVITY, cap, ptr(counts), ptr(nrows), ptr(rows),
+                                                 ptr(ws), ws.numel(), ops.stream), "effq_seg_lesion_table")
+    for key, lg in (("lesion_table", net_logits[0].contiguous()), ("lesion_table_random_logits", stitched[0].contiguous())):
+        ms = timed(lambda: table(lg))
+        ms_cc = timed(lambda: ops.seg_lesions(lg, lab8, "brats", "agg"))
+        n = nrows.tolist()
+        sizes = [rows[q, :min(n[q], cap), 1] for q in range(planes)]
+        res[key] = {"ms": round(ms, 4), "lesions_ms": round(ms_cc, 4), "nrows": n,
+                    "largest": [int(s.max()) if s.numel() else 0 for s in sizes],
+                    "counts_equal": bool(torch.equal(counts, ops.seg_lesions(lg, lab8, "brats", "agg")))}
+    res["cc_table_ws_MB"] = round(need / 1e6, 1)
+    res["cc_ws_MB"] = round(ops.lib.effq_cc_ws_bytes(planes, *shape) / 1e6, 1)
+
+    def wall_table(**kw):
+        ms = []
+        for i in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            E.validate_seg(model, loader * 3, "brats", p, o, window_batch=nwin, fuse="agg", **kw)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3 / 3)
+        return round(sorted(ms[1:])[1], 2)
+    res["validate_ms_per_case"] = wall_table()
+    res["validate_lesions_ms_per_case"] = wall_table(lesions=True)
+    res["validate_lesion_table_ms_per_case"] = wall_table(lesions=True, lesion_table=True)
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    res["scipy"] = ndimage is not None
+    if ndimage is not None:
+        import numpy as np
+        pred = ops.seg_labels(net_logits, "planes", "agg")[0]
+
+        def host_way():
+            pm, gm = pred.cpu().numpy(), lab8.cpu().numpy()
+            out = []
+            for c in range(3):
+                for m, other in ((gm[c], pm[c]), (pm[c], gm[c])):
+                    lab, n = ndimage.label(m, np.ones((3, 3, 3)))
+                    out.append((np.bincount(lab.reshape(-1), minlength=n + 1)[1:],
+                                np.bincount(lab.reshape(-1)[other.reshape(-1) != 0], minlength=n + 1)[1:]))
+            return out
+        ms = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host_way()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        res["scipy_table_ms"] = round(min(ms), 1)
+        res["scipy_over_kernel"] = round(res["scipy_table_ms"] / res["lesion_table"]["ms"], 1)
 if cli.surf_dist:
     with torch.no_grad():
         out = E._last_head(model(from_ndhwc(win)))
