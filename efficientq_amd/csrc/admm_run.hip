@@ -389,26 +389,23 @@ static FpKind fp_kind(const AdmmPlan& p, bool use_traj) {
 // Bm (the first solve of the layer builds Bm itself: bias column, padding).  *bm_ready: Bm holds it.
 static int enqueue_fixed_point(const effq_admm_run_args* a, const AdmmPlan& p, const AdmmIter& it, bool* bm_ready) {
   const int nwrow = p.n - p.has_b;
-  const uintptr_t al16 = reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->wstar) |
-                         reinterpret_cast<uintptr_t>(it.G) | reinterpret_cast<uintptr_t>(a->dual) |
-                         (it.next_rhs ? (reinterpret_cast<uintptr_t>(a->W0) | reinterpret_cast<uintptr_t>(p.bm)) : 0);
-  const bool vec_ok = (al16 & 15) == 0 && (reinterpret_cast<uintptr_t>(it.Gq) & 3) == 0 && (p.nw % 4) == 0 &&
-                      (!it.next_rhs || ((nwrow % 4) == 0 && (p.bm_ld % 4) == 0));
+  ProjNext nx;                     // zero (Bm == NULL) on the last iteration
+  memset(&nx, 0, sizeof(nx));
+  if (it.next_rhs) nx = ProjNext{p.bm, a->B0, a->W0, nwrow, p.n, p.bm_ld, (float)it.rho_next, (float)a->eta};
+  const ProjNext* nxp = it.next_rhs ? &nx : nullptr;
   const FpKind kind = fp_kind(p, it.use_traj);
   // The projection as the EPILOGUE of a single-workgroup fixed point: one launch per iteration less.  Measured (us per
   // iteration, fused against fixed point + projection): 2048 weights 13.8 against 12.2 + 7.1, 3456 at 256 levels 231.8
-  // against 229.3 + 8.3 - but 27648 weights on the bucketed kernel 56.3 against 33.6 + 7.1: only the 256 threads of its
-  // iteration phase are left for the epilogue.  So: the small kernel's layers (<= 32768 weights), and the channel kernel.
-  const bool fuse_proj = kind == FpKind::channels || (kind == FpKind::small && vec_ok);
+  // against 229.3 + 8.3.  So: the small kernel's layers (<= 32768 weights), and the channel kernel.  (The bucketed kernel
+  // has only the 256 threads of its iteration phase left for an epilogue: slower, DESIGN.md.)
+  const bool fuse_proj = kind == FpKind::channels ||
+                         (kind == FpKind::small && proj_vec_ok(a->v, a->wstar, it.G, a->dual, it.Gq, p.nw, nxp));
   ProjFused pf;                    // (the small kernel's epilogue)
   memset(&pf, 0, sizeof(pf));
   pf.wstar = a->wstar; pf.G = it.G; pf.dual = a->dual; pf.Gq = it.Gq; pf.err_flag = a->err_flag;
   pf.d = 2.0 / (double)(a->w_levels - 1); pf.dual_div = it.dual_div; pf.lm1 = a->w_levels - 1;
   pf.n4 = (unsigned)(p.nw / 4);
-  if (it.next_rhs) {
-    pf.nx.Bm = p.bm; pf.nx.B0 = a->B0; pf.nx.W0 = a->W0; pf.nx.nwrow = nwrow; pf.nx.n = p.n; pf.nx.ldb = p.bm_ld;
-    pf.nx.rho = (float)it.rho_next; pf.nx.eta = (float)a->eta;
-  }
+  pf.nx = nx;
   void* rec = p.traj ? a->fp_pred : nullptr;
   const int maxit = 100 * a->w_levels;
   ProfScope p_fp(it.prof, PROF_FIXED_POINT, it.i, a, p.s_main);
@@ -440,12 +437,8 @@ static int enqueue_fixed_point(const effq_admm_run_args* a, const AdmmPlan& p, c
   *bm_ready = it.next_rhs;
   if (fuse_proj) return EFFQ_OK;
   ProfScope p_pr(it.prof, PROF_PROJECT, it.i, a, p.s_main);
-  if (it.next_rhs)
-    rc = effq_project_dual_next(a->v, a->wstar, it.st, a->w_levels, it.G, a->dual, it.dual_div, it.Gq, p.nw, a->err_flag,
-                                p.bm, a->B0, a->W0, nwrow, p.n, p.bm_ld, it.rho_next, a->eta, p.s_main);
-  else
-    rc = effq_project_dual_checked(a->v, a->wstar, it.st, a->w_levels, it.G, a->dual, it.dual_div, it.Gq, p.nw,
-                                   a->err_flag, p.s_main);
+  rc = effq_project_dual_impl(a->v, a->wstar, it.st, a->w_levels, it.G, a->dual, it.dual_div, it.Gq, p.nw, a->err_flag,
+                              nxp, p.s_main);
   if (rc != EFFQ_OK) return rc;
   p_pr.close();
   return EFFQ_OK;

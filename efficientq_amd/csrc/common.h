@@ -84,6 +84,15 @@ static inline RedWs red_ws(void* ws) {
   return r;
 }
 
+// The streaming kernels (quant_reduce.hip, project_dual.hip): TPB threads, grid-stride over at most RED_MAX_BLOCKS blocks.
+constexpr int TPB = 256;
+static inline int stream_grid(size_t n_vec) {
+  size_t b = (n_vec + TPB - 1) / TPB;
+  if (b < 1) b = 1;
+  if (b > RED_MAX_BLOCKS) b = RED_MAX_BLOCKS;
+  return (int)b;
+}
+
 #ifdef __HIPCC__
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a fence + barrier and the fence waits for
 // vmcnt(0): every global load in flight - i.e. the register prefetch of the NEXT tile - is drained at each barrier

@@ -22,7 +22,6 @@
 // atomics (k_fpg_sum / k_fpg_count / k_fpg_scan / k_fpg_scatter_iter), the last workgroup to finish regrouping iterates.
 #include "common.h"
 #include "fp_level.h"
-#include "project_dual.h"
 
 namespace effq {
 
@@ -109,8 +108,7 @@ struct TabSeg {
 template <typename Tab>
 __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, const Tab& tab, const FpbGeo& g, size_t n,
                                             double tot_abs, double lo, double hi, double d, int levels, double tol,
-                                            int max_iter, FpbShared& sh, effq_fp_state* st, FptPred* pred = nullptr,
-                                            double* alpha_out = nullptr, int* done_out = nullptr) {
+                                            int max_iter, FpbShared& sh, effq_fp_state* st, FptPred* pred = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nthr = levels - 1;                 // level boundaries k = 1 .. L-1
   int p2 = 1;
@@ -261,8 +259,6 @@ __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, cons
     last1 = t1;
   }
   if (tid == 0) fp_state_finish(st, pred, alpha, alpha_prev, last0, last1, it, done, tot_abs, levels);
-  if (alpha_out != nullptr) *alpha_out = alpha;      // (every thread of the iteration phase holds the same values)
-  if (done_out != nullptr) *done_out = done;
 }
 
 // ---- path S: one workgroup, everything in LDS ---------------------------------------------------------------------------
@@ -273,7 +269,7 @@ constexpr int FPS2_MAXN = 32768;
 template <int PER>   // register slots per thread (values stay in registers through the three build passes)
 __global__ __launch_bounds__(FPS2_T) void k_fps(const float* __restrict__ a, const float* b2, float* v_out, size_t n,
                                                 effq_fp_state* st, double lo, double hi, double d, int levels, double tol,
-                                                int max_iter, FptPred* pred, ProjFused pf) {
+                                                int max_iter, FptPred* pred) {
   __builtin_amdgcn_s_setprio(3);        // latency-bound, shares its CU with loss-conv waves
 
   constexpr int B = FPS2_B;
@@ -454,12 +450,7 @@ __global__ __launch_bounds__(FPS2_T) void k_fps(const float* __restrict__ a, con
   FPB_TRACE(5);
   if (tid >= FPB_TI) return;                    // the barriers below only count the surviving waves
   TabFlat tab{off, spre};
-  double alpha_fin = 0.0;
-  int done_fin = 0;
-  fpb_iterate(vals, tab, g, n, tot, lo, hi, d, levels, tol, max_iter, sh, st, pred, &alpha_fin, &done_fin);
-  // the projection + dual update of this ADMM iteration as the epilogue of the same launch (the FPB_TI surviving threads;
-  // v_out was stored before the build passes' barriers)
-  if (pf.G != nullptr) proj_fused_epilogue(pf, v_out, alpha_fin, done_fin, tid, FPB_TI);
+  fpb_iterate(vals, tab, g, n, tot, lo, hi, d, levels, tol, max_iter, sh, st, pred);
 }
 
 // ---- path G: large tensors, four launches ------------------------------------------------------------------------------------
@@ -797,8 +788,6 @@ int effq_fixed_point_bucket_rec(const float* a, const float* b, float* v_out, si
                                 double tol, int max_iter, effq_fp_state* state_dev, void* ws, size_t ws_bytes,
                                 void* pred_dev, void* stream) {
   FptPred* pred = reinterpret_cast<FptPred*>(pred_dev);
-  ProjFused pf;                  // k_fps's projection epilogue stays off (measured slower, admm_run.hip)
-  memset(&pf, 0, sizeof(pf));
   EFFQ_CHECK_ARG(a && state_dev && n > 0 && levels >= 2 && levels <= 256 && hi > lo && max_iter > 0);
   EFFQ_CHECK_ARG(n <= effq_fp_bucket_max());
   EFFQ_CHECK_ARG(b == nullptr || v_out != nullptr);
@@ -836,11 +825,11 @@ int effq_fixed_point_bucket_rec(const float* a, const float* b, float* v_out, si
   const size_t lds = fps_lds_bytes(n);
   const int per = (int)((n + FPS2_T - 1) / FPS2_T);
   if (per <= 8)
-    hipLaunchKernelGGL(k_fps<8>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred, pf);
+    hipLaunchKernelGGL(k_fps<8>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred);
   else if (per <= 16)
-    hipLaunchKernelGGL(k_fps<16>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred, pf);
+    hipLaunchKernelGGL(k_fps<16>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred);
   else
-    hipLaunchKernelGGL(k_fps<32>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred, pf);
+    hipLaunchKernelGGL(k_fps<32>, dim3(1), dim3(FPS2_T), lds, st, a, b, v_out, n, state_dev, lo, hi, d, levels, tol, max_iter, pred);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

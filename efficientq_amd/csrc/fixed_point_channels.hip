@@ -7,7 +7,7 @@
 // a <- sum b v_c / sum b b until |a - a_prev| <= tol or max_iter iterations.  A row with sum|v_c| = 0 has no scale (the
 // formula divides by zero): it is defined as a = 0, 0 iterations, converged, G_c = 0.
 //
-// Arithmetic as in k_fp_small (quant_reduce.hip): the level index from the fp32 screen with the reference's fp64
+// Arithmetic as in k_fp_small (fixed_point_values.hip): the level index from the fp32 screen with the reference's fp64
 // arithmetic near a rounding boundary, sum b v = d sum(r v) + lo sum(v), sum b^2 = d^2 sum(r^2) + 2 d lo sum(r) + lo^2 n
 // with integer sum(r), sum(r^2); wave sums through the DPP tree with whole waves (absent elements hold 0), waves added in
 // wave order: a fixed reduction order, no atomics - two launches give the same bits.

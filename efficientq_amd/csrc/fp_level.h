@@ -1,7 +1,7 @@
 // The quantiser arithmetic every fixed-point family must agree on bit for bit: the level index of the reference
 // (layer_helper.py:25-37 evaluated in fp64) with its fp32 screen, the scale sums from integer level tallies, the stop
 // rule of project_by_iter (layer_helper.py:55-64) and the final state store.  The kernels (quant_reduce.hip,
-// project_dual.h, fixed_point_{bucket,bracket,channels}.hip, fp_traj.h) keep their own loops and reductions around them.
+// project_dual.{h,hip}, fixed_point_{values,bucket,bracket,channels}.hip, fp_traj.h) keep their own loops and reductions around them.
 #pragma once
 #include <math.h>
 #include "common.h"
@@ -13,6 +13,12 @@ __device__ __forceinline__ double level_exact(double x, double a, double lo, dou
   double t = x / a;
   t = fmin(fmax(t, lo), hi);
   return rint((t - lo) / d);
+}
+// discretize (layer_helper.py:25-37) in fp64: the exact level and its value r d + lo
+__device__ __forceinline__ double disc64(double x, double alpha, double lo, double hi, double d, double* idx) {
+  const double r = level_exact(x, alpha, lo, hi, d);
+  *idx = r;
+  return r * d + lo;
 }
 // (not inlined: the fallback of the screen is taken for ~4 values in 10 000, and its two IEEE divisions are ~100
 // instructions that would otherwise be copied into every unrolled call site)

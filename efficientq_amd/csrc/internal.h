@@ -6,23 +6,21 @@
 
 namespace effq {
 struct ProjFused;   // project_dual.h
+struct ProjNext;
 }
 
 extern "C" {
 
-// quant_reduce.hip: effq_fixed_point_small with pf != NULL running the projection of the ADMM iteration as the epilogue
+// fixed_point_values.hip: effq_fixed_point_small with pf != NULL running the projection of the ADMM iteration as the
+// epilogue
 int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, size_t n, int levels, double lo, double hi,
                                  double tol, int max_iter, effq_fp_state* state_dev, const effq::ProjFused* pf_in,
                                  void* stream);
-// quant_reduce.hip: effq_admm_project_dual with the convergence check of state_dev folded in (err_flag_dev) ...
-int effq_project_dual_checked(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
-                              float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
-                              void* stream);
-// ... and also leaving the right-hand side of the next prox solve in Bm
-int effq_project_dual_next(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
-                           float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev, float* Bm,
-                           const float* B0, const float* W0, int nwrow, int nb0, int ldb, double rho_next, double eta,
-                           void* stream);
+// project_dual.hip: effq_admm_project_dual with the convergence check of state_dev folded in (err_flag_dev) and, with
+// nx != NULL, also leaving the right-hand side of the next prox solve in nx->Bm
+int effq_project_dual_impl(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
+                           float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
+                           const effq::ProjNext* nx, void* stream);
 
 // solve.hip: Bm (the start of the prox workspace) and its row length; the prox solve on a Bm already written, whole or
 // as the slices of its product (*part_out != NULL)

@@ -1,6 +1,7 @@
 // The projection + dual update of an ADMM iteration (EfficientQConv.py:108-111, 129-137) as device code shared by the
-// stand-alone kernels (quant_reduce.hip) and by the single-workgroup fixed points that run it as their epilogue
-// (k_fp_small, k_fps: one launch per iteration less on the layers whose weights fit one workgroup).
+// stand-alone kernels (project_dual.hip), by the single-workgroup fixed point that runs it as its epilogue (k_fp_small,
+// fixed_point_values.hip: one launch per iteration less on the layers whose weights fit one workgroup) and, element by
+// element, by the per-channel fixed point (fixed_point_channels.hip).
 #pragma once
 #include "common.h"
 #include "fp_level.h"
@@ -17,6 +18,16 @@ struct ProjNext {
   int nwrow, n, ldb;       // weights per output channel, row length of B0, row length of Bm
   float rho, eta;
 };
+
+// Host side: whether the projection of n weights may take the 16-byte path (proj4_apply: k_project_dual4 and the epilogue
+// of k_fp_small).  nx == NULL: no next right-hand side.  (With one, nwrow % 4 == 0 also keeps a group of 4 inside a row.)
+static inline bool proj_vec_ok(const float* v, const float* wstar, const float* G, const float* dual, const int8_t* Gq,
+                               size_t n, const ProjNext* nx) {
+  const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if (((addr(v) | addr(wstar) | addr(G) | addr(dual)) & 15) != 0 || (addr(Gq) & 3) != 0) return false;
+  if ((n % 4) != 0 || n >= ((size_t)1 << 32)) return false;
+  return nx == nullptr || ((nx->nwrow % 4) == 0 && (nx->ldb % 4) == 0 && ((addr(nx->W0) | addr(nx->Bm)) & 15) == 0);
+}
 
 // Four consecutive weights: 16-byte accesses, one (row, column) split with 32-bit arithmetic, and the level index from
 // the screen of fp_level.h (levels on [-1, 1]).

@@ -432,3 +432,73 @@ def test_fused_admm_iterates_equal_the_step_by_step_ops(ops, c1, c2, variant):
     assert torch.equal(_bits(run.wstar), _bits(wstar.view(-1))), "last prox solve, weight columns"
     assert torch.equal(_bits(run.dual), _bits(dual.view(-1))), "final dual"
     assert len(inverses) == n_inv
+
+
+@pytest.mark.parametrize("c1,c2,k,shape,fused", [(32, 32, 1, (2, 32, 4, 4, 8), True), (1, 8, 3, (2, 1, 6, 6, 8), False)],
+                         ids=["small-kernel-epilogue", "scalar-projection-next-rhs"])
+def test_fused_admm_projection_paths_equal_the_step_by_step_ops(ops, c1, c2, k, shape, fused):
+    """The construction, schedule and equalities of test_fused_admm_iterates_equal_the_step_by_step_ops on the two ways
+    through the projection that its layers do not take; both layers have nw <= 4096, where effq_admm_run takes the
+    single-workgroup all-values fixed point, and the step-by-step loop takes the same kernel (weight_fixed_point).
+
+    small-kernel-epilogue: rows of 32 weights and 16-byte aligned ring slots - the run does the projection, the dual update
+    and the next right-hand side inside the fixed-point kernel; the loop with the stand-alone vector kernel.
+    scalar-projection-next-rhs: rows of 27 weights - nothing is fused, the run's projection is the element-by-element kernel
+    (level index from the fp64 arithmetic) and writes Bm one float at a time; the loop's is the vector kernel on 216 aligned
+    weights (level index from the fp32 screen)."""
+    from efficientq_amd.hip_ops import make_geom, to_ndhwc
+    nwrow = c1 * k ** 3
+    nw = c2 * nwrow
+    assert nw <= 4096 and nw % 4 == 0 and (nwrow % 4 == 0) == fused
+    gen = torch.Generator().manual_seed(c1 + 3 * c2)
+    x = torch.relu(torch.randn(*shape, generator=gen))
+    w = torch.randn(c2, c1, k, k, k, generator=gen) * 0.1
+    b = torch.randn(c2, generator=gen) * 0.1
+    y = F.conv3d(x, w, b, padding=k // 2)
+    geom = make_geom(x.shape, c2, k, 1, k // 2)
+    xq, yn = dev(to_ndhwc(x)), dev(to_ndhwc(y))
+    W0, b0 = dev(w.reshape(c2, nwrow).contiguous()), dev(b)       # (c1 = 1 or k = 1: every row order is this one)
+    A0, B0 = ops.gram(xq, None, yn, geom, True)
+    scale = max(y.numel() * y.std().item() / (w.numel() * w.std().item()), 1.0)
+    rho, rho_max, eta = 10.0 * scale, 50.0 * scale, 1.0 * scale
+    iters, period, levels = 7, 2, 4
+    sched = _rho_schedule(rho, rho_max, iters, period)
+    assert [d for _, d in sched] == pytest.approx([2.0, 1.0, 2.0, 1.0, 1.25, 1.0, 1.0])
+    n_inv = ops.lib.effq_admm_num_inverses(rho, rho_max, iters, period)
+    assert n_inv == len({r for r, _ in sched}) - 1
+
+    run = ops.admm_run(A0, B0, W0, b0, geom, yn, xq=xq, rho=rho, rho_max=rho_max, eta=eta, iters=iters, period=period,
+                       levels=levels, channel_wise=False)
+    torch.cuda.synchronize()
+    assert int(run.err.item()) == 0
+    assert run.G_ring.data_ptr() % 16 == 0 and run.v.data_ptr() % 16 == 0 and run.dual.data_ptr() % 16 == 0
+
+    G = W0.clone()
+    dual = torch.zeros_like(W0)
+    wstar, v = torch.empty_like(W0), torch.empty_like(W0)
+    bstar = torch.empty(c2, device=DEV)
+    st = ops.new_fp_state()
+    inverses = {}
+    for i, (rho_i, div) in enumerate(sched):
+        rho_use = sched[1][0] if i == 0 else rho_i
+        if rho_use not in inverses:
+            inverses[rho_use] = ops.spd_inverse(A0, True, rho_use, eta)
+        if i == 0:
+            ops.prox_solve_shifted(B0, inverses[rho_use], W0, b0, G, dual, rho_i, eta, rho_use, wstar, bstar)
+        else:
+            ops.prox_solve(B0, inverses[rho_use], W0, b0, G, dual, rho_i, eta, wstar, bstar)
+        ops.weight_fixed_point(wstar.view(-1), dual.view(-1), v.view(-1), levels, st)
+        Gn = torch.empty_like(W0)
+        ops.admm_project_dual(v.view(-1), wstar.view(-1), st, levels, Gn.view(-1), dual.view(-1), div)
+        torch.cuda.synchronize()
+        where = f"iteration {i} (rho {rho_i:g}, dual divisor {div:g})"
+        assert torch.equal(_bits(run.b_ring[i]), _bits(bstar)), \
+            f"{where}: prox solve, bias column differs by {(run.b_ring[i] - bstar).abs().max().item():.3e}"
+        assert run.state_ring[i, 0].item() == st[0].item(), \
+            f"{where}: weight scale {run.state_ring[i, 0].item()!r} != {st[0].item()!r}"
+        diff = (run.G_ring[i].view_as(Gn) - Gn).abs().max().item()
+        assert torch.equal(_bits(run.G_ring[i]), _bits(Gn.view(-1))), f"{where}: projected weights differ by {diff:.3e}"
+        G = Gn
+    assert torch.equal(_bits(run.wstar), _bits(wstar.view(-1))), "last prox solve, weight columns"
+    assert torch.equal(_bits(run.dual), _bits(dual.view(-1))), "final dual"
+    assert len(inverses) == n_inv
