@@ -187,6 +187,7 @@ SIGNATURES = {
     "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
+    "effq_seg_agreement": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "effq_seg_lesions": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _SZ, _P]),
@@ -204,6 +205,8 @@ SIGNATURES = {
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
 SEG_TALLIES_WS_BYTES = 1024 * 3 * 8 * 4
 SEG_TALLIES_MAX_CLASSES = 8
+# include/effq_hip.h: scratch of effq_seg_agreement
+SEG_AGREEMENT_WS_BYTES = 768 * (4 * SEG_TALLIES_MAX_CLASSES * 8 + (3 * SEG_TALLIES_MAX_CLASSES + 1) * 4)
 SEG_ARGMAX, SEG_SIGMOID = 0, 1
 SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 # include/effq_hip.h: the label rules of effq_seg_labels

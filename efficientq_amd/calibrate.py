@@ -10,6 +10,7 @@ snapshots.  Differences, all deliberate and MI355X-first:
 """
 from __future__ import annotations
 
+import copy
 import os
 import os.path as P
 import time
@@ -211,6 +212,11 @@ def center_crop(t: torch.Tensor, size):
     return t[..., x1:x1 + size[0], y1:y1 + size[1], z1:z1 + size[2]]
 
 
+def _crop_label(label, crop):
+    """The label cropped like its image; an unlabelled volume's empty label (--unlabelled) stays as it is."""
+    return label if label.numel() == 0 else center_crop(label, crop)
+
+
 def get_calibration_data(args, data_cube):
     data_cube.trainseqloader.dataset.use_fix_transform()
     it = iter(data_cube.trainseqloader)
@@ -220,13 +226,13 @@ def get_calibration_data(args, data_cube):
         data, label = next(it)
         crop = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else \
             [min(v, 192) // 64 * 64 for v in data.shape[-3:]]
-        return center_crop(data, crop), center_crop(label, crop)
+        return center_crop(data, crop), _crop_label(label, crop)
     crop = [int(v) for v in args.lwq_patchsz.split(',')]
     ds, ls = [], []
     for _ in range(args.lwq_batchsz):
         d, l = next(it)
         ds.append(center_crop(d, crop))
-        ls.append(center_crop(l, crop))
+        ls.append(_crop_label(l, crop))
     return torch.cat(ds, 0), torch.cat(ls, 0)
 
 
@@ -303,6 +309,12 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     model.eval()
     search_fold_and_remove_bn(model)
     model.to(device)
+    # --vs_fp: the network as it is before the calibration rewrites its weights, to validate the calibrated one against
+    fp_model = None
+    if getattr(args, 'vs_fp', False) and not args.no_test:
+        fp_model = copy.deepcopy(model)
+        fp_model.eval()
+        set_fp(fp_model)
 
     data_batch, label_batch = get_calibration_data(args, data_cube)
     data_batch = data_batch.to(device)
@@ -336,7 +348,10 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
         _save_nifti(res, args.task, snap_dir)
 
     if not args.no_test:
+        if fp_model is not None:        # passed only when set: a tester that does not know the keyword keeps working
+            cc['fp_model'] = fp_model
         tester.test_as_is('ptq', args.save_nii, **cc)
+    fp_model = None
     model.cpu()
     tester.snapshot('state_in_fp.pkl', compress=False)
     store_int_weight(model)

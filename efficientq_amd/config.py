@@ -76,6 +76,10 @@ def build_parser():
     p.add_argument('--surf_dist', action='store_true', help='surface distances hd, hd95, assd (voxel units)')
     p.add_argument('--lesion_table', action='store_true',
                    help='one row per lesion (first voxel, size, overlap) in <snap>/{fp,ptq}/lesions.csv')
+    p.add_argument('--vs_fp', action='store_true',
+                   help='validate the calibrated network against the FP network: <snap>/ptq/agreement.csv')
+    p.add_argument('--unlabelled', action='store_true',
+                   help='the data has no seg/ labels: validation against the FP network only (needs --vs_fp)')
     p.add_argument('--src_geom', action='store_true',
                    help="take every val subject's affine, spacing and shape from the image sn_fn.txt names: surface "
                         "distances in mm, label maps on the source grid")
@@ -166,7 +170,7 @@ TINY_NET = dict(task='lits', model='UResQ', nMod=1, nClass=3, multi_label=None, 
 
 def make_args(net: dict, qlvl_w: int, qlvl_a: int, **over):
     base = dict(pretrain=None, resume=None, device=0, round='1', suffix='', config=None, test_fp=False,
-                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, src_geom=False, spacing=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
+                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, vs_fp=False, unlabelled=False, src_geom=False, spacing=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
                 lwq_verbose=False, qlvl_w=qlvl_w, qlvl_a=qlvl_a)
     base.update(net)
     base.update(over)

@@ -1,16 +1,16 @@
 // The per-voxel decisions of the validation kernels: which classes a voxel is predicted as and labelled as.  One
-// definition for the tallies, the label maps (seg_eval.hip) and the lesion counts (seg_cc.hip), so that they cannot
-// disagree about a voxel.
+// definition for the tallies, the label maps (seg_eval.hip), the lesion counts (seg_cc.hip) and the agreement of two
+// networks (seg_agree.hip), so that they cannot disagree about a voxel.
 #pragma once
 #include "common.h"
 
 namespace effq {
 
-// the decisions of one voxel: pred / gt bit c for class c
+// the predicted classes of one voxel from its C logits: bit c for class c (needs no label: seg_agree.hip decides both
+// networks' voxels with it)
 template <int MODE, int C>
-__device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,
-                                       uint32_t& gt) {
-  pred = gt = 0;
+__device__ __forceinline__ uint32_t predict(const float* v, int fuse, float thresh) {
+  uint32_t pred = 0;
   if constexpr (MODE == EFFQ_SEG_ARGMAX) {
     // torch.max over the channels: the first maximum wins, NaN counts as the largest value
     int best = 0;
@@ -24,14 +24,9 @@ __device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int f
       }
     }
     pred = 1u << best;
-    const int l = lab[0];
-    gt = l < C ? (1u << l) : 0u;
   } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-      pred |= (v[c] >= thresh ? 1u : 0u) << c;
-      gt |= (lab[c] != 0 ? 1u : 0u) << c;
-    }
+    for (int c = 0; c < C; ++c) pred |= (v[c] >= thresh ? 1u : 0u) << c;
     if (fuse == EFFQ_SEG_FUSE_AGG) {        // p[i] = any(p[i:])
       uint32_t f = 0, any = 0;
 #pragma unroll
@@ -49,6 +44,22 @@ __device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int f
       }
       pred = f;
     }
+  }
+  return pred;
+}
+
+// the decisions of one voxel: pred / gt bit c for class c
+template <int MODE, int C>
+__device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,
+                                       uint32_t& gt) {
+  pred = predict<MODE, C>(v, fuse, thresh);
+  gt = 0;
+  if constexpr (MODE == EFFQ_SEG_ARGMAX) {
+    const int l = lab[0];
+    gt = l < C ? (1u << l) : 0u;
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) gt |= (lab[c] != 0 ? 1u : 0u) << c;
   }
 }
 

@@ -9,7 +9,8 @@ With ``--src_geom`` two more files of the reference's layout are read (datahub.p
     data_dir/sn_fn.txt                      ``subject,path`` per line: the subject's source NIfTI image
     data_dir/restore_shape_infokw.pickle    optional: {subject: {pmin, pmax, shape}}, how the arrays were cropped
 
-Modalities are flair, t1, t1ce, t2 for brats and ct for lits; the label is the modality ``seg``.  Subjects are
+Modalities are flair, t1, t1ce, t2 for brats and ct for lits; the label is the modality ``seg`` (never opened with
+``--unlabelled``: every subject then carries an empty label).  Subjects are
 taken in sorted order, as the reference's Dataset_SEG loads them.  Images are used as stored: the reference's README
 asks for volumes already standardised to zero mean and unit variance, and no augmentation or random crop is applied.
 The returned cube has the interface ``calibrate.get_calibration_data`` and the validation tester use:
@@ -96,10 +97,12 @@ def array_shape(data_dir: str, modality: str, subject: str, access_type: str) ->
     return tuple(load_array(data_dir, modality, subject, access_type, np.uint8).shape)
 
 
-def read_source_geometry(data_dir: str, subjects: Sequence[str], access_type: str = "npy") -> List[dict]:
+def read_source_geometry(data_dir: str, subjects: Sequence[str], access_type: str = "npy",
+                         modality: str = LABEL_MODALITY) -> List[dict]:
     """One entry per subject for --src_geom: `affine`, `spacing`, `source_shape` and `header` (nifti.read_geometry of the
     image sn_fn.txt names) and, when the subject's array is a crop of it, `pmin` / `pmax`.  Every failure names the
-    subject."""
+    subject.  `modality` is the array whose shape is compared with the source's (an image modality when there are no
+    labels)."""
     from .nifti import read_geometry
     if not P.isfile(P.join(data_dir, SN_FN_FILE)):
         raise RuntimeError(f"--src_geom: {P.join(data_dir, SN_FN_FILE)} is missing (needed for {', '.join(subjects)})")
@@ -115,7 +118,7 @@ def read_source_geometry(data_dir: str, subjects: Sequence[str], access_type: st
             raise RuntimeError(f"--src_geom: subject {sn}: cannot read the geometry of {sn_fn[sn]}: {e}") from e
         src = tuple(hdr["shape"][:3])
         entry = {"affine": hdr["affine"], "spacing": hdr["spacing"], "source_shape": src, "header": hdr}
-        have = array_shape(data_dir, LABEL_MODALITY, sn, access_type)
+        have = array_shape(data_dir, modality, sn, access_type)
         if have != src:
             kw = restore.get(sn)
             ok = kw is not None and tuple(int(n) for n in kw["shape"]) == src and \
@@ -174,14 +177,15 @@ def label_transform(bin_label=None, multi_label=None) -> Optional[Callable]:
 
 
 class SegVolumes(torch.utils.data.Dataset):
-    """(image C x D x H x W float32, label) per subject, read from disk when indexed."""
+    """(image C x D x H x W float32, label) per subject, read from disk when indexed.  labels=False: seg/ is never
+    opened and the label is an empty uint8 tensor (evaluate.validate_seg takes such a case as unlabelled)."""
 
     def __init__(self, data_dir: str, subjects: Sequence[str], modalities: Sequence[str], access_type: str = "npy",
-                 label_fn: Optional[Callable] = None):
+                 label_fn: Optional[Callable] = None, labels: bool = True):
         if access_type not in ACCESS_TYPES:
             raise RuntimeError(f"Unknown access type {access_type} (one of {', '.join(ACCESS_TYPES)})")
         self.data_dir, self.subjects, self.modalities = data_dir, list(subjects), tuple(modalities)
-        self.access_type, self.label_fn = access_type, label_fn
+        self.access_type, self.label_fn, self.labels = access_type, label_fn, labels
 
     def __len__(self):
         return len(self.subjects)
@@ -189,6 +193,8 @@ class SegVolumes(torch.utils.data.Dataset):
     def __getitem__(self, i):
         sn = self.subjects[i]
         img = np.stack([load_array(self.data_dir, m, sn, self.access_type, np.float32) for m in self.modalities])
+        if not self.labels:
+            return torch.from_numpy(img), torch.empty(0, dtype=torch.uint8)
         label = torch.from_numpy(load_array(self.data_dir, LABEL_MODALITY, sn, self.access_type, np.uint8)).long()
         if self.label_fn is not None:
             label = self.label_fn(label)
@@ -200,7 +206,7 @@ class SegVolumes(torch.utils.data.Dataset):
 
 class DataCube:
     def __init__(self, data_dir, split_dir, round_, task, access_type="npy", bin_label=None, multi_label=None,
-                 merge_type=None, patch_size=None, src_geom=False, spacing=None):
+                 merge_type=None, patch_size=None, src_geom=False, spacing=None, labels=True):
         task = task.lower()
         if task not in MODALITIES:
             raise RuntimeError(f"Unknown task: {task}")
@@ -208,10 +214,11 @@ class DataCube:
         self.train_sn = read_split(P.join(split, "train.txt"))
         self.val_sn = read_split(P.join(split, "val.txt")) if P.isfile(P.join(split, "val.txt")) else []
         fn = label_transform(bin_label, multi_label)
-        mk = lambda names: SegVolumes(data_dir, names, MODALITIES[task], access_type, fn)
+        mk = lambda names: SegVolumes(data_dir, names, MODALITIES[task], access_type, fn, labels)
         self.trainseqloader = torch.utils.data.DataLoader(mk(self.train_sn), 1, shuffle=False)
         self.valloader = torch.utils.data.DataLoader(mk(self.val_sn), 1, shuffle=False) if self.val_sn else None
         self.multi_label = multi_label
+        self.labelled = labels
         self.multilabel_fusetype = merge_type
         self.patch_size = parse_patch(patch_size) if patch_size else PATCH_DEFAULT[task]
         self.overlap = OVERLAP_DEFAULT
@@ -220,7 +227,8 @@ class DataCube:
         if src_geom and spacing:
             raise RuntimeError("--src_geom and --spacing exclude each other: the source images carry their own spacing")
         if src_geom:
-            self.geometry = read_source_geometry(data_dir, self.val_sn, access_type)
+            self.geometry = read_source_geometry(data_dir, self.val_sn, access_type,
+                                                 LABEL_MODALITY if labels else MODALITIES[task][0])
         elif spacing:
             self.spacing = parse_spacing(spacing)
 
@@ -234,8 +242,9 @@ def parse_patch(s) -> tuple:
 
 def get_data_cube(args) -> DataCube:
     """The data cube of `args` (--data_dir, --split_dir, --round, --task, --access_type, --bin_label, --multi_label,
-    --merge_type, --patch_size, --src_geom, --spacing)."""
+    --merge_type, --patch_size, --src_geom, --spacing, --unlabelled)."""
     return DataCube(args.data_dir, args.split_dir, args.round, args.task, getattr(args, "access_type", "npy"),
                     getattr(args, "bin_label", None), getattr(args, "multi_label", None),
                     getattr(args, "merge_type", None), getattr(args, "patch_size", None),
-                    getattr(args, "src_geom", False), getattr(args, "spacing", None))
+                    getattr(args, "src_geom", False), getattr(args, "spacing", None),
+                    not getattr(args, "unlabelled", False))

@@ -15,7 +15,14 @@ voxel, size, overlap; ``vol_mm3`` with ``--src_geom`` / ``--spacing``), and prin
 ``--src_geom`` reads every val subject's source image header (``data_dir/sn_fn.txt``, data.py): the distances become
 ``hd_mm, hd95_mm, assd_mm`` in millimetres and the val maps are written on the source grid with the source's geometry;
 ``--spacing d,h,w`` gives the distances in millimetres from one spacing for all subjects, without any file.
-``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing; without
+``--vs_fp`` validates the calibrated network against the network it was calibrated from (a copy taken before the
+calibration): ``<snap>/ptq/agreement.csv`` with, per subject and class, the FP-vs-Q Dice and counts, the share of voxels
+decided differently, the logit drift and the probability drift, the lesion / surface columns of ``--is_cc`` /
+``--surf_dist`` against the FP decisions, and with ``--save_nii`` the map of the differing classes
+``<snap>/ptq/val_vs_fp/<subject>.nii.gz``; it needs no label;
+``--unlabelled`` (with ``--vs_fp``) reads data without a ``seg/`` folder: only the FP-vs-Q validation runs.
+``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing, unless ``--vs_fp``
+is given: then two held-out synthetic volumes are validated against the FP network; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
 the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
 """
@@ -58,7 +65,9 @@ class _ValidationTester(_SnapshotWriter):
     """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
     <root>/<folder>/metrics.csv, with is_save_nii also every val subject's predicted map as
     <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns, with is_surf also the
-    surface distances, with is_table also <root>/<folder>/lesions.csv."""
+    surface distances, with is_table also <root>/<folder>/lesions.csv, with fp_model (--vs_fp) also
+    <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
+    labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written."""
 
     def __init__(self, model, root, data_cube, task, rank=0):
         super().__init__(model, root)
@@ -75,21 +84,33 @@ class _ValidationTester(_SnapshotWriter):
             return {'geometry': spacing}
         return {}
 
-    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False, is_table=False):
+    def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False, is_table=False,
+                   fp_model=None):
         if self.rank != 0:
             return
         if self.cube.valloader is None:
             print('[entrance] no val split: validation skipped')
             return
-        t0 = time.time()
         out = os.path.join(self.root, folder)
+        labelled = getattr(self.cube, 'labelled', True)
+        if not labelled and fp_model is None:
+            print(f'[entrance] {folder}: the val cases have no labels: validation skipped')
+            return
+        t0 = time.time()
         res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
                              fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
                              save_dir=os.path.join(out, 'val') if is_save_nii else None,
                              multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
                              surface=is_surf, **({'lesion_table': True} if is_table else {}),
+                             **({'fp_model': fp_model} if fp_model is not None else {}),
                              **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
+        if fp_model is not None:
+            E.write_agreement_csv(os.path.join(out, 'agreement.csv'), res)
+        if not labelled:
+            print(f'[entrance] {folder}: {len(res)} unlabelled val cases in {time.time() - t0:.2f}s')
+            self._print_agreement(folder, res)
+            return
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         if is_table:
             E.write_lesions_csv(os.path.join(out, 'lesions.csv'), res)
@@ -111,10 +132,25 @@ class _ValidationTester(_SnapshotWriter):
             print(f'[entrance] {folder}: label lesions detected / all, by size in voxels:')
             for c in range(bins.shape[0]):
                 print(f'  class {c}: ' + ', '.join(f'{n}: {int(k[1])} / {int(k[0])}' for n, k in zip(names, bins[c])))
+        if fp_model is not None:
+            self._print_agreement(folder, res)
+
+    @staticmethod
+    def _print_agreement(folder, res):
+        m = E.agreement_means(res)
+        print(f'[entrance] {folder} against the FP network: {100 * m["flip_frac"]:.4f} % of the voxels decided '
+              f'differently, per-class means:')
+        for c in range(len(m['dsc'])):
+            print(f'  class {c}: dsc = {float(m["dsc"][c]):.4f}, logit_rel_mse = {float(m["logit_rel_mse"][c]):.4g}, '
+                  f'prob_mae = {float(m["prob_mae"][c]):.4g}')
 
 
 class _SyntheticCube:
-    def __init__(self, task, n, size):
+    """The calibration volumes of --synthetic; with `validate` (--vs_fp) also two held-out volumes without labels, each
+    one window of the calibration size."""
+    valloader = None
+
+    def __init__(self, task, n, size, validate=False, multi_label=None):
         vols = synth.calib_batch(task, range(n), size)
 
         class DS(torch.utils.data.Dataset):
@@ -127,6 +163,28 @@ class _SyntheticCube:
             def use_fix_transform(self):
                 pass
         self.trainseqloader = torch.utils.data.DataLoader(DS(), 1, shuffle=False)
+        if validate:
+            held = synth.calib_batch(task, [n, n + 1], size)
+            self.valloader = [(v[None], torch.empty(1, 0, dtype=torch.uint8)) for v in held]
+            self.val_sn = [f'synth{n}', f'synth{n + 1}']
+            self.labelled = False
+            self.patch_size, self.overlap = tuple(held.shape[2:]), 0
+            self.multi_label, self.multilabel_fusetype = multi_label, None
+
+
+def check_switches(args):
+    """The combinations of --vs_fp / --unlabelled that cannot run, refused before anything touches the device (host only:
+    SystemExit naming the switches)."""
+    if not getattr(args, 'unlabelled', False):
+        return
+    if not getattr(args, 'vs_fp', False):
+        raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add --vs_fp')
+    if getattr(args, 'test_fp', False):
+        raise SystemExit('--unlabelled --test_fp: the FP network cannot be validated against labels that are not there: '
+                         'drop --test_fp')
+    if getattr(args, 'lesion_table', False):
+        raise SystemExit('--unlabelled --lesion_table: the per-lesion table is written against labels only (--is_cc and '
+                         '--surf_dist are measured against the FP network): drop --lesion_table')
 
 
 def main(argv=None):
@@ -135,6 +193,7 @@ def main(argv=None):
         args = Cf.merge_config(args.config, args)
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)
+    check_switches(args)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -172,9 +231,14 @@ def main(argv=None):
         return
     size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
     size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
-    data_cube = _SyntheticCube(args.task, args.lwq_batchsz, size)
+    data_cube = _SyntheticCube(args.task, args.lwq_batchsz, size, getattr(args, 'vs_fp', False),
+                               getattr(args, 'multi_label', None))
     with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
         f.write(' '.join(sys.argv) + '\n')
+    if data_cube.valloader is not None:
+        rank = int(os.environ.get('RANK', '0'))
+        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank), snap)
+        return
     K.do_ptq(args, cube, data_cube, _SnapshotWriter(model, snap), snap)
 
 

@@ -5,7 +5,8 @@ forward / stitch (``utils/validate.py:212-264``, ``utils/transforms.py:784-852``
 (``utils/metrics.py:119-148``).  The per-patch forward is the calibrated ``UResQ`` in
 quantized mode, i.e. every conv runs ``conv3d_quant_calib_step`` with the activation quantiser fused
 (``PTQConv.py:163-167``).  ``validate_seg`` below is the HIP path of the reference's validation on labelled volumes
-(batched windows, stitch, confusion counts and, with ``save_dir``, the NIfTI label maps: DESIGN.md section 13).
+(batched windows, stitch, confusion counts and, with ``save_dir``, the NIfTI label maps: DESIGN.md section 13); with
+``fp_model`` it also measures the calibrated network against the FP network, which needs no label.
 """
 from __future__ import annotations
 
@@ -249,10 +250,45 @@ def _write_map(path, host, dtype, entry=None):
     write_nifti(path, a, geometry=entry["header"])
 
 
+def _surface_entries(ops, logits, lab, kind, fuse, shape, spacing) -> dict:
+    """The surface entries of one case against `lab`: "surface" and "surface_counts" in voxel units, or with a spacing
+    in millimetres, then also "surface_sq" and "surface_unit"."""
+    if spacing is None:
+        sc, ss = ops.seg_surface(logits, lab, kind, fuse)
+        sc = sc.cpu()
+        return {"surface_counts": sc, "surface": surface_metrics(sc, ss, shape)}
+    sc, sq, ss = ops.seg_surface_mm(logits, lab, kind, fuse, spacing)
+    sc, sq = sc.cpu(), sq.cpu()
+    return {"surface_counts": sc, "surface_sq": sq, "surface": surface_metrics_mm(sc, sq, ss, shape, spacing),
+            "surface_unit": "mm"}
+
+
+def _vs_fp(ops, q, f, kind, fuse, shape, spacing, lesions, surface, want_map) -> dict:
+    """The "vs_fp" entry of one case: the calibrated network's stitched logits `q` against the FP network's `f`
+    (effq_seg_agreement); for the lesion and surface entries the FP decisions are the label (seg_labels: the merged
+    planes in sigmoid mode, the argmax map otherwise).  With `want_map` it also holds "map", still on the device."""
+    counts, flips, stats, vmap = ops.seg_agreement(q, f, kind, fuse, want_map)
+    counts, stats, S = counts.cpu(), stats.cpu(), q[0].numel()
+    flips = int(flips.cpu()[0])
+    out = {"counts": counts}
+    out.update(metrics_from_counts(counts))
+    out.update(flips=flips, flip_frac=flips / S, logit_rel_mse=stats[:, 0] / stats[:, 1], logit_max=stats[:, 2].clone(),
+               prob_mae=stats[:, 3] / S)
+    if lesions or surface:
+        lab = ops.seg_labels(f[None], "planes" if kind == "brats" else "argmax", fuse)[0]
+        if lesions:
+            out["lesions"] = ops.seg_lesions(q, lab, kind, fuse).cpu()
+        if surface:
+            out.update(_surface_entries(ops, q, lab, kind, fuse, shape, spacing))
+    if want_map:
+        out["map"] = vmap
+    return out
+
+
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
-                 geometry=None, lesion_table=False):
+                 geometry=None, lesion_table=False, fp_model=None):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -282,7 +318,19 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     arrays n x LESION_TABLE_COLUMNS = first voxel as d, h, w, size in voxels, overlap (the voxels the other mask of the
     class holds too; 0 = a missed / an invented lesion), in raster order of the first voxel (effq_seg_lesion_table: the
     launches of the lesion counts and four more), and with a geometry "spacing", the (d, h, w) mm of the case.  With
-    lesions=True as well "lesions" comes from the same call: the case is labelled once."""
+    lesions=True as well "lesions" comes from the same call: the case is labelled once.
+    fp_model: the full-precision network (a copy taken before the calibration, on the same device, in fp mode).  Every
+    batch of windows also runs through it, its last head is stitched the same way, and each dict gains "vs_fp", the
+    calibrated network measured against it (effq_seg_agreement, one pass over both stitched logits): counts (C x 4 =
+    both, Q only, FP only, neither - TP, FP, FN, TN with the FP decision as the truth) with dsc / sens / spec / acc,
+    flips and flip_frac (voxels decided differently in any class, and their share), and per class logit_rel_mse =
+    sum (q - f)^2 / sum f^2, logit_max = max |q - f| and prob_mae = mean |p_q - p_f| (p: sigmoid per channel, softmax in
+    argmax mode).  With lesions / surface it also carries "lesions" / "surface" (and surface_counts, surface_sq,
+    surface_unit) against the FP decisions (seg_labels of the FP logits as the label).  With save_dir the uint8 map of
+    the differing classes (bit c = class c) goes to <save_dir>_vs_fp/<name>.nii.gz, on the source grid when the case has
+    a source geometry.  The window batches are sized for both forwards.  A case whose label is empty (numel() == 0,
+    data.SegVolumes(labels=False)) is unlabelled: it needs fp_model, takes the counting from `multi_label` (set: sigmoid
+    per channel, else argmax) and its dict carries name and vs_fp only."""
     from .hip_ops import from_ndhwc, get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -298,15 +346,23 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
         if map_dtype is None:
             raise RuntimeError(f"label maps are written as uint8 or uint16, not {np.dtype(label_dtype)}")
         os.makedirs(save_dir, exist_ok=True)
+        if fp_model is not None:
+            os.makedirs(save_dir + "_vs_fp", exist_ok=True)
         pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-nifti")
     try:
         for images, labels in loader:
+            labelled = labels.numel() > 0
+            if not labelled and fp_model is None:
+                sn = names[len(results)] if names is not None else str(len(results))
+                raise RuntimeError(f"validate_seg: case {sn} has no label: an unlabelled case is validated against the "
+                                   f"FP network only (fp_model=...)")
             vol = images.to(dev, torch.float32).contiguous()
             N = int(vol.shape[0])
             nwin = 1
             for n in ops.window_grid(vol.shape[-3:], p, o):
                 nwin *= n
-            buf = None
+            nets = [model] if fp_model is None else [model, fp_model]
+            bufs = [None] * len(nets)
             first = 0
             while first < nwin:
                 cnt = min(bsz or 1, nwin - first)
@@ -315,18 +371,24 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                     base = torch.cuda.memory_allocated(dev)
                     torch.cuda.reset_peak_memory_stats(dev)
                 x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
-                last = _last_head(model(x))
-                if buf is None:
-                    buf = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-                buf[first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+                for k, net in enumerate(nets):      # the peak below covers both forwards
+                    last = _last_head(net(x))
+                    if bufs[k] is None:
+                        bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+                    bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+                    del last
                 if bsz is None:
                     per = max(1, torch.cuda.max_memory_allocated(dev) - base)
                     free, _ = torch.cuda.mem_get_info(dev)
                     bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
                 first += cnt
-            stitched = ops.window_stitch(buf, (N,) + tuple(buf.shape[-1:]) + tuple(vol.shape[-3:]), p, o)
-            lab = labels.to(dev).to(torch.uint8)
-            multi = lab.dim() == vol.dim()      # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append
+            full = (N,) + tuple(bufs[0].shape[-1:]) + tuple(vol.shape[-3:])
+            stitched = ops.window_stitch(bufs[0], full, p, o)
+            stitched_fp = ops.window_stitch(bufs[1], full, p, o) if fp_model is not None else None
+            lab = labels.to(dev).to(torch.uint8) if labelled else None
+            # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append; without a label multi_label decides
+            multi = lab.dim() == vol.dim() if labelled else bool(multi_label)
+            kind, fz = ("brats", fuse) if multi else ("lits", None)
             maps = None
             if pool is not None:                # the planes are 0/1 uint8 on the device, cast when written
                 rule = label_rule(multi, multi_label, task)
@@ -339,37 +401,33 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                 maps = ops.seg_labels(stitched, rule, fuse if multi else None,
                                       torch.uint8 if rule == "planes" else map_dtype).cpu().numpy()
             for n in range(N):
-                counts = ops.seg_tallies(stitched[n], lab[n], "brats" if multi else "lits",
-                                         fuse if multi else None).cpu()
                 i = len(results)
-                res = {"name": names[i] if names is not None else str(i), "counts": counts}
-                res.update(metrics_from_counts(counts))
+                res = {"name": names[i] if names is not None else str(i)}
                 spacing, entry = _case_geometry(geometry, i) if geometry is not None else (None, None)
-                if lesion_table:
-                    cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], "brats" if multi else "lits",
-                                                        fuse if multi else None)
-                    ncls = int(cnt.shape[0])
-                    res["lesion_table"] = [(_lesion_rows(rows[ncls + c], vol.shape[-3:]),
-                                            _lesion_rows(rows[c], vol.shape[-3:])) for c in range(ncls)]
-                    if spacing is not None:
-                        res["spacing"] = spacing
-                    if lesions:
-                        res["lesions"] = cnt
-                elif lesions:
-                    res["lesions"] = ops.seg_lesions(stitched[n], lab[n], "brats" if multi else "lits",
-                                                     fuse if multi else None).cpu()
-                if surface and spacing is None:
-                    sc, ss = ops.seg_surface(stitched[n], lab[n], "brats" if multi else "lits",
-                                             fuse if multi else None)
-                    res["surface_counts"] = sc.cpu()
-                    res["surface"] = surface_metrics(res["surface_counts"], ss, vol.shape[-3:])
-                elif surface:
-                    sc, sq, ss = ops.seg_surface_mm(stitched[n], lab[n], "brats" if multi else "lits",
-                                                    fuse if multi else None, spacing)
-                    res["surface_counts"], res["surface_sq"] = sc.cpu(), sq.cpu()
-                    res["surface"] = surface_metrics_mm(res["surface_counts"], res["surface_sq"], ss, vol.shape[-3:],
-                                                        spacing)
-                    res["surface_unit"] = "mm"
+                if labelled:
+                    counts = ops.seg_tallies(stitched[n], lab[n], kind, fz).cpu()
+                    res["counts"] = counts
+                    res.update(metrics_from_counts(counts))
+                    if lesion_table:
+                        cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], kind, fz)
+                        ncls = int(cnt.shape[0])
+                        res["lesion_table"] = [(_lesion_rows(rows[ncls + c], vol.shape[-3:]),
+                                                _lesion_rows(rows[c], vol.shape[-3:])) for c in range(ncls)]
+                        if spacing is not None:
+                            res["spacing"] = spacing
+                        if lesions:
+                            res["lesions"] = cnt
+                    elif lesions:
+                        res["lesions"] = ops.seg_lesions(stitched[n], lab[n], kind, fz).cpu()
+                    if surface:
+                        res.update(_surface_entries(ops, stitched[n], lab[n], kind, fz, vol.shape[-3:], spacing))
+                if fp_model is not None:
+                    res["vs_fp"] = _vs_fp(ops, stitched[n], stitched_fp[n], kind, fz, vol.shape[-3:], spacing, lesions,
+                                          surface, pool is not None)
+                    if pool is not None:
+                        vmap = res["vs_fp"].pop("map").cpu().numpy()
+                        writes.append(pool.submit(_write_map, os.path.join(save_dir + "_vs_fp", f"{res['name']}.nii.gz"),
+                                                  vmap, np.uint8, entry))
                 results.append(res)
                 if maps is not None and entry is None:
                     writes.append(pool.submit(_write_map, os.path.join(save_dir, f"{res['name']}.nii.gz"), maps[n],
@@ -406,6 +464,45 @@ def write_metrics_csv(path: str, results) -> None:
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
                             [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []) +
                             (["%.7g" % float(v) for v in r["surface"][c]] if sd else []))
+
+
+AGREEMENT_COUNTS = ("both", "q_only", "fp_only", "neither")          # the columns of "vs_fp"'s counts
+AGREEMENT_DRIFT = ("logit_rel_mse", "logit_max", "prob_mae")        # the per-class drift entries of "vs_fp"
+
+
+def write_agreement_csv(path: str, results) -> None:
+    """One row per subject and class from the "vs_fp" entries (validate_seg(..., fp_model=...)): subject, class, dsc,
+    sens, spec, acc, both, q_only, fp_only, neither, flip_frac_class = (q_only + fp_only) / voxels, logit_rel_mse,
+    logit_max, prob_mae, and when the entries carry "lesions" / "surface" (against the FP decisions) the columns of
+    write_metrics_csv after them, under its names and its unit rule; a file never mixes voxel units and mm."""
+    import csv
+    vs = [(r["name"], r["vs_fp"]) for r in results if "vs_fp" in r]
+    cc = any("lesions" in v for _, v in vs)
+    sd = any("surface" in v for _, v in vs)
+    units = {v.get("surface_unit", "voxel") for _, v in vs if "surface" in v}
+    if len(units) > 1:
+        raise RuntimeError("write_agreement_csv: surface distances in voxel units and in mm in one file")
+    sd_cols = SURFACE_COLUMNS_MM if units == {"mm"} else SURFACE_COLUMNS
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(("subject", "class") + METRICS + AGREEMENT_COUNTS + ("flip_frac_class",) + AGREEMENT_DRIFT +
+                    (LESION_COLUMNS if cc else ()) + (sd_cols if sd else ()))
+        for name, v in vs:
+            for c in range(v["counts"].shape[0]):
+                row = [int(n) for n in v["counts"][c]]
+                wr.writerow([name, c] + ["%.7g" % float(v[m][c]) for m in METRICS] + row +
+                            ["%.7g" % ((row[1] + row[2]) / sum(row))] +
+                            ["%.7g" % float(v[k][c]) for k in AGREEMENT_DRIFT] +
+                            ([int(n) for n in v["lesions"][c]] if cc else []) +
+                            (["%.7g" % float(n) for n in v["surface"][c]] if sd else []))
+
+
+def agreement_means(results) -> dict:
+    """Means over the cases of the "vs_fp" entries: dsc, logit_rel_mse and prob_mae per class, and flip_frac."""
+    vs = [r["vs_fp"] for r in results if "vs_fp" in r]
+    out = {k: torch.stack([v[k].to(torch.float64) for v in vs]).mean(0) for k in ("dsc", "logit_rel_mse", "prob_mae")}
+    out["flip_frac"] = sum(v["flip_frac"] for v in vs) / len(vs)
+    return out
 
 
 def write_lesions_csv(path: str, results) -> None:

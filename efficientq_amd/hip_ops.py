@@ -1153,6 +1153,46 @@ class HipOps:
                                        out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
         return out
 
+    def seg_agreement(self, logits_q: torch.Tensor, logits_fp: torch.Tensor, mode: str, fuse: Optional[str] = None,
+                      want_map: bool = False):
+        """Where and how much two networks differ on one case (effq_seg_agreement): the stitched last-head logits of the
+        calibrated and of the FP network, C x spatial fp32 each.  mode 'argmax' (or the task 'lits') / 'sigmoid' ('brats')
+        and `fuse` as seg_tallies: both networks' voxels are decided by its rule.  Returns (counts, flips, stats, map):
+        counts C x 4 int64 = both, Q only, FP only, neither (TP, FP, FN, TN with the FP decision as the truth); flips (1)
+        int64, the voxels decided differently in any class; stats C x 4 float64 = sum (q - f)^2, sum f^2, max |q - f|,
+        sum |p_q - p_f| (p: sigmoid of the channel / softmax over the channels, in fp64); map: uint8 of the spatial
+        shape with bit c set where class c is decided differently, or None without `want_map`."""
+        if logits_q.dtype != torch.float32 or logits_fp.dtype != torch.float32:
+            raise _lib.EffqError(f"seg_agreement: expected float32 logits, got {logits_q.dtype} and {logits_fp.dtype}")
+        if logits_q.shape != logits_fp.shape or logits_q.dim() < 2 or logits_q.numel() == 0:
+            raise _lib.EffqError(f"seg_agreement: logits {tuple(logits_q.shape)} and {tuple(logits_fp.shape)}, needs the "
+                                 f"same C x spatial shape for both")
+        if logits_q.device != logits_fp.device:
+            raise _lib.EffqError(f"seg_agreement: logits on {logits_q.device} and on {logits_fp.device}")
+        if not (logits_q.is_contiguous() and logits_fp.is_contiguous()):
+            raise _lib.EffqError("seg_agreement: the logits must be contiguous")
+        q, f = self._f32(logits_q), self._f32(logits_fp)
+        Cc, S = int(q.shape[0]), q[0].numel()
+        key = {"argmax": _lib.SEG_ARGMAX, "lits": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID,
+               "brats": _lib.SEG_SIGMOID}.get(mode)
+        if key is None:
+            raise _lib.EffqError(f"seg_agreement: unknown mode {mode!r} (argmax or sigmoid)")
+        fkey = fuse.lower() if isinstance(fuse, str) else fuse
+        if fkey not in _lib.SEG_FUSE or (key == _lib.SEG_ARGMAX and fkey is not None):
+            raise _lib.EffqError(f"seg_agreement: merge type {fuse!r} for mode {mode}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_agreement: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        thresh = 0.0 if key == _lib.SEG_ARGMAX else self.sigmoid_threshold()
+        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
+        flips = torch.empty(1, dtype=torch.int64, device=self.device)
+        stats = torch.empty(Cc, 4, dtype=torch.float64, device=self.device)
+        vmap = torch.empty(tuple(q.shape[1:]), dtype=torch.uint8, device=self.device) if want_map else None
+        ws = self._workspace("seg_agreement", _lib.SEG_AGREEMENT_WS_BYTES)
+        check(self.lib.effq_seg_agreement(_ptr(q), _ptr(f), Cc, S, key, _lib.SEG_FUSE[fkey], thresh, _ptr(counts),
+                                          _ptr(flips), _ptr(stats), _ptr(vmap), _ptr(ws), ws.numel(), self.stream),
+              "effq_seg_agreement")
+        return counts, flips, stats, vmap
+
     def cc_label(self, mask: torch.Tensor, connectivity: int = 26):
         """Connected components of 0/1 volumes (effq_cc_label; scipy.ndimage.label in metrics.py:69-73): `mask` D x H x W
         or P x D x H x W uint8, non-zero = foreground.  Returns (labels, ncomp): int32 labels of the mask's shape, 0 for

@@ -577,6 +577,24 @@ int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int 
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* Agreement of two networks on one case (validate_seg(..., fp_model=...), --vs_fp): logits_q and logits_fp, the stitched
+ * last-head logits (C, S) fp32 of the calibrated and of the full-precision network; mode, fuse and thresh as
+ * effq_seg_tallies, and both networks' voxels are decided by the tallies' own rule.  One pass over the 2 C S floats:
+ *   counts (C, 4) int64 = both, Q only, FP only, neither: TP, FP, FN, TN with the FP network's decision as the truth.
+ *   flips  (1)    int64 = the voxels where the decision of at least one class differs.
+ *   stats  (C, 4) fp64  = sum (q - f)^2, sum f^2, max |q - f|, sum |p_q - p_f| per class, differences and squares formed
+ *          in fp64 from the fp32 logits; p is in fp64 the sigmoid of the channel (before `fuse`) for EFFQ_SEG_SIGMOID and
+ *          the softmax over the C channels for EFFQ_SEG_ARGMAX.
+ *   map    (S) uint8, or NULL: bit c set where the decision of class c differs.
+ * Per-workgroup partials, then one workgroup adds them in block order; no floating-point atomics, so equal inputs give
+ * equal bits.  16-B loads for the first 4 (S / 4) voxels of every channel whatever S is, the last S % 4 voxels one by one.
+ * Two launches on `stream`, no read by the host, no workgroup that waits for another.  ws: EFFQ_SEG_AGREEMENT_WS_BYTES of
+ * scratch, 8-B aligned. */
+#define EFFQ_SEG_AGREEMENT_WS_BYTES (768 * (4 * EFFQ_SEG_TALLIES_MAX_CLASSES * 8 + (3 * EFFQ_SEG_TALLIES_MAX_CLASSES + 1) * 4))
+int effq_seg_agreement(const float* logits_q, const float* logits_fp, int C, long long S, int mode, int fuse,
+                       float thresh, long long* counts, long long* flips, double* stats, uint8_t* map, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* Labels: logits (N, C, S) of N cases -> one label map (N, S) of out_bytes = 1 (uint8) or 2 (uint16) per voxel, or
  * for EFFQ_SEG_LABEL_PLANES the C merged 0/1 planes (N, C, S) uint8.  The per-voxel decisions are the tallies': the
  * ARGMAX rule uses EFFQ_SEG_ARGMAX (fuse must be NONE), every other rule EFFQ_SEG_SIGMOID with `thresh` and `fuse`.
