@@ -4,6 +4,7 @@
 // Reference: layer_helper.py:25-70 (discretize, project_by_iter), PTQConv.py:114-116.
 // All arithmetic follows the reference's operation order with IEEE divisions and no FMA
 // contraction (the library is built with -ffp-contract=off).
+#include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include "common.h"
@@ -281,18 +282,19 @@ __global__ __launch_bounds__(TPB) void k_act_quant_bwd(const float* __restrict__
 }
 
 __global__ __launch_bounds__(TPB) void k_adam(float* __restrict__ p, const float* __restrict__ g,
-                                              float* __restrict__ m, float* __restrict__ v, float lr, float b1,
-                                              float b2, float eps, float bc1, float bc2, size_t n) {
-  // torch.optim.Adam (no weight decay, no amsgrad): ptqer.py:255 Adam(opt_param, lr=5e-4)
+                                              float* __restrict__ m, float* __restrict__ v, float w1, float b2,
+                                              float w2, float eps, float step, float bc2_sqrt, size_t n) {
+  // torch.optim.Adam (no weight decay, no amsgrad): ptqer.py:255 Adam(opt_param, lr=5e-4).  w1 = 1 - beta1, w2 = 1 - beta2,
+  // step = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double on the host and rounded once, as torch does
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float gi = g[i];
-    float mi = m[i] + (1.0f - b1) * (gi - m[i]);          // lerp form used by torch
-    float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    float mi = m[i] + w1 * (gi - m[i]);                   // lerp form used by torch
+    float vi = b2 * v[i] + w2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] = p[i] - (lr / bc1) * (mi / denom);
+    float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] - step * (mi / denom);
   }
 }
 
@@ -430,13 +432,15 @@ int effq_act_quant_backward(const float* x, const float* alpha_dev, int levels, 
   return EFFQ_OK;
 }
 
-int effq_adam_step(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t,
+int effq_adam_step(float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps, int t,
                    size_t n, void* stream) {
-  EFFQ_CHECK_ARG(p && g && m && v && t >= 1);
-  if (n == 0) return EFFQ_OK;
-  const float bc1 = 1.0f - powf(b1, (float)t), bc2 = 1.0f - powf(b2, (float)t);
-  hipLaunchKernelGGL(k_adam, dim3(stream_grid(n)), dim3(TPB), 0, as_stream(stream), p, g, m, v, lr, b1, b2, eps, bc1,
-                     bc2, n);
+  EFFQ_CHECK_ARG(t >= 1);
+  if (n == 0) return EFFQ_OK;  /* an empty parameter vector is legal (and carries null pointers) */
+  EFFQ_CHECK_ARG(p && g && m && v);
+  // 1 - (float)0.999 is 1.3e-5 off 1 - 0.999, and that error does not cancel against 1 - beta2^t once t is large
+  const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
+  hipLaunchKernelGGL(k_adam, dim3(stream_grid(n)), dim3(TPB), 0, as_stream(stream), p, g, m, v, (float)(1.0 - b1),
+                     (float)b2, (float)(1.0 - b2), (float)eps, (float)(lr / bc1), (float)sqrt(bc2), n);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

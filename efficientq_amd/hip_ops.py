@@ -976,8 +976,9 @@ class HipOps:
         return gx, ga
 
     def adam_step(self, p, g, m, v, lr: float, t: int, b1=0.9, b2=0.999, eps=1e-8):
-        """torch.optim.Adam step in place on flat fp32 tensors (effq_adam_step)."""
-        check(self.lib.effq_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), lr, b1, b2, eps, int(t), p.numel(),
+        """torch.optim.Adam step in place on flat fp32 tensors (effq_adam_step); lr, betas and eps travel as doubles."""
+        check(self.lib.effq_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), float(lr), float(b1), float(b2), float(eps),
+                                      int(t), p.numel(),
                                       self.stream), "effq_adam_step")
 
     # -- the conv ---------------------------------------------------------------------------------

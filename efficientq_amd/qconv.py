@@ -195,16 +195,19 @@ class PTQConv(nn.Conv3d):
         return from_ndhwc(out)
 
     def _dgrad(self, g):
-        """Gradient of the conv w.r.t. its input: the conv kernel on g with flipped, transposed weights (stride 1)."""
+        """Gradient of the conv w.r.t. its input: the conv kernel on g with flipped, transposed weights.  Stride 1 and
+        "same" padding (2 p = k - 1 on every axis) only: there the gradient conv has the forward's own padding."""
         if self.stride != (1, 1, 1):
             raise NotImplementedError("input gradient of a strided conv is not needed on the calibrated path")
+        if any(2 * p != k - 1 for p, k in zip(self.padding, self.kernel_size)):
+            raise NotImplementedError(f"input gradient needs 'same' padding (2 * padding == kernel_size - 1), got "
+                                      f"kernel_size {tuple(self.kernel_size)} with padding {tuple(self.padding)}")
         ops = get_ops(g.device)
-        key = (self.weight.data_ptr(), self.weight._version)
-        if getattr(self, "_wt_key", None) != key:
-            self._wt = self.weight.data.flip(2, 3, 4).transpose(0, 1).contiguous()
-            self._wt_key = key
+        # formed on every backward: the weights are written through .data, which leaves no trace a cache could key on
+        # (neither _version nor, with the caching allocator, the address), and the tensor is small beside the conv
+        wt = self.weight.data.flip(2, 3, 4).transpose(0, 1).contiguous()
         geom = make_geom(g.shape, self.in_channels, self.kernel_size, self.stride, self.padding)
-        out, _ = ops.conv_step(to_ndhwc(g.detach()), self._wt, None, geom, want_out=True)
+        out, _ = ops.conv_step(to_ndhwc(g.detach()), wt, None, geom, want_out=True)
         return from_ndhwc(out)
 
     def _quantize_act(self, x):

@@ -437,8 +437,10 @@ int conv3d_calib_step_i8s(const uint8_t* xidx_ndhwc, const int8_t* Gq, const flo
  * applied to the output gradient with flipped, transposed weights (stride 1). */
 int effq_act_quant_backward(const float* x, const float* alpha_dev, int levels, const float* gq, float* gx_out,
                             double* galpha_out, size_t n, void* ws, void* stream);
-/* torch.optim.Adam step (no weight decay, no amsgrad) on n parameters; t = step number starting at 1. */
-int effq_adam_step(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps,
+/* torch.optim.Adam step (no weight decay, no amsgrad) on n parameters; t = step number starting at 1.  The hyper-parameters
+ * are doubles: 1 - beta, the bias corrections 1 - beta^t and lr / (1 - beta1^t) are formed in double, as torch forms them
+ * from Python floats, and rounded to fp32 once.  n = 0 is a no-op. */
+int effq_adam_step(float* p, const float* g, float* m, float* v, double lr, double b1, double b2, double eps,
                    int t, size_t n, void* stream);
 
 /* ---- the whole ADMM loop of a layer in ONE call (EfficientQConv.py:99-144) -----------------------------------
