@@ -200,6 +200,13 @@ SIGNATURES = {
     "effq_surf_mm_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_edt_sq_mm": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _SZ, _P]),
     "effq_seg_surface_mm": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _SZ, _P]),
+    "effq_prep_window": (_I, [_P, _SZ, _F, _F, _P]),
+    "effq_prep_resample": (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _I, _P, _I, _I, _I, _P]),
+    "effq_prep_bbox_moments": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "effq_prep_sqdev": (_I, [_P, _I, _LL, _I, _P, _P, _P, _SZ, _P]),
+    "effq_prep_standardise_crop": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "effq_prep_crop_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "effq_prep_union_mask": (_I, [_P, _I, _LL, _I, _P, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -221,6 +228,11 @@ LESION_TABLE_ROWS = 4096
 EDT_MAX_LINE = 16382
 # include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)
 EDT_MM_MAX_EXTENT = 4096
+# include/effq_hip.h: the prep kernels' most modalities, scratch, mask modes and resampling modes
+PREP_MAX_MODALITIES = 4
+PREP_WS_BYTES = 1024 * (2 * PREP_MAX_MODALITIES * 8 + 8 * 4)
+PREP_MASKS = {"nonzero": 0, "all": 1}
+PREP_LINEAR, PREP_NEAREST = 0, 1
 
 _lib = None
 

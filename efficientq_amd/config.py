@@ -1,4 +1,4 @@
-"""CLI / YAML surface and factories of the ``ptq`` mission, same flag names and semantics as the
+"""CLI / YAML surface of both missions (``prep``: prep.py) and factories of the ``ptq`` mission, same flag names and semantics as the
 reference (src/entrance.py:17-128, src/definer.py:130-248,286-329): YAML values override the
 command line for every non-null key (quirk Q15); ``qlvl_*`` are LEVEL counts (4 => 2-bit);
 ``q_first/q_last "W,A"`` with A=-1 => full-precision activations (quirk Q14); every ``lwq_*``
@@ -7,6 +7,7 @@ argument is forwarded to the conv constructor as ``**kwQ``.
 from __future__ import annotations
 
 import argparse
+import re
 
 import torch.nn as nn
 import yaml
@@ -28,7 +29,7 @@ def merge_config(cfg: str, args: argparse.Namespace):
 
 def build_parser():
     p = argparse.ArgumentParser(description='EfficientQ PTQ calibration on MI355X')
-    p.add_argument('mission', choices=['ptq'])
+    p.add_argument('mission', choices=['ptq', 'prep'])
     p.add_argument('--pretrain')
     p.add_argument('--resume')
     p.add_argument('--device', default=0, type=int, help='GPU ID.')
@@ -87,6 +88,19 @@ def build_parser():
     # new in this build: synthetic calibration volumes (no dataset is shipped with either repo)
     p.add_argument('--synthetic', action='store_true', help='calibrate on seeded synthetic volumes')
     p.add_argument('--snap_dir', default=None)
+    # the prep mission (prep.py): source NIfTI scans to the data layout --data_dir / --split_dir name
+    p.add_argument('--src_list', default=None, help='prep: CSV `subject,<modality>,...[,seg]` of NIfTI paths')
+    p.add_argument('--val_every', default=None, type=int,
+                   help='prep, with --split_dir: every K-th of the sorted subjects goes to val.txt, the rest to train.txt')
+    p.add_argument('--prep_mask', default=None, choices=['nonzero', 'all'],
+                   help='prep: the voxels a modality is standardised over (brats: nonzero, lits: all)')
+    p.add_argument('--prep_window', default=None, help='prep: lo,hi to clip to first, or none (lits: -200,250)')
+    p.add_argument('--prep_spacing', default=None, help='prep: d,h,w in mm to resample every subject to')
+    p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
+    p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
+    # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
+    # number, and its own pattern knows no comma
+    p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
     return p
 
 

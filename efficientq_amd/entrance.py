@@ -25,6 +25,11 @@ decided differently, the logit drift and the probability drift, the lesion / sur
 is given: then two held-out synthetic volumes are validated against the FP network; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
 the calibration volumes are sharded over N GPUs and the validation runs on rank 0.
+
+The ``prep`` mission (prep.py) writes that layout from source NIfTI scans:
+
+    python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data --split_dir out/split \
+        --val_every 5
 """
 from __future__ import annotations
 
@@ -191,6 +196,10 @@ def main(argv=None):
     args = Cf.build_parser().parse_args(argv)
     if args.config:
         args = Cf.merge_config(args.config, args)
+    if args.mission == 'prep':
+        from . import prep
+        prep.run(args)
+        return
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)
     check_switches(args)

@@ -1375,6 +1375,119 @@ class HipOps:
                                            _ptr(sq), _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface_mm")
         return counts, sq, sums
 
+    # -- the prep mission (prep.py) ---------------------------------------------------------------------------------
+    def _prep_volumes(self, what: str, x: torch.Tensor, dtype=torch.float32, limit_c: bool = True):
+        """The checked (tensor, C, D, H, W) of a contiguous C x D x H x W device tensor of `dtype`."""
+        if x.dim() != 4 or x.dtype != dtype or x.numel() == 0 or not x.is_contiguous() or self._elsewhere(x):
+            raise _lib.EffqError(f"{what}: needs a contiguous C x D x H x W {dtype} tensor on {self.device}, got "
+                                 f"{tuple(x.shape)} {x.dtype} on {x.device}")
+        Cc, D, H, W = (int(n) for n in x.shape)
+        if (limit_c and Cc > _lib.PREP_MAX_MODALITIES) or x.numel() >= 2 ** 31 or max(D, H, W) > 32767:
+            raise _lib.EffqError(f"{what}: shape {tuple(x.shape)}: at most {_lib.PREP_MAX_MODALITIES} modalities, 2^31 - 1 "
+                                 f"voxels in all and 32767 along an axis")
+        return x, Cc, D, H, W
+
+    def _elsewhere(self, t: torch.Tensor) -> bool:
+        return t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index))
+
+    @staticmethod
+    def _prep_mask(what: str, mask: str) -> int:
+        if mask not in _lib.PREP_MASKS:
+            raise _lib.EffqError(f"{what}: unknown mask {mask!r} (one of {', '.join(_lib.PREP_MASKS)})")
+        return _lib.PREP_MASKS[mask]
+
+    @staticmethod
+    def _prep_box(what: str, shape, pmin, pmax):
+        lo, hi = tuple(int(v) for v in pmin), tuple(int(v) for v in pmax)
+        if len(lo) != 3 or len(hi) != 3 or not all(0 <= a < b <= n for a, b, n in zip(lo, hi, shape)):
+            raise _lib.EffqError(f"{what}: box {lo} : {hi} does not lie in a grid of {tuple(shape)}")
+        return lo, hi, (C.c_int * 3)(*lo), (C.c_int * 3)(*hi)
+
+    def _prep_stats(self, what: str, v, n: int) -> torch.Tensor:
+        t = torch.as_tensor(v, dtype=torch.float64).reshape(-1).to(self.device)
+        if t.numel() != n:
+            raise _lib.EffqError(f"{what}: {t.numel()} values for {n} modalities")
+        return t
+
+    def prep_window(self, x: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+        """Clip the float32 tensor `x` to [lo, hi] in place (effq_prep_window: numpy.clip, a NaN stays)."""
+        if x.dtype != torch.float32 or not x.is_contiguous() or self._elsewhere(x) or x.numel() == 0:
+            raise _lib.EffqError(f"prep_window: needs a contiguous float32 tensor on {self.device}")
+        if not float(lo) <= float(hi):
+            raise _lib.EffqError(f"prep_window: bounds {lo}, {hi}")
+        check(self.lib.effq_prep_window(_ptr(x), x.numel(), float(lo), float(hi), self.stream), "effq_prep_window")
+        return x
+
+    def prep_resample(self, x: torch.Tensor, factors, out_shape, nearest: bool = False) -> torch.Tensor:
+        """N x D x H x W volumes on a grid of another spacing (effq_prep_resample): `factors` = target spacing / source
+        spacing per axis, `out_shape` the output extents (prep.resample_extent).  float32 volumes are interpolated
+        trilinearly; with `nearest` the volumes are uint8 labels and keep their values."""
+        x, N, D, H, W = self._prep_volumes("prep_resample", x, torch.uint8 if nearest else torch.float32, limit_c=False)
+        f = tuple(float(v) for v in factors)
+        o = tuple(int(v) for v in out_shape)
+        if len(f) != 3 or len(o) != 3 or not all(0.0 < v <= 1e6 for v in f) or min(o) < 1 or max(o) > 32767 or \
+                N * o[0] * o[1] * o[2] >= 2 ** 31:
+            raise _lib.EffqError(f"prep_resample: factors {f}, output extents {o}")
+        y = torch.empty((N,) + o, dtype=x.dtype, device=self.device)
+        check(self.lib.effq_prep_resample(_ptr(x), N, D, H, W, f[0], f[1], f[2],
+                                          _lib.PREP_NEAREST if nearest else _lib.PREP_LINEAR, _ptr(y), o[0], o[1], o[2],
+                                          self.stream), "effq_prep_resample")
+        return y
+
+    def prep_bbox_moments(self, x: torch.Tensor, mask: str = "nonzero"):
+        """Pass 1 over one subject (effq_prep_bbox_moments), x = C x D x H x W float32.  Returns (bbox, count, sum):
+        bbox int32[6] = the least d, h, w and the greatest d, h, w of the union of the modalities' masks (least > greatest
+        when it is empty), count int64[C] and sum float64[C] over each modality's own mask.  mask 'nonzero': x_c != 0;
+        'all': every voxel, the box is the grid."""
+        x, Cc, D, H, W = self._prep_volumes("prep_bbox_moments", x)
+        mode = self._prep_mask("prep_bbox_moments", mask)
+        bbox = torch.empty(6, dtype=torch.int32, device=self.device)
+        count = torch.empty(Cc, dtype=torch.int64, device=self.device)
+        total = torch.empty(Cc, dtype=torch.float64, device=self.device)
+        ws = self._workspace("prep", _lib.PREP_WS_BYTES)
+        check(self.lib.effq_prep_bbox_moments(_ptr(x), Cc, D, H, W, mode, _ptr(bbox), _ptr(count), _ptr(total), _ptr(ws),
+                                              ws.numel(), self.stream), "effq_prep_bbox_moments")
+        return bbox, count, total
+
+    def prep_sqdev(self, x: torch.Tensor, mean, mask: str = "nonzero") -> torch.Tensor:
+        """Pass 2 (effq_prep_sqdev): float64[C] = the sum over each modality's mask of (double(x) - mean[c])^2."""
+        x, Cc, D, H, W = self._prep_volumes("prep_sqdev", x)
+        mode = self._prep_mask("prep_sqdev", mask)
+        mu = self._prep_stats("prep_sqdev", mean, Cc)
+        out = torch.empty(Cc, dtype=torch.float64, device=self.device)
+        ws = self._workspace("prep", _lib.PREP_WS_BYTES)
+        check(self.lib.effq_prep_sqdev(_ptr(x), Cc, D * H * W, mode, _ptr(mu), _ptr(out), _ptr(ws), ws.numel(),
+                                       self.stream), "effq_prep_sqdev")
+        return out
+
+    def prep_standardise_crop(self, x: torch.Tensor, pmin, pmax, mean, std, mask: str = "nonzero") -> torch.Tensor:
+        """Pass 3 (effq_prep_standardise_crop): the box pmin <= (d, h, w) < pmax of every modality as
+        float((double(x) - mean[c]) / std[c]) inside the modality's mask and +0.0 outside it."""
+        x, Cc, D, H, W = self._prep_volumes("prep_standardise_crop", x)
+        mode = self._prep_mask("prep_standardise_crop", mask)
+        lo, hi, clo, chi = self._prep_box("prep_standardise_crop", (D, H, W), pmin, pmax)
+        mu, sd = self._prep_stats("prep_standardise_crop", mean, Cc), self._prep_stats("prep_standardise_crop", std, Cc)
+        y = torch.empty((Cc,) + tuple(b - a for a, b in zip(lo, hi)), dtype=torch.float32, device=self.device)
+        check(self.lib.effq_prep_standardise_crop(_ptr(x), Cc, D, H, W, mode, clo, chi, _ptr(mu), _ptr(sd), _ptr(y),
+                                                  self.stream), "effq_prep_standardise_crop")
+        return y
+
+    def prep_crop_u8(self, x: torch.Tensor, pmin, pmax) -> torch.Tensor:
+        """The box pmin <= (d, h, w) < pmax of C x D x H x W uint8 volumes (effq_prep_crop_u8: the label)."""
+        x, Cc, D, H, W = self._prep_volumes("prep_crop_u8", x, torch.uint8, limit_c=False)
+        lo, hi, clo, chi = self._prep_box("prep_crop_u8", (D, H, W), pmin, pmax)
+        y = torch.empty((Cc,) + tuple(b - a for a, b in zip(lo, hi)), dtype=torch.uint8, device=self.device)
+        check(self.lib.effq_prep_crop_u8(_ptr(x), Cc, D, H, W, clo, chi, _ptr(y), self.stream), "effq_prep_crop_u8")
+        return y
+
+    def prep_union_mask(self, x: torch.Tensor, mask: str = "nonzero") -> torch.Tensor:
+        """D x H x W uint8, 1 where the mask of any modality of x (C x D x H x W) holds (effq_prep_union_mask)."""
+        x, Cc, D, H, W = self._prep_volumes("prep_union_mask", x)
+        mode = self._prep_mask("prep_union_mask", mask)
+        m = torch.empty((D, H, W), dtype=torch.uint8, device=self.device)
+        check(self.lib.effq_prep_union_mask(_ptr(x), Cc, D * H * W, mode, _ptr(m), self.stream), "effq_prep_union_mask")
+        return m
+
 
 _OPS = {}
 

@@ -7,6 +7,8 @@ and in Fortran order (first array axis fastest), so a NIfTI reader gets back ``a
 files carry no name and ``mtime`` 0: the same map always gives the same bytes.
 
 The reader is the inverse for these files (uint8 / uint16 data, either byte order) and rejects anything else.
+``read_image`` reads the source scans of the ``prep`` mission: 3-D images of the common integer and float datatypes, as
+float32 with the header's scaling applied.
 
 ``read_geometry`` reads only the header of an image of any datatype: where the voxels of a scan lie in space.  With
 ``--src_geom`` the label maps are written with the geometry of the scan they belong to (``write_nifti(..., geometry=)``:
@@ -205,3 +207,68 @@ def read_geometry(path: str) -> dict:
     g["affine"] = aff
     g["spacing"] = tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
     return g
+
+
+# ---- source scans (the `prep` mission) -----------------------------------------------------------------------------------
+# NIfTI datatype code -> dtype of the images read_image reads
+IMAGE_DATATYPES = {2: np.dtype(np.uint8), 4: np.dtype(np.int16), 8: np.dtype(np.int32), 16: np.dtype(np.float32),
+                   64: np.dtype(np.float64), 256: np.dtype(np.int8), 512: np.dtype(np.uint16), 768: np.dtype(np.uint32)}
+
+
+def decode_image(raw: bytes, path: str = "<bytes>"):
+    """(float32 array, header fields) of the bytes of a single-file NIfTI-1 image; see read_image."""
+    if len(raw) < VOX_OFFSET:
+        raise ValueError(f"read_image: {path}: {len(raw)} bytes, shorter than a NIfTI-1 header")
+    for end in "<>":
+        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
+            break
+    else:
+        raise ValueError(f"read_image: {path}: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
+    f = {}
+    for name, fmt, off in FIELDS:
+        v = struct.unpack_from(end + fmt, raw, off)
+        f[name] = v[0] if len(v) == 1 else v
+    if f["magic"] != MAGIC:
+        raise ValueError(f"read_image: {path}: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    if f["datatype"] not in IMAGE_DATATYPES:
+        raise ValueError(f"read_image: {path}: datatype {f['datatype']}, one of {sorted(IMAGE_DATATYPES)} is read")
+    dt = IMAGE_DATATYPES[f["datatype"]].newbyteorder(end)
+    if f["bitpix"] != 8 * dt.itemsize:
+        raise ValueError(f"read_image: {path}: bitpix {f['bitpix']} for datatype {f['datatype']}")
+    ndim = f["dim"][0]
+    shape = tuple(int(n) for n in f["dim"][1:1 + max(ndim, 0)])
+    if ndim == 4 and shape[3] == 1:                                    # a 4-D image with one volume
+        shape = shape[:3]
+    if len(shape) != 3 or not 3 <= ndim <= 4 or min(shape) < 1:
+        raise ValueError(f"read_image: {path}: dim = {f['dim']}: only 3-D images (or 4-D with a last extent of 1) are read")
+    off = int(f["vox_offset"])
+    count = int(np.prod(shape))
+    if off < VOX_OFFSET or len(raw) < off + count * dt.itemsize:
+        raise ValueError(f"read_image: {path}: shape {shape} at offset {off} does not fit {len(raw)} bytes")
+    a = np.frombuffer(raw, dtype=dt, count=count, offset=off).reshape(shape, order="F")
+    slope, inter = float(f["scl_slope"]), float(f["scl_inter"])
+    if slope != 0.0 and np.isfinite(slope) and np.isfinite(inter):     # nifti1.h: scaling applies when scl_slope != 0
+        a = (a.astype(np.float64) * slope + inter).astype(np.float32)
+    if f["sform_code"] > 0:
+        aff = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
+    elif f["qform_code"] > 0:
+        aff = qform_affine(f["quatern"], f["pixdim"])
+    else:
+        aff = np.diag([float(f["pixdim"][1]), float(f["pixdim"][2]), float(f["pixdim"][3]), 1.0])
+    f["affine"] = aff
+    f["spacing"] = tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
+    f["shape"] = shape
+    return np.ascontiguousarray(a, dtype=np.float32), f
+
+
+def read_image(path: str):
+    """(float32 array, header fields) of a 3-D single-file NIfTI-1 image (``.nii`` / ``.nii.gz``, either byte order) of
+    datatype uint8, int16, int32, float32, float64, int8, uint16 or uint32.  ``value = scl_slope * stored + scl_inter``
+    (in float64, then cast) when scl_slope != 0.  Array axes 0, 1, 2 are the image's i, j, k.  A 4-D image whose last
+    extent is 1 is squeezed; any other dimensionality, datatype or file kind raises a ValueError naming the path.  The
+    fields are those of FIELDS plus `shape`, `affine` and `spacing`, chosen as read_geometry chooses them."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if raw[:2] == b"\x1f\x8b":
+        raw = gzip.decompress(raw)
+    return decode_image(raw, str(path))

@@ -1,0 +1,448 @@
+"""The ``prep`` mission: source NIfTI scans to the data layout the ``ptq`` mission reads (data.py).
+
+    python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
+        [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|none] \
+        [--prep_spacing d,h,w] [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
+
+``--src_list`` is a CSV with the header ``subject,<modality>,...[,seg]`` (the task's modalities, data.MODALITIES, in any
+order) and one row per subject with one NIfTI path per column, relative to the CSV unless absolute; an empty ``seg``
+cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
+
+    window     --prep_window lo,hi: clip in place (lits: -200,250 unless ``none``; brats: none)
+    resample   --prep_spacing d,h,w: trilinear for the images, nearest for the label, no filter before down-sampling
+    pass 1     the box of the union of the modalities' masks, per modality the count and the sum over its own mask
+               (--prep_mask nonzero: x != 0, the brats default; all: every voxel, the lits default)
+    pass 2     per modality the squared deviations from the mean of pass 1; std = sqrt(sqdev / count)
+    pass 3     (x - mean) / std inside the mask and exactly 0 outside it, cropped to the box
+
+and the files ``data_dir/<modality>/<subject>.npy`` (float32), ``data_dir/seg/<subject>.npy`` (uint8), and at the end
+``data_dir/sn_fn.txt``, ``data_dir/restore_shape_infokw.pickle`` and ``data_dir/prep.csv``, merged with what an earlier
+run into the same ``data_dir`` left.  Without ``--prep_spacing`` sn_fn.txt names the first modality's own source image,
+so ``ptq --src_geom --save_nii`` writes maps that overlay the scan; with it the arrays live on a new grid, which
+``data_dir/grid/<subject>.nii.gz`` (the union mask, uint8, with the grid's affine) records and sn_fn.txt names.
+``--split_dir --val_every K`` also writes ``split_dir/round<R>/{train,val}.txt``.
+
+What the headers decide (the list itself, shapes and affines within a subject, a grid smaller than --prep_min_size, a
+split that already exists) is checked for every subject before anything is written.  What only the voxels decide (an
+empty mask, a constant modality) stops the run at that subject: none of its files and none of the files written at the
+end exist then.  The next subject's files are read and gunzipped by one background thread while the device works.
+There is no CPU path: `ops` is hip_ops.get_ops(device) unless a caller passes its own.
+"""
+from __future__ import annotations
+
+import csv
+import math
+import os
+import os.path as P
+import pickle
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import data as D
+from . import nifti
+
+GRID_DIR = "grid"
+PREP_CSV = "prep.csv"
+MASK_DEFAULT = {"brats": "nonzero", "lits": "all"}
+WINDOW_DEFAULT = {"brats": None, "lits": (-200.0, 250.0)}
+AFFINE_TRANSLATION_TOL_MM = 1e-3
+AFFINE_LINEAR_RTOL = 1e-4
+
+
+class PrepError(SystemExit):
+    """A run that cannot go on; the message names the row or the subject."""
+
+
+# ---- the geometry of the steps (host, no device) ------------------------------------------------------------------------
+def resample_extent(extent: int, factor: float) -> int:
+    """Output extent of an axis: max(1, round(extent / factor)) with Python's round on the fp64 quotient (ties to even)."""
+    return max(1, int(round(float(extent) / float(factor))))
+
+
+def resample_affine(affine: np.ndarray, factors: Sequence[float]) -> np.ndarray:
+    """A' = A [[diag(f), (f - 1) / 2], [0, 1]]: output voxel o lies at source coordinate (o + 0.5) f - 0.5."""
+    f = np.asarray(factors, dtype=np.float64)
+    m = np.eye(4)
+    m[:3, :3] = np.diag(f)
+    m[:3, 3] = (f - 1.0) / 2.0
+    return np.asarray(affine, dtype=np.float64) @ m
+
+
+def widen_box(pmin: Sequence[int], pmax: Sequence[int], grid: Sequence[int], min_size: Sequence[int]):
+    """The box pmin:pmax widened to at least `min_size` per axis: symmetrically, the extra voxel of an odd widening on
+    the low side, then shifted back into the grid.  The grid must hold `min_size`."""
+    lo, hi = [], []
+    for a, b, n, m in zip(pmin, pmax, grid, min_size):
+        a, b, n, m = int(a), int(b), int(n), int(m)
+        if m > n:
+            raise ValueError(f"grid extent {n} smaller than the least size {m}")
+        need = m - (b - a)
+        if need > 0:
+            a -= (need + 1) // 2
+            b += need // 2
+            if a < 0:
+                a, b = 0, b - a
+            if b > n:
+                a, b = a - (b - n), n
+        lo.append(a)
+        hi.append(b)
+    return tuple(lo), tuple(hi)
+
+
+def _triple(s, what: str, cast=float) -> tuple:
+    try:
+        v = tuple(cast(x) for x in (s.split(",") if isinstance(s, str) else s))
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 3 or not all(math.isfinite(x) and x > 0 for x in v):
+        raise PrepError(f"{what} {s!r}: needs three positive numbers d,h,w")
+    return v
+
+
+def parse_window(s, task: str) -> Optional[Tuple[float, float]]:
+    if s is None:
+        return WINDOW_DEFAULT[task]
+    if isinstance(s, str) and s.strip().lower() in ("none", ""):
+        return None
+    try:
+        lo, hi = (float(x) for x in (s.split(",") if isinstance(s, str) else s))
+    except (TypeError, ValueError):
+        raise PrepError(f"--prep_window {s!r}: needs lo,hi or none")
+    if not lo <= hi:
+        raise PrepError(f"--prep_window {s!r}: lo must not exceed hi")
+    return lo, hi
+
+
+# ---- the source list ---------------------------------------------------------------------------------------------------
+def read_src_list(path: str, task: str) -> List[dict]:
+    """The rows of --src_list, sorted by subject: {subject, images: {modality: path}, seg: path or None}.  Everything the
+    list alone decides is refused here, naming the row."""
+    mods = D.MODALITIES[task]
+    base = P.dirname(P.abspath(path))
+    with open(path, "r", newline="") as f:
+        rows = [r for r in csv.reader(f) if any(c.strip() for c in r)]
+    if not rows:
+        raise PrepError(f"--src_list {path}: empty")
+    head = [c.strip() for c in rows[0]]
+    want = set(mods)
+    if head[0] != "subject" or len(set(head)) != len(head) or set(head[1:]) - {D.LABEL_MODALITY} != want \
+            or len(head) not in (1 + len(mods), 2 + len(mods)):
+        raise PrepError(f"--src_list {path}: row 1: columns {head}, needs subject,{','.join(mods)}[,{D.LABEL_MODALITY}] "
+                        f"(each once)")
+    out, seen = [], set()
+    for i, r in enumerate(rows[1:], start=2):
+        cells = [c.strip() for c in r] + [""] * (len(head) - len(r))
+        if len(cells) != len(head):
+            raise PrepError(f"--src_list {path}: row {i}: {len(r)} cells for {len(head)} columns")
+        rec = dict(zip(head, cells))
+        sn = rec["subject"]
+        if not sn or "," in sn or "/" in sn or os.sep in sn or (os.altsep and os.altsep in sn) or sn in (".", ".."):
+            raise PrepError(f"--src_list {path}: row {i}: subject name {sn!r} is empty or holds a comma or a path separator")
+        if sn in seen:
+            raise PrepError(f"--src_list {path}: row {i}: subject {sn} is listed twice")
+        seen.add(sn)
+        entry = {"subject": sn, "images": {}, "seg": None, "row": i}
+        for col in head[1:]:
+            cell = rec[col]
+            if not cell:
+                if col == D.LABEL_MODALITY:
+                    continue
+                raise PrepError(f"--src_list {path}: row {i} (subject {sn}): no path for {col}")
+            full = cell if P.isabs(cell) else P.join(base, cell)
+            if not P.isfile(full):
+                raise PrepError(f"--src_list {path}: row {i} (subject {sn}): {col}: {full} is missing")
+            if "," in full or "\n" in full:
+                raise PrepError(f"--src_list {path}: row {i} (subject {sn}): {col}: a path with a comma cannot be named "
+                                f"in {D.SN_FN_FILE}")
+            if col == D.LABEL_MODALITY:
+                entry["seg"] = full
+            else:
+                entry["images"][col] = full
+        out.append(entry)
+    if not out:
+        raise PrepError(f"--src_list {path}: no subject")
+    return sorted(out, key=lambda e: e["subject"])
+
+
+def check_same_grid(subject: str, first: dict, other: dict, name: str) -> None:
+    """`other` (a header: shape, affine) must lie on the grid of the subject's first modality."""
+    if tuple(first["shape"][:3]) != tuple(other["shape"][:3]):
+        raise PrepError(f"subject {subject}: {name} has shape {tuple(other['shape'][:3])}, the first modality "
+                        f"{tuple(first['shape'][:3])}")
+    a, b = np.asarray(first["affine"], dtype=np.float64), np.asarray(other["affine"], dtype=np.float64)
+    dt = float(np.abs(a[:3, 3] - b[:3, 3]).max())
+    scale = float(np.abs(a[:3, :3]).max())
+    dl = float(np.abs(a[:3, :3] - b[:3, :3]).max())
+    if dt > AFFINE_TRANSLATION_TOL_MM or dl > AFFINE_LINEAR_RTOL * scale:
+        raise PrepError(f"subject {subject}: the affine of {name} differs from the first modality's (translation by "
+                        f"{dt:.4g} mm, 3 x 3 part by {dl:.4g})")
+
+
+class _Plan:
+    """What the headers of one subject decide."""
+
+    def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size):
+        sn = self.subject = entry["subject"]
+        self.entry = entry
+        heads = {}
+        for name, path in list(entry["images"].items()) + ([(D.LABEL_MODALITY, entry["seg"])] if entry["seg"] else []):
+            try:
+                h = nifti.read_geometry(path)
+            except (OSError, ValueError, EOFError) as e:
+                raise PrepError(f"subject {sn}: {name}: cannot read {path}: {e}") from e
+            if len(h["shape"]) > 3 and any(n != 1 for n in h["shape"][3:]):
+                raise PrepError(f"subject {sn}: {name}: {path} has shape {h['shape']}, only 3-D images are read")
+            if h["datatype"] not in nifti.IMAGE_DATATYPES:
+                raise PrepError(f"subject {sn}: {name}: {path} has datatype {h['datatype']}, one of "
+                                f"{sorted(nifti.IMAGE_DATATYPES)} is read")
+            heads[name] = h
+        first = heads[mods[0]]
+        for name, h in heads.items():
+            if name != mods[0]:
+                check_same_grid(sn, first, h, name)
+        self.source_shape = tuple(int(n) for n in first["shape"][:3])
+        self.source_spacing = tuple(first["spacing"])
+        self.affine = first["affine"]
+        if spacing is None:
+            self.factors, self.grid_shape, self.grid_spacing, self.grid_affine = None, self.source_shape, \
+                self.source_spacing, self.affine
+        else:
+            if min(self.source_spacing) <= 0:
+                raise PrepError(f"subject {sn}: source spacing {self.source_spacing} cannot be resampled")
+            self.factors = tuple(t / s for t, s in zip(spacing, self.source_spacing))
+            self.grid_shape = tuple(resample_extent(n, f) for n, f in zip(self.source_shape, self.factors))
+            self.grid_spacing = tuple(spacing)
+            self.grid_affine = resample_affine(self.affine, self.factors)
+        if any(g < m for g, m in zip(self.grid_shape, min_size)):
+            raise PrepError(f"subject {sn}: grid of {self.grid_shape} is smaller than --prep_min_size "
+                            f"{tuple(min_size)}: the validation's sliding window needs one whole patch")
+
+
+def _load(entry: dict, mods: Sequence[str]):
+    """Read one subject's files (the background thread): ({modality: array}, label or None), or the exception."""
+    try:
+        imgs = {m: nifti.read_image(entry["images"][m])[0] for m in mods}
+        seg = None
+        if entry["seg"]:
+            lab = nifti.read_image(entry["seg"])[0]
+            if lab.size and (np.any(lab != np.floor(lab)) or lab.min() < 0 or lab.max() > 255):
+                raise ValueError(f"the label {entry['seg']} is not integral within 0 ... 255")
+            seg = lab.astype(np.uint8)
+        return imgs, seg
+    except Exception as e:        # handed to the main thread, which names the subject
+        return e
+
+
+# ---- the files ---------------------------------------------------------------------------------------------------------
+def _replace(path: str, write) -> None:
+    tmp = path + ".tmp"
+    write(tmp)
+    os.replace(tmp, path)
+
+
+def _replace_text(path: str, text: str) -> None:
+    def dump(p):
+        with open(p, "w") as f:
+            f.write(text)
+    _replace(path, dump)
+
+
+def _save_array(data_dir: str, modality: str, subject: str, access_type: str, a: np.ndarray) -> None:
+    os.makedirs(P.join(data_dir, modality), exist_ok=True)
+    if access_type == "npz":
+        np.savez(P.join(data_dir, modality, f"{subject}.npz"), a)
+    else:
+        np.save(P.join(data_dir, modality, f"{subject}.npy"), a)
+
+
+def _read_sn_fn_raw(data_dir: str) -> Dict[str, str]:
+    out = {}
+    path = P.join(data_dir, D.SN_FN_FILE)
+    if P.isfile(path):
+        with open(path, "r") as f:
+            for line in f.read().splitlines():
+                if line.strip() and line.count(",") == 1:
+                    sn, fn = (s.strip() for s in line.split(","))
+                    out[sn] = fn
+    return out
+
+
+def write_index_files(data_dir: str, sn_fn: Dict[str, str], restore: Dict[str, Optional[dict]], rows: List[dict],
+                      header: List[str]) -> None:
+    """sn_fn.txt, the restore pickle and prep.csv, each merged with the file an earlier run left (the newer entry wins,
+    lines sorted by subject) and written through a temporary file and a rename."""
+    names = dict(_read_sn_fn_raw(data_dir))
+    names.update(sn_fn)
+    _replace_text(P.join(data_dir, D.SN_FN_FILE), "".join(f"{sn},{names[sn]}\n" for sn in sorted(names)))
+    kept = dict(D.read_restore_info(data_dir) or {})
+    for sn, kw in restore.items():
+        if kw is None:
+            kept.pop(sn, None)
+        else:
+            kept[sn] = {k: tuple(int(v) for v in kw[k]) for k in ("pmin", "pmax", "shape")}
+    if kept or P.isfile(P.join(data_dir, D.RESTORE_FILE)):
+        def dump(p):
+            with open(p, "wb") as f:
+                pickle.dump({sn: kept[sn] for sn in sorted(kept)}, f, protocol=4)
+        _replace(P.join(data_dir, D.RESTORE_FILE), dump)
+    old = {}
+    path = P.join(data_dir, PREP_CSV)
+    if P.isfile(path):
+        with open(path, "r", newline="") as f:
+            r = list(csv.reader(f))
+        if r and r[0] == header:
+            old = {line[0]: line for line in r[1:] if line}
+    for row in rows:
+        old[row["subject"]] = [row[k] for k in header]
+
+    def dump_csv(p):
+        with open(p, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(header)
+            w.writerows(old[sn] for sn in sorted(old))
+    _replace(path, dump_csv)
+
+
+def prep_csv_header(mods: Sequence[str]) -> List[str]:
+    return ["subject", "source_shape", "source_spacing", "grid_shape", "grid_spacing", "pmin", "pmax"] + \
+        [f"{m}_{k}" for m in mods for k in ("count", "mean", "std")]
+
+
+def _fmt(v) -> str:
+    return " ".join(f"{x:.7g}" if isinstance(x, float) else str(int(x)) for x in v)
+
+
+# ---- one subject on the device -------------------------------------------------------------------------------------------
+def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str],
+                    mask: str, window, min_size, no_crop: bool):
+    """The device pipeline of one subject.  Returns (arrays C x d x h x w float32, label or None, union mask of the grid
+    or None, pmin, pmax, count, mean, std), host arrays."""
+    sn = plan.subject
+    for m in mods:
+        if tuple(imgs[m].shape) != plan.source_shape:
+            raise PrepError(f"subject {sn}: {m} holds an array of shape {tuple(imgs[m].shape)}, its header says "
+                            f"{plan.source_shape}")
+    if seg is not None and tuple(seg.shape) != plan.source_shape:
+        raise PrepError(f"subject {sn}: the label holds an array of shape {tuple(seg.shape)}, not {plan.source_shape}")
+    dev = ops.device
+    x = torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
+    lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
+    if window is not None:
+        ops.prep_window(x, window[0], window[1])
+    if plan.factors is not None:
+        x = ops.prep_resample(x, plan.factors, plan.grid_shape)
+        if lab is not None:
+            lab = ops.prep_resample(lab, plan.factors, plan.grid_shape, nearest=True)
+    bbox, count, total = ops.prep_bbox_moments(x, mask)
+    bbox, count, total = bbox.cpu().tolist(), count.cpu().tolist(), total.cpu().tolist()
+    if any(a > b for a, b in zip(bbox[:3], bbox[3:])):
+        raise PrepError(f"subject {sn}: every voxel of every modality is zero: there is no body to crop to")
+    for m, n in zip(mods, count):
+        if n < 2:
+            raise PrepError(f"subject {sn}: modality {m}: {n} voxels inside the mask, the standard deviation needs two")
+    mean = [s / n for s, n in zip(total, count)]
+    sqdev = ops.prep_sqdev(x, mean, mask).cpu().tolist()
+    std = [math.sqrt(q / n) for q, n in zip(sqdev, count)]
+    for m, s in zip(mods, std):
+        if not s > 0.0 or not math.isfinite(s):
+            raise PrepError(f"subject {sn}: modality {m}: standard deviation {s} over the mask: a constant (or "
+                            f"non-finite) image cannot be standardised")
+    if no_crop:
+        pmin, pmax = (0, 0, 0), tuple(plan.grid_shape)
+    else:
+        pmin, pmax = widen_box(bbox[:3], [b + 1 for b in bbox[3:]], plan.grid_shape, min_size)
+    y = ops.prep_standardise_crop(x, pmin, pmax, mean, std, mask)
+    lab_out = ops.prep_crop_u8(lab, pmin, pmax)[0].cpu().numpy() if lab is not None else None
+    union = ops.prep_union_mask(x, mask).cpu().numpy() if plan.factors is not None else None
+    return y.cpu().numpy(), lab_out, union, pmin, pmax, count, mean, std
+
+
+# ---- the mission -------------------------------------------------------------------------------------------------------
+def run(args, ops=None) -> List[dict]:
+    """The `prep` mission of `args` (config.build_parser); returns the rows of prep.csv of this run.  `ops`: the object
+    whose prep_* methods do the device work and whose `device` holds the tensors, hip_ops.get_ops(args.device) by
+    default."""
+    task = (getattr(args, "task", None) or "").lower()
+    if task not in D.MODALITIES:
+        raise PrepError(f"prep: --task {getattr(args, 'task', None)!r}, one of {', '.join(D.MODALITIES)}")
+    if not getattr(args, "src_list", None) or not getattr(args, "data_dir", None):
+        raise PrepError("prep: needs --src_list and --data_dir")
+    mods = D.MODALITIES[task]
+    mask = getattr(args, "prep_mask", None) or MASK_DEFAULT[task]
+    if mask not in ("nonzero", "all"):
+        raise PrepError(f"--prep_mask {mask!r}: nonzero or all")
+    window = parse_window(getattr(args, "prep_window", None), task)
+    spacing = _triple(args.prep_spacing, "--prep_spacing") if getattr(args, "prep_spacing", None) else None
+    min_size = _triple(args.prep_min_size, "--prep_min_size", int) if getattr(args, "prep_min_size", None) \
+        else D.PATCH_DEFAULT[task]
+    no_crop = bool(getattr(args, "prep_no_crop", False))
+    access = getattr(args, "access_type", None) or "npy"
+    if access not in D.ACCESS_TYPES:
+        raise PrepError(f"--access_type {access!r}: one of {', '.join(D.ACCESS_TYPES)}")
+    data_dir = args.data_dir
+
+    # everything the list and the headers decide, before anything is written
+    entries = read_src_list(args.src_list, task)
+    plans = [_Plan(e, mods, spacing, min_size) for e in entries]
+    split = None
+    if getattr(args, "split_dir", None):
+        k = getattr(args, "val_every", None)
+        if k is None or int(k) < 1:
+            raise PrepError("--split_dir: needs --val_every K (K >= 1): every K-th of the sorted subjects validates")
+        split = P.join(args.split_dir, f"round{args.round}")
+        for name in ("train.txt", "val.txt"):
+            if P.exists(P.join(split, name)):
+                raise PrepError(f"--split_dir: {P.join(split, name)} exists already: prep does not overwrite a split")
+        k = int(k)
+    if ops is None:
+        from .hip_ops import get_ops
+        ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
+
+    os.makedirs(data_dir, exist_ok=True)
+    sn_fn, restore, rows = {}, {}, []
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-prep-read")
+    try:
+        nxt = pool.submit(_load, entries[0], mods)
+        for i, plan in enumerate(plans):
+            got = nxt.result()
+            nxt = pool.submit(_load, entries[i + 1], mods) if i + 1 < len(entries) else None
+            sn = plan.subject
+            if isinstance(got, Exception):
+                raise PrepError(f"subject {sn}: {got}") from got
+            imgs, seg = got
+            y, lab, union, pmin, pmax, count, mean, std = process_subject(ops, plan, imgs, seg, mods, mask, window,
+                                                                          min_size, no_crop)
+            for c, m in enumerate(mods):
+                _save_array(data_dir, m, sn, access, y[c])
+            if lab is not None:
+                _save_array(data_dir, D.LABEL_MODALITY, sn, access, lab)
+            if union is not None:
+                os.makedirs(P.join(data_dir, GRID_DIR), exist_ok=True)
+                nifti.write_nifti(P.join(data_dir, GRID_DIR, f"{sn}.nii.gz"), union, plan.grid_affine)
+                sn_fn[sn] = f"{GRID_DIR}/{sn}.nii.gz"
+            else:
+                sn_fn[sn] = P.abspath(plan.entry["images"][mods[0]])
+            cropped = tuple(y.shape[1:]) != tuple(plan.grid_shape)
+            restore[sn] = {"pmin": pmin, "pmax": pmax, "shape": plan.grid_shape} if cropped else None
+            row = {"subject": sn, "source_shape": _fmt(plan.source_shape), "source_spacing": _fmt(plan.source_spacing),
+                   "grid_shape": _fmt(plan.grid_shape), "grid_spacing": _fmt(plan.grid_spacing), "pmin": _fmt(pmin),
+                   "pmax": _fmt(pmax)}
+            for c, m in enumerate(mods):
+                row.update({f"{m}_count": str(int(count[c])), f"{m}_mean": repr(float(mean[c])),
+                            f"{m}_std": repr(float(std[c]))})
+            rows.append(row)
+            print(f"[prep] {sn}: {_fmt(plan.source_shape)} -> {_fmt(y.shape[1:])} at {_fmt(pmin)}")
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+    write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods))
+    if split is not None:
+        names = [p.subject for p in plans]
+        val = names[k - 1::k]
+        os.makedirs(split, exist_ok=True)
+        for name, sns in (("train.txt", [s for s in names if s not in set(val)]), ("val.txt", val)):
+            _replace_text(P.join(split, name), "".join(s + "\n" for s in sns))
+    print(f"[prep] {len(rows)} subjects written to {data_dir}")
+    return rows

@@ -737,6 +737,48 @@ int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D,
                         float thresh, float wd, float wh, float ww, long long* counts, float* sq, double* sums, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- the `prep` mission (prep.py): source scans to the standardised, cropped arrays the `ptq` mission reads.  One
+ * subject at a time: x (C, D, H, W) fp32, contiguous, S = D H W voxels per modality, C <= EFFQ_PREP_MAX_MODALITIES,
+ * C S < 2^31, every extent <= 32767.  mask_mode EFFQ_PREP_MASK_NONZERO: the mask of modality c is x_c != 0 (a NaN is
+ * inside); EFFQ_PREP_MASK_ALL: every voxel.  All pointers are device memory except pmin / pmax (three host ints each,
+ * read before the call returns).  Reductions go through per-workgroup partials in `ws` (EFFQ_PREP_WS_BYTES, 8-B aligned)
+ * and one finishing workgroup that adds them in block order: no floating-point atomics, equal inputs give equal bits.
+ * fp32 pointers need 4-B alignment only (16-B accesses go through a type of that alignment).  Nothing is read by the
+ * host, no workgroup waits for another; bad arguments return EFFQ_ERR_ARG and launch nothing.
+ *
+ * window:  x[i] = x[i] < lo ? lo : x[i] > hi ? hi : x[i] in place (numpy.clip; a NaN stays), lo <= hi.
+ * resample: x (N, D, H, W) -> y (N, OD, OH, OW) with the factors f = target spacing / source spacing per axis; the
+ *   caller gives the output extents (prep.resample_extent).  Output index o of an axis of source extent n:
+ *   EFFQ_PREP_LINEAR (fp32 in and out): s = (o + 0.5) f - 0.5 in fp64, clamped to [0, n - 1]; i0 = floor(s), i1 =
+ *     min(i0 + 1, n - 1), l1 = float(s - i0), l0 = 1.0f - l1; the eight neighbours are combined in fp32 as
+ *     l0d (l0h (l0w v000 + l1w v001) + l1h (l0w v010 + l1w v011)) + l1d (...), nothing fused.  No filter before
+ *     down-sampling.
+ *   EFFQ_PREP_NEAREST (uint8 in and out): index min(n - 1, floor((o + 0.5) f)) per axis.
+ * bbox_moments (pass 1): bbox_out[6] int32 = the least d, h, w and the greatest d, h, w of the union of the modalities'
+ *   masks (the whole grid for MASK_ALL; least = the extent and greatest = -1 when the union is empty); count_out[C]
+ *   int64 and sum_out[C] fp64 = the voxels of modality c's own mask and the sum of their values.  Two launches.
+ * sqdev (pass 2): sqdev_out[C] fp64 = sum over the mask of (double(x) - mean[c])^2.  Two launches.
+ * standardise_crop (pass 3): y (C, pmax - pmin) = mask ? float((double(x) - mean[c]) / std[c]) : +0.0f over the box
+ *   pmin <= (d, h, w) < pmax.
+ * crop_u8: the same box of C uint8 volumes (the label).
+ * union_mask: mask (S) uint8 = 1 where any modality's mask holds, else 0. */
+#define EFFQ_PREP_MAX_MODALITIES 4
+#define EFFQ_PREP_WS_BYTES (1024 * (2 * EFFQ_PREP_MAX_MODALITIES * 8 + 8 * 4))
+enum { EFFQ_PREP_MASK_NONZERO = 0, EFFQ_PREP_MASK_ALL = 1 };
+enum { EFFQ_PREP_LINEAR = 0, EFFQ_PREP_NEAREST = 1 };
+int effq_prep_window(float* x, size_t n, float lo, float hi, void* stream);
+int effq_prep_resample(const void* x, int N, int D, int H, int W, double fd, double fh, double fw, int mode, void* y,
+                       int OD, int OH, int OW, void* stream);
+int effq_prep_bbox_moments(const float* x, int C, int D, int H, int W, int mask_mode, int* bbox_out, long long* count_out,
+                           double* sum_out, void* ws, size_t ws_bytes, void* stream);
+int effq_prep_sqdev(const float* x, int C, long long S, int mask_mode, const double* mean, double* sqdev_out, void* ws,
+                    size_t ws_bytes, void* stream);
+int effq_prep_standardise_crop(const float* x, int C, int D, int H, int W, int mask_mode, const int* pmin,
+                               const int* pmax, const double* mean, const double* stdev, float* y, void* stream);
+int effq_prep_crop_u8(const uint8_t* x, int C, int D, int H, int W, const int* pmin, const int* pmax, uint8_t* y,
+                      void* stream);
+int effq_prep_union_mask(const float* x, int C, long long S, int mask_mode, uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
