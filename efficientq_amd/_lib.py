@@ -187,6 +187,7 @@ SIGNATURES = {
     "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
+    "effq_seg_labels_source": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P]),
     "effq_seg_agreement": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),

@@ -360,6 +360,60 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
     return res
 
 
+def load_calibrated(model: nn.Module, path: str, device):
+    """Put a snapshot do_ptq wrote back into the freshly built `model` (the network of the same --config and levels):
+    fold the BN layers as do_ptq does before it calibrates (the snapshots hold the folded network), load the state
+    dict strictly, move the model to `device` and set it to the quantised mode.  Returns the model.
+    state_in_fp.pkl: the weights as they are - the logits are those of the calibrated model in memory, bit for bit.
+    state_in_int8.pkl (integer weights on the quantised convs): the level ids are loaded and every conv's
+    restore_fp_weight() puts them back on alpha_w's grid.  In channel mode (alpha_w of shape (c2, 1, 1, 1): the model
+    must be built with lwq_channel_wise) that is exact.  In per-tensor mode the snapshot holds the LAST iterate's alpha_w
+    beside the BEST iterate's ids (quirk Q6): the restored weights lie on that grid but are not the calibrated weights;
+    one line says so.
+    A snapshot whose keys or shapes do not fit the network ends with a SystemExit naming the first missing and the
+    first unexpected key; the model is then as it was built, but for the folding."""
+    try:
+        blob = torch.load(path, map_location='cpu')
+    except Exception as e:
+        raise SystemExit(f'--resume {path}: cannot read the snapshot: {e}')
+    sd = blob.get('state_dict') if isinstance(blob, dict) else None
+    if not isinstance(sd, dict) or not all(torch.is_tensor(v) for v in sd.values()):
+        raise SystemExit(f"--resume {path}: no 'state_dict' of tensors inside: not a snapshot of the ptq mission")
+    model.eval()
+    search_fold_and_remove_bn(model)
+    own = model.state_dict()
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    shapes = [k for k in own if k in sd and tuple(own[k].shape) != tuple(sd[k].shape)]
+    if missing or unexpected or shapes:
+        parts = []
+        if missing:
+            parts.append(f'{len(missing)} keys of the network are missing, the first {missing[0]}')
+        if unexpected:
+            parts.append(f'{len(unexpected)} keys are unexpected, the first {unexpected[0]}')
+        if shapes:
+            k = shapes[0]
+            parts.append(f'{len(shapes)} shapes differ, the first {k}: {tuple(sd[k].shape)} in the snapshot, '
+                         f'{tuple(own[k].shape)} in the network')
+        raise SystemExit(f'--resume {path}: the snapshot does not fit the network of --config (widths, levels, '
+                         f'--lwq_channel_wise?): ' + '; '.join(parts))
+    convs = list(_each_q(model))
+    ints = [name for name, _ in convs if not sd[name + '.weight'].dtype.is_floating_point]
+    if ints and len(ints) != len(convs):
+        raise SystemExit(f'--resume {path}: integer weights on {len(ints)} of {len(convs)} quantised convs: the first '
+                         f'is {ints[0]}')
+    model.load_state_dict(sd, strict=True)
+    if ints:
+        restore_fp_weight(model)
+        if not all(q.channel_wise for _, q in convs):
+            print(f'[resume] {path}: per-tensor level ids were stored beside the last iterate\'s alpha_w, not the best '
+                  f'iterate\'s (quirk Q6): the restored weights lie on that grid but are not the calibrated weights; '
+                  f'state_in_fp.pkl holds those exactly')
+    model.to(device)
+    set_quantized(model)
+    return model
+
+
 def _volume_offset(n: int) -> int:
     """Index of this rank's first calibration volume in the whole batch: the volume count of the lower ranks."""
     import torch.distributed as dist

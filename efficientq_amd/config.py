@@ -1,4 +1,4 @@
-"""CLI / YAML surface of both missions (``prep``: prep.py) and factories of the ``ptq`` mission, same flag names and semantics as the
+"""CLI / YAML surface of the missions (``prep``: prep.py, ``predict``: predict.py) and factories of the ``ptq`` mission, same flag names and semantics as the
 reference (src/entrance.py:17-128, src/definer.py:130-248,286-329): YAML values override the
 command line for every non-null key (quirk Q15); ``qlvl_*`` are LEVEL counts (4 => 2-bit);
 ``q_first/q_last "W,A"`` with A=-1 => full-precision activations (quirk Q14); every ``lwq_*``
@@ -29,7 +29,7 @@ def merge_config(cfg: str, args: argparse.Namespace):
 
 def build_parser():
     p = argparse.ArgumentParser(description='EfficientQ PTQ calibration on MI355X')
-    p.add_argument('mission', choices=['ptq', 'prep'])
+    p.add_argument('mission', choices=['ptq', 'prep', 'predict'])
     p.add_argument('--pretrain')
     p.add_argument('--resume')
     p.add_argument('--device', default=0, type=int, help='GPU ID.')
@@ -98,6 +98,8 @@ def build_parser():
     p.add_argument('--prep_spacing', default=None, help='prep: d,h,w in mm to resample every subject to')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
+    # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint
+    p.add_argument('--out_dir', default=None, help='predict: where <subject>.nii.gz and predict.csv are written')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')

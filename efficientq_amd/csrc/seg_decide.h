@@ -48,6 +48,24 @@ __device__ __forceinline__ uint32_t predict(const float* v, int fuse, float thre
   return pred;
 }
 
+// the label of one voxel from its predicted classes, for the label maps on the working grid (seg_eval.hip) and on the
+// source grid (seg_source.hip)
+template <int RULE, int C>
+__device__ __forceinline__ uint32_t label_of(uint32_t pred) {
+  if constexpr (RULE == EFFQ_SEG_LABEL_ARGMAX) {
+    return 31 - __builtin_clz(pred);                  // pred = 1 << winning class
+  } else if constexpr (RULE == EFFQ_SEG_LABEL_BRATS) {
+    // misc.merge_label_brats, later assignments winning: WT -> 1, WT and not TC -> 2, ET -> 4
+    uint32_t l = 0;
+    if (pred & 1u) l = 1;
+    if ((pred & 3u) == 1u) l = 2;
+    if (pred & 4u) l = 4;
+    return l;
+  } else {                                            // RANK: i + 1 of the highest set channel, 0 when none
+    return pred ? 32 - __builtin_clz(pred) : 0u;
+  }
+}
+
 // the decisions of one voxel: pred / gt bit c for class c
 template <int MODE, int C>
 __device__ __forceinline__ void decide(const float* v, const uint8_t* lab, int fuse, float thresh, uint32_t& pred,

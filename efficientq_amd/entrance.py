@@ -30,6 +30,13 @@ The ``prep`` mission (prep.py) writes that layout from source NIfTI scans:
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data --split_dir out/split \
         --val_every 5
+
+The ``predict`` mission (predict.py) segments new scans with a snapshot the ``ptq`` mission wrote (``--resume``, loaded by
+calibrate.load_calibrated) or with the FP checkpoint (``--pretrain --qconv conv``), and writes one uint8 label map per
+subject on the scan's own grid, with the scan's header, and ``predict.csv``:
+
+    python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
+        --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/
 """
 from __future__ import annotations
 
@@ -199,6 +206,10 @@ def main(argv=None):
     if args.mission == 'prep':
         from . import prep
         prep.run(args)
+        return
+    if args.mission == 'predict':
+        from . import predict
+        predict.run(args)
         return
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)

@@ -286,6 +286,47 @@ def _vs_fp(ops, q, f, kind, fuse, shape, spacing, lesions, surface, want_map) ->
 
 
 @torch.no_grad()
+def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_batch=None):
+    """The sliding-window forward of validate_seg and of the `predict` mission: the windows of `vol` (N x C x D x H x W
+    fp32 on the device of `ops`) gathered into batches of `window_batch` (effq_window_gather), every network of `nets`
+    run on each batch, its last head copied into the network's window buffer and the buffer stitched
+    (effq_window_stitch).  window_batch=None: the first window runs alone and its peak memory - over all the forwards
+    of `nets` - sizes the batches, half the free device memory at most WINDOW_BATCH_MAX windows.  Returns (one stitched
+    N x classes x D x H x W tensor per network, the number of windows, the window batch in use): a caller hands the
+    last back in for its next volume."""
+    from .hip_ops import from_ndhwc
+    dev = vol.device
+    p, o = _triple(patch), _triple(overlap)
+    bsz = window_batch
+    N = int(vol.shape[0])
+    nwin = 1
+    for n in ops.window_grid(vol.shape[-3:], p, o):
+        nwin *= n
+    bufs = [None] * len(nets)
+    first = 0
+    while first < nwin:
+        cnt = min(bsz or 1, nwin - first)
+        if bsz is None:
+            torch.cuda.synchronize(dev)
+            base = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+        x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
+        for k, net in enumerate(nets):      # the peak below covers every forward
+            last = _last_head(net(x))
+            if bufs[k] is None:
+                bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+            bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+            del last
+        if bsz is None:
+            per = max(1, torch.cuda.max_memory_allocated(dev) - base)
+            free, _ = torch.cuda.mem_get_info(dev)
+            bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
+        first += cnt
+    full = (N,) + tuple(bufs[0].shape[-1:]) + tuple(vol.shape[-3:])
+    return [ops.window_stitch(b, full, p, o) for b in bufs], nwin, bsz
+
+
+@torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
                  geometry=None, lesion_table=False, fp_model=None):
@@ -331,7 +372,7 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     a source geometry.  The window batches are sized for both forwards.  A case whose label is empty (numel() == 0,
     data.SegVolumes(labels=False)) is unlabelled: it needs fp_model, takes the counting from `multi_label` (set: sigmoid
     per channel, else argmax) and its dict carries name and vs_fp only."""
-    from .hip_ops import from_ndhwc, get_ops
+    from .hip_ops import get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
     dev = next(model.parameters()).device
@@ -358,33 +399,10 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                                    f"FP network only (fp_model=...)")
             vol = images.to(dev, torch.float32).contiguous()
             N = int(vol.shape[0])
-            nwin = 1
-            for n in ops.window_grid(vol.shape[-3:], p, o):
-                nwin *= n
             nets = [model] if fp_model is None else [model, fp_model]
-            bufs = [None] * len(nets)
-            first = 0
-            while first < nwin:
-                cnt = min(bsz or 1, nwin - first)
-                if bsz is None:
-                    torch.cuda.synchronize(dev)
-                    base = torch.cuda.memory_allocated(dev)
-                    torch.cuda.reset_peak_memory_stats(dev)
-                x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
-                for k, net in enumerate(nets):      # the peak below covers both forwards
-                    last = _last_head(net(x))
-                    if bufs[k] is None:
-                        bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-                    bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
-                    del last
-                if bsz is None:
-                    per = max(1, torch.cuda.max_memory_allocated(dev) - base)
-                    free, _ = torch.cuda.mem_get_info(dev)
-                    bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
-                first += cnt
-            full = (N,) + tuple(bufs[0].shape[-1:]) + tuple(vol.shape[-3:])
-            stitched = ops.window_stitch(bufs[0], full, p, o)
-            stitched_fp = ops.window_stitch(bufs[1], full, p, o) if fp_model is not None else None
+            outs, _, bsz = stitched_window_logits(ops, nets, vol, p, o, bsz)
+            stitched = outs[0]
+            stitched_fp = outs[1] if fp_model is not None else None
             lab = labels.to(dev).to(torch.uint8) if labelled else None
             # one 0/1 channel per class (--multi_label): sigmoid, as evaluate_append; without a label multi_label decides
             multi = lab.dim() == vol.dim() if labelled else bool(multi_label)

@@ -1154,6 +1154,46 @@ class HipOps:
                                        out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
         return out
 
+    def seg_labels_source(self, logits: torch.Tensor, pmin, grid, factors, source_shape, rule: str,
+                          fuse: Optional[str] = None) -> torch.Tensor:
+        """The label map of one subject on its SOURCE grid (effq_seg_labels_source): `logits` C x d x h x w fp32 are the
+        stitched logits on the box pmin : pmin + (d, h, w) of the working grid `grid`, which prep made from the source
+        grid `source_shape` with `factors` = target spacing / source spacing per axis (None: 1, no resampling).  Every
+        source voxel whose centre falls into the box gets the label of `rule` ('argmax', 'brats', 'rank'; 'planes' is
+        refused) and `fuse` from the trilinearly interpolated logits, every other voxel 0.  Returns uint8 of
+        `source_shape`."""
+        x = self._f32(logits)
+        if x.dim() != 4:
+            raise _lib.EffqError(f"seg_labels_source: expected C x d x h x w logits, got {tuple(x.shape)}")
+        Cc = int(x.shape[0])
+        if rule not in _lib.SEG_LABEL_RULES:
+            raise _lib.EffqError(f"seg_labels_source: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (rule == "argmax" and key is not None):
+            raise _lib.EffqError(f"seg_labels_source: merge type {fuse!r} for rule {rule}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_labels_source: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if rule == "brats" and Cc < 3:
+            raise _lib.EffqError(f"seg_labels_source: the brats rule needs 3 channels or more, got {Cc}")
+        try:
+            lo, G, src = (tuple(int(v) for v in t) for t in (pmin, grid, source_shape))
+            f = (1.0, 1.0, 1.0) if factors is None else tuple(float(v) for v in factors)
+        except (TypeError, ValueError) as e:
+            raise _lib.EffqError(f"seg_labels_source: {e}") from e
+        if len(lo) != 3 or len(G) != 3 or len(src) != 3 or len(f) != 3 or x.numel() == 0:
+            raise _lib.EffqError(f"seg_labels_source: box at {lo} of {tuple(x.shape[1:])}, grid {G}, factors {f}, source "
+                                 f"{src}: three values each")
+        if min(src) < 1 or max(src) > 32767 or math.prod(src) >= 2 ** 31:     # the output is not allocated for these
+            raise _lib.EffqError(f"seg_labels_source: source grid {src}: 1 to 32767 along an axis, 2^31 - 1 voxels at most")
+        out = torch.empty(src, dtype=torch.uint8, device=self.device)
+        thresh = 0.0 if rule == "argmax" else self.sigmoid_threshold()
+        i3 = C.c_int * 3
+        check(self.lib.effq_seg_labels_source(_ptr(x), Cc, i3(*(int(v) for v in x.shape[1:])), i3(*lo), i3(*G),
+                                              (C.c_double * 3)(*f), i3(*src), _lib.SEG_LABEL_RULES[rule],
+                                              _lib.SEG_FUSE[key], thresh, _ptr(out), self.stream),
+              "effq_seg_labels_source")
+        return out
+
     def seg_agreement(self, logits_q: torch.Tensor, logits_fp: torch.Tensor, mode: str, fuse: Optional[str] = None,
                       want_map: bool = False):
         """Where and how much two networks differ on one case (effq_seg_agreement): the stitched last-head logits of the

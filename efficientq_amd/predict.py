@@ -1,0 +1,202 @@
+"""The ``predict`` mission: segment new scans with a calibrated snapshot and write label maps that overlay the scans.
+
+    python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
+        --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/ \
+        [--prep_window -200,250 --prep_spacing 1,1,2.5 --prep_mask all --prep_min_size d,h,w --patch_size d,h,w]
+
+``--src_list`` is the CSV of the ``prep`` mission (prep.read_src_list; a ``seg`` column is allowed and ignored).  The
+``--prep_*`` switches and ``--patch_size`` mean what they mean in ``prep`` and ``ptq`` and have the same per-task
+defaults (``--prep_min_size``: the patch); they must be what the calibration data was prepared with, and the values used
+are written into ``predict.csv``.  The network is exactly one of ``--resume`` (a snapshot of the ``ptq`` mission,
+calibrate.load_calibrated) and ``--pretrain`` with ``--qconv conv`` (the FP checkpoint, folded as do_ptq folds it).
+
+Per subject: the scans are read (the next subject's by one background thread), windowed, resampled, standardised and
+cropped in memory (prep.process_subject), the windows of the crop run through the network and the last head is stitched
+(evaluate.stitched_window_logits), and effq_seg_labels_source turns the stitched logits on the working grid into one
+label per voxel of the scan's own grid: ``<out_dir>/<subject>.nii.gz``, uint8, with the header of the first modality,
+written by a background thread.  ``<out_dir>/predict.csv`` gets one row per subject: the source shape and spacing, the
+grid, the box, the number of windows, the prep options used, and per label value present in the map its voxel count
+(counted on the device) and its volume in ml.
+
+Everything the list and the headers decide, ``--multi_label lits`` (one plane per class has no place on a source grid)
+and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
+"""
+from __future__ import annotations
+
+import csv
+import os
+import os.path as P
+from concurrent.futures import ThreadPoolExecutor
+from typing import List
+
+import numpy as np
+import torch
+
+from . import data as D
+from . import evaluate as E
+from . import nifti
+from . import prep
+from .prep import PrepError
+
+PREDICT_CSV = "predict.csv"
+MAX_PENDING_WRITES = 2        # host maps waiting for the writing thread at most
+CSV_HEADER = ["subject", "source_shape", "source_spacing", "grid_shape", "pmin", "pmax", "windows", "prep_mask",
+              "prep_window", "prep_spacing", "prep_min_size", "patch_size", "labels", "voxels", "volume_ml"]
+
+
+def _network(args, dev):
+    """The network of --resume / --pretrain on `dev`, in the mode it is to run in."""
+    from . import calibrate as K
+    from . import config as Cf
+    QConv, _, kwQ = Cf.get_conv_class(args)
+    model = Cf.get_model_cube(args, QConv, kwQ)[0]["model"]
+    if args.resume:
+        return K.load_calibrated(model, args.resume, dev)
+    try:
+        sd = torch.load(args.pretrain, map_location="cpu")["state_dict"]
+    except Exception as e:
+        raise SystemExit(f"--pretrain {args.pretrain}: cannot read the checkpoint: {e}")
+    if not isinstance(sd, dict):
+        raise SystemExit(f"--pretrain {args.pretrain}: its 'state_dict' is no dict of tensors")
+    # not strict, as do_ptq loads it (a training checkpoint may carry more than the network); but a checkpoint that
+    # fits no key, or leaves a key of the network unset, would segment with random weights: refused, by key
+    own = model.state_dict()
+    missing = [k for k in own if k not in sd]
+    unexpected = [k for k in sd if k not in own]
+    shapes = [k for k in own if k in sd and tuple(own[k].shape) != tuple(sd[k].shape)]
+    if missing or shapes:
+        what = (f"{len(missing)} keys of the network are missing, the first {missing[0]}" if missing else
+                f"{len(shapes)} shapes differ, the first {shapes[0]}: {tuple(sd[shapes[0]].shape)} in the checkpoint, "
+                f"{tuple(own[shapes[0]].shape)} in the network")
+        if unexpected:
+            what += f"; {len(unexpected)} keys are unexpected, the first {unexpected[0]}"
+        raise SystemExit(f"--pretrain {args.pretrain}: the checkpoint does not fit the network of --config: {what}")
+    if unexpected:
+        print(f"[predict] --pretrain {args.pretrain}: {len(unexpected)} keys of the checkpoint are not the network's "
+              f"and are ignored, the first {unexpected[0]}")
+    model.load_state_dict(sd, strict=False)
+    model.eval()
+    K.search_fold_and_remove_bn(model)
+    model.to(dev)
+    K.set_fp(model)
+    return model
+
+
+def _write_csv(path: str, rows: List[dict]) -> None:
+    def dump(p):
+        with open(p, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(CSV_HEADER)
+            w.writerows([r[k] for k in CSV_HEADER] for r in rows)
+    prep._replace(path, dump)
+
+
+def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
+    """The `predict` mission of `args` (config.build_parser); returns the rows of predict.csv.  `ops`: the object whose
+    prep_*, window_* and seg_labels_source methods do the device work and whose `device` holds the tensors
+    (hip_ops.get_ops(args.device) by default); `model`: the network, already on that device and in its mode (by default
+    the one --resume / --pretrain name); `window_batch`: windows per forward (None: sized from the first window's peak
+    memory, as validate_seg sizes it)."""
+    task = (getattr(args, "task", None) or "").lower()
+    if task not in D.MODALITIES:
+        raise PrepError(f"predict: --task {getattr(args, 'task', None)!r}, one of {', '.join(D.MODALITIES)}")
+    if not getattr(args, "src_list", None) or not getattr(args, "out_dir", None):
+        raise PrepError("predict: needs --src_list and --out_dir")
+    if model is None:
+        resume, pretrain = getattr(args, "resume", None), getattr(args, "pretrain", None)
+        if bool(resume) == bool(pretrain):
+            raise SystemExit(f"predict: needs exactly one of --resume (a calibrated snapshot of the ptq mission) and "
+                             f"--pretrain (the FP checkpoint, with --qconv conv), got "
+                             f"{'both' if resume else 'neither'}")
+        if pretrain and (getattr(args, "qconv", None) or "conv").lower() != "conv":
+            raise SystemExit(f"predict: --pretrain is the FP checkpoint and runs with --qconv conv, not --qconv "
+                             f"{args.qconv}: a calibrated network is loaded with --resume")
+        if resume and not P.isfile(resume):
+            raise SystemExit(f"--resume {resume}: no such file")
+        if pretrain and not P.isfile(pretrain):
+            raise SystemExit(f"--pretrain {pretrain}: no such file")
+    multi_label = getattr(args, "multi_label", None)
+    try:
+        rule = E.label_rule(bool(multi_label), multi_label, task)
+    except RuntimeError as e:
+        raise PrepError(f"predict: {e}")
+    if rule == "planes":
+        raise PrepError(f"predict: the maps of --multi_label {multi_label} hold one plane per class (C x D x H x W); a "
+                        f"NIfTI image has its spatial axes first, so they cannot be written on the source grid")
+    fuse = getattr(args, "merge_type", None) if multi_label else None
+    mods = D.MODALITIES[task]
+    mask = getattr(args, "prep_mask", None) or prep.MASK_DEFAULT[task]
+    if mask not in ("nonzero", "all"):
+        raise PrepError(f"--prep_mask {mask!r}: nonzero or all")
+    window = prep.parse_window(getattr(args, "prep_window", None), task)
+    spacing = prep._triple(args.prep_spacing, "--prep_spacing") if getattr(args, "prep_spacing", None) else None
+    try:
+        patch = D.parse_patch(args.patch_size) if getattr(args, "patch_size", None) else D.PATCH_DEFAULT[task]
+    except ValueError:
+        patch = ()
+    if len(patch) != 3 or min(patch) < 1:
+        raise PrepError(f"--patch_size {args.patch_size!r}: needs one or three positive integers")
+    overlap = tuple(min(D.OVERLAP_DEFAULT, p // 2) for p in patch)      # the validation's overlap, half a patch at most
+    min_size = prep._triple(args.prep_min_size, "--prep_min_size", int) if getattr(args, "prep_min_size", None) else patch
+    if any(m < p for m, p in zip(min_size, patch)):
+        raise PrepError(f"--prep_min_size {tuple(min_size)} is smaller than --patch_size {tuple(patch)}: the sliding "
+                        f"window needs one whole patch")
+    no_crop = bool(getattr(args, "prep_no_crop", False))
+
+    # everything the list and the headers decide, before anything touches the device or out_dir
+    entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
+    plans = [prep._Plan(e, mods, spacing, min_size) for e in entries]
+    if ops is None:
+        from .hip_ops import get_ops
+        ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
+    if model is None:
+        model = _network(args, ops.device)
+    model.eval()
+
+    out_dir = args.out_dir
+    os.makedirs(out_dir, exist_ok=True)
+    used = {"prep_mask": mask, "prep_window": prep._fmt(window) if window else "none",
+            "prep_spacing": prep._fmt(spacing) if spacing else "none", "prep_min_size": prep._fmt(min_size),
+            "patch_size": prep._fmt(patch)}
+    rows, writes = [], []
+    bsz = window_batch
+    reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-read")
+    writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-write")
+    try:
+        nxt = reader.submit(prep._load, entries[0], mods)
+        for i, plan in enumerate(plans):
+            got = nxt.result()
+            nxt = reader.submit(prep._load, entries[i + 1], mods) if i + 1 < len(entries) else None
+            sn = plan.subject
+            if isinstance(got, Exception):
+                raise PrepError(f"subject {sn}: {got}") from got
+            y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, got[0], None, mods, mask, window, min_size,
+                                                                no_crop)
+            vol = torch.from_numpy(y)[None].to(ops.device)
+            outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz)
+            labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.source_shape, rule, fuse)
+            counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
+            host = labels.cpu().numpy()
+            while len(writes) >= MAX_PENDING_WRITES:       # gzip slower than the device: wait, do not pile maps up
+                writes.pop(0).result()
+            writes.append(writer.submit(nifti.write_nifti, P.join(out_dir, f"{sn}.nii.gz"), host, None, plan.header))
+            present = [v for v, n in enumerate(counts) if n]
+            ml = float(np.prod(plan.source_spacing)) / 1000.0
+            row = {"subject": sn, "source_shape": prep._fmt(plan.source_shape),
+                   "source_spacing": prep._fmt(plan.source_spacing), "grid_shape": prep._fmt(plan.grid_shape),
+                   "pmin": prep._fmt(pmin), "pmax": prep._fmt(pmax), "windows": str(nwin),
+                   "labels": prep._fmt(present), "voxels": prep._fmt(counts[v] for v in present),
+                   "volume_ml": " ".join(f"{counts[v] * ml:.7g}" for v in present)}
+            row.update(used)
+            rows.append(row)
+            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)} -> grid {prep._fmt(plan.grid_shape)}, box at "
+                  f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows, labels {row['labels']}: "
+                  f"{row['voxels']} voxels")
+    finally:
+        reader.shutdown(wait=True, cancel_futures=True)
+        writer.shutdown(wait=True)
+    for w in writes:
+        w.result()                              # re-raises a failed write
+    _write_csv(P.join(out_dir, PREDICT_CSV), rows)
+    print(f"[predict] {len(rows)} maps written to {out_dir}")
+    return rows

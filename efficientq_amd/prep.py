@@ -206,6 +206,7 @@ class _Plan:
         self.source_shape = tuple(int(n) for n in first["shape"][:3])
         self.source_spacing = tuple(first["spacing"])
         self.affine = first["affine"]
+        self.header = first             # nifti.read_geometry of the first modality: write_nifti(..., geometry=header)
         if spacing is None:
             self.factors, self.grid_shape, self.grid_spacing, self.grid_affine = None, self.source_shape, \
                 self.source_spacing, self.affine

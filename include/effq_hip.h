@@ -612,6 +612,22 @@ int effq_seg_agreement(const float* logits_q, const float* logits_fp, int C, lon
 int effq_seg_labels(const float* logits, int N, int C, long long S, int rule, int fuse, float thresh, int out_bytes,
                     void* out, void* stream);
 
+/* Labels on the source grid (the `predict` mission, predict.py): the stitched logits (C, box) of one subject live on
+ * the box pmin <= (d, h, w) < pmin + box of the working grid `grid`, which effq_prep_resample made from the source grid
+ * `source` with `factors` = target spacing / source spacing per axis (1 without resampling).  out (source) uint8 gets
+ * one label per source voxel.  Per axis, source index s, in fp64: t = (s + 0.5) / factor (a division); the voxel is
+ * inside iff pmin <= min(floor(t), grid - 1) < pmin + box on all three axes, and is 0 otherwise; inside, q = clamp(t -
+ * 0.5 - pmin, 0, box - 1), i0 = floor(q), i1 = min(i0 + 1, box - 1), l1 = float(q - i0), l0 = 1.0f - l1, and each
+ * logit is combined in fp32 in the order of EFFQ_PREP_LINEAR, nothing fused.  The C values are decided and mapped to a
+ * label as effq_seg_labels does for `rule` (ARGMAX, BRATS or RANK; PLANES is an argument error: C planes have no place
+ * on a source grid), `fuse` and `thresh`.  box, pmin, grid, source (three ints each) and factors (three doubles) are
+ * host memory, read before the call returns.  1 <= C <= EFFQ_SEG_TALLIES_MAX_CLASSES; every extent <= 32767, the
+ * voxels of source, of grid and of the C box planes together < 2^31 each; 0 <= pmin, pmin + box <= grid; factors in
+ * (0, 1e6].  One launch, no atomics, no reductions: equal inputs give equal bits. */
+int effq_seg_labels_source(const float* logits, int C, const int* box, const int* pmin, const int* grid,
+                           const double* factors, const int* source, int rule, int fuse, float thresh, uint8_t* out,
+                           void* stream);
+
 /* ---- connected components of 0/1 volumes and the lesion-level columns of the validation (validate_seg(..., is_cc=True):
  * utils/validate.py:28-36, utils/metrics.py:69-94: num_component, num_false_positive, num_positive, num_false_negative,
  * there with scipy.ndimage.label on the host).  Block-based union-find: tiles of 8 x 8 x 32 voxels are labelled in LDS,
