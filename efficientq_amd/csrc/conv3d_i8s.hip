@@ -5,7 +5,8 @@
 //
 // Integers.  Activation level u in [0, La-1]; for La > 128 the byte is re-centred u' = u - 128 (one XOR 0x80,
 // zero padding becomes -128 by the same XOR).  Weight level k in [0, Lw-1], numerator m = 2k - (Lw-1); for
-// Lw <= 128 the int8 operand is m itself, for Lw > 128 it is k' = k - 128 and m = 2k' + 1.  With
+// Lw <= 128 the int8 operand is m itself, for Lw = 256 it is k' = k - 128 and m = 2k' + 1 (129 <= Lw <= 255 would need
+// m = 2k' + 257 - Lw, which the kernel does not do: refused).  With
 //   acc  = sum over ALL taps (padded ones included) of (weight operand) * (activation operand)   [i8 MFMA, int32]
 //   Ksum = sum over all taps of the weight operand (per output channel)
 //   Su   = sum over the receptive field of u (per output voxel; computed once per layer by the same kernel)
@@ -284,7 +285,7 @@ static int i8s_plan(const effq_geom* g, int act_levels, int w_levels, I8sPlan* p
   EFFQ_CHECK_ARG(g->N > 0 && g->C1 > 0 && g->C2 > 0 && g->D > 0 && g->H > 0 && g->W > 0);
   EFFQ_CHECK_ARG(g->KD >= 1 && g->KH >= 1 && g->KW >= 1 && g->SD >= 1 && g->SH >= 1 && g->SW >= 1);
   EFFQ_CHECK_ARG(g->PD >= 0 && g->PH >= 0 && g->PW >= 0);
-  EFFQ_CHECK_ARG(act_levels >= 2 && act_levels <= 256 && w_levels >= 2 && w_levels <= 256);
+  EFFQ_CHECK_ARG(act_levels >= 2 && act_levels <= 256 && w_levels >= 2 && (w_levels <= 128 || w_levels == 256));
   ConvI8sParams& p = pl->p;
   memset(&p, 0, sizeof(p));
   p.N = g->N; p.C1 = g->C1; p.C2 = g->C2; p.D = g->D; p.H = g->H; p.W = g->W;
@@ -359,7 +360,7 @@ int effq_conv_i8s_supported(const effq_geom* g, int act_levels, int w_levels) {
   if (g == nullptr) return 0;
   if (g->KD * g->KH * g->KW > 27 || g->KD * g->KH * g->KW * g->C1 > 256) return 0;
   if (!(g->C1 == 4 || (g->C1 % 16) == 0)) return 0;
-  if (act_levels < 2 || act_levels > 256 || w_levels < 2 || w_levels > 256) return 0;
+  if (act_levels < 2 || act_levels > 256 || w_levels < 2 || (w_levels > 128 && w_levels != 256)) return 0;
   const int nj = (g->KD * g->KH * g->KW * g->C1 + 31) / 32, ct = (g->C2 + 31) / 32;
   if (!i8s_has_variant(nj, ct)) return 0;
   if (i8s_plan(g, act_levels, w_levels, &pl) != EFFQ_OK) return 0;

@@ -349,7 +349,7 @@ int effq_fixed_point_small_fused(const float* a, const float* b, float* v_out, s
   memset(&pf, 0, sizeof(pf));
   if (pf_in != nullptr) pf = *pf_in;
   EFFQ_CHECK_ARG(pf.G == nullptr || v_out != nullptr);
-  EFFQ_CHECK_ARG(a && state_dev && n > 0 && levels >= 2 && hi > lo && max_iter > 0);
+  EFFQ_CHECK_ARG(a && state_dev && n > 0 && levels >= 2 && levels <= FP_LEVELS_MAX && hi > lo && max_iter > 0);
   EFFQ_CHECK_ARG(n <= effq_fp_small_max());
   EFFQ_CHECK_ARG(b == nullptr || v_out != nullptr);
   const double d = (hi - lo) / (double)(levels - 1);
@@ -403,7 +403,7 @@ int effq_fixed_point_coop_rec(const float* a, const float* b, float* v_out, size
                               double tol, int max_iter, effq_fp_state* state_dev, void* ws, void* pred_dev,
                               void* stream) {
   FptPred* pred = reinterpret_cast<FptPred*>(pred_dev);
-  EFFQ_CHECK_ARG(a && state_dev && ws && n > 0 && levels >= 2 && hi > lo && max_iter > 0);
+  EFFQ_CHECK_ARG(a && state_dev && ws && n > 0 && levels >= 2 && levels <= FP_LEVELS_MAX && hi > lo && max_iter > 0);
   EFFQ_CHECK_ARG(n <= effq_fp_coop_max());
   EFFQ_CHECK_ARG(b == nullptr || v_out != nullptr);
   EFFQ_CHECK_ARG(v_out == nullptr || (v_out != a && v_out != b));      // k_fp_coop's operands are __restrict__

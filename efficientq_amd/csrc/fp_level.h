@@ -48,8 +48,13 @@ __device__ __forceinline__ LevelConsts level_grid(double lo, double hi, double d
   return c;
 }
 
-// The fp32 screen: u is off by <= 3e-5 at 256 levels, so rint(u) is the exact level unless u lies within 2e-4 of a
-// rounding boundary (or is NaN).  Returns false there: the caller's exact arithmetic decides.
+// The fp32 screen: u is off by <= 1.5 lmax 2^-24 (c1 rounded to fp32 on a product of <= lmax / 2, the fma's own rounding
+// of <= lmax 2^-24; c0 is exact) = 2.3e-5 at 256 levels, so rint(u) is the exact level unless u lies within 2e-4 of a
+// rounding boundary (or is NaN).  Returns false there: the caller's exact arithmetic decides.  The band is a constant, so
+// the bound on u must stay well inside it: every entry point that gets here refuses levels > FP_LEVELS_MAX (the bound
+// reaches the band near 2200 levels; emulated in numpy at 65536 levels, the screen puts 4 in 1000 of the values next to
+// a boundary on the wrong level).
+constexpr int FP_LEVELS_MAX = 256;
 __device__ __forceinline__ bool level_screen(float v, const LevelConsts& c, float& rf) {
   float u = __builtin_fmaf(v, c.c1, c.c0);
   u = fminf(fmaxf(u, 0.0f), c.lmax);

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(TPB) void k_project_dual(const float* __restrict__ 
     float g = alpha32 * b;
     G[i] = g;
     // int8 operand of the exact-integer convs: the signed numerator j' = 2*level - (L-1), or, beyond 128
-    // levels where that no longer fits, level - 128 (conv3d_i8s.hip rebuilds j' = 2*(level-128) + 1)
+    // levels where that no longer fits, level - 128 (at 256 levels conv3d_i8s.hip rebuilds j' = 2*(level-128) + 1)
     if (Gq != nullptr) Gq[i] = (lm1 >= 128) ? (int8_t)((int)r - 128) : (int8_t)(2 * (int)r - lm1);
     float du = (wstar[i] - g) + dual[i];        // EfficientQConv.py:111
     if (dual_div != 1.0f) du = du / dual_div;   // "dual /= 2" or "dual /= rho_m/rho" (:131-136)
@@ -82,8 +82,7 @@ int effq_admm_presum(const float* wstar, const float* dual, float* v, size_t n, 
 int effq_project_dual_impl(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels, float* G,
                            float* dual, float dual_div, int8_t* Gq_out, size_t n, int32_t* err_flag_dev,
                            const ProjNext* nx_in, void* stream) {
-  EFFQ_CHECK_ARG(v && wstar && state_dev && G && dual && levels >= 2 && dual_div > 0.0f);
-  EFFQ_CHECK_ARG(Gq_out == nullptr || levels <= 256);
+  EFFQ_CHECK_ARG(v && wstar && state_dev && G && dual && levels >= 2 && levels <= FP_LEVELS_MAX && dual_div > 0.0f);
   ProjNext nx;
   memset(&nx, 0, sizeof(nx));
   if (nx_in != nullptr) {

@@ -385,7 +385,7 @@ int effq_moments_f64(const float* x, size_t n, double* sums_out, void* ws, void*
 
 int effq_alpha_stats_f64(const float* x, const double* alpha_dev, double lo, double hi, int levels, size_t n,
                          double* sums_out, const int32_t* done_flag_dev, void* ws, void* stream) {
-  EFFQ_CHECK_ARG(x && alpha_dev && sums_out && ws && n > 0 && levels >= 2 && hi > lo);
+  EFFQ_CHECK_ARG(x && alpha_dev && sums_out && ws && n > 0 && levels >= 2 && levels <= FP_LEVELS_MAX && hi > lo);
   RedWs r = red_ws(ws);
   const double d = (hi - lo) / (double)(levels - 1);
   hipLaunchKernelGGL(k_reduce<2>, dim3(stream_grid((n + 3) / 4)), dim3(TPB), 0, as_stream(stream), x, n, alpha_dev,
@@ -410,7 +410,7 @@ int effq_fp_update(effq_fp_state* state_dev, double tol, int max_iter, void* str
 
 int effq_alpha_fixed_point(const float* x, size_t n, int levels, double lo, double hi, double tol, int max_iter,
                            int n_iters, effq_fp_state* state_dev, void* ws, void* stream) {
-  EFFQ_CHECK_ARG(x && state_dev && ws && n > 0 && n_iters >= 0 && levels >= 2 && hi > lo);
+  EFFQ_CHECK_ARG(x && state_dev && ws && n > 0 && n_iters >= 0 && levels >= 2 && levels <= FP_LEVELS_MAX && hi > lo);
   RedWs r = red_ws(ws);
   const double d = (hi - lo) / (double)(levels - 1);
   const int grid = stream_grid((n + 3) / 4);

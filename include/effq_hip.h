@@ -372,11 +372,16 @@ int effq_prox_solve_shifted(const float* B0, const float* Ainv, const float* W0,
  * v = wstar + dual                                  (input of the weight projection) */
 int effq_admm_presum(const float* wstar, const float* dual, float* v, size_t n, void* stream);
 /* G = f32(alpha)*b with b=f32(discretize(f64(v)/alpha,-1,1)); dual = (wstar - G + dual) / dual_div.
- * dual_div is 1, or 2 / (rho_max/rho) on the rho-schedule iterations (i % 50 == 0).  alpha from state_dev. */
+ * dual_div is 1, or 2 / (rho_max/rho) on the rho-schedule iterations (i % 50 == 0).  alpha from state_dev.
+ * 2 <= levels <= 256, with or without Gq_out: the fp32 screen that finds the level of most values is exact up to there
+ * (csrc/fp_level.h).  The same bound holds for every fixed point and statistics pass above that uses the screen:
+ * effq_alpha_stats_f64, effq_alpha_fixed_point, effq_fixed_point_small, effq_fixed_point_coop(_rec) (their level
+ * tallies are sized for it too), as it does for the bucket, bracket, trajectory and channel fixed points. */
 int effq_admm_project_dual(const float* v, const float* wstar, const effq_fp_state* state_dev, int levels,
                            float* G, float* dual, float dual_div, int8_t* Gq_out, size_t n, void* stream);
-/* Gq_out (optional, levels <= 128): signed level numerators j' = 2*level-(L-1), so that G = alpha_w*j'/(L-1);
- * the operand of the exact-integer conv below. */
+/* Gq_out (optional): the int8 operand of the exact-integer convs below.  levels <= 128: the signed level numerator
+ * j' = 2*level-(L-1) itself, so that G = alpha_w*j'/(L-1); 129 <= levels <= 256, where j' no longer fits: level-128,
+ * i.e. j' = 2*(level-128) + (257-L); conv3d_calib_step_i8s takes that encoding at 256 levels only (+ 1). */
 /* ---- the entry point north_star names ------------------------------------------------
  * One ADMM iteration's device work (EfficientQConv.py:118-122,161-165; PTQConv.py:154-167):
  * out = conv3d(xq, G, bias) in fp32 on the matrix cores (f32 MFMA, exact fp32 fma chains),
@@ -418,8 +423,8 @@ int conv3d_quant_forward_i8(const uint8_t* xidx_ndhwc, const int8_t* Gq, const f
 
 /* The same exact-integer loss for the layers the tiled kernels above do not take: few taps*channels
  * (KD*KH*KW*C1 <= 256 with C1 == 4 or C1 % 16 == 0: the first conv, the 1x1x1 convs, the classifier), any
- * stride/padding, and up to 256 levels on either side (q_first/q_last = 256 in the reference's recipes).
- * Gq holds the int8 operands effq_admm_project_dual emits (2*level-(Lw-1), or level-128 when Lw > 128).
+ * stride/padding, up to 256 activation levels, and up to 128 or exactly 256 weight levels (q_first/q_last = 256 in the
+ * reference's recipes).  Gq holds the int8 operands effq_admm_project_dual emits (2*level-(Lw-1), or level-128 at Lw = 256).
  * prepare != 0 (first call of a layer) also rebuilds the per-voxel level sums the Lw > 128 form needs; they
  * live in ws between calls.  ws: effq_conv_i8s_ws_bytes(geom, act_levels, w_levels). */
 int effq_conv_i8s_supported(const effq_geom* g, int act_levels, int w_levels);

@@ -753,6 +753,11 @@ def test_short_k_exact_int_conv_rejects_what_it_cannot_do(ops):
     assert not ops.conv_i8s_supported(make_geom((1, 8, 8, 8, 8), 32, 1, 1, 0), 4, 4)       # C1 = 8
     assert not ops.conv_i8s_supported(make_geom((1, 256, 8, 8, 8), 128, 1, 1, 0), 4, 4)    # too many B operands
     assert not ops.conv_i8s_supported(make_geom((1, 4, 8, 8, 8), 32, 3, 2, 1), 4, 300)
+    # 129 .. 255 weight levels: the operand is level - 128 and the numerator 2 (level - 128) + 257 - Lw, not the + 1 of 256
+    assert not ops.conv_i8s_supported(make_geom((1, 4, 8, 8, 8), 32, 3, 2, 1), 4, 129)
+    assert not ops.conv_i8s_supported(make_geom((1, 4, 8, 8, 8), 32, 3, 2, 1), 4, 255)
+    assert ops.conv_i8s_supported(make_geom((1, 4, 8, 8, 8), 32, 3, 2, 1), 4, 128)
+    assert ops.conv_i8s_supported(make_geom((1, 4, 8, 8, 8), 32, 3, 2, 1), 256, 256)
 
 
 @pytest.mark.parametrize("n,L", [(40000, 4), (110592, 4), (442368, 16), (1769472, 4), (300001, 256), (7077888, 4)])
