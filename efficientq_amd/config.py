@@ -100,10 +100,31 @@ def build_parser():
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
     # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint
     p.add_argument('--out_dir', default=None, help='predict: where <subject>.nii.gz and predict.csv are written')
+    # the sliding window of the validation (ptq) and of predict: window weights and mirror test-time augmentation; the
+    # values are checked by blend_switches, after the YAML has been merged in
+    p.add_argument('--blend', default='uniform', help='window weights of the stitch: uniform or gauss (sigma = patch / 8)')
+    p.add_argument('--tta_mirror', default=None,
+                   help='mirror test-time augmentation: letters of d, h, w, each at most once (w, hw, dhw); every '
+                        'window also runs mirrored along each subset of the axes and the logits are averaged')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
     return p
+
+
+def blend_switches(args):
+    """(blend, flips) of --blend / --tta_mirror (or the YAML keys `blend`, `tta_mirror`) for
+    evaluate.stitched_window_logits; a value that is not understood is refused by name (SystemExit), host only."""
+    from .evaluate import BLEND_KINDS, mirror_flips
+    blend = getattr(args, 'blend', None)
+    blend = 'uniform' if blend is None else blend
+    if blend not in BLEND_KINDS:
+        raise SystemExit(f'--blend {blend!r}: one of {", ".join(BLEND_KINDS)}')
+    try:
+        flips = mirror_flips(getattr(args, 'tta_mirror', None))
+    except ValueError as e:
+        raise SystemExit(f'--tta_mirror {e}')
+    return blend, flips
 
 
 def _pair(s):

@@ -12,24 +12,9 @@
 // Tallies: wave reductions into per-block partials, summed in block order by a second launch; integer counts only.
 #include "common.h"
 #include "seg_decide.h"
+#include "seg_window.h"      // WinAxes, win_start, make_axes, grid_for, STITCH_MAX_C: shared with window_blend.hip
 
 namespace effq {
-
-struct WinAxes {
-  int D, H, W;        // volume extent
-  int pd, ph, pw;     // window extent
-  int sd, sh, sw;     // step = patch - overlap
-  int nd, nh, nw;     // windows per axis
-};
-
-static inline int n_windows(int size, int patch, int step) {
-  return (size - patch + step - 1) / step + 1;
-}
-
-__device__ __forceinline__ int win_start(int i, int size, int patch, int step) {
-  const int s = i * step;
-  return s < size - patch ? s : size - patch;
-}
 
 // ---- gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1 -------------
 template <int VEC>
@@ -67,8 +52,6 @@ __global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__
 }
 
 // ---- stitch: win (nwin, N, pd, ph, pw, C) -> out (N, C, D, H, W) --------------------------------------------------
-constexpr int STITCH_MAX_C = 8;
-
 __global__ __launch_bounds__(256) void k_window_stitch(const float* __restrict__ win, float* __restrict__ out, WinAxes a,
                                                        int N, int C, uint32_t total) {
   const size_t plane = (size_t)a.D * a.H * a.W;
@@ -313,21 +296,6 @@ static void launch_tallies(int mode, bool v4, dim3 g, dim3 b, hipStream_t st, co
     if (v4) hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_SIGMOID, 4, C>), g, b, 0, st, p);
     else hipLaunchKernelGGL((k_seg_tallies<EFFQ_SEG_SIGMOID, 1, C>), g, b, 0, st, p);
   }
-}
-
-static bool make_axes(int D, int H, int W, int pd, int ph, int pw, int od, int oh, int ow, WinAxes& a) {
-  if (pd <= 0 || ph <= 0 || pw <= 0 || pd > D || ph > H || pw > W) return false;
-  if (od < 0 || oh < 0 || ow < 0 || od >= pd || oh >= ph || ow >= pw) return false;
-  a.D = D; a.H = H; a.W = W; a.pd = pd; a.ph = ph; a.pw = pw;
-  a.sd = pd - od; a.sh = ph - oh; a.sw = pw - ow;
-  a.nd = n_windows(D, pd, a.sd); a.nh = n_windows(H, ph, a.sh); a.nw = n_windows(W, pw, a.sw);
-  return true;
-}
-
-static unsigned grid_for(size_t items, size_t cap) {
-  size_t nb = (items + 255) / 256;
-  if (nb < 1) nb = 1;
-  return (unsigned)(nb < cap ? nb : cap);
 }
 
 }  // namespace effq

@@ -21,6 +21,9 @@ decided differently, the logit drift and the probability drift, the lesion / sur
 ``--surf_dist`` against the FP decisions, and with ``--save_nii`` the map of the differing classes
 ``<snap>/ptq/val_vs_fp/<subject>.nii.gz``; it needs no label;
 ``--unlabelled`` (with ``--vs_fp``) reads data without a ``seg/`` folder: only the FP-vs-Q validation runs.
+``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched, and
+``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
+averages the logits; both hold for every validation of the run (and for ``predict``), the FP network's included.
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing, unless ``--vs_fp``
 is given: then two held-out synthetic volumes are validated against the FP network; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
@@ -81,9 +84,10 @@ class _ValidationTester(_SnapshotWriter):
     <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
     labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written."""
 
-    def __init__(self, model, root, data_cube, task, rank=0):
+    def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,)):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
+        self.blend, self.flips = blend, tuple(flips)
 
     def _geometry(self, is_save_nii, is_surf, is_table=False):
         """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances,
@@ -115,6 +119,8 @@ class _ValidationTester(_SnapshotWriter):
                              multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
                              surface=is_surf, **({'lesion_table': True} if is_table else {}),
                              **({'fp_model': fp_model} if fp_model is not None else {}),
+                             **({'blend': self.blend, 'flips': self.flips}
+                                if (self.blend, self.flips) != ('uniform', (0,)) else {}),
                              **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
         if fp_model is not None:
@@ -185,8 +191,9 @@ class _SyntheticCube:
 
 
 def check_switches(args):
-    """The combinations of --vs_fp / --unlabelled that cannot run, refused before anything touches the device (host only:
-    SystemExit naming the switches)."""
+    """The combinations of --vs_fp / --unlabelled that cannot run and the values of --blend / --tta_mirror that are not
+    understood, refused before anything touches the device (host only: SystemExit naming the switches)."""
+    Cf.blend_switches(args)
     if not getattr(args, 'unlabelled', False):
         return
     if not getattr(args, 'vs_fp', False):
@@ -214,6 +221,11 @@ def main(argv=None):
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)
     check_switches(args)
+    blend, flips = Cf.blend_switches(args)
+    sliding = {} if (blend, flips) == ('uniform', (0,)) else {'blend': blend, 'flips': flips}
+    if sliding:
+        print(f'[entrance] sliding window: blend {blend}, {len(flips)} passes per window (flip masks '
+              f'{" ".join(str(m) for m in flips)})')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -247,7 +259,7 @@ def main(argv=None):
         with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
             f.write(' '.join(sys.argv) + '\n')
         rank = int(os.environ.get('RANK', '0'))
-        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank), snap)
+        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank, **sliding), snap)
         return
     size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
     size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
@@ -257,7 +269,7 @@ def main(argv=None):
         f.write(' '.join(sys.argv) + '\n')
     if data_cube.valloader is not None:
         rank = int(os.environ.get('RANK', '0'))
-        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank), snap)
+        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank, **sliding), snap)
         return
     K.do_ptq(args, cube, data_cube, _SnapshotWriter(model, snap), snap)
 

@@ -285,16 +285,53 @@ def _vs_fp(ops, q, f, kind, fuse, shape, spacing, lesions, surface, want_map) ->
     return out
 
 
+BLEND_KINDS = ("uniform", "gauss")       # --blend: the window weights of the stitch (hip_ops.blend_weights_host)
+MIRROR_AXES = "dhw"                      # --tta_mirror: bit i of a flip mask mirrors axis MIRROR_AXES[i]
+
+
+def mirror_flips(axes) -> tuple:
+    """The flip masks of --tta_mirror `axes`, ascending: every subset of the named axes, the empty one (mask 0, the
+    un-mirrored pass) included - "w" -> (0, 4), "hw" -> (0, 2, 4, 6), "dhw" -> (0, ..., 7).  None: (0,).  `axes` is a
+    non-empty string over d, h, w with no letter twice; anything else is a ValueError."""
+    if axes is None:
+        return (0,)
+    if not isinstance(axes, str) or not axes or any(a not in MIRROR_AXES for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"{axes!r}: a non-empty string over the letters d, h, w, each at most once (w, hw, dhw, ...)")
+    bits = sum(1 << MIRROR_AXES.index(a) for a in axes)
+    return tuple(m for m in range(8) if m & ~bits == 0)
+
+
+def check_flips(flips) -> tuple:
+    """`flips` as a tuple of distinct masks 0..7 in ascending order; a ValueError otherwise."""
+    f = tuple(flips)
+    if not f or any(isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= 7 for m in f) or \
+            list(f) != sorted(set(f)):
+        raise ValueError(f"flips {flips!r}: distinct flip masks 0..7 in ascending order, at least one")
+    return f
+
+
 @torch.no_grad()
-def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_batch=None):
+def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_batch=None, blend="uniform",
+                           flips=(0,)):
     """The sliding-window forward of validate_seg and of the `predict` mission: the windows of `vol` (N x C x D x H x W
     fp32 on the device of `ops`) gathered into batches of `window_batch` (effq_window_gather), every network of `nets`
     run on each batch, its last head copied into the network's window buffer and the buffer stitched
     (effq_window_stitch).  window_batch=None: the first window runs alone and its peak memory - over all the forwards
     of `nets` - sizes the batches, half the free device memory at most WINDOW_BATCH_MAX windows.  Returns (one stitched
     N x classes x D x H x W tensor per network, the number of windows, the window batch in use): a caller hands the
-    last back in for its next volume."""
+    last back in for its next volume.
+    blend: "uniform" (every covering window counts alike) or "gauss" (a window's voxels are weighted by a separable
+    Gaussian of sigma = patch / 8 around its centre, hip_ops.blend_weights_host).  flips: the flip masks of mirror
+    test-time augmentation (mirror_flips), ascending; every batch runs once per mask, mirrored (effq_window_gather_flip),
+    and effq_window_put un-mirrors the last head into the window buffer, storing the first pass and adding the others,
+    so the buffer keeps its size.  The buffer is then stitched with the weights and divided by the number of passes
+    (effq_window_stitch_weighted): the logits are averaged, not the probabilities.  With the defaults exactly the
+    statements above run."""
     from .hip_ops import from_ndhwc
+    if blend not in BLEND_KINDS:
+        raise ValueError(f"blend {blend!r}: one of {', '.join(BLEND_KINDS)}")
+    flips = check_flips(flips)
+    plain = blend == "uniform" and flips == (0,)
     dev = vol.device
     p, o = _triple(patch), _triple(overlap)
     bsz = window_batch
@@ -310,26 +347,40 @@ def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_
             torch.cuda.synchronize(dev)
             base = torch.cuda.memory_allocated(dev)
             torch.cuda.reset_peak_memory_stats(dev)
-        x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
-        for k, net in enumerate(nets):      # the peak below covers every forward
-            last = _last_head(net(x))
-            if bufs[k] is None:
-                bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-            bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
-            del last
+        if plain:
+            x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
+            for k, net in enumerate(nets):      # the peak below covers every forward
+                last = _last_head(net(x))
+                if bufs[k] is None:
+                    bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+                bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+                del last
+        else:
+            for m in flips:                     # the peak below covers every forward of every pass
+                x = from_ndhwc(ops.window_gather_flip(vol, p, o, first, cnt, m))
+                for k, net in enumerate(nets):
+                    last = _last_head(net(x))
+                    if bufs[k] is None:
+                        bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
+                    ops.window_put(last, bufs[k][first * N:(first + cnt) * N], m, m != flips[0])
+                    del last
+                del x
         if bsz is None:
             per = max(1, torch.cuda.max_memory_allocated(dev) - base)
             free, _ = torch.cuda.mem_get_info(dev)
             bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
         first += cnt
     full = (N,) + tuple(bufs[0].shape[-1:]) + tuple(vol.shape[-3:])
-    return [ops.window_stitch(b, full, p, o) for b in bufs], nwin, bsz
+    if plain:
+        return [ops.window_stitch(b, full, p, o) for b in bufs], nwin, bsz
+    weights = ops.blend_weights(p, blend)
+    return [ops.window_stitch_weighted(b, full, p, o, weights, len(flips)) for b in bufs], nwin, bsz
 
 
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
-                 geometry=None, lesion_table=False, fp_model=None):
+                 geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,)):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -371,7 +422,9 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     the differing classes (bit c = class c) goes to <save_dir>_vs_fp/<name>.nii.gz, on the source grid when the case has
     a source geometry.  The window batches are sized for both forwards.  A case whose label is empty (numel() == 0,
     data.SegVolumes(labels=False)) is unlabelled: it needs fp_model, takes the counting from `multi_label` (set: sigmoid
-    per channel, else argmax) and its dict carries name and vs_fp only."""
+    per channel, else argmax) and its dict carries name and vs_fp only.
+    blend, flips: the window weights and the mirror passes of stitched_window_logits (--blend, --tta_mirror); with
+    fp_model both networks are blended and augmented alike.  Everything after the stitch is unchanged."""
     from .hip_ops import get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -400,7 +453,7 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
             vol = images.to(dev, torch.float32).contiguous()
             N = int(vol.shape[0])
             nets = [model] if fp_model is None else [model, fp_model]
-            outs, _, bsz = stitched_window_logits(ops, nets, vol, p, o, bsz)
+            outs, _, bsz = stitched_window_logits(ops, nets, vol, p, o, bsz, blend, flips)
             stitched = outs[0]
             stitched_fp = outs[1] if fp_model is not None else None
             lab = labels.to(dev).to(torch.uint8) if labelled else None

@@ -42,6 +42,36 @@ def _triple(v):
     return (v, v, v) if isinstance(v, int) else tuple(int(i) for i in v)
 
 
+def _flip_mask(flip, who: str) -> int:
+    if isinstance(flip, bool) or int(flip) != flip or not 0 <= flip <= 7:
+        raise _lib.EffqError(f"{who}: flip mask {flip!r}, an int 0..7 (bit 0 = d, bit 1 = h, bit 2 = w)")
+    return int(flip)
+
+
+BLEND_KINDS = ("uniform", "gauss")
+
+
+def blend_weights_host(patch, kind: str = "uniform"):
+    """The per-axis window weights of the blend `kind` for the window extent `patch`, three fp32 numpy vectors whose
+    outer product weighs a window's voxels.  uniform: ones.  gauss: w(i) = exp(-0.5 ((i - (p - 1) / 2) / (p / 8))^2),
+    sigma = patch / 8 with the peak 1 at the centre, computed in fp64 and rounded once to fp32.  The least value of an
+    axis is exp(-0.5 (4 (p - 1) / p)^2) > exp(-8) = 3.4e-4 at any p, so the least product of three is above 3.7e-11:
+    thirty orders of magnitude from the fp32 denormals, and no floor is needed."""
+    import numpy as np
+    if kind not in BLEND_KINDS:
+        raise _lib.EffqError(f"blend {kind!r}, one of {', '.join(BLEND_KINDS)}")
+    out = []
+    for p in _triple(patch):
+        if p <= 0:
+            raise _lib.EffqError(f"window extent {p} must be positive")
+        if kind == "uniform":
+            out.append(np.ones(p, dtype=np.float32))
+        else:
+            i = np.arange(p, dtype=np.float64)
+            out.append(np.exp(-0.5 * ((i - (p - 1) / 2.0) / (p / 8.0)) ** 2).astype(np.float32))
+    return tuple(out)
+
+
 def make_geom(x_shape_ncdhw, c2: int, ksize, stride, padding) -> Geom:
     n, c1, d, h, w = (int(i) for i in x_shape_ncdhw)
     k, s, p = _triple(ksize), _triple(stride), _triple(padding)
@@ -1050,6 +1080,78 @@ class HipOps:
         check(self.lib.effq_window_stitch(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], _ptr(out),
                                           self.stream), "effq_window_stitch")
         return out
+
+    # -- centre-weighted blending and mirror test-time augmentation (evaluate.stitched_window_logits) ------------
+    def window_gather_flip(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None,
+                           flip: int = 0):
+        """window_gather with the content of every window mirrored along the axes of the mask `flip` (bit 0 = d, bit 1
+        = h, bit 2 = w; effq_window_gather_flip).  flip = 0 gives window_gather's bits."""
+        x = self._f32(vol)
+        if x.dim() != 5:
+            raise _lib.EffqError(f"window_gather_flip: expected N x C x D x H x W, got {tuple(x.shape)}")
+        flip = _flip_mask(flip, "window_gather_flip")
+        N, Cc, D, H, W = (int(i) for i in x.shape)
+        p, o = _triple(patch), _triple(overlap)
+        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        count = nwin - first if count is None else int(count)
+        if first < 0 or count <= 0 or first + count > nwin:
+            raise _lib.EffqError(f"windows {first}..{first + count - 1} of {nwin}")
+        out = torch.empty(count * N, p[0], p[1], p[2], Cc, dtype=torch.float32, device=self.device)
+        check(self.lib.effq_window_gather_flip(_ptr(x), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], int(first),
+                                               count, flip, _ptr(out), self.stream), "effq_window_gather_flip")
+        return out
+
+    def window_put(self, last: torch.Tensor, buf_slice: torch.Tensor, flip: int = 0, accumulate: bool = False) -> None:
+        """A network's last head `last` (M x C x pd x ph x pw, the windows of one batch mirrored by `flip`) into
+        `buf_slice`, the M x pd x ph x pw x C slice of the stitch's window buffer: transposed to channels-last,
+        un-mirrored, and stored (accumulate=False) or added onto what the slice holds (effq_window_put).  The slice is
+        written in place: it must be fp32, contiguous and on this device."""
+        src = self._f32(last)
+        if src.dim() != 5:
+            raise _lib.EffqError(f"window_put: expected M x C x pd x ph x pw, got {tuple(src.shape)}")
+        flip = _flip_mask(flip, "window_put")
+        M, Cc, pd, ph, pw = (int(i) for i in src.shape)
+        if not 0 < Cc <= 8:
+            raise _lib.EffqError(f"window_put: {Cc} channels, at most 8")
+        if tuple(buf_slice.shape) != (M, pd, ph, pw, Cc):
+            raise _lib.EffqError(f"window_put: buffer slice {tuple(buf_slice.shape)}, the head needs {(M, pd, ph, pw, Cc)}")
+        if self._f32(buf_slice) is not buf_slice:
+            raise _lib.EffqError("window_put: the buffer slice is written in place and must be contiguous")
+        if M * Cc * pd * ph * pw >= 1 << 31:
+            raise _lib.EffqError(f"window_put: {M * Cc * pd * ph * pw} elements, fewer than 2^31 per call")
+        check(self.lib.effq_window_put(_ptr(src), M, Cc, pd, ph, pw, flip, int(bool(accumulate)), _ptr(buf_slice),
+                                       self.stream), "effq_window_put")
+
+    def window_stitch_weighted(self, win: torch.Tensor, shape, patch, overlap, weights, nflip: int = 1) -> torch.Tensor:
+        """window_stitch with the separable per-axis `weights` (three fp32 device tensors of pd, ph, pw values:
+        blend_weights) on the sum of `nflip` passes in `win`: each voxel is the weighted sum over its covering windows
+        over (nflip * the sum of their weights) (effq_window_stitch_weighted).  Ones and nflip = 1: window_stitch's bits."""
+        w = self._f32(win)
+        N, Cc, D, H, W = (int(i) for i in shape)
+        p, o = _triple(patch), _triple(overlap)
+        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        if tuple(w.shape) != (nwin * N, p[0], p[1], p[2], Cc):
+            raise _lib.EffqError(f"window_stitch_weighted: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
+        if not 0 < Cc <= 8:
+            raise _lib.EffqError(f"window_stitch_weighted: {Cc} channels, at most 8")
+        if int(nflip) != nflip or nflip < 1:
+            raise _lib.EffqError(f"window_stitch_weighted: nflip {nflip!r}, the number of passes summed, is at least 1")
+        if len(weights) != 3:
+            raise _lib.EffqError(f"window_stitch_weighted: {len(weights)} weight tensors, one per axis d, h, w")
+        ws = [self._f32(t) for t in weights]
+        for t, n, ax in zip(ws, p, "dhw"):
+            if t.dim() != 1 or int(t.numel()) != n:
+                raise _lib.EffqError(f"window_stitch_weighted: weights of axis {ax} have shape {tuple(t.shape)}, the "
+                                     f"window needs ({n},)")
+        out = torch.empty(N, Cc, D, H, W, dtype=torch.float32, device=self.device)
+        check(self.lib.effq_window_stitch_weighted(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2],
+                                                   _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), int(nflip), _ptr(out),
+                                                   self.stream), "effq_window_stitch_weighted")
+        return out
+
+    def blend_weights(self, patch, kind: str = "uniform"):
+        """The three per-axis fp32 weight tensors of window_stitch_weighted on this device (blend_weights_host)."""
+        return tuple(torch.from_numpy(w).to(self.device) for w in blend_weights_host(patch, kind))
 
     def sigmoid_threshold(self) -> float:
         """The least fp32 x at which the framework's fp32 `torch.sigmoid(x) >= 0.5` holds on this device.  Near 0 it is

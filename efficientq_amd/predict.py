@@ -3,6 +3,7 @@
     python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/ \
         [--prep_window -200,250 --prep_spacing 1,1,2.5 --prep_mask all --prep_min_size d,h,w --patch_size d,h,w]
+        [--blend gauss --tta_mirror hw]
 
 ``--src_list`` is the CSV of the ``prep`` mission (prep.read_src_list; a ``seg`` column is allowed and ignored).  The
 ``--prep_*`` switches and ``--patch_size`` mean what they mean in ``prep`` and ``ptq`` and have the same per-task
@@ -18,7 +19,12 @@ written by a background thread.  ``<out_dir>/predict.csv`` gets one row per subj
 grid, the box, the number of windows, the prep options used, and per label value present in the map its voxel count
 (counted on the device) and its volume in ml.
 
-Everything the list and the headers decide, ``--multi_label lits`` (one plane per class has no place on a source grid)
+``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched;
+``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
+averages the logits: 2, 4 or 8 forwards per window.  When either is given ``predict.csv`` gains the columns ``blend`` and
+``tta_mirror`` after the others; otherwise the file is what it was.
+
+Everything the list and the headers decide, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
 and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
 """
 from __future__ import annotations
@@ -82,12 +88,15 @@ def _network(args, dev):
     return model
 
 
-def _write_csv(path: str, rows: List[dict]) -> None:
+CSV_BLEND_COLUMNS = ["blend", "tta_mirror"]       # after CSV_HEADER, only when --blend / --tta_mirror is given
+
+
+def _write_csv(path: str, rows: List[dict], header=CSV_HEADER) -> None:
     def dump(p):
         with open(p, "w", newline="") as f:
             w = csv.writer(f)
-            w.writerow(CSV_HEADER)
-            w.writerows([r[k] for k in CSV_HEADER] for r in rows)
+            w.writerow(header)
+            w.writerows([r[k] for k in header] for r in rows)
     prep._replace(path, dump)
 
 
@@ -142,6 +151,9 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         raise PrepError(f"--prep_min_size {tuple(min_size)} is smaller than --patch_size {tuple(patch)}: the sliding "
                         f"window needs one whole patch")
     no_crop = bool(getattr(args, "prep_no_crop", False))
+    from . import config as Cf
+    blend, flips = Cf.blend_switches(args)
+    sliding = (blend, flips) != ("uniform", (0,))
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
@@ -158,6 +170,8 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     used = {"prep_mask": mask, "prep_window": prep._fmt(window) if window else "none",
             "prep_spacing": prep._fmt(spacing) if spacing else "none", "prep_min_size": prep._fmt(min_size),
             "patch_size": prep._fmt(patch)}
+    if sliding:
+        used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
     rows, writes = [], []
     bsz = window_batch
     reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-read")
@@ -173,7 +187,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, got[0], None, mods, mask, window, min_size,
                                                                 no_crop)
             vol = torch.from_numpy(y)[None].to(ops.device)
-            outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz)
+            outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz, blend, flips)
             labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.source_shape, rule, fuse)
             counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
             host = labels.cpu().numpy()
@@ -190,13 +204,14 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             row.update(used)
             rows.append(row)
             print(f"[predict] {sn}: {prep._fmt(plan.source_shape)} -> grid {prep._fmt(plan.grid_shape)}, box at "
-                  f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows, labels {row['labels']}: "
+                  f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
+                  f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
                   f"{row['voxels']} voxels")
     finally:
         reader.shutdown(wait=True, cancel_futures=True)
         writer.shutdown(wait=True)
     for w in writes:
         w.result()                              # re-raises a failed write
-    _write_csv(P.join(out_dir, PREDICT_CSV), rows)
+    _write_csv(P.join(out_dir, PREDICT_CSV), rows, CSV_HEADER + CSV_BLEND_COLUMNS if sliding else CSV_HEADER)
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

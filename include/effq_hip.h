@@ -581,6 +581,24 @@ int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int 
                        int ow, int first, int count, float* out, void* stream);
 int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
                        int ow, float* out, void* stream);
+/* Centre-weighted blending and mirror test-time augmentation of the sliding window (window_blend.hip).  A flip mask is
+ * 0..7: bit 0 mirrors d, bit 1 mirrors h, bit 2 mirrors w; a mirrored axis maps window-local index z to p - 1 - z.
+ * Gather, flipped: as the gather, the content of every window mirrored along the axes of `flip`; flip = 0 gives the
+ *   gather's bits.
+ * Put: src (count, C, pd, ph, pw), a network's last head with count = windows * N, un-mirrored into dst (count, pd, ph,
+ *   pw, C), a slice of the stitch's window buffer:  dst[m, z, y, x, c] = (accumulate ? dst[m, z, y, x, c] : 0) +
+ *   src[m, c, flip(z), flip(y), flip(x)], one fp32 add; accumulate = 0 copies the bits.  C <= 8, count C pd ph pw < 2^31.
+ * Stitch, weighted: wd, wh, ww are pd, ph, pw fp32 per-axis weights on the device, nflip >= 1 the number of passes
+ *   summed into win.  Over the covering windows in raster order  wgt = (wd[z] wh[y]) ww[x], acc[c] += wgt win[..],
+ *   wsum += wgt  in fp32, then out = acc[c] / ((float)nflip wsum).  All weights 1.0f and nflip = 1: the stitch's bits.
+ * One owner thread per destination element, no atomics: equal inputs give equal bits. */
+int effq_window_gather_flip(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                            int ow, int first, int count, int flip, float* out, void* stream);
+int effq_window_put(const float* src, int count, int C, int pd, int ph, int pw, int flip, int accumulate, float* dst,
+                    void* stream);
+int effq_window_stitch_weighted(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od,
+                                int oh, int ow, const float* wd, const float* wh, const float* ww, int nflip, float* out,
+                                void* stream);
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream);
 
