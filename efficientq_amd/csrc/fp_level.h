@@ -50,7 +50,12 @@ __device__ __forceinline__ LevelConsts level_grid(double lo, double hi, double d
 
 // The fp32 screen: u is off by <= 1.5 lmax 2^-24 (c1 rounded to fp32 on a product of <= lmax / 2, the fma's own rounding
 // of <= lmax 2^-24; c0 is exact) = 2.3e-5 at 256 levels, so rint(u) is the exact level unless u lies within 2e-4 of a
-// rounding boundary (or is NaN).  Returns false there: the caller's exact arithmetic decides.  The band is a constant, so
+// rounding boundary.  Returns false there: the caller's exact arithmetic decides.  A NaN does NOT fail the screen: a NaN v
+// (or a NaN c1) makes u NaN, fmaxf(NaN, 0) is 0 and level 0 is accepted - the level level_exact gives it too, its fmax
+// dropping the NaN of v / a the same way.  A NaN value is not lost for that: level_accum of quant_reduce.hip adds
+// fma(0, NaN) to its sum of r v, which is then NaN, and the scale update ends NaN with done = 1, as the reference's loop
+// does (tests/test_quant_reduce_gpu.py).
+// The band is a constant, so
 // the bound on u must stay well inside it: every entry point that gets here refuses levels > FP_LEVELS_MAX (the bound
 // reaches the band near 2200 levels; emulated in numpy at 65536 levels, the screen puts 4 in 1000 of the values next to
 // a boundary on the wrong level).

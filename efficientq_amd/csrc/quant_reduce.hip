@@ -114,6 +114,13 @@ __global__ __launch_bounds__(TPB) void k_quant_dequant_f32(const float* __restri
   }
 }
 
+// b of the fp64 path: disc64 rounded to fp32, with torch.clamp's NaN propagation as in qd32 (the fmin / fmax of
+// level_exact drop a NaN and would return lo for it); the level id of a NaN is unspecified (include/effq_hip.h)
+__device__ __forceinline__ float qd64(float x, double alpha, double lo, double hi, double d, double* idx) {
+  const float b = (float)disc64((double)x, alpha, lo, hi, d, idx);
+  return (x != x) ? x : b;
+}
+
 __global__ __launch_bounds__(TPB) void k_quant_dequant_f64path(const float* __restrict__ x,
                                                                const double* __restrict__ alpha_dev, double lo,
                                                                double hi, double d, float* __restrict__ y,
@@ -127,10 +134,10 @@ __global__ __launch_bounds__(TPB) void k_quant_dequant_f64path(const float* __re
     float4 v = reinterpret_cast<const float4*>(x)[i];
     double r0, r1, r2, r3;
     float4 b;
-    b.x = (float)disc64((double)v.x, alpha, lo, hi, d, &r0);
-    b.y = (float)disc64((double)v.y, alpha, lo, hi, d, &r1);
-    b.z = (float)disc64((double)v.z, alpha, lo, hi, d, &r2);
-    b.w = (float)disc64((double)v.w, alpha, lo, hi, d, &r3);
+    b.x = qd64(v.x, alpha, lo, hi, d, &r0);
+    b.y = qd64(v.y, alpha, lo, hi, d, &r1);
+    b.z = qd64(v.z, alpha, lo, hi, d, &r2);
+    b.w = qd64(v.w, alpha, lo, hi, d, &r3);
     if (bout) reinterpret_cast<float4*>(bout)[i] = b;
     if (y) {
       float4 o = make_float4(alpha32 * b.x, alpha32 * b.y, alpha32 * b.z, alpha32 * b.w);
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(TPB) void k_quant_dequant_f64path(const float* __re
   }
   for (size_t i = nv * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     double r;
-    float b = (float)disc64((double)x[i], alpha, lo, hi, d, &r);
+    float b = qd64(x[i], alpha, lo, hi, d, &r);
     if (bout) bout[i] = b;
     if (y) y[i] = alpha32 * b;
     if (idx) idx[i] = (unsigned char)r;

@@ -54,13 +54,17 @@ int effq_device_count(int* count);
  * layer_helper.py:25-37, PTQConv.py:114-116.
  * fp32 path: y = (rint((clamp(x/alpha,lo,hi)-lo)/d)*d+lo)*alpha with d=f32((hi-lo)/(L-1)),
  * IEEE divisions, round-half-even, no FMA contraction.  alpha is read from DEVICE
- * memory (one float).  idx_out (uint8 level ids) and y_out may each be NULL. */
+ * memory (one float).  idx_out (uint8 level ids) and y_out may each be NULL.
+ * Non-finite inputs follow torch: -inf / +inf land on level 0 / L-1, a NaN stays NaN in y_out
+ * (torch.clamp propagates it); the level id written for a NaN is unspecified. */
 int effq_quant_dequant_f32(const float* x, const float* alpha_dev, float lo, float hi, int levels,
                            float* y_out, uint8_t* idx_out, size_t n, void* stream);
 
 /* fp64 path used during calibration (project_by_iter's final discretize,
  * layer_helper.py:50-66, then "a * b", EfficientQConv.py:68-70):
- * b = f32(discretize(f64(x)/alpha)), y = f32(alpha)*b.  alpha is a DEVICE double. */
+ * b = f32(discretize(f64(x)/alpha)), y = f32(alpha)*b.  alpha is a DEVICE double.
+ * y_out, b_out and idx_out may each be NULL.  A NaN in x is NaN in b_out and y_out; its level
+ * id is unspecified, as above. */
 int effq_quant_dequant_f64path(const float* x, const double* alpha_dev, double lo, double hi, int levels,
                                float* y_out, float* b_out, uint8_t* idx_out, size_t n, void* stream);
 
