@@ -198,6 +198,10 @@ SIGNATURES = {
     "effq_cc_table_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "effq_cc_table": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "effq_seg_lesion_table": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "effq_label_clean_ws_bytes": (_SZ, [_I, _I, _I]),
+    "effq_label_clean": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "effq_label_tallies_ws_bytes": (_SZ, []),
+    "effq_label_tallies": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P, _SZ, _P]),
     "effq_surf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_edt_sq": (_I, [_P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_seg_surface": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
@@ -228,6 +232,9 @@ LESION_CONNECTIVITY = 26
 CC_TABLE_CHUNK = 2048
 # rows per plane that cc_table / seg_lesion_table ask for first; a plane with more components costs one more call
 LESION_TABLE_ROWS = 4096
+# include/effq_hip.h: the rules of effq_label_clean (--post) and how many one call takes
+LABEL_CLEAN_MAX_RULES = 8
+LABEL_CLEAN_OPS = {"largest": 0, "min": 1}
 # include/effq_hip.h: the longest line of the h and d passes of the distance transform
 EDT_MAX_LINE = 16382
 # include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)

@@ -7,6 +7,7 @@ argument is forwarded to the conv constructor as ``**kwQ``.
 from __future__ import annotations
 
 import argparse
+import collections
 import re
 
 import torch.nn as nn
@@ -106,6 +107,14 @@ def build_parser():
     p.add_argument('--tta_mirror', default=None,
                    help='mirror test-time augmentation: letters of d, h, w, each at most once (w, hw, dhw); every '
                         'window also runs mirrored along each subset of the axes and the logits are averaged')
+    # connected-component clean-up of the predicted label maps (predict, and the validation of ptq); the rules are checked
+    # by post_rules, after the YAML has been merged in
+    p.add_argument('--post', action='append', default=None, metavar='RULE',
+                   help='clean the predicted map by connected components, repeatable, in order: LABELS:largest[>TO] keeps '
+                        'the largest component of the voxels whose label is one of LABELS, LABELS:minN[>TO] relabels '
+                        'every component of fewer than N voxels; the others become TO (default 0): 1,2:largest  \'4:min500>1\' '
+                        '(quote a rule with > on a shell command line: unquoted, the shell takes >TO for a redirection)')
+    p.add_argument('--post_conn', default=None, help='the neighbourhood of every --post rule: 26 (default) or 6')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
@@ -125,6 +134,88 @@ def blend_switches(args):
     except ValueError as e:
         raise SystemExit(f'--tta_mirror {e}')
     return blend, flips
+
+
+POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES
+POST_CONN_DEFAULT = 26       # the neighbourhood of --is_cc
+PostRule = collections.namedtuple('PostRule', 'labels op n to')      # labels: tuple of 1..255; op: largest / min
+
+
+def post_rule_text(rule) -> str:
+    """A rule in the form --post takes it: `1,2:largest`, `4:min500>1`."""
+    labels, op, n, to = rule
+    return ','.join(str(v) for v in labels) + ':' + op + (str(n) if op == 'min' else '') + (f'>{to}' if to else '')
+
+
+def post_text(rules, connectivity=POST_CONN_DEFAULT) -> str:
+    """The `post` column of predict.csv: the rules joined by a space, ` conn6` when the neighbourhood is not the default."""
+    return ' '.join([post_rule_text(r) for r in rules] +
+                    ([f'conn{connectivity}'] if connectivity != POST_CONN_DEFAULT else []))
+
+
+def parse_post_rule(text) -> PostRule:
+    """One RULE = LABELS ":" OP [ ">" TO ] of --post; what is not understood is refused by name (SystemExit)."""
+    t = str(text).strip()
+    m = re.fullmatch(r'([^:>]*):([^:>]*)(?:>([^:>]*))?', t)
+    if m is None:
+        raise SystemExit(f'--post {t!r}: a rule is LABELS:OP or LABELS:OP>TO, as in 1,2:largest or 4:min500>1')
+    labs, op, to = m.group(1).strip(), m.group(2).strip(), m.group(3)
+    if not labs:
+        raise SystemExit(f'--post {t!r}: empty LABELS: name the label values of the mask, as in 1,2:largest')
+    labels = []
+    for v in labs.split(','):
+        if not re.fullmatch(r'\s*\d+\s*', v) or not 1 <= int(v) <= 255:
+            raise SystemExit(f'--post {t!r}: label {v.strip()!r}: the label values of a mask are 1 to 255')
+        if int(v) not in labels:
+            labels.append(int(v))
+    mm = re.fullmatch(r'min\s*(-?\d+)', op)
+    if op == 'largest':
+        n = 0
+    elif mm is not None:
+        n = int(mm.group(1))
+        if n < 1:
+            raise SystemExit(f'--post {t!r}: min {n}: N is a size in voxels, 1 or more')
+    else:
+        raise SystemExit(f'--post {t!r}: unknown op {op!r}: one of largest, minN (N voxels)')
+    dest = 0
+    if to is not None:
+        if not re.fullmatch(r'\s*\d+\s*', to) or int(to) > 255:
+            raise SystemExit(f'--post {t!r}: TO {to.strip()!r}: the new label is 0 to 255')
+        dest = int(to)
+    if dest in labels:
+        raise SystemExit(f'--post {t!r}: TO {dest} is one of LABELS: the relabelled voxels would stay in the mask')
+    return PostRule(tuple(labels), 'largest' if op == 'largest' else 'min', n, dest)
+
+
+def parse_post_text(text):
+    """(rules, connectivity) back from post_text's string."""
+    words = str(text).split()
+    conn = POST_CONN_DEFAULT
+    if words and words[-1].startswith('conn'):
+        conn = int(words.pop()[4:])
+    return [parse_post_rule(w) for w in words], conn
+
+
+def post_rules(args):
+    """(rules, connectivity) of --post / --post_conn (or the YAML keys `post`, a list, and `post_conn`): a list of PostRule
+    in the order given ([] without --post) and 6 or 26.  What is not understood is refused by name (SystemExit), host
+    only."""
+    given = getattr(args, 'post', None)
+    conn = getattr(args, 'post_conn', None)
+    if given is None or given == []:
+        if conn is not None:
+            raise SystemExit(f'--post_conn {conn}: the neighbourhood of the --post rules, and no --post is given')
+        return [], POST_CONN_DEFAULT
+    if isinstance(given, (str, int)):
+        given = [given]
+    if len(given) > POST_MAX_RULES:
+        raise SystemExit(f'--post: {len(given)} rules, at most {POST_MAX_RULES}')
+    rules = [parse_post_rule(t) for t in given]
+    if conn is None:
+        return rules, POST_CONN_DEFAULT
+    if str(conn).strip() not in ('6', '26'):
+        raise SystemExit(f'--post_conn {conn!r}: one of 6, 26')
+    return rules, int(conn)
 
 
 def _pair(s):
@@ -207,7 +298,7 @@ TINY_NET = dict(task='lits', model='UResQ', nMod=1, nClass=3, multi_label=None, 
 
 def make_args(net: dict, qlvl_w: int, qlvl_a: int, **over):
     base = dict(pretrain=None, resume=None, device=0, round='1', suffix='', config=None, test_fp=False,
-                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, vs_fp=False, unlabelled=False, src_geom=False, spacing=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
+                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, vs_fp=False, unlabelled=False, src_geom=False, spacing=None, post=None, post_conn=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
                 lwq_verbose=False, qlvl_w=qlvl_w, qlvl_a=qlvl_a)
     base.update(net)
     base.update(over)

@@ -10,6 +10,8 @@
 //   flatten  every voxel is pointed at its root; a voxel that both masks of a class hold flags the two roots
 //   count    roots and roots without a flag, per-block partials, added in block order by the last launch
 //   table    (effq_cc_table, effq_seg_lesion_table) one record per component, four more launches: see "table" below
+//   clean    (effq_label_clean) the components of a label map's values sized at their roots and the small or losing ones
+//            relabelled: see "clean" below
 //
 // The parent of a voxel always has a smaller index than the voxel, so the root of a component is its least index whatever
 // order the unions ran in: the labels are the same bits every time.  Every loop ends by itself: a find walks down strictly
@@ -529,6 +531,134 @@ static int cc_table_run(const CcTableWs& t, const uint16_t* bits, int C, int P, 
   return EFFQ_OK;
 }
 
+// ---- clean ----------------------------------------------------------------------------------------------------------
+// effq_label_clean: the rules of --post on a uint8 label map, one after the other on the map the previous rule left.  Per
+// rule, after the five launches of cc_run on the plane "the voxel's value is in the rule's set":
+//
+//   mask     (before cc_run) the membership of every voxel -> one 0/1 plane; the size words are zeroed in the same pass
+//   sizes    every foreground voxel adds 1 to the size word of its root: equal roots of a wave are added once (the lane
+//            count), as k_cc_accum does
+//   best     (largest only) every root offers size << 32 | (0xFFFFFFFF - root) to one 64-bit atomicMax: the largest size
+//            wins, and of equal sizes the least root (the component whose first voxel comes first)
+//   apply    the voxels of a losing (largest) or small (min) component become TO and are counted
+//
+// Integer adds and one max only: equal inputs give equal bits.  The map is rewritten in place (`out`, a copy of `in` when
+// they differ): a voxel is written by the thread that read it, and the labels of a rule are complete before its apply.
+struct CleanSet {
+  unsigned long long w[4];   // bit v set: the value v is in the rule's mask
+};
+
+struct CleanWs {
+  uint32_t* partial;             // (CC_COUNT_BLOCKS, 2): cc_run's
+  int* labels;                   // (S)
+  int* sizes;                    // (S): the voxels of a component, at its root
+  uint8_t* mask;                 // (S)
+  unsigned long long* best;      // (EFFQ_LABEL_CLEAN_MAX_RULES)
+  size_t bytes;
+};
+
+static CleanWs clean_ws(void* ws, size_t S) {
+  CleanWs r;
+  char* p = static_cast<char*>(ws);
+  size_t off = 0;
+  r.partial = reinterpret_cast<uint32_t*>(p + off); off += align16((size_t)CC_COUNT_BLOCKS * 2 * sizeof(uint32_t));
+  r.labels = reinterpret_cast<int*>(p + off);       off += align16(S * sizeof(int));
+  r.sizes = reinterpret_cast<int*>(p + off);        off += align16(S * sizeof(int));
+  r.mask = reinterpret_cast<uint8_t*>(p + off);     off += align16(S);
+  r.best = reinterpret_cast<unsigned long long*>(p + off);
+  off += align16(EFFQ_LABEL_CLEAN_MAX_RULES * sizeof(unsigned long long));
+  r.bytes = off;
+  return r;
+}
+
+// stats (R, 2): the relabelled voxels start at 0 (the components are written by k_cc_final); best (R) starts at 0
+__global__ __launch_bounds__(64) void k_clean_init(unsigned long long* __restrict__ best, long long* __restrict__ stats,
+                                                   int R) {
+  const int r = threadIdx.x;
+  if (r >= R) return;
+  best[r] = 0ull;
+  stats[2 * r + 1] = 0;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_clean_mask(const uint8_t* __restrict__ map, CleanSet set, int S,
+                                                           uint8_t* __restrict__ mask, int* __restrict__ sizes) {
+  for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * CC_THREADS) {
+    const uint32_t v = map[i];
+    mask[i] = (uint8_t)((set.w[v >> 6] >> (v & 63u)) & 1ull);
+    sizes[i] = 0;
+  }
+}
+
+// labels: flattened (labels[v] = root + 1, 0 for background)
+__global__ __launch_bounds__(CC_THREADS) void k_clean_sizes(const int* __restrict__ labels, int S,
+                                                            int* __restrict__ sizes) {
+  const int lane = threadIdx.x & 63;
+  // the trip count is the same for every lane of a wave: the ballots below need them all
+  for (long long i0 = (long long)blockIdx.x * CC_THREADS; i0 < S; i0 += (long long)gridDim.x * CC_THREADS) {
+    const long long i = i0 + threadIdx.x;
+    const int r = i < S ? labels[i] - 1 : -1;      // the root of this lane's voxel; -1: nothing to add
+    unsigned long long todo = __ballot(r >= 0);
+    int add = 0;                                    // the leader of a group carries the group's count
+    for (int round = 0; round < CC_MATCH_ROUNDS && todo; ++round) {
+      const int lead = __ffsll((long long)todo) - 1;
+      const int key = __shfl(r, lead, 64);
+      const unsigned long long m = __ballot(r == key) & todo;
+      if (lane == lead) add = __popcll(m);
+      todo &= ~m;
+    }
+    if ((todo >> lane) & 1ull) add = 1;            // more distinct roots than rounds: one add per voxel
+    if (add) atomicAdd(&sizes[r], add);
+  }
+}
+
+__global__ __launch_bounds__(CC_THREADS) void k_clean_best(const int* __restrict__ labels,
+                                                           const int* __restrict__ sizes, int S,
+                                                           unsigned long long* __restrict__ best) {
+  unsigned long long key = 0ull;
+  for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * CC_THREADS) {
+    const int v = (int)i;
+    if (labels[v] != v + 1) continue;
+    const unsigned long long k = ((unsigned long long)(uint32_t)sizes[v] << 32) | (0xFFFFFFFFull - (uint32_t)v);
+    key = k > key ? k : key;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o, 64);
+    key = other > key ? other : key;
+  }
+  if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
+}
+
+// OP LARGEST: every component but the winner of `best` loses; OP MIN: every component of fewer than n voxels does
+template <int OP>
+__global__ __launch_bounds__(CC_THREADS) void k_clean_apply(const int* __restrict__ labels,
+                                                            const int* __restrict__ sizes,
+                                                            const unsigned long long* __restrict__ best, long long n,
+                                                            int to, int S, uint8_t* __restrict__ map,
+                                                            unsigned long long* __restrict__ changed) {
+  int keep = -1;
+  if constexpr (OP == EFFQ_LABEL_CLEAN_LARGEST) keep = (int)(0xFFFFFFFFu - (uint32_t)(*best & 0xFFFFFFFFull));
+  uint32_t cnt = 0;
+  for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * CC_THREADS) {
+    const int l = labels[i];
+    if (l == 0) continue;
+    const bool lose = OP == EFFQ_LABEL_CLEAN_LARGEST ? l - 1 != keep : (long long)sizes[l - 1] < n;
+    if (lose) {
+      map[i] = (uint8_t)to;
+      ++cnt;
+    }
+  }
+  __shared__ uint32_t red[CC_WAVES];
+  cnt = cc_wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (int w = 0; w < CC_WAVES; ++w) s += red[w];
+    if (s) atomicAdd(changed, (unsigned long long)s);
+  }
+}
+
 }  // namespace effq
 using namespace effq;
 
@@ -623,6 +753,65 @@ int effq_seg_lesion_table(const float* logits, const uint8_t* label, int C, int 
   rc = cc_run(src, P, D, H, W, connectivity, t.cc.labels, t.cc.flags, C, t.cc.partial, counts, st);
   if (rc != EFFQ_OK) return rc;
   return cc_table_run(t, t.cc.bits, C, P, (int)S, max_rows, 3, rows, nrows, st);
+}
+
+size_t effq_label_clean_ws_bytes(int D, int H, int W) {
+  if (!cc_dims_ok(1, D, H, W)) return 0;
+  return clean_ws(nullptr, (size_t)D * H * W).bytes;
+}
+
+int effq_label_clean(const uint8_t* in, int D, int H, int W, int connectivity, int R, const uint8_t* sets,
+                     const long long* rules, uint8_t* out, long long* stats, void* ws, size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(in && sets && rules && out && stats && ws);
+  EFFQ_CHECK_ARG(R >= 1 && R <= EFFQ_LABEL_CLEAN_MAX_RULES);
+  EFFQ_CHECK_ARG(cc_dims_ok(1, D, H, W));
+  EFFQ_CHECK_ARG(connectivity == 6 || connectivity == 26);
+  CleanSet set[EFFQ_LABEL_CLEAN_MAX_RULES];
+  for (int r = 0; r < R; ++r) {
+    const long long op = rules[3 * r], n = rules[3 * r + 1], to = rules[3 * r + 2];
+    EFFQ_CHECK_ARG(op == EFFQ_LABEL_CLEAN_LARGEST || op == EFFQ_LABEL_CLEAN_MIN);
+    EFFQ_CHECK_ARG(op != EFFQ_LABEL_CLEAN_MIN || n >= 1);
+    EFFQ_CHECK_ARG(to >= 0 && to <= 255);
+    EFFQ_CHECK_ARG(sets[256 * r] == 0 && sets[256 * r + to] == 0);
+    for (int k = 0; k < 4; ++k) set[r].w[k] = 0ull;
+    for (int v = 0; v < 256; ++v)
+      if (sets[256 * r + v]) set[r].w[v >> 6] |= 1ull << (v & 63);
+  }
+  const int S = D * H * W;
+  const CleanWs s = clean_ws(ws, (size_t)S);
+  if (ws_bytes < s.bytes) {
+    set_error("effq_label_clean: workspace of %zu bytes, needs %zu", ws_bytes, s.bytes);
+    return EFFQ_ERR_WORKSPACE;
+  }
+  const hipStream_t st = as_stream(stream);
+  const dim3 b(CC_THREADS), gs(cc_grid((size_t)S, CC_STREAM_BLOCKS));
+  if (out != in) EFFQ_HIP(hipMemcpyAsync(out, in, (size_t)S, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_clean_init, dim3(1), dim3(64), 0, st, s.best, stats, R);
+  EFFQ_LAUNCH_CHECK();
+  CcSrc src;
+  src.masks = s.mask; src.bits = nullptr; src.C = 0;
+  for (int r = 0; r < R; ++r) {
+    const long long n = rules[3 * r + 1];
+    const int to = (int)rules[3 * r + 2];
+    unsigned long long* changed = reinterpret_cast<unsigned long long*>(stats + 2 * r + 1);
+    hipLaunchKernelGGL(k_clean_mask, gs, b, 0, st, out, set[r], S, s.mask, s.sizes);
+    EFFQ_LAUNCH_CHECK();
+    const int rc = cc_run(src, 1, D, H, W, connectivity, s.labels, nullptr, 0, s.partial, stats + 2 * r, st);
+    if (rc != EFFQ_OK) return rc;
+    hipLaunchKernelGGL(k_clean_sizes, gs, b, 0, st, s.labels, S, s.sizes);
+    EFFQ_LAUNCH_CHECK();
+    if (rules[3 * r] == EFFQ_LABEL_CLEAN_LARGEST) {
+      hipLaunchKernelGGL(k_clean_best, gs, b, 0, st, s.labels, s.sizes, S, s.best + r);
+      EFFQ_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_clean_apply<EFFQ_LABEL_CLEAN_LARGEST>, gs, b, 0, st, s.labels, s.sizes, s.best + r, n, to, S,
+                         out, changed);
+    } else {
+      hipLaunchKernelGGL(k_clean_apply<EFFQ_LABEL_CLEAN_MIN>, gs, b, 0, st, s.labels, s.sizes, s.best + r, n, to, S, out,
+                         changed);
+    }
+    EFFQ_LAUNCH_CHECK();
+  }
+  return EFFQ_OK;
 }
 
 }  // extern "C"

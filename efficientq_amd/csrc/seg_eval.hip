@@ -1,7 +1,8 @@
 // Validation of a segmentation network on whole volumes (evaluate.validate_seg): the overlapped windows of a volume
 // gathered into one channels-last batch, the per-window logits stitched back to the volume, and the per-class confusion
-// counts of the stitched logits against the label, and the label maps written for the viewer (--save_nii).  All four
-// stream HBM once and do no arithmetic to speak of.
+// counts of the stitched logits against the label, the label maps written for the viewer (--save_nii), and the counts
+// of a label map against the label (effq_label_tallies, the score of a map cleaned by --post).  All five stream HBM once
+// and do no arithmetic to speak of.
 //
 // Windows: along each axis the starts are  min(i * (patch - overlap), size - patch)  for i = 0 .. n-1 with
 // n = ceil((size - patch) / (patch - overlap)) + 1, i.e. evaluate.window_starts: steps while a whole patch ends strictly
@@ -192,6 +193,106 @@ __global__ __launch_bounds__(64) void k_seg_tallies_final(const uint32_t* __rest
   }
 }
 
+// ---- tallies of a label map -------------------------------------------------------------------------------------------
+// effq_label_tallies: the counters of k_seg_tallies for a uint8 label map instead of logits.  The class bits of a value
+// come from a 256-entry table (kept in LDS); the truth is a map read through the same table, or C 0/1 planes.  VEC 4: one
+// 4-B load per thread, map and plane; the last S % 4 voxels are counted one by one by the first threads of the grid.
+constexpr int LTALLY_MAX_BLOCKS = 512;
+static_assert(LTALLY_MAX_BLOCKS <= TALLY_MAX_BLOCKS, "the partials fit the tallies' workspace");
+
+struct LabelLut {
+  uint16_t v[256];
+};
+
+struct LabelTallyParams {
+  const uint8_t* pred;    // (S)
+  const uint8_t* truth;   // (S) label values, or (C, S) 0/1 planes
+  uint32_t* partial;      // (gridDim.x, 3 * C)
+  long long S;
+};
+
+template <int VEC, bool PLANES, int C>
+__global__ __launch_bounds__(TALLY_THREADS) void k_label_tallies(LabelTallyParams p, LabelLut lut) {
+  __shared__ uint16_t s_lut[256];
+  for (int k = threadIdx.x; k < 256; k += TALLY_THREADS) s_lut[k] = lut.v[k];
+  __syncthreads();
+  uint32_t cnt[3 * C];
+#pragma unroll
+  for (int q = 0; q < 3 * C; ++q) cnt[q] = 0;
+  auto tally = [&](uint32_t pred, uint32_t gt) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      cnt[3 * c + 0] += (pred >> c) & (gt >> c) & 1u;
+      cnt[3 * c + 1] += (pred >> c) & 1u;
+      cnt[3 * c + 2] += (gt >> c) & 1u;
+    }
+  };
+  auto truth_bits = [&](long long v) -> uint32_t {
+    if constexpr (!PLANES) {
+      return s_lut[p.truth[v]];
+    } else {
+      uint32_t gt = 0;
+#pragma unroll
+      for (int c = 0; c < C; ++c) gt |= (p.truth[c * p.S + v] != 0 ? 1u : 0u) << c;
+      return gt;
+    }
+  };
+  const long long groups = p.S / VEC;
+  const long long tid = (long long)blockIdx.x * TALLY_THREADS + threadIdx.x;
+  for (long long g = tid; g < groups; g += (long long)gridDim.x * TALLY_THREADS) {
+    if constexpr (VEC == 4) {
+      const uchar4 m = *reinterpret_cast<const uchar4*>(p.pred + g * 4);
+      const uint32_t pr[4] = {s_lut[m.x], s_lut[m.y], s_lut[m.z], s_lut[m.w]};
+      uint32_t gt[4] = {0, 0, 0, 0};
+      if constexpr (!PLANES) {
+        const uchar4 t = *reinterpret_cast<const uchar4*>(p.truth + g * 4);
+        gt[0] = s_lut[t.x]; gt[1] = s_lut[t.y]; gt[2] = s_lut[t.z]; gt[3] = s_lut[t.w];
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const uchar4 t = *reinterpret_cast<const uchar4*>(p.truth + c * p.S + g * 4);
+          gt[0] |= (t.x != 0 ? 1u : 0u) << c; gt[1] |= (t.y != 0 ? 1u : 0u) << c;
+          gt[2] |= (t.z != 0 ? 1u : 0u) << c; gt[3] |= (t.w != 0 ? 1u : 0u) << c;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) tally(pr[u], gt[u]);
+    } else {
+      tally(s_lut[p.pred[g]], truth_bits(g));
+    }
+  }
+  if (VEC == 4 && tid < p.S - groups * 4) {          // the tail
+    const long long v = groups * 4 + tid;
+    tally(s_lut[p.pred[v]], truth_bits(v));
+  }
+  __shared__ uint32_t red[TALLY_WAVES][3 * C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < 3 * C; ++q) {
+    const uint32_t s = wave_sum(cnt[q]);
+    if (lane == 0) red[wave][q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * C) {
+    uint32_t s = 0;
+    for (int w = 0; w < TALLY_WAVES; ++w) s += red[w][threadIdx.x];
+    p.partial[(size_t)blockIdx.x * 3 * C + threadIdx.x] = s;
+  }
+}
+
+template <int C>
+static void launch_label_tallies(bool planes, bool v4, dim3 g, hipStream_t st, const LabelTallyParams& p,
+                                 const LabelLut& lut) {
+  const dim3 b(TALLY_THREADS);
+  if (planes) {
+    if (v4) hipLaunchKernelGGL((k_label_tallies<4, true, C>), g, b, 0, st, p, lut);
+    else hipLaunchKernelGGL((k_label_tallies<1, true, C>), g, b, 0, st, p, lut);
+  } else {
+    if (v4) hipLaunchKernelGGL((k_label_tallies<4, false, C>), g, b, 0, st, p, lut);
+    else hipLaunchKernelGGL((k_label_tallies<1, false, C>), g, b, 0, st, p, lut);
+  }
+}
+
 // ---- label maps ---------------------------------------------------------------------------------------------------
 // The decisions of decide<MODE, C> (the tallies' own, so the maps and the counts cannot disagree) turned into a label
 // per voxel, or into C 0/1 planes.  One thread per VEC voxels, 16-B logit loads per channel, one store per thread and
@@ -360,6 +461,42 @@ int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long
   }
   EFFQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_seg_tallies_final, dim3(1), dim3(64), 0, as_stream(stream), p.partial, (int)nb, C, S, counts);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+size_t effq_label_tallies_ws_bytes(void) { return (size_t)LTALLY_MAX_BLOCKS * TALLY_NCNT * sizeof(uint32_t); }
+
+int effq_label_tallies(const uint8_t* pred, const uint8_t* truth, int truth_planes, int C, long long S,
+                       const uint16_t* lut, long long* counts, void* ws, size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(pred && truth && lut && counts && ws && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
+  EFFQ_CHECK_ARG(S > 0 && S < (1ll << 40));            // a workgroup's partial counts are 32-bit
+  if (ws_bytes < effq_label_tallies_ws_bytes()) {
+    set_error("effq_label_tallies: workspace of %zu bytes, needs %zu", ws_bytes, effq_label_tallies_ws_bytes());
+    return EFFQ_ERR_WORKSPACE;
+  }
+  LabelLut l;
+  for (int v = 0; v < 256; ++v) l.v[v] = (uint16_t)(lut[v] & ((1u << C) - 1u));
+  LabelTallyParams p;
+  p.pred = pred; p.truth = truth; p.partial = static_cast<uint32_t*>(ws); p.S = S;
+  const bool planes = truth_planes != 0;
+  const bool v4 = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(truth)) & 3) == 0 &&
+                  (!planes || S % 4 == 0);
+  const unsigned nb = grid_for((size_t)(v4 ? (S + 3) / 4 : S), LTALLY_MAX_BLOCKS);
+  const dim3 g(nb);
+  const hipStream_t st = as_stream(stream);
+  switch (C) {
+    case 1: launch_label_tallies<1>(planes, v4, g, st, p, l); break;
+    case 2: launch_label_tallies<2>(planes, v4, g, st, p, l); break;
+    case 3: launch_label_tallies<3>(planes, v4, g, st, p, l); break;
+    case 4: launch_label_tallies<4>(planes, v4, g, st, p, l); break;
+    case 5: launch_label_tallies<5>(planes, v4, g, st, p, l); break;
+    case 6: launch_label_tallies<6>(planes, v4, g, st, p, l); break;
+    case 7: launch_label_tallies<7>(planes, v4, g, st, p, l); break;
+    default: launch_label_tallies<8>(planes, v4, g, st, p, l); break;
+  }
+  EFFQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_seg_tallies_final, dim3(1), dim3(64), 0, st, p.partial, (int)nb, C, S, counts);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

@@ -24,6 +24,11 @@ decided differently, the logit drift and the probability drift, the lesion / sur
 ``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched, and
 ``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
 averages the logits; both hold for every validation of the run (and for ``predict``), the FP network's included.
+``--post RULE`` (repeatable, ``--post_conn 6|26``) also cleans every labelled val case's predicted map by connected
+components on the device (``1,2:largest`` keeps the largest component of the labels 1 and 2, ``'4:min500>1'`` - quoted,
+or the shell takes ``>1`` for a redirection - relabels every component of label 4 with fewer than 500 voxels to 1) and
+scores the cleaned map: ``<snap>/{fp,ptq}/metrics_post.csv``; ``metrics.csv`` and every other file stay what they are.
+It needs labels: with ``--unlabelled`` or ``--synthetic`` it is refused.  ``predict --post`` writes the cleaned maps.
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing, unless ``--vs_fp``
 is given: then two held-out synthetic volumes are validated against the FP network; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
@@ -84,10 +89,11 @@ class _ValidationTester(_SnapshotWriter):
     <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
     labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written."""
 
-    def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,)):
+    def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,), post=(), post_conn=26):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
         self.blend, self.flips = blend, tuple(flips)
+        self.post, self.post_conn = list(post), post_conn
 
     def _geometry(self, is_save_nii, is_surf, is_table=False):
         """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances,
@@ -121,6 +127,7 @@ class _ValidationTester(_SnapshotWriter):
                              **({'fp_model': fp_model} if fp_model is not None else {}),
                              **({'blend': self.blend, 'flips': self.flips}
                                 if (self.blend, self.flips) != ('uniform', (0,)) else {}),
+                             **({'post': self.post, 'post_conn': self.post_conn} if self.post else {}),
                              **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
         if fp_model is not None:
@@ -150,6 +157,14 @@ class _ValidationTester(_SnapshotWriter):
             print(f'[entrance] {folder}: label lesions detected / all, by size in voxels:')
             for c in range(bins.shape[0]):
                 print(f'  class {c}: ' + ', '.join(f'{n}: {int(k[1])} / {int(k[0])}' for n, k in zip(names, bins[c])))
+        if self.post:
+            E.write_metrics_post_csv(os.path.join(out, 'metrics_post.csv'), res)
+            after = E.post_means(res)
+            changed = [sum(r['post']['changed'][k] for r in res) for k in range(len(self.post))]
+            print(f'[entrance] {folder}: --post {Cf.post_text(self.post, self.post_conn)}: '
+                  f'{" ".join(str(v) for v in changed)} voxels relabelled, per-class mean dsc before -> after:')
+            for c in range(len(means['dsc'])):
+                print(f'  class {c}: {float(means["dsc"][c]):.4f} -> {float(after["dsc"][c]):.4f}')
         if fp_model is not None:
             self._print_agreement(folder, res)
 
@@ -194,6 +209,7 @@ def check_switches(args):
     """The combinations of --vs_fp / --unlabelled that cannot run and the values of --blend / --tta_mirror that are not
     understood, refused before anything touches the device (host only: SystemExit naming the switches)."""
     Cf.blend_switches(args)
+    check_post(args)
     if not getattr(args, 'unlabelled', False):
         return
     if not getattr(args, 'vs_fp', False):
@@ -206,11 +222,32 @@ def check_switches(args):
                          '--surf_dist are measured against the FP network): drop --lesion_table')
 
 
+def check_post(args):
+    """The --post rules that are not understood and the missions and label forms they cannot serve, refused by name
+    before anything runs (host only: SystemExit); returns (rules, connectivity)."""
+    rules, conn = Cf.post_rules(args)
+    if not rules:
+        return rules, conn
+    if getattr(args, 'mission', None) == 'prep':
+        raise SystemExit('--post cleans predicted label maps: the prep mission predicts nothing, drop --post')
+    multi_label = getattr(args, 'multi_label', None)
+    if multi_label:
+        rule = E.label_rule(True, multi_label, (getattr(args, 'task', None) or 'lits').lower())
+        if rule == 'planes' or not getattr(args, 'merge_type', None):
+            raise SystemExit(E.post_refusal(rule))
+    for switch in ('unlabelled', 'synthetic'):
+        if getattr(args, switch, False):
+            raise SystemExit(f'--post --{switch}: a cleaned map is scored against the labels, and there are none: drop '
+                             f'--post (the predict mission cleans maps without labels)')
+    return rules, conn
+
+
 def main(argv=None):
     args = Cf.build_parser().parse_args(argv)
     if args.config:
         args = Cf.merge_config(args.config, args)
     if args.mission == 'prep':
+        check_post(args)
         from . import prep
         prep.run(args)
         return
@@ -226,6 +263,11 @@ def main(argv=None):
     if sliding:
         print(f'[entrance] sliding window: blend {blend}, {len(flips)} passes per window (flip masks '
               f'{" ".join(str(m) for m in flips)})')
+    post, post_conn = Cf.post_rules(args)
+    cleaning = {'post': post, 'post_conn': post_conn} if post else {}
+    if post:
+        print(f'[entrance] --post {Cf.post_text(post, post_conn)}: every labelled validation also scores the cleaned map '
+              f'(metrics_post.csv)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -259,7 +301,8 @@ def main(argv=None):
         with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
             f.write(' '.join(sys.argv) + '\n')
         rank = int(os.environ.get('RANK', '0'))
-        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank, **sliding), snap)
+        tester = _ValidationTester(model, snap, data_cube, args.task, rank, **sliding, **cleaning)
+        K.do_ptq(args, cube, data_cube, tester, snap)
         return
     size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
     size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
@@ -269,7 +312,8 @@ def main(argv=None):
         f.write(' '.join(sys.argv) + '\n')
     if data_cube.valloader is not None:
         rank = int(os.environ.get('RANK', '0'))
-        K.do_ptq(args, cube, data_cube, _ValidationTester(model, snap, data_cube, args.task, rank, **sliding), snap)
+        tester = _ValidationTester(model, snap, data_cube, args.task, rank, **sliding, **cleaning)
+        K.do_ptq(args, cube, data_cube, tester, snap)
         return
     K.do_ptq(args, cube, data_cube, _SnapshotWriter(model, snap), snap)
 

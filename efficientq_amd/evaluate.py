@@ -234,6 +234,29 @@ def label_rule(multi: bool, multi_label=None, task: str = "lits") -> str:
     return "brats" if key == "brats" else "planes"
 
 
+def post_class_lut(rule: str, C: int) -> list:
+    """The 256-entry class table of effq_label_tallies for the maps of `rule`: bit c set = the value belongs to class c.
+    argmax: class c is the value c.  brats (merge_label_brats of nested planes): WT = {1, 2, 4}, TC = {1, 4}, ET = {4}."""
+    lut = [0] * 256
+    if rule == "argmax":
+        for c in range(C):
+            lut[c] = 1 << c
+    elif rule == "brats" and C == 3:
+        lut[1], lut[2], lut[4] = 0b011, 0b001, 0b111
+    else:
+        raise RuntimeError(f"post_class_lut: no class table for the maps of rule {rule} with {C} classes")
+    return lut
+
+
+def post_refusal(rule: str) -> str:
+    """Why the maps of `rule` cannot be cleaned and scored (validate_seg(..., post=...)), in the switches' names."""
+    if rule == "planes":
+        return ("--post with --multi_label lits: the prediction is one plane per class (C x D x H x W), not a label map "
+                "whose components could be cleaned")
+    return ("--post with --multi_label brats needs --merge_type agg or con: planes that are not nested cannot be read "
+            "back from the merged label map")
+
+
 def _write_map(path, host, dtype, entry=None):
     """The map of one case; with the entry of its source image (data.read_source_geometry) restored into the source's
     shape (zeros outside pmin:pmax) and written with the source's geometry."""
@@ -380,7 +403,7 @@ def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
-                 geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,)):
+                 geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,), post=None, post_conn=26):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -424,10 +447,17 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     data.SegVolumes(labels=False)) is unlabelled: it needs fp_model, takes the counting from `multi_label` (set: sigmoid
     per channel, else argmax) and its dict carries name and vs_fp only.
     blend, flips: the window weights and the mirror passes of stitched_window_logits (--blend, --tta_mirror); with
-    fp_model both networks are blended and augmented alike.  Everything after the stitch is unchanged."""
+    fp_model both networks are blended and augmented alike.  Everything after the stitch is unchanged.
+    post, post_conn: the rules (config.post_rules) and the neighbourhood of --post.  Each labelled case's predicted map
+    (effq_seg_labels, uint8, rule label_rule(...)) is also cleaned by connected components on the given grid
+    (effq_label_clean) and tallied against the label (effq_label_tallies with post_class_lut's table), and its dict gains
+    "post": counts (C x 4) with dsc / sens / spec / acc, and "changed", the voxels each rule relabelled.  Every other
+    entry and the maps of save_dir stay what they are.  The planes of --multi_label lits are no label map, and the
+    planes of --multi_label brats are read back from the map only when `fuse` nests them: both are a RuntimeError."""
     from .hip_ops import get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
+    post = list(post) if post else []
     dev = next(model.parameters()).device
     ops = get_ops(dev)
     p, o = _triple(patch_size), _triple(overlap)
@@ -471,6 +501,13 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                                            f"cannot be written on the source grid: save them without --src_geom")
                 maps = ops.seg_labels(stitched, rule, fuse if multi else None,
                                       torch.uint8 if rule == "planes" else map_dtype).cpu().numpy()
+            post_maps = None
+            if post and labelled:
+                post_rule = label_rule(multi, multi_label, task)
+                if post_rule == "planes" or (post_rule == "brats" and not fuse):
+                    raise RuntimeError("validate_seg: post: " + post_refusal(post_rule))
+                post_maps = ops.seg_labels(stitched, post_rule, fuse if multi else None, torch.uint8)
+                post_lut = post_class_lut(post_rule, int(stitched.shape[1]))
             for n in range(N):
                 i = len(results)
                 res = {"name": names[i] if names is not None else str(i)}
@@ -492,6 +529,11 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                         res["lesions"] = ops.seg_lesions(stitched[n], lab[n], kind, fz).cpu()
                     if surface:
                         res.update(_surface_entries(ops, stitched[n], lab[n], kind, fz, vol.shape[-3:], spacing))
+                    if post_maps is not None:
+                        cleaned, stats = ops.label_clean(post_maps[n], post, post_conn)
+                        pc = ops.label_tallies(cleaned, lab[n], post_lut, int(stitched.shape[1])).cpu()
+                        res["post"] = dict(metrics_from_counts(pc), counts=pc,
+                                           changed=[int(v) for v in stats.cpu()[:, 1]])
                 if fp_model is not None:
                     res["vs_fp"] = _vs_fp(ops, stitched[n], stitched_fp[n], kind, fz, vol.shape[-3:], spacing, lesions,
                                           surface, pool is not None)
@@ -535,6 +577,29 @@ def write_metrics_csv(path: str, results) -> None:
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
                             [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []) +
                             (["%.7g" % float(v) for v in r["surface"][c]] if sd else []))
+
+
+def write_metrics_post_csv(path: str, results) -> None:
+    """One row per subject and class from the "post" entries (validate_seg(..., post=...)): subject, class, dsc, sens,
+    spec, acc, tp, fp, fn, tn of the cleaned map, then changed_<k>, the voxels rule k relabelled in the subject's map
+    (the same in every row of a subject)."""
+    import csv
+    rows = [r for r in results if "post" in r]
+    nrules = max((len(r["post"]["changed"]) for r in rows), default=0)
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(("subject", "class") + METRICS + ("tp", "fp", "fn", "tn") +
+                    tuple(f"changed_{k}" for k in range(nrules)))
+        for r in rows:
+            q = r["post"]
+            for c in range(q["counts"].shape[0]):
+                wr.writerow([r["name"], c] + ["%.7g" % float(q[m][c]) for m in METRICS] +
+                            [int(v) for v in q["counts"][c]] + [int(v) for v in q["changed"]])
+
+
+def post_means(results) -> dict:
+    """Per-class mean of dsc / sens / spec / acc over the "post" entries."""
+    return {m: torch.stack([r["post"][m] for r in results if "post" in r]).mean(0) for m in METRICS}
 
 
 AGREEMENT_COUNTS = ("both", "q_only", "fp_only", "neither")          # the columns of "vs_fp"'s counts

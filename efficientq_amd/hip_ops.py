@@ -1430,6 +1430,90 @@ class HipOps:
         counts, nrows, rows = self._table_call("seg_lesion_table", 2 * Cc, 4 * Cc, 3, max_rows, call)
         return counts.view(Cc, 4), nrows, rows
 
+    def label_clean(self, label_map: torch.Tensor, rules, connectivity: int = 26, out: Optional[torch.Tensor] = None):
+        """A predicted label map cleaned by connected components (effq_label_clean, --post): `label_map` D x H x W uint8;
+        `rules` a list of at most _lib.LABEL_CLEAN_MAX_RULES (labels, op, n, to) - config.PostRule - applied in order,
+        each to the map the previous one left: op 'largest' keeps the largest component of the voxels whose value is one
+        of `labels` (of equal sizes the one whose first voxel comes first) and gives every other component the value
+        `to`; op 'min' gives `to` to every component of fewer than `n` voxels.  connectivity 26 or 6.  Returns (map,
+        stats): the cleaned map (a new tensor, or `out`, which may be `label_map` itself) and R x 2 int64 on the device:
+        per rule the components its mask had and the voxels it relabelled."""
+        m, P, D, H, W = self._mask_planes("label_clean", label_map)
+        if m.dim() != 3:
+            raise _lib.EffqError(f"label_clean: map {tuple(m.shape)}, needs D x H x W")
+        if connectivity not in (6, 26):
+            raise _lib.EffqError(f"label_clean: connectivity {connectivity}, 6 or 26")
+        if m.numel() >= 2 ** 31:
+            raise _lib.EffqError(f"label_clean: a map of {m.numel()} voxels (2^31 - 1 at most)")
+        rules = list(rules)
+        R = len(rules)
+        if not 1 <= R <= _lib.LABEL_CLEAN_MAX_RULES:
+            raise _lib.EffqError(f"label_clean: {R} rules, 1 to {_lib.LABEL_CLEAN_MAX_RULES}")
+        sets = (C.c_uint8 * (256 * R))()
+        words = (C.c_longlong * (3 * R))()
+        for r, rule in enumerate(rules):
+            try:
+                labels, op, n, to = rule
+                labels, n, to = [int(v) for v in labels], int(n), int(to)
+            except (TypeError, ValueError) as e:
+                raise _lib.EffqError(f"label_clean: rule {r}: {rule!r} is no (labels, op, n, to): {e}") from e
+            if op not in _lib.LABEL_CLEAN_OPS:
+                raise _lib.EffqError(f"label_clean: rule {r}: unknown op {op!r} (one of {', '.join(_lib.LABEL_CLEAN_OPS)})")
+            if not labels or min(labels) < 1 or max(labels) > 255:
+                raise _lib.EffqError(f"label_clean: rule {r}: labels {labels}, needs values of 1 to 255")
+            if not 0 <= to <= 255 or to in labels:
+                raise _lib.EffqError(f"label_clean: rule {r}: the new label {to} is outside 0..255 or one of {labels}")
+            if op == "min" and n < 1:
+                raise _lib.EffqError(f"label_clean: rule {r}: min {n}, needs 1 or more voxels")
+            for v in labels:
+                sets[256 * r + v] = 1
+            words[3 * r], words[3 * r + 1], words[3 * r + 2] = _lib.LABEL_CLEAN_OPS[op], n, to
+        if out is None:
+            out = torch.empty_like(m)
+        elif out.shape != m.shape or out.dtype != torch.uint8 or out.device != m.device or not out.is_contiguous():
+            raise _lib.EffqError(f"label_clean: out {tuple(out.shape)} {out.dtype} on {out.device}, needs a contiguous "
+                                 f"{tuple(m.shape)} torch.uint8 on {m.device}")
+        elif out is label_map and m is not label_map:
+            raise _lib.EffqError("label_clean: a map cleaned in place must be contiguous")
+        stats = torch.empty(R, 2, dtype=torch.int64, device=self.device)
+        ws = self._workspace("label_clean", self.lib.effq_label_clean_ws_bytes(D, H, W))
+        check(self.lib.effq_label_clean(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
+                                        _ptr(ws), ws.numel(), self.stream), "effq_label_clean")
+        return out, stats
+
+    def label_tallies(self, pred: torch.Tensor, truth: torch.Tensor, lut, C_: int):
+        """TP, FP, FN, TN per class (C x 4 int64, seg_tallies' layout) of a uint8 label map against the truth
+        (effq_label_tallies).  `lut`: 256 integers, bit c set = that label value belongs to class c; `truth`: a label map
+        of `pred`'s shape, read through `lut`, or C 0/1 planes (C x pred's shape)."""
+        Cc = int(C_)
+        if pred.dtype != torch.uint8 or truth.dtype != torch.uint8 or pred.numel() == 0:
+            raise _lib.EffqError(f"label_tallies: pred {tuple(pred.shape)} {pred.dtype}, truth {tuple(truth.shape)} "
+                                 f"{truth.dtype}: needs torch.uint8, not empty")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"label_tallies: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if tuple(truth.shape) == tuple(pred.shape):
+            planes = 0
+        elif tuple(truth.shape) == (Cc,) + tuple(pred.shape):
+            planes = 1
+        else:
+            raise _lib.EffqError(f"label_tallies: truth {tuple(truth.shape)} for a map {tuple(pred.shape)}: needs the "
+                                 f"map's shape, or {Cc} planes of it")
+        for t, who in ((pred, "pred"), (truth, "truth")):
+            if t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index)):
+                raise _lib.EffqError(f"label_tallies: {who} on {t.device}, ops on {self.device}")
+        try:
+            table = [int(v) for v in lut]
+        except (TypeError, ValueError) as e:
+            raise _lib.EffqError(f"label_tallies: lut: {e}") from e
+        if len(table) != 256 or min(table) < 0 or max(table) >= 1 << Cc:
+            raise _lib.EffqError(f"label_tallies: lut of {len(table)} entries, needs 256 of {Cc} class bits each")
+        p, t = pred.contiguous(), truth.contiguous()
+        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
+        ws = self._workspace("label_tallies", self.lib.effq_label_tallies_ws_bytes())
+        check(self.lib.effq_label_tallies(_ptr(p), _ptr(t), planes, Cc, p.numel(), (C.c_uint16 * 256)(*table),
+                                          _ptr(counts), _ptr(ws), ws.numel(), self.stream), "effq_label_tallies")
+        return counts
+
     def edt_sq(self, mask: torch.Tensor):
         """Exact squared Euclidean distance transform (effq_edt_sq): `mask` D x H x W or P x D x H x W uint8, non-zero =
         site.  Returns an int32 tensor of the mask's shape: the squared distance (voxel units) of every voxel to the

@@ -24,7 +24,13 @@ grid, the box, the number of windows, the prep options used, and per label value
 averages the logits: 2, 4 or 8 forwards per window.  When either is given ``predict.csv`` gains the columns ``blend`` and
 ``tta_mirror`` after the others; otherwise the file is what it was.
 
-Everything the list and the headers decide, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
+``--post RULE`` (repeatable; config.post_rules, ``--post_conn 6|26``) cleans the map by connected components on the
+scan's own grid before it is counted, copied and written (effq_label_clean): ``--post 1,2:largest`` keeps the largest
+component of the labels 1 and 2, ``--post '4:min500>1'`` relabels every component of label 4 with fewer than 500 voxels to
+1.  ``predict.csv`` then gains the columns ``post`` (the rules) and ``post_changed`` (the voxels each rule relabelled)
+after all others, and ``labels``, ``voxels`` and ``volume_ml`` are the cleaned map's; without ``--post`` nothing changes.
+
+Everything the list and the headers decide, a ``--post`` rule that is not understood, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
 and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
 """
 from __future__ import annotations
@@ -89,6 +95,7 @@ def _network(args, dev):
 
 
 CSV_BLEND_COLUMNS = ["blend", "tta_mirror"]       # after CSV_HEADER, only when --blend / --tta_mirror is given
+CSV_POST_COLUMNS = ["post", "post_changed"]       # after those, only when --post is given
 
 
 def _write_csv(path: str, rows: List[dict], header=CSV_HEADER) -> None:
@@ -154,6 +161,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     from . import config as Cf
     blend, flips = Cf.blend_switches(args)
     sliding = (blend, flips) != ("uniform", (0,))
+    post, post_conn = Cf.post_rules(args)
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
@@ -172,6 +180,9 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             "patch_size": prep._fmt(patch)}
     if sliding:
         used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
+    post_said = Cf.post_text(post, post_conn) if post else None
+    if post:
+        used.update(post=post_said)
     rows, writes = [], []
     bsz = window_batch
     reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-read")
@@ -189,6 +200,11 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             vol = torch.from_numpy(y)[None].to(ops.device)
             outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz, blend, flips)
             labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.source_shape, rule, fuse)
+            cleaned = ""
+            if post:        # on the source grid, in place: the counts, the copy and the file are the cleaned map's
+                labels, stats = ops.label_clean(labels, post, post_conn, out=labels)
+                changed = prep._fmt(int(v) for v in stats.cpu()[:, 1])
+                cleaned = f", post {post_said}: {changed} voxels relabelled"
             counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
             host = labels.cpu().numpy()
             while len(writes) >= MAX_PENDING_WRITES:       # gzip slower than the device: wait, do not pile maps up
@@ -202,16 +218,19 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                    "labels": prep._fmt(present), "voxels": prep._fmt(counts[v] for v in present),
                    "volume_ml": " ".join(f"{counts[v] * ml:.7g}" for v in present)}
             row.update(used)
+            if post:
+                row["post_changed"] = changed
             rows.append(row)
             print(f"[predict] {sn}: {prep._fmt(plan.source_shape)} -> grid {prep._fmt(plan.grid_shape)}, box at "
                   f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
                   f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
-                  f"{row['voxels']} voxels")
+                  f"{row['voxels']} voxels{cleaned}")
     finally:
         reader.shutdown(wait=True, cancel_futures=True)
         writer.shutdown(wait=True)
     for w in writes:
         w.result()                              # re-raises a failed write
-    _write_csv(P.join(out_dir, PREDICT_CSV), rows, CSV_HEADER + CSV_BLEND_COLUMNS if sliding else CSV_HEADER)
+    _write_csv(P.join(out_dir, PREDICT_CSV), rows,
+               CSV_HEADER + (CSV_BLEND_COLUMNS if sliding else []) + (CSV_POST_COLUMNS if post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

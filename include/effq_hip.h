@@ -714,6 +714,48 @@ int effq_seg_lesion_table(const float* logits, const uint8_t* label, int C, int 
                           float thresh, int connectivity, int max_rows, long long* counts, long long* nrows,
                           int32_t* rows, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cleaning a predicted label map by connected components (--post: keep the largest liver, relabel small specks; the
+ * reference's merge_label_brats_inference, utils/misc.py, is the need, not the specification).  in (D, H, W) uint8 label
+ * values -> out (D, H, W), which may be `in` itself.  R rules, 1 <= R <= EFFQ_LABEL_CLEAN_MAX_RULES, apply in order, each
+ * to the map the previous one left.  Rule r: sets (R, 256) uint8 on the host, non-zero = the value is in the rule's mask
+ * (sets[r][0] must be 0); rules (R, 3) long long on the host = op, N, TO.  Both host arrays are read before the call
+ * returns.
+ *   EFFQ_LABEL_CLEAN_LARGEST: the largest component of the mask stays, the voxels of every other become TO (N ignored).
+ *     Of several largest components of equal size the one whose first voxel (least linear index d*H*W + h*W + w) is
+ *     least stays.
+ *   EFFQ_LABEL_CLEAN_MIN: the voxels of every component with fewer than N voxels become TO (N >= 1; size == N stays).
+ *   TO is 0..255 and not in the rule's own set.  A rule whose mask is empty changes nothing.
+ * stats (R, 2) int64 on the device: the components the rule's mask had, the voxels the rule relabelled.
+ * Per rule: the membership plane (one launch), the five labelling launches of effq_cc_label on it, the component sizes
+ *   added at the roots (equal roots of a wave combined before the atomic; int32, a plane holds < 2^31 voxels), for
+ *   LARGEST one 64-bit atomicMax over the roots of size << 32 | (0xFFFFFFFF - root), and one pass that rewrites and
+ *   counts: 8 launches for MIN, 9 for LARGEST, after one launch that zeroes the counters (and a device copy when out is
+ *   not in).  All on `stream`, no read by the host and no workgroup that waits for another.  Integer adds and a max only,
+ *   so equal inputs give equal bits, whatever the scheduling.
+ * ws: effq_label_clean_ws_bytes(D, H, W) bytes: 4 B of label, 4 B of size and 1 B of mask per voxel, and 4.2 KB of
+ *   counters - 80 MB for 155 x 240 x 240; 0 for dimensions out of range.  Limits: effq_cc_label's with P = 1.  Bad
+ *   arguments (a null pointer, R out of range, an unknown op, N < 1, TO out of range or in its own set, sets[r][0] set, a
+ *   connectivity other than 6 or 26, dimensions out of range) return EFFQ_ERR_ARG, a short workspace
+ *   EFFQ_ERR_WORKSPACE; both launch nothing and leave out and stats as they were. */
+#define EFFQ_LABEL_CLEAN_MAX_RULES 8
+#define EFFQ_LABEL_CLEAN_LARGEST 0
+#define EFFQ_LABEL_CLEAN_MIN 1
+size_t effq_label_clean_ws_bytes(int D, int H, int W);
+int effq_label_clean(const uint8_t* in, int D, int H, int W, int connectivity, int R, const uint8_t* sets,
+                     const long long* rules, uint8_t* out, long long* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* Tallies of a label map (the score of a cleaned map): pred (S) uint8 label values against the truth -> counts (C, 4)
+ * int64 = TP, FP, FN, TN per class, the layout of effq_seg_tallies.  lut: 256 uint16 on the host, read before the call
+ * returns; bit c set = that label value belongs to class c.  The class bits of a predicted voxel are lut[pred[v]]; those
+ * of the truth are lut[truth[v]] when truth_planes == 0 (truth (S) label values), and otherwise bit c is
+ * truth[c * S + v] != 0 (truth (C, S) 0/1 planes).  1 <= C <= EFFQ_SEG_TALLIES_MAX_CLASSES, S < 2^40.  Per-workgroup
+ * integer partials, added in block order by a second launch: equal inputs give equal bits.  4-B loads when pred and
+ * truth are 4-B aligned (and S % 4 == 0 for planes), the last S % 4 voxels one by one.  ws:
+ * effq_label_tallies_ws_bytes() of scratch; a shorter one returns EFFQ_ERR_WORKSPACE. */
+size_t effq_label_tallies_ws_bytes(void);
+int effq_label_tallies(const uint8_t* pred, const uint8_t* truth, int truth_planes, int C, long long S,
+                       const uint16_t* lut, long long* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- exact Euclidean distance transform of 3-D masks and the surface-distance columns of the validation
  * (validate_seg(..., surface=True): hd, hd95, assd per class; the reference has no counterpart, the definitions are
  * DESIGN section 13's).  Voxel units.  Separable and in integers throughout, so the squared distances are exact: along
