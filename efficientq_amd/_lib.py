@@ -215,6 +215,8 @@ SIGNATURES = {
     "effq_prep_standardise_crop": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "effq_prep_crop_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "effq_prep_union_mask": (_I, [_P, _I, _LL, _I, _P, _P]),
+    "effq_prep_reorient": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
+    "effq_prep_reorient_plan": (_I, [_P, _I, _I, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges

@@ -96,6 +96,9 @@ def build_parser():
     p.add_argument('--prep_mask', default=None, choices=['nonzero', 'all'],
                    help='prep: the voxels a modality is standardised over (brats: nonzero, lits: all)')
     p.add_argument('--prep_window', default=None, help='prep: lo,hi to clip to first, or none (lits: -200,250)')
+    p.add_argument('--prep_orient', default=None,
+                   help='prep, predict: three letters, one each of R/L, A/P, S/I (RAS, LPS, SAR, ...): the anatomical '
+                        'direction array axis 0, 1, 2 of the working arrays runs towards; every scan is reoriented to it')
     p.add_argument('--prep_spacing', default=None, help='prep: d,h,w in mm to resample every subject to')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')

@@ -1714,6 +1714,46 @@ class HipOps:
         check(self.lib.effq_prep_union_mask(_ptr(x), Cc, D * H * W, mode, _ptr(m), self.stream), "effq_prep_union_mask")
         return m
 
+    @staticmethod
+    def _orient_plan(what: str, src_axis, flip):
+        """(ctypes int[3], flip mask) of a plan: `flip` is three truth values, one per output axis."""
+        try:
+            axes, fl = tuple(int(a) for a in src_axis), tuple(bool(f) for f in flip)
+        except (TypeError, ValueError):
+            axes, fl = (), ()
+        if sorted(axes) != [0, 1, 2] or len(fl) != 3:
+            raise _lib.EffqError(f"{what}: src_axis {src_axis!r} must be a permutation of 0, 1, 2 and flip {flip!r} three "
+                                 f"truth values")
+        return axes, (C.c_int * 3)(*axes), sum(1 << p for p in range(3) if fl[p])
+
+    def prep_reorient_variant(self, src_axis, flip, elem_bytes: int) -> int:
+        """The kernel effq_prep_reorient would launch for this plan (effq_prep_reorient_plan): 0 rows, 1 tiled transpose."""
+        _, cax, mask = self._orient_plan("prep_reorient_variant", src_axis, flip)
+        v = C.c_int(-1)
+        check(self.lib.effq_prep_reorient_plan(cax, mask, int(elem_bytes), C.byref(v)), "effq_prep_reorient_plan")
+        return int(v.value)
+
+    def prep_reorient(self, x: torch.Tensor, src_axis, flip) -> torch.Tensor:
+        """N x D x H x W (or D x H x W) float32 or uint8 volumes with their axes permuted and reversed
+        (effq_prep_reorient): output axis p is source axis src_axis[p], reversed iff flip[p]; a new tensor, bit for bit
+        numpy.flip(numpy.transpose(x)).  The tensor must be contiguous in its own storage; a uint8 one may start at any
+        byte of a larger buffer."""
+        if x.dim() not in (3, 4) or x.dtype not in (torch.float32, torch.uint8) or x.numel() == 0 or \
+                not x.is_contiguous() or self._elsewhere(x):
+            raise _lib.EffqError(f"prep_reorient: needs a contiguous [N x] D x H x W float32 or uint8 tensor on "
+                                 f"{self.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+        axes, cax, mask = self._orient_plan("prep_reorient", src_axis, flip)
+        dims = tuple(int(n) for n in x.shape[-3:])
+        N = int(x.shape[0]) if x.dim() == 4 else 1
+        if x.numel() >= 2 ** 31 or max(dims) > 32767:
+            raise _lib.EffqError(f"prep_reorient: shape {tuple(x.shape)}: 2^31 - 1 voxels in all and 32767 along an axis "
+                                 f"at most")
+        out = tuple(dims[a] for a in axes)
+        y = torch.empty(((N,) if x.dim() == 4 else ()) + out, dtype=x.dtype, device=x.device)
+        check(self.lib.effq_prep_reorient(_ptr(x), N, dims[0], dims[1], dims[2], cax, mask, x.element_size(), _ptr(y),
+                                          self.stream), "effq_prep_reorient")
+        return y
+
 
 _OPS = {}
 

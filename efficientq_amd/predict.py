@@ -3,7 +3,7 @@
     python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/ \
         [--prep_window -200,250 --prep_spacing 1,1,2.5 --prep_mask all --prep_min_size d,h,w --patch_size d,h,w]
-        [--blend gauss --tta_mirror hw]
+        [--prep_orient RAS] [--blend gauss --tta_mirror hw]
 
 ``--src_list`` is the CSV of the ``prep`` mission (prep.read_src_list; a ``seg`` column is allowed and ignored).  The
 ``--prep_*`` switches and ``--patch_size`` mean what they mean in ``prep`` and ``ptq`` and have the same per-task
@@ -18,6 +18,12 @@ label per voxel of the scan's own grid: ``<out_dir>/<subject>.nii.gz``, uint8, w
 written by a background thread.  ``<out_dir>/predict.csv`` gets one row per subject: the source shape and spacing, the
 grid, the box, the number of windows, the prep options used, and per label value present in the map its voxel count
 (counted on the device) and its volume in ml.
+
+``--prep_orient CODE`` reorients the working arrays as ``prep`` does (it must be what the calibration data was prepared
+with): effq_seg_labels_source then writes the map on the oriented source grid, and one effq_prep_reorient of that uint8
+map with the inverse plan puts it on the scan's own grid before ``--post``, the counts, the copy and the write, so the file
+still has the scan's header and overlays it.  ``predict.csv`` then gains the columns ``source_orient`` (the scan's own
+code) and ``orient`` after those of the list above and before the blend and post columns.
 
 ``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched;
 ``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
@@ -158,6 +164,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         raise PrepError(f"--prep_min_size {tuple(min_size)} is smaller than --patch_size {tuple(patch)}: the sliding "
                         f"window needs one whole patch")
     no_crop = bool(getattr(args, "prep_no_crop", False))
+    orient = prep.parse_orient(getattr(args, "prep_orient", None))
     from . import config as Cf
     blend, flips = Cf.blend_switches(args)
     sliding = (blend, flips) != ("uniform", (0,))
@@ -165,7 +172,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
-    plans = [prep._Plan(e, mods, spacing, min_size) for e in entries]
+    plans = [prep._Plan(e, mods, spacing, min_size, orient) for e in entries]
     if ops is None:
         from .hip_ops import get_ops
         ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
@@ -178,6 +185,8 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     used = {"prep_mask": mask, "prep_window": prep._fmt(window) if window else "none",
             "prep_spacing": prep._fmt(spacing) if spacing else "none", "prep_min_size": prep._fmt(min_size),
             "patch_size": prep._fmt(patch)}
+    if orient:
+        used.update(orient=orient)
     if sliding:
         used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
     post_said = Cf.post_text(post, post_conn) if post else None
@@ -199,7 +208,10 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                                                                 no_crop)
             vol = torch.from_numpy(y)[None].to(ops.device)
             outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz, blend, flips)
-            labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.source_shape, rule, fuse)
+            labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.oriented_shape, rule,
+                                           fuse)
+            if plan.orient is not None and not prep.orient_is_identity(*plan.orient):
+                labels = ops.prep_reorient(labels, *prep.orient_inverse(*plan.orient))     # back on the scan's own grid
             cleaned = ""
             if post:        # on the source grid, in place: the counts, the copy and the file are the cleaned map's
                 labels, stats = ops.label_clean(labels, post, post_conn, out=labels)
@@ -218,10 +230,13 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                    "labels": prep._fmt(present), "voxels": prep._fmt(counts[v] for v in present),
                    "volume_ml": " ".join(f"{counts[v] * ml:.7g}" for v in present)}
             row.update(used)
+            if orient:
+                row["source_orient"] = plan.orient_code
             if post:
                 row["post_changed"] = changed
             rows.append(row)
-            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)} -> grid {prep._fmt(plan.grid_shape)}, box at "
+            turned = f" ({plan.orient_code} -> {orient})" if orient and plan.orient_code != orient else ""
+            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned} -> grid {prep._fmt(plan.grid_shape)}, box at "
                   f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
                   f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
                   f"{row['voxels']} voxels{cleaned}")
@@ -231,6 +246,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     for w in writes:
         w.result()                              # re-raises a failed write
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
-               CSV_HEADER + (CSV_BLEND_COLUMNS if sliding else []) + (CSV_POST_COLUMNS if post else []))
+               CSV_HEADER + (prep.ORIENT_COLUMNS if orient else []) + (CSV_BLEND_COLUMNS if sliding else []) +
+               (CSV_POST_COLUMNS if post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

@@ -2,12 +2,15 @@
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
         [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|none] \
-        [--prep_spacing d,h,w] [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
+        [--prep_orient RAS] [--prep_spacing d,h,w] [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
 ``--src_list`` is a CSV with the header ``subject,<modality>,...[,seg]`` (the task's modalities, data.MODALITIES, in any
 order) and one row per subject with one NIfTI path per column, relative to the CSV unless absolute; an empty ``seg``
 cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
 
+    reorient   --prep_orient CODE: the axes permuted and reversed (csrc/reorient.hip) so that array axis 0, 1, 2 runs
+               towards the three letters of CODE (one each of R/L, A/P, S/I: RAS, LPS, SAR, ...), whatever orientation
+               the scan's affine gives it; --prep_spacing and --prep_min_size then refer to the oriented axes
     window     --prep_window lo,hi: clip in place (lits: -200,250 unless ``none``; brats: none)
     resample   --prep_spacing d,h,w: trilinear for the images, nearest for the label, no filter before down-sampling
     pass 1     the box of the union of the modalities' masks, per modality the count and the sum over its own mask
@@ -19,7 +22,9 @@ and the files ``data_dir/<modality>/<subject>.npy`` (float32), ``data_dir/seg/<s
 ``data_dir/sn_fn.txt``, ``data_dir/restore_shape_infokw.pickle`` and ``data_dir/prep.csv``, merged with what an earlier
 run into the same ``data_dir`` left.  Without ``--prep_spacing`` sn_fn.txt names the first modality's own source image,
 so ``ptq --src_geom --save_nii`` writes maps that overlay the scan; with it the arrays live on a new grid, which
-``data_dir/grid/<subject>.nii.gz`` (the union mask, uint8, with the grid's affine) records and sn_fn.txt names.
+``data_dir/grid/<subject>.nii.gz`` (the union mask, uint8, with the grid's affine) records and sn_fn.txt names.  With
+``--prep_orient`` the arrays do not share the scan's axes either: the grid image is written then too (for every subject,
+also one that was oriented as asked already), and prep.csv gains the columns ``source_orient`` and ``orient``.
 ``--split_dir --val_every K`` also writes ``split_dir/round<R>/{train,val}.txt``.
 
 What the headers decide (the list itself, shapes and affines within a subject, a grid smaller than --prep_min_size, a
@@ -116,6 +121,97 @@ def parse_window(s, task: str) -> Optional[Tuple[float, float]]:
     return lo, hi
 
 
+# ---- orientation (host, no device) ---------------------------------------------------------------------------------------
+# NIfTI world axes: +x = R, +y = A, +z = S.  A code names, per array axis 0, 1, 2 (D, H, W = NIfTI i, j, k), the
+# anatomical direction the axis runs towards.
+ORIENT_LETTERS = {"R": (0, 1), "L": (0, -1), "A": (1, 1), "P": (1, -1), "S": (2, 1), "I": (2, -1)}
+_LETTER_OF = {v: k for k, v in ORIENT_LETTERS.items()}
+
+
+def parse_orient(code) -> Optional[str]:
+    """The code of --prep_orient in capitals, or None when the switch is absent; a code that is not understood is
+    refused by name."""
+    if code is None:
+        return None
+    text = str(code).strip().upper()
+    why = None
+    if len(text) != 3:
+        why = f"{len(text)} letters"
+    elif any(c not in ORIENT_LETTERS for c in text):
+        why = f"the letter {next(c for c in text if c not in ORIENT_LETTERS)!r} is none of R, L, A, P, S, I"
+    elif len({ORIENT_LETTERS[c][0] for c in text}) != 3:
+        why = "two letters of one pair"
+    if why:
+        raise PrepError(f"--prep_orient {code!r}: {why}: needs three letters, one each of R/L, A/P and S/I, in any order "
+                        f"(RAS, LPS, SAR, ...)")
+    return text
+
+
+def orient_code(world_axis: Sequence[int], sign: Sequence[int]) -> str:
+    """The three letters of an orientation: array axis a runs along world axis world_axis[a] in the direction sign[a]."""
+    return "".join(_LETTER_OF[(int(w), 1 if s > 0 else -1)] for w, s in zip(world_axis, sign))
+
+
+def scan_orientation(affine) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """(world_axis, sign) of a voxel-to-world affine: array axis a runs nearest to world axis world_axis[a] (0 = x, R; 1 =
+    y, A; 2 = z, S), towards + (sign 1) or - (sign -1); orient_code(...) spells it.  The columns of the 3 x 3 part are
+    normalised to unit length; the row of the largest absolute component decides.  Refused (PrepError with the cause;
+    the caller names the subject): a column of zero or non-finite length, a column whose largest component does not
+    strictly exceed its second largest (a 45 degree oblique), two array axes nearest to the same world axis."""
+    m = np.asarray(affine, dtype=np.float64)[:3, :3]
+    world, sign = [], []
+    for a in range(3):
+        col = m[:, a]
+        length = float(np.sqrt((col * col).sum()))
+        if not math.isfinite(length) or length <= 0.0:
+            raise PrepError(f"the affine's column {a} has length {length}: array axis {a} has no direction")
+        c = np.abs(col / length)
+        order = np.argsort(-c, kind="stable")
+        if not c[order[0]] > c[order[1]]:
+            raise PrepError(f"the affine's column {a} lies at 45 degrees between two world axes (components "
+                            f"{_fmt(float(v) for v in col / length)}): no nearest anatomical axis")
+        world.append(int(order[0]))
+        sign.append(1 if col[order[0]] > 0 else -1)
+    if sorted(world) != [0, 1, 2]:
+        raise PrepError(f"the affine maps two array axes nearest to the same world axis (axes 0, 1, 2 -> world "
+                        f"{tuple(world)}): it is sheared too far to name an orientation")
+    return tuple(world), tuple(sign)
+
+
+def orient_plan(world_axis: Sequence[int], sign: Sequence[int], code: str, shape: Sequence[int]):
+    """(src_axis, flip, out_shape) that turn a scan of orientation (world_axis, sign) and `shape` into `code`: output
+    axis p is source axis src_axis[p], reversed iff flip[p]:  y[n0, n1, n2] = x[s] with
+    s[src_axis[p]] = shape[src_axis[p]] - 1 - n_p if flip[p] else n_p."""
+    src, flip = [], []
+    for letter in parse_orient(code):
+        w, s = ORIENT_LETTERS[letter]
+        a = list(world_axis).index(w)
+        src.append(a)
+        flip.append(int(sign[a]) != s)
+    return tuple(src), tuple(flip), tuple(int(shape[a]) for a in src)
+
+
+def orient_inverse(src_axis: Sequence[int], flip: Sequence[bool]):
+    """(inv_src_axis, inv_flip): the plan that, applied to the output of (src_axis, flip), gives the input back."""
+    inv = [list(src_axis).index(a) for a in range(3)]
+    return tuple(inv), tuple(bool(flip[p]) for p in inv)
+
+
+def orient_is_identity(src_axis: Sequence[int], flip: Sequence[bool]) -> bool:
+    return tuple(src_axis) == (0, 1, 2) and not any(flip)
+
+
+def orient_affine(affine, src_axis: Sequence[int], flip: Sequence[bool], shape: Sequence[int]) -> np.ndarray:
+    """A T with T the 4 x 4 integer matrix of the plan's index map (output index -> source index, `shape` the source's):
+    every voxel keeps its world position."""
+    t = np.zeros((4, 4))
+    t[3, 3] = 1.0
+    for p, (a, f) in enumerate(zip(src_axis, flip)):
+        t[a, p] = -1.0 if f else 1.0
+        t[a, 3] = float(int(shape[a]) - 1) if f else 0.0
+    return np.asarray(affine, dtype=np.float64) @ t
+
+
 # ---- the source list ---------------------------------------------------------------------------------------------------
 def read_src_list(path: str, task: str) -> List[dict]:
     """The rows of --src_list, sorted by subject: {subject, images: {modality: path}, seg: path or None}.  Everything the
@@ -184,7 +280,7 @@ def check_same_grid(subject: str, first: dict, other: dict, name: str) -> None:
 class _Plan:
     """What the headers of one subject decide."""
 
-    def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size):
+    def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size, orient: Optional[str] = None):
         sn = self.subject = entry["subject"]
         self.entry = entry
         heads = {}
@@ -207,16 +303,31 @@ class _Plan:
         self.source_spacing = tuple(first["spacing"])
         self.affine = first["affine"]
         self.header = first             # nifti.read_geometry of the first modality: write_nifti(..., geometry=header)
+        # --prep_orient: the scan's own code and the plan (src_axis, flip) that turns it into the target's; without the
+        # switch the affine is not looked at (orient_code None) and the oriented values are the scan's own
+        self.orient_code, self.orient = None, None
+        self.oriented_shape, self.oriented_spacing, self.oriented_affine = self.source_shape, self.source_spacing, \
+            self.affine
+        if orient is not None:
+            try:
+                world, sign = scan_orientation(self.affine)
+            except PrepError as e:
+                raise PrepError(f"subject {sn}: --prep_orient {orient}: {e}") from e
+            self.orient_code = orient_code(world, sign)
+            src, flip, self.oriented_shape = orient_plan(world, sign, orient, self.source_shape)
+            self.orient = (src, flip)
+            self.oriented_spacing = tuple(self.source_spacing[a] for a in src)
+            self.oriented_affine = orient_affine(self.affine, src, flip, self.source_shape)
         if spacing is None:
-            self.factors, self.grid_shape, self.grid_spacing, self.grid_affine = None, self.source_shape, \
-                self.source_spacing, self.affine
+            self.factors, self.grid_shape, self.grid_spacing, self.grid_affine = None, self.oriented_shape, \
+                self.oriented_spacing, self.oriented_affine
         else:
-            if min(self.source_spacing) <= 0:
+            if min(self.oriented_spacing) <= 0:
                 raise PrepError(f"subject {sn}: source spacing {self.source_spacing} cannot be resampled")
-            self.factors = tuple(t / s for t, s in zip(spacing, self.source_spacing))
-            self.grid_shape = tuple(resample_extent(n, f) for n, f in zip(self.source_shape, self.factors))
+            self.factors = tuple(t / s for t, s in zip(spacing, self.oriented_spacing))
+            self.grid_shape = tuple(resample_extent(n, f) for n, f in zip(self.oriented_shape, self.factors))
             self.grid_spacing = tuple(spacing)
-            self.grid_affine = resample_affine(self.affine, self.factors)
+            self.grid_affine = resample_affine(self.oriented_affine, self.factors)
         if any(g < m for g, m in zip(self.grid_shape, min_size)):
             raise PrepError(f"subject {sn}: grid of {self.grid_shape} is smaller than --prep_min_size "
                             f"{tuple(min_size)}: the validation's sliding window needs one whole patch")
@@ -312,6 +423,9 @@ def prep_csv_header(mods: Sequence[str]) -> List[str]:
         [f"{m}_{k}" for m in mods for k in ("count", "mean", "std")]
 
 
+ORIENT_COLUMNS = ["source_orient", "orient"]      # prep.csv and predict.csv, only with --prep_orient
+
+
 def _fmt(v) -> str:
     return " ".join(f"{x:.7g}" if isinstance(x, float) else str(int(x)) for x in v)
 
@@ -331,6 +445,10 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
     dev = ops.device
     x = torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
     lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
+    if plan.orient is not None and not orient_is_identity(*plan.orient):
+        x = ops.prep_reorient(x, *plan.orient)
+        if lab is not None:
+            lab = ops.prep_reorient(lab, *plan.orient)
     if window is not None:
         ops.prep_window(x, window[0], window[1])
     if plan.factors is not None:
@@ -357,7 +475,8 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
         pmin, pmax = widen_box(bbox[:3], [b + 1 for b in bbox[3:]], plan.grid_shape, min_size)
     y = ops.prep_standardise_crop(x, pmin, pmax, mean, std, mask)
     lab_out = ops.prep_crop_u8(lab, pmin, pmax)[0].cpu().numpy() if lab is not None else None
-    union = ops.prep_union_mask(x, mask).cpu().numpy() if plan.factors is not None else None
+    on_new_grid = plan.factors is not None or plan.orient is not None        # the arrays left the scan's own axes
+    union = ops.prep_union_mask(x, mask).cpu().numpy() if on_new_grid else None
     return y.cpu().numpy(), lab_out, union, pmin, pmax, count, mean, std
 
 
@@ -380,6 +499,7 @@ def run(args, ops=None) -> List[dict]:
     min_size = _triple(args.prep_min_size, "--prep_min_size", int) if getattr(args, "prep_min_size", None) \
         else D.PATCH_DEFAULT[task]
     no_crop = bool(getattr(args, "prep_no_crop", False))
+    orient = parse_orient(getattr(args, "prep_orient", None))
     access = getattr(args, "access_type", None) or "npy"
     if access not in D.ACCESS_TYPES:
         raise PrepError(f"--access_type {access!r}: one of {', '.join(D.ACCESS_TYPES)}")
@@ -387,7 +507,7 @@ def run(args, ops=None) -> List[dict]:
 
     # everything the list and the headers decide, before anything is written
     entries = read_src_list(args.src_list, task)
-    plans = [_Plan(e, mods, spacing, min_size) for e in entries]
+    plans = [_Plan(e, mods, spacing, min_size, orient) for e in entries]
     split = None
     if getattr(args, "split_dir", None):
         k = getattr(args, "val_every", None)
@@ -434,11 +554,15 @@ def run(args, ops=None) -> List[dict]:
             for c, m in enumerate(mods):
                 row.update({f"{m}_count": str(int(count[c])), f"{m}_mean": repr(float(mean[c])),
                             f"{m}_std": repr(float(std[c]))})
+            turned = ""
+            if orient is not None:
+                row.update(source_orient=plan.orient_code, orient=orient)
+                turned = f" ({plan.orient_code} -> {orient})" if plan.orient_code != orient else ""
             rows.append(row)
-            print(f"[prep] {sn}: {_fmt(plan.source_shape)} -> {_fmt(y.shape[1:])} at {_fmt(pmin)}")
+            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned} -> {_fmt(y.shape[1:])} at {_fmt(pmin)}")
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
-    write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods))
+    write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods) + (ORIENT_COLUMNS if orient else []))
     if split is not None:
         names = [p.subject for p in plans]
         val = names[k - 1::k]

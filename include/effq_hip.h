@@ -864,6 +864,22 @@ int effq_prep_crop_u8(const uint8_t* x, int C, int D, int H, int W, const int* p
                       void* stream);
 int effq_prep_union_mask(const float* x, int C, long long S, int mask_mode, uint8_t* mask, void* stream);
 
+/* ---- reorientation (csrc/reorient.hip; prep.py --prep_orient): x (N, D, H, W) -> y (N, dims[src_axis[0]],
+ * dims[src_axis[1]], dims[src_axis[2]]) with dims = {D, H, W}: output axis p is source axis src_axis[p] (three host ints,
+ * a permutation of 0, 1, 2, read before the call returns), reversed iff bit p of flip_mask is set:
+ *   y[n][o0][o1][o2] = x[n][s],  s[src_axis[p]] = flip_mask >> p & 1 ? dims[src_axis[p]] - 1 - o_p : o_p.
+ * elem_bytes 4 (fp32, moved as 32-bit words: a NaN keeps its payload) or 1 (uint8).  Two variants, which
+ * effq_prep_reorient_plan reports in *variant without touching the device: 0 when src_axis[2] == 2 (source W stays the
+ * innermost axis: rows are copied, 16 B per thread, reversed inside the vector, scalar tail), 1 otherwise (a tiled
+ * transpose through LDS, flips applied to the destination coordinates of the tile).  One launch, no atomics, no
+ * reductions: equal inputs give equal bits.  Refused with EFFQ_ERR_ARG before any launch: a null pointer, extents outside
+ * 1 ... 32767, N D H W >= 2^31, elem_bytes other than 1 and 4, a src_axis that is no permutation, flip_mask outside
+ * 0 ... 7, a pointer not aligned to elem_bytes, x and y overlapping.  uint8 volumes may start at any byte (a slice of a
+ * larger buffer): their wider accesses go through types of 1-B alignment. */
+int effq_prep_reorient(const void* x, int N, int D, int H, int W, const int* src_axis, int flip_mask, int elem_bytes,
+                       void* y, void* stream);
+int effq_prep_reorient_plan(const int* src_axis, int flip_mask, int elem_bytes, int* variant);
+
 #ifdef __cplusplus
 }
 #endif
