@@ -172,6 +172,9 @@ SIGNATURES = {
     "effq_prox_solve_shifted": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _I, _P, _P, _P, _SZ, _P]),
     "effq_admm_presum": (_I, [_P, _P, _P, _SZ, _P]),
     "effq_admm_project_dual": (_I, [_P, _P, _P, _I, _P, _P, _F, _P, _SZ, _P]),
+    "effq_conv_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _LLP]),
+    "effq_conv_i8_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP]),
+    "effq_conv_i8s_plan_query": (_I, [_GP, _I, _I, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "effq_conv_i8_supported": (_I, [_GP, _I, _I]),
     "effq_conv_i8s_supported": (_I, [_GP, _I, _I]),
     "effq_conv_i8s_ws_bytes": (_SZ, [_GP, _I, _I]),

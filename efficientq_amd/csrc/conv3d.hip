@@ -638,6 +638,20 @@ static size_t conv_ws_bytes(const ConvPlan& pl) {
   return 256 + conv_partial_slots(pl) * 2 * sizeof(double) + pl.wp_floats * sizeof(float) + 256;
 }
 
+// The direct-gather kind (conv_direct.h) of a call and the sizes its kernels take; 0: the tiled kernels serve it.
+// loss_only: no output, no mask, no fused quantiser.
+static int conv_direct_pick(const effq_geom* g, const ConvParams& p, bool loss_only, DirectParams* dp) {
+  if (!loss_only || effq_ablate_env("EFFQ_NO_DIRECT") != 0) return 0;
+  const int kind = conv_direct_kind(g);
+  if (kind == 0) return 0;
+  memset(dp, 0, sizeof(*dp));
+  dp->N = p.N; dp->C1 = p.C1; dp->C2 = p.C2; dp->D = p.D; dp->H = p.H; dp->W = p.W;
+  dp->OD = p.OD; dp->OH = p.OH; dp->OW = p.OW; dp->SD = p.SD; dp->SH = p.SH; dp->SW = p.SW;
+  dp->PD = p.PD; dp->PH = p.PH; dp->PW = p.PW;
+  dp->V = (long long)p.N * p.OD * p.OH * p.OW;
+  return kind;
+}
+
 }  // namespace effq
 
 using namespace effq;
@@ -650,16 +664,48 @@ size_t effq_conv_ws_bytes(const effq_geom* g) {
   return conv_ws_bytes(pl);
 }
 
+// the launch conv3d_quant_calib_step makes for a geometry (launches nothing): the same make_plan, conv_direct_pick and
+// conv_direct_plan
+int effq_conv_plan_query(const effq_geom* g, int loss_only, int* kind, int* fast, int* cslab, int* nslab, int* nt,
+                         int* grid_x, int* grid_y, int* ntiles, long long* lds_bytes) {
+  EFFQ_CHECK_ARG(kind && fast && cslab && nslab && nt && grid_x && grid_y && ntiles && lds_bytes);
+  ConvPlan pl;
+  const int rc = make_plan(g, &pl);
+  if (rc != EFFQ_OK) return rc;
+  DirectParams dp;
+  const int dkind = conv_direct_pick(g, pl.p, loss_only != 0, &dp);
+  const DirectLaunch dl = conv_direct_plan(dkind, dp, DIRECT_MAX_BLOCKS);
+  *kind = dl.kernel;
+  if (dl.kernel != 0) {
+    *fast = *cslab = *nslab = *nt = 0;
+    *grid_x = (int)dl.grid;
+    *grid_y = 1;
+    *ntiles = dl.ntiles;
+    *lds_bytes = 0;
+    return EFFQ_OK;
+  }
+  *fast = pl.fast ? 1 : 0;
+  *cslab = pl.p.cslab;
+  *nslab = pl.p.nslab;
+  *nt = pl.nt;
+  *grid_x = (int)pl.grid.x;
+  *grid_y = (int)pl.grid.y;
+  *ntiles = pl.p.ntiles;
+  *lds_bytes = (long long)pl.lds_bytes;
+  return EFFQ_OK;
+}
+
 int conv3d_quant_calib_step(const float* xq_ndhwc, const float* G, const float* bias, const float* y_fp,
                             const float* att, const effq_geom* g, const float* act_alpha_dev, int act_levels,
                             double* sqerr_out, float* out, void* ws, size_t ws_bytes, void* stream) {
+  // the geometry first: a refused one reports the planner's reason whatever else the call lacks (its workspace has 0 bytes)
+  ConvPlan pl;
+  int rc = make_plan(g, &pl);
+  if (rc != EFFQ_OK) return rc;
   EFFQ_CHECK_ARG(xq_ndhwc && G && g && ws);
   EFFQ_CHECK_ARG(y_fp != nullptr || out != nullptr);
   EFFQ_CHECK_ARG(y_fp == nullptr || sqerr_out != nullptr);
   EFFQ_CHECK_ARG(act_alpha_dev == nullptr || act_levels >= 2);
-  ConvPlan pl;
-  int rc = make_plan(g, &pl);
-  if (rc != EFFQ_OK) return rc;
   if (ws_bytes < conv_ws_bytes(pl)) {
     set_error("conv3d: workspace %zu < required %zu", ws_bytes, conv_ws_bytes(pl));
     return EFFQ_ERR_WORKSPACE;
@@ -686,16 +732,10 @@ int conv3d_quant_calib_step(const float* xq_ndhwc, const float* G, const float* 
   // (the ticket of the last-block reduction is left at zero by the kernel that used it: the caller zero-fills
   //  the workspace once, effq_hip.h)
   // loss-only calls of the short-K layers go to the direct-gather kernels
-  const int dkind = (out == nullptr && att == nullptr && !p.act_on && y_fp != nullptr && effq_ablate_env("EFFQ_NO_DIRECT") == 0)
-                        ? conv_direct_kind(g) : 0;
+  DirectParams dp;
+  const int dkind = conv_direct_pick(g, p, out == nullptr && att == nullptr && !p.act_on && y_fp != nullptr, &dp);
   if (dkind != 0) {
-    DirectParams dp;
-    memset(&dp, 0, sizeof(dp));
     dp.x = xq_ndhwc; dp.G = G; dp.bias = bias; dp.y = y_fp;
-    dp.N = p.N; dp.C1 = p.C1; dp.C2 = p.C2; dp.D = p.D; dp.H = p.H; dp.W = p.W;
-    dp.OD = p.OD; dp.OH = p.OH; dp.OW = p.OW; dp.SD = p.SD; dp.SH = p.SH; dp.SW = p.SW;
-    dp.PD = p.PD; dp.PH = p.PH; dp.PW = p.PW;
-    dp.V = (long long)p.N * p.OD * p.OH * p.OW;
     dp.partials = p.partials; dp.ticket = p.ticket; dp.sqerr = sqerr_out;
     rc = conv_direct_launch(dkind, dp, DIRECT_MAX_BLOCKS, st);
     if (rc == EFFQ_OK) {

@@ -454,55 +454,76 @@ int conv_direct_kind(const effq_geom* g) {
   return 0;
 }
 
-int conv_direct_launch(int kind, DirectParams& p, size_t max_blocks, hipStream_t st) {
-  if ((long long)p.N * p.D * p.H * p.W * p.C1 >= (1ll << 31) || p.V >= (1ll << 31)) return EFFQ_ERR_ARG;
-  p.ntiles = (int)((p.V + 31) / 32);
-  if (kind == 3) {
-    const int td = (p.OD + C4_TD - 1) / C4_TD, th = (p.OH + C4_TH - 1) / C4_TH, tw = (p.OW + C4_TW - 1) / C4_TW;
-    const long long nt = (long long)p.N * td * th * tw;
-    if (nt >= (1ll << 30)) return EFFQ_ERR_ARG;
-    size_t grid = (size_t)nt < 512 ? (size_t)nt : 512;
+DirectLaunch conv_direct_plan(int kind, const DirectParams& p, size_t max_blocks) {
+  DirectLaunch dl;
+  memset(&dl, 0, sizeof(dl));
+  if (kind == 0) return dl;
+  if ((long long)p.N * p.D * p.H * p.W * p.C1 >= (1ll << 31) || p.V >= (1ll << 31)) return dl;
+  const int td = (p.OD + C4_TD - 1) / C4_TD, th = (p.OH + C4_TH - 1) / C4_TH, tw = (p.OW + C4_TW - 1) / C4_TW;
+  const long long nt = (long long)p.N * td * th * tw;
+  const bool staged = kind == 3 || (kind == 1 && p.SD == p.SH && p.SH == p.SW && (p.SD == 1 || p.SD == 2));
+  if (kind == 3 && nt >= (1ll << 30)) return dl;
+  if (staged && nt < (1ll << 30)) {
+    size_t grid = (size_t)nt < 512 ? (size_t)nt : 512;   // 2 workgroups per CU
     if (grid > max_blocks) grid = max_blocks;
-    if (p.SD == 2 && p.SW == 2)
-      hipLaunchKernelGGL((k_conv3d_c1h<2, 2, 2>), dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-    else if (p.SD == 2)
-      hipLaunchKernelGGL((k_conv3d_c1h<2, 2, 1>), dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);   // LiTS
-    else
-      hipLaunchKernelGGL((k_conv3d_c1h<1, 1, 1>), dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-    return EFFQ_OK;
-  }
-  if (kind == 1 && p.SD == p.SH && p.SH == p.SW && (p.SD == 1 || p.SD == 2)) {
-    const int td = (p.OD + C4_TD - 1) / C4_TD, th = (p.OH + C4_TH - 1) / C4_TH, tw = (p.OW + C4_TW - 1) / C4_TW;
-    const long long nt = (long long)p.N * td * th * tw;
-    if (nt < (1ll << 30)) {
-      size_t grid = (size_t)nt < 512 ? (size_t)nt : 512;   // 2 workgroups per CU
-      if (grid > max_blocks) grid = max_blocks;
-      if (p.SD == 2)
-        hipLaunchKernelGGL(k_conv3d_c4h<2>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-      else
-        hipLaunchKernelGGL(k_conv3d_c4h<1>, dim3((unsigned)grid), dim3(256), 0, st, p, td, th, tw, (int)nt);
-      return EFFQ_OK;
-    }
+    dl.kernel = kind;
+    dl.grid = (unsigned)grid;
+    dl.td = td; dl.th = th; dl.tw = tw;
+    dl.ntiles = (int)nt;
+    return dl;
   }
   if (kind == 1) {
-    size_t grid = ((size_t)p.ntiles + 3) / 4;
+    dl.ntiles = (int)((p.V + 31) / 32);
+    size_t grid = ((size_t)dl.ntiles + 3) / 4;
     // 2 workgroups per CU (3 are 5 % faster alone): the 164-VGPR waves then leave room for the scale fixed point
     // of the next ADMM iteration to run beside this kernel instead of queueing behind it (first-conv layer 135 -> 122 ms)
     if (grid > 512) grid = 512;
     if (grid > max_blocks) grid = max_blocks;
-    hipLaunchKernelGGL(k_conv3d_c4, dim3((unsigned)grid), dim3(256), 0, st, p);
-    return EFFQ_OK;
+    dl.kernel = 4;
+    dl.grid = (unsigned)grid;
+    return dl;
   }
   const size_t nbody4 = (size_t)((p.V + 63) / 64);
   size_t grid = (nbody4 + 3) / 4;
   if (grid > 1024) grid = 1024;
   if (grid > max_blocks) grid = max_blocks;
   if (grid < 1) grid = 1;
+  dl.kernel = 2;
+  dl.grid = (unsigned)grid;
+  dl.ntiles = (int)((p.V + 15) / 16);
+  return dl;
+}
+
+int conv_direct_launch(int kind, DirectParams& p, size_t max_blocks, hipStream_t st) {
+  const DirectLaunch dl = conv_direct_plan(kind, p, max_blocks);
+  if (dl.kernel == 0) return EFFQ_ERR_ARG;
+  p.ntiles = (int)((p.V + 31) / 32);
+  const dim3 grid(dl.grid), block(256);
+  if (dl.kernel == 3) {
+    if (p.SD == 2 && p.SW == 2)
+      hipLaunchKernelGGL((k_conv3d_c1h<2, 2, 2>), grid, block, 0, st, p, dl.td, dl.th, dl.tw, dl.ntiles);
+    else if (p.SD == 2)
+      hipLaunchKernelGGL((k_conv3d_c1h<2, 2, 1>), grid, block, 0, st, p, dl.td, dl.th, dl.tw, dl.ntiles);   // LiTS
+    else
+      hipLaunchKernelGGL((k_conv3d_c1h<1, 1, 1>), grid, block, 0, st, p, dl.td, dl.th, dl.tw, dl.ntiles);
+    return EFFQ_OK;
+  }
+  if (dl.kernel == 1) {
+    if (p.SD == 2)
+      hipLaunchKernelGGL(k_conv3d_c4h<2>, grid, block, 0, st, p, dl.td, dl.th, dl.tw, dl.ntiles);
+    else
+      hipLaunchKernelGGL(k_conv3d_c4h<1>, grid, block, 0, st, p, dl.td, dl.th, dl.tw, dl.ntiles);
+    return EFFQ_OK;
+  }
+  if (dl.kernel == 4) {
+    hipLaunchKernelGGL(k_conv3d_c4, grid, block, 0, st, p);
+    return EFFQ_OK;
+  }
   switch (p.C1) {
-    case 32: hipLaunchKernelGGL((k_conv1_mfma<32, 4>), dim3((unsigned)grid), dim3(256), 0, st, p); break;
-    case 64: hipLaunchKernelGGL((k_conv1_mfma<64, 4>), dim3((unsigned)grid), dim3(256), 0, st, p); break;
-    case 128: hipLaunchKernelGGL((k_conv1_mfma<128, 2>), dim3((unsigned)grid), dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((k_conv1_mfma<256, 1>), dim3((unsigned)grid), dim3(256), 0, st, p); break;
+    case 32: hipLaunchKernelGGL((k_conv1_mfma<32, 4>), grid, block, 0, st, p); break;
+    case 64: hipLaunchKernelGGL((k_conv1_mfma<64, 4>), grid, block, 0, st, p); break;
+    case 128: hipLaunchKernelGGL((k_conv1_mfma<128, 2>), grid, block, 0, st, p); break;
+    default: hipLaunchKernelGGL((k_conv1_mfma<256, 1>), grid, block, 0, st, p); break;
   }
   return EFFQ_OK;
 }

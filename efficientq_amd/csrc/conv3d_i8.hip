@@ -1178,6 +1178,25 @@ int effq_conv_i8_out_supported(const effq_geom* g, int act_levels, int w_levels)
   return i8_out_kernel(pl.p) != 0 ? 1 : 0;
 }
 
+// The kernel conv_i8_impl launches and its grid.x (effq_conv_i8_plan_query reports both): 1 k_conv3d_i8l2e, 2 k_conv3d_i8l2,
+// 3 k_conv3d_i8<2>, 4 k_conv3d_i8w, 5 k_conv3d_i8g<4>, 6 k_conv3d_i8g<8>, 7 k_conv3d_i8g2<16>; 0: an output is wanted and
+// no output-storing kernel serves the shape.
+static int i8_kernel(const I8Plan& pl, bool want_out, int* grid_x) {
+  const ConvI8Params& p = pl.p;
+  *grid_x = (int)pl.grid.x;
+  if (want_out && i8_out_kernel(p) == 0) return 0;
+  if (i8_w64(p)) {
+    int gx = 256;                           // one workgroup per CU (LDS); pl.nblk = 256 partial slots
+    if (gx > p.ntiles) gx = p.ntiles;
+    if ((size_t)gx > pl.nblk) gx = (int)pl.nblk;
+    *grid_x = gx;
+    return 4;
+  }
+  if (p.C1 == 32) return (want_out || i8_l2e(p)) ? 1 : 2;
+  if (p.C1 == 64) return 3;
+  return p.C1 == 512 ? 7 : p.C1 == 128 ? 5 : 6;
+}
+
 static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float* bias, const float* y_fp,
                         const effq_geom* g, const float* act_alpha_dev, int act_levels,
                         const effq_fp_state* w_state_dev, int w_levels, double* sqerr_out, void* ws, size_t ws_bytes,
@@ -1209,24 +1228,20 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
   p.debug = effq_ablate_env("EFFQ_I8_DEBUG");
   p.out = out;
   p.att = att;
-  const int outk = (out != nullptr) ? i8_out_kernel(p) : 0;
-  if (out != nullptr && outk == 0) {
+  int gx = 0;
+  const int kern = i8_kernel(pl, out != nullptr, &gx);
+  if (kern == 0) {
     set_error("conv_i8: no output-storing kernel for this shape (effq_conv_i8_out_supported)");
     return EFFQ_ERR_ARG;
   }
   hipStream_t st = as_stream(stream);
   // (the ticket of the last-block reduction is left at zero by the kernel that used it: the caller zero-fills
   //  the workspace once, effq_hip.h)
-  if (i8_w64(p)) {
-    size_t nb = (pl.wq_bytes + 255) / 256;
-    if (nb > 2048) nb = 2048;
+  if (kern == 4) {
     hipLaunchKernelGGL(k_pack_weight_i8g<4>, dim3((unsigned)((p.c2p + 3) / 4)), dim3(256), (size_t)4 * p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
     const size_t lds = (size_t)W64_WLB + W64_HALOB;
     EFFQ_HIP(raise_lds_limit<k_conv3d_i8w<false>>(lds));
     EFFQ_HIP(raise_lds_limit<k_conv3d_i8w<true>>(lds));
-    int gx = 256;                           // one workgroup per CU (LDS); pl.nblk = 256 partial slots
-    if (gx > p.ntiles) gx = p.ntiles;
-    if ((size_t)gx > pl.nblk) gx = (int)pl.nblk;
     if (out != nullptr)
       hipLaunchKernelGGL(k_conv3d_i8w<true>, dim3((unsigned)gx), dim3(512), lds, st, p);
     else
@@ -1244,25 +1259,25 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
       hipLaunchKernelGGL(k_pack_weight_i8g<1>, dim3((unsigned)p.c2p), dim3(256), (size_t)p.C1 * 27, st, Gq, wq, p.C1, p.C2, 27, p.c2p);
     EFFQ_LAUNCH_CHECK();
   }
-  if (p.C1 == 32) {
+  if (kern == 1) {
     if (out != nullptr)
       hipLaunchKernelGGL(k_conv3d_i8l2e<true>, pl.grid, dim3(256), 0, st, p);
-    else if (i8_l2e(p))
-      hipLaunchKernelGGL(k_conv3d_i8l2e<false>, pl.grid, dim3(256), 0, st, p);
     else
-      hipLaunchKernelGGL(k_conv3d_i8l2, pl.grid, dim3(256), 0, st, p);
-  } else if (p.C1 == 64) {
+      hipLaunchKernelGGL(k_conv3d_i8l2e<false>, pl.grid, dim3(256), 0, st, p);
+  } else if (kern == 2) {
+    hipLaunchKernelGGL(k_conv3d_i8l2, pl.grid, dim3(256), 0, st, p);
+  } else if (kern == 3) {
     hipLaunchKernelGGL(k_conv3d_i8<2>, pl.grid, dim3(256), 0, st, p);
   } else {
     const int cg = p.C1 / 32;
     const size_t lds = (size_t)((I_NH * (32 * cg + 16) + I_HD * I_HH * halo_row_pad(cg) + 15) / 16) * 16 +
                        (size_t)128 * I_TS * sizeof(float);
-    if (cg == 16) {
+    if (kern == 7) {
       const size_t lds2 = (size_t)((G2_NH * (32 * 16 + 16) + G2_HD * I_HH * halo_row_pad(16) + 15) / 16) * 16 +
                           (size_t)64 * G2_TS * sizeof(float);
       EFFQ_HIP(raise_lds_limit<k_conv3d_i8g2<16>>(lds2));
       hipLaunchKernelGGL(k_conv3d_i8g2<16>, pl.grid, dim3(256), lds2, st, p);
-    } else if (cg == 4) {
+    } else if (kern == 5) {
       EFFQ_HIP(raise_lds_limit<k_conv3d_i8g<4>>(lds));
       hipLaunchKernelGGL(k_conv3d_i8g<4>, pl.grid, dim3(256), lds, st, p);
     } else {
@@ -1271,6 +1286,23 @@ static int conv_i8_impl(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float
     }
   }
   EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+// the launch conv3d_calib_step_i8 (want_out == 0) or conv3d_quant_forward_i8 makes for a geometry (launches nothing): the
+// same i8_plan and i8_kernel
+int effq_conv_i8_plan_query(const effq_geom* g, int want_out, int* kernel, int* grid_x, int* grid_y, int* ntiles) {
+  EFFQ_CHECK_ARG(kernel && grid_x && grid_y && ntiles);
+  I8Plan pl;
+  const int rc = i8_plan(g, &pl);
+  if (rc != EFFQ_OK) return rc;
+  *kernel = i8_kernel(pl, want_out != 0, grid_x);
+  if (*kernel == 0) {
+    set_error("conv_i8: no output-storing kernel for this shape (effq_conv_i8_out_supported)");
+    return EFFQ_ERR_ARG;
+  }
+  *grid_y = (*kernel == 4) ? 1 : (int)pl.grid.y;
+  *ntiles = pl.p.ntiles;
   return EFFQ_OK;
 }
 

@@ -374,6 +374,18 @@ size_t effq_conv_i8s_ws_bytes(const effq_geom* g, int act_levels, int w_levels) 
          pl.su_bytes + 256;
 }
 
+// the launch conv3d_calib_step_i8s makes for a geometry and a level pair (launches nothing): the same i8s_plan
+int effq_conv_i8s_plan_query(const effq_geom* g, int act_levels, int w_levels, int* nj, int* ct, int* taps, int* k,
+                             int* aoff, int* wmul, int* grid) {
+  EFFQ_CHECK_ARG(nj && ct && taps && k && aoff && wmul && grid);
+  EFFQ_CHECK_ARG(effq_conv_i8s_supported(g, act_levels, w_levels));
+  I8sPlan pl;
+  const int rc = i8s_plan(g, act_levels, w_levels, &pl);
+  if (rc != EFFQ_OK) return rc;
+  *nj = pl.p.NJ; *ct = pl.p.CT; *taps = pl.p.T; *k = pl.p.K; *aoff = pl.p.aoff; *wmul = pl.p.wmul; *grid = pl.grid;
+  return EFFQ_OK;
+}
+
 int conv3d_calib_step_i8s(const uint8_t* xidx_ndhwc, const int8_t* Gq, const float* bias, const float* y_fp,
                           const effq_geom* g, const float* act_alpha_dev, int act_levels,
                           const effq_fp_state* w_state_dev, int w_levels, int prepare, double* sqerr_out, void* ws,

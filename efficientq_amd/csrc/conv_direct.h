@@ -19,6 +19,18 @@ struct DirectParams {
 
 // 0: not served; 1: 4-channel 3x3x3 conv onto 32 channels; 2: 1x1x1 conv onto <= 4 channels; 3: 1-channel 3x3x3 conv onto 32
 int conv_direct_kind(const effq_geom* g);
+
+// The launch conv_direct_launch makes for a kind: which kernel, its grid and the tiles it walks.  kernel: 0 none (the
+// sizes are beyond the direct kernels' 32-bit indices: the tiled kernels serve the call), 1 k_conv3d_c4h<S>,
+// 2 k_conv1_mfma, 3 k_conv3d_c1h<SD, SH, SW>, 4 k_conv3d_c4 (the 4-channel conv at every stride k_conv3d_c4h has no
+// instance for).  ntiles: 4 x 4 x 8 output tiles (td x th x tw per volume) for kernels 1 and 3, 32-voxel wave tiles for 4,
+// 16-voxel wave tiles for 2.
+struct DirectLaunch {
+  int kernel;
+  unsigned grid;
+  int td, th, tw, ntiles;
+};
+DirectLaunch conv_direct_plan(int kind, const DirectParams& p, size_t max_blocks);
 int conv_direct_launch(int kind, DirectParams& p, size_t max_blocks, hipStream_t st);
 
 }  // namespace effq

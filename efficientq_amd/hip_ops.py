@@ -94,6 +94,41 @@ def _check_shapes(geom: Geom, x, w=None, bias=None, y=None, att=None):
             raise _lib.EffqError(f"{name} has {t.numel()} elements, geometry needs {n}")
 
 
+CONV_KINDS = ("tiled", "k_conv3d_c4h", "k_conv1_mfma", "k_conv3d_c1h", "k_conv3d_c4")
+CONV_I8_KERNELS = (None, "l2e", "l2", "i8<2>", "i8w", "i8g<4>", "i8g<8>", "i8g2<16>")
+
+
+def conv_plan_query(lib, geom: Geom, loss_only: bool = False) -> dict:
+    """The launch conv3d_quant_calib_step makes for a geometry; loss_only: targets, no output, no mask, no fused quantiser
+    (effq_conv_plan_query: answered on the host, needs no device).  A refused geometry raises EffqError."""
+    out = [C.c_int() for _ in range(8)]
+    lds = C.c_longlong()
+    check(lib.effq_conv_plan_query(C.byref(geom), int(bool(loss_only)), *[C.byref(o) for o in out], C.byref(lds)),
+          "effq_conv_plan_query")
+    d = dict(zip(("kind", "fast", "cslab", "nslab", "nt", "grid_x", "grid_y", "ntiles"), (o.value for o in out)))
+    d.update(fast=bool(d["fast"]), lds_bytes=lds.value, kernel=CONV_KINDS[d["kind"]])
+    return d
+
+
+def conv_i8_plan_query(lib, geom: Geom, want_out: bool = False) -> dict:
+    """The launch conv3d_calib_step_i8 (want_out: conv3d_quant_forward_i8) makes for a geometry (effq_conv_i8_plan_query,
+    on the host)."""
+    out = [C.c_int() for _ in range(4)]
+    check(lib.effq_conv_i8_plan_query(C.byref(geom), int(bool(want_out)), *[C.byref(o) for o in out]),
+          "effq_conv_i8_plan_query")
+    d = dict(zip(("kind", "grid_x", "grid_y", "ntiles"), (o.value for o in out)))
+    d["kernel"] = CONV_I8_KERNELS[d["kind"]]
+    return d
+
+
+def conv_i8s_plan_query(lib, geom: Geom, act_levels: int, w_levels: int) -> dict:
+    """The launch conv3d_calib_step_i8s makes for a geometry and a level pair (effq_conv_i8s_plan_query, on the host)."""
+    out = [C.c_int() for _ in range(7)]
+    check(lib.effq_conv_i8s_plan_query(C.byref(geom), int(act_levels), int(w_levels), *[C.byref(o) for o in out]),
+          "effq_conv_i8s_plan_query")
+    return dict(zip(("NJ", "CT", "T", "K", "aoff", "wmul", "grid"), (o.value for o in out)))
+
+
 class HipOps:
     """Per-device handle: stream + library-owned workspaces (grown on demand, never shrunk)."""
 
@@ -929,6 +964,18 @@ class HipOps:
         check(self.lib.effq_admm_project_dual(_ptr(v), _ptr(wstar), _ptr(state), levels, _ptr(G), _ptr(dual),
                                               float(dual_div), _ptr(Gq), v.numel(), self.stream),
               "effq_admm_project_dual")
+
+    def conv_plan(self, geom: Geom, loss_only: bool = False) -> dict:
+        """The launch conv_step makes for a geometry (conv_plan_query)."""
+        return conv_plan_query(self.lib, geom, loss_only)
+
+    def conv_i8_plan(self, geom: Geom, want_out: bool = False) -> dict:
+        """The launch conv_step_i8 (or, with want_out, conv_forward_i8) makes for a geometry (conv_i8_plan_query)."""
+        return conv_i8_plan_query(self.lib, geom, want_out)
+
+    def conv_i8s_plan(self, geom: Geom, act_levels: int, w_levels: int) -> dict:
+        """The launch conv_step_i8s makes for a geometry and a level pair (conv_i8s_plan_query)."""
+        return conv_i8s_plan_query(self.lib, geom, act_levels, w_levels)
 
     def conv_i8_supported(self, geom: Geom, act_levels: int, w_levels: int) -> bool:
         return bool(self.lib.effq_conv_i8_supported(C.byref(geom), int(act_levels), int(w_levels)))

@@ -399,6 +399,15 @@ size_t effq_conv_ws_bytes(const effq_geom* g);
 int conv3d_quant_calib_step(const float* xq_ndhwc, const float* G, const float* bias, const float* y_fp,
                             const float* att, const effq_geom* g, const float* act_alpha_dev, int act_levels,
                             double* sqerr_out, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The launch conv3d_quant_calib_step makes for a geometry, answered on the host (no device, nothing launched).
+ * loss_only != 0: a call with targets and no output, no mask and no fused quantiser, the only one the direct-gather
+ * kernels take.  kind: 0 a tiled kernel (k_conv3d_k3 when fast, else k_conv3d), 1 k_conv3d_c4h<S>, 2 k_conv1_mfma,
+ * 3 k_conv3d_c1h<SD, SH, SW>, 4 k_conv3d_c4.  kind 0: cslab channels per LDS slab, nslab slabs per tile, nt 32-channel
+ * output blocks per wave, the grid, the 4 x 4 x 8-voxel output tiles and the dynamic LDS bytes.  kind != 0: fast, cslab,
+ * nslab, nt and lds_bytes are 0, grid_y is 1 and ntiles counts what the kernel walks (4 x 4 x 8 tiles for 1 and 3, 32-voxel
+ * wave tiles for 4, 16-voxel wave tiles for 2).  A geometry the planner refuses returns its error (effq_last_error). */
+int effq_conv_plan_query(const effq_geom* g, int loss_only, int* kind, int* fast, int* cslab, int* nslab, int* nt,
+                         int* grid_x, int* grid_y, int* ntiles, long long* lds_bytes);
 
 /* ---- exact-integer ("int-simulated") form of the per-iteration loss evaluation -------------------
  * Same quantity as conv3d_quant_calib_step(xq, G, bias, y_fp, NULL, ...)'s sqerr_out[0], for quantised
@@ -424,6 +433,11 @@ int conv3d_quant_forward_i8(const uint8_t* xidx_ndhwc, const int8_t* Gq, const f
                             const float* att, const effq_geom* g, const float* act_alpha_dev, int act_levels,
                             const effq_fp_state* w_state_dev, int w_levels, double* sqerr_out, float* out, void* ws,
                             size_t ws_bytes, void* stream);
+/* The launch conv3d_calib_step_i8 (want_out == 0) or conv3d_quant_forward_i8 (want_out != 0) makes for a geometry, answered
+ * on the host.  kernel: 1 k_conv3d_i8l2e, 2 k_conv3d_i8l2, 3 k_conv3d_i8<2>, 4 k_conv3d_i8w, 5 k_conv3d_i8g<4>,
+ * 6 k_conv3d_i8g<8>, 7 k_conv3d_i8g2<16>; ntiles: output tiles of 8 x 4 x 8 (C1 = 32), 2 x 4 x 8 (C1 = 512) or 4 x 4 x 8
+ * voxels.  An output no kernel can store is an error. */
+int effq_conv_i8_plan_query(const effq_geom* g, int want_out, int* kernel, int* grid_x, int* grid_y, int* ntiles);
 
 /* The same exact-integer loss for the layers the tiled kernels above do not take: few taps*channels
  * (KD*KH*KW*C1 <= 256 with C1 == 4 or C1 % 16 == 0: the first conv, the 1x1x1 convs, the classifier), any
@@ -437,6 +451,11 @@ int conv3d_calib_step_i8s(const uint8_t* xidx_ndhwc, const int8_t* Gq, const flo
                           const effq_geom* g, const float* act_alpha_dev, int act_levels,
                           const effq_fp_state* w_state_dev, int w_levels, int prepare, double* sqerr_out,
                           void* ws, size_t ws_bytes, void* stream);
+/* The launch conv3d_calib_step_i8s makes, answered on the host: nj K steps of 32 x ct column tiles of 32 channels, the taps
+ * and K = taps * C1, the activation offset aoff (128 above 128 levels) and the weight multiplier wmul (2 at 256 levels),
+ * and the grid.  An unsupported geometry or level pair is an error. */
+int effq_conv_i8s_plan_query(const effq_geom* g, int act_levels, int w_levels, int* nj, int* ct, int* taps, int* k,
+                             int* aoff, int* wmul, int* grid);
 
 /* ---- f3: tune_activation_range (ptqer.py:238-272) - Adam on every alpha_act, end-to-end MSE, STE through discretize ----
  * Backward of q = discretize(x / alpha, L, 0, 1) * alpha (PTQConv.py:114-116; round with identity gradient,

@@ -123,6 +123,114 @@ def test_gram_dispatch_queries_launch_nothing():
         assert lib.effq_gram_loss_i8_num_planes(cap + 1) == (P + 1 if P < 6 else -1)
 
 
+def test_conv_dispatch_queries_answer_the_classes_of_the_geometry_cases():
+    """effq_conv_plan_query / effq_conv_i8_plan_query / effq_conv_i8s_plan_query answer without a device, from the planners
+    and the kernel choice the launches use: every case of tests/test_conv_geometry_gpu.py lands in the class it names, and
+    the two halo refusals are make_plan's own error."""
+    import math
+    from efficientq_amd import _lib
+    from efficientq_amd import hip_ops as H
+    from tests import test_conv_geometry_gpu as G
+    lib = _lib.load()
+    n = G.N
+    for case, (c1, c2, k, s, p, sp, want) in G.F32_TILED.items():
+        geom = H.make_geom((n, c1, *sp), c2, k, s, p)
+        G.assert_tiled_plan(H.conv_plan_query(lib, geom, False), want)
+        assert H.conv_plan_query(lib, geom, True)["kind"] == 0, case
+    # every plan branch the cases were written for is there
+    plans = {c: H.conv_plan_query(lib, H.make_geom((n, v[0], *v[5]), v[1], v[2], v[3], v[4]), False)
+             for c, v in G.F32_TILED.items()}
+    big = [c for c, pl in plans.items() if pl["lds_bytes"] > 64 * 1024]
+    assert any(plans[c]["nslab"] > 1 for c in big) and any(plans[c]["nslab"] == 1 for c in big)
+    assert {pl["cslab"] for pl in plans.values()} == {8, 16, 32} and any(pl["grid_y"] == 3 for pl in plans.values())
+    assert all(pl["lds_bytes"] <= 160 * 1024 for pl in plans.values())
+    for case, (c1, c2, k, s, p, nn, sp, kernel) in G.DIRECT.items():
+        geom = H.make_geom((nn, c1, *sp), c2, k, s, p)
+        G.assert_direct_plan(case, H.conv_plan_query(lib, geom, True))
+        assert H.conv_plan_query(lib, geom, False)["kind"] == 0, case
+    assert {v[7] for v in G.DIRECT.values()} == set(H.CONV_KINDS[1:])
+    for case, (c1, c2, k, s, p, sp) in G.F32_REFUSED.items():
+        geom = H.make_geom((n, c1, *sp), c2, k, s, p)
+        for lo in (False, True):
+            with pytest.raises(_lib.EffqError, match=r"EFFQ_ERR_ARG.*halo tile of \d+ voxels does not fit LDS"):
+                H.conv_plan_query(lib, geom, lo)
+        assert lib.effq_conv_ws_bytes(geom) == 0
+    for case, (c1, c2, out, pad, la, lw, _, kern) in list(G.I8.items()) + list(G.I8_FORWARD.items()):
+        geom = H.make_geom((n, c1, *G._i8_in(out, pad)), c2, 3, 1, pad)
+        assert geom.out_dims() == out and lib.effq_conv_i8_supported(geom, la, lw) == 1, case
+        fwd = case in G.I8_FORWARD
+        plan = H.conv_i8_plan_query(lib, geom, fwd)
+        assert plan["kernel"] == kern and 0 < plan["grid_x"] <= plan["ntiles"], (case, plan)
+        if kern not in ("l2e", "i8w"):
+            with pytest.raises(_lib.EffqError, match="output"):
+                H.conv_i8_plan_query(lib, geom, True)
+    assert {v[7] for v in G.I8.values()} == set(H.CONV_I8_KERNELS[1:])
+    with pytest.raises(_lib.EffqError):
+        H.conv_i8_plan_query(lib, H.make_geom((n, 48, 6, 6, 10), 32, 3, 1, 1), False)
+    for case, (c1, c2, k, s, p, la, lw, sp, want) in G.I8S.items():
+        geom = H.make_geom((n, c1, *sp), c2, k, s, p)
+        G.assert_i8s_plan(H.conv_i8s_plan_query(lib, geom, la, lw), want, c1, k)
+    with pytest.raises(_lib.EffqError):
+        H.conv_i8s_plan_query(lib, H.make_geom((n, 32, 8, 8, 8), 32, 3, 1, 1), 4, 4)              # K = 864
+    # the shipped first convs and the classifier keep their kernels
+    for shape, c2, k, s, p, kernel in [((1, 4, 32, 32, 32), 32, 3, 2, 1, "k_conv3d_c4h"), ((1, 4, 32, 32, 32), 32, 3, 1, 1, "k_conv3d_c4h"),
+                                       ((1, 1, 32, 32, 32), 32, 3, (2, 2, 1), 1, "k_conv3d_c1h"), ((1, 32, 8, 8, 8), 3, 1, 1, 0, "k_conv1_mfma"),
+                                       ((1, 4, 32, 32, 32), 32, 3, (2, 2, 1), 1, "k_conv3d_c4"), ((1, 32, 8, 8, 8), 32, 3, 1, 1, "tiled")]:
+        assert H.conv_plan_query(lib, H.make_geom(shape, c2, k, s, p), True)["kernel"] == kernel
+
+
+def test_conv_comparison_rejects_a_dropped_tap_and_swapped_kernel_axes():
+    """The comparison helper of tests/test_conv_geometry_gpu.py can fail.  (a) The fp64 reference of the padding-0 case with
+    the largest tap product of one output channel left out at one corner output (all 27 taps there), and the same at the
+    padding-(0, 1, 2) case, whose corner has 6 of 27 taps: the elementwise bound rejects both - and so does the max-norm bound
+    alone, since an ordinary product is about 1e-1 of the largest output, four orders above 1e-5.  What the elementwise bound
+    adds is smaller errors at outputs with a small S: at the 6-tap corner it is 9.7e-6 against the max-norm bound's 2.7e-5, and
+    an error between the two is rejected by it alone.  At the 27-tap corner it is the looser one, 7.0e-5 against 2.7e-5: K =
+    216, so (K + 2) 2^-24 = 1.3e-5 already exceeds 1e-5, and S there exceeds the largest output.  (b) The (3, 3, 1) case computed with the two kernel axes H and W
+    swapped (a (3, 1, 3) kernel on the matching padding): both bounds reject it; an exact copy passes both."""
+    import torch.nn.functional as F
+    from tests import test_conv_geometry_gpu as G
+    for case in ("k3_pad0", "k3_pad012"):
+        c1, c2, k, s, p, sp, _ = G.F32_TILED[case]
+        pr = G._f32_problem(c1, c2, k, s, p, sp)
+        ref, S, K = pr["ref"], pr["S"], pr["K"]
+        assert G.value_report(ref.clone(), ref, S, K)[:2] == (True, True)
+        pd, ph, pw = G._triple(p)
+        # corner output (0, 0, 0) of channel 0, batch 1: its taps are x[1, c, kd - pd, kh - ph, kw - pw] w[0, c, kd, kh, kw]
+        prods = {}
+        for c in range(c1):
+            for kd in range(3):
+                for kh in range(3):
+                    for kw in range(3):
+                        i = (kd - pd, kh - ph, kw - pw)
+                        if min(i) >= 0:
+                            prods[(c, kd, kh, kw)] = pr["x"][1, c, i[0], i[1], i[2]].double() * pr["w"][0, c, kd, kh, kw].double()
+        assert len(prods) == c1 * (27 if case == "k3_pad0" else 6)
+        assert abs(sum(prods.values()) + pr["b"][0].double() - ref[1, 0, 0, 0, 0]) <= 1e-12
+        got = ref.clone()
+        got[1, 0, 0, 0, 0] -= max(prods.values(), key=abs)
+        maxnorm_ok, elem_ok, worst = G.value_report(got, ref, S, K)
+        assert not elem_ok and worst > 1e3 and not maxnorm_ok
+        with pytest.raises(AssertionError, match="max-norm"):
+            G.check_values(got, ref, S, K)
+        if case == "k3_pad012":
+            eb = (K + 2) * 2.0 ** -24 * S[1, 0, 0, 0, 0].item()
+            mb = 1e-5 * ref.abs().max().item()
+            assert eb < 0.9 * mb, (eb, mb)
+            got = ref.clone()
+            got[1, 0, 0, 0, 0] += (eb * mb) ** 0.5
+            assert G.value_report(got, ref, S, K)[:2] == (True, False)
+            with pytest.raises(AssertionError, match="elementwise"):
+                G.check_values(got, ref, S, K)
+    c1, c2, k, s, p, sp, _ = G.F32_TILED["k331_not_cubic"]
+    assert k == (3, 3, 1) and p == (1, 1, 0)
+    pr = G._f32_problem(c1, c2, k, s, p, sp)
+    swapped = F.conv3d(pr["x"].double(), pr["w"].double().transpose(3, 4), pr["b"].double(), s, (1, 0, 1))
+    assert swapped.shape == pr["ref"].shape                       # a 1-wide axis at padding 0 on either side: same output
+    maxnorm_ok, elem_ok, _ = G.value_report(swapped, pr["ref"], pr["S"], pr["K"])
+    assert not maxnorm_ok and not elem_ok
+
+
 def test_gram_test_reference_agrees_with_the_oracle():
     """The fp64 slab reference of tests/test_gram_shapes_gpu.py (strided views, slab by slab) against the oracle's
     patch_matrix and ProxSystem at two small shapes - one strided, one without bias - to 1e-12 of the largest entry."""
