@@ -186,11 +186,9 @@ SIGNATURES = {
     "effq_conv_ws_bytes": (_SZ, [_GP]),
     "conv3d_quant_calib_step": (_I, [_P, _P, _P, _P, _P, _GP, _P, _I, _P, _P, _P, _SZ, _P]),
     "effq_adam_step": (_I, [_P, _P, _P, _P, _D, _D, _D, _D, _I, _SZ, _P]),
-    "effq_window_gather": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "effq_window_gather_flip": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "effq_window_gather": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_window_put": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "effq_window_stitch_weighted": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
     "effq_seg_labels_source": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P]),

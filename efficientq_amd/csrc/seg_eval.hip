@@ -1,97 +1,14 @@
-// Validation of a segmentation network on whole volumes (evaluate.validate_seg): the overlapped windows of a volume
-// gathered into one channels-last batch, the per-window logits stitched back to the volume, and the per-class confusion
-// counts of the stitched logits against the label, the label maps written for the viewer (--save_nii), and the counts
-// of a label map against the label (effq_label_tallies, the score of a map cleaned by --post).  All five stream HBM once
-// and do no arithmetic to speak of.
+// Validation of a segmentation network on whole volumes (evaluate.validate_seg), after window.hip has stitched the
+// logits: the per-class confusion counts of the stitched logits against the label, the label maps written for the viewer
+// (--save_nii), and the counts of a label map against the label (effq_label_tallies, the score of a map cleaned by
+// --post).  All three stream HBM once and do no arithmetic to speak of.
 //
-// Windows: along each axis the starts are  min(i * (patch - overlap), size - patch)  for i = 0 .. n-1 with
-// n = ceil((size - patch) / (patch - overlap)) + 1, i.e. evaluate.window_starts: steps while a whole patch ends strictly
-// before the border, then one patch flush with it.  Windows are numbered in (d, h, w) raster order.
-//
-// Stitch: one thread per output voxel adds the covering windows in raster order onto 0.0f and divides once by their
-// count - the addends, the order and the rounding of evaluate.patch_to_image3d, so the result is the same bits.
 // Tallies: wave reductions into per-block partials, summed in block order by a second launch; integer counts only.
 #include "common.h"
 #include "seg_decide.h"
-#include "seg_window.h"      // WinAxes, win_start, make_axes, grid_for, STITCH_MAX_C: shared with window_blend.hip
+#include "seg_window.h"      // grid_for
 
 namespace effq {
-
-// ---- gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1 -------------
-template <int VEC>
-__global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ vol, float* __restrict__ out, WinAxes a,
-                                                       int N, int C, int first, uint32_t total) {
-  const size_t plane = (size_t)a.D * a.H * a.W;
-  // 32-bit index arithmetic (the entry point bounds `total`): 64-bit division is a long software sequence on the GPU
-  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    uint32_t r = e;
-    const int x = (int)(r % a.pw); r /= a.pw;
-    const int y = (int)(r % a.ph); r /= a.ph;
-    const int z = (int)(r % a.pd); r /= a.pd;
-    const int n = (int)(r % N);
-    const int win = first + (int)(r / N);
-    const int k = win % a.nw, j = (win / a.nw) % a.nh, i = win / (a.nw * a.nh);
-    const int d = win_start(i, a.D, a.pd, a.sd) + z;
-    const int h = win_start(j, a.H, a.ph, a.sh) + y;
-    const int w = win_start(k, a.W, a.pw, a.sw) + x;
-    // lanes of a wave hold consecutive x: every channel plane is read coalesced, every voxel written as C contiguous floats
-    const float* src = vol + (size_t)n * C * plane + ((size_t)d * a.H + h) * a.W + w;
-    float* dst = out + (size_t)e * C;
-    for (int c = 0; c < C; c += VEC) {
-      if constexpr (VEC == 4) {
-        float4 v;
-        v.x = src[(size_t)c * plane];
-        v.y = src[(size_t)(c + 1) * plane];
-        v.z = src[(size_t)(c + 2) * plane];
-        v.w = src[(size_t)(c + 3) * plane];
-        *reinterpret_cast<float4*>(dst + c) = v;
-      } else {
-        dst[c] = src[(size_t)c * plane];
-      }
-    }
-  }
-}
-
-// ---- stitch: win (nwin, N, pd, ph, pw, C) -> out (N, C, D, H, W) --------------------------------------------------
-__global__ __launch_bounds__(256) void k_window_stitch(const float* __restrict__ win, float* __restrict__ out, WinAxes a,
-                                                       int N, int C, uint32_t total) {
-  const size_t plane = (size_t)a.D * a.H * a.W;
-  const size_t wvox = (size_t)a.pd * a.ph * a.pw;
-  for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    uint32_t r = e;
-    const int w = (int)(r % a.W); r /= a.W;
-    const int h = (int)(r % a.H); r /= a.H;
-    const int d = (int)(r % a.D);
-    const int n = (int)(r / a.D);
-    float acc[STITCH_MAX_C];
-#pragma unroll
-    for (int c = 0; c < STITCH_MAX_C; ++c) acc[c] = 0.0f;
-    int cnt = 0;
-    for (int i = 0; i < a.nd; ++i) {
-      const int z = d - win_start(i, a.D, a.pd, a.sd);
-      if (z < 0 || z >= a.pd) continue;
-      for (int j = 0; j < a.nh; ++j) {
-        const int y = h - win_start(j, a.H, a.ph, a.sh);
-        if (y < 0 || y >= a.ph) continue;
-        for (int k = 0; k < a.nw; ++k) {
-          const int x = w - win_start(k, a.W, a.pw, a.sw);
-          if (x < 0 || x >= a.pw) continue;
-          const size_t widx = ((size_t)(i * a.nh + j) * a.nw + k) * N + n;
-          const float* src = win + ((widx * wvox) + ((size_t)z * a.ph + y) * a.pw + x) * C;
-#pragma unroll
-          for (int c = 0; c < STITCH_MAX_C; ++c)
-            if (c < C) acc[c] = acc[c] + src[c];
-          ++cnt;
-        }
-      }
-    }
-    const float fc = (float)cnt;
-    float* dst = out + (size_t)n * C * plane + ((size_t)d * a.H + h) * a.W + w;
-#pragma unroll
-    for (int c = 0; c < STITCH_MAX_C; ++c)
-      if (c < C) dst[(size_t)c * plane] = acc[c] / fc;
-  }
-}
 
 // ---- tallies ------------------------------------------------------------------------------------------------------
 // per class three counters: true positives, predicted positives, labelled positives (FP, FN and TN follow from them)
@@ -403,38 +320,6 @@ static void launch_tallies(int mode, bool v4, dim3 g, dim3 b, hipStream_t st, co
 using namespace effq;
 
 extern "C" {
-
-int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                       int ow, int first, int count, float* out, void* stream) {
-  EFFQ_CHECK_ARG(vol && out && N > 0 && C > 0 && D > 0 && H > 0 && W > 0);
-  WinAxes a;
-  EFFQ_CHECK_ARG(make_axes(D, H, W, pd, ph, pw, od, oh, ow, a));
-  EFFQ_CHECK_ARG(first >= 0 && count > 0 && (long long)first + count <= (long long)a.nd * a.nh * a.nw);
-  const size_t total = (size_t)count * N * pd * ph * pw;
-  EFFQ_CHECK_ARG(total < (1u << 31));
-  const bool v4 = C % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  if (v4)
-    hipLaunchKernelGGL(k_window_gather<4>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
-                       N, C, first, (uint32_t)total);
-  else
-    hipLaunchKernelGGL(k_window_gather<1>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
-                       N, C, first, (uint32_t)total);
-  EFFQ_LAUNCH_CHECK();
-  return EFFQ_OK;
-}
-
-int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                       int ow, float* out, void* stream) {
-  EFFQ_CHECK_ARG(win && out && N > 0 && C > 0 && C <= STITCH_MAX_C && D > 0 && H > 0 && W > 0);
-  WinAxes a;
-  EFFQ_CHECK_ARG(make_axes(D, H, W, pd, ph, pw, od, oh, ow, a));
-  const size_t total = (size_t)N * D * H * W;
-  EFFQ_CHECK_ARG(total < (1u << 31));
-  hipLaunchKernelGGL(k_window_stitch, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), win, out, a, N,
-                     C, (uint32_t)total);
-  EFFQ_LAUNCH_CHECK();
-  return EFFQ_OK;
-}
 
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream) {

@@ -1,5 +1,5 @@
-// The sliding-window rule shared by seg_eval.hip (gather, stitch) and window_blend.hip (flipped gather, put, weighted
-// stitch): one definition of the window starts, the raster numbering and the argument checks.
+// The sliding-window rule of window.hip (gather, put, stitch): one definition of the window starts, the raster numbering
+// and the argument checks.  seg_eval.hip sizes its grids with grid_for.
 //
 // Windows: along each axis the starts are  min(i * (patch - overlap), size - patch)  for i = 0 .. n-1 with
 // n = ceil((size - patch) / (patch - overlap)) + 1, i.e. evaluate.window_starts: steps while a whole patch ends strictly

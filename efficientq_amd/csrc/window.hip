@@ -1,15 +1,16 @@
-// Centre-weighted blending and mirror test-time augmentation of the sliding window (evaluate.stitched_window_logits with
-// blend / flips).  Three streaming kernels beside seg_eval.hip's gather and stitch, with its window
-// rule (seg_window.h):
+// The sliding window of evaluate.stitched_window_logits (validate_seg, the predict mission): three
+// streaming kernels over the window rule of seg_window.h.
 //
-//   gather_flip     the windows of a volume, each mirrored along the axes of a flip mask, as one channels-last batch
-//   put             the network's last head (NCDHW) un-mirrored into the channels-last window buffer, stored or added
-//   stitch_weighted the buffer stitched with a separable per-axis weight and divided by (passes * weight sum)
+//   gather  the windows of a volume, each mirrored along the axes of a flip mask, as one channels-last batch
+//   put     the network's last head (NCDHW) un-mirrored into the channels-last window buffer, stored or added
+//   stitch  the buffer stitched back to the volume: the sum of the covering windows over their count, or with a
+//           separable per-axis weight over the weight sum; either divided by the number of passes in the buffer
 //
 // A flip mask is 0..7: bit 0 mirrors d, bit 1 mirrors h, bit 2 mirrors w; a mirrored axis maps window-local z to p-1-z.
 // Every destination element has one owner thread, the covering windows are added in raster order and nothing is reduced
 // across threads: no atomics, equal inputs give equal bits.  32-bit index arithmetic on the per-element path (the entry
-// points bound the element counts below 2^31); bounded loops; no workgroup waits for another.
+// points bound the element counts below 2^31: 64-bit division is a long software sequence on the GPU); bounded loops;
+// no workgroup waits for another.
 #include "common.h"
 #include "seg_window.h"
 
@@ -17,11 +18,10 @@ namespace effq {
 
 __device__ __forceinline__ int mirror(int z, int p, int on) { return on ? p - 1 - z : z; }
 
-// ---- gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), the content of every window mirrored -----------
+// ---- gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1, mirrored ----
 template <int VEC>
-__global__ __launch_bounds__(256) void k_window_gather_flip(const float* __restrict__ vol, float* __restrict__ out,
-                                                            WinAxes a, int N, int C, int first, int flip,
-                                                            uint32_t total) {
+__global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ vol, float* __restrict__ out, WinAxes a,
+                                                       int N, int C, int first, int flip, uint32_t total) {
   const size_t plane = (size_t)a.D * a.H * a.W;
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     uint32_t r = e;
@@ -90,15 +90,22 @@ __global__ __launch_bounds__(256) void k_window_put(const float* __restrict__ sr
   }
 }
 
-// ---- weighted stitch: win (nwin, N, pd, ph, pw, C) -> out (N, C, D, H, W) -----------------------------------------
-// k_window_stitch with every addend scaled by (wd[z] wh[y]) ww[x] and the sum divided by nflip times the weight sum.
-// With weights 1.0f and nflip 1 every product is the addend itself and the weight sum is the count: the bits of
-// k_window_stitch.
-__global__ __launch_bounds__(256) void k_window_stitch_weighted(const float* __restrict__ win,
-                                                                const float* __restrict__ wd,
-                                                                const float* __restrict__ wh,
-                                                                const float* __restrict__ ww, float* __restrict__ out,
-                                                                WinAxes a, int N, int C, float fn, uint32_t total) {
+// ---- stitch: win (nwin, N, pd, ph, pw, C) -> out (N, C, D, H, W) --------------------------------------------------
+// One thread per output voxel adds the covering windows in raster order onto 0.0f and divides once.  Unweighted: the
+// addends, the order and the rounding of evaluate.patch_to_image3d over fn times their count.  WEIGHTED: every addend
+// scaled by (wd[z] wh[y]) ww[x], over fn times the weight sum; with weights 1.0f every product is the addend itself and
+// the weight sum is the exact count, so the two instances give equal bits.
+//
+// The loops keep the window rule and the hoisted `c < C` masks in scalar registers, and the scalar registers, not the
+// vector ones, set the occupancy here: they are handed out in blocks of 16, so the 98 the unweighted instance would take
+// (104 the weighted one) cost the eighth wave per SIMD that 96 still has - measured on the (512, 512, 200) volume as
+// 0.94 ms against 0.85 ms, and 1.19 ms against 1.08 ms.  Hence the cap: the compiler moves 2 (8) of them into lanes of
+// a vector register, no scratch, and both instances run 8 waves.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96)))
+void k_window_stitch(const float* __restrict__ win, const float* __restrict__ wd, const float* __restrict__ wh,
+                     const float* __restrict__ ww, float* __restrict__ out, WinAxes a, int N, int C, float fn,
+                     uint32_t total) {
   const size_t plane = (size_t)a.D * a.H * a.W;
   const size_t wvox = (size_t)a.pd * a.ph * a.pw;
   for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
@@ -111,28 +118,38 @@ __global__ __launch_bounds__(256) void k_window_stitch_weighted(const float* __r
 #pragma unroll
     for (int c = 0; c < STITCH_MAX_C; ++c) acc[c] = 0.0f;
     float wsum = 0.0f;
+    int cnt = 0;
     for (int i = 0; i < a.nd; ++i) {
       const int z = d - win_start(i, a.D, a.pd, a.sd);
       if (z < 0 || z >= a.pd) continue;
-      const float gz = wd[z];
+      float gz = 1.0f;
+      if constexpr (WEIGHTED) gz = wd[z];
       for (int j = 0; j < a.nh; ++j) {
         const int y = h - win_start(j, a.H, a.ph, a.sh);
         if (y < 0 || y >= a.ph) continue;
-        const float gzy = gz * wh[y];
+        float gzy = gz;
+        if constexpr (WEIGHTED) gzy = gz * wh[y];
         for (int k = 0; k < a.nw; ++k) {
           const int x = w - win_start(k, a.W, a.pw, a.sw);
           if (x < 0 || x >= a.pw) continue;
-          const float wgt = gzy * ww[x];
           const size_t widx = ((size_t)(i * a.nh + j) * a.nw + k) * N + n;
           const float* src = win + ((widx * wvox) + ((size_t)z * a.ph + y) * a.pw + x) * C;
+          if constexpr (WEIGHTED) {
+            const float wgt = gzy * ww[x];
 #pragma unroll
-          for (int c = 0; c < STITCH_MAX_C; ++c)
-            if (c < C) acc[c] = acc[c] + wgt * src[c];
-          wsum = wsum + wgt;
+            for (int c = 0; c < STITCH_MAX_C; ++c)
+              if (c < C) acc[c] = acc[c] + wgt * src[c];
+            wsum = wsum + wgt;
+          } else {
+#pragma unroll
+            for (int c = 0; c < STITCH_MAX_C; ++c)
+              if (c < C) acc[c] = acc[c] + src[c];
+            ++cnt;
+          }
         }
       }
     }
-    const float den = fn * wsum;
+    const float den = fn * (WEIGHTED ? wsum : (float)cnt);
     float* dst = out + (size_t)n * C * plane + ((size_t)d * a.H + h) * a.W + w;
 #pragma unroll
     for (int c = 0; c < STITCH_MAX_C; ++c)
@@ -154,8 +171,8 @@ using namespace effq;
 
 extern "C" {
 
-int effq_window_gather_flip(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                            int ow, int first, int count, int flip, float* out, void* stream) {
+int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, int first, int count, int flip, float* out, void* stream) {
   EFFQ_CHECK_ARG(vol && out && N > 0 && C > 0 && D > 0 && H > 0 && W > 0);
   EFFQ_CHECK_ARG(flip >= 0 && flip <= 7);
   WinAxes a;
@@ -165,11 +182,11 @@ int effq_window_gather_flip(const float* vol, int N, int C, int D, int H, int W,
   EFFQ_CHECK_ARG(total < (1u << 31));
   const bool v4 = C % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   if (v4)
-    hipLaunchKernelGGL(k_window_gather_flip<4>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol,
-                       out, a, N, C, first, flip, (uint32_t)total);
+    hipLaunchKernelGGL(k_window_gather<4>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
+                       N, C, first, flip, (uint32_t)total);
   else
-    hipLaunchKernelGGL(k_window_gather_flip<1>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol,
-                       out, a, N, C, first, flip, (uint32_t)total);
+    hipLaunchKernelGGL(k_window_gather<1>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), vol, out, a,
+                       N, C, first, flip, (uint32_t)total);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }
@@ -192,17 +209,21 @@ int effq_window_put(const float* src, int count, int C, int pd, int ph, int pw, 
   return EFFQ_OK;
 }
 
-int effq_window_stitch_weighted(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od,
-                                int oh, int ow, const float* wd, const float* wh, const float* ww, int nflip, float* out,
-                                void* stream) {
+int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, const float* wd, const float* wh, const float* ww, int nflip, float* out, void* stream) {
   EFFQ_CHECK_ARG(win && out && N > 0 && C > 0 && C <= STITCH_MAX_C && D > 0 && H > 0 && W > 0);
-  EFFQ_CHECK_ARG(wd && wh && ww && nflip >= 1);
+  const bool weighted = wd && wh && ww;
+  EFFQ_CHECK_ARG((weighted || (!wd && !wh && !ww)) && nflip >= 1);
   WinAxes a;
   EFFQ_CHECK_ARG(make_axes(D, H, W, pd, ph, pw, od, oh, ow, a));
   const size_t total = (size_t)N * D * H * W;
   EFFQ_CHECK_ARG(total < (1u << 31));
-  hipLaunchKernelGGL(k_window_stitch_weighted, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), win, wd,
-                     wh, ww, out, a, N, C, (float)nflip, (uint32_t)total);
+  if (weighted)
+    hipLaunchKernelGGL(k_window_stitch<true>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), win, wd,
+                       wh, ww, out, a, N, C, (float)nflip, (uint32_t)total);
+  else
+    hipLaunchKernelGGL(k_window_stitch<false>, dim3(grid_for(total, 1 << 16)), dim3(256), 0, as_stream(stream), win, wd,
+                       wh, ww, out, a, N, C, (float)nflip, (uint32_t)total);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

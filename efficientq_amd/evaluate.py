@@ -17,6 +17,8 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
+from .hip_ops import BLEND_KINDS         # --blend: the window weights of the stitch (hip_ops.blend_weights_host)
+
 
 def _triple(v):
     return (v, v, v) if isinstance(v, int) else tuple(int(i) for i in v)
@@ -308,7 +310,6 @@ def _vs_fp(ops, q, f, kind, fuse, shape, spacing, lesions, surface, want_map) ->
     return out
 
 
-BLEND_KINDS = ("uniform", "gauss")       # --blend: the window weights of the stitch (hip_ops.blend_weights_host)
 MIRROR_AXES = "dhw"                      # --tta_mirror: bit i of a flip mask mirrors axis MIRROR_AXES[i]
 
 
@@ -337,24 +338,21 @@ def check_flips(flips) -> tuple:
 def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_batch=None, blend="uniform",
                            flips=(0,)):
     """The sliding-window forward of validate_seg and of the `predict` mission: the windows of `vol` (N x C x D x H x W
-    fp32 on the device of `ops`) gathered into batches of `window_batch` (effq_window_gather), every network of `nets`
-    run on each batch, its last head copied into the network's window buffer and the buffer stitched
-    (effq_window_stitch).  window_batch=None: the first window runs alone and its peak memory - over all the forwards
-    of `nets` - sizes the batches, half the free device memory at most WINDOW_BATCH_MAX windows.  Returns (one stitched
-    N x classes x D x H x W tensor per network, the number of windows, the window batch in use): a caller hands the
-    last back in for its next volume.
+    fp32 on the device of `ops`) gathered into batches of `window_batch`, once per mask of `flips` and mirrored by it
+    (effq_window_gather); every network of `nets` run on each; its last head un-mirrored into the network's window
+    buffer, the first pass stored and the others added, so the buffer keeps its size (effq_window_put); and the buffer
+    stitched and divided by the number of passes (effq_window_stitch): the logits are averaged, not the probabilities.
+    window_batch=None: the first window runs alone and its peak memory - over all the forwards of `nets` - sizes the
+    batches, half the free device memory at most WINDOW_BATCH_MAX windows.  Returns (one stitched N x classes x D x H x
+    W tensor per network, the number of windows, the window batch in use): a caller hands the last back in for its next
+    volume.
     blend: "uniform" (every covering window counts alike) or "gauss" (a window's voxels are weighted by a separable
     Gaussian of sigma = patch / 8 around its centre, hip_ops.blend_weights_host).  flips: the flip masks of mirror
-    test-time augmentation (mirror_flips), ascending; every batch runs once per mask, mirrored (effq_window_gather_flip),
-    and effq_window_put un-mirrors the last head into the window buffer, storing the first pass and adding the others,
-    so the buffer keeps its size.  The buffer is then stitched with the weights and divided by the number of passes
-    (effq_window_stitch_weighted): the logits are averaged, not the probabilities.  With the defaults exactly the
-    statements above run."""
+    test-time augmentation (mirror_flips), ascending."""
     from .hip_ops import from_ndhwc
     if blend not in BLEND_KINDS:
         raise ValueError(f"blend {blend!r}: one of {', '.join(BLEND_KINDS)}")
     flips = check_flips(flips)
-    plain = blend == "uniform" and flips == (0,)
     dev = vol.device
     p, o = _triple(patch), _triple(overlap)
     bsz = window_batch
@@ -370,34 +368,23 @@ def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_
             torch.cuda.synchronize(dev)
             base = torch.cuda.memory_allocated(dev)
             torch.cuda.reset_peak_memory_stats(dev)
-        if plain:
-            x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt))
-            for k, net in enumerate(nets):      # the peak below covers every forward
+        for m in flips:                         # the peak below covers every forward of every pass
+            x = from_ndhwc(ops.window_gather(vol, p, o, first, cnt, m))
+            for k, net in enumerate(nets):
                 last = _last_head(net(x))
                 if bufs[k] is None:
                     bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-                bufs[k][first * N:(first + cnt) * N].copy_(last.permute(0, 2, 3, 4, 1))
+                ops.window_put(last, bufs[k][first * N:(first + cnt) * N], m, m != flips[0])
                 del last
-        else:
-            for m in flips:                     # the peak below covers every forward of every pass
-                x = from_ndhwc(ops.window_gather_flip(vol, p, o, first, cnt, m))
-                for k, net in enumerate(nets):
-                    last = _last_head(net(x))
-                    if bufs[k] is None:
-                        bufs[k] = torch.empty(nwin * N, *p, int(last.shape[1]), dtype=torch.float32, device=dev)
-                    ops.window_put(last, bufs[k][first * N:(first + cnt) * N], m, m != flips[0])
-                    del last
-                del x
+            del x
         if bsz is None:
             per = max(1, torch.cuda.max_memory_allocated(dev) - base)
             free, _ = torch.cuda.mem_get_info(dev)
             bsz = int(max(1, min(WINDOW_BATCH_MAX, free // 2 // per)))
         first += cnt
     full = (N,) + tuple(bufs[0].shape[-1:]) + tuple(vol.shape[-3:])
-    if plain:
-        return [ops.window_stitch(b, full, p, o) for b in bufs], nwin, bsz
-    weights = ops.blend_weights(p, blend)
-    return [ops.window_stitch_weighted(b, full, p, o, weights, len(flips)) for b in bufs], nwin, bsz
+    weights = None if blend == "uniform" else ops.blend_weights(p, blend)
+    return [ops.window_stitch(b, full, p, o, weights, len(flips)) for b in bufs], nwin, bsz
 
 
 @torch.no_grad()

@@ -141,29 +141,12 @@ class HipOps:
         self._red_ws = torch.zeros(self.lib.effq_reduce_ws_bytes(), dtype=torch.uint8, device=device)
         self._ws = {}
         self._att_cache = {}
-        self._pinned_stream = None
-        self._pinned_torch = None
         self._ws_retired = []
 
     # -- plumbing ---------------------------------------------------------------------------
     @property
     def stream(self):
-        # looking the current stream up through torch costs ~4 us per op; a caller that issues hundreds of ops on
-        # a known stream pins it with on_stream()
-        if self._pinned_stream is not None:
-            return self._pinned_stream
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def on_stream(self, stream: Optional["torch.cuda.Stream"]):
-        """Pin the HIP stream the following ops launch on (None: follow torch's current stream again).
-        Returns the previous pin so that callers can restore it."""
-        prev = (self._pinned_stream, self._pinned_torch)
-        self._pinned_stream = None if stream is None else C.c_void_p(stream.cuda_stream)
-        self._pinned_torch = stream
-        return prev
-
-    def restore_stream(self, pin):
-        self._pinned_stream, self._pinned_torch = pin if pin is not None else (None, None)
 
     def loss_stream(self):
         """The stream the per-iteration loss evaluation runs on, one iteration behind the ADMM chain."""
@@ -200,33 +183,26 @@ class HipOps:
         self._warm = True
 
     def _workspace(self, key: str, nbytes: int) -> torch.Tensor:
-        """Library workspace `key`, zero-filled when (re)allocated.  The fill is issued on the stream the NEXT op
-        launches on (the pinned stream when one is set): a fill on torch's current stream would race with kernels
-        of a pinned loss stream that only waited for an event recorded before the fill.  A replaced buffer stays
+        """Library workspace `key`, zero-filled on the current stream when (re)allocated.  A replaced buffer stays
         referenced until release_retired() (kernels of another stream may still be reading it, and the caching
         allocator only orders a block against the stream it was allocated on)."""
         cur = self._ws.get(key)
         if cur is None or cur.numel() < nbytes:
             if cur is not None:
                 self._ws_retired.append(cur)
-            if self._pinned_torch is not None:
-                with torch.cuda.stream(self._pinned_torch):
-                    cur = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
-            else:
-                cur = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
+            cur = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
             self._ws[key] = cur
         return cur
-
-    def reserve(self, key: str, nbytes: int):
-        """Size workspace `key` ahead of a multi-stream section (on the current stream, before its events)."""
-        self._workspace(key, nbytes)
 
     def release_retired(self):
         """Drop replaced workspaces; call only where every stream of this handle has been joined."""
         self._ws_retired.clear()
 
+    def _elsewhere(self, t: torch.Tensor) -> bool:
+        return t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index))
+
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
-        if t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index)):
+        if self._elsewhere(t):
             raise _lib.EffqError(f"tensor on {t.device}, ops on {self.device}")
         if t.dtype != torch.float32:
             raise _lib.EffqError(f"expected float32, got {t.dtype}")
@@ -1095,109 +1071,93 @@ class HipOps:
             n.append(len(range(0, s - p, p - o)) + 1)
         return tuple(n)
 
-    def window_gather(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None):
+    def _window_case(self, shape, patch, overlap):
+        """(N, C, D, H, W, patch, overlap, number of windows) of the N x C x D x H x W volume `shape`, window_grid's
+        refusals applied."""
+        N, Cc, D, H, W = (int(i) for i in shape)
+        p, o = _triple(patch), _triple(overlap)
+        return N, Cc, D, H, W, p, o, math.prod(self.window_grid((D, H, W), p, o))
+
+    @staticmethod
+    def _window_channels(what: str, Cc: int):
+        if not 0 < Cc <= 8:
+            raise _lib.EffqError(f"{what}: {Cc} channels, at most 8")
+
+    def window_gather(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None,
+                      flip: int = 0):
         """Windows first .. first+count-1 of the N x C x D x H x W volume as one (count*N, pd, ph, pw, C)
-        channels-last batch, window-major (effq_window_gather)."""
+        channels-last batch, window-major, the content of every window mirrored along the axes of the mask `flip`
+        (bit 0 = d, bit 1 = h, bit 2 = w; effq_window_gather)."""
         x = self._f32(vol)
         if x.dim() != 5:
             raise _lib.EffqError(f"window_gather: expected N x C x D x H x W, got {tuple(x.shape)}")
-        N, Cc, D, H, W = (int(i) for i in x.shape)
-        p, o = _triple(patch), _triple(overlap)
-        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        flip = _flip_mask(flip, "window_gather")
+        N, Cc, D, H, W, p, o, nwin = self._window_case(x.shape, patch, overlap)
         count = nwin - first if count is None else int(count)
         if first < 0 or count <= 0 or first + count > nwin:
             raise _lib.EffqError(f"windows {first}..{first + count - 1} of {nwin}")
         out = torch.empty(count * N, p[0], p[1], p[2], Cc, dtype=torch.float32, device=self.device)
         check(self.lib.effq_window_gather(_ptr(x), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], int(first), count,
-                                          _ptr(out), self.stream), "effq_window_gather")
-        return out
-
-    def window_stitch(self, win: torch.Tensor, shape, patch, overlap) -> torch.Tensor:
-        """Every window's logits, (nwin*N, pd, ph, pw, C) channels-last and window-major, stitched to the N x C x D x H
-        x W volume `shape` as the mean over the covering windows (effq_window_stitch; evaluate.patch_to_image3d)."""
-        w = self._f32(win)
-        N, Cc, D, H, W = (int(i) for i in shape)
-        p, o = _triple(patch), _triple(overlap)
-        nwin = math.prod(self.window_grid((D, H, W), p, o))
-        if tuple(w.shape) != (nwin * N, p[0], p[1], p[2], Cc):
-            raise _lib.EffqError(f"window_stitch: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
-        if not 0 < Cc <= 8:
-            raise _lib.EffqError(f"window_stitch: {Cc} channels, at most 8")
-        out = torch.empty(N, Cc, D, H, W, dtype=torch.float32, device=self.device)
-        check(self.lib.effq_window_stitch(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], _ptr(out),
-                                          self.stream), "effq_window_stitch")
-        return out
-
-    # -- centre-weighted blending and mirror test-time augmentation (evaluate.stitched_window_logits) ------------
-    def window_gather_flip(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None,
-                           flip: int = 0):
-        """window_gather with the content of every window mirrored along the axes of the mask `flip` (bit 0 = d, bit 1
-        = h, bit 2 = w; effq_window_gather_flip).  flip = 0 gives window_gather's bits."""
-        x = self._f32(vol)
-        if x.dim() != 5:
-            raise _lib.EffqError(f"window_gather_flip: expected N x C x D x H x W, got {tuple(x.shape)}")
-        flip = _flip_mask(flip, "window_gather_flip")
-        N, Cc, D, H, W = (int(i) for i in x.shape)
-        p, o = _triple(patch), _triple(overlap)
-        nwin = math.prod(self.window_grid((D, H, W), p, o))
-        count = nwin - first if count is None else int(count)
-        if first < 0 or count <= 0 or first + count > nwin:
-            raise _lib.EffqError(f"windows {first}..{first + count - 1} of {nwin}")
-        out = torch.empty(count * N, p[0], p[1], p[2], Cc, dtype=torch.float32, device=self.device)
-        check(self.lib.effq_window_gather_flip(_ptr(x), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], int(first),
-                                               count, flip, _ptr(out), self.stream), "effq_window_gather_flip")
+                                          flip, _ptr(out), self.stream), "effq_window_gather")
         return out
 
     def window_put(self, last: torch.Tensor, buf_slice: torch.Tensor, flip: int = 0, accumulate: bool = False) -> None:
         """A network's last head `last` (M x C x pd x ph x pw, the windows of one batch mirrored by `flip`) into
         `buf_slice`, the M x pd x ph x pw x C slice of the stitch's window buffer: transposed to channels-last,
         un-mirrored, and stored (accumulate=False) or added onto what the slice holds (effq_window_put).  The slice is
-        written in place: it must be fp32, contiguous and on this device."""
-        src = self._f32(last)
-        if src.dim() != 5:
-            raise _lib.EffqError(f"window_put: expected M x C x pd x ph x pw, got {tuple(src.shape)}")
+        written in place: it must be fp32, contiguous and on this device.  A head with channels-last strides (from_ndhwc:
+        what the convs of this package return) stored with flip 0 is in the slice's layout already, and the bits are
+        copied device to device as they lie; for any other pass such a head is first made contiguous, which allocates
+        a tensor of its size."""
+        if last.dim() != 5:
+            raise _lib.EffqError(f"window_put: expected M x C x pd x ph x pw, got {tuple(last.shape)}")
         flip = _flip_mask(flip, "window_put")
-        M, Cc, pd, ph, pw = (int(i) for i in src.shape)
-        if not 0 < Cc <= 8:
-            raise _lib.EffqError(f"window_put: {Cc} channels, at most 8")
+        M, Cc, pd, ph, pw = (int(i) for i in last.shape)
+        self._window_channels("window_put", Cc)
         if tuple(buf_slice.shape) != (M, pd, ph, pw, Cc):
             raise _lib.EffqError(f"window_put: buffer slice {tuple(buf_slice.shape)}, the head needs {(M, pd, ph, pw, Cc)}")
         if self._f32(buf_slice) is not buf_slice:
             raise _lib.EffqError("window_put: the buffer slice is written in place and must be contiguous")
         if M * Cc * pd * ph * pw >= 1 << 31:
             raise _lib.EffqError(f"window_put: {M * Cc * pd * ph * pw} elements, fewer than 2^31 per call")
+        as_stored = last.permute(0, 2, 3, 4, 1)
+        if flip == 0 and not accumulate and not last.is_contiguous() and as_stored.is_contiguous():
+            buf_slice.copy_(self._f32(as_stored))           # _f32: the checks of device and dtype, no copy
+            return
+        src = self._f32(last)
         check(self.lib.effq_window_put(_ptr(src), M, Cc, pd, ph, pw, flip, int(bool(accumulate)), _ptr(buf_slice),
                                        self.stream), "effq_window_put")
 
-    def window_stitch_weighted(self, win: torch.Tensor, shape, patch, overlap, weights, nflip: int = 1) -> torch.Tensor:
-        """window_stitch with the separable per-axis `weights` (three fp32 device tensors of pd, ph, pw values:
-        blend_weights) on the sum of `nflip` passes in `win`: each voxel is the weighted sum over its covering windows
-        over (nflip * the sum of their weights) (effq_window_stitch_weighted).  Ones and nflip = 1: window_stitch's bits."""
+    def window_stitch(self, win: torch.Tensor, shape, patch, overlap, weights=None, nflip: int = 1) -> torch.Tensor:
+        """The window buffer, (nwin*N, pd, ph, pw, C) channels-last and window-major and holding the sum of `nflip`
+        passes, stitched to the N x C x D x H x W volume `shape` (effq_window_stitch).  weights=None: each voxel is the
+        sum over its covering windows over (nflip * their count); with nflip = 1 evaluate.patch_to_image3d.  Otherwise
+        the separable per-axis `weights` (three fp32 device tensors of pd, ph, pw values: blend_weights): the weighted
+        sum over (nflip * the sum of the weights).  Ones give the bits of None."""
         w = self._f32(win)
-        N, Cc, D, H, W = (int(i) for i in shape)
-        p, o = _triple(patch), _triple(overlap)
-        nwin = math.prod(self.window_grid((D, H, W), p, o))
+        N, Cc, D, H, W, p, o, nwin = self._window_case(shape, patch, overlap)
         if tuple(w.shape) != (nwin * N, p[0], p[1], p[2], Cc):
-            raise _lib.EffqError(f"window_stitch_weighted: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
-        if not 0 < Cc <= 8:
-            raise _lib.EffqError(f"window_stitch_weighted: {Cc} channels, at most 8")
+            raise _lib.EffqError(f"window_stitch: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
+        self._window_channels("window_stitch", Cc)
         if int(nflip) != nflip or nflip < 1:
-            raise _lib.EffqError(f"window_stitch_weighted: nflip {nflip!r}, the number of passes summed, is at least 1")
-        if len(weights) != 3:
-            raise _lib.EffqError(f"window_stitch_weighted: {len(weights)} weight tensors, one per axis d, h, w")
-        ws = [self._f32(t) for t in weights]
-        for t, n, ax in zip(ws, p, "dhw"):
-            if t.dim() != 1 or int(t.numel()) != n:
-                raise _lib.EffqError(f"window_stitch_weighted: weights of axis {ax} have shape {tuple(t.shape)}, the "
-                                     f"window needs ({n},)")
+            raise _lib.EffqError(f"window_stitch: nflip {nflip!r}, the number of passes summed, is at least 1")
+        ws = (None, None, None)
+        if weights is not None:
+            if len(weights) != 3:
+                raise _lib.EffqError(f"window_stitch: {len(weights)} weight tensors, one per axis d, h, w")
+            ws = [self._f32(t) for t in weights]
+            for t, n, ax in zip(ws, p, "dhw"):
+                if t.dim() != 1 or int(t.numel()) != n:
+                    raise _lib.EffqError(f"window_stitch: weights of axis {ax} have shape {tuple(t.shape)}, the window "
+                                         f"needs ({n},)")
         out = torch.empty(N, Cc, D, H, W, dtype=torch.float32, device=self.device)
-        check(self.lib.effq_window_stitch_weighted(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2],
-                                                   _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), int(nflip), _ptr(out),
-                                                   self.stream), "effq_window_stitch_weighted")
+        check(self.lib.effq_window_stitch(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], _ptr(ws[0]),
+                                          _ptr(ws[1]), _ptr(ws[2]), int(nflip), _ptr(out), self.stream),
+              "effq_window_stitch")
         return out
 
     def blend_weights(self, patch, kind: str = "uniform"):
-        """The three per-axis fp32 weight tensors of window_stitch_weighted on this device (blend_weights_host)."""
+        """The three per-axis fp32 weight tensors of window_stitch on this device (blend_weights_host)."""
         return tuple(torch.from_numpy(w).to(self.device) for w in blend_weights_host(patch, kind))
 
     def sigmoid_threshold(self) -> float:
@@ -1225,6 +1185,19 @@ class HipOps:
         self._sig_thresh = float(-torch.tensor([lo], dtype=torch.int32).view(torch.float32).item())
         return self._sig_thresh
 
+    @staticmethod
+    def _fuse_code(what: str, fuse, argmax: bool, by: str, Cc: int, rule: Optional[str] = None) -> int:
+        """The code of the merge type `fuse`, checked for a decision by argmax or by sigmoid (named `by` in the refusal),
+        together with the class count and, for the label rule 'brats', its three channels."""
+        key = fuse.lower() if isinstance(fuse, str) else fuse
+        if key not in _lib.SEG_FUSE or (argmax and key is not None):
+            raise _lib.EffqError(f"{what}: merge type {fuse!r} for {by}")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"{what}: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if rule == "brats" and Cc < 3:
+            raise _lib.EffqError(f"{what}: the brats rule needs 3 channels or more, got {Cc}")
+        return _lib.SEG_FUSE[key]
+
     def _seg_case(self, what: str, logits: torch.Tensor, label: torch.Tensor, task: str, fuse, spatial: bool):
         """The arguments of one case that seg_tallies, seg_lesions, seg_surface and seg_surface_mm share, checked:
         returns (x, lab, Cc, extents, mode, fuse code, thresh) - the fp32 logits, the contiguous label, the class count,
@@ -1240,23 +1213,18 @@ class HipOps:
             mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
         else:
             raise _lib.EffqError(f"Unknown task {task}")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (mode == _lib.SEG_ARGMAX and key is not None):
-            raise _lib.EffqError(f"{what}: merge type {fuse!r} for task {task}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"{what}: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        fcode = self._fuse_code(what, fuse, mode == _lib.SEG_ARGMAX, f"task {task}", Cc)
         if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
             raise _lib.EffqError(f"{what}: label {tuple(label.shape)} {label.dtype} on {label.device}, "
                                  f"needs {lshape} torch.uint8 on {x.device}")
-        return x, label.contiguous(), Cc, extents, mode, _lib.SEG_FUSE[key], thresh
+        return x, label.contiguous(), Cc, extents, mode, fcode, thresh
 
     def _mask_planes(self, what: str, mask: torch.Tensor):
         """(m, P, D, H, W) of the masks cc_label, edt_sq and edt_sq_mm take: D x H x W or P x D x H x W uint8, not empty,
         on the device of the ops; m is contiguous."""
         if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
             raise _lib.EffqError(f"{what}: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
-        if mask.device != self.device and not (mask.device.type == "cuda" and
-                                               self.device.index in (None, mask.device.index)):
+        if self._elsewhere(mask):
             raise _lib.EffqError(f"{what}: mask on {mask.device}, ops on {self.device}")
         m = mask.contiguous()
         D, H, W = (int(i) for i in m.shape[-3:])
@@ -1285,13 +1253,7 @@ class HipOps:
         N, Cc, S = int(x.shape[0]), int(x.shape[1]), math.prod(x.shape[2:])
         if rule not in _lib.SEG_LABEL_RULES:
             raise _lib.EffqError(f"seg_labels: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (rule == "argmax" and key is not None):
-            raise _lib.EffqError(f"seg_labels: merge type {fuse!r} for rule {rule}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_labels: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if rule == "brats" and Cc < 3:
-            raise _lib.EffqError(f"seg_labels: the brats rule needs 3 channels or more, got {Cc}")
+        fcode = self._fuse_code("seg_labels", fuse, rule == "argmax", f"rule {rule}", Cc, rule)
         if dtype not in (torch.uint8, torch.uint16) or (rule == "planes" and dtype != torch.uint8):
             raise _lib.EffqError(f"seg_labels: output {dtype} for rule {rule}")
         if N == 0 or S == 0 or N > 65535:
@@ -1299,7 +1261,7 @@ class HipOps:
         shape = tuple(x.shape) if rule == "planes" else (N,) + tuple(x.shape[2:])
         out = torch.empty(shape, dtype=dtype, device=self.device)
         thresh = 0.0 if rule == "argmax" else self.sigmoid_threshold()
-        check(self.lib.effq_seg_labels(_ptr(x), N, Cc, S, _lib.SEG_LABEL_RULES[rule], _lib.SEG_FUSE[key], thresh,
+        check(self.lib.effq_seg_labels(_ptr(x), N, Cc, S, _lib.SEG_LABEL_RULES[rule], fcode, thresh,
                                        out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
         return out
 
@@ -1317,13 +1279,7 @@ class HipOps:
         Cc = int(x.shape[0])
         if rule not in _lib.SEG_LABEL_RULES:
             raise _lib.EffqError(f"seg_labels_source: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (rule == "argmax" and key is not None):
-            raise _lib.EffqError(f"seg_labels_source: merge type {fuse!r} for rule {rule}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_labels_source: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if rule == "brats" and Cc < 3:
-            raise _lib.EffqError(f"seg_labels_source: the brats rule needs 3 channels or more, got {Cc}")
+        fcode = self._fuse_code("seg_labels_source", fuse, rule == "argmax", f"rule {rule}", Cc, rule)
         try:
             lo, G, src = (tuple(int(v) for v in t) for t in (pmin, grid, source_shape))
             f = (1.0, 1.0, 1.0) if factors is None else tuple(float(v) for v in factors)
@@ -1339,8 +1295,7 @@ class HipOps:
         i3 = C.c_int * 3
         check(self.lib.effq_seg_labels_source(_ptr(x), Cc, i3(*(int(v) for v in x.shape[1:])), i3(*lo), i3(*G),
                                               (C.c_double * 3)(*f), i3(*src), _lib.SEG_LABEL_RULES[rule],
-                                              _lib.SEG_FUSE[key], thresh, _ptr(out), self.stream),
-              "effq_seg_labels_source")
+                                              fcode, thresh, _ptr(out), self.stream), "effq_seg_labels_source")
         return out
 
     def seg_agreement(self, logits_q: torch.Tensor, logits_fp: torch.Tensor, mode: str, fuse: Optional[str] = None,
@@ -1367,18 +1322,14 @@ class HipOps:
                "brats": _lib.SEG_SIGMOID}.get(mode)
         if key is None:
             raise _lib.EffqError(f"seg_agreement: unknown mode {mode!r} (argmax or sigmoid)")
-        fkey = fuse.lower() if isinstance(fuse, str) else fuse
-        if fkey not in _lib.SEG_FUSE or (key == _lib.SEG_ARGMAX and fkey is not None):
-            raise _lib.EffqError(f"seg_agreement: merge type {fuse!r} for mode {mode}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_agreement: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        fcode = self._fuse_code("seg_agreement", fuse, key == _lib.SEG_ARGMAX, f"mode {mode}", Cc)
         thresh = 0.0 if key == _lib.SEG_ARGMAX else self.sigmoid_threshold()
         counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
         flips = torch.empty(1, dtype=torch.int64, device=self.device)
         stats = torch.empty(Cc, 4, dtype=torch.float64, device=self.device)
         vmap = torch.empty(tuple(q.shape[1:]), dtype=torch.uint8, device=self.device) if want_map else None
         ws = self._workspace("seg_agreement", _lib.SEG_AGREEMENT_WS_BYTES)
-        check(self.lib.effq_seg_agreement(_ptr(q), _ptr(f), Cc, S, key, _lib.SEG_FUSE[fkey], thresh, _ptr(counts),
+        check(self.lib.effq_seg_agreement(_ptr(q), _ptr(f), Cc, S, key, fcode, thresh, _ptr(counts),
                                           _ptr(flips), _ptr(stats), _ptr(vmap), _ptr(ws), ws.numel(), self.stream),
               "effq_seg_agreement")
         return counts, flips, stats, vmap
@@ -1546,7 +1497,7 @@ class HipOps:
             raise _lib.EffqError(f"label_tallies: truth {tuple(truth.shape)} for a map {tuple(pred.shape)}: needs the "
                                  f"map's shape, or {Cc} planes of it")
         for t, who in ((pred, "pred"), (truth, "truth")):
-            if t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index)):
+            if self._elsewhere(t):
                 raise _lib.EffqError(f"label_tallies: {who} on {t.device}, ops on {self.device}")
         try:
             table = [int(v) for v in lut]
@@ -1659,9 +1610,6 @@ class HipOps:
             raise _lib.EffqError(f"{what}: shape {tuple(x.shape)}: at most {_lib.PREP_MAX_MODALITIES} modalities, 2^31 - 1 "
                                  f"voxels in all and 32767 along an axis")
         return x, Cc, D, H, W
-
-    def _elsewhere(self, t: torch.Tensor) -> bool:
-        return t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index))
 
     @staticmethod
     def _prep_mask(what: str, mask: str) -> int:

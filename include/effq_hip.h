@@ -588,9 +588,22 @@ int effq_unpack_levels(const uint8_t* packed, size_t n, int bits, uint8_t* idx, 
  * while a whole window still ends strictly before the border, then one window lies flush with it; windows are numbered
  * in (d, h, w) raster order (evaluate.window_starts / image_to_patch3d).
  *
- * Gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1, channels-last.
- * Stitch: win (nwin, N, pd, ph, pw, C) holding every window -> out (N, C, D, H, W): each voxel is the sum of its
- *   covering windows in raster order over their count, bit for bit evaluate.patch_to_image3d.  C <= 8.
+ * A flip mask is 0..7: bit 0 mirrors d, bit 1 mirrors h, bit 2 mirrors w; a mirrored axis maps window-local index z to
+ * p - 1 - z.  The three window entry points (window.hip) have one owner thread per destination element and no atomics:
+ * equal inputs give equal bits.
+ *
+ * Gather: vol (N, C, D, H, W) -> out (count, N, pd, ph, pw, C), windows first .. first + count - 1, channels-last, the
+ *   content of every window mirrored along the axes of `flip`.  flip outside 0..7: EFFQ_ERR_ARG.
+ * Put: src (count, C, pd, ph, pw), a network's last head with count = windows * N, un-mirrored into dst (count, pd, ph,
+ *   pw, C), a slice of the stitch's window buffer:  dst[m, z, y, x, c] = (accumulate ? dst[m, z, y, x, c] : 0) +
+ *   src[m, c, flip(z), flip(y), flip(x)], one fp32 add; accumulate = 0 copies the bits.  C <= 8, count C pd ph pw < 2^31.
+ * Stitch: win (nwin, N, pd, ph, pw, C) holding the sum of nflip >= 1 passes over every window -> out (N, C, D, H, W),
+ *   C <= 8.  wd, wh, ww all NULL: each voxel is the sum of its covering windows in raster order over ((float)nflip times
+ *   their count); with nflip = 1 bit for bit evaluate.patch_to_image3d.  All three given, pd, ph, pw fp32 per-axis
+ *   weights on the device: over the covering windows in raster order  wgt = (wd[z] wh[y]) ww[x], acc[c] += wgt win[..],
+ *   wsum += wgt  in fp32, then out = acc[c] / ((float)nflip wsum).  With all weights 1.0f and any nflip that is the bits
+ *   of the unweighted stitch (every product is its addend, the weight sum is the exact count).  Some but not all of
+ *   wd, wh, ww NULL, nflip < 1 or C > 8: EFFQ_ERR_ARG.
  * Tallies: logits (C, S) of one case and its label -> counts (C, 4) int64 = TP, FP, FN, TN per class.
  *   EFFQ_SEG_ARGMAX: label (S) class ids; prediction = the first largest channel (torch.max).
  *   EFFQ_SEG_SIGMOID: label (C, S) 0/1; channel c predicted when logit >= thresh, where thresh is the least float at
@@ -601,27 +614,11 @@ int effq_unpack_levels(const uint8_t* packed, size_t n, int bits, uint8_t* idx, 
 enum { EFFQ_SEG_ARGMAX = 0, EFFQ_SEG_SIGMOID = 1 };
 enum { EFFQ_SEG_FUSE_NONE = 0, EFFQ_SEG_FUSE_AGG = 1, EFFQ_SEG_FUSE_CON = 2 };
 int effq_window_gather(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                       int ow, int first, int count, float* out, void* stream);
-int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                       int ow, float* out, void* stream);
-/* Centre-weighted blending and mirror test-time augmentation of the sliding window (window_blend.hip).  A flip mask is
- * 0..7: bit 0 mirrors d, bit 1 mirrors h, bit 2 mirrors w; a mirrored axis maps window-local index z to p - 1 - z.
- * Gather, flipped: as the gather, the content of every window mirrored along the axes of `flip`; flip = 0 gives the
- *   gather's bits.
- * Put: src (count, C, pd, ph, pw), a network's last head with count = windows * N, un-mirrored into dst (count, pd, ph,
- *   pw, C), a slice of the stitch's window buffer:  dst[m, z, y, x, c] = (accumulate ? dst[m, z, y, x, c] : 0) +
- *   src[m, c, flip(z), flip(y), flip(x)], one fp32 add; accumulate = 0 copies the bits.  C <= 8, count C pd ph pw < 2^31.
- * Stitch, weighted: wd, wh, ww are pd, ph, pw fp32 per-axis weights on the device, nflip >= 1 the number of passes
- *   summed into win.  Over the covering windows in raster order  wgt = (wd[z] wh[y]) ww[x], acc[c] += wgt win[..],
- *   wsum += wgt  in fp32, then out = acc[c] / ((float)nflip wsum).  All weights 1.0f and nflip = 1: the stitch's bits.
- * One owner thread per destination element, no atomics: equal inputs give equal bits. */
-int effq_window_gather_flip(const float* vol, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
-                            int ow, int first, int count, int flip, float* out, void* stream);
+                       int ow, int first, int count, int flip, float* out, void* stream);
 int effq_window_put(const float* src, int count, int C, int pd, int ph, int pw, int flip, int accumulate, float* dst,
                     void* stream);
-int effq_window_stitch_weighted(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od,
-                                int oh, int ow, const float* wd, const float* wh, const float* ww, int nflip, float* out,
-                                void* stream);
+int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int pd, int ph, int pw, int od, int oh,
+                       int ow, const float* wd, const float* wh, const float* ww, int nflip, float* out, void* stream);
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream);
 

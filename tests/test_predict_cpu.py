@@ -83,12 +83,25 @@ class PredictOps(NumpyOps):
     def window_grid(dhw, patch, overlap):
         return tuple(len(E.window_starts(s, p, o)) for s, p, o in zip(dhw, patch, overlap))
 
-    def window_gather(self, vol, patch, overlap, first=0, count=None):
+    def window_gather(self, vol, patch, overlap, first=0, count=None, flip=0):
         pats = E.image_to_patch3d(vol, patch, overlap)
         pats = pats[first:] if count is None else pats[first:first + count]
-        return torch.cat([pt.permute(0, 2, 3, 4, 1) for pt in pats]).contiguous()
+        win = torch.cat([pt.permute(0, 2, 3, 4, 1) for pt in pats]).contiguous()
+        dims = [1 + b for b in range(3) if flip >> b & 1]
+        return torch.flip(win, dims).contiguous() if dims else win
 
-    def window_stitch(self, win, shape, patch, overlap):
+    def window_put(self, last, buf_slice, flip=0, accumulate=False):
+        assert buf_slice.is_contiguous()
+        dims = [1 + b for b in range(3) if flip >> b & 1]
+        v = last.permute(0, 2, 3, 4, 1)
+        v = torch.flip(v, dims) if dims else v
+        if accumulate:
+            buf_slice.add_(v)
+        else:
+            buf_slice.copy_(v)
+
+    def window_stitch(self, win, shape, patch, overlap, weights=None, nflip=1):
+        assert weights is None and nflip == 1       # the blend is tests.test_window_blend_cpu.BlendOps'
         N = int(shape[0])
         pats = [win[i * N:(i + 1) * N].permute(0, 4, 1, 2, 3) for i in range(win.shape[0] // N)]
         return E.patch_to_image3d(torch.empty(tuple(shape)), pats, patch, overlap).contiguous()

@@ -1,6 +1,6 @@
 """Gaussian window blending and mirror test-time augmentation, host side (no GPU): the switches and what they refuse,
 the axes -> flip-mask mapping, the Gaussian weights against their formula, the fp64 restatement of the whole blend
-(ref_blend, which the GPU tests compare the kernels with) pinned on a hand-computed case, the C-ABI rows of the new
+(ref_blend, which the GPU tests compare the kernels with) pinned on a hand-computed case, the C-ABI rows of the window
 symbols, and the `predict` mission through numpy / torch stand-ins for the device ops."""
 import csv
 import os
@@ -181,58 +181,47 @@ def test_header_and_lib_rows_of_the_new_symbols_have_matching_signatures():
 
     def ctype(decl):
         return _lib._P if "*" in decl else {"int": _lib._I, "float": _lib._F}[decl.split()[0]]
-    for name, nargs in (("effq_window_gather_flip", 17), ("effq_window_put", 10), ("effq_window_stitch_weighted", 18)):
+    for name, nargs in (("effq_window_gather", 17), ("effq_window_put", 10), ("effq_window_stitch", 18)):
         found = re.findall(r"\bint (%s)\s*\((.*?)\)\s*;" % name, code, flags=re.S)
         assert len(found) == 1, name
         res, got = _lib.SIGNATURES[name]
         assert res == _lib._I and got == [ctype(a) for a in found[0][1].split(",")] and len(got) == nargs, name
         assert hasattr(_lib.load(), name)
+    # and no other window symbol: the mirrored gather and the weighted stitch are these, not entry points of their own
+    three = {"effq_window_gather", "effq_window_put", "effq_window_stitch"}
+    assert set(re.findall(r"\beffq_window_\w+", hdr)) == three == {n for n in _lib.SIGNATURES if "_window_" in n}
     mk = open(os.path.join(ROOT, "efficientq_amd", "csrc", "Makefile")).read()
-    assert "window_blend.hip" in mk and "seg_window.h" in mk
-    src = open(os.path.join(ROOT, "efficientq_amd", "csrc", "window_blend.hip")).read()
+    assert " window.hip" in mk and "seg_window.h" in mk
+    src = open(os.path.join(ROOT, "efficientq_amd", "csrc", "window.hip")).read()
     assert not re.search(r"atomic\w*\s*\(", re.sub(r"//.*", "", src))       # one owner per element: no atomics at all
     assert '#include "seg_window.h"' in src
 
 
 # ---- the window function and the predict mission on the host ----------------------------------------------------------------
 class BlendOps(PredictOps):
-    """PredictOps with the three new window ops in torch on the host (fp32, the kernels' order of operations) and a
-    record of the calls."""
+    """PredictOps with the weighted stitch in fp64 on the host (ref_blend) and a record of the calls and their
+    arguments."""
 
     def __init__(self):
         super().__init__()
         self.calls = []
 
-    def window_gather(self, vol, patch, overlap, first=0, count=None):
-        self.calls.append(("gather", first))
-        return super().window_gather(vol, patch, overlap, first, count)
-
-    def window_stitch(self, win, shape, patch, overlap):
-        self.calls.append(("stitch",))
-        return super().window_stitch(win, shape, patch, overlap)
-
-    def window_gather_flip(self, vol, patch, overlap, first=0, count=None, flip=0):
-        self.calls.append(("gather_flip", first, flip))
-        win = PredictOps.window_gather(self, vol, patch, overlap, first, count)
-        dims = [1 + b for b in range(3) if flip >> b & 1]
-        return torch.flip(win, dims).contiguous() if dims else win
+    def window_gather(self, vol, patch, overlap, first=0, count=None, flip=0):
+        self.calls.append(("gather", first, flip))
+        return super().window_gather(vol, patch, overlap, first, count, flip)
 
     def window_put(self, last, buf_slice, flip=0, accumulate=False):
         self.calls.append(("put", flip, bool(accumulate)))
-        assert buf_slice.is_contiguous()
-        dims = [1 + b for b in range(3) if flip >> b & 1]
-        v = last.permute(0, 2, 3, 4, 1)
-        v = torch.flip(v, dims) if dims else v
-        if accumulate:
-            buf_slice.add_(v)
-        else:
-            buf_slice.copy_(v)
+        super().window_put(last, buf_slice, flip, accumulate)
 
     def blend_weights(self, patch, kind="uniform"):
         return tuple(torch.from_numpy(w) for w in hip_ops.blend_weights_host(patch, kind))
 
-    def window_stitch_weighted(self, win, shape, patch, overlap, weights, nflip=1):
-        self.calls.append(("stitch_weighted", nflip))
+    def window_stitch(self, win, shape, patch, overlap, weights=None, nflip=1):
+        self.calls.append(("stitch", weights is None, nflip))
+        if weights is None and nflip == 1:
+            return super().window_stitch(win, shape, patch, overlap)
+        weights = self.blend_weights(patch) if weights is None else weights
         out, _, _ = ref_blend([win.numpy()], [w.numpy() for w in weights], tuple(shape), patch, overlap)
         return torch.from_numpy((out / nflip).astype(np.float32))
 
@@ -245,24 +234,34 @@ class EdgeNet(torch.nn.Module):
         return torch.cat([x + 2.0 * left, x - left], 1)
 
 
+def _default_calls_are_one_plain_pass(calls):
+    """The record of a default run: every gather un-mirrored, every put a store of mask 0, every stitch without weights
+    over one pass - what was gather, copy_, stitch before the window function had one path."""
+    assert {c[0] for c in calls} == {"gather", "put", "stitch"}
+    assert all(c[2] == 0 for c in calls if c[0] == "gather")
+    assert all(c[1:] == (0, False) for c in calls if c[0] == "put")
+    assert all(c[1:] == (True, 1) for c in calls if c[0] == "stitch")
+
+
 def test_window_function_runs_todays_statements_by_default_and_the_passes_otherwise():
     g = torch.Generator().manual_seed(3)
     vol = torch.randn(2, 1, 9, 8, 11, generator=g)
     p, o = (4, 4, 6), (1, 2, 3)
     ops = BlendOps()
     base, nwin, _ = E.stitched_window_logits(ops, [EdgeNet()], vol, p, o, 5)
-    assert {c[0] for c in ops.calls} == {"gather", "stitch"} and nwin == 3 * 3 * 3
+    _default_calls_are_one_plain_pass(ops.calls)
+    assert nwin == 3 * 3 * 3
     want = E.sliding_window_forward(EdgeNet(), vol, p, o)[-1]
     assert torch.equal(base[0], want)
-    # every pass of every batch: flipped gather, forward, put - the first stored, the others added
+    # every pass of every batch: mirrored gather, forward, put - the first stored, the others added
     ops = BlendOps()
     flips = (0, 2, 4, 6)
     got, nwin, _ = E.stitched_window_logits(ops, [EdgeNet(), EdgeNet()], vol, p, o, 5, "gauss", flips)
-    assert {c[0] for c in ops.calls} == {"gather_flip", "put", "stitch_weighted"}
+    assert {c[0] for c in ops.calls} == {"gather", "put", "stitch"}
     batches = [0, 5, 10, 15, 20, 25]
-    assert [c[1:] for c in ops.calls if c[0] == "gather_flip"] == [(b, m) for b in batches for m in flips]
+    assert [c[1:] for c in ops.calls if c[0] == "gather"] == [(b, m) for b in batches for m in flips]
     assert [c[1:] for c in ops.calls if c[0] == "put"] == [(m, m != 0) for b in batches for m in flips for _ in range(2)]
-    assert [c for c in ops.calls if c[0] == "stitch_weighted"] == [("stitch_weighted", 4)] * 2
+    assert [c for c in ops.calls if c[0] == "stitch"] == [("stitch", False, 4)] * 2           # with weights, 4 passes
     assert torch.equal(got[0], got[1])
     # against the restatement of the whole pipeline in fp64
     net64, passes = EdgeNet().double(), []
@@ -276,6 +275,13 @@ def test_window_function_runs_todays_statements_by_default_and_the_passes_otherw
     err = np.abs(got[0].numpy() - ref)
     assert (err <= blend_bound(mag, cover, len(flips)) + 8 * 2.0 ** -24 * mag).all()      # + the fp32 forward and puts
     assert np.abs(ref - base[0].numpy()).max() > 0.05           # the passes and the weights changed the result
+    # uniform blending with mirror passes: no weights reach the stitch, the passes do
+    ops = BlendOps()
+    uni, _, _ = E.stitched_window_logits(ops, [EdgeNet()], vol, p, o, 5, "uniform", (0, 4))
+    assert [c for c in ops.calls if c[0] == "stitch"] == [("stitch", True, 2)]
+    assert [c[1:] for c in ops.calls if c[0] == "put"] == [(m, m != 0) for b in batches for m in (0, 4)]
+    ref, mag, cover = ref_blend(passes[:1] + passes[2:3], hip_ops.blend_weights_host(p, "uniform"), (2, 2, 9, 8, 11), p, o)
+    assert (np.abs(uni[0].numpy() - ref) <= blend_bound(mag, cover, 2) + 8 * 2.0 ** -24 * mag).all()
     for bad in (dict(blend="cosine"), dict(flips=()), dict(flips=(4, 0)), dict(flips=(0, 9))):
         with pytest.raises(ValueError):
             E.stitched_window_logits(BlendOps(), [EdgeNet()], vol, p, o, 5, **bad)
@@ -301,7 +307,7 @@ def test_predict_csv_is_unchanged_by_default_and_records_the_switches_otherwise(
         table = list(csv.reader(f))
     assert table[0] == predict.CSV_HEADER and "blend" not in table[0] and len(table) == 3
     assert predict.CSV_HEADER[-1] == "volume_ml" and len(predict.CSV_HEADER) == 15
-    assert {c[0] for c in ops.calls} == {"gather", "stitch"}
+    _default_calls_are_one_plain_pass(ops.calls)
     assert "blend" not in rows[0] and "tta_mirror" not in rows[0]
 
     rows2, out2, ops2 = _run_predict(tmp_path, "tta", "--blend", "gauss", "--tta_mirror", "hw")
@@ -310,8 +316,9 @@ def test_predict_csv_is_unchanged_by_default_and_records_the_switches_otherwise(
     table2 = list(csv.DictReader(open(os.path.join(out2, predict.PREDICT_CSV))))
     assert list(table2[0]) == predict.CSV_HEADER + ["blend", "tta_mirror"]
     assert [(r["blend"], r["tta_mirror"]) for r in table2] == [("gauss", "hw")] * 2
-    assert {c[0] for c in ops2.calls} == {"gather_flip", "put", "stitch_weighted"}
-    assert {c[2] for c in ops2.calls if c[0] == "gather_flip"} == {0, 2, 4, 6}
+    assert {c[0] for c in ops2.calls} == {"gather", "put", "stitch"}
+    assert {c[2] for c in ops2.calls if c[0] == "gather"} == {0, 2, 4, 6}
+    assert {c[1:] for c in ops2.calls if c[0] == "stitch"} == {(False, 4)}
     # every earlier column holds what it held (PointNet works voxel by voxel: the maps agree as well)
     for r, r2 in zip(rows, rows2):
         assert all(r[k] == r2[k] for k in predict.CSV_HEADER)
@@ -323,7 +330,8 @@ def test_predict_csv_is_unchanged_by_default_and_records_the_switches_otherwise(
     _, out4, ops4 = _run_predict(tmp_path, "g", blend="gauss")
     t4 = list(csv.DictReader(open(os.path.join(out4, predict.PREDICT_CSV))))
     assert (t4[0]["blend"], t4[0]["tta_mirror"]) == ("gauss", "none")
-    assert {c[2] for c in ops4.calls if c[0] == "gather_flip"} == {0}
+    assert {c[2] for c in ops4.calls if c[0] == "gather"} == {0}
+    assert {c[1:] for c in ops4.calls if c[0] == "stitch"} == {(False, 1)}
 
 
 def test_predict_refuses_the_switches_by_name_and_leaves_out_dir_empty(tmp_path):

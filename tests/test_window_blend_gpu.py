@@ -1,4 +1,4 @@
-"""Gaussian window blending and mirror test-time augmentation on a real MI355X (-m gpu): the flipped gather, the put
+"""Gaussian window blending and mirror test-time augmentation on a real MI355X (-m gpu): the mirrored gather, the put
 and the weighted stitch against torch and against the fp64 restatement of tests/test_window_blend_cpu.py, the window
 function end to end with toy modules, validate_seg, and what the ops refuse.
 
@@ -40,9 +40,9 @@ def _same_bits(a, b):
     return a.shape == b.shape and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
 
 
-# ---- gather, flipped ------------------------------------------------------------------------------------------------------
+# ---- gather, mirrored -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C", CHANNELS)
-def test_gather_flip_equals_the_flipped_gather_bitwise(ops, C):
+def test_gather_with_a_flip_mask_equals_the_flipped_gather_bitwise(ops, C):
     g = torch.Generator().manual_seed(C)
     for shape in (VOL, P):
         vol = torch.randn(N, C, *shape, generator=g).to(DEV)
@@ -50,16 +50,16 @@ def test_gather_flip_equals_the_flipped_gather_bitwise(ops, C):
         plain = ops.window_gather(vol, P, O)
         assert plain.shape[0] == (NWIN if shape == VOL else 1) * N
         for flip in range(8):
-            got = ops.window_gather_flip(vol, P, O, flip=flip)
+            got = ops.window_gather(vol, P, O, flip=flip)
             assert _same_bits(got, _flip(plain, flip)), (shape, flip)
-        assert _same_bits(ops.window_gather_flip(vol, P, O), plain)
+        assert _same_bits(ops.window_gather(vol, P, O, flip=0), plain)
     # a sub-range of the windows (vol is the one-window volume now: take the large one again)
     vol = torch.randn(N, C, *VOL, generator=g).to(DEV)
     plain = ops.window_gather(vol, P, O)
     for flip in (0, 3, 7):
-        part = ops.window_gather_flip(vol, P, O, 5, 7, flip)
+        part = ops.window_gather(vol, P, O, 5, 7, flip)
         assert _same_bits(part, _flip(plain[5 * N:12 * N], flip)), flip
-    last = ops.window_gather_flip(vol, P, O, NWIN - 1, 1, 5)
+    last = ops.window_gather(vol, P, O, NWIN - 1, 1, 5)
     assert _same_bits(last, _flip(plain[(NWIN - 1) * N:], 5))
 
 
@@ -88,6 +88,28 @@ def test_put_transposes_unmirrors_and_stores_or_adds_bitwise(ops, C):
     assert _same_bits(flat[1:].view(2, *P, C), _flip(src.permute(0, 2, 3, 4, 1), 6)) and float(flat[0]) == 0.0
 
 
+@pytest.mark.parametrize("C", [3, 4])
+def test_put_takes_a_channels_last_head_and_stores_it_unmirrored_without_allocating(ops, C):
+    # what the convs of the package return: N x C x pd x ph x pw over channels-last storage (from_ndhwc)
+    g = torch.Generator().manual_seed(30 + C)
+    stored = (4.0 * torch.randn(5, *P, C, generator=g)).to(DEV)
+    head = from_ndhwc(stored)
+    assert not head.is_contiguous()
+    was = torch.randn(5, *P, C, generator=g).to(DEV)
+    buf = was.clone()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated(DEV)
+    torch.cuda.reset_peak_memory_stats(DEV)
+    ops.window_put(head, buf, 0, False)
+    assert torch.cuda.max_memory_allocated(DEV) == base         # the default run's store sizes no window batch
+    assert _same_bits(buf, stored)
+    for flip, acc in ((0, True), (5, False), (5, True)):
+        buf = was.clone()
+        ops.window_put(head, buf, flip, acc)
+        want = _flip(stored, flip)
+        assert _same_bits(buf, was + want if acc else want), (flip, acc)
+
+
 # ---- weighted stitch --------------------------------------------------------------------------------------------------------
 def _weights_dev(kind):
     return tuple(torch.from_numpy(w).to(DEV) for w in blend_weights_host(P, kind))
@@ -102,9 +124,24 @@ def test_weighted_stitch_with_ones_equals_the_stitch_bitwise(ops, C):
         win[0, 0, 0, 0, 0] = -0.0
         full = (N, C) + shape
         want = ops.window_stitch(win, full, P, O)
-        assert _same_bits(ops.window_stitch_weighted(win, full, P, O, ops.blend_weights(P, "uniform"), 1), want)
+        assert _same_bits(ops.window_stitch(win, full, P, O, ops.blend_weights(P, "uniform"), 1), want)
     got = ops.blend_weights(P, "gauss")
     assert all(_same_bits(a, b) for a, b in zip(got, _weights_dev("gauss"))) and got[0].device.type == "cuda"
+
+
+@pytest.mark.parametrize("nflip", [1, 8])
+@pytest.mark.parametrize("C", CHANNELS)
+def test_stitch_without_weights_equals_the_stitch_with_ones_bitwise_at_any_nflip(ops, C, nflip):
+    # the two instances of the kernel: 1.0f * x is x and the weight sum is the exact count (18 at most here), so the
+    # unweighted one - the route of uniform blending with mirror passes - divides by the same nflip * count
+    g = torch.Generator().manual_seed(50 + C)
+    for shape in (VOL, P):
+        nwin = NWIN if shape == VOL else 1
+        win = (3.0 * torch.randn(nwin * N, *P, C, generator=g)).to(DEV)
+        win[0, 0, 0, 0, 0] = -0.0
+        full = (N, C) + shape
+        ones = ops.blend_weights(P, "uniform")
+        assert _same_bits(ops.window_stitch(win, full, P, O, None, nflip), ops.window_stitch(win, full, P, O, ones, nflip))
 
 
 @pytest.mark.parametrize("nflip", [1, 8])
@@ -116,7 +153,7 @@ def test_weighted_stitch_against_the_fp64_restatement(ops, C, nflip):
         nwin = NWIN if shape == VOL else 1
         win = 4.0 * torch.randn(nwin * N, *P, C, generator=g)
         full = (N, C) + shape
-        got = ops.window_stitch_weighted(win.to(DEV), full, P, O, _weights_dev("gauss"), nflip).cpu().numpy()
+        got = ops.window_stitch(win.to(DEV), full, P, O, _weights_dev("gauss"), nflip).cpu().numpy()
         ref, mag, cover = ref_blend([win.numpy()], w, full, P, O)
         ref, mag = ref / nflip, mag / nflip               # win holds the sum of nflip passes
         assert cover.max() == (18 if shape == VOL else 1) and cover.min() == 1
@@ -132,7 +169,7 @@ def test_weighted_stitch_lets_the_weights_decide_not_the_counts(ops):
     k = (1 * 16 + 1 * 4 + 1) * N            # window (1, 1, 1), starts (5, 4, 6), n = 0
     win[k, 0, 0, 0, 1] = 1e6                # its corner: volume voxel (5, 4, 6), also covered by window (0, 0, 0)
     w = blend_weights_host(P, "gauss")
-    got = ops.window_stitch_weighted(win.to(DEV), full, P, O, _weights_dev("gauss"), 1).cpu().numpy()
+    got = ops.window_stitch(win.to(DEV), full, P, O, _weights_dev("gauss"), 1).cpu().numpy()
     ref, mag, cover = ref_blend([win.numpy()], w, full, P, O)
     assert (np.abs(got - ref) <= blend_bound(mag, cover[None, None])).all()
     assert cover[5, 4, 6] == 8
@@ -257,19 +294,19 @@ def test_bad_arguments_are_host_side_errors_and_launch_nothing(ops):
     wts = ops.blend_weights(P, "gauss")
     for flip in (8, -1, 1.5, True):
         with pytest.raises(_lib.EffqError, match="flip"):
-            ops.window_gather_flip(vol, P, O, flip=flip)
+            ops.window_gather(vol, P, O, flip=flip)
         with pytest.raises(_lib.EffqError, match="flip"):
             ops.window_put(torch.zeros(1, 3, *P, device=DEV), win, flip, False)
     with pytest.raises(_lib.EffqError, match="9 channels"):
         ops.window_put(torch.zeros(1, 9, *P, device=DEV), torch.zeros(1, *P, 9, device=DEV), 0, False)
     with pytest.raises(_lib.EffqError, match="9 channels"):
-        ops.window_stitch_weighted(torch.zeros(1, *P, 9, device=DEV), (1, 9) + P, P, O, wts, 1)
+        ops.window_stitch(torch.zeros(1, *P, 9, device=DEV), (1, 9) + P, P, O, wts, 1)
     with pytest.raises(_lib.EffqError, match="nflip"):
-        ops.window_stitch_weighted(win, (1, 3) + P, P, O, wts, 0)
+        ops.window_stitch(win, (1, 3) + P, P, O, wts, 0)
     with pytest.raises(_lib.EffqError, match="axis h"):
-        ops.window_stitch_weighted(win, (1, 3) + P, P, O, (wts[0], wts[1][:-1], wts[2]), 1)
+        ops.window_stitch(win, (1, 3) + P, P, O, (wts[0], wts[1][:-1], wts[2]), 1)
     with pytest.raises(_lib.EffqError, match="weight tensors"):
-        ops.window_stitch_weighted(win, (1, 3) + P, P, O, wts[:2], 1)
+        ops.window_stitch(win, (1, 3) + P, P, O, wts[:2], 1)
     with pytest.raises(_lib.EffqError, match="buffer slice"):
         ops.window_put(torch.zeros(1, 3, *P, device=DEV), torch.zeros(2, *P, 3, device=DEV), 0, False)
     with pytest.raises(_lib.EffqError, match="contiguous"):
@@ -285,11 +322,11 @@ def test_bad_arguments_are_host_side_errors_and_launch_nothing(ops):
     assert lib.effq_window_put(ptr(src), 1, 3, *P, 0, 2, ptr(dst), st) == bad
     assert lib.effq_window_put(ptr(src), 1, 9, *P, 0, 0, ptr(dst), st) == bad
     assert lib.effq_window_put(ptr(src), 1 << 20, 8, 128, 128, 128, 0, 0, ptr(dst), st) == bad        # 2^44 elements
-    assert lib.effq_window_gather_flip(ptr(src), 1, 3, *P, *P, *O, 0, 1, 8, ptr(dst), st) == bad
-    assert lib.effq_window_gather_flip(ptr(src), 1, 3, *P, *P, *O, 0, 2, 0, ptr(dst), st) == bad      # one window only
+    assert lib.effq_window_gather(ptr(src), 1, 3, *P, *P, *O, 0, 1, 8, ptr(dst), st) == bad
+    assert lib.effq_window_gather(ptr(src), 1, 3, *P, *P, *O, 0, 2, 0, ptr(dst), st) == bad           # one window only
     w3 = [ptr(t) for t in wts]
-    assert lib.effq_window_stitch_weighted(ptr(dst), 1, 3, *P, *P, *O, *w3, 0, ptr(out), st) == bad
-    assert lib.effq_window_stitch_weighted(ptr(dst), 1, 9, *P, *P, *O, *w3, 1, ptr(out), st) == bad
-    assert lib.effq_window_stitch_weighted(ptr(dst), 1, 3, *P, *P, *O, w3[0], None, w3[2], 1, ptr(out), st) == bad
+    assert lib.effq_window_stitch(ptr(dst), 1, 3, *P, *P, *O, *w3, 0, ptr(out), st) == bad
+    assert lib.effq_window_stitch(ptr(dst), 1, 9, *P, *P, *O, *w3, 1, ptr(out), st) == bad
+    assert lib.effq_window_stitch(ptr(dst), 1, 3, *P, *P, *O, w3[0], None, w3[2], 1, ptr(out), st) == bad
     torch.cuda.synchronize()
     assert bool((dst == 7.0).all()) and bool((out == 7.0).all())
