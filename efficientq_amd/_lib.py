@@ -190,6 +190,9 @@ SIGNATURES = {
     "effq_window_put": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_window_stitch": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "effq_seg_tallies": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _SZ, _P]),
+    "effq_seg_sweep": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P]),
+    "effq_seg_sweep_edges": (_I, [_I, _F, _P]),
+    "effq_seg_sweep_plan": (_I, [_I, _LL, _I, _IP, _IP]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
     "effq_seg_labels_source": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P]),
     "effq_seg_agreement": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P]),
@@ -226,6 +229,8 @@ SEG_TALLIES_MAX_CLASSES = 8
 # include/effq_hip.h: scratch of effq_seg_agreement
 SEG_AGREEMENT_WS_BYTES = 768 * (4 * SEG_TALLIES_MAX_CLASSES * 8 + (3 * SEG_TALLIES_MAX_CLASSES + 1) * 4)
 SEG_ARGMAX, SEG_SIGMOID = 0, 1
+# include/effq_hip.h (EFFQ_SEG_SWEEP_BINS): the score bins of effq_seg_sweep
+SEG_SWEEP_BINS = 4096
 SEG_FUSE = {None: 0, "agg": 1, "aggressive": 1, "con": 2, "conservative": 2}
 # include/effq_hip.h: the label rules of effq_seg_labels
 SEG_LABEL_RULES = {"argmax": 0, "brats": 1, "rank": 2, "planes": 3}

@@ -118,6 +118,14 @@ def build_parser():
                         'every component of fewer than N voxels; the others become TO (default 0): 1,2:largest  \'4:min500>1\' '
                         '(quote a rule with > on a shell command line: unquoted, the shell takes >TO for a redirection)')
     p.add_argument('--post_conn', default=None, help='the neighbourhood of every --post rule: 26 (default) or 6')
+    # the threshold sweep of the validation and the decision threshold of a run; refused combinations and values are
+    # named by thr_switches, after the YAML has been merged in
+    p.add_argument('--thr_sweep', action='store_true',
+                   help='ptq: sweep the decision threshold of every validation: ROC AUC, the best-Dice threshold and the '
+                        'pooled curve in <snap>/{fp,ptq}/threshold.csv and threshold_curve.csv')
+    p.add_argument('--thresh', default=None, metavar='VALUE',
+                   help='ptq, predict, with --multi_label: decide every channel at this threshold instead of sigmoid >= '
+                        '0.5: a probability P (0 < P < 1) or logit:X')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
@@ -137,6 +145,60 @@ def blend_switches(args):
     except ValueError as e:
         raise SystemExit(f'--tta_mirror {e}')
     return blend, flips
+
+
+def parse_thresh(value):
+    """The fp32 logit of a --thresh VALUE: `P` with 0 < P < 1 is a probability and gives the fp32 nearest
+    log(P / (1 - P)) in fp64, `logit:X` the fp32 nearest X.  None for 0.5 and logit:0, the default decision.  What is
+    not understood is refused by name (SystemExit)."""
+    import math
+    import numpy as np
+    t = str(value).strip()
+    is_logit = t.lower().startswith('logit:')
+    try:
+        x = float(t[6:] if is_logit else t)
+    except ValueError:
+        raise SystemExit(f'--thresh {t!r}: a probability P with 0 < P < 1, or logit:X')
+    if not math.isfinite(x):
+        raise SystemExit(f'--thresh {t!r}: the value is not finite')
+    if not is_logit:
+        if not 0.0 < x < 1.0:
+            raise SystemExit(f'--thresh {t!r}: a probability lies strictly between 0 and 1 (a logit is given as logit:X)')
+        x = math.log(x / (1.0 - x))
+    with np.errstate(over='ignore'):
+        v = float(np.float32(x))
+    if not math.isfinite(v):
+        raise SystemExit(f'--thresh {t!r}: the logit is not finite in fp32')
+    return None if v == 0.0 else v
+
+
+def thr_switches(args, mission=None):
+    """(sweep, thresh) of --thr_sweep / --thresh (or the YAML keys `thr_sweep`, `thresh`): whether the validations sweep
+    the threshold, and the fp32 logit every sigmoid decision is taken at (None: the default).  The missions and
+    combinations they cannot serve and the values that are not understood are refused by name (SystemExit), host only."""
+    mission = mission or getattr(args, 'mission', None)
+    sweep = bool(getattr(args, 'thr_sweep', False))
+    given = getattr(args, 'thresh', None)
+    if sweep:
+        if mission in ('prep', 'predict'):
+            raise SystemExit(f'--thr_sweep sweeps the threshold of a validation against labels: the {mission} mission '
+                             f'validates nothing, drop --thr_sweep')
+        for switch in ('unlabelled', 'synthetic'):
+            if getattr(args, switch, False):
+                raise SystemExit(f'--thr_sweep --{switch}: the sweep counts labelled and unlabelled voxels, and there is '
+                                 f'no truth: drop --thr_sweep')
+        if getattr(args, 'no_test', False):
+            raise SystemExit('--thr_sweep --no_test: the sweep belongs to the validation that --no_test skips: drop one '
+                             'of them')
+    thresh = None
+    if given is not None:
+        if mission == 'prep':
+            raise SystemExit('--thresh sets the threshold of a decision: the prep mission decides nothing, drop --thresh')
+        thresh = parse_thresh(given)
+        if not getattr(args, 'multi_label', None):
+            raise SystemExit(f'--thresh {given}: without --multi_label the classes are decided by argmax (class-id mode), '
+                             f'which has no threshold: it needs --multi_label')
+    return sweep, thresh
 
 
 POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES

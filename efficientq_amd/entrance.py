@@ -29,6 +29,13 @@ components on the device (``1,2:largest`` keeps the largest component of the lab
 or the shell takes ``>1`` for a redirection - relabels every component of label 4 with fewer than 500 voxels to 1) and
 scores the cleaned map: ``<snap>/{fp,ptq}/metrics_post.csv``; ``metrics.csv`` and every other file stay what they are.
 It needs labels: with ``--unlabelled`` or ``--synthetic`` it is refused.  ``predict --post`` writes the cleaned maps.
+``--thr_sweep`` also sweeps the decision threshold of every labelled validation in one more pass over the stitched logits
+(effq_seg_sweep): ``<snap>/{fp,ptq}/threshold.csv`` (per subject and class, and pooled: the ROC AUC, the Dice at the default
+decision, the threshold of the best Dice and the Dice, sensitivity and specificity there) and ``threshold_curve.csv`` (the
+pooled counts and Dice of every threshold), and per class the mean AUC and the pooled Dice at the default and at the best
+threshold, with ``--test_fp`` for both networks side by side; it needs labels and a validation: with ``--unlabelled``,
+``--synthetic`` or ``--no_test`` it is refused.  ``--thresh P`` / ``--thresh logit:X`` (with ``--multi_label``) takes every
+sigmoid decision of the run, for both networks, at that threshold instead of 0.5 (``predict`` takes it too).
 ``--synthetic`` instead calibrates on seeded synthetic volumes (``synth.py``) and validates nothing, unless ``--vs_fp``
 is given: then two held-out synthetic volumes are validated against the FP network; without
 ``--pretrain`` a seeded random-init network stands in for the checkpoint.  With ``torchrun --nproc-per-node N``
@@ -87,13 +94,16 @@ class _ValidationTester(_SnapshotWriter):
     <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns, with is_surf also the
     surface distances, with is_table also <root>/<folder>/lesions.csv, with fp_model (--vs_fp) also
     <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
-    labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written."""
+    labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written.
+    With sweep (--thr_sweep) also <root>/<folder>/threshold.csv and threshold_curve.csv (_sweep)."""
 
-    def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,), post=(), post_conn=26):
+    def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,), post=(), post_conn=26,
+                 sweep=False):
         super().__init__(model, root)
         self.cube, self.task, self.rank = data_cube, task.lower(), rank
         self.blend, self.flips = blend, tuple(flips)
         self.post, self.post_conn = list(post), post_conn
+        self.sweep, self.swept = bool(sweep), {}           # swept: folder -> (mean AUC per class, pooled summary)
 
     def _geometry(self, is_save_nii, is_surf, is_table=False):
         """validate_seg's `geometry`, only when a switch asks for one: the per-subject entries of --src_geom (distances,
@@ -128,6 +138,7 @@ class _ValidationTester(_SnapshotWriter):
                              **({'blend': self.blend, 'flips': self.flips}
                                 if (self.blend, self.flips) != ('uniform', (0,)) else {}),
                              **({'post': self.post, 'post_conn': self.post_conn} if self.post else {}),
+                             **({'sweep': True} if self.sweep and labelled else {}),
                              **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
         if fp_model is not None:
@@ -165,8 +176,31 @@ class _ValidationTester(_SnapshotWriter):
                   f'{" ".join(str(v) for v in changed)} voxels relabelled, per-class mean dsc before -> after:')
             for c in range(len(means['dsc'])):
                 print(f'  class {c}: {float(means["dsc"][c]):.4f} -> {float(after["dsc"][c]):.4f}')
+        if self.sweep:
+            self._sweep(folder, out, res)
         if fp_model is not None:
             self._print_agreement(folder, res)
+
+    def _sweep(self, folder, out, res):
+        """--thr_sweep: threshold.csv and threshold_curve.csv of `folder`, and per class the mean AUC, the pooled best
+        threshold and the pooled Dice at the default threshold and at the best; every network swept so far side by side."""
+        E.write_threshold_csv(os.path.join(out, 'threshold.csv'), res)
+        E.write_threshold_curve_csv(os.path.join(out, 'threshold_curve.csv'), res)
+        per, pooled, _ = E.sweep_results(res)
+        ncls = len(pooled)
+        self.swept[folder] = ([sum(s[c]['auc'] for _, s in per) / len(per) for c in range(ncls)], pooled)
+        sigmoid = bool(getattr(self.cube, 'multi_label', None))
+
+        def said(name, c):
+            auc, pool = self.swept[name]
+            q = pool[c]
+            at = f'{E.logit_prob(q["best_thr"]):.4f} (logit {q["best_thr"]:.9g})' if sigmoid else f'margin {q["best_thr"]:.9g}'
+            return (f'{name.upper()}: AUC {auc[c]:.4f}, Dice {float(q["dsc_default"]):.4f} at '
+                    f'{"0.5" if sigmoid else "argmax"}, {float(q["dsc_best"]):.4f} at {at}')
+        print(f'[entrance] {folder}: --thr_sweep, per class the mean AUC and the pooled Dice at the default and at the '
+              f'best threshold:')
+        for c in range(ncls):
+            print(f'  class {c}: ' + '; '.join(said(name, c) for name in self.swept))
 
     @staticmethod
     def _print_agreement(folder, res):
@@ -210,6 +244,7 @@ def check_switches(args):
     understood, refused before anything touches the device (host only: SystemExit naming the switches)."""
     Cf.blend_switches(args)
     check_post(args)
+    Cf.thr_switches(args)
     if not getattr(args, 'unlabelled', False):
         return
     if not getattr(args, 'vs_fp', False):
@@ -248,10 +283,12 @@ def main(argv=None):
         args = Cf.merge_config(args.config, args)
     if args.mission == 'prep':
         check_post(args)
+        Cf.thr_switches(args)
         from . import prep
         prep.run(args)
         return
     if args.mission == 'predict':
+        Cf.thr_switches(args)
         from . import predict
         predict.run(args)
         return
@@ -268,6 +305,11 @@ def main(argv=None):
     if post:
         print(f'[entrance] --post {Cf.post_text(post, post_conn)}: every labelled validation also scores the cleaned map '
               f'(metrics_post.csv)')
+    sweep, thresh = Cf.thr_switches(args)
+    if sweep:
+        cleaning = dict(cleaning, sweep=True)
+        print('[entrance] --thr_sweep: every labelled validation also sweeps the decision threshold (threshold.csv, '
+              'threshold_curve.csv)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -278,6 +320,21 @@ def main(argv=None):
         # an eagerly created framework communicator brings streams of its own that slow the calibration by 20 %)
         dist.init_process_group('nccl')
         args.device = local
+    if thresh is None:
+        return _ptq(args, sliding, cleaning)
+    from .hip_ops import get_ops
+    ops = get_ops(torch.device('cuda', int(args.device)))
+    print(f'[entrance] --thresh {args.thresh}: every channel is decided at logit >= {thresh:.9g} (sigmoid >= '
+          f'{E.logit_prob(thresh):.6g}) in every validation and map of this run, for both networks alike')
+    ops.set_decision_threshold(thresh)
+    try:
+        return _ptq(args, sliding, cleaning)
+    finally:
+        ops.set_decision_threshold(None)
+
+
+def _ptq(args, sliding, cleaning):
+    """The ptq mission after its switches are checked: `sliding` and `cleaning` are the tester's keywords."""
     QConv, Qinfo, kwQ = Cf.get_conv_class(args)
     cube, info = Cf.get_model_cube(args, QConv, kwQ)
     model = cube['model']

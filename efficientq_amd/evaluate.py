@@ -390,7 +390,8 @@ def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_
 @torch.no_grad()
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
-                 geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,), post=None, post_conn=26):
+                 geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,), post=None, post_conn=26,
+                 sweep=False):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -440,7 +441,10 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     (effq_label_clean) and tallied against the label (effq_label_tallies with post_class_lut's table), and its dict gains
     "post": counts (C x 4) with dsc / sens / spec / acc, and "changed", the voxels each rule relabelled.  Every other
     entry and the maps of save_dir stay what they are.  The planes of --multi_label lits are no label map, and the
-    planes of --multi_label brats are read back from the map only when `fuse` nests them: both are a RuntimeError."""
+    planes of --multi_label brats are read back from the map only when `fuse` nests them: both are a RuntimeError.
+    sweep: each labelled case's dict also carries "sweep", the C x 2 x 4096 int64 histogram of the case's scores by truth
+    on the host (effq_seg_sweep, one more call per case after the tallies), and "sweep_edges", the 4096 fp32 edges of its
+    bins (hip_ops.sweep_edges): what sweep_summary, write_threshold_csv and write_threshold_curve_csv take."""
     from .hip_ops import get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -450,6 +454,7 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     p, o = _triple(patch_size), _triple(overlap)
     bsz = window_batch
     results = []
+    sweep_edges = {}
     pool, writes = None, []
     if save_dir is not None:
         from concurrent.futures import ThreadPoolExecutor
@@ -503,6 +508,11 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                     counts = ops.seg_tallies(stitched[n], lab[n], kind, fz).cpu()
                     res["counts"] = counts
                     res.update(metrics_from_counts(counts))
+                    if sweep:
+                        res["sweep"] = ops.seg_sweep(stitched[n], lab[n], kind, fz).cpu()
+                        if kind not in sweep_edges:
+                            sweep_edges[kind] = ops.sweep_edges(kind)
+                        res["sweep_edges"] = sweep_edges[kind]
                     if lesion_table:
                         cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], kind, fz)
                         ncls = int(cnt.shape[0])
@@ -564,6 +574,125 @@ def write_metrics_csv(path: str, results) -> None:
                 wr.writerow([r["name"], c] + ["%.7g" % float(r[m][c]) for m in METRICS] +
                             [int(v) for v in r["counts"][c]] + ([int(v) for v in r["lesions"][c]] if cc else []) +
                             (["%.7g" % float(v) for v in r["surface"][c]] if sd else []))
+
+
+# ---- the threshold sweep (validate_seg(..., sweep=True), --thr_sweep) -----------------------------------------------------
+SWEEP_BINS = 4096
+SWEEP_MID = 2048          # the edge of the default decision: row 2048 of a sweep is the counts of metrics.csv
+THRESHOLD_COLUMNS = ("subject", "class", "auc", "dsc", "best_thr_logit", "best_thr_prob", "dsc_best", "sens_best",
+                     "spec_best", "pos", "neg")
+THRESHOLD_CURVE_COLUMNS = ("class", "k", "thr_logit", "thr_prob", "tp", "fp", "fn", "tn", "dsc", "sens", "spec")
+
+
+def _sweep_ints(hist):
+    """A histogram (tensor, array or nested lists; C x 2 x 4096) as nested lists of Python integers."""
+    if hasattr(hist, "tolist"):
+        hist = hist.tolist()
+    out = [[[int(v) for v in row] for row in cls] for cls in hist]
+    if any(len(cls) != 2 or any(len(row) != SWEEP_BINS for row in cls) for cls in out):
+        raise ValueError(f"a sweep histogram is C x 2 x {SWEEP_BINS}")
+    return out
+
+
+def sweep_pooled(hists):
+    """The sum of histograms (each C x 2 x 4096) in Python integers, as nested lists."""
+    hs = [_sweep_ints(h) for h in hists]
+    return [[[sum(col) for col in zip(*(h[c][g] for h in hs))] for g in range(2)] for c in range(len(hs[0]))]
+
+
+def sweep_summary(hist, edges):
+    """Per class of a sweep histogram (C x 2 x 4096: [c][g][b] = the voxels of truth g in score bin b; hip_ops.seg_sweep, or
+    sweep_pooled of several) and the 4096 edges of its bins, on the host and in integers, a dict of
+      auc          (2 sum_b pos_b below_b + sum_b pos_b neg_b) / (2 P N), below_b = the negatives in the bins under b: the
+                   Mann-Whitney statistic with the ties inside a bin counted half (roc_auc_score(truth, bin)); the
+                   numerator is an exact Python integer; 1.0 when P = 0 or N = 0 (metrics.py:60-67)
+      counts       4096 x 4 int64, row k = TP, FP, FN, TN of the decision "score >= edge k" (suffix sums; row 0: all)
+      best_k       the k in 1 .. 4095 with the largest 2 TP / (2 TP + FP + FN) in fp64 (a zero denominator counts as -1);
+                   ties go to the least |k - 2048|, then to the lower k
+      best_thr     edge best_k as a Python float (an fp32 value)
+      dsc_default, dsc_best, sens_best, spec_best    metrics_from_counts of the rows 2048 and best_k (the arithmetic of
+                   metrics.csv)
+      pos, neg     P and N."""
+    h = _sweep_ints(hist)
+    e = [float(v) for v in (edges.tolist() if hasattr(edges, "tolist") else edges)]
+    if len(e) != SWEEP_BINS:
+        raise ValueError(f"{len(e)} edges, a sweep has {SWEEP_BINS}")
+    out = []
+    for neg, pos in h:
+        P, N = sum(pos), sum(neg)
+        num, below = 0, 0
+        for pb, nb in zip(pos, neg):
+            num += 2 * pb * below + pb * nb
+            below += nb
+        auc = num / (2 * P * N) if P and N else 1.0
+        rows, tp, fp = [None] * SWEEP_BINS, 0, 0
+        for k in range(SWEEP_BINS - 1, -1, -1):
+            tp += pos[k]
+            fp += neg[k]
+            rows[k] = (tp, fp, P - tp, N - fp)
+        best_k, best = None, None
+        for k in range(1, SWEEP_BINS):
+            tp, fp, fn, _ = rows[k]
+            den = 2 * tp + fp + fn
+            key = ((2 * tp) / den if den else -1.0, -abs(k - SWEEP_MID), -k)
+            if best is None or key > best:
+                best_k, best = k, key
+        counts = torch.tensor(rows, dtype=torch.int64)
+        m = metrics_from_counts(counts[[SWEEP_MID, best_k]])
+        out.append({"auc": auc, "counts": counts, "best_k": best_k, "best_thr": e[best_k],
+                    "dsc_default": m["dsc"][0], "dsc_best": m["dsc"][1], "sens_best": m["sens"][1],
+                    "spec_best": m["spec"][1], "pos": P, "neg": N})
+    return out
+
+
+def logit_prob(logit: float) -> float:
+    """1 / (1 + exp(-logit)) in fp64."""
+    return 1.0 / (1.0 + math.exp(-logit))
+
+
+def sweep_results(results):
+    """(per-subject [(name, summary)], pooled summary, edges) of the results that carry "sweep"."""
+    res = [r for r in results if "sweep" in r]
+    if not res:
+        raise RuntimeError("no result carries a sweep (validate_seg(..., sweep=True) on labelled cases)")
+    edges = res[0]["sweep_edges"]
+    if any(not torch.equal(torch.as_tensor(r["sweep_edges"]), torch.as_tensor(edges)) for r in res):
+        raise RuntimeError("sweeps with different edges in one file")
+    per = [(r["name"], sweep_summary(r["sweep"], edges)) for r in res]
+    return per, sweep_summary(sweep_pooled([r["sweep"] for r in res]), edges), edges
+
+
+def write_threshold_csv(path: str, results) -> None:
+    """One row per subject and class from the "sweep" entries (validate_seg(..., sweep=True)), then one row per class
+    with the subject `pooled` from the summed histograms: THRESHOLD_COLUMNS.  dsc is the Dice at the default decision
+    (metrics.csv's), best_thr_logit the edge of the best Dice as %.9g (the fp32 value reads back exactly),
+    best_thr_prob its sigmoid in fp64."""
+    import csv
+    per, pooled, _ = sweep_results(results)
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(THRESHOLD_COLUMNS)
+        for name, summ in per + [("pooled", pooled)]:
+            for c, q in enumerate(summ):
+                wr.writerow([name, c, "%.9g" % q["auc"], "%.7g" % float(q["dsc_default"]), "%.9g" % q["best_thr"],
+                             "%.9g" % logit_prob(q["best_thr"])] +
+                            ["%.7g" % float(q[k]) for k in ("dsc_best", "sens_best", "spec_best")] + [q["pos"], q["neg"]])
+
+
+def write_threshold_curve_csv(path: str, results) -> None:
+    """The pooled curve of the "sweep" entries, one row per class and k = 1 .. 4095: THRESHOLD_CURVE_COLUMNS, the counts
+    of the decision "score >= edge k" summed over the subjects and their dsc, sens and spec (metrics_from_counts)."""
+    import csv
+    _, pooled, edges = sweep_results(results)
+    e = [float(v) for v in torch.as_tensor(edges).tolist()]
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(THRESHOLD_CURVE_COLUMNS)
+        for c, q in enumerate(pooled):
+            m = metrics_from_counts(q["counts"])
+            for k in range(1, SWEEP_BINS):
+                wr.writerow([c, k, "%.9g" % e[k], "%.9g" % logit_prob(e[k])] + [int(v) for v in q["counts"][k]] +
+                            ["%.7g" % float(m[j][k]) for j in ("dsc", "sens", "spec")])
 
 
 def write_metrics_post_csv(path: str, results) -> None:

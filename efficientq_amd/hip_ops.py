@@ -1160,7 +1160,25 @@ class HipOps:
         """The three per-axis fp32 weight tensors of window_stitch on this device (blend_weights_host)."""
         return tuple(torch.from_numpy(w).to(self.device) for w in blend_weights_host(patch, kind))
 
+    def set_decision_threshold(self, logit: Optional[float]) -> None:
+        """The logit every sigmoid decision of these ops is taken at from now on (--thresh): sigmoid_threshold() returns
+        the fp32 nearest `logit`, so the tallies, the label maps, the lesions, the surfaces and the agreement follow it.
+        None: the default again.  seg_sweep and sweep_edges keep the default: the sweep does not depend on it."""
+        if logit is None:
+            self._decision_thresh = None
+            return
+        v = float(torch.tensor(float(logit), dtype=torch.float32).item())
+        if not math.isfinite(v):
+            raise _lib.EffqError(f"set_decision_threshold: {logit!r} is no finite fp32 logit")
+        self._decision_thresh = v
+
     def sigmoid_threshold(self) -> float:
+        """The logit a sigmoid decision is taken at: the one set_decision_threshold set, or default_sigmoid_threshold()."""
+        if getattr(self, "_decision_thresh", None) is not None:
+            return self._decision_thresh
+        return self.default_sigmoid_threshold()
+
+    def default_sigmoid_threshold(self) -> float:
         """The least fp32 x at which the framework's fp32 `torch.sigmoid(x) >= 0.5` holds on this device.  Near 0 it is
         not 0: a small negative logit rounds to exactly 0.5.  Found by bisection over the bit patterns of -x, then
         checked on the 2^17 floats around it; cached."""
@@ -1240,6 +1258,42 @@ class HipOps:
         check(self.lib.effq_seg_tallies(_ptr(x), _ptr(lab), Cc, S, mode, fcode, thresh, _ptr(counts), _ptr(ws), ws.numel(),
                                         self.stream), "effq_seg_tallies")
         return counts
+
+    def seg_sweep(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
+        """The threshold sweep of one case (effq_seg_sweep), arguments as seg_tallies: C x 2 x 4096 int64 on the device,
+        [c][g][b] = the voxels with truth g for class c whose score for class c falls in bin b of sweep_edges.  The
+        counts of the decision "score >= edge k" are the sums over the bins from k on; row 2048 is seg_tallies at the
+        default threshold, which is the pinned edge whatever set_decision_threshold set."""
+        x, lab, Cc, S, mode, fcode, _ = self._seg_case("seg_sweep", logits, label, task, fuse, False)
+        if not 0 < S < 2 ** 31:
+            raise _lib.EffqError(f"seg_sweep: {S} voxels, needs 1 to 2^31 - 1")
+        thresh = 0.0 if mode == _lib.SEG_ARGMAX else self.default_sigmoid_threshold()
+        hist = torch.empty(Cc, 2, _lib.SEG_SWEEP_BINS, dtype=torch.int64, device=self.device)
+        check(self.lib.effq_seg_sweep(_ptr(x), _ptr(lab), Cc, S, mode, fcode, thresh, _ptr(hist), self.stream),
+              "effq_seg_sweep")
+        return hist
+
+    def seg_sweep_plan(self, Cc: int, S: int, task: str) -> dict:
+        """The launch seg_sweep makes for Cc classes and S voxels (effq_seg_sweep_plan): grid, the workgroups, and trips,
+        the trips of each over its groups of four voxels."""
+        mode = {"lits": _lib.SEG_ARGMAX, "brats": _lib.SEG_SIGMOID}.get(task)
+        if mode is None:
+            raise _lib.EffqError(f"Unknown task {task}")
+        grid, trips = C.c_int(0), C.c_int(0)
+        check(self.lib.effq_seg_sweep_plan(int(Cc), int(S), mode, C.byref(grid), C.byref(trips)), "effq_seg_sweep_plan")
+        return {"grid": grid.value, "trips": trips.value}
+
+    def sweep_edges(self, kind: str) -> torch.Tensor:
+        """The 4096 fp32 edges of seg_sweep's bins on the host (effq_seg_sweep_edges), index 0 = -inf: kind 'lits' /
+        'argmax' (edge 2048 = 0) or 'brats' / 'sigmoid' (edge 2048 = the default sigmoid threshold)."""
+        mode = {"argmax": _lib.SEG_ARGMAX, "lits": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID,
+                "brats": _lib.SEG_SIGMOID}.get(kind)
+        if mode is None:
+            raise _lib.EffqError(f"sweep_edges: unknown kind {kind!r} (argmax or sigmoid)")
+        thresh = 0.0 if mode == _lib.SEG_ARGMAX else self.default_sigmoid_threshold()
+        edges = (C.c_float * _lib.SEG_SWEEP_BINS)()
+        check(self.lib.effq_seg_sweep_edges(mode, thresh, edges), "effq_seg_sweep_edges")
+        return torch.frombuffer(bytearray(edges), dtype=torch.float32).clone()
 
     def seg_labels(self, logits: torch.Tensor, rule: str, fuse: Optional[str] = None, dtype=torch.uint8):
         """Label maps of N cases' logits (N x C x spatial, fp32) from the decisions seg_tallies counts

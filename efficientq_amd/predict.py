@@ -36,7 +36,11 @@ component of the labels 1 and 2, ``--post '4:min500>1'`` relabels every componen
 1.  ``predict.csv`` then gains the columns ``post`` (the rules) and ``post_changed`` (the voxels each rule relabelled)
 after all others, and ``labels``, ``voxels`` and ``volume_ml`` are the cleaned map's; without ``--post`` nothing changes.
 
-Everything the list and the headers decide, a ``--post`` rule that is not understood, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
+``--thresh VALUE`` (with ``--multi_label``; a probability ``P`` or ``logit:X``, config.parse_thresh) decides every channel
+at that threshold instead of sigmoid >= 0.5.  ``predict.csv`` then gains the column ``thresh`` (the fp32 logit, ``%.9g``)
+after the blend columns and before the post columns; ``0.5`` and ``logit:0`` are the default and change nothing.
+
+Everything the list and the headers decide, a ``--thresh`` that is not understood or given without ``--multi_label``, a ``--post`` rule that is not understood, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
 and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
 """
 from __future__ import annotations
@@ -101,6 +105,7 @@ def _network(args, dev):
 
 
 CSV_BLEND_COLUMNS = ["blend", "tta_mirror"]       # after CSV_HEADER, only when --blend / --tta_mirror is given
+CSV_THRESH_COLUMNS = ["thresh"]                   # after those, only when --thresh is given (and is not the default)
 CSV_POST_COLUMNS = ["post", "post_changed"]       # after those, only when --post is given
 
 
@@ -169,6 +174,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     blend, flips = Cf.blend_switches(args)
     sliding = (blend, flips) != ("uniform", (0,))
     post, post_conn = Cf.post_rules(args)
+    _, thresh = Cf.thr_switches(args, 'predict')
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
@@ -189,6 +195,11 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         used.update(orient=orient)
     if sliding:
         used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
+    if thresh is not None:
+        used.update(thresh="%.9g" % thresh)
+        print(f"[predict] --thresh {args.thresh}: every channel is decided at logit >= {thresh:.9g} (sigmoid >= "
+              f"{E.logit_prob(thresh):.6g})")
+        ops.set_decision_threshold(thresh)
     post_said = Cf.post_text(post, post_conn) if post else None
     if post:
         used.update(post=post_said)
@@ -243,10 +254,12 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     finally:
         reader.shutdown(wait=True, cancel_futures=True)
         writer.shutdown(wait=True)
+        if thresh is not None:
+            ops.set_decision_threshold(None)
     for w in writes:
         w.result()                              # re-raises a failed write
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
                CSV_HEADER + (prep.ORIENT_COLUMNS if orient else []) + (CSV_BLEND_COLUMNS if sliding else []) +
-               (CSV_POST_COLUMNS if post else []))
+               (CSV_THRESH_COLUMNS if thresh is not None else []) + (CSV_POST_COLUMNS if post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

@@ -622,6 +622,32 @@ int effq_window_stitch(const float* win, int N, int C, int D, int H, int W, int 
 int effq_seg_tallies(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
                      long long* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* Threshold sweep of one case (validate_seg(..., sweep=True), --thr_sweep): logits (C, S), label, mode and fuse as
+ * effq_seg_tallies -> hist (C, 2, EFFQ_SEG_SWEEP_BINS) int64 on the device, overwritten: hist[c][g][b] = the voxels with
+ * truth g for class c (the gt bit of the tallies' decision) whose score for class c falls in bin b.
+ *   Scores, fp32, nothing fused.  EFFQ_SEG_SIGMOID: NONE s_c = x_c; AGG s_c = the largest non-NaN of x_c .. x_{C-1} (NaN
+ *   when all are NaN); CON s_c = the least of x_0 .. x_c (NaN when any is NaN).  EFFQ_SEG_ARGMAX: s_c = x_c - max_{j != c}
+ *   x_j, one subtraction, the max with NaN as the largest value (torch.max), so a NaN in another channel makes s_c NaN;
+ *   C = 1: s_0 = x_0.
+ *   Edges: e_0 = -inf, e_k = (k - 2048) / 128 for k = 1 .. 4095, except e_2048 = thresh in sigmoid mode (it must lie
+ *   strictly between e_2047 and e_2049) and 0 in argmax mode, where thresh is not read.  bin(s) = the number of k >= 1
+ *   with e_k <= s; NaN -> 0.  In sigmoid mode bin >= 2048 is the tallies' decision at `thresh`.  In argmax mode the bin is
+ *   then pinned to the tallies' decision: max(bin, 2048) for the predicted class, min(bin, 2047) for every other.
+ *   The counts TP, FP, FN, TN of "score >= e_k" are the sums of hist[c][1][k:], hist[c][0][k:], hist[c][1][:k],
+ *   hist[c][0][:k]; row 2048 is what effq_seg_tallies returns.
+ * 1 <= C <= EFFQ_SEG_TALLIES_MAX_CLASSES, 0 < S < 2^31, fuse NONE in argmax mode, logits 4-B and hist 8-B aligned;
+ * anything else returns EFFQ_ERR_ARG before a launch and leaves hist untouched.  Workgroup-private 32-bit counters in
+ * LDS, flushed with 64-bit integer atomics into hist, which a first launch zeroes: integer adds only, so equal inputs
+ * give equal bits.  Two launches on `stream`, no read by the host, no workgroup that waits for another.
+ * effq_seg_sweep_edges: the EFFQ_SEG_SWEEP_BINS edges of a mode and thresh into host memory, index 0 = -inf.
+ * effq_seg_sweep_plan: the launch effq_seg_sweep makes; launches nothing.  *grid workgroups (voxel ranges x
+ * ceil(C / 2) class pairs), each of which makes *trips trips over its groups of four voxels (0 when S < 4). */
+#define EFFQ_SEG_SWEEP_BINS 4096
+int effq_seg_sweep(const float* logits, const uint8_t* label, int C, long long S, int mode, int fuse, float thresh,
+                   long long* hist, void* stream);
+int effq_seg_sweep_edges(int mode, float thresh, float* edges_host);
+int effq_seg_sweep_plan(int C, long long S, int mode, int* grid, int* trips);
+
 /* Agreement of two networks on one case (validate_seg(..., fp_model=...), --vs_fp): logits_q and logits_fp, the stitched
  * last-head logits (C, S) fp32 of the calibrated and of the full-precision network; mode, fuse and thresh as
  * effq_seg_tallies, and both networks' voxels are decided by the tallies' own rule.  One pass over the 2 C S floats:
