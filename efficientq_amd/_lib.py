@@ -195,6 +195,7 @@ SIGNATURES = {
     "effq_seg_sweep_plan": (_I, [_I, _LL, _I, _IP, _IP]),
     "effq_seg_labels": (_I, [_P, _I, _I, _LL, _I, _I, _F, _I, _P, _P]),
     "effq_seg_labels_source": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P]),
+    "effq_seg_probs_source": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "effq_seg_agreement": (_I, [_P, _P, _I, _LL, _I, _I, _F, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_cc_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_cc_label": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),

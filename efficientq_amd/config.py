@@ -126,6 +126,14 @@ def build_parser():
     p.add_argument('--thresh', default=None, metavar='VALUE',
                    help='ptq, predict, with --multi_label: decide every channel at this threshold instead of sigmoid >= '
                         '0.5: a probability P (0 < P < 1) or logit:X')
+    # the probabilities behind the label maps of predict; refused by name in the other missions (prob_switches)
+    p.add_argument('--save_prob', action='store_true',
+                   help='predict: also write <out_dir>/prob/<subject>.nii.gz, the probability of every class (softmax) or '
+                        'raw channel (sigmoid, with --multi_label) on the scan\'s grid: uint8 (SD, SH, SW, C), scl_slope '
+                        '1/255')
+    p.add_argument('--save_unc', action='store_true',
+                   help='predict: also write <out_dir>/unc/<subject>.nii.gz, one uncertainty per voxel of the scan\'s grid '
+                        '(entropy as a share of its maximum): uint8, scl_slope 1/255')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
@@ -199,6 +207,22 @@ def thr_switches(args, mission=None):
             raise SystemExit(f'--thresh {given}: without --multi_label the classes are decided by argmax (class-id mode), '
                              f'which has no threshold: it needs --multi_label')
     return sweep, thresh
+
+
+def prob_switches(args, mission=None):
+    """(save_prob, save_unc) of --save_prob / --save_unc (or the YAML keys `save_prob`, `save_unc`); the missions that
+    write no maps on a scan's grid refuse them by name (SystemExit), host only."""
+    mission = mission or getattr(args, 'mission', None)
+    got = tuple(bool(getattr(args, k, False)) for k in ('save_prob', 'save_unc'))
+    for on, switch in zip(got, ('save_prob', 'save_unc')):
+        if on and mission == 'prep':
+            raise SystemExit(f'--{switch} writes the probabilities behind a predicted label map: the prep mission '
+                             f'predicts nothing, drop --{switch}')
+        if on and mission == 'ptq':
+            raise SystemExit(f'--{switch} writes maps on the grid of a source scan: the ptq mission validates on the '
+                             f'working grid (--save_nii writes its label maps), it belongs to the predict mission: drop '
+                             f'--{switch}')
+    return got
 
 
 POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES

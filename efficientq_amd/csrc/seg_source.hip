@@ -19,15 +19,12 @@
 // reads per channel and voxel, neighbours in w share lines, the d and h corners come back from L2; measured, the pass runs
 // at about a tenth of the HBM rate: the gather and the per-voxel work set its time, not the bytes.  No atomics, no reductions: equal inputs
 // give equal bits.  Every index is 32-bit: the voxel counts are checked to lie below 2^31.
+// src_axis, the eight-corner blend, the store and the checks live in seg_source.h, shared with seg_prob.hip.
 #include "common.h"
 #include "seg_decide.h"
+#include "seg_source.h"
 
 namespace effq {
-
-constexpr int SRC_THREADS = 256;
-constexpr int SRC_MAX_BLOCKS = 4096;
-
-struct __attribute__((packed, aligned(1))) SByte4 { uint8_t x, y, z, w; };
 
 struct SourceParams {
   const float* logits;      // (C, gd, gh, gw)
@@ -38,30 +35,6 @@ struct SourceParams {
   int fuse, al4;            // al4: every group of four lies on a 4-B boundary
   float thresh;
 };
-
-struct SrcAxis {
-  unsigned i0, i1;
-  float l0, l1;
-  bool inside;
-};
-
-__device__ __forceinline__ SrcAxis src_axis(unsigned s, double f, int G, int pmin, int g) {
-  SrcAxis a;
-  const double t = ((double)s + 0.5) / f;
-  double n = floor(t);
-  const double last = (double)(G - 1);
-  n = n > last ? last : n;
-  a.inside = n >= (double)pmin && n < (double)(pmin + g);
-  double q = t - 0.5 - (double)pmin;
-  const double top = (double)(g - 1);
-  q = q < 0.0 ? 0.0 : (q > top ? top : q);
-  const double fl = floor(q);
-  a.i0 = (unsigned)fl;
-  a.i1 = a.i0 + (a.i0 < (unsigned)(g - 1) ? 1u : 0u);
-  a.l1 = (float)(q - fl);
-  a.l0 = 1.0f - a.l1;
-  return a;
-}
 
 template <int RULE, int C>
 __global__ __launch_bounds__(SRC_THREADS) void k_seg_labels_source(SourceParams p) {
@@ -88,29 +61,12 @@ __global__ __launch_bounds__(SRC_THREADS) void k_seg_labels_source(SourceParams 
         float v[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          const unsigned o = (unsigned)c * plane;
-          // the order of k_prep_resample_linear: l0d (l0h (l0w v000 + l1w v001) + l1h (...)) + l1d (...), fp32
-          const float a = ad.l0 * (ah.l0 * (aw.l0 * r00[o + aw.i0] + aw.l1 * r00[o + aw.i1]) +
-                                   ah.l1 * (aw.l0 * r01[o + aw.i0] + aw.l1 * r01[o + aw.i1]));
-          const float b = ad.l1 * (ah.l0 * (aw.l0 * r10[o + aw.i0] + aw.l1 * r10[o + aw.i1]) +
-                                   ah.l1 * (aw.l0 * r11[o + aw.i0] + aw.l1 * r11[o + aw.i1]));
-          v[c] = a + b;
+          v[c] = src_blend(r00, r01, r10, r11, (unsigned)c * plane, ad, ah, aw);   // seg_source.h: the fp32 nesting order
         }
         lab[u] = (uint8_t)label_of<RULE, C>(predict<MODE, C>(v, p.fuse, p.thresh));
       }
     }
-    uint8_t* dst = p.out + (size_t)row * p.SW + w0;
-    if (w0 + 4 <= p.SW) {
-      if (p.al4) {
-        *reinterpret_cast<uchar4*>(dst) = make_uchar4(lab[0], lab[1], lab[2], lab[3]);
-      } else {
-        SByte4 o;
-        o.x = lab[0]; o.y = lab[1]; o.z = lab[2]; o.w = lab[3];
-        *reinterpret_cast<SByte4*>(dst) = o;
-      }
-    } else {
-      for (unsigned u = 0; w0 + u < p.SW; ++u) dst[u] = lab[u];
-    }
+    src_store4(p.out + (size_t)row * p.SW + w0, lab, w0, p.SW, p.al4);
   }
 }
 
@@ -122,11 +78,6 @@ static void launch_source(int rule, dim3 g, hipStream_t st, const SourceParams& 
     case EFFQ_SEG_LABEL_BRATS: hipLaunchKernelGGL((k_seg_labels_source<EFFQ_SEG_LABEL_BRATS, C>), g, t, 0, st, p); break;
     default: hipLaunchKernelGGL((k_seg_labels_source<EFFQ_SEG_LABEL_RANK, C>), g, t, 0, st, p); break;
   }
-}
-
-// the checks of prep_fits (prep.hip)
-static inline bool source_fits(long long N, long long D, long long H, long long W) {
-  return N > 0 && D > 0 && H > 0 && W > 0 && D <= 32767 && H <= 32767 && W <= 32767 && N * D * H * W < (1ll << 31);
 }
 
 }  // namespace effq
@@ -157,10 +108,7 @@ int effq_seg_labels_source(const float* logits, int C, const int* box, const int
   for (int a = 0; a < 3; ++a) { p.G[a] = grid[a]; p.pmin[a] = pmin[a]; p.g[a] = box[a]; p.f[a] = factors[a]; }
   p.fuse = fuse; p.thresh = thresh;
   p.al4 = source[2] % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-  const size_t items = (size_t)source[0] * source[1] * ((source[2] + 3) / 4);
-  size_t nb = (items + SRC_THREADS - 1) / SRC_THREADS;
-  nb = nb < 1 ? 1 : (nb > (size_t)SRC_MAX_BLOCKS ? (size_t)SRC_MAX_BLOCKS : nb);
-  const dim3 g((unsigned)nb);
+  const dim3 g(source_blocks(source));
   const hipStream_t st = as_stream(stream);
   switch (C) {
     case 1: launch_source<1>(rule, g, st, p); break;

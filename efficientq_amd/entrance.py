@@ -245,6 +245,7 @@ def check_switches(args):
     Cf.blend_switches(args)
     check_post(args)
     Cf.thr_switches(args)
+    Cf.prob_switches(args)
     if not getattr(args, 'unlabelled', False):
         return
     if not getattr(args, 'vs_fp', False):
@@ -284,6 +285,7 @@ def main(argv=None):
     if args.mission == 'prep':
         check_post(args)
         Cf.thr_switches(args)
+        Cf.prob_switches(args)
         from . import prep
         prep.run(args)
         return

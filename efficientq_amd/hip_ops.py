@@ -1352,6 +1352,44 @@ class HipOps:
                                               fcode, thresh, _ptr(out), self.stream), "effq_seg_labels_source")
         return out
 
+    def seg_probs_source(self, logits: torch.Tensor, pmin, grid, factors, source_shape, mode: str,
+                         want_prob: bool = True, want_unc: bool = False):
+        """The probability planes and the uncertainty of one subject on its SOURCE grid (effq_seg_probs_source):
+        `logits`, `pmin`, `grid`, `factors` and `source_shape` as seg_labels_source, whose interpolated logits these are
+        computed from.  mode 'argmax' (class ids: softmax over the C channels, entropy as a share of ln C) or 'sigmoid'
+        (per raw channel; the largest binary entropy in bits).  Returns (probs, unc): C x source and source, uint8 levels
+        of 1 / 255, each None when not wanted; outside the box probs are 0 (argmax: channel 0 is 255) and unc is 0."""
+        x = self._f32(logits)
+        if x.dim() != 4:
+            raise _lib.EffqError(f"seg_probs_source: expected C x d x h x w logits, got {tuple(x.shape)}")
+        Cc = int(x.shape[0])
+        code = {"argmax": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID}.get(mode)
+        if code is None:
+            raise _lib.EffqError(f"seg_probs_source: unknown mode {mode!r} (argmax or sigmoid)")
+        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
+            raise _lib.EffqError(f"seg_probs_source: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
+        if not (want_prob or want_unc):
+            raise _lib.EffqError("seg_probs_source: neither the probabilities nor the uncertainty is wanted")
+        try:
+            lo, G, src = (tuple(int(v) for v in t) for t in (pmin, grid, source_shape))
+            f = (1.0, 1.0, 1.0) if factors is None else tuple(float(v) for v in factors)
+        except (TypeError, ValueError) as e:
+            raise _lib.EffqError(f"seg_probs_source: {e}") from e
+        if len(lo) != 3 or len(G) != 3 or len(src) != 3 or len(f) != 3 or x.numel() == 0:
+            raise _lib.EffqError(f"seg_probs_source: box at {lo} of {tuple(x.shape[1:])}, grid {G}, factors {f}, source "
+                                 f"{src}: three values each")
+        planes = Cc if want_prob else 1
+        if min(src) < 1 or max(src) > 32767 or planes * math.prod(src) >= 2 ** 31:   # the outputs are not allocated for these
+            raise _lib.EffqError(f"seg_probs_source: source grid {src}, {planes} planes: 1 to 32767 along an axis, "
+                                 f"2^31 - 1 bytes at most")
+        probs = torch.empty((Cc,) + src, dtype=torch.uint8, device=self.device) if want_prob else None
+        unc = torch.empty(src, dtype=torch.uint8, device=self.device) if want_unc else None
+        i3 = C.c_int * 3
+        check(self.lib.effq_seg_probs_source(_ptr(x), Cc, i3(*(int(v) for v in x.shape[1:])), i3(*lo), i3(*G),
+                                             (C.c_double * 3)(*f), i3(*src), code, _ptr(probs), _ptr(unc), self.stream),
+              "effq_seg_probs_source")
+        return probs, unc
+
     def seg_agreement(self, logits_q: torch.Tensor, logits_fp: torch.Tensor, mode: str, fuse: Optional[str] = None,
                       want_map: bool = False):
         """Where and how much two networks differ on one case (effq_seg_agreement): the stitched last-head logits of the

@@ -38,7 +38,7 @@ FIELDS = (("sizeof_hdr", "i", 0), ("dim", "8h", 40), ("datatype", "h", 70), ("bi
           ("srow_y", "4f", 296), ("srow_z", "4f", 312), ("magic", "4s", 344))
 
 
-def _header(shape, dtype: np.dtype, affine: np.ndarray, geometry=None) -> bytes:
+def _header(shape, dtype: np.dtype, affine: np.ndarray, geometry=None, scale=None) -> bytes:
     hdr = bytearray(HEADER_BYTES)
     dim = [len(shape)] + list(shape) + [1] * (7 - len(shape))
     values = {"sizeof_hdr": (HEADER_BYTES,), "dim": dim, "datatype": (_CODES[dtype],), "bitpix": (8 * dtype.itemsize,),
@@ -51,14 +51,24 @@ def _header(shape, dtype: np.dtype, affine: np.ndarray, geometry=None) -> bytes:
                        "sform_code": (int(geometry["sform_code"]),), "quatern": list(geometry["quatern"]),
                        "srow_x": list(geometry["srow_x"]), "srow_y": list(geometry["srow_y"]),
                        "srow_z": list(geometry["srow_z"])})
+    if scale is not None:                                              # value = scl_slope * stored + scl_inter
+        values.update({"scl_slope": (float(scale[0]),), "scl_inter": (float(scale[1]),)})
     for name, fmt, off in FIELDS:
         struct.pack_into("<" + fmt, hdr, off, *values[name])
     hdr[38:39] = b"r"                                                  # `regular`, as the ANALYZE readers expect
     return bytes(hdr)
 
 
-def encode_nifti(array, affine=None, geometry=None) -> bytes:
+def encode_nifti(array, affine=None, geometry=None, scale=None) -> bytes:
     """The uncompressed ``.nii`` bytes of a uint8 / uint16 array of 1 to 7 dimensions; see write_nifti."""
+    if scale is not None:
+        try:
+            slope, inter = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"write_nifti: scale {scale!r}, needs (slope, inter)")
+        if not (np.isfinite(slope) and np.isfinite(inter)) or slope == 0.0:
+            raise ValueError(f"write_nifti: scale {scale!r}: a finite slope other than 0 and a finite inter")
+        scale = (slope, inter)
     a = np.asarray(array)
     if a.dtype.newbyteorder("=") not in _CODES:
         raise ValueError(f"write_nifti: {a.dtype} data, only uint8 and uint16 are written")
@@ -74,17 +84,19 @@ def encode_nifti(array, affine=None, geometry=None) -> bytes:
             raise ValueError(f"write_nifti: array of shape {a.shape} for a geometry of shape {tuple(geometry['shape'])}")
     dt = a.dtype.newbyteorder("=")
     data = np.asarray(a, dtype=dt.newbyteorder("<")).tobytes(order="F")
-    return _header(a.shape, dt, aff, geometry) + b"\0" * (VOX_OFFSET - HEADER_BYTES) + data
+    return _header(a.shape, dt, aff, geometry, scale) + b"\0" * (VOX_OFFSET - HEADER_BYTES) + data
 
 
-def write_nifti(path: str, array, affine=None, geometry=None) -> None:
+def write_nifti(path: str, array, affine=None, geometry=None, scale=None) -> None:
     """Write `array` (uint8 / uint16) to `path` as a single-file NIfTI-1 image with the given 4 x 4 affine (identity by
     default); a path ending in ``.gz`` is gzip-compressed with no name and mtime 0.  With `geometry` (what read_geometry
     returned for the scan the map belongs to) the header carries that image's sform and qform fields, both codes, its
     ``pixdim`` and its ``xyzt_units`` (what unit the pixdim are in) instead; the other fields of the source header
     (descrip, intent, cal_min / cal_max, slice timing) are not copied.  The array's first three axes are the image's i,
-    j, k and must have the source's extents."""
-    raw = encode_nifti(array, affine, geometry)
+    j, k and must have the source's extents.  With `scale` = (slope, inter) the header's ``scl_slope`` and ``scl_inter``
+    are set, so a reader shows ``slope * stored + inter`` (the probability maps of ``predict --save_prob``: 1 / 255 and
+    0); without it both are 0, which means no scaling, and the bytes are what they were."""
+    raw = encode_nifti(array, affine, geometry, scale)
     with open(path, "wb") as f:
         if str(path).endswith(".gz"):
             with gzip.GzipFile(filename="", mode="wb", compresslevel=GZIP_LEVEL, fileobj=f, mtime=0) as gz:

@@ -40,6 +40,15 @@ after all others, and ``labels``, ``voxels`` and ``volume_ml`` are the cleaned m
 at that threshold instead of sigmoid >= 0.5.  ``predict.csv`` then gains the column ``thresh`` (the fp32 logit, ``%.9g``)
 after the blend columns and before the post columns; ``0.5`` and ``logit:0`` are the default and change nothing.
 
+``--save_prob`` also writes ``<out_dir>/prob/<subject>.nii.gz``, uint8 ``(SD, SH, SW, C)`` on the scan's grid with the
+scan's header and ``scl_slope`` 1/255: the softmax over the C classes (class-id mode) or the sigmoid of every raw channel
+(``--multi_label``; ``--merge_type`` and ``--thresh`` do not enter) of the logits interpolated exactly as for the label
+map (effq_seg_probs_source, one call per subject).  ``--save_unc`` writes ``<out_dir>/unc/<subject>.nii.gz``, one uint8
+per voxel with the same slope: the entropy over the classes as a share of ln C, or the largest binary entropy of a
+channel in bits.  Outside the box the probabilities are the background's (class-id: channel 0 is 255; sigmoid: all 0)
+and the uncertainty is 0.  ``--blend`` and ``--tta_mirror`` act through the logits, ``--post`` does not touch these
+files, ``predict.csv`` is unchanged, and without the switches nothing changes.
+
 Everything the list and the headers decide, a ``--thresh`` that is not understood or given without ``--multi_label``, a ``--post`` rule that is not understood, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
 and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
 """
@@ -62,6 +71,8 @@ from .prep import PrepError
 
 PREDICT_CSV = "predict.csv"
 MAX_PENDING_WRITES = 2        # host maps waiting for the writing thread at most
+PROB_DIR, UNC_DIR = "prob", "unc"     # under out_dir, made only for --save_prob / --save_unc
+PROB_SCALE = (1.0 / 255.0, 0.0)       # scl_slope, scl_inter of both: a reader shows values in [0, 1]
 CSV_HEADER = ["subject", "source_shape", "source_spacing", "grid_shape", "pmin", "pmax", "windows", "prep_mask",
               "prep_window", "prep_spacing", "prep_min_size", "patch_size", "labels", "voxels", "volume_ml"]
 
@@ -120,7 +131,7 @@ def _write_csv(path: str, rows: List[dict], header=CSV_HEADER) -> None:
 
 def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     """The `predict` mission of `args` (config.build_parser); returns the rows of predict.csv.  `ops`: the object whose
-    prep_*, window_* and seg_labels_source methods do the device work and whose `device` holds the tensors
+    prep_*, window_*, seg_labels_source and (for --save_prob / --save_unc) seg_probs_source methods do the device work and whose `device` holds the tensors
     (hip_ops.get_ops(args.device) by default); `model`: the network, already on that device and in its mode (by default
     the one --resume / --pretrain name); `window_batch`: windows per forward (None: sized from the first window's peak
     memory, as validate_seg sizes it)."""
@@ -175,6 +186,8 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     sliding = (blend, flips) != ("uniform", (0,))
     post, post_conn = Cf.post_rules(args)
     _, thresh = Cf.thr_switches(args, 'predict')
+    save_prob, save_unc = Cf.prob_switches(args, 'predict')
+    prob_mode = "argmax" if rule == "argmax" else "sigmoid"
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
@@ -200,6 +213,22 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         print(f"[predict] --thresh {args.thresh}: every channel is decided at logit >= {thresh:.9g} (sigmoid >= "
               f"{E.logit_prob(thresh):.6g})")
         ops.set_decision_threshold(thresh)
+    if save_prob or save_unc:
+        nc = getattr(args, "nClass", None)
+        what = " and ".join(w for w, on in ((f"{PROB_DIR}/<subject>.nii.gz (SD, SH, SW, C)", save_prob),
+                                            (f"{UNC_DIR}/<subject>.nii.gz", save_unc)) if on)
+        how = (f"softmax over {nc if nc else 'the'} classes, uncertainty = entropy / ln C" if prob_mode == "argmax" else
+               "sigmoid per channel, uncertainty = the largest binary entropy of a channel in bits")
+        print(f"[predict] {what}: {how}, from the logits interpolated as for the label map; uint8 in steps of 1/255 "
+              f"(scl_slope), --post does not touch them")
+        if save_prob and prob_mode == "sigmoid" and (fuse or thresh is not None):
+            given = " and ".join(w for w, on in ((f"--merge_type {fuse}", fuse), (f"--thresh {getattr(args, 'thresh', None)}",
+                                                                                 thresh is not None)) if on)
+            print(f"[predict] --save_prob: {given} decide the label map only: the probabilities are the network's, per "
+                  f"raw channel, not a decision's")
+        for on, sub in ((save_prob, PROB_DIR), (save_unc, UNC_DIR)):
+            if on:
+                os.makedirs(P.join(out_dir, sub), exist_ok=True)
     post_said = Cf.post_text(post, post_conn) if post else None
     if post:
         used.update(post=post_said)
@@ -207,6 +236,12 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     bsz = window_batch
     reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-read")
     writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-write")
+
+    def write(path, host, geometry, scale=None):
+        while len(writes) >= MAX_PENDING_WRITES:       # gzip slower than the device: wait, do not pile maps up
+            writes.pop(0).result()
+        writes.append(writer.submit(nifti.write_nifti, path, host, None, geometry, scale))
+
     try:
         nxt = reader.submit(prep._load, entries[0], mods)
         for i, plan in enumerate(plans):
@@ -230,9 +265,24 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                 cleaned = f", post {post_said}: {changed} voxels relabelled"
             counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
             host = labels.cpu().numpy()
-            while len(writes) >= MAX_PENDING_WRITES:       # gzip slower than the device: wait, do not pile maps up
-                writes.pop(0).result()
-            writes.append(writer.submit(nifti.write_nifti, P.join(out_dir, f"{sn}.nii.gz"), host, None, plan.header))
+            write(P.join(out_dir, f"{sn}.nii.gz"), host, plan.header)
+            extra = ""
+            if save_prob or save_unc:       # from the same stitched logits, on the same grid; --post does not enter
+                probs, unc = ops.seg_probs_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.oriented_shape,
+                                                  prob_mode, save_prob, save_unc)
+                if plan.orient is not None and not prep.orient_is_identity(*plan.orient):
+                    back = prep.orient_inverse(*plan.orient)
+                    probs = ops.prep_reorient(probs, *back) if save_prob else None      # the C planes as N = C volumes
+                    unc = ops.prep_reorient(unc, *back) if save_unc else None
+                if save_prob:       # (C, SD, SH, SW) -> the view (SD, SH, SW, C): a 4-D image, pixdim[4] = 1
+                    geo = dict(plan.header, pixdim=tuple(plan.header["pixdim"][:4]) + (1.0,) +
+                               tuple(plan.header["pixdim"][5:]))
+                    write(P.join(out_dir, PROB_DIR, f"{sn}.nii.gz"), np.moveaxis(probs.cpu().numpy(), 0, -1), geo,
+                          PROB_SCALE)
+                    extra += f", {PROB_DIR}/{sn}.nii.gz ({probs.shape[0]} channels)"
+                if save_unc:
+                    write(P.join(out_dir, UNC_DIR, f"{sn}.nii.gz"), unc.cpu().numpy(), plan.header, PROB_SCALE)
+                    extra += f", {UNC_DIR}/{sn}.nii.gz"
             present = [v for v, n in enumerate(counts) if n]
             ml = float(np.prod(plan.source_spacing)) / 1000.0
             row = {"subject": sn, "source_shape": prep._fmt(plan.source_shape),
@@ -250,7 +300,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned} -> grid {prep._fmt(plan.grid_shape)}, box at "
                   f"{prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
                   f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
-                  f"{row['voxels']} voxels{cleaned}")
+                  f"{row['voxels']} voxels{cleaned}{extra}")
     finally:
         reader.shutdown(wait=True, cancel_futures=True)
         writer.shutdown(wait=True)

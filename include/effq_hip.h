@@ -697,6 +697,22 @@ int effq_seg_labels_source(const float* logits, int C, const int* box, const int
                            const double* factors, const int* source, int rule, int fuse, float thresh, uint8_t* out,
                            void* stream);
 
+/* Probabilities and an uncertainty on the source grid (`predict --save_prob / --save_unc`): logits, C, box, pmin, grid,
+ * factors and source as effq_seg_labels_source, with its argument checks; v_c, the logit of channel c at a source
+ * voxel, is interpolated exactly as there (the same fp64 axis arithmetic, inside rule and fp32 corner order).  probs
+ * (C, source) uint8 and unc (source) uint8 hold rintf(255 x), half to even, a NaN x as 0; either may be null, not both.
+ *   EFFQ_SEG_ARGMAX:  p_c = exp(v_c - m) / S with m = max v and S = sum_c exp(v_c - m); u = (ln S - sum_c p_c (v_c - m))
+ *                     / ln C, the entropy over the C classes as a share of its maximum; C = 1: p = 1, u = 0.  Channels
+ *                     equal to an infinite m count as v_c - m = 0 (k channels at +inf: 1 / k each).
+ *   EFFQ_SEG_SIGMOID: p_c = 1 / (1 + exp(-v_c)) per raw channel (no merge, no threshold); u = max_c h(v_c), the binary
+ *                     entropy of p_c in bits, computed from |v_c|.
+ * Outside the box: SIGMOID every channel 0, ARGMAX channel 0 = 255 and the others 0; u = 0.  fp32 with expf, logf and
+ * true divisions: 255 p within 5e-4 and 255 u within 1e-3 of the exact value of the fp32 v_c, before the rounding to a
+ * level.  With probs, C times the voxels of source < 2^31.  One launch, no atomics, no reductions: equal inputs give
+ * equal bits. */
+int effq_seg_probs_source(const float* logits, int C, const int* box, const int* pmin, const int* grid,
+                          const double* factors, const int* source, int mode, uint8_t* probs, uint8_t* unc, void* stream);
+
 /* ---- connected components of 0/1 volumes and the lesion-level columns of the validation (validate_seg(..., is_cc=True):
  * utils/validate.py:28-36, utils/metrics.py:69-94: num_component, num_false_positive, num_positive, num_false_negative,
  * there with scipy.ndimage.label on the host).  Block-based union-find: tiles of 8 x 8 x 32 voxels are labelled in LDS,

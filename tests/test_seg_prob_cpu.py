@@ -1,0 +1,307 @@
+"""`predict --save_prob / --save_unc`, host side (no GPU): hand-computed values of the restatement (seg_prob_ref), the
+parser and the YAML keys, the refusals of `prep` and `ptq`, the C-ABI row of effq_seg_probs_source, the `scale` of the
+NIfTI writer, and the whole mission driven through numpy stand-ins whose seg_probs_source answers from the restatement."""
+import hashlib
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from efficientq_amd import _lib, config as Cf, entrance, evaluate as E, nifti, predict, prep
+from tests import seg_prob_ref as R
+from tests.test_orient_cpu import CANON, VARIANTS, ref_reorient, variant_affine
+from tests.test_predict_cpu import PointNet, PredictOps, ct_like, predict_args, write_cases
+from tests.test_prep_cpu import write_scan, written
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- the restatement --------------------------------------------------------------------------------------------------
+def test_restatement_matches_hand_computed_values():
+    ln = np.log
+    v = np.zeros((3, 1, 1, 6), dtype=np.float32)
+    v[:, 0, 0, 0] = (0.0, 0.0, 0.0)                      # uniform: 1/3 each, u = 1
+    v[:, 0, 0, 1] = (2.0, 2.0, -np.inf)                  # two equal maxima, one impossible class: 1/2, 1/2, 0
+    v[:, 0, 0, 2] = (np.inf, 1.0, np.inf)                # two channels at +inf share the mass
+    v[:, 0, 0, 3] = (-np.inf, -np.inf, -np.inf)          # all at -inf: uniform
+    v[:, 0, 0, 4] = (np.nan, 1.0, 2.0)                   # NaN anywhere: every value NaN, stored as 0
+    v[:, 0, 0, 5] = (100.0, 0.0, -100.0)                 # decided
+    # the definitions themselves (through the interpolation a weight of 0 times an infinite neighbour is NaN, as in the
+    # label kernel: the planted values are looked at one voxel at a time)
+    p, u = R.probs_of(v[:, 0, 0], "argmax")
+    P, U = 255 * p, 255 * u
+    assert p[:, 0] == pytest.approx([1 / 3] * 3, abs=1e-15) and u[0] == pytest.approx(1.0, abs=1e-15)
+    assert p[:, 1].tolist() == [0.5, 0.5, 0.0] and u[1] == pytest.approx(ln(2) / ln(3), abs=1e-15)
+    assert p[:, 2].tolist() == [0.5, 0.0, 0.5] and u[2] == pytest.approx(ln(2) / ln(3), abs=1e-15)
+    assert p[:, 3] == pytest.approx([1 / 3] * 3, abs=1e-15) and u[3] == pytest.approx(1.0, abs=1e-15)
+    assert np.isnan(p[:, 4]).all() and np.isnan(u[4])
+    assert p[:, 5] == pytest.approx([1.0, np.exp(-100.0), 0.0], abs=1e-60) and 0 <= u[5] < 1e-40
+    assert R.stored(P).T.tolist() == [[85, 85, 85], [128, 128, 0], [128, 0, 128], [85, 85, 85], [0, 0, 0], [255, 0, 0]]
+    assert R.stored(U).tolist() == [255, 161, 161, 255, 0, 0]              # 255 ln 2 / ln 3 = 160.9
+    # sigmoid: per raw channel; u = the largest binary entropy in bits
+    p, u = R.probs_of(v[:, 0, 0], "sigmoid")
+    assert p[:, 0].tolist() == [0.5] * 3 and u[0] == pytest.approx(1.0, abs=1e-15)
+    s2 = 1 / (1 + np.exp(-2.0))
+    h2 = -(s2 * np.log2(s2) + (1 - s2) * np.log2(1 - s2))
+    assert p[:, 1] == pytest.approx([s2, s2, 0.0], abs=1e-15) and u[1] == pytest.approx(h2, abs=1e-14)
+    assert p[:, 2] == pytest.approx([1.0, 1 / (1 + np.exp(-1.0)), 1.0], abs=1e-15)
+    assert p[:, 3].tolist() == [0.0] * 3 and u[3] == 0.0
+    assert np.isnan(p[0, 4]) and not np.isnan(p[1:, 4]).any() and np.isnan(u[4])
+    assert u[5] == pytest.approx(1.0, abs=1e-15)                                  # the channel at logit 0
+    # one class: p = 1, u = 0
+    p, u = R.probs_of(v[:1, 0, 0], "argmax")
+    assert p[0, :4].tolist() == [1.0] * 4 and u[:4].tolist() == [0.0] * 4 and np.isnan(p[0, 4]) and np.isnan(u[4])
+    # through the interpolation, f = 1 and a box of two voxels: the values inside, the background outside
+    w = np.array([[[[0.0, 1.0]]], [[[0.0, -1.0]]], [[[0.0, 3.0]]]], dtype=np.float32)
+    P, U, inside, x = R.ref_probs_source(w, (0, 0, 2), (1, 1, 6), None, (1, 1, 6), "argmax")
+    assert inside.ravel().tolist() == [False, False, True, True, False, False]
+    assert x.dtype == np.float32 and np.array_equal(x[:, :, :, 2:4], w)
+    assert P[:, 0, 0, 0].tolist() == [255.0, 0.0, 0.0] and U[0, 0, 0] == 0.0
+    assert P[:, 0, 0, 2] == pytest.approx([85.0] * 3, abs=1e-12) and U[0, 0, 2] == pytest.approx(255.0, abs=1e-12)
+    assert np.array_equal(P[:, 0, 0, 3], 255 * R.probs_of(w[:, 0, 0, 1:], "argmax")[0][:, 0])
+    P, U, _, _ = R.ref_probs_source(w, (0, 0, 2), (1, 1, 6), None, (1, 1, 6), "sigmoid")
+    assert P[:, 0, 0, 5].tolist() == [0.0, 0.0, 0.0] and U[0, 0, 5] == 0.0 and P[:, 0, 0, 2].tolist() == [127.5] * 3
+    # half to even, NaN to 0
+    assert R.stored([127.5, 128.5, 0.5, 254.5, np.nan]).tolist() == [128, 128, 0, 254, 0]
+    assert R.E_PROB < 0.01 and R.E_UNC < 0.01
+
+
+def test_fp32_interpolation_of_the_restatement_is_the_label_restatement_up_to_rounding():
+    from tests.test_predict_cpu import ref_labels_source
+    g = np.random.default_rng(5)
+    logits = (4 * g.standard_normal((3, 4, 5, 3))).astype(np.float32)
+    args = ((1, 1, 2), (6, 7, 5), (1.5, 1.4, 2.5), (9, 10, 12))
+    v, inside = R.ref_logits_source(logits, *args)
+    lab, _, inside64 = ref_labels_source(logits, *args, "argmax")
+    assert np.array_equal(inside, inside64) and 0 < inside.sum() < inside.size
+    assert np.array_equal(np.argmax(v, 0)[inside], lab[inside])                 # no near-tie in this draw
+    # f = 1: the weights are 0 and 1 and the values are the logits themselves
+    v, inside = R.ref_logits_source(logits, (1, 1, 2), (6, 7, 5), None, (6, 7, 5))
+    assert np.array_equal(v[:, 1:5, 1:6, 2:5], logits) and inside.sum() == 4 * 5 * 3
+
+
+# ---- the switches -----------------------------------------------------------------------------------------------------------
+def test_parser_and_yaml_know_both_switches(tmp_path):
+    a = Cf.build_parser().parse_args(["predict", "--task", "lits"])
+    assert a.save_prob is False and a.save_unc is False and Cf.prob_switches(a) == (False, False)
+    assert Cf.prob_switches(Cf.make_args(Cf.TINY_NET, 4, 4)) == (False, False)        # arguments from before the switches
+    a = Cf.build_parser().parse_args(["predict", "--task", "lits", "--save_prob"])
+    assert Cf.prob_switches(a) == (True, False)
+    a = Cf.build_parser().parse_args(["predict", "--task", "lits", "--save_unc"])
+    assert Cf.prob_switches(a) == (False, True)
+    cfg = tmp_path / "p.yaml"
+    cfg.write_text("save_prob: true\nsave_unc: true\n")
+    assert Cf.prob_switches(Cf.merge_config(str(cfg), predict_args())) == (True, True)
+    cfg.write_text("save_unc: false\n")
+    assert Cf.prob_switches(Cf.merge_config(str(cfg), predict_args("--save_unc"))) == (False, False)   # YAML wins
+
+
+@pytest.mark.parametrize("mission", ["prep", "ptq"])
+@pytest.mark.parametrize("switch", ["--save_prob", "--save_unc"])
+def test_prep_and_ptq_refuse_the_switches_by_name_before_anything_is_created(tmp_path, mission, switch):
+    with pytest.raises(SystemExit) as e:
+        entrance.main([mission, "--task", "lits", switch, "--snap_dir", str(tmp_path / "snap"), "--data_dir",
+                       str(tmp_path / "data"), "--split_dir", str(tmp_path / "split"), "--src_list",
+                       str(tmp_path / "none.csv"), "--out_dir", str(tmp_path / "seg"), "--qlvl_w", "4", "--qlvl_a", "4"])
+    assert switch in str(e.value) and mission in str(e.value) and "predict" in str(e.value)
+    assert os.listdir(str(tmp_path)) == []
+    # the YAML key is refused as the switch is
+    cfg = tmp_path / "p.yaml"
+    cfg.write_text(f"{switch[2:]}: true\n")
+    with pytest.raises(SystemExit) as e:
+        entrance.main([mission, "--task", "lits", "--config", str(cfg), "--out_dir", str(tmp_path / "seg"), "--snap_dir",
+                       str(tmp_path / "snap"), "--qlvl_w", "4", "--qlvl_a", "4"])
+    assert switch in str(e.value) and os.listdir(str(tmp_path)) == ["p.yaml"]
+
+
+def test_header_and_lib_row_of_the_source_probabilities_have_matching_signatures():
+    hdr = open(os.path.join(ROOT, "include", "effq_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    found = re.findall(r"\bint (effq_seg_probs_source)\s*\((.*?)\)\s*;", code, flags=re.S)
+    assert len(found) == 1
+
+    def ctype(decl):
+        decl = decl.strip()
+        if "*" in decl:
+            return _lib._P
+        return {"int": _lib._I, "float": _lib._F, "double": _lib._D}[decl.split()[0]]
+    res, got = _lib.SIGNATURES["effq_seg_probs_source"]
+    assert res == _lib._I and got == [ctype(a) for a in found[0][1].split(",")] and len(got) == 11
+    names = [a.strip().split()[-1].lstrip("*") for a in found[0][1].split(",")]
+    assert names == ["logits", "C", "box", "pmin", "grid", "factors", "source", "mode", "probs", "unc", "stream"]
+    assert "seg_prob.hip" in open(os.path.join(ROOT, "efficientq_amd", "csrc", "Makefile")).read()
+    src = open(os.path.join(ROOT, "efficientq_amd", "csrc", "seg_prob.hip")).read()
+    body = re.sub(r"//.*", "", src)
+    assert not re.search(r"atomic\w*\s*\(", body)                      # deterministic: no atomics at all
+    assert not re.search(r"__expf|__logf|__fdividef", body)            # the accurate functions: the bound is derived for them
+    # one definition of the coordinates and the blend for both kernels
+    lab = open(os.path.join(ROOT, "efficientq_amd", "csrc", "seg_source.hip")).read()
+    shared = open(os.path.join(ROOT, "efficientq_amd", "csrc", "seg_source.h")).read()
+    for text in (src, lab):
+        assert '#include "seg_source.h"' in text and "src_axis(" in text and "src_blend(" in text
+        assert "SrcAxis src_axis(" not in text
+    assert "SrcAxis src_axis(" in shared and "float src_blend(" in shared
+
+
+# ---- the writer -----------------------------------------------------------------------------------------------------------------
+def test_scale_fills_the_slope_and_the_bytes_without_it_are_the_earlier_ones(tmp_path):
+    a = (np.arange(5 * 6 * 7, dtype=np.uint8).reshape(5, 6, 7) * 3)
+    aff = np.array([[0.0, -1.0, 0, 30.0], [1.0, 0.0, 0, -4.0], [0, 0, 2.0, 5.0], [0, 0, 0, 1.0]])
+    b = np.arange(2 * 3 * 4 * 2, dtype=np.uint8).reshape(2, 3, 4, 2)
+    # the digests of what encode_nifti gave for these arrays before `scale` existed
+    assert hashlib.sha256(nifti.encode_nifti(a, aff)).hexdigest() == \
+        "9088567cc5316bbf02fcbb56d79befcc6d603861adfaf0bc475d7f6814545547"
+    assert hashlib.sha256(nifti.encode_nifti(b)).hexdigest() == \
+        "d4da166904a8099d91c7add4f0e446b815e76988cf5aa722fdbb34025508839e"
+    plain, scaled = nifti.encode_nifti(a, aff), nifti.encode_nifti(a, aff, scale=(1 / 255, 0))
+    differ = [i for i in range(len(plain)) if plain[i] != scaled[i]]
+    assert differ and set(differ) <= set(range(112, 116))                # scl_slope alone (scl_inter stays 0)
+    for gz in (".nii", ".nii.gz"):
+        path = str(tmp_path / f"p{gz}")
+        nifti.write_nifti(path, b, aff, scale=(1 / 255, 0))
+        got, h = nifti.read_nifti(path)
+        assert np.array_equal(got, b) and got.dtype == np.uint8
+        assert h["scl_slope"] == np.float32(1 / 255) and h["scl_inter"] == 0.0 and h["dim"][:5] == (4, 2, 3, 4, 2)
+    for bad in ((0.0, 0.0), (float("nan"), 0.0), (1.0,), "x", (1.0, float("inf"))):
+        with pytest.raises(ValueError):
+            nifti.encode_nifti(a, aff, scale=bad)
+
+
+# ---- the whole mission on the host ----------------------------------------------------------------------------------------------
+class ProbOps(PredictOps):
+    """PredictOps with prep_reorient as numpy.flip(numpy.transpose(...)) and seg_probs_source through the restatement."""
+
+    def __init__(self):
+        self.prob_calls, self.reoriented = [], []
+
+    def prep_reorient(self, x, src_axis, flip):
+        self.reoriented.append((tuple(x.shape), str(x.dtype)))
+        return torch.from_numpy(ref_reorient(x.numpy(), src_axis, flip))
+
+    def seg_probs_source(self, logits, pmin, grid, factors, source_shape, mode, want_prob=True, want_unc=False):
+        assert want_prob or want_unc
+        self.prob_calls.append((mode, bool(want_prob), bool(want_unc)))
+        P, U, _, _ = R.ref_probs_source(logits.numpy(), pmin, grid, factors, source_shape, mode)
+        return (torch.from_numpy(R.stored(P)) if want_prob else None, torch.from_numpy(R.stored(U)) if want_unc else None)
+
+
+AFF = np.array([[0.0, -1.0, 0, 30.0], [1.0, 0.0, 0, -4.0], [0, 0, 2.0, 5.0], [0, 0, 0, 1.0]])
+CASES = {"f1": dict(), "spacing": dict(prep_spacing="2,2,2.5"), "orient": dict(prep_orient="RAS")}
+TURNED = VARIANTS[4]              # ((2, 0, 1), (True, True, False)): a permutation and two reversed axes
+
+
+def _cases(root, case):
+    if case != "orient":
+        return write_cases(root, ["s2", "s1"], [3, 4], affine=AFF)[0], AFF
+    vol, _ = ct_like(3)
+    os.makedirs(os.path.join(root, "src"), exist_ok=True)
+    aff = variant_affine(CANON, *TURNED, vol.shape)
+    write_scan(os.path.join(root, "src", "t_ct.nii.gz"), ref_reorient(vol, *TURNED), affine=aff)
+    with open(os.path.join(root, "cases.csv"), "w") as f:
+        f.write("subject,ct\nt,src/t_ct.nii.gz\n")
+    return os.path.join(root, "cases.csv"), aff
+
+
+def _expected(ops, entry, kw, mode):
+    """(probs (SD, SH, SW, C), unc (SD, SH, SW)) of one subject on the scan's own axes: the logits go the mission's own
+    way, the restatement turns them into bytes on the oriented grid, numpy.flip / transpose put them back."""
+    spacing = prep._triple(kw["prep_spacing"], "spacing") if kw.get("prep_spacing") else None
+    plan = prep._Plan(dict(entry, seg=None), ("ct",), spacing, (8, 8, 8), prep.parse_orient(kw.get("prep_orient")))
+    imgs = {"ct": nifti.read_image(entry["images"]["ct"])[0]}
+    y, _, _, pmin, _, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), "nonzero", (-200.0, 250.0), (8, 8, 8),
+                                                     False)
+    outs, _, _ = E.stitched_window_logits(ops, [PointNet()], torch.from_numpy(y)[None], (8, 8, 8), (4, 4, 4), 3)
+    P, U, inside, _ = R.ref_probs_source(outs[0][0].numpy(), pmin, plan.grid_shape, plan.factors, plan.oriented_shape, mode)
+    p, u = R.stored(P), R.stored(U)
+    if plan.orient is not None and not prep.orient_is_identity(*plan.orient):
+        back = prep.orient_inverse(*plan.orient)
+        p, u, inside = ref_reorient(p, *back), ref_reorient(u, *back), ref_reorient(inside, *back)
+    return np.moveaxis(p, 0, -1), u, inside, plan
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_whole_mission_writes_the_maps_on_the_scans_own_grid_and_changes_nothing_else(tmp_path, case, capsys):
+    root = str(tmp_path)
+    kw = CASES[case]
+    lst, aff = _cases(root, case)
+    base = dict(src_list=lst, patch_size="8,8,8", prep_mask="nonzero", **kw)
+    run = lambda out, *flags: predict.run(predict_args(*flags, out_dir=os.path.join(root, out), **base), ops=ProbOps(),
+                                          model=PointNet(), window_batch=3)
+    rows0 = run("plain")
+    capsys.readouterr()
+    ops = ProbOps()
+    rows = predict.run(predict_args("--save_prob", "--save_unc", out_dir=os.path.join(root, "both"), **base), ops=ops,
+                       model=PointNet(), window_batch=3)
+    said = capsys.readouterr().out
+    names = [r["subject"] for r in rows]
+    assert rows == rows0 and ops.prob_calls == [("argmax", True, True)] * len(names)
+    assert written(os.path.join(root, "plain")) == ["predict.csv"] + [f"{sn}.nii.gz" for sn in names]
+    assert written(os.path.join(root, "both")) == ["predict.csv"] + [f"prob/{sn}.nii.gz" for sn in names] + \
+        [f"{sn}.nii.gz" for sn in names] + [f"unc/{sn}.nii.gz" for sn in names]
+    for name in ["predict.csv"] + [f"{sn}.nii.gz" for sn in names]:       # the label maps and the table: byte for byte
+        assert open(os.path.join(root, "plain", name), "rb").read() == open(os.path.join(root, "both", name), "rb").read()
+    up = [ln for ln in said.splitlines() if ln.startswith("[predict] prob/")]
+    assert len(up) == 1 and "softmax" in up[0] and "1/255" in up[0] and "unc/" in up[0]
+    for sn, entry in zip(names, prep.read_src_list(lst, "lits")):
+        want_p, want_u, inside, plan = _expected(ProbOps(), entry, kw, "argmax")
+        scan = nifti.read_geometry(entry["images"]["ct"])
+        got_p, hp = nifti.read_nifti(os.path.join(root, "both", "prob", f"{sn}.nii.gz"))
+        got_u, hu = nifti.read_nifti(os.path.join(root, "both", "unc", f"{sn}.nii.gz"))
+        shape = tuple(scan["shape"])
+        assert got_p.dtype == got_u.dtype == np.uint8 and got_p.shape == shape + (3,) and got_u.shape == shape
+        assert shape == ((20, 24, 28) if case != "orient" else tuple((20, 24, 28)[a] for a in TURNED[0]))
+        assert np.array_equal(got_p, want_p) and np.array_equal(got_u, want_u)
+        for h in (hp, hu):                                              # the scan's header, slope 1/255
+            assert np.array_equal(h["affine"], scan["affine"]) and np.allclose(h["affine"], aff)
+            assert h["sform_code"] == scan["sform_code"] and h["qform_code"] == scan["qform_code"]
+            assert list(h["pixdim"][:4]) == list(scan["pixdim"][:4])
+            assert h["scl_slope"] == np.float32(1 / 255) and h["scl_inter"] == 0.0
+        assert hp["dim"][0] == 4 and hp["pixdim"][4] == 1.0 and hu["dim"][0] == 3
+        # inside the box the classes share the mass, outside it is the background's
+        assert 0 < inside.sum() < inside.size
+        assert (got_p[~inside] == (255, 0, 0)).all() and not got_u[~inside].any() and got_u[inside].any()
+        assert np.abs(got_p[inside].astype(int).sum(-1) - 255).max() <= 2
+        lab, _ = nifti.read_nifti(os.path.join(root, "both", f"{sn}.nii.gz"))
+        assert (np.take_along_axis(got_p, lab[..., None].astype(np.int64), -1)[..., 0] == got_p.max(-1)).all()
+        assert f"prob/{sn}.nii.gz (3 channels), unc/{sn}.nii.gz" in said
+    if case == "orient":            # the scan in, the label map, the C planes (N = C) and the uncertainty back out
+        assert ops.reoriented == [((1, 28, 20, 24), "torch.float32"), ((20, 24, 28), "torch.uint8"),
+                                  ((3, 20, 24, 28), "torch.uint8"), ((20, 24, 28), "torch.uint8")]
+    else:
+        assert ops.reoriented == []
+    # one switch alone: the other folder is not made, and the ops are asked for that output only
+    ops = ProbOps()
+    predict.run(predict_args("--save_unc", out_dir=os.path.join(root, "unc_only"), **base), ops=ops, model=PointNet(),
+                window_batch=3)
+    assert ops.prob_calls == [("argmax", False, True)] * len(names)
+    assert written(os.path.join(root, "unc_only")) == ["predict.csv"] + [f"{sn}.nii.gz" for sn in names] + \
+        [f"unc/{sn}.nii.gz" for sn in names]
+    for sn in names:
+        assert open(os.path.join(root, "unc_only", "unc", f"{sn}.nii.gz"), "rb").read() == \
+            open(os.path.join(root, "both", "unc", f"{sn}.nii.gz"), "rb").read()
+
+
+def test_sigmoid_mode_writes_the_raw_channels_and_says_that_the_merge_does_not_enter(tmp_path, capsys):
+    root = str(tmp_path)
+    lst, _ = write_cases(root, ["a"], [7], affine=AFF)
+    base = dict(src_list=lst, patch_size="8,8,8", prep_mask="nonzero", multi_label="brats", merge_type="con")
+    ops = ProbOps()
+    predict.run(predict_args("--save_prob", out_dir=os.path.join(root, "seg"), **base), ops=ops, model=PointNet(),
+                window_batch=3)
+    said = capsys.readouterr().out
+    assert ops.prob_calls == [("sigmoid", True, False)]
+    assert "sigmoid per channel" in said and "1/255" in said
+    line = [ln for ln in said.splitlines() if ln.startswith("[predict] --save_prob:")]
+    assert len(line) == 1 and "--merge_type con" in line[0] and "raw channel" in line[0]
+    assert written(os.path.join(root, "seg")) == ["a.nii.gz", "predict.csv", "prob/a.nii.gz"]
+    entry = prep.read_src_list(lst, "lits")[0]
+    want_p, _, inside, _ = _expected(ProbOps(), entry, {}, "sigmoid")
+    got, h = nifti.read_nifti(os.path.join(root, "seg", "prob", "a.nii.gz"))
+    assert np.array_equal(got, want_p) and not got[~inside].any() and h["scl_slope"] == np.float32(1 / 255)
+    # --multi_label lits stays refused, with the switches too
+    with pytest.raises(SystemExit) as e:
+        predict.run(predict_args("--save_prob", out_dir=os.path.join(root, "no"), **dict(base, multi_label="lits")),
+                    ops=ProbOps(), model=PointNet(), window_batch=3)
+    assert "--multi_label lits" in str(e.value) and not os.path.exists(os.path.join(root, "no"))
