@@ -146,6 +146,7 @@ SIGNATURES = {
     "effq_gram_f64_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_f64": (_I, [_P, _P, _GP, _I, _P, _P, _P, _SZ, _P]),
     "effq_gram_f64_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP]),
+    "effq_gram_f64_pipelined": (_I, [_P, _P, _GP, _I]),
     "effq_gram_loss_ws_bytes": (_SZ, [_I]),
     "effq_gram_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "effq_packed_bytes": (_SZ, [_SZ, _I]),

@@ -575,6 +575,10 @@ class HipOps:
     def gram_f64_supported(self, geom: Geom, has_bias: bool) -> bool:
         return bool(self.lib.effq_gram_f64_supported(C.byref(geom), int(has_bias)))
 
+    def gram_f64_pipelined(self, x_ndhwc: torch.Tensor, y_ndhwc: torch.Tensor, geom: Geom, has_bias: bool) -> bool:
+        """Whether gram_f64() gathers these inputs with its pipelined loop (effq_gram_f64_pipelined; launches nothing)."""
+        return bool(self.lib.effq_gram_f64_pipelined(_ptr(x_ndhwc), _ptr(y_ndhwc), C.byref(geom), int(has_bias)))
+
     def gram_f64(self, x_ndhwc: torch.Tensor, y_ndhwc: torch.Tensor, geom: Geom, has_bias: bool):
         """(Au, Bu): the unweighted fp64 Gram system of a layer with full-precision input (effq_gram_f64) - the
         operands of gram_loss() for the first conv and the classifier."""

@@ -290,6 +290,11 @@ int effq_gram_f64(const float* x_ndhwc, const float* y_ndhwc, const effq_geom* g
 /* The launch effq_gram_f64 makes for a supported geometry; launches nothing.  *grid persistent workgroups (1024 at most)
  * walk *nchunk chunks of 32 voxels; *ntiles 16 x 16 accumulator tiles, *tpw (3, 6, 11 or 18) of them per wave. */
 int effq_gram_f64_plan_query(const effq_geom* g, int has_bias, int* nchunk, int* grid, int* ntiles, int* tpw);
+/* 1 where effq_gram_f64 gathers these inputs with its pipelined loop (C1 % 4 == 0, x 16-byte aligned, at most four 16-byte
+ * cells of x and one cell - C2 % 4 == 0 and y 16-byte aligned - or value of y per thread and 32-voxel chunk, at most 11 tiles
+ * per wave), 0 where with the plain loop or for an unsupported geometry.  Both loops stage the same values: the results
+ * do not depend on the answer.  Launches nothing. */
+int effq_gram_f64_pipelined(const float* x_ndhwc, const float* y_ndhwc, const effq_geom* g, int has_bias);
 
 /* ---- the loss of one iterate from the unweighted Gram system (EfficientQConv.py:118-122 without the pass over the voxels)
  * sum_v,c (conv(Qx, G, b)_v,c - y_v,c)^2 = sum_c g_c^T Au g_c - 2 sum_c g_c . Bu_c + syy with g_c = [G[c,:], b_c], in fp64:
