@@ -141,6 +141,8 @@ SIGNATURES = {
     "effq_gram_accum_i8": (_I, [_P, _P, _GP, _I, _P, _I, _P, _P, _P, _I, _LL, _P, _P, _I, _P, _SZ, _P]),
     "effq_gram_accum_i8_unw": (_I, [_P, _P, _GP, _I, _P, _I, _P, _P, _P, _I, _LL, _P, _P, _I, _P, _P, _P, _SZ, _P]),
     "effq_gram_i8_plan_query": (_I, [_GP, _I, _LL, _IP, _IP, _IP, _IP, _IP, _IP]),
+    "effq_gram_i8_group_query": (_I, [_GP, _I, _LL, _IP, _IP, _IP, _IP]),
+    "effq_gram_i8_set_group": (_I, [_I, _I]),
     "effq_upsample_trilinear": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "effq_gram_f64_supported": (_I, [_GP, _I]),
     "effq_gram_f64_ws_bytes": (_SZ, [_GP, _I]),

@@ -26,9 +26,11 @@ typedef int gi_v16i __attribute__((ext_vector_type(16)));
 constexpr int GI_KC = 128;                 // voxels per chunk (4 MFMA K steps)
 constexpr int GI_MB = 128;                 // rows per macro block
 constexpr int GI_RS = GI_KC + 16;          // LDS row stride (bytes): 144 keeps ds_read_b128 conflict free
-constexpr int GI_T = 256;                  // threads: 4 waves, each a 64x64 sub-block
-constexpr int GI_PANEL = GI_MB * GI_RS;    // bytes per staged panel
-constexpr int GI_LDS = 4 * GI_PANEL + 2 * GI_KC * 16;
+constexpr int GI_T = 256;                  // threads per 128 staged rows: a G x G group runs G * GI_T threads
+constexpr int GI_PANEL = GI_MB * GI_RS;    // bytes per staged 128-row panel
+constexpr int GI_GROUP = 2;                // edge of the block group one workgroup computes (gram_i8_group)
+constexpr int gi_lds_bytes(int G) { return 4 * G * GI_PANEL + 2 * GI_KC * 16; }
+static_assert(gi_lds_bytes(GI_GROUP) <= 160 * 1024, "two stages of both group panels and the tables fit one CU's LDS");
 constexpr int GI_MAXCLS = 16;
 constexpr int GI_MAX_CPS = 1000;           // chunks per split: 128 * 1000 * 128*127 < 2^31 (int32 accumulators)
 
@@ -43,6 +45,7 @@ struct GramI8Params {
   int T, RX, YR0, E, NB, NBX, npairs;
   long long V;
   int nchunks, nsplit, cps, ncls;
+  int sub;            // workgroups per (group, split): the launch may cut a planned split into sub parts (gram_i8_launch)
   long long* slabs;   // [ncls][npairs][128*128]
   int debug;          // profiling ablations (EFFQ_GI8_DEBUG): 1 no MFMA, 2 no global loads, 3 no LDS staging
 };
@@ -97,26 +100,46 @@ __global__ __launch_bounds__(256) void k_gi_voxtable(GramI8Params p, gi_v4i* __r
   }
 }
 
-__global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
+// One workgroup computes a G x G group of adjacent 128-row blocks: it stages G*128 rows of the I side and G*128 rows of
+// the J side per chunk ONCE and every block pair of the group reads them from LDS, so a block is gathered (and
+// byte-transposed, and stored) once per GROUP it takes part in instead of once per pair.  The pairs, their numbering and
+// their slabs are those of gram_i8_plan: only which workgroup computes a pair depends on G, and the sums are exact.
+//   G = 1: 4 waves, each a 64 x 64 sub-block of the one pair (2 ds_read_b128 per 2 MFMAs).
+//   G = 2: 8 waves, each 128 rows of ONE I block x 64 columns of ONE J block (6 ds_read_b128 per 8 MFMAs).  Group rows
+//          start at even I; a diagonal group (J0 == I0) stages its 256 rows once and leaves the pair below the diagonal
+//          out; blocks past NBX (I side) or NB (J side) at a group's edge are staged as padding and not computed.
+template <int G>
+__global__ __launch_bounds__(G * GI_T, 2) void k_gram_i8(GramI8Params p) {
+  constexpr int GP = G * GI_PANEL;                          // bytes per staged group panel
+  constexpr int MT = 2 * G;                                 // 32-row MFMA tiles per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char gi_smem[];
-  unsigned char* const panI = gi_smem;                      // [2][GI_PANEL]
-  unsigned char* const panJ = gi_smem + 2 * GI_PANEL;       // [2][GI_PANEL]
-  gi_v4i* const tbl = reinterpret_cast<gi_v4i*>(gi_smem + 4 * GI_PANEL);   // [2][GI_KC] {xbase, mask, vout, -}
+  unsigned char* const panI = gi_smem;                      // [2][GP]
+  unsigned char* const panJ = gi_smem + 2 * GP;             // [2][GP]
+  gi_v4i* const tbl = reinterpret_cast<gi_v4i*>(gi_smem + 4 * GP);   // [2][GI_KC] {xbase, mask, vout, -}
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
-  const int wr = wid >> 1, wc = wid & 1;
+  // the wave's pair inside the group (bi, bj), its first row inside the I block and its 64-column half of the J block
+  const int wc = wid & 1;
+  const int bi = (G == 2) ? (wid >> 2) : 0, bj = (G == 2) ? ((wid >> 1) & 1) : 0;
+  const int wrow = (G == 2) ? 0 : (wid >> 1) * 64;
 
-  int I = 0, rem = blockIdx.x;
-  while (rem >= p.NB - I) {
-    rem -= p.NB - I;
-    ++I;
+  int I0 = 0, rem = blockIdx.x;
+  while (rem >= (p.NB - I0 + G - 1) / G) {
+    rem -= (p.NB - I0 + G - 1) / G;
+    I0 += G;
   }
-  const int J = I + rem;
-  const bool diag = (I == J);
+  const int J0 = I0 + rem * G;
+  const bool diag = (I0 == J0);
+  const int I = I0 + bi, J = J0 + bj;
+  const int pair = I * p.NB - I * (I - 1) / 2 + (J - I);   // gram_i8_plan's numbering (k_gram_i8_finish reads by it)
 
-  const int c_begin = blockIdx.y * p.cps;
-  const int c_end = min(c_begin + p.cps, p.nchunks);
+  // blockIdx.y = split * sub + part: the chunks of the planned split, cut into sub consecutive parts
+  const int split = blockIdx.y / p.sub, part = blockIdx.y - split * p.sub;
+  const int s_begin = split * p.cps;
+  const int s_len = min(s_begin + p.cps, p.nchunks) - s_begin;
+  const int c_begin = s_begin + s_len * part / p.sub;
+  const int c_end = s_begin + s_len * (part + 1) / p.sub;
   if (c_begin >= c_end) return;   // uniform over the workgroup
 
   // staging role: 16 rows (16*rg ..) x 4 voxels of each panel.  The 4 voxels are list slots vg, vg+32, vg+64,
@@ -143,8 +166,8 @@ __global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
       off = r0 - p.YR0;     // d*C2P + c0
     }
   };
-  make_rg(I * GI_MB + 16 * rg, kindI, tapI, offI);
-  make_rg(J * GI_MB + 16 * rg, kindJ, tapJ, offJ);
+  make_rg(I0 * GI_MB + 16 * rg, kindI, tapI, offI);
+  make_rg(J0 * GI_MB + 16 * rg, kindJ, tapJ, offJ);
   const unsigned char* const srcI = (kindI == 1) ? reinterpret_cast<const unsigned char*>(p.yd) : p.x;
   const unsigned char* const srcJ = (kindJ == 1) ? reinterpret_cast<const unsigned char*>(p.yd) : p.x;
   const int ystride = 4 * p.C2P;
@@ -187,24 +210,24 @@ __global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
     }
   };
 
-  gi_v16i acc[2][2];
+  gi_v16i acc[MT][2];
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0;
-  const bool live = (I * GI_MB + wr * 64 < p.E) && (J * GI_MB + wc * 64 < p.E);
+  const bool live = (I < p.NBX) && (J < p.NB) && (J >= I) && (I * GI_MB + wrow < p.E) && (J * GI_MB + wc * 64 < p.E);
 
   auto flush = [&](int cls) {
-    long long* S = p.slabs + ((size_t)cls * p.npairs + blockIdx.x) * (size_t)(GI_MB * GI_MB);
+    long long* S = p.slabs + ((size_t)cls * p.npairs + pair) * (size_t)(GI_MB * GI_MB);
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wr * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int row = wrow + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
           const int col = wc * 64 + n * 32 + li;
           const int v = acc[m][n][r];
           if (v != 0)
@@ -217,7 +240,7 @@ __global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
   {
     const int k = tid & (GI_KC - 1);
     const int cc = (tid < GI_KC) ? c_begin : min(c_begin + 1, c_end - 1);
-    tbl[(tid < GI_KC ? 0 : 1) * GI_KC + k] = vtab[(size_t)cc * GI_KC + k];
+    if (tid < 2 * GI_KC) tbl[(tid < GI_KC ? 0 : 1) * GI_KC + k] = vtab[(size_t)cc * GI_KC + k];
   }
   __syncthreads();
   GI_FETCH(vI, okI, kindI, tapI, offI, srcI, 0)
@@ -241,17 +264,17 @@ __global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
     if (!diag) GI_FETCH(vJ, okJ, kindJ, tapJ, offJ, srcJ, b ^ 1)
     __builtin_amdgcn_sched_barrier(0);
     if (live && EFFQ_DBG(p) != 1) {
-      const unsigned char* PI = panI + b * GI_PANEL + (wr * 64 + li) * GI_RS + lh * 16;
-      const unsigned char* PJ = (diag ? panI : panJ) + b * GI_PANEL + (wc * 64 + li) * GI_RS + lh * 16;
+      const unsigned char* PI = panI + b * GP + (bi * GI_MB + wrow + li) * GI_RS + lh * 16;
+      const unsigned char* PJ = (diag ? panI : panJ) + b * GP + (bj * GI_MB + wc * 64 + li) * GI_RS + lh * 16;
 #pragma unroll
       for (int s = 0; s < GI_KC / 32; ++s) {
-        gi_v4i a[2], bb[2];
+        gi_v4i a[MT], bb[2];
 #pragma unroll
-        for (int m = 0; m < 2; ++m) a[m] = *reinterpret_cast<const gi_v4i*>(PI + m * 32 * GI_RS + s * 32);
+        for (int m = 0; m < MT; ++m) a[m] = *reinterpret_cast<const gi_v4i*>(PI + m * 32 * GI_RS + s * 32);
 #pragma unroll
         for (int n = 0; n < 2; ++n) bb[n] = *reinterpret_cast<const gi_v4i*>(PJ + n * 32 * GI_RS + s * 32);
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < MT; ++m)
 #pragma unroll
           for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[m], bb[n], acc[m][n], 0, 0, 0);
       }
@@ -259,8 +282,8 @@ __global__ __launch_bounds__(GI_T, 2) void k_gram_i8(GramI8Params p) {
     if (cls_next != cls_cur && live) flush(cls_cur);
     if (tid < GI_KC) tbl[b * GI_KC + tid] = traw;              // table of chunk c+2 replaces chunk c's
     if (EFFQ_DBG(p) != 3) {
-      stage(panI + (b ^ 1) * GI_PANEL, vI, okI, kindI);
-      if (!diag) stage(panJ + (b ^ 1) * GI_PANEL, vJ, okJ, kindJ);
+      stage(panI + (b ^ 1) * GP, vI, okI, kindI);
+      if (!diag) stage(panJ + (b ^ 1) * GP, vJ, okJ, kindJ);
     }
     cls_cur = cls_next;
     cls_next = (c + 2 < c_end) ? (has_cls ? cls_raw : 0) : -1;
@@ -431,6 +454,43 @@ static int gram_i8_plan(const effq_geom* g, int ncls, long long n_list, GramI8Pa
   return EFFQ_OK;
 }
 
+// Which block pairs one workgroup computes: a G x G group of adjacent blocks, G = gram_i8_group().  THE dispatch rule:
+// GI_GROUP x GI_GROUP groups where the system has at least two block rows (NBX >= 2) AND a planned split holds at least
+// GI_GROUP_MIN_CPS chunks; one pair per workgroup otherwise.  A group stages half the rows per MAC, but it fills a CU
+// with ONE workgroup (a quarter as many of them, in whole rounds over the chip) and flushes as many atomics: measured
+// (profiles/gram_i8_groups_after.txt), it wins at 373, 171 and 86 chunks per split and loses 1 - 9 % at 32 (n = 6913)
+// and at the 4 chunks of the 1^3 layers.  Where it runs, every planned split is cut into two parts (grid.y = 2 nsplit,
+// gram_i8_sub): twice the workgroups for the last round over the chip, at the price of a second flush per pair.
+// The plan itself - blocks, pairs, slabs, chunks per split, splits - does not depend on any of this.
+// g_gi_group: effq_gram_i8_set_group (test hook), 0 = the rule.
+constexpr int GI_GROUP_MIN_CPS = 64;
+static int g_gi_group = 0;
+
+static int gram_i8_group(const GramI8Params& p) {
+  if (g_gi_group != 0) return g_gi_group;
+  return (p.NBX >= 2 && p.cps >= GI_GROUP_MIN_CPS) ? GI_GROUP : 1;
+}
+
+static int gram_i8_sub(const GramI8Params& p, int G) {
+  return (G == GI_GROUP && p.cps >= GI_GROUP_MIN_CPS && 2 * p.nsplit <= 65535) ? 2 : 1;
+}
+
+static int gram_i8_ngroups(const GramI8Params& p, int G) {
+  int n = 0;
+  for (int I0 = 0; I0 < p.NBX; I0 += G) n += (p.NB - I0 + G - 1) / G;
+  return n;
+}
+
+template <int G>
+static hipError_t gram_i8_launch(GramI8Params p, hipStream_t st) {
+  hipError_t e = raise_lds_limit<k_gram_i8<G>>(gi_lds_bytes(G));
+  if (e != hipSuccess) return e;
+  p.sub = gram_i8_sub(p, G);
+  hipLaunchKernelGGL(k_gram_i8<G>, dim3((unsigned)gram_i8_ngroups(p, G), (unsigned)(p.nsplit * p.sub)), dim3(G * GI_T),
+                     gi_lds_bytes(G), st, p);
+  return hipGetLastError();
+}
+
 // upper bound of the list length: every class run is padded to a multiple of 128 slots
 static size_t gram_i8_table_bytes(long long V, int ncls) { return (size_t)(V + (long long)GI_KC * (ncls + 1)) * 16; }
 
@@ -510,9 +570,7 @@ int effq_gram_accum_i8_unw(const uint8_t* xidx_ndhwc, const float* y_ndhwc, cons
     hipLaunchKernelGGL(k_gi_voxtable, dim3((unsigned)nt), dim3(256), 0, st, p, vtab);
     EFFQ_LAUNCH_CHECK();
   }
-  EFFQ_HIP(raise_lds_limit<k_gram_i8>(GI_LDS));
-  hipLaunchKernelGGL(k_gram_i8, dim3((unsigned)p.npairs, (unsigned)p.nsplit), dim3(GI_T), GI_LDS, st, p);
-  EFFQ_LAUNCH_CHECK();
+  EFFQ_HIP(gram_i8_group(p) == GI_GROUP ? gram_i8_launch<GI_GROUP>(p, st) : gram_i8_launch<1>(p, st));
   const int n = p.RX + (has_bias ? 1 : 0);
   size_t tot = (size_t)n * n + (size_t)p.C2 * n;
   size_t nb = (tot + 255) / 256;
@@ -537,6 +595,27 @@ int effq_gram_i8_plan_query(const effq_geom* g, int ncls, long long n_list, int*
   *nchunks = p.nchunks;
   *cps = p.cps;
   *nsplit = p.nsplit;
+  return EFFQ_OK;
+}
+
+// the block groups of that launch: one workgroup computes gi x gj adjacent blocks, the grid is ngroups x grid_y
+// (grid_y = the plan's nsplit, or twice that where the splits are cut in two).  Launches nothing.
+int effq_gram_i8_group_query(const effq_geom* g, int ncls, long long n_list, int* gi, int* gj, int* ngroups, int* grid_y) {
+  EFFQ_CHECK_ARG(gi && gj && ngroups && grid_y && n_list >= 0 && (n_list % GI_KC) == 0);
+  GramI8Params p;
+  const int rc = gram_i8_plan(g, ncls, n_list, &p);
+  if (rc != EFFQ_OK) return rc;
+  const int G = gram_i8_group(p);
+  *gi = G;
+  *gj = G;
+  *ngroups = gram_i8_ngroups(p, G);
+  *grid_y = p.nsplit * gram_i8_sub(p, G);
+  return EFFQ_OK;
+}
+
+int effq_gram_i8_set_group(int gi, int gj) {
+  EFFQ_CHECK_ARG(gi == gj && (gi == 0 || gi == 1 || gi == GI_GROUP));
+  g_gi_group = gi;
   return EFFQ_OK;
 }
 

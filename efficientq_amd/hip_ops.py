@@ -495,6 +495,18 @@ class HipOps:
               "effq_gram_i8_plan_query")
         return dict(zip(("NB", "NBX", "npairs", "nchunks", "cps", "nsplit"), (o.value for o in out)))
 
+    def gram_i8_groups(self, geom: Geom, ncls: int = 1, n_list: int = 0) -> dict:
+        """Which block pairs of gram_i8_plan() one workgroup of gram_i8() computes: gi x gj adjacent blocks, ngroups x
+        grid_y workgroups (effq_gram_i8_group_query; launches nothing)."""
+        out = [C.c_int() for _ in range(4)]
+        check(self.lib.effq_gram_i8_group_query(C.byref(geom), int(ncls), int(n_list), *[C.byref(o) for o in out]),
+              "effq_gram_i8_group_query")
+        return dict(zip(("gi", "gj", "ngroups", "grid_y"), (o.value for o in out)))
+
+    def gram_i8_set_group(self, gi: int, gj: int) -> None:
+        """Process-wide override of the grouping rule (test hook): (1, 1) one pair per workgroup, (0, 0) the rule."""
+        check(self.lib.effq_gram_i8_set_group(int(gi), int(gj)), "effq_gram_i8_set_group")
+
     def gram_f64_plan(self, geom: Geom, has_bias: bool) -> dict:
         """The launch gram_f64() makes for a supported geometry (effq_gram_f64_plan_query; launches nothing)."""
         out = [C.c_int() for _ in range(4)]

@@ -276,6 +276,16 @@ int effq_gram_accum_i8_unw(const uint8_t* xidx_ndhwc, const float* y_ndhwc, cons
  * *nsplit splits of *cps chunks (128 voxels each, *nchunks in all); a split accumulates in int32 and flushes per class. */
 int effq_gram_i8_plan_query(const effq_geom* g, int ncls, long long n_list, int* nb, int* nbx, int* npairs, int* nchunks,
                             int* cps, int* nsplit);
+/* Which of those block pairs one workgroup computes; launches nothing.  A workgroup owns *gi x *gj adjacent blocks and
+ * stages their rows once per chunk for all of its pairs: the grid is *ngroups x *grid_y.  2 x 2 on systems with at least
+ * two block rows (nbx >= 2) whose splits hold at least 64 chunks, and there every split is cut into two workgroups
+ * (*grid_y = 2 nsplit); 1 x 1 otherwise (one pair per workgroup, *ngroups = npairs, *grid_y = nsplit).  The plan above,
+ * the slabs and with them every output bit do not depend on the grouping.
+ * effq_gram_i8_set_group: process-wide override of that rule (test hook): (1, 1) one pair per workgroup everywhere (the
+ * launch without groups), (2, 2) groups everywhere (splits still cut in two only from 64 chunks on); (0, 0) restores the
+ * rule.  Anything else: EFFQ_ERR_ARG. */
+int effq_gram_i8_group_query(const effq_geom* g, int ncls, long long n_list, int* gi, int* gj, int* ngroups, int* grid_y);
+int effq_gram_i8_set_group(int gi, int gj);
 
 /* The unweighted system of a layer whose input is NOT quantised (first conv / classifier, q_first = q_last = "256,-1":
  * definer.py:296-299, model_blk.py:98-107), in fp64 on the matrix cores: Au [n][n] = sum_v xhat xhat^T with
