@@ -208,6 +208,8 @@ SIGNATURES = {
     "effq_seg_lesion_table": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "effq_label_clean_ws_bytes": (_SZ, [_I, _I, _I]),
     "effq_label_clean": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "effq_label_post_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "effq_label_post": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_label_tallies_ws_bytes": (_SZ, []),
     "effq_label_tallies": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P, _SZ, _P]),
     "effq_surf_ws_bytes": (_SZ, [_I, _I, _I, _I]),
@@ -247,6 +249,9 @@ LESION_TABLE_ROWS = 4096
 # include/effq_hip.h: the rules of effq_label_clean (--post) and how many one call takes
 LABEL_CLEAN_MAX_RULES = 8
 LABEL_CLEAN_OPS = {"largest": 0, "min": 1}
+# include/effq_hip.h: the further rules of effq_label_post (fill, closeR, openR) and the largest radius R, in voxels
+LABEL_POST_OPS = {"fill": 2, "close": 3, "open": 4}
+LABEL_POST_MAX_RADIUS = 32
 # include/effq_hip.h: the longest line of the h and d passes of the distance transform
 EDT_MAX_LINE = 16382
 # include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)

@@ -116,7 +116,11 @@ def build_parser():
                    help='clean the predicted map by connected components, repeatable, in order: LABELS:largest[>TO] keeps '
                         'the largest component of the voxels whose label is one of LABELS, LABELS:minN[>TO] relabels '
                         'every component of fewer than N voxels; the others become TO (default 0): 1,2:largest  \'4:min500>1\' '
-                        '(quote a rule with > on a shell command line: unquoted, the shell takes >TO for a redirection)')
+                        '(quote a rule with > on a shell command line: unquoted, the shell takes >TO for a redirection).  '
+                        'LABELS:fill[>TO] fills the holes of the mask (enclosed voxels of any other label included), '
+                        'LABELS:closeR[>TO] closes it by a ball of R voxels (1 to 32): the added voxels become TO, one of '
+                        'LABELS (default the first); LABELS:openR[>TO] opens it: the removed voxels become TO (default '
+                        '0): \'1,2:fill>1\'  2:open1')
     p.add_argument('--post_conn', default=None, help='the neighbourhood of every --post rule: 26 (default) or 6')
     # the threshold sweep of the validation and the decision threshold of a run; refused combinations and values are
     # named by thr_switches, after the YAML has been merged in
@@ -226,14 +230,18 @@ def prob_switches(args, mission=None):
 
 
 POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES
+POST_MAX_RADIUS = 32         # effq_hip.h: EFFQ_LABEL_POST_MAX_RADIUS
 POST_CONN_DEFAULT = 26       # the neighbourhood of --is_cc
-PostRule = collections.namedtuple('PostRule', 'labels op n to')      # labels: tuple of 1..255; op: largest / min
+# labels: tuple of 1..255; op: largest / min (n voxels) / fill / close / open (n = the radius R in voxels)
+PostRule = collections.namedtuple('PostRule', 'labels op n to')
+POST_GROWING_OPS = ('fill', 'close')         # they add voxels to the mask: TO is one of LABELS
 
 
 def post_rule_text(rule) -> str:
-    """A rule in the form --post takes it: `1,2:largest`, `4:min500>1`."""
+    """A rule in the form --post takes it: `1,2:largest`, `4:min500>1`, `1,2:fill>1`, `1:close2>1`, `2:open3`."""
     labels, op, n, to = rule
-    return ','.join(str(v) for v in labels) + ':' + op + (str(n) if op == 'min' else '') + (f'>{to}' if to else '')
+    said = ','.join(str(v) for v in labels) + ':' + op + (str(n) if op in ('min', 'close', 'open') else '')
+    return said + (f'>{to}' if to or op in POST_GROWING_OPS else '')
 
 
 def post_text(rules, connectivity=POST_CONN_DEFAULT) -> str:
@@ -257,23 +265,30 @@ def parse_post_rule(text) -> PostRule:
             raise SystemExit(f'--post {t!r}: label {v.strip()!r}: the label values of a mask are 1 to 255')
         if int(v) not in labels:
             labels.append(int(v))
-    mm = re.fullmatch(r'min\s*(-?\d+)', op)
-    if op == 'largest':
-        n = 0
+    mm = re.fullmatch(r'(min|close|open)\s*(-?\d+)', op)
+    if op in ('largest', 'fill'):
+        name, n = op, 0
     elif mm is not None:
-        n = int(mm.group(1))
-        if n < 1:
+        name, n = mm.group(1), int(mm.group(2))
+        if name == 'min' and n < 1:
             raise SystemExit(f'--post {t!r}: min {n}: N is a size in voxels, 1 or more')
+        if name != 'min' and not 1 <= n <= POST_MAX_RADIUS:
+            raise SystemExit(f'--post {t!r}: {name} {n}: R is a radius in voxels, 1 to {POST_MAX_RADIUS}')
     else:
-        raise SystemExit(f'--post {t!r}: unknown op {op!r}: one of largest, minN (N voxels)')
-    dest = 0
+        raise SystemExit(f'--post {t!r}: unknown op {op!r}: one of largest, minN (N voxels), fill, closeR, openR '
+                         f'(R voxels)')
+    grows = name in POST_GROWING_OPS
+    dest = labels[0] if grows else 0
     if to is not None:
         if not re.fullmatch(r'\s*\d+\s*', to) or int(to) > 255:
             raise SystemExit(f'--post {t!r}: TO {to.strip()!r}: the new label is 0 to 255')
         dest = int(to)
-    if dest in labels:
+    if grows and dest not in labels:
+        raise SystemExit(f'--post {t!r}: TO {dest} is not one of LABELS: {name} adds voxels to the mask, so they take '
+                         f'one of its labels')
+    if not grows and dest in labels:
         raise SystemExit(f'--post {t!r}: TO {dest} is one of LABELS: the relabelled voxels would stay in the mask')
-    return PostRule(tuple(labels), 'largest' if op == 'largest' else 'min', n, dest)
+    return PostRule(tuple(labels), name, n, dest)
 
 
 def parse_post_text(text):

@@ -191,6 +191,14 @@ __global__ __launch_bounds__(EDT_THREADS) void k_edt_lines(typename M::T* __rest
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
+// the limits of effq_edt_sq (include/effq_hip.h): every voxel index and every squared distance fits an int32, and a line
+// of the h and d passes fits the LDS of one workgroup
+static inline bool edt_dims_ok(int P, int D, int H, int W) {
+  return P > 0 && P <= 65535 && D > 0 && H > 0 && W > 0 && (long long)P * D * H * W < (1ll << 31) &&
+         (long long)D * D + (long long)H * H + (long long)W * W < (1ll << 31) && D <= EFFQ_EDT_MAX_LINE &&
+         H <= EFFQ_EDT_MAX_LINE;
+}
+
 template <class M>
 static int edt_line_pass(typename M::T* sq, int P, int S, int W, int n, int stride, int nouter, int ostride,
                          typename M::Weight wa, hipStream_t st) {

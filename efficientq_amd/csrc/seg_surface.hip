@@ -172,13 +172,6 @@ __global__ __launch_bounds__(SURF_FINAL_THREADS) void k_surf_final(const uint32_
   }
 }
 
-// ---- host -----------------------------------------------------------------------------------------------------------
-static bool edt_dims_ok(int P, int D, int H, int W) {
-  return P > 0 && P <= 65535 && D > 0 && H > 0 && W > 0 && (long long)P * D * H * W < (1ll << 31) &&
-         (long long)D * D + (long long)H * H + (long long)W * W < (1ll << 31) && D <= EFFQ_EDT_MAX_LINE &&
-         H <= EFFQ_EDT_MAX_LINE;
-}
-
 }  // namespace effq
 using namespace effq;
 

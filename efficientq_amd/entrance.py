@@ -26,8 +26,10 @@ decided differently, the logit drift and the probability drift, the lesion / sur
 averages the logits; both hold for every validation of the run (and for ``predict``), the FP network's included.
 ``--post RULE`` (repeatable, ``--post_conn 6|26``) also cleans every labelled val case's predicted map by connected
 components on the device (``1,2:largest`` keeps the largest component of the labels 1 and 2, ``'4:min500>1'`` - quoted,
-or the shell takes ``>1`` for a redirection - relabels every component of label 4 with fewer than 500 voxels to 1) and
-scores the cleaned map: ``<snap>/{fp,ptq}/metrics_post.csv``; ``metrics.csv`` and every other file stay what they are.
+or the shell takes ``>1`` for a redirection - relabels every component of label 4 with fewer than 500 voxels to 1;
+``'1,2:fill>1'`` fills the holes of the mask of the labels 1 and 2 with 1, ``'1:close2>1'`` closes and ``2:open1`` opens a
+mask by a ball of that radius in voxels: effq_label_post) and scores the cleaned map:
+``<snap>/{fp,ptq}/metrics_post.csv``; ``metrics.csv`` and every other file stay what they are.
 It needs labels: with ``--unlabelled`` or ``--synthetic`` it is refused.  ``predict --post`` writes the cleaned maps.
 ``--thr_sweep`` also sweeps the decision threshold of every labelled validation in one more pass over the stitched logits
 (effq_seg_sweep): ``<snap>/{fp,ptq}/threshold.csv`` (per subject and class, and pooled: the ROC AUC, the Dice at the default

@@ -438,7 +438,8 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     fp_model both networks are blended and augmented alike.  Everything after the stitch is unchanged.
     post, post_conn: the rules (config.post_rules) and the neighbourhood of --post.  Each labelled case's predicted map
     (effq_seg_labels, uint8, rule label_rule(...)) is also cleaned by connected components on the given grid
-    (effq_label_clean) and tallied against the label (effq_label_tallies with post_class_lut's table), and its dict gains
+    (effq_label_clean; effq_label_post when a rule fills, closes or opens) and tallied against the label
+    (effq_label_tallies with post_class_lut's table), and its dict gains
     "post": counts (C x 4) with dsc / sens / spec / acc, and "changed", the voxels each rule relabelled.  Every other
     entry and the maps of save_dir stay what they are.  The planes of --multi_label lits are no label map, and the
     planes of --multi_label brats are read back from the map only when `fuse` nests them: both are a RuntimeError.

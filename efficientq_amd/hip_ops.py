@@ -1541,9 +1541,14 @@ class HipOps:
         `rules` a list of at most _lib.LABEL_CLEAN_MAX_RULES (labels, op, n, to) - config.PostRule - applied in order,
         each to the map the previous one left: op 'largest' keeps the largest component of the voxels whose value is one
         of `labels` (of equal sizes the one whose first voxel comes first) and gives every other component the value
-        `to`; op 'min' gives `to` to every component of fewer than `n` voxels.  connectivity 26 or 6.  Returns (map,
+        `to`; op 'min' gives `to` to every component of fewer than `n` voxels.  Ops 'fill', 'close' and 'open'
+        (effq_label_post, called when a rule has one of them): 'fill' gives `to` to every hole of the mask (a component
+        of its complement, at the dual connectivity, that touches no face of the volume), 'close' to the voxels that
+        closing by a ball of `n` voxels (1 to _lib.LABEL_POST_MAX_RADIUS) adds - for both `to` is one of `labels` -
+        and 'open' to the voxels of the mask that opening by such a ball removes.  connectivity 26 or 6.  Returns (map,
         stats): the cleaned map (a new tensor, or `out`, which may be `label_map` itself) and R x 2 int64 on the device:
-        per rule the components its mask had and the voxels it relabelled."""
+        per rule the components its mask had ('fill': the holes filled; 'close', 'open': the voxels of the mask before
+        the rule) and the voxels it relabelled."""
         m, P, D, H, W = self._mask_planes("label_clean", label_map)
         if m.dim() != 3:
             raise _lib.EffqError(f"label_clean: map {tuple(m.shape)}, needs D x H x W")
@@ -1557,23 +1562,36 @@ class HipOps:
             raise _lib.EffqError(f"label_clean: {R} rules, 1 to {_lib.LABEL_CLEAN_MAX_RULES}")
         sets = (C.c_uint8 * (256 * R))()
         words = (C.c_longlong * (3 * R))()
+        morph, max_radius = False, 0
         for r, rule in enumerate(rules):
             try:
                 labels, op, n, to = rule
                 labels, n, to = [int(v) for v in labels], int(n), int(to)
             except (TypeError, ValueError) as e:
                 raise _lib.EffqError(f"label_clean: rule {r}: {rule!r} is no (labels, op, n, to): {e}") from e
-            if op not in _lib.LABEL_CLEAN_OPS:
-                raise _lib.EffqError(f"label_clean: rule {r}: unknown op {op!r} (one of {', '.join(_lib.LABEL_CLEAN_OPS)})")
+            if op not in _lib.LABEL_CLEAN_OPS and op not in _lib.LABEL_POST_OPS:
+                raise _lib.EffqError(f"label_clean: rule {r}: unknown op {op!r} (one of "
+                                     f"{', '.join(list(_lib.LABEL_CLEAN_OPS) + list(_lib.LABEL_POST_OPS))})")
             if not labels or min(labels) < 1 or max(labels) > 255:
                 raise _lib.EffqError(f"label_clean: rule {r}: labels {labels}, needs values of 1 to 255")
-            if not 0 <= to <= 255 or to in labels:
+            if op in ("fill", "close"):
+                if to not in labels:
+                    raise _lib.EffqError(f"label_clean: rule {r}: {op} adds voxels to the mask: the new label {to} is "
+                                         f"not one of {labels}")
+            elif not 0 <= to <= 255 or to in labels:
                 raise _lib.EffqError(f"label_clean: rule {r}: the new label {to} is outside 0..255 or one of {labels}")
             if op == "min" and n < 1:
                 raise _lib.EffqError(f"label_clean: rule {r}: min {n}, needs 1 or more voxels")
+            if op in ("close", "open"):
+                if not 1 <= n <= _lib.LABEL_POST_MAX_RADIUS:
+                    raise _lib.EffqError(f"label_clean: rule {r}: {op} {n}, needs a radius of 1 to "
+                                         f"{_lib.LABEL_POST_MAX_RADIUS} voxels")
+                max_radius = max(max_radius, n)
             for v in labels:
                 sets[256 * r + v] = 1
-            words[3 * r], words[3 * r + 1], words[3 * r + 2] = _lib.LABEL_CLEAN_OPS[op], n, to
+            code = _lib.LABEL_CLEAN_OPS[op] if op in _lib.LABEL_CLEAN_OPS else _lib.LABEL_POST_OPS[op]
+            words[3 * r], words[3 * r + 1], words[3 * r + 2] = code, n, to
+            morph = morph or op in _lib.LABEL_POST_OPS
         if out is None:
             out = torch.empty_like(m)
         elif out.shape != m.shape or out.dtype != torch.uint8 or out.device != m.device or not out.is_contiguous():
@@ -1582,9 +1600,19 @@ class HipOps:
         elif out is label_map and m is not label_map:
             raise _lib.EffqError("label_clean: a map cleaned in place must be contiguous")
         stats = torch.empty(R, 2, dtype=torch.int64, device=self.device)
-        ws = self._workspace("label_clean", self.lib.effq_label_clean_ws_bytes(D, H, W))
-        check(self.lib.effq_label_clean(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
-                                        _ptr(ws), ws.numel(), self.stream), "effq_label_clean")
+        if not morph:
+            ws = self._workspace("label_clean", self.lib.effq_label_clean_ws_bytes(D, H, W))
+            check(self.lib.effq_label_clean(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
+                                            _ptr(ws), ws.numel(), self.stream), "effq_label_clean")
+            return out, stats
+        need = self.lib.effq_label_post_ws_bytes(D, H, W, max_radius)
+        if need == 0:
+            raise _lib.EffqError(f"label_clean: a map {D} x {H} x {W} padded by the radius {max_radius} is outside the "
+                                 f"distance transform's limits (fewer than 2^31 voxels, D and H at most "
+                                 f"{_lib.EDT_MAX_LINE})")
+        ws = self._workspace("label_clean", need)
+        check(self.lib.effq_label_post(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
+                                       _ptr(ws), ws.numel(), self.stream), "effq_label_post")
         return out, stats
 
     def label_tallies(self, pred: torch.Tensor, truth: torch.Tensor, lut, C_: int):

@@ -33,7 +33,9 @@ averages the logits: 2, 4 or 8 forwards per window.  When either is given ``pred
 ``--post RULE`` (repeatable; config.post_rules, ``--post_conn 6|26``) cleans the map by connected components on the
 scan's own grid before it is counted, copied and written (effq_label_clean): ``--post 1,2:largest`` keeps the largest
 component of the labels 1 and 2, ``--post '4:min500>1'`` relabels every component of label 4 with fewer than 500 voxels to
-1.  ``predict.csv`` then gains the columns ``post`` (the rules) and ``post_changed`` (the voxels each rule relabelled)
+1; ``'1,2:fill>1'`` fills the holes of the mask of the labels 1 and 2 with label 1, ``'1:close2>1'`` closes and
+``2:open1`` opens a mask by a ball of that radius in voxels of the scan's grid (effq_label_post).
+``predict.csv`` then gains the columns ``post`` (the rules) and ``post_changed`` (the voxels each rule relabelled)
 after all others, and ``labels``, ``voxels`` and ``volume_ml`` are the cleaned map's; without ``--post`` nothing changes.
 
 ``--thresh VALUE`` (with ``--multi_label``; a probability ``P`` or ``logit:X``, config.parse_thresh) decides every channel

@@ -817,6 +817,47 @@ size_t effq_label_clean_ws_bytes(int D, int H, int W);
 int effq_label_clean(const uint8_t* in, int D, int H, int W, int connectivity, int R, const uint8_t* sets,
                      const long long* rules, uint8_t* out, long long* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- filling holes and closing or opening masks by a ball (--post fill, closeR, openR).  Arguments,
+ * layout and meaning as effq_label_clean; ops EFFQ_LABEL_CLEAN_LARGEST and EFFQ_LABEL_CLEAN_MIN run the same launches
+ * and give the same bits as there.  M = the voxels whose value is in the rule's set, on the map the previous rule left;
+ * B_R = {(dd, dh, dw): dd^2 + dh^2 + dw^2 <= R^2}, R = N in voxels, 1 <= R <= EFFQ_LABEL_POST_MAX_RADIUS.
+ *   EFFQ_LABEL_POST_FILL: every hole of M becomes TO (N ignored).  A hole is a connected component of the voxels not in
+ *     M that holds no voxel on any of the six faces of the volume; the holes are connected by the dual of `connectivity`
+ *     (6 when the rules use 26, 26 when they use 6).  Every voxel of a hole becomes TO whatever value it had.  An axis of
+ *     extent 1 leaves no holes.
+ *   EFFQ_LABEL_POST_CLOSE: the voxels of (M + B_R) - B_R (dilation, then erosion) that are not in M become TO.
+ *   EFFQ_LABEL_POST_OPEN: the voxels of M that are not in (M - B_R) + B_R (erosion, then dilation) become TO.
+ *     Both are taken on the infinite grid with everything outside the volume background, and restricted to the volume:
+ *     closing is extensive and idempotent (a mask closer than R to a face does not grow towards it), opening is
+ *     anti-extensive and idempotent.
+ *   TO is 0..255; for FILL and CLOSE, which add to the mask, it is one of the rule's set, for the other ops it is not.
+ * stats (R, 2) int64 on the device: FILL - the holes filled, the voxels relabelled; CLOSE and OPEN - the voxels of M
+ *   before the rule, the voxels relabelled; LARGEST and MIN as effq_label_clean.
+ * Per rule: FILL - the complement plane (one launch), the five labelling launches at the dual connectivity, the voxels
+ *   of the faces marking their roots, and one pass that rewrites and counts: 8 launches.  CLOSE, OPEN - dilation and
+ *   erosion are thresholds of the exact squared distance (effq_edt_sq's three launches): dilate(X) = {edt_sq(., X) <=
+ *   R^2}, erode(X) = {edt_sq(., complement of X) > R^2}, both on the plane padded by R voxels on every side (background
+ *   for CLOSE, sites of the complement for OPEN), which makes them those of the infinite grid: a memset and 9 launches
+ *   (sites, transform, threshold, transform, rewrite and count).  One launch zeroes the counters first (and a device
+ *   copy when out is not in).  All on `stream`, no read by the host and no workgroup that waits for another.  Integer
+ *   compares, adds and a max only, so equal inputs give equal bits, whatever the scheduling.
+ * ws: effq_label_post_ws_bytes(D, H, W, max_radius) bytes, max_radius = the largest R of the CLOSE and OPEN rules, 0
+ *   without one: effq_label_clean_ws_bytes(D, H, W) and 16 B, and for max_radius > 0 1 B of site and 4 B of squared
+ *   distance per voxel of the padded plane (D + 2 max_radius)(H + 2 max_radius)(W + 2 max_radius), each rounded up to
+ *   16 B - 129 071 568 B for 155 x 240 x 240 at radius 3 (80 MB without a ball).  0 for max_radius outside 0..32 or
+ *   dimensions out of range.  Limits: effq_cc_label's with P = 1, and effq_edt_sq's with P = 1 for the padded plane
+ *   (fewer than 2^31 voxels).  Bad arguments (a null pointer, R out of range, an unknown op, N < 1 for MIN, a radius
+ *   outside 1..32, TO out of range, in the set for LARGEST, MIN and OPEN or outside it for FILL and CLOSE, sets[r][0]
+ *   set, a connectivity other than 6 or 26, dimensions out of range) return EFFQ_ERR_ARG, a short workspace
+ *   EFFQ_ERR_WORKSPACE; both launch nothing and leave out and stats as they were. */
+#define EFFQ_LABEL_POST_FILL 2
+#define EFFQ_LABEL_POST_CLOSE 3
+#define EFFQ_LABEL_POST_OPEN 4
+#define EFFQ_LABEL_POST_MAX_RADIUS 32
+size_t effq_label_post_ws_bytes(int D, int H, int W, int max_radius);
+int effq_label_post(const uint8_t* in, int D, int H, int W, int connectivity, int R, const uint8_t* sets,
+                    const long long* rules, uint8_t* out, long long* stats, void* ws, size_t ws_bytes, void* stream);
+
 /* Tallies of a label map (the score of a cleaned map): pred (S) uint8 label values against the truth -> counts (C, 4)
  * int64 = TP, FP, FN, TN per class, the layout of effq_seg_tallies.  lut: 256 uint16 on the host, read before the call
  * returns; bit c set = that label value belongs to class c.  The class bits of a predicted voxel are lut[pred[v]]; those
