@@ -225,6 +225,7 @@ SIGNATURES = {
     "effq_prep_standardise_crop": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "effq_prep_crop_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "effq_prep_union_mask": (_I, [_P, _I, _LL, _I, _P, _P]),
+    "effq_prep_smooth": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
     "effq_prep_reorient": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "effq_prep_reorient_plan": (_I, [_P, _I, _I, _P]),
 }
@@ -261,6 +262,8 @@ PREP_MAX_MODALITIES = 4
 PREP_WS_BYTES = 1024 * (2 * PREP_MAX_MODALITIES * 8 + 8 * 4)
 PREP_MASKS = {"nonzero": 0, "all": 1}
 PREP_LINEAR, PREP_NEAREST = 0, 1
+# include/effq_hip.h (EFFQ_PREP_SMOOTH_MAX_RADIUS): the largest radius of an axis of effq_prep_smooth
+PREP_SMOOTH_MAX_RADIUS = 32
 
 _lib = None
 

@@ -100,6 +100,9 @@ def build_parser():
                    help='prep, predict: three letters, one each of R/L, A/P, S/I (RAS, LPS, SAR, ...): the anatomical '
                         'direction array axis 0, 1, 2 of the working arrays runs towards; every scan is reoriented to it')
     p.add_argument('--prep_spacing', default=None, help='prep: d,h,w in mm to resample every subject to')
+    p.add_argument('--prep_antialias', action='store_true',
+                   help='prep, predict, with --prep_spacing: a Gaussian over the images before they are down-sampled, per '
+                        'axis of factor f > 1 with sigma = (f - 1) / 2 voxels of the source grid (truncated at 4 sigma)')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
     # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint

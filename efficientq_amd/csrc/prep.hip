@@ -5,7 +5,8 @@
 //   3 effq_prep_standardise_crop   y = mask ? float((double(x) - mean) / std) : +0.0f inside the crop box.
 // The variance takes two passes because CT values lie thousands of units from zero with a spread of tens: sum x^2 -
 // n mean^2 in one pass cancels the digits the spread lives in.  Before them, optionally, effq_prep_window (clip in place)
-// and effq_prep_resample (one voxel spacing); beside them effq_prep_crop_u8 (the label) and effq_prep_union_mask.
+// and effq_prep_resample (one voxel spacing; the anti-alias filter that may go in front of it is prep_smooth.hip); beside
+// them effq_prep_crop_u8 (the label) and effq_prep_union_mask.
 //
 // Streaming, HBM-bound: each thread takes groups of four consecutive voxels with one 16-B load per modality, through a
 // type of 4-B alignment since neither the planes (S % 4 != 0) nor the rows of a crop start on 16 B.  Reductions: every
@@ -13,17 +14,14 @@
 // in `ws`, and one finishing workgroup that adds them in block order.  The grid depends on the extents alone and there
 // is no floating-point atomic: equal inputs give equal bits.  Every index is 32-bit: C S < 2^31 is an argument check.
 #include "common.h"
+#include "prep_rows.h"
 
 namespace effq {
 
-constexpr int PREP_THREADS = 256;
-constexpr int PREP_WAVES = PREP_THREADS / 64;
-constexpr int PREP_MAX_BLOCKS = 1024;
 constexpr int PREP_MAXC = EFFQ_PREP_MAX_MODALITIES;
 // per workgroup: PREP_MAXC sums, PREP_MAXC counts, the six box values
 static_assert((size_t)PREP_MAX_BLOCKS * (PREP_MAXC * 8 + PREP_MAXC * 8 + 8 * 4) <= EFFQ_PREP_WS_BYTES, "workspace");
 
-struct __attribute__((packed, aligned(4))) PFloat4 { float x, y, z, w; };    // 16 B at any 4-B boundary
 struct __attribute__((packed, aligned(1))) PByte4 { uint8_t x, y, z, w; };
 
 struct PrepWs {
@@ -37,11 +35,6 @@ static inline PrepWs prep_ws(void* ws) {
   r.cnt = reinterpret_cast<long long*>(r.sum + (size_t)PREP_MAX_BLOCKS * PREP_MAXC);
   r.box = reinterpret_cast<int*>(r.cnt + (size_t)PREP_MAX_BLOCKS * PREP_MAXC);
   return r;
-}
-
-static inline unsigned prep_grid(size_t groups) {
-  size_t nb = (groups + PREP_THREADS - 1) / PREP_THREADS;
-  return (unsigned)(nb < 1 ? 1 : (nb > (size_t)PREP_MAX_BLOCKS ? (size_t)PREP_MAX_BLOCKS : nb));
 }
 
 __device__ __forceinline__ bool in_mask(float v, int mask_mode) { return mask_mode != 0 || v != 0.0f; }
@@ -260,21 +253,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_sqdev(const float* __rest
 }
 
 // ---- pass 3 and the other row-wise kernels ----------------------------------------------------------------------------
-// A thread takes four consecutive w of one output row: gw = ceil(OW / 4) threads per row, rows = N * OD * OH.
-struct RowItem {
-  unsigned n, d, h, w0;
-};
-__device__ __forceinline__ RowItem row_item(unsigned e, unsigned gw, unsigned OD, unsigned OH) {
-  RowItem r;
-  unsigned row = e / gw;
-  r.w0 = (e - row * gw) * 4;
-  r.h = row % OH;
-  row /= OH;
-  r.d = row % OD;
-  r.n = row / OD;
-  return r;
-}
-
+// A thread takes four consecutive w of one output row (row_item of prep_rows.h).
 struct CropParams {
   const void* x;
   void* y;
@@ -445,11 +424,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_resample_nearest(Resample
   }
 }
 
-static inline bool prep_fits(long long N, long long D, long long H, long long W) {
-  return N > 0 && D > 0 && H > 0 && W > 0 && D <= 32767 && H <= 32767 && W <= 32767 && N * D * H * W < (1ll << 31);
-}
 static inline bool prep_fits_flat(long long C, long long S) { return C > 0 && S > 0 && S < (1ll << 31) && C * S < (1ll << 31); }
-static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace effq
 using namespace effq;

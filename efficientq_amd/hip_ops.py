@@ -1791,6 +1791,30 @@ class HipOps:
                                           self.stream), "effq_prep_resample")
         return y
 
+    def prep_smooth(self, x: torch.Tensor, sigmas, keep_zero: bool = False) -> torch.Tensor:
+        """The anti-alias filter of --prep_antialias (effq_prep_smooth): N x D x H x W float32 volumes filtered along
+        D, H, W with Gaussians of `sigmas` (voxels; prep.antialias_sigma of the resampling factors), the taps and radii
+        from prep.antialias_taps, edges replicated.  `keep_zero`: a voxel that is exactly 0 in `x` is +0.0 in the result.
+        A new tensor; `x` itself when every radius is 0.  A NaN or an Inf spreads over its stencil."""
+        from . import prep
+        x, N, D, H, W = self._prep_volumes("prep_smooth", x, limit_c=False)
+        s = tuple(float(v) for v in sigmas)
+        if len(s) != 3 or not all(0.0 <= v < float("inf") for v in s):
+            raise _lib.EffqError(f"prep_smooth: sigmas {s}: needs three finite values >= 0 (d, h, w)")
+        taps = [prep.antialias_taps(v) for v in s]
+        radii = [len(t) - 1 for t in taps]
+        if max(radii) > _lib.PREP_SMOOTH_MAX_RADIUS:
+            raise _lib.EffqError(f"prep_smooth: sigmas {s} give the radii {radii}, at most {_lib.PREP_SMOOTH_MAX_RADIUS}")
+        if max(radii) == 0:
+            return x
+        y = torch.empty_like(x)
+        tmp = torch.empty_like(x) if sum(r > 0 for r in radii) > 1 else None
+        # the taps are contiguous float32 host arrays, r + 1 each, read before the call returns
+        check(self.lib.effq_prep_smooth(_ptr(x), N, D, H, W, taps[0].ctypes.data, radii[0], taps[1].ctypes.data, radii[1],
+                                        taps[2].ctypes.data, radii[2], int(bool(keep_zero)), _ptr(y), _ptr(tmp),
+                                        self.stream), "effq_prep_smooth")
+        return y
+
     def prep_bbox_moments(self, x: torch.Tensor, mask: str = "nonzero"):
         """Pass 1 over one subject (effq_prep_bbox_moments), x = C x D x H x W float32.  Returns (bbox, count, sum):
         bbox int32[6] = the least d, h, w and the greatest d, h, w of the union of the modalities' masks (least > greatest

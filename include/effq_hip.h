@@ -951,7 +951,7 @@ int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D,
  *   EFFQ_PREP_LINEAR (fp32 in and out): s = (o + 0.5) f - 0.5 in fp64, clamped to [0, n - 1]; i0 = floor(s), i1 =
  *     min(i0 + 1, n - 1), l1 = float(s - i0), l0 = 1.0f - l1; the eight neighbours are combined in fp32 as
  *     l0d (l0h (l0w v000 + l1w v001) + l1h (l0w v010 + l1w v011)) + l1d (...), nothing fused.  No filter before
- *     down-sampling.
+ *     down-sampling: that is effq_prep_smooth below, a call of its own.
  *   EFFQ_PREP_NEAREST (uint8 in and out): index min(n - 1, floor((o + 0.5) f)) per axis.
  * bbox_moments (pass 1): bbox_out[6] int32 = the least d, h, w and the greatest d, h, w of the union of the modalities'
  *   masks (the whole grid for MASK_ALL; least = the extent and greatest = -1 when the union is empty); count_out[C]
@@ -977,6 +977,33 @@ int effq_prep_standardise_crop(const float* x, int C, int D, int H, int W, int m
 int effq_prep_crop_u8(const uint8_t* x, int C, int D, int H, int W, const int* pmin, const int* pmax, uint8_t* y,
                       void* stream);
 int effq_prep_union_mask(const float* x, int C, long long S, int mask_mode, uint8_t* mask, void* stream);
+
+/* ---- the anti-alias filter before down-sampling (csrc/prep_smooth.hip; prep.py --prep_antialias): a separable Gaussian
+ * on the source grid, x (N, D, H, W) fp32 -> y of the same shape.  Per array axis a with the factor f_a = target spacing /
+ * source spacing of the resampling that follows (the caller's rule, prep.antialias_taps):
+ *   sigma_a = (f_a - 1) / 2 if f_a > 1, else 0 (an axis that is kept or up-sampled is not filtered);
+ *   r_a = int(4 sigma_a + 0.5) (scipy's truncate = 4.0); an axis with r_a = 0 is not filtered, whatever sigma_a is;
+ *   g_k = exp(-k^2 / (2 sigma_a^2)), k = -r_a .. r_a, in fp64 on the host, normalised to sum 1, then rounded to fp32
+ *     and not normalised again: the fp32 taps sum to 1 within (2 r_a + 1) 2^-24.
+ * taps_d, taps_h, taps_w are HOST arrays of r + 1 floats, g_0 first (g_-k = g_k), each in (0, 1]; they are read before
+ * the call returns and travel in the launch parameters: no device allocation, no copy.  taps of an axis with r = 0 are
+ * not read and may be null.  Along a filtered axis of extent n
+ *   y[i] = sum_k g_k x[clamp(i + k, 0, n - 1)]
+ * (edge replication, scipy's mode = 'nearest', the clamping of EFFQ_PREP_LINEAR; n < r is legal), formed in fp32 as
+ * acc = g_0 x[i], then acc = fmaf(g_k, x[clamp(i - k)] + x[clamp(i + k)], acc) for k = 1 .. r.  The filtered axes are
+ * applied one after the other, W then H then D, one launch each, fp32 stored between them: the first of three passes
+ * writes y, the one before the last writes tmp, the last writes y.  tmp (N D H W floats) may be null when at most one
+ * axis is filtered; no other device memory is used.  keep_zero = 1: a voxel whose value in x is exactly 0.0f (either
+ * sign) is exactly +0.0f in y, whatever its neighbours hold, so a zero background does not take up the body's values
+ * (x is read again in the last pass for this).  A NaN or an Inf spreads to every voxel within the radius along each
+ * filtered axis; nothing treats them specially.  The grid depends on the extents alone and there is no atomic: equal
+ * inputs give equal bits.  Refused with EFFQ_ERR_ARG before any launch: a null x or y, extents outside those of the
+ * prep kernels (N D H W < 2^31, every extent <= 32767), a radius outside 0 ... EFFQ_PREP_SMOOTH_MAX_RADIUS, all three
+ * radii 0 (nothing to do), null or non-finite taps of a filtered axis, keep_zero other than 0 and 1, a null tmp when two
+ * or three axes are filtered, a pointer not aligned to 4 B, and x, y, tmp overlapping one another. */
+#define EFFQ_PREP_SMOOTH_MAX_RADIUS 32
+int effq_prep_smooth(const float* x, int N, int D, int H, int W, const float* taps_d, int rd, const float* taps_h, int rh,
+                     const float* taps_w, int rw, int keep_zero, float* y, float* tmp, void* stream);
 
 /* ---- reorientation (csrc/reorient.hip; prep.py --prep_orient): x (N, D, H, W) -> y (N, dims[src_axis[0]],
  * dims[src_axis[1]], dims[src_axis[2]]) with dims = {D, H, W}: output axis p is source axis src_axis[p] (three host ints,
