@@ -226,6 +226,10 @@ SIGNATURES = {
     "effq_prep_crop_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "effq_prep_union_mask": (_I, [_P, _I, _LL, _I, _P, _P]),
     "effq_prep_smooth": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "effq_prep_cubic_ws_bytes": (_I, [_I, _I, _I, _I, _P]),
+    "effq_prep_cubic_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "effq_prep_spline_prefilter": (_I, [_P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "effq_prep_resample_cubic": (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _I, _P, _I, _I, _I, _P, _SZ, _P]),
     "effq_prep_reorient": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "effq_prep_reorient_plan": (_I, [_P, _I, _I, _P]),
 }
@@ -264,6 +268,8 @@ PREP_MASKS = {"nonzero": 0, "all": 1}
 PREP_LINEAR, PREP_NEAREST = 0, 1
 # include/effq_hip.h (EFFQ_PREP_SMOOTH_MAX_RADIUS): the largest radius of an axis of effq_prep_smooth
 PREP_SMOOTH_MAX_RADIUS = 32
+# include/effq_hip.h (EFFQ_PREP_SPLINE_PASS_*): the prefilter passes of effq_prep_spline_prefilter
+PREP_SPLINE_PASSES = {"d": 1, "h": 2, "w": 4}
 
 _lib = None
 

@@ -103,6 +103,10 @@ def build_parser():
     p.add_argument('--prep_antialias', action='store_true',
                    help='prep, predict, with --prep_spacing: a Gaussian over the images before they are down-sampled, per '
                         'axis of factor f > 1 with sigma = (f - 1) / 2 voxels of the source grid (truncated at 4 sigma)')
+    p.add_argument('--prep_interp', default='linear',
+                   help='prep, predict: linear (trilinear, the default) or cubic (with --prep_spacing): the images are '
+                        'resampled by cubic B-spline interpolation, as scipy and skimage do at order=3 with mode mirror; '
+                        'the label stays nearest')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
     # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint

@@ -1791,6 +1791,60 @@ class HipOps:
                                           self.stream), "effq_prep_resample")
         return y
 
+    def prep_resample_cubic(self, x: torch.Tensor, factors, out_shape, keep_zero: bool = False) -> torch.Tensor:
+        """N x D x H x W float32 volumes on a grid of another spacing by cubic B-spline interpolation
+        (effq_prep_resample_cubic; the rule of prep.py's --prep_interp cubic): `factors` and `out_shape` as in
+        prep_resample.  `keep_zero`: an output voxel whose trilinear footprint in `x` is all exactly 0 is +0.0.  The
+        fp64 coefficients live in a workspace of 8 B per voxel of `x`; `x` is not modified.  A new tensor."""
+        x, N, D, H, W = self._prep_volumes("prep_resample_cubic", x, limit_c=False)
+        f = tuple(float(v) for v in factors)
+        o = tuple(int(v) for v in out_shape)
+        if len(f) != 3 or len(o) != 3 or not all(0.0 < v <= 1e6 for v in f) or min(o) < 1 or max(o) > 32767 or \
+                N * o[0] * o[1] * o[2] >= 2 ** 31:
+            raise _lib.EffqError(f"prep_resample_cubic: factors {f}, output extents {o}")
+        y = torch.empty((N,) + o, dtype=torch.float32, device=self.device)
+        need = C.c_size_t()
+        check(self.lib.effq_prep_cubic_ws_bytes(N, D, H, W, C.byref(need)), "effq_prep_cubic_ws_bytes")
+        ws = self._workspace("prep_cubic", need.value)
+        check(self.lib.effq_prep_resample_cubic(_ptr(x), N, D, H, W, f[0], f[1], f[2], int(bool(keep_zero)), _ptr(y),
+                                                o[0], o[1], o[2], _ptr(ws), ws.numel(), self.stream),
+              "effq_prep_resample_cubic")
+        return y
+
+    def prep_cubic_plan(self, shape, out_shape) -> dict:
+        """How prep_resample_cubic walks N x D x H x W volumes resampled to `out_shape` (effq_prep_cubic_plan; launches
+        nothing): chunk and tile_rows of the W prefilter pass, and per launch ('d', 'h', 'w', 'eval') its work items and
+        how many of them one trip of its grid covers."""
+        n, d, h, w = (int(v) for v in shape)
+        o = tuple(int(v) for v in out_shape)
+        chunk, rows = C.c_int(), C.c_int()
+        items, trip = (C.c_longlong * 4)(), (C.c_longlong * 4)()
+        check(self.lib.effq_prep_cubic_plan(n, d, h, w, o[0], o[1], o[2], C.addressof(chunk), C.addressof(rows),
+                                            C.addressof(items), C.addressof(trip)),
+              "effq_prep_cubic_plan")
+        names = ("d", "h", "w", "eval")
+        return dict(chunk=chunk.value, tile_rows=rows.value, items=dict(zip(names, (int(v) for v in items))),
+                    trip=dict(zip(names, (int(v) for v in trip))))
+
+    def prep_spline_prefilter(self, x: torch.Tensor, passes: str = "dhw", out: Optional[torch.Tensor] = None):
+        """The B-spline coefficients of N x D x H x W float32 volumes as a float64 tensor (effq_prep_spline_prefilter), or
+        some of the passes alone: 'd' reads `x` and writes `out` (a new tensor unless given), 'h' and 'w' filter `out` in
+        place, so without 'd' the caller passes the `out` of an earlier call (`x` gives the shape only)."""
+        x, N, D, H, W = self._prep_volumes("prep_spline_prefilter", x, limit_c=False)
+        mask = sum(_lib.PREP_SPLINE_PASSES.get(c, 8) for c in set(passes))
+        if not 0 < mask <= 7:
+            raise _lib.EffqError(f"prep_spline_prefilter: passes {passes!r}: letters of d, h, w")
+        if out is None:
+            if not mask & 1:
+                raise _lib.EffqError("prep_spline_prefilter: the passes h and w work in place: they need `out`")
+            out = torch.empty(x.shape, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or \
+                self._elsewhere(out):
+            raise _lib.EffqError(f"prep_spline_prefilter: `out` must be a contiguous float64 tensor of {tuple(x.shape)}")
+        check(self.lib.effq_prep_spline_prefilter(_ptr(x), N, D, H, W, mask, _ptr(out), out.numel() * 8, self.stream),
+              "effq_prep_spline_prefilter")
+        return out
+
     def prep_smooth(self, x: torch.Tensor, sigmas, keep_zero: bool = False) -> torch.Tensor:
         """The anti-alias filter of --prep_antialias (effq_prep_smooth): N x D x H x W float32 volumes filtered along
         D, H, W with Gaussians of `sigmas` (voxels; prep.antialias_sigma of the resampling factors), the taps and radii

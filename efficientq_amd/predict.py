@@ -3,7 +3,7 @@
     python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/ \
         [--prep_window -200,250 --prep_spacing 1,1,2.5 --prep_mask all --prep_min_size d,h,w --patch_size d,h,w]
-        [--prep_orient RAS] [--prep_antialias] [--blend gauss --tta_mirror hw]
+        [--prep_orient RAS] [--prep_antialias] [--prep_interp cubic] [--blend gauss --tta_mirror hw]
 
 ``--src_list`` is the CSV of the ``prep`` mission (prep.read_src_list; a ``seg`` column is allowed and ignored).  The
 ``--prep_*`` switches and ``--patch_size`` mean what they mean in ``prep`` and ``ptq`` and have the same per-task
@@ -29,6 +29,12 @@ code) and ``orient`` after those of the list above and before the blend and post
 what the calibration data was prepared with).  ``predict.csv`` then gains the column ``antialias`` (the sigmas of the
 three array axes, ``0 0 0`` for a subject with nothing to filter) after the orient columns and before those of
 ``--blend``; without ``--prep_spacing`` the switch is refused by name.
+
+``--prep_interp cubic`` (with ``--prep_spacing``) resamples the images by cubic B-spline interpolation as ``prep`` does
+(pass what the calibration data was prepared with).  ``predict.csv`` then gains the column ``interp`` (``cubic``) after
+the ``antialias`` column's place and before those of ``--blend``; the step back to the scan's grid stays trilinear on
+the logits.  ``linear``, the default, changes nothing; another value, or cubic without ``--prep_spacing``, is refused by
+name.
 
 ``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched;
 ``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
@@ -189,6 +195,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
     no_crop = bool(getattr(args, "prep_no_crop", False))
     orient = prep.parse_orient(getattr(args, "prep_orient", None))
     antialias = prep.antialias_switch(args, spacing)
+    interp = prep.interp_switch(args, spacing)
     from . import config as Cf
     blend, flips = Cf.blend_switches(args)
     sliding = (blend, flips) != ("uniform", (0,))
@@ -199,7 +206,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
 
     # everything the list and the headers decide, before anything touches the device or out_dir
     entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
-    plans = [prep._Plan(e, mods, spacing, min_size, orient, antialias) for e in entries]
+    plans = [prep._Plan(e, mods, spacing, min_size, orient, antialias, interp) for e in entries]
     if ops is None:
         from .hip_ops import get_ops
         ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
@@ -303,11 +310,13 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                 row["source_orient"] = plan.orient_code
             if antialias:
                 row["antialias"] = prep._fmt(plan.sigmas)
+            if interp == "cubic":
+                row["interp"] = interp
             if post:
                 row["post_changed"] = changed
             rows.append(row)
             turned = f" ({plan.orient_code} -> {orient})" if orient and plan.orient_code != orient else ""
-            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned}{prep.antialias_said(plan)} -> grid "
+            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned}{prep.antialias_said(plan)}{prep.interp_said(plan)} -> grid "
                   f"{prep._fmt(plan.grid_shape)}, box at {prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
                   f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
                   f"{row['voxels']} voxels{cleaned}{extra}")
@@ -320,6 +329,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         w.result()                              # re-raises a failed write
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
                CSV_HEADER + (prep.ORIENT_COLUMNS if orient else []) + (prep.ANTIALIAS_COLUMNS if antialias else []) +
+               (prep.INTERP_COLUMNS if interp == "cubic" else []) +
                (CSV_BLEND_COLUMNS if sliding else []) +
                (CSV_THRESH_COLUMNS if thresh is not None else []) + (CSV_POST_COLUMNS if post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")

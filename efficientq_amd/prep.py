@@ -2,8 +2,8 @@
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
         [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|none] \
-        [--prep_orient RAS] [--prep_spacing d,h,w [--prep_antialias]] [--prep_min_size d,h,w] [--prep_no_crop] \
-        [--access_type npy|npz]
+        [--prep_orient RAS] [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
+        [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
 ``--src_list`` is a CSV with the header ``subject,<modality>,...[,seg]`` (the task's modalities, data.MODALITIES, in any
 order) and one row per subject with one NIfTI path per column, relative to the CSV unless absolute; an empty ``seg``
@@ -17,7 +17,9 @@ cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
                they are down-sampled, per axis of factor f = target / source spacing > 1 with sigma = (f - 1) / 2 and
                the radius int(4 sigma + 0.5) (antialias_taps; csrc/prep_smooth.hip); the label is not touched
     resample   --prep_spacing d,h,w: trilinear for the images, nearest for the label; no filter before down-sampling
-               unless --prep_antialias asks for one
+               unless --prep_antialias asks for one.  --prep_interp cubic: the images by cubic B-spline interpolation
+               instead (the rule below at CUBIC_POLE; csrc/prep_spline.hip), on the same grid; the window is applied
+               once more after it, since a cubic spline overshoots; the label stays nearest
     pass 1     the box of the union of the modalities' masks, per modality the count and the sum over its own mask
                (--prep_mask nonzero: x != 0, the brats default; all: every voxel, the lits default)
     pass 2     per modality the squared deviations from the mean of pass 1; std = sqrt(sqdev / count)
@@ -32,6 +34,9 @@ so ``ptq --src_geom --save_nii`` writes maps that overlay the scan; with it the 
 also one that was oriented as asked already), and prep.csv gains the columns ``source_orient`` and ``orient``.
 With ``--prep_antialias`` prep.csv gains the column ``antialias`` after all others: the sigmas of the three array axes
 in voxels of the source grid, ``0 0 0`` for a subject no axis of which is down-sampled far enough to be filtered.
+With ``--prep_interp cubic`` prep.csv gains the column ``interp`` (``cubic``) after all others, the anti-alias column
+included.  A NaN or an Inf in a scan is carried along whole lines by the spline's recursions; the check of the standard
+deviation then stops the run at that subject.
 ``--split_dir --val_every K`` also writes ``split_dir/round<R>/{train,val}.txt``.
 
 What the headers decide (the list itself, shapes and affines within a subject, a grid smaller than --prep_min_size, a
@@ -157,6 +162,39 @@ def antialias_taps(sigma: float) -> np.ndarray:
     g = np.exp(-(k * k) / (2.0 * float(sigma) * float(sigma)))
     g /= g.sum()
     return g[r:].astype(np.float32)
+
+
+# ---- cubic B-spline resampling (host, no device) -----------------------------------------------------------------------
+# The one definition of the rule of --prep_interp cubic; include/effq_hip.h (effq_prep_resample_cubic) restates it.
+# 1 Prefilter (the B-spline coefficient transform), along each array axis of extent n >= 2, in fp64: the coefficients c
+#   solve (c[k-1] + 4 c[k] + c[k+1]) / 6 = x[k] with the whole-sample mirror c[-1] = c[1], c[n] = c[n-2] (scipy's
+#   mode='mirror'), by the recursion with the pole z = CUBIC_POLE and the gain CUBIC_GAIN:
+#     c+[0] = 6 sum_{k=0}^{2n-3} z^k xm[k] / (1 - z^(2n-2)), xm the mirrored line of period 2n - 2: the exact sum, no
+#       truncated horizon;  c+[k] = 6 x[k] + z c+[k-1];
+#     c[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]);  c[k] = z (c[k+1] - c+[k]).
+#   An axis of extent 1 is not filtered; all three axes are filtered, one with factor 1 included (it is the same spline).
+# 2 Evaluation: output index o of an axis sits at s = (o + 0.5) f - 0.5 in fp64, clamped to [0, n - 1] (the coordinate of
+#   the trilinear path); i0 = floor(s), t = s - i0, and the weights on c[i0-1 .. i0+2] are cubic_weights(t), the indices
+#   -1 and n mirrored; on an axis of extent 1 the one coefficient has weight 1.  The 64 terms are summed in fp64, w
+#   innermost, then h, then d, and the sum is rounded to float32 once.  The output extents and the grid's affine are
+#   resample_extent and resample_affine: the grid does not change with the order.
+# 3 With --prep_mask nonzero (zero_keep) an output voxel is exactly 0 when every source voxel of its trilinear footprint
+#   is exactly 0 (per axis i0 and i0 + 1, the second only when s > i0 and i0 < n - 1; a NaN is not 0): the prefilter has
+#   infinite support, and the calibration takes exact 0 as background.  The body cannot grow past what the trilinear
+#   step reaches.  --prep_mask all: nothing is kept.
+# 4 With a --prep_window in force the window is applied once more after the resampling: values lie in [lo, hi].
+# 5 A NaN or an Inf is carried along whole lines; the check of the standard deviation stops the run at that subject.
+CUBIC_POLE = math.sqrt(3.0) - 2.0
+CUBIC_GAIN = 6.0
+INTERP_ORDERS = ("linear", "cubic")
+INTERP_COLUMNS = ["interp"]      # prep.csv and predict.csv, only with --prep_interp cubic
+
+
+def cubic_weights(t: float) -> Tuple[float, float, float, float]:
+    """The cubic B-spline's weights on the coefficients i0 - 1, i0, i0 + 1, i0 + 2 at the offset t = s - i0 in [0, 1)."""
+    t = float(t)
+    return ((1.0 - t) ** 3 / 6.0, (3.0 * t ** 3 - 6.0 * t ** 2 + 4.0) / 6.0,
+            (-3.0 * t ** 3 + 3.0 * t ** 2 + 3.0 * t + 1.0) / 6.0, t ** 3 / 6.0)
 
 
 # ---- orientation (host, no device) ---------------------------------------------------------------------------------------
@@ -325,6 +363,23 @@ def antialias_switch(args, spacing) -> bool:
     return on
 
 
+def interp_switch(args, spacing) -> str:
+    """--prep_interp of `args` (or the YAML key): 'linear' (also when absent) or 'cubic'; any other value is refused by
+    name, and so is cubic without --prep_spacing, since it is the resampling that interpolates."""
+    order = getattr(args, "prep_interp", None)
+    order = "linear" if order is None else str(order).strip().lower()
+    if order not in INTERP_ORDERS:
+        raise PrepError(f"--prep_interp {getattr(args, 'prep_interp', None)!r}: linear or cubic")
+    if order == "cubic" and spacing is None:
+        raise PrepError("--prep_interp cubic is how --prep_spacing resamples the images: it needs --prep_spacing d,h,w")
+    return order
+
+
+def interp_said(plan) -> str:
+    """What the per-subject line says of the interpolation: nothing for linear."""
+    return ", cubic" if plan.interp == "cubic" else ""
+
+
 def antialias_said(plan) -> str:
     """What the per-subject line says of the filter: the sigmas when any is above 0, else nothing."""
     return f", anti-alias sigma {_fmt(plan.sigmas)}" if any(s > 0 for s in plan.sigmas) else ""
@@ -334,8 +389,9 @@ class _Plan:
     """What the headers of one subject decide."""
 
     def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size, orient: Optional[str] = None,
-                 antialias: bool = False):
+                 antialias: bool = False, interp: str = "linear"):
         sn = self.subject = entry["subject"]
+        self.interp = interp if spacing is not None else "linear"      # how the images are resampled (--prep_interp)
         self.entry = entry
         heads = {}
         for name, path in list(entry["images"].items()) + ([(D.LABEL_MODALITY, entry["seg"])] if entry["seg"] else []):
@@ -519,7 +575,12 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
     if plan.factors is not None:
         if any(r > 0 for r in plan.radii):       # --prep_antialias; the label is not filtered
             x = ops.prep_smooth(x, plan.sigmas, mask == "nonzero")
-        x = ops.prep_resample(x, plan.factors, plan.grid_shape)
+        if plan.interp == "cubic":       # --prep_interp cubic; the spline overshoots, so the window once more
+            x = ops.prep_resample_cubic(x, plan.factors, plan.grid_shape, mask == "nonzero")
+            if window is not None:
+                ops.prep_window(x, window[0], window[1])
+        else:
+            x = ops.prep_resample(x, plan.factors, plan.grid_shape)
         if lab is not None:
             lab = ops.prep_resample(lab, plan.factors, plan.grid_shape, nearest=True)
     bbox, count, total = ops.prep_bbox_moments(x, mask)
@@ -568,6 +629,7 @@ def run(args, ops=None) -> List[dict]:
     no_crop = bool(getattr(args, "prep_no_crop", False))
     orient = parse_orient(getattr(args, "prep_orient", None))
     antialias = antialias_switch(args, spacing)
+    interp = interp_switch(args, spacing)
     access = getattr(args, "access_type", None) or "npy"
     if access not in D.ACCESS_TYPES:
         raise PrepError(f"--access_type {access!r}: one of {', '.join(D.ACCESS_TYPES)}")
@@ -575,7 +637,7 @@ def run(args, ops=None) -> List[dict]:
 
     # everything the list and the headers decide, before anything is written
     entries = read_src_list(args.src_list, task)
-    plans = [_Plan(e, mods, spacing, min_size, orient, antialias) for e in entries]
+    plans = [_Plan(e, mods, spacing, min_size, orient, antialias, interp) for e in entries]
     split = None
     if getattr(args, "split_dir", None):
         k = getattr(args, "val_every", None)
@@ -628,13 +690,15 @@ def run(args, ops=None) -> List[dict]:
                 turned = f" ({plan.orient_code} -> {orient})" if plan.orient_code != orient else ""
             if antialias:
                 row.update(antialias=_fmt(plan.sigmas))
+            if interp == "cubic":
+                row.update(interp=interp)
             rows.append(row)
-            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned}{antialias_said(plan)} -> {_fmt(y.shape[1:])} at "
+            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned}{antialias_said(plan)}{interp_said(plan)} -> {_fmt(y.shape[1:])} at "
                   f"{_fmt(pmin)}")
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
     write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods) + (ORIENT_COLUMNS if orient else []) +
-                      (ANTIALIAS_COLUMNS if antialias else []))
+                      (ANTIALIAS_COLUMNS if antialias else []) + (INTERP_COLUMNS if interp == "cubic" else []))
     if split is not None:
         names = [p.subject for p in plans]
         val = names[k - 1::k]

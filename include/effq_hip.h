@@ -1005,6 +1005,48 @@ int effq_prep_union_mask(const float* x, int C, long long S, int mask_mode, uint
 int effq_prep_smooth(const float* x, int N, int D, int H, int W, const float* taps_d, int rd, const float* taps_h, int rh,
                      const float* taps_w, int rw, int keep_zero, float* y, float* tmp, void* stream);
 
+/* ---- cubic B-spline resampling (csrc/prep_spline.hip; prep.py --prep_interp cubic, where the rule is defined):
+ * x (N, D, H, W) fp32 -> y (N, OD, OH, OW) fp32 with the factors and the output extents of effq_prep_resample; x is not
+ * modified.  The extents of x and of y obey the limits of the prep kernels (N D H W < 2^31, every extent <= 32767).
+ * 1 Prefilter, the B-spline coefficient transform, along D, then H, then W, in fp64 into `ws`
+ *   (*bytes of effq_prep_cubic_ws_bytes = 8 N D H W, 8-B aligned).  Per axis of extent n >= 2 the coefficients solve
+ *   (c[k-1] + 4 c[k] + c[k+1]) / 6 = x[k] with the whole-sample mirror c[-1] = c[1], c[n] = c[n-2] (scipy's
+ *   mode='mirror'), by the recursion with the pole z = sqrt(3) - 2 and the gain 6:
+ *     c+[0] = 6 s / (1 - z^(2n-2)),  s = sum_{k=0}^{2n-3} z^k xm[k],  xm the mirrored line (xm[k] = x[k] for k < n,
+ *       x[2n-2-k] after it): the exact sum over the period, no truncated horizon (a term whose power z^k, formed by
+ *       repeated multiplication, has underflowed to 0 in fp64 is 0 and is not visited);
+ *     c+[k] = 6 x[k] + z c+[k-1];   c[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]);   c[k] = z (c[k+1] - c+[k]).
+ *   An axis of extent 1 is not filtered; all three axes are filtered whatever their factors.
+ * 2 Evaluation.  Output index o of an axis sits at s = (o + 0.5) f - 0.5 in fp64, clamped to [0, n - 1] (the coordinate
+ *   of EFFQ_PREP_LINEAR); i0 = floor(s), t = s - i0; the weights on c[i0-1 .. i0+2] are (1-t)^3 / 6,
+ *   (3t^3 - 6t^2 + 4) / 6, (-3t^3 + 3t^2 + 3t + 1) / 6, t^3 / 6, the indices -1 and n mirrored (an index still outside
+ *   after that has weight 0 and is clamped); on an axis of extent 1 the one coefficient has weight 1.  The 64
+ *   coefficients are combined in fp64 in one fixed order, w innermost, then h, then d: the four products of a row are
+ *   added in index order, the four row sums times their h weights likewise, then the four plane sums times their d
+ *   weights; the sum is rounded to fp32 once.  Nothing is fused.
+ * 3 zero_keep = 1: an output voxel is exactly +0.0f when every source voxel of its trilinear footprint is exactly 0
+ *   (per axis i0 and i0 + 1, the second only when s > i0 and i0 < n - 1; a NaN is not 0), so a zero background stays
+ *   exactly zero and the body reaches no further than under EFFQ_PREP_LINEAR.  zero_keep = 0: no voxel is treated so.
+ * A NaN or an Inf is carried along its whole lines by the recursions, and from there over the volume.
+ * Four launches (three prefilter passes, one evaluation), no atomics, grids that depend on the extents alone: equal
+ * inputs give equal bits.  Refused with EFFQ_ERR_ARG before any launch: a null x, y or ws, extents outside the limits, x
+ * or y not aligned to 4 B, ws not aligned to 8 B, ws_bytes below what effq_prep_cubic_ws_bytes gives (itself refused
+ * for extents outside the limits), a factor outside (0, 1e6] or NaN, zero_keep other than 0 and 1.
+ * effq_prep_cubic_plan (launches nothing): *chunk = the voxels of a row the W pass visits at a time, *tile_rows = the rows
+ * of one of its tiles; items[4] = the work items of the D, H and W prefilter passes (lines, lines, rows; 0 for a pass that
+ * is not launched: H = 1, W = 1) and of the evaluation (groups of four output voxels along W); trip[4] = how many of
+ * them one trip of each launch's capped grid covers (items > trip: the grid-stride loop takes a further trip).
+ * effq_prep_spline_prefilter: the passes of step 1 alone (`passes` = a sum of EFFQ_PREP_SPLINE_PASS_*; D reads x and writes
+ * ws, H and W work in place in ws; x may be null without the D pass), for tests and profiles. */
+enum { EFFQ_PREP_SPLINE_PASS_D = 1, EFFQ_PREP_SPLINE_PASS_H = 2, EFFQ_PREP_SPLINE_PASS_W = 4 };
+int effq_prep_cubic_ws_bytes(int N, int D, int H, int W, size_t* bytes);
+int effq_prep_cubic_plan(int N, int D, int H, int W, int OD, int OH, int OW, int* chunk, int* tile_rows, long long* items,
+                         long long* trip);
+int effq_prep_spline_prefilter(const float* x, int N, int D, int H, int W, int passes, void* ws, size_t ws_bytes,
+                               void* stream);
+int effq_prep_resample_cubic(const float* x, int N, int D, int H, int W, double fd, double fh, double fw, int zero_keep,
+                             float* y, int OD, int OH, int OW, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reorientation (csrc/reorient.hip; prep.py --prep_orient): x (N, D, H, W) -> y (N, dims[src_axis[0]],
  * dims[src_axis[1]], dims[src_axis[2]]) with dims = {D, H, W}: output axis p is source axis src_axis[p] (three host ints,
  * a permutation of 0, 1, 2, read before the call returns), reversed iff bit p of flip_mask is set:

@@ -6,6 +6,10 @@ events, one JSON line per subject.
   with the anti-alias filter of --prep_antialias ahead of it: `smooth` is the whole filter, `smooth_d`, `smooth_h`,
   `smooth_w` one filtered axis each (one pass: the volume read once and written once);
 --size d,h,w with --modalities C: any other grid.
+--factors d,h,w resamples any of them (brats: not resampled without it).  Beside `resample` (trilinear) the cubic
+  B-spline path of --prep_interp cubic is timed: `resample_cubic` is the whole call (three prefilter passes and the
+  evaluation), `spline_d`, `spline_h`, `spline_w` one prefilter pass each (d reads the float32 volume and writes the fp64
+  coefficients, h and w filter them in place: read once and written once, 16 B per voxel), `cubic_eval` the rest.
 Each step runs once unmeasured, then REPS times (median), warm and after 512 MiB of other writes have pushed the subject
 out of the Infinity Cache.  gbps = the bytes the step must move (what it reads once plus what it writes) over the time;
 hbm_frac = that over the 8 TB/s peak.  numpy_ms is the same arithmetic on the host in numpy, one run, as context."""
@@ -33,10 +37,10 @@ if cli.size == "brats":
     C, grid, mask, window, factors = 4, (240, 240, 155), "nonzero", None, None
 elif cli.size == "lits":
     C, grid, mask, window, factors = 1, (512, 512, cli.depth), "all", (-200.0, 250.0), (2.0, 2.0, 0.64)
-    if cli.factors:
-        factors = tuple(float(v) for v in cli.factors.split(","))
 else:
     C, grid, mask, window, factors = cli.modalities, tuple(int(v) for v in cli.size.split(",")), "nonzero", None, None
+if cli.factors:
+    factors = tuple(float(v) for v in cli.factors.split(","))
 S = grid[0] * grid[1] * grid[2]
 x = torch.randn(C, *grid, generator=g) * 300.0 + 40.0
 if mask == "nonzero":
@@ -84,6 +88,17 @@ if factors is not None:
             one = tuple(sig[b] if b == a else 0.0 for b in range(3))
             step("smooth_" + "dhw"[a], lambda: ops.prep_smooth(x, one, mask == "nonzero"), 2 * 4 * C * S)
     step("resample", lambda: ops.prep_resample(x, factors, out), 4 * C * (S + out[0] * out[1] * out[2]))
+    # --prep_interp cubic: the whole call, then its prefilter passes one by one; the evaluation is the difference
+    O = out[0] * out[1] * out[2]
+    step("resample_cubic", lambda: ops.prep_resample_cubic(x, factors, out, mask == "nonzero"),
+         C * (4 * S + 8 * S + 2 * 16 * S + 8 * S + 4 * O))
+    coef = ops.prep_spline_prefilter(x, "d")
+    step("spline_d", lambda: ops.prep_spline_prefilter(x, "d", out=coef), C * (4 + 8) * S)
+    for a in "hw":
+        step("spline_" + a, lambda: ops.prep_spline_prefilter(x, a, out=coef), C * 16 * S)      # in place, again and again
+    res["cubic_eval"] = {"ms": round(res["resample_cubic"]["ms"] - sum(res["spline_" + a]["ms"] for a in "dhw"), 4),
+                         "bytes": C * (8 * S + 4 * O)}
+    del coef
     x = ops.prep_resample(x, factors, out)
     grid, S = out, out[0] * out[1] * out[2]
     res["resampled_grid"] = list(grid)
@@ -97,7 +112,8 @@ crop = (pmax[0] - pmin[0]) * (pmax[1] - pmin[1]) * (pmax[2] - pmin[2])
 step("standardise_crop", lambda: ops.prep_standardise_crop(x, pmin, pmax, mean, std, mask), 2 * 4 * C * crop)
 res["crop"] = [list(pmin), list(pmax)]
 res["device_ms_total"] = round(sum(v["ms"] for k, v in res.items()
-                                   if isinstance(v, dict) and not k.startswith("smooth_")), 3)      # `smooth` holds its passes
+                                   if isinstance(v, dict) and not k.startswith(("smooth_", "spline_", "cubic_")) and
+                                   k != "resample_cubic"), 3)      # the trilinear pipeline; `smooth` holds its passes
 
 if not cli.no_numpy:
     h = x.cpu().numpy()
