@@ -136,6 +136,8 @@ SIGNATURES = {
     "effq_gram_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_accum": (_I, [_P, _P, _P, _GP, _I, _P, _P, _I, _P, _SZ, _P]),
     "effq_gram_plan_query": (_I, [_GP, _I, _IP, _IP, _IP, _IP, _LLP, _IP, _IP]),
+    "effq_gram_streamed": (_I, [_P, _P, _GP, _I]),
+    "effq_gram_finish": (_I, [_GP, _I, _P, _P, _I, _P, _SZ, _P]),
     "effq_gram_i8_supported": (_I, [_GP, _I]),
     "effq_gram_i8_ws_bytes": (_SZ, [_GP, _I]),
     "effq_gram_accum_i8": (_I, [_P, _P, _GP, _I, _P, _I, _P, _P, _P, _I, _LL, _P, _P, _I, _P, _SZ, _P]),

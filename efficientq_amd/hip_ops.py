@@ -487,6 +487,10 @@ class HipOps:
         return dict(vec=bool(vec.value), NB=nb.value, npairs=npairs.value, nsplit=nsplit.value, vox_per_split=vps.value,
                     fold=fold.value, finish_blocks=fin.value)
 
+    def gram_streamed(self, x_ndhwc: torch.Tensor, y_ndhwc: torch.Tensor, geom: Geom, has_bias: bool) -> bool:
+        """Whether gram() gathers these inputs with its streamed kernel (effq_gram_streamed; launches nothing)."""
+        return bool(self.lib.effq_gram_streamed(_ptr(x_ndhwc), _ptr(y_ndhwc), C.byref(geom), int(has_bias)))
+
     def gram_i8_plan(self, geom: Geom, ncls: int = 1, n_list: int = 0) -> dict:
         """The launch gram_i8() makes for a geometry, ncls classes and a voxel list of n_list slots (0: no list)
         (effq_gram_i8_plan_query; launches nothing)."""

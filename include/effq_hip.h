@@ -245,9 +245,17 @@ int effq_gram_accum(const float* x_ndhwc, const float* att, const float* y_ndhwc
 /* The launch effq_gram_accum makes for a geometry; launches nothing.  *vec: 1 = the kernel that stages 16-byte cells
  * (C1 and C2 multiples of 4), 0 = the row-by-row kernel; the grid is *npairs blocks of the upper block triangle (*nb
  * 128-row blocks per side) x *nsplit voxel ranges of *vox_per_split voxels; the fp32 accumulators are folded into fp64 every
- * *fold chunks of 32 voxels; *finish_blocks workgroups add the slabs up (8192 at most, strided beyond). */
+ * *fold chunks of 32 voxels; *finish_blocks groups of 256 threads (four workgroups each) add the slabs up (8192 at most, strided beyond). */
 int effq_gram_plan_query(const effq_geom* g, int has_bias, int* vec, int* nb, int* npairs, int* nsplit,
                          long long* vox_per_split, int* fold, int* finish_blocks);
+/* 1 where effq_gram_accum gathers these inputs with the streamed kernel (C1 a multiple of 4 and x 16-byte aligned; y by
+ * 16-byte cells where C2 is a multiple of 4 and y is aligned, by values up to C2 = 32 otherwise), 0 where with the kernels
+ * *vec of effq_gram_plan_query names; both give the same bits.  Launches nothing. */
+int effq_gram_streamed(const float* x_ndhwc, const float* y_ndhwc, const effq_geom* g, int has_bias);
+/* The second launch of effq_gram_accum alone (profiling): A0 / B0 from the slabs a previous effq_gram_accum of the same
+ * geometry left in ws. */
+int effq_gram_finish(const effq_geom* g, int has_bias, float* A0, float* B0, int accumulate, void* ws, size_t ws_bytes,
+                     void* stream);
 
 /* The same A0/B0 for a layer whose input is already quantised (EfficientQConv.py:64-72 ran first), evaluated
  * exactly on the i8 matrix cores: xidx = level ids of the quantised input (uint8, NDHWC, value k means
