@@ -1,13 +1,17 @@
 """Launch one conv-step shape a few times (used under rocprofv3 --kernel-trace / --pmc so traces stay small).
 usage: prof_conv.py MODE [n]   MODE: f32_32 (32->32 3^3, 16x64^3, f32 MFMA) | i8_32 (same shape, exact-int)
-                               | f32_128 (128->128 3^3, 16x16^3) | i8_64 | i8_128 | i8_256 (exact-int, 16x32^3 / 16^3 / 8^3)"""
+                               | f32_128 (128->128 3^3, 16x16^3) | i8_64 | i8_128 | i8_256 (exact-int, 16x32^3 / 16^3 / 8^3)
+                               | i8_32r (16x62^3, ragged: k_conv3d_i8l2) | i8_64r (16x30^3, ragged: k_conv3d_i8<2>)
+                               | i8_512 (512->512, 8x10^3: k_conv3d_i8g2<16>) | i8_32o | i8_64o (i8_32 / i8_64 through
+                                 conv_forward_i8: the output-storing forms of k_conv3d_i8l2e and k_conv3d_i8w)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from efficientq_amd.hip_ops import get_ops, make_geom
 mode = sys.argv[1] if len(sys.argv) > 1 else "f32_32"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-N, C, S = {"f32_128": (16, 128, 16), "i8_64": (16, 64, 32), "i8_128": (16, 128, 16), "i8_256": (16, 256, 8)}.get(mode, (16, 32, 64))
+N, C, S = {"f32_128": (16, 128, 16), "i8_64": (16, 64, 32), "i8_128": (16, 128, 16), "i8_256": (16, 256, 8),
+           "i8_32r": (16, 32, 62), "i8_64r": (16, 64, 30), "i8_512": (8, 512, 10), "i8_64o": (16, 64, 32)}.get(mode, (16, 32, 64))
 dev = "cuda:0"
 ops = get_ops(dev)
 g = torch.Generator().manual_seed(0)
@@ -26,7 +30,9 @@ st_w = ops.new_fp_state()
 ops.weight_fixed_point(w, dual, v, 4, st_w)
 ops.admm_project_dual(v, w, st_w, 4, G, dual, 1.0, Gq)
 def step():
-    if mode.startswith("i8"):
+    if mode in ("i8_32o", "i8_64o"):
+        sq.copy_(ops.conv_forward_i8(xidx, G, b, geom, y, None, alpha, 4, st_w, 4)[1])
+    elif mode.startswith("i8"):
         ops.conv_step_i8(xidx, Gq, b, geom, y, alpha, 4, st_w, 4, sq)
     else:
         ops.conv_step(xq, G, b, geom, y, None, sqerr=sq)
