@@ -349,8 +349,8 @@ struct AdmmIter {                  // iteration i: the rho it runs with and hand
   float *G, *bstar;
   int8_t* Gq;
   effq_fp_state* st;
-  const float* parts;              // set by enqueue_prox where it leaves the K slices of the product for the trajectory
-  int parts_n, parts_ld;           // kernel to add up in its prologue (one launch less); NULL: the product is whole
+  ProxParts parts;                 // set by enqueue_prox where it leaves the K slices of the product for the trajectory
+                                   // kernel to add up in its prologue (one launch less); part == NULL: the product is whole
 };
 static AdmmIter admm_iter(const effq_admm_run_args* a, const AdmmPlan& p, int i, double rho, bool use_traj) {
   const bool step = i % a->rho_period == 0, doubles = rho * 2 <= a->rho_max;   // rho changes after this iteration
@@ -360,21 +360,24 @@ static AdmmIter admm_iter(const effq_admm_run_args* a, const AdmmPlan& p, int i,
                   !step ? 1.0f : doubles ? 2.0f : (float)(a->rho_max / rho), use_shift, use_traj, prof, i + 1 < a->iters,
                   (i == 0) ? a->W0 : a->G_ring + (size_t)(i - 1) * p.nw, a->G_ring + (size_t)i * p.nw,
                   p.has_b ? a->b_ring + (size_t)i * p.c2 : nullptr, a->Gq_ring ? a->Gq_ring + (size_t)i * p.nw : nullptr,
-                  a->state_ring + i, nullptr, 1, 0};
+                  a->state_ring + i, ProxParts{nullptr, 1, 0}};
 }
 
 static int enqueue_prox(const effq_admm_run_args* a, const AdmmPlan& p, AdmmIter* it, const float* Ainv, bool bm_ready) {
-  if (!it->use_shift && bm_ready && it->use_traj && p.c2 <= 512)
-    return effq_prox_solve_prebuilt_parts(a->B0, Ainv, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho,
-                                          a->eta, a->wstar, it->bstar, a->prox_ws, a->prox_ws_bytes, p.s_main,
-                                          &it->parts, &it->parts_n, &it->parts_ld);
-  if (it->use_shift)
-    return effq_prox_solve_shifted(a->B0, a->ainv_pool, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho,
-                                   a->eta, p.rhos.rho[1], shift_terms(it->rho, a->eta, p.rhos.rho[1]), a->wstar, it->bstar,
-                                   a->prox_ws, a->prox_ws_bytes, p.s_main);
-  const auto solve = bm_ready ? effq_prox_solve_prebuilt : effq_prox_solve;   // Bm written by the last projection or not
-  return solve(a->B0, Ainv, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho, a->eta, a->wstar, it->bstar,
-               a->prox_ws, a->prox_ws_bytes, p.s_main);
+  // prebuilt: Bm written by the last projection or not
+  ProxSolve s = {a->B0, Ainv, a->W0, a->b0, it->G_prev, a->dual, p.c2, p.n, p.has_b, it->rho, a->eta, 0.0, 1, bm_ready,
+                 a->wstar, it->bstar, a->prox_ws, a->prox_ws_bytes, nullptr};
+  if (it->use_shift) {             // through the inverse of A(rho[1]), its Bm rebuilt for every term
+    const double rho_inv = p.rhos.rho[1];
+    EFFQ_CHECK_ARG(rho_inv >= it->rho && it->rho > 0.0 && a->eta >= 0.0);
+    s.Ainv = a->ainv_pool;
+    s.shift = rho_inv - it->rho;
+    s.nterms = shift_terms(it->rho, a->eta, rho_inv);
+    s.prebuilt = false;
+  } else if (bm_ready && it->use_traj && p.c2 <= 512) {
+    s.parts = &it->parts;
+  }
+  return effq_prox_enqueue(&s, p.s_main);
 }
 
 enum class FpKind { channels, traj, bucket, small, coop };   // the weight-scale fixed point of an iteration
@@ -416,8 +419,8 @@ static int enqueue_fixed_point(const effq_admm_run_args* a, const AdmmPlan& p, c
                                         a->w_iters_ring ? a->w_iters_ring + (size_t)it.i * p.c2 : nullptr, a->err_flag,
                                         it.G, it.dual_div, it.next_rhs ? p.bm : nullptr, a->B0, a->W0, p.n, p.bm_ld,
                                         it.rho_next, a->eta, p.s_main);
-  else if (kind == FpKind::traj && it.parts != nullptr)
-    rc = effq_fixed_point_traj_parts(it.parts, it.parts_n, it.parts_ld, p.c2, nwrow, p.has_b, a->dual, a->wstar, it.bstar,
+  else if (kind == FpKind::traj && it.parts.part != nullptr)
+    rc = effq_fixed_point_traj_parts(it.parts.part, it.parts.nsplit, it.parts.ldp, p.c2, nwrow, p.has_b, a->dual, a->wstar, it.bstar,
                                      a->v, a->w_levels, -1.0, 1.0, a->tol, maxit, it.st, a->fp_pred, a->fp_traj_ws,
                                      a->fp_traj_ws_bytes, p.s_main);
   else if (kind == FpKind::traj)

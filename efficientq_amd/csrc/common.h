@@ -31,6 +31,7 @@ void set_error(const char* fmt, ...);
 #define EFFQ_LAUNCH_CHECK() EFFQ_HIP(hipGetLastError())
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // Raises KERNEL's dynamic-LDS limit on the current device to at least `bytes`.  The attribute belongs to the device, so
 // the record of what was set is kept per device (hipGetDevice): a fixed size is set once per device, a varying one again

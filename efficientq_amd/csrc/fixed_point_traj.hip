@@ -148,7 +148,7 @@ int effq_fixed_point_traj(const float* a, const float* b, float* v_out, size_t n
   return EFFQ_OK;
 }
 
-// internal (admm_run.hip): the same on the K slices of the prox product (effq_prox_solve_prebuilt_parts): w* = their sum is
+// internal (admm_run.hip): the same on the K slices of the prox product (effq::ProxParts): w* = their sum is
 // written to wstar_out ([c2][nwrow]), b* to bstar_out, v = w* + dual to v_out
 int effq_fixed_point_traj_parts(const float* part, int nsplit, int ldp, int c2, int nwrow, int has_bias, const float* dual,
                                 float* wstar_out, float* bstar_out, float* v_out, int levels, double lo, double hi, double tol,

@@ -269,8 +269,6 @@ __global__ __launch_bounds__(256) void k_gl8_finish(const Gl8Fin p) {
   }
 }
 
-static inline int g8_round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 }  // namespace effq
 using namespace effq;
 
@@ -294,14 +292,14 @@ int effq_gram_loss_i8_num_planes(long long kmax) {
 size_t effq_gram_loss_i8_planes_bytes(int n, int has_bias, int nplanes) {
   const int nw = n - (has_bias ? 1 : 0);
   if (nw <= 0 || nplanes <= 0) return 0;
-  return (size_t)nplanes * (size_t)g8_round_up(nw, G8_TM) * (size_t)nw;
+  return (size_t)nplanes * (size_t)round_up(nw, G8_TM) * (size_t)nw;
 }
 
 int effq_gram_loss_i8_prepare(const double* Au, int n, int has_bias, const float* act_alpha_dev, int act_levels,
                               int nplanes, int8_t* planes, int32_t* err_flag_dev, void* stream) {
   EFFQ_CHECK_ARG(Au && act_alpha_dev && planes && err_flag_dev && n > 1 && act_levels >= 2);
   EFFQ_CHECK_ARG(nplanes >= 1 && nplanes <= G8_MAXP);
-  const int nw = n - (has_bias ? 1 : 0), nwp = g8_round_up(nw, G8_TM);
+  const int nw = n - (has_bias ? 1 : 0), nwp = round_up(nw, G8_TM);
   size_t nb = ((size_t)nwp * nw + 255) / 256;
   if (nb > 8192) nb = 8192;
   hipLaunchKernelGGL(k_gl8_planes, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), Au, n, nw, nwp, act_alpha_dev,
@@ -335,7 +333,7 @@ int effq_gram_loss_i8(const int8_t* planes, int nplanes, const double* Au, const
   double* partials = reinterpret_cast<double*>(base + 256 + sizeof(unsigned long long) * G8_MAXGROUP);
   Gl8Params p;
   p.planes = planes; p.Gq = Gq; p.Qacc = Qacc;
-  p.P = nplanes; p.nw = nw; p.nwp = g8_round_up(nw, G8_TM); p.ncols = count * c2; p.c2 = c2;
+  p.P = nplanes; p.nw = nw; p.nwp = round_up(nw, G8_TM); p.ncols = count * c2; p.c2 = c2;
   p.mt = p.nwp / G8_TM; p.nt = (p.ncols + G8_TN - 1) / G8_TN;
   p.ntiles = p.mt * p.P * p.nt;
   p.ticket = tile_ticket;

@@ -8,9 +8,17 @@
 
 namespace effq {
 
-// Optional extra output of the projection: Bm = B0 + eta [W0|b0] + rho (G - dual) for the next iteration's prox solve,
-// element for element what k_build_b4 (solve.hip) computes - one launch per ADMM iteration less.  The bias column and the
-// zero padding of Bm do not depend on the iterate: they stay as the first build of the layer left them.
+// One weight column of the prox solve's right-hand side Bm = B0 + eta [W0|b0] + rho [G - dual|0] (solver.py:316-322) in
+// the reference's fp32 operation order.  The build kernels of prox_solve.hip and the projections below all form it here:
+// a solve on a Bm the projection left equals a solve that builds its own, bit for bit.
+__device__ __forceinline__ float prox_rhs(float b0, float w0, float g, float dual, float eta, float rho) {
+  const float t = b0 + eta * w0;
+  return t + rho * (g - dual);
+}
+
+// Optional extra output of the projection: Bm's weight columns (prox_rhs) for the next iteration's prox solve - one launch
+// per ADMM iteration less.  The bias column and the zero padding of Bm do not depend on the iterate: they stay as the
+// first build of the layer left them.
 struct ProjNext {
   float* Bm;
   const float* B0;
@@ -62,7 +70,7 @@ __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const fl
     }
     *reinterpret_cast<char4*>(Gq + i) = c;
   }
-  if (nx.Bm != nullptr) {                       // right-hand side of the NEXT prox solve (k_build_b4's arithmetic)
+  if (nx.Bm != nullptr) {                       // right-hand side of the NEXT prox solve
     const unsigned i32 = q * 4u;
     const unsigned r = i32 / (unsigned)nx.nwrow, k = i32 - r * (unsigned)nx.nwrow;   // a group of 4 never straddles rows
     const float* bp = nx.B0 + (size_t)r * (size_t)nx.n + k;                            // (rows of B0 are n long: unaligned)
@@ -70,10 +78,7 @@ __device__ __forceinline__ void proj4_apply(unsigned q, const float* v, const fl
     const float w0e[4] = {w0.x, w0.y, w0.z, w0.w};
     float be[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float t = bp[e] + nx.eta * w0e[e];
-      be[e] = t + nx.rho * (ge[e] - du[e]);
-    }
+    for (int e = 0; e < 4; ++e) be[e] = prox_rhs(bp[e], w0e[e], ge[e], du[e], nx.eta, nx.rho);
     *reinterpret_cast<float4*>(nx.Bm + (size_t)r * (size_t)nx.ldb + k) = make_float4(be[0], be[1], be[2], be[3]);
   }
 }
@@ -92,10 +97,8 @@ __device__ __forceinline__ void proj1_apply(size_t i, unsigned r, unsigned k, fl
   if (dual_div != 1.0f) t = t / dual_div;
   G[i] = g;
   dual[i] = t;
-  if (nx.Bm != nullptr) {
-    float bv = nx.B0[(size_t)r * (size_t)nx.n + k] + nx.eta * nx.W0[i];
-    nx.Bm[(size_t)r * (size_t)nx.ldb + k] = bv + nx.rho * (g - t);
-  }
+  if (nx.Bm != nullptr)
+    nx.Bm[(size_t)r * (size_t)nx.ldb + k] = prox_rhs(nx.B0[(size_t)r * (size_t)nx.n + k], nx.W0[i], g, t, nx.eta, nx.rho);
 }
 
 // The same projection as the EPILOGUE of a single-workgroup fixed point (G == nullptr: none): every thread of the

@@ -37,11 +37,9 @@ __global__ __launch_bounds__(TPB) void k_project_dual(const float* __restrict__ 
     float du = (wstar[i] - g) + dual[i];        // EfficientQConv.py:111
     if (dual_div != 1.0f) du = du / dual_div;   // "dual /= 2" or "dual /= rho_m/rho" (:131-136)
     dual[i] = du;
-    if (nx.Bm != nullptr) {                     // right-hand side of the NEXT prox solve (k_build_b4's arithmetic)
+    if (nx.Bm != nullptr) {                     // right-hand side of the NEXT prox solve
       const size_t r = i / (size_t)nx.nwrow, k = i - r * (size_t)nx.nwrow;
-      float bv = nx.B0[r * (size_t)nx.n + k] + nx.eta * nx.W0[i];
-      bv = bv + nx.rho * (g - du);
-      nx.Bm[r * (size_t)nx.ldb + k] = bv;
+      nx.Bm[r * (size_t)nx.ldb + k] = prox_rhs(nx.B0[r * (size_t)nx.n + k], nx.W0[i], g, du, nx.eta, nx.rho);
     }
   }
 }

@@ -5,7 +5,7 @@ and the small fixed point, on 7 iterations that can never reach the trajectory k
 
   a. the same equality over 34 iterations at period 16 (rho changes after iterations 0, 16 and 32; the trajectory kernel runs at
      13-16 and 29-32 and hands back to the older kernel at 33) on the remaining classes of fp_kind(): traj fed by a whole
-     product, traj fed by K slices (effq_prox_solve_prebuilt_parts + effq_fixed_point_traj_parts), traj warmed by the
+     product, traj fed by K slices (effq_prox_enqueue with parts + effq_fixed_point_traj_parts), traj warmed by the
      cooperative recorder, coop alone, and the channel kernel against its own public op - with an oracle / fp64 anchor on the
      trajectory iterations and on the first iteration after every change of rho, and hist of all 34 slots against conv_step
      (nine hand-overs to the loss stream on its four recycled events);

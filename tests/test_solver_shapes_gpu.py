@@ -1,4 +1,4 @@
-"""Every dispatch class of the prox solver and of the SPD inverse (csrc/solve.hip) against fp64 (-m gpu).
+"""Every dispatch class of the prox solver and of the SPD inverse (csrc/prox_solve.hip, csrc/spd_inverse.hip) against fp64 (-m gpu).
 
 effq_prox_solve* picks one of six GEMM variants plus a K split from (c2, n), effq_spd_inverse the rank-64 or the 256-row
 sweep from n.  Each case here first asserts, through effq_prox_plan_query / effq_spd_inverse_plan, the class it was chosen
@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 GUARD = 64                     # floats on either side of an output (keeps the output 256-byte aligned)
 SENTINEL = -7.25e33
-PROX_KT = {0: 32, 1: 32, 2: 32, 3: 32, 5: 16, 7: 16}     # K tile of each variant (PBK / B3_K of solve.hip)
+PROX_KT = {0: 32, 1: 32, 2: 32, 3: 32, 5: 16, 7: 16}     # K tile of each variant (PBK / B3_K of prox_solve.hip)
 
 
 @pytest.fixture(scope="module")
