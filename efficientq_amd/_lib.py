@@ -227,6 +227,9 @@ SIGNATURES = {
     "effq_prep_standardise_crop": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "effq_prep_crop_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "effq_prep_union_mask": (_I, [_P, _I, _LL, _I, _P, _P]),
+    "effq_prep_quantile_ws_bytes": (_I, [_P]),
+    "effq_prep_quantiles": (_I, [_P, _I, _LL, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "effq_prep_mask_window": (_I, [_P, _SZ, _F, _F, _I, _P]),
     "effq_prep_smooth": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
     "effq_prep_cubic_ws_bytes": (_I, [_I, _I, _I, _I, _P]),
     "effq_prep_cubic_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
@@ -268,6 +271,8 @@ PREP_MAX_MODALITIES = 4
 PREP_WS_BYTES = 1024 * (2 * PREP_MAX_MODALITIES * 8 + 8 * 4)
 PREP_MASKS = {"nonzero": 0, "all": 1}
 PREP_LINEAR, PREP_NEAREST = 0, 1
+# include/effq_hip.h (EFFQ_PREP_QUANTILE_MAX): the most percentiles of one effq_prep_quantiles call
+PREP_QUANTILE_MAX = 4
 # include/effq_hip.h (EFFQ_PREP_SMOOTH_MAX_RADIUS): the largest radius of an axis of effq_prep_smooth
 PREP_SMOOTH_MAX_RADIUS = 32
 # include/effq_hip.h (EFFQ_PREP_SPLINE_PASS_*): the prefilter passes of effq_prep_spline_prefilter

@@ -95,7 +95,8 @@ def build_parser():
                    help='prep, with --split_dir: every K-th of the sorted subjects goes to val.txt, the rest to train.txt')
     p.add_argument('--prep_mask', default=None, choices=['nonzero', 'all'],
                    help='prep: the voxels a modality is standardised over (brats: nonzero, lits: all)')
-    p.add_argument('--prep_window', default=None, help='prep: lo,hi to clip to first, or none (lits: -200,250)')
+    p.add_argument('--prep_window', default=None, help='prep, predict: lo,hi to clip to first (lits: -200,250), pLO,pHI (p0.5,p99.5) to clip every '
+                        'modality inside its mask to its own percentiles over that mask, or none')
     p.add_argument('--prep_orient', default=None,
                    help='prep, predict: three letters, one each of R/L, A/P, S/I (RAS, LPS, SAR, ...): the anatomical '
                         'direction array axis 0, 1, 2 of the working arrays runs towards; every scan is reoriented to it')

@@ -37,8 +37,6 @@ static inline PrepWs prep_ws(void* ws) {
   return r;
 }
 
-__device__ __forceinline__ bool in_mask(float v, int mask_mode) { return mask_mode != 0 || v != 0.0f; }
-
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -423,8 +421,6 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_resample_nearest(Resample
     }
   }
 }
-
-static inline bool prep_fits_flat(long long C, long long S) { return C > 0 && S > 0 && S < (1ll << 31) && C * S < (1ll << 31); }
 
 }  // namespace effq
 using namespace effq;

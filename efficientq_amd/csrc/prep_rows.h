@@ -1,5 +1,5 @@
-// What the row-wise prep kernels share (prep.hip, prep_smooth.hip): the launch shape, the 16-B vector of 4-B alignment,
-// the item of four consecutive w of one row, and the argument checks of the extents and the pointers.
+// What the prep kernels share (prep.hip, prep_smooth.hip, prep_quantile.hip): the launch shape, the 16-B vector of 4-B
+// alignment, the mask, the item of four consecutive w of one row, and the argument checks of the extents and the pointers.
 #pragma once
 #include "common.h"
 
@@ -15,6 +15,9 @@ static inline unsigned prep_grid(size_t groups) {
   size_t nb = (groups + PREP_THREADS - 1) / PREP_THREADS;
   return (unsigned)(nb < 1 ? 1 : (nb > (size_t)PREP_MAX_BLOCKS ? (size_t)PREP_MAX_BLOCKS : nb));
 }
+
+// the mask of a modality: EFFQ_PREP_MASK_NONZERO (0) x != 0, a NaN inside; EFFQ_PREP_MASK_ALL every voxel
+__device__ __forceinline__ bool in_mask(float v, int mask_mode) { return mask_mode != 0 || v != 0.0f; }
 
 // A thread takes four consecutive w of one output row: gw = ceil(OW / 4) threads per row, rows = N * OD * OH.
 struct RowItem {
@@ -34,6 +37,7 @@ __device__ __forceinline__ RowItem row_item(unsigned e, unsigned gw, unsigned OD
 static inline bool prep_fits(long long N, long long D, long long H, long long W) {
   return N > 0 && D > 0 && H > 0 && W > 0 && D <= 32767 && H <= 32767 && W <= 32767 && N * D * H * W < (1ll << 31);
 }
+static inline bool prep_fits_flat(long long C, long long S) { return C > 0 && S > 0 && S < (1ll << 31) && C * S < (1ll << 31); }
 static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace effq

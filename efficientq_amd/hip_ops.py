@@ -1779,6 +1779,50 @@ class HipOps:
         check(self.lib.effq_prep_window(_ptr(x), x.numel(), float(lo), float(hi), self.stream), "effq_prep_window")
         return x
 
+    def prep_quantiles(self, x: torch.Tensor, qs, mask: str = "nonzero"):
+        """The order statistics around the percentiles `qs` (1 to PREP_QUANTILE_MAX values in [0, 100]) of every
+        modality of x = C x S (or C x D x H x W) float32 over its own mask (effq_prep_quantiles; the rule of prep.py's
+        --prep_window pLO,pHI).  Returns (count int64[C], stats float32[C, len(qs), 2]) on the device: stats[c, r] =
+        sorted[k], sorted[min(k + 1, n - 1)] with k = floor((n - 1) qs[r] / 100); NaN where the mask is empty.
+        prep.percentile_value interpolates between the two."""
+        if x.dim() < 2 or x.dtype != torch.float32 or x.numel() == 0 or not x.is_contiguous() or self._elsewhere(x):
+            raise _lib.EffqError(f"prep_quantiles: needs a contiguous C x S float32 tensor on {self.device}, got "
+                                 f"{tuple(x.shape)} {x.dtype} on {x.device}")
+        Cc = int(x.shape[0])
+        if Cc > _lib.PREP_MAX_MODALITIES or x.numel() >= 2 ** 31:
+            raise _lib.EffqError(f"prep_quantiles: shape {tuple(x.shape)}: at most {_lib.PREP_MAX_MODALITIES} modalities and "
+                                 f"2^31 - 1 voxels in all")
+        mode = self._prep_mask("prep_quantiles", mask)
+        try:
+            q = [float(v) for v in qs]
+        except (TypeError, ValueError):
+            q = []
+        if not 1 <= len(q) <= _lib.PREP_QUANTILE_MAX or not all(0.0 <= v <= 100.0 for v in q):
+            raise _lib.EffqError(f"prep_quantiles: percentiles {qs!r}: needs 1 to {_lib.PREP_QUANTILE_MAX} values in "
+                                 f"[0, 100]")
+        count = torch.empty(Cc, dtype=torch.int64, device=self.device)
+        stats = torch.empty((Cc, len(q), 2), dtype=torch.float32, device=self.device)
+        need = C.c_size_t()
+        check(self.lib.effq_prep_quantile_ws_bytes(C.byref(need)), "effq_prep_quantile_ws_bytes")
+        ws = self._workspace("prep_quantile", need.value)
+        # the percentiles are host doubles, read before the call returns
+        check(self.lib.effq_prep_quantiles(_ptr(x), Cc, x.numel() // Cc, mode, (C.c_double * len(q))(*q), len(q),
+                                           _ptr(count), _ptr(stats), _ptr(ws), ws.numel(), self.stream),
+              "effq_prep_quantiles")
+        return count, stats
+
+    def prep_window_mask(self, x: torch.Tensor, lo: float, hi: float, mask: str = "nonzero") -> torch.Tensor:
+        """Clip the voxels of the float32 tensor `x` (one modality's plane) that lie inside the mask to [lo, hi] in place
+        and leave the others alone (effq_prep_mask_window: a NaN stays; with 'all' it is prep_window)."""
+        if x.dtype != torch.float32 or not x.is_contiguous() or self._elsewhere(x) or x.numel() == 0:
+            raise _lib.EffqError(f"prep_window_mask: needs a contiguous float32 tensor on {self.device}")
+        mode = self._prep_mask("prep_window_mask", mask)
+        if not float(lo) <= float(hi):
+            raise _lib.EffqError(f"prep_window_mask: bounds {lo}, {hi}")
+        check(self.lib.effq_prep_mask_window(_ptr(x), x.numel(), float(lo), float(hi), mode, self.stream),
+              "effq_prep_mask_window")
+        return x
+
     def prep_resample(self, x: torch.Tensor, factors, out_shape, nearest: bool = False) -> torch.Tensor:
         """N x D x H x W volumes on a grid of another spacing (effq_prep_resample): `factors` = target spacing / source
         spacing per axis, `out_shape` the output extents (prep.resample_extent).  float32 volumes are interpolated

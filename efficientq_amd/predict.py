@@ -36,6 +36,11 @@ the ``antialias`` column's place and before those of ``--blend``; the step back 
 the logits.  ``linear``, the default, changes nothing; another value, or cubic without ``--prep_spacing``, is refused by
 name.
 
+``--prep_window pLO,pHI`` (``p0.5,p99.5``) clips every modality of every scan to a pair of its own percentiles over its
+own mask as ``prep`` does (pass what the calibration data was prepared with).  The column ``prep_window`` then reads
+``p0.5 p99.5`` and ``predict.csv`` gains the column ``window_bounds`` (``lo hi`` per modality, joined by ``;``) after the
+``interp`` column's place and before those of ``--blend``.
+
 ``--blend gauss`` weighs every window's logits by a Gaussian around the window's centre when the windows are stitched;
 ``--tta_mirror AXES`` (letters of ``d``, ``h``, ``w``) also runs every window mirrored along each subset of the axes and
 averages the logits: 2, 4 or 8 forwards per window.  When either is given ``predict.csv`` gains the columns ``blend`` and
@@ -128,6 +133,7 @@ def _network(args, dev):
     return model
 
 
+CSV_WINDOW_COLUMNS = ["window_bounds"]            # after the interp column's place, only with --prep_window pLO,pHI
 CSV_BLEND_COLUMNS = ["blend", "tta_mirror"]       # after CSV_HEADER, only when --blend / --tta_mirror is given
 CSV_THRESH_COLUMNS = ["thresh"]                   # after those, only when --thresh is given (and is not the default)
 CSV_POST_COLUMNS = ["post", "post_changed"]       # after those, only when --post is given
@@ -216,7 +222,8 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
 
     out_dir = args.out_dir
     os.makedirs(out_dir, exist_ok=True)
-    used = {"prep_mask": mask, "prep_window": prep._fmt(window) if window else "none",
+    pct = isinstance(window, prep.PercentileWindow)
+    used = {"prep_mask": mask, "prep_window": str(window) if pct else prep._fmt(window) if window else "none",
             "prep_spacing": prep._fmt(spacing) if spacing else "none", "prep_min_size": prep._fmt(min_size),
             "patch_size": prep._fmt(patch)}
     if orient:
@@ -312,11 +319,13 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                 row["antialias"] = prep._fmt(plan.sigmas)
             if interp == "cubic":
                 row["interp"] = interp
+            if pct:
+                row["window_bounds"] = ";".join(prep._fmt(b) for b in plan.window_bounds)
             if post:
                 row["post_changed"] = changed
             rows.append(row)
             turned = f" ({plan.orient_code} -> {orient})" if orient and plan.orient_code != orient else ""
-            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned}{prep.antialias_said(plan)}{prep.interp_said(plan)} -> grid "
+            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned}{prep.window_said(plan, mods)}{prep.antialias_said(plan)}{prep.interp_said(plan)} -> grid "
                   f"{prep._fmt(plan.grid_shape)}, box at {prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
                   f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
                   f"{row['voxels']} voxels{cleaned}{extra}")
@@ -329,7 +338,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         w.result()                              # re-raises a failed write
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
                CSV_HEADER + (prep.ORIENT_COLUMNS if orient else []) + (prep.ANTIALIAS_COLUMNS if antialias else []) +
-               (prep.INTERP_COLUMNS if interp == "cubic" else []) +
+               (prep.INTERP_COLUMNS if interp == "cubic" else []) + (CSV_WINDOW_COLUMNS if pct else []) +
                (CSV_BLEND_COLUMNS if sliding else []) +
                (CSV_THRESH_COLUMNS if thresh is not None else []) + (CSV_POST_COLUMNS if post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")

@@ -1,7 +1,7 @@
 """The ``prep`` mission: source NIfTI scans to the data layout the ``ptq`` mission reads (data.py).
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
-        [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|none] \
+        [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|pLO,pHI|none] \
         [--prep_orient RAS] [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
         [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
@@ -12,14 +12,17 @@ cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
     reorient   --prep_orient CODE: the axes permuted and reversed (csrc/reorient.hip) so that array axis 0, 1, 2 runs
                towards the three letters of CODE (one each of R/L, A/P, S/I: RAS, LPS, SAR, ...), whatever orientation
                the scan's affine gives it; --prep_spacing and --prep_min_size then refer to the oriented axes
-    window     --prep_window lo,hi: clip in place (lits: -200,250 unless ``none``; brats: none)
+    window     --prep_window lo,hi: clip in place (lits: -200,250 unless ``none``; brats: none).  --prep_window pLO,pHI
+               (p0.5,p99.5): every modality of every subject is clipped to a pair of its own percentiles over its own
+               mask instead, and only inside that mask (the rule below at PercentileWindow; csrc/prep_quantile.hip)
     filter     --prep_antialias (with --prep_spacing): a separable Gaussian over the images on the source grid before
                they are down-sampled, per axis of factor f = target / source spacing > 1 with sigma = (f - 1) / 2 and
                the radius int(4 sigma + 0.5) (antialias_taps; csrc/prep_smooth.hip); the label is not touched
     resample   --prep_spacing d,h,w: trilinear for the images, nearest for the label; no filter before down-sampling
                unless --prep_antialias asks for one.  --prep_interp cubic: the images by cubic B-spline interpolation
                instead (the rule below at CUBIC_POLE; csrc/prep_spline.hip), on the same grid; the window is applied
-               once more after it, since a cubic spline overshoots; the label stays nearest
+               once more after it, since a cubic spline overshoots (a percentile window with the bounds found on the
+               source grid); the label stays nearest
     pass 1     the box of the union of the modalities' masks, per modality the count and the sum over its own mask
                (--prep_mask nonzero: x != 0, the brats default; all: every voxel, the lits default)
     pass 2     per modality the squared deviations from the mean of pass 1; std = sqrt(sqdev / count)
@@ -35,14 +38,16 @@ also one that was oriented as asked already), and prep.csv gains the columns ``s
 With ``--prep_antialias`` prep.csv gains the column ``antialias`` after all others: the sigmas of the three array axes
 in voxels of the source grid, ``0 0 0`` for a subject no axis of which is down-sampled far enough to be filtered.
 With ``--prep_interp cubic`` prep.csv gains the column ``interp`` (``cubic``) after all others, the anti-alias column
-included.  A NaN or an Inf in a scan is carried along whole lines by the spline's recursions; the check of the standard
-deviation then stops the run at that subject.
+included.  With ``--prep_window pLO,pHI`` prep.csv gains ``<modality>_win_lo`` and ``<modality>_win_hi`` per modality
+(``repr(float)``) after all others, ``interp`` included.  A NaN or an Inf in a scan is carried along whole lines by the
+spline's recursions; the check of the standard deviation then stops the run at that subject.
 ``--split_dir --val_every K`` also writes ``split_dir/round<R>/{train,val}.txt``.
 
 What the headers decide (the list itself, shapes and affines within a subject, a grid smaller than --prep_min_size, a
 split that already exists) is checked for every subject before anything is written.  What only the voxels decide (an
-empty mask, a constant modality) stops the run at that subject: none of its files and none of the files written at the
-end exist then.  The next subject's files are read and gunzipped by one background thread while the device works.
+empty mask, a constant modality, a percentile bound that is not finite or, with the mask ``nonzero``, exactly 0) stops
+the run at that subject: none of its files and none of the files written at the end exist then.  The next subject's
+files are read and gunzipped by one background thread while the device works.
 There is no CPU path: `ops` is hip_ops.get_ops(device) unless a caller passes its own.
 """
 from __future__ import annotations
@@ -119,15 +124,88 @@ def _triple(s, what: str, cast=float) -> tuple:
     return v
 
 
-def parse_window(s, task: str) -> Optional[Tuple[float, float]]:
+# ---- the percentile window (host, no device) ------------------------------------------------------------------------------
+# The one definition of the rule of --prep_window pLO,pHI; include/effq_hip.h (effq_prep_quantiles) restates it.
+# 1 The step runs where the absolute window runs: after the reorientation, before the filter and the resampling.
+# 2 For modality c take the n voxels of its own mask (--prep_mask nonzero: x != 0, a NaN is inside; all: every voxel)
+#   and sort them ascending: -Inf first, -0.0 counted as +0.0, every NaN after +Inf.
+# 3 The value of percentile q, in fp64 with the product first: h = (n - 1) * q / 100, k = floor(h), a = sorted[k],
+#   b = sorted[min(k + 1, n - 1)]; v = a when a == b, else a + (h - k) * (b - a); the bound is the float32 nearest v
+#   (percentile_value).  That is numpy's default `linear` method, up to the rounding of h.
+# 4 The voxels inside the mask are clipped to [lo_c, hi_c]; those outside it are left alone: with `nonzero` an exact zero
+#   stays an exact zero, so the background and the crop box stay what they were.  A NaN stays a NaN.
+# 5 The run stops at the subject (PrepError naming the subject, the modality and the bound; none of its files are
+#   written) when a modality has fewer than two voxels inside its mask, when a bound is not finite, and, with `nonzero`,
+#   when a bound comes to exactly 0: it would move voxels out of the mask.
+# 6 With --prep_interp cubic the window applied once more after the resampling is this masked window with the same
+#   bounds, found once, on the source grid.
+class PercentileWindow:
+    """--prep_window pLO,pHI: the percentiles 0 <= lo_q < hi_q <= 100 every modality is clipped to, over its own mask."""
+    __slots__ = ("lo_q", "hi_q")
+
+    def __init__(self, lo_q: float, hi_q: float):
+        self.lo_q, self.hi_q = float(lo_q), float(hi_q)
+
+    def __eq__(self, other):
+        return isinstance(other, PercentileWindow) and (self.lo_q, self.hi_q) == (other.lo_q, other.hi_q)
+
+    def __hash__(self):
+        return hash((self.lo_q, self.hi_q))
+
+    def __repr__(self):
+        return f"PercentileWindow({self.lo_q!r}, {self.hi_q!r})"
+
+    def __str__(self):      # as predict.csv spells it: p0.5 p99.5
+        return f"p{self.lo_q:.7g} p{self.hi_q:.7g}"
+
+
+WINDOW_FORMS = "lo,hi, pLO,pHI (percentiles, 0 <= LO < HI <= 100) or none"
+
+
+def window_columns(mods: Sequence[str]) -> List[str]:
+    """prep.csv, only with --prep_window pLO,pHI: the bounds of every modality, after all other columns."""
+    return [f"{m}_win_{k}" for m in mods for k in ("lo", "hi")]
+
+
+def percentile_value(n: int, q: float, a, b) -> float:
+    """The host half of the rule: the float32 bound from the order statistics a = sorted[k] and b = sorted[min(k + 1,
+    n - 1)], k = floor((n - 1) * q / 100), that the device found (hip_ops.prep_quantiles)."""
+    h = float(int(n) - 1) * float(q) / 100.0
+    k = math.floor(h)
+    a, b = float(a), float(b)
+    v = a if a == b else a + (h - k) * (b - a)
+    return float(np.float32(v))
+
+
+def parse_window(s, task: str):
+    """None, the pair (lo, hi) of an absolute window, or a PercentileWindow."""
     if s is None:
         return WINDOW_DEFAULT[task]
     if isinstance(s, str) and s.strip().lower() in ("none", ""):
         return None
+    parts = s.split(",") if isinstance(s, str) else s
     try:
-        lo, hi = (float(x) for x in (s.split(",") if isinstance(s, str) else s))
+        pct = [isinstance(x, str) and x.strip().lower().startswith("p") for x in parts]
+    except TypeError:
+        pct = []
+    if any(pct):
+        if len(pct) != 2:
+            raise PrepError(f"--prep_window {s!r}: needs {WINDOW_FORMS}")
+        if not all(pct):
+            raise PrepError(f"--prep_window {s!r}: one bound is a percentile and the other is not: needs {WINDOW_FORMS}")
+        try:
+            lo, hi = (float(x.strip()[1:]) for x in parts)
+        except ValueError:
+            raise PrepError(f"--prep_window {s!r}: needs {WINDOW_FORMS}")
+        if not all(math.isfinite(v) and 0.0 <= v <= 100.0 for v in (lo, hi)):
+            raise PrepError(f"--prep_window {s!r}: a percentile lies within 0 and 100: needs {WINDOW_FORMS}")
+        if not lo < hi:
+            raise PrepError(f"--prep_window {s!r}: pLO must lie below pHI: needs {WINDOW_FORMS}")
+        return PercentileWindow(lo, hi)
+    try:
+        lo, hi = (float(x) for x in parts)
     except (TypeError, ValueError):
-        raise PrepError(f"--prep_window {s!r}: needs lo,hi or none")
+        raise PrepError(f"--prep_window {s!r}: needs {WINDOW_FORMS}")
     if not lo <= hi:
         raise PrepError(f"--prep_window {s!r}: lo must not exceed hi")
     return lo, hi
@@ -182,7 +260,8 @@ def antialias_taps(sigma: float) -> np.ndarray:
 #   is exactly 0 (per axis i0 and i0 + 1, the second only when s > i0 and i0 < n - 1; a NaN is not 0): the prefilter has
 #   infinite support, and the calibration takes exact 0 as background.  The body cannot grow past what the trilinear
 #   step reaches.  --prep_mask all: nothing is kept.
-# 4 With a --prep_window in force the window is applied once more after the resampling: values lie in [lo, hi].
+# 4 With a --prep_window in force the window is applied once more after the resampling: values lie in [lo, hi] (a
+#   percentile window: inside the mask, with the bounds found on the source grid).
 # 5 A NaN or an Inf is carried along whole lines; the check of the standard deviation stops the run at that subject.
 CUBIC_POLE = math.sqrt(3.0) - 2.0
 CUBIC_GAIN = 6.0
@@ -375,6 +454,13 @@ def interp_switch(args, spacing) -> str:
     return order
 
 
+def window_said(plan, mods: Sequence[str]) -> str:
+    """What the per-subject line says of a percentile window: every modality's bounds; nothing otherwise."""
+    if plan.window_bounds is None:
+        return ""
+    return ", window " + ", ".join(f"{m} {lo:.7g} {hi:.7g}" for m, (lo, hi) in zip(mods, plan.window_bounds))
+
+
 def interp_said(plan) -> str:
     """What the per-subject line says of the interpolation: nothing for linear."""
     return ", cubic" if plan.interp == "cubic" else ""
@@ -392,6 +478,7 @@ class _Plan:
                  antialias: bool = False, interp: str = "linear"):
         sn = self.subject = entry["subject"]
         self.interp = interp if spacing is not None else "linear"      # how the images are resampled (--prep_interp)
+        self.window_bounds = None       # --prep_window pLO,pHI: (lo, hi) per modality, set by process_subject
         self.entry = entry
         heads = {}
         for name, path in list(entry["images"].items()) + ([(D.LABEL_MODALITY, entry["seg"])] if entry["seg"] else []):
@@ -552,6 +639,38 @@ def _fmt(v) -> str:
 
 
 # ---- one subject on the device -------------------------------------------------------------------------------------------
+def percentile_bounds(ops, sn: str, x, mods: Sequence[str], mask: str, window: PercentileWindow):
+    """(lo, hi) per modality of C x D x H x W `x` by the rule at PercentileWindow, or the PrepError of its step 5."""
+    qs = (window.lo_q, window.hi_q)
+    count, stats = ops.prep_quantiles(x.reshape(x.shape[0], -1), qs, mask)
+    count, stats = count.cpu().tolist(), stats.cpu().numpy()
+    bounds = []
+    for c, m in enumerate(mods):
+        n = int(count[c])
+        if n < 2:
+            raise PrepError(f"subject {sn}: modality {m}: {n} voxels inside the mask, the percentiles p{qs[0]:.7g} and "
+                            f"p{qs[1]:.7g} of --prep_window need two")
+        pair = tuple(percentile_value(n, q, stats[c, r, 0], stats[c, r, 1]) for r, q in enumerate(qs))
+        for q, v in zip(qs, pair):
+            if not math.isfinite(v):
+                raise PrepError(f"subject {sn}: modality {m}: the bound p{q:.7g} of --prep_window is {v}: a window "
+                                f"needs finite bounds")
+            if mask == "nonzero" and v == 0.0:
+                raise PrepError(f"subject {sn}: modality {m}: the bound p{q:.7g} of --prep_window is exactly 0: with "
+                                f"--prep_mask nonzero it would move voxels out of the mask")
+        bounds.append(pair)
+    return bounds
+
+
+def _apply_window(ops, plan, x, window, mask: str) -> None:
+    """The window in place: the absolute one over every voxel, the percentile one per modality inside its mask."""
+    if plan.window_bounds is not None:
+        for c, (lo, hi) in enumerate(plan.window_bounds):
+            ops.prep_window_mask(x[c], lo, hi, mask)
+    elif window is not None:
+        ops.prep_window(x, window[0], window[1])
+
+
 def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str],
                     mask: str, window, min_size, no_crop: bool):
     """The device pipeline of one subject.  Returns (arrays C x d x h x w float32, label or None, union mask of the grid
@@ -570,15 +689,15 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
         x = ops.prep_reorient(x, *plan.orient)
         if lab is not None:
             lab = ops.prep_reorient(lab, *plan.orient)
-    if window is not None:
-        ops.prep_window(x, window[0], window[1])
+    plan.window_bounds = percentile_bounds(ops, sn, x, mods, mask, window) if isinstance(window, PercentileWindow) \
+        else None
+    _apply_window(ops, plan, x, window, mask)
     if plan.factors is not None:
         if any(r > 0 for r in plan.radii):       # --prep_antialias; the label is not filtered
             x = ops.prep_smooth(x, plan.sigmas, mask == "nonzero")
         if plan.interp == "cubic":       # --prep_interp cubic; the spline overshoots, so the window once more
             x = ops.prep_resample_cubic(x, plan.factors, plan.grid_shape, mask == "nonzero")
-            if window is not None:
-                ops.prep_window(x, window[0], window[1])
+            _apply_window(ops, plan, x, window, mask)
         else:
             x = ops.prep_resample(x, plan.factors, plan.grid_shape)
         if lab is not None:
@@ -692,13 +811,17 @@ def run(args, ops=None) -> List[dict]:
                 row.update(antialias=_fmt(plan.sigmas))
             if interp == "cubic":
                 row.update(interp=interp)
+            if plan.window_bounds is not None:
+                for m, (lo, hi) in zip(mods, plan.window_bounds):
+                    row.update({f"{m}_win_lo": repr(float(lo)), f"{m}_win_hi": repr(float(hi))})
             rows.append(row)
-            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned}{antialias_said(plan)}{interp_said(plan)} -> {_fmt(y.shape[1:])} at "
+            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned}{window_said(plan, mods)}{antialias_said(plan)}{interp_said(plan)} -> {_fmt(y.shape[1:])} at "
                   f"{_fmt(pmin)}")
     finally:
         pool.shutdown(wait=True, cancel_futures=True)
     write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods) + (ORIENT_COLUMNS if orient else []) +
-                      (ANTIALIAS_COLUMNS if antialias else []) + (INTERP_COLUMNS if interp == "cubic" else []))
+                      (ANTIALIAS_COLUMNS if antialias else []) + (INTERP_COLUMNS if interp == "cubic" else []) +
+                      (window_columns(mods) if isinstance(window, PercentileWindow) else []))
     if split is not None:
         names = [p.subject for p in plans]
         val = names[k - 1::k]

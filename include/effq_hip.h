@@ -986,6 +986,38 @@ int effq_prep_crop_u8(const uint8_t* x, int C, int D, int H, int W, const int* p
                       void* stream);
 int effq_prep_union_mask(const float* x, int C, long long S, int mask_mode, uint8_t* mask, void* stream);
 
+/* ---- the percentile window (csrc/prep_quantile.hip; prep.py --prep_window pLO,pHI, where the rule is defined): every
+ * modality is clipped to a pair of its own percentiles over its own mask.  The rule, restated: the n voxels of modality
+ * c's mask (mask_mode as above) are sorted ascending, -Inf first, -0.0 counted as +0.0, every NaN after +Inf.  For a
+ * percentile q in [0, 100], all in fp64 with the product first: h = (n - 1) q / 100, k = floor(h), a = sorted[k],
+ * b = sorted[min(k + 1, n - 1)], v = a when a == b, else a + (h - k) (b - a); the bound is the fp32 value nearest v
+ * (numpy's default `linear` method, up to the rounding of h).  The voxels inside the mask are then clipped to [lo, hi],
+ * those outside it are left alone; the host stops at n < 2, at a bound that is not finite and, with MASK_NONZERO, at a
+ * bound of exactly 0 (it would move voxels out of the mask).
+ *
+ * effq_prep_quantiles: the device half.  x (C, S) fp32 under the limits above (C <= EFFQ_PREP_MAX_MODALITIES, C S < 2^31,
+ *   4-B aligned); q: R HOST doubles in [0, 100], 1 <= R <= EFFQ_PREP_QUANTILE_MAX, read before the call returns.
+ *   count_out[c] int64 = n; stat_out[c][r][0..1] fp32 = a and b for q[r], with k formed on the device in fp64 from the
+ *   count it found; both are NaN when n = 0, a zero of either sign is returned as +0.0, a NaN as a quiet NaN.  The host
+ *   interpolates (prep.percentile_value).  Method: a radix select over the order-preserving 32-bit key of the float, most
+ *   significant digit first, 8 bits in four passes.  Each pass streams x and counts the next digit of the voxels under
+ *   the prefixes still followed (up to 2 R, targets with equal prefixes share one) in 32-bit LDS counters per workgroup,
+ *   equal digits of a wave combined by ballot first; the workgroups' totals are combined in `ws` by integer atomics, and
+ *   a one-workgroup step picks each target's digit and remaining rank.  Nine launches on `stream`; nothing is read by
+ *   the host, no workgroup waits for another, no floating-point atomic: equal inputs give equal bits.  `ws`:
+ *   *bytes of effq_prep_quantile_ws_bytes (as effq_prep_cubic_ws_bytes reports its own), 8-B aligned, any contents (the
+ *   call clears what it counts in).
+ * effq_prep_mask_window: x[i] = in_mask(x[i]) ? clip(x[i]) : x[i] in place over n floats, clip that of effq_prep_window
+ *   (a NaN stays), lo <= hi.
+ * Refused with EFFQ_ERR_ARG before any launch: a null pointer, C or S out of range, a mask_mode that is neither, R outside
+ * 1 ... EFFQ_PREP_QUANTILE_MAX, a q outside [0, 100] or NaN, a workspace that is too short or not aligned to 8 B, x or
+ * stat_out not aligned to 4 B, count_out not aligned to 8 B, lo > hi or a NaN bound. */
+#define EFFQ_PREP_QUANTILE_MAX 4
+int effq_prep_quantile_ws_bytes(size_t* bytes);
+int effq_prep_quantiles(const float* x, int C, long long S, int mask_mode, const double* q, int R, long long* count_out,
+                        float* stat_out, void* ws, size_t ws_bytes, void* stream);
+int effq_prep_mask_window(float* x, size_t n, float lo, float hi, int mask_mode, void* stream);
+
 /* ---- the anti-alias filter before down-sampling (csrc/prep_smooth.hip; prep.py --prep_antialias): a separable Gaussian
  * on the source grid, x (N, D, H, W) fp32 -> y of the same shape.  Per array axis a with the factor f_a = target spacing /
  * source spacing of the resampling that follows (the caller's rule, prep.antialias_taps):

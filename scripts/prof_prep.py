@@ -10,6 +10,9 @@ events, one JSON line per subject.
   B-spline path of --prep_interp cubic is timed: `resample_cubic` is the whole call (three prefilter passes and the
   evaluation), `spline_d`, `spline_h`, `spline_w` one prefilter pass each (d reads the float32 volume and writes the fp64
   coefficients, h and w filter them in place: read once and written once, 16 B per voxel), `cubic_eval` the rest.
+`quantiles` is effq_prep_quantiles of --prep_window pLO,pHI on the source grid (p0.5, p99.5: R = 2; four passes over the
+  subject, its bytes count the subject four times; the eight one-workgroup launches between and after them are in its
+  time), `window_mask` the masked window of one modality; neither enters device_ms_total.
 Each step runs once unmeasured, then REPS times (median), warm and after 512 MiB of other writes have pushed the subject
 out of the Infinity Cache.  gbps = the bytes the step must move (what it reads once plus what it writes) over the time;
 hbm_frac = that over the 8 TB/s peak.  numpy_ms is the same arithmetic on the host in numpy, one run, as context."""
@@ -74,6 +77,11 @@ def step(name, fn, nbytes):
                  "hbm_frac_after_evict": round(nbytes / (cold * 1e-3) / HBM_PEAK, 3)}
 
 
+step("quantiles", lambda: ops.prep_quantiles(x.reshape(C, -1), (0.5, 99.5), mask), 4 * 4 * C * S)
+res["quantiles"]["passes"] = 4
+plane = x[0].clone()
+step("window_mask", lambda: ops.prep_window_mask(plane, -1e30, 1e30, mask), 2 * 4 * S)
+del plane
 if window is not None:
     step("window", lambda: ops.prep_window(x, *window), 2 * 4 * C * S)
 if factors is not None:
@@ -113,7 +121,7 @@ step("standardise_crop", lambda: ops.prep_standardise_crop(x, pmin, pmax, mean, 
 res["crop"] = [list(pmin), list(pmax)]
 res["device_ms_total"] = round(sum(v["ms"] for k, v in res.items()
                                    if isinstance(v, dict) and not k.startswith(("smooth_", "spline_", "cubic_")) and
-                                   k != "resample_cubic"), 3)      # the trilinear pipeline; `smooth` holds its passes
+                                   k not in ("resample_cubic", "quantiles", "window_mask")), 3)      # the trilinear pipeline; `smooth` holds its passes
 
 if not cli.no_numpy:
     h = x.cpu().numpy()
