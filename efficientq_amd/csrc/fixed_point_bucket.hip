@@ -42,7 +42,8 @@ struct FpbGeo {
   int B;
 };
 
-__device__ __forceinline__ FpbGeo fpb_geo(float R, int B) {
+// extra: bits by which the unit is finer than bucket width * 2^-FPB_SHIFT (k_fps on a range an outlier stretched)
+__device__ __forceinline__ FpbGeo fpb_geo(float R, int B, int extra = 0) {
   if (!(R >= 1e-30f)) R = 1e-30f;
   if (!(R <= 3.0e38f)) R = 3.0e38f;
   FpbGeo g;
@@ -51,7 +52,7 @@ __device__ __forceinline__ FpbGeo fpb_geo(float R, int B) {
   g.scale = (float)B / (2.0f * R);
   g.R64 = (double)R;
   g.w = 2.0 * g.R64 / (double)B;
-  g.q = ldexp(g.w, -FPB_SHIFT);
+  g.q = ldexp(g.w, -(FPB_SHIFT + extra));
   g.rq = 1.0 / g.q;
   return g;
 }
@@ -74,7 +75,8 @@ __device__ __forceinline__ float fpb_step(float v, int dir) {
 }
 // integer contribution of v relative to the lower edge of bucket (b - 1): positive for every v of buckets >= b
 // (values beyond the range are clamped INTO the end buckets and may lie far outside them: the conversion saturates
-// nowhere near that: |v - origin| / q < 2^63 needs |v| < 2^27 * range; beyond it the kernel reports non-convergence)
+// nowhere near that: |v - origin| / q < 2^63 needs |v| < 2^27 * range - 2^20 with k_fps' finest unit; beyond it the kernel
+// reports non-convergence)
 __device__ __forceinline__ long long fpb_units(float v, int b, const FpbGeo& g) {
   return __double2ll_rn(((double)v - ((double)(b - 1) * g.w - g.R64)) * g.rq);
 }
@@ -196,8 +198,10 @@ __device__ __forceinline__ void fpb_iterate(const float* __restrict__ vals, cons
           }
         }
       }
-      // integer sums across the group: exact in any order.  Per lane qs < 2^42 (values < 2^39 each): two 21-bit limbs
-      // keep every partial sum of a 64-lane group below 2^32; a third limb only where a lane exceeds 2^42
+      // integer sums across the group: exact in any order.  With the plain unit a lane's qs stays below 2^42 (values
+      // < 2^39 each): two 21-bit limbs keep every partial sum of a 64-lane group below 2^32.  A third limb is summed only
+      // where a lane exceeds 2^42: segments longer than the register cache, and k_fps' finer unit on outlier tensors
+      // (values up to 2^46 each); it stays below 2^21 per lane there too - a segment sum is below 2^60 (k_fps)
       if (gs > 1) {
         const unsigned long long uq = (unsigned long long)qs;
         unsigned l0 = (unsigned)(uq & 0x1fffffu), l1 = (unsigned)((uq >> 21) & 0x1fffffu), l2 = (unsigned)(uq >> 42);
@@ -337,7 +341,17 @@ __global__ __launch_bounds__(FPS2_T) void k_fps(const float* __restrict__ a, con
     tot += s_red[w];
     R = fmaxf(R, s_max[w]);
   }
-  const FpbGeo g = fpb_geo(R, B);
+  // The unit of the integer sums is a fraction of the bucket WIDTH, and one outlier widens every bucket: at max|v| =
+  // 5000 mean|v| the values were rounded to 7e-11 of themselves and alpha ended 2e-13 from fp64 (ordinary tensors: 1e-15).
+  // From max|v| >= 64 mean|v| on the unit gets those bits back, ilogb(max / mean) - 5 of them and 7 at the most: with
+  // n <= 2^15 a bucket sum stays below 2^(15 + 44), a boundary segment of three buckets below 2^(15 + 45).  Below that
+  // ratio - every tensor of a calibration - nothing changes.  (tot and R are the same bits in every thread.)
+  int extra = 0;
+  {
+    const double ratio = (double)R * (double)n / tot;
+    if (ratio >= 64.0 && ratio < 1e30) extra = min(ilogb(ratio) - 5, 7);
+  }
+  const FpbGeo g = fpb_geo(R, B, extra);
   FPB_TRACE(1);
   // ---- pass 1: bucket counts (the returned count is the value's rank inside its bucket) ---------------------------
   unsigned rank2[KEEP_RANK ? (PER + 1) / 2 : 1];   // two 16-bit ranks per register (n <= 32768 < 2^16)

@@ -131,8 +131,12 @@ __device__ __forceinline__ void fpt_phase1(FptSmem& sm, const float (&vv)[EPT], 
   if (warm && tid < 4 * K) {
     const int c = tid & 3;
     const double ew = p_eps, en = fmin(p_epsn, ew);
-    const double end = (c == 0) ? p_lo * (1.0 - ew) : (c == 1) ? p_lo * (1.0 - en)
-                     : (c == 2) ? p_hi * (1.0 + en) : p_hi * (1.0 + ew);
+    const double e0 = p_lo * (1.0 - ew), e1 = p_lo * (1.0 - en), e2 = p_hi * (1.0 + en), e3 = p_hi * (1.0 + ew);
+    // "equal levels at both ends, hence at every scale between" needs positive, ordered ends (the level is monotone in the
+    // scale on a > 0 only), and phase 2 takes narrow inside wide for granted: a slot whose fields do not give that (a
+    // prediction buffer that holds anything but a previous call's record) gets NaN ends - no iterate is ever inside it
+    const bool sane = e0 > 0.0 && e0 <= e1 && e1 <= e2 && e2 <= e3 && e3 < 1e300;
+    const double end = !sane ? __builtin_nan("") : (c == 0) ? e0 : (c == 1) ? e1 : (c == 2) ? e2 : e3;
     sm.end[tid] = end;
     sm.c1[tid] = (float)((1.0 / end) * rd);
   }
@@ -389,7 +393,10 @@ __device__ __forceinline__ void fpt_phase2(FptSmem& sm, const FptCtx& cx, const 
     const double bound = (double)(levels - 1) * tot_abs;
     if (bound > 0.0 && bound < 1e300) e_full = 58 - ilogb(bound);
   }
-  const bool tallies_ok = warm && ((double)(levels - 1) * tot_abs * inv_q < 2.0e18);
+  // ... and be fine enough: the recorder's unit of a tensor within 4 x of this one (a coarser one - the tensor shrank, or
+  // the exponent is not a record at all - would round the tallies; every bracket of such a tensor misses anyway)
+  const bool tallies_ok = warm && ((double)(levels - 1) * tot_abs * inv_q < 2.0e18) && e_units >= e_full - 2 &&
+                          e_units <= e_full + 2;
   const double q_tally = ldexp(1.0, -e_units), inv_qf = ldexp(1.0, e_full), q_full = ldexp(1.0, -e_full);
 
   const long long tr2 = wall_clock64();

@@ -447,7 +447,8 @@ class HipOps:
         fn = pred[16 + 8 * 45:16 + 8 * 53].view(torch.float64).cpu()
         j64 = pred[16 + 8 * 53:16 + 8 * 63].view(torch.int64).cpu()
         K = int(i32[0])
-        return {"K": K, "e": int(i32[1]), "lo": f[0:8].tolist(), "hi": f[8:16].tolist(), "eps": f[16:24].tolist(),
+        return {"K": K, "e": int(i32[1]), "e_valid": int(i32[2]), "lo": f[0:8].tolist(), "hi": f[8:16].tolist(),
+                "eps": f[16:24].tolist(),
                 "eps_n": fn.tolist(), "calls": int(i64[0]), "warm_iters": int(i64[1]), "full_iters": int(i64[2]),
                 "listed": int(i64[3]), "list_max": int(i64[4]), "ring_iters": int(j64[0]), "ring_listed": int(j64[1]),
                 "trace_us": [(int(j64[2 + k]) - int(j64[2])) / 100.0 for k in range(5)],
