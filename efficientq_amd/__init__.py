@@ -1,7 +1,9 @@
 """efficientq_amd -- MI355X-native layer-wise PTQ calibration (the hot path of rongzhao-zhang/EfficientQ).
 
     csrc/            hand-written HIP kernels + the C ABI (include/effq_hip.h) -> libeffq_hip.so
-    _lib, hip_ops    ctypes binding and tensor-level front end (no CPU fallback)
+    _lib, hip_ops    ctypes binding and tensor-level front end (no CPU fallback): HipOps holds the calibration wrappers
+    ops_base, ops_window, ops_seg, ops_prep
+                     the handle and the sliding-window, validation and prep wrappers HipOps is composed from
     qconv            PTQConv / EfficientQConvHIP (reference class contract)
     unet             UResQ host graph (reference module tree / state_dict keys)
     calibrate        do_ptq orchestrator, BN folding, attention-mask pyramid

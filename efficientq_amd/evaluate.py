@@ -17,7 +17,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from .hip_ops import BLEND_KINDS         # --blend: the window weights of the stitch (hip_ops.blend_weights_host)
+from .ops_window import BLEND_KINDS      # --blend: the window weights of the stitch (ops_window.blend_weights_host)
 
 
 def _triple(v):

@@ -2,17 +2,25 @@
 the HIP stream; every computation is a call into ``libeffq_hip.so``.
 
 No CPU fallback exists here on purpose: tensors must live on a HIP device.
+
+``HipOps`` holds the calibration wrappers; the sliding window, the validation and the prep mission come from the
+mixins of ``ops_window``, ``ops_seg`` and ``ops_prep`` over the handle of ``ops_base``.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Tuple
+from types import SimpleNamespace
+from typing import Optional
 
 import torch
 
 from . import _lib
 from ._lib import Geom, check
+from .ops_base import _ptr, _triple
+from .ops_prep import PrepOps
+from .ops_seg import SegOps
+from .ops_window import BLEND_KINDS, WindowOps, blend_weights_host  # noqa: F401  (re-exported)
 
 ADMM_TOL = 1e-5   # layer_helper.py:55
 # tensors from this size on are fitted by the bracketed fixed point (effq_fp_bracket_*)
@@ -24,10 +32,6 @@ DP_GATHER_AFTER = 4
 DP_GATHER_MAX_BYTES = 128 << 20
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def to_ndhwc(x: torch.Tensor) -> torch.Tensor:
     """(N,C,D,H,W) logical -> contiguous (N,D,H,W,C) storage (no copy if already channels_last_3d)."""
     return x.permute(0, 2, 3, 4, 1).contiguous()
@@ -36,40 +40,6 @@ def to_ndhwc(x: torch.Tensor) -> torch.Tensor:
 def from_ndhwc(t: torch.Tensor) -> torch.Tensor:
     """contiguous (N,D,H,W,C) -> logical (N,C,D,H,W) view (channels_last_3d strides)."""
     return t.permute(0, 4, 1, 2, 3)
-
-
-def _triple(v):
-    return (v, v, v) if isinstance(v, int) else tuple(int(i) for i in v)
-
-
-def _flip_mask(flip, who: str) -> int:
-    if isinstance(flip, bool) or int(flip) != flip or not 0 <= flip <= 7:
-        raise _lib.EffqError(f"{who}: flip mask {flip!r}, an int 0..7 (bit 0 = d, bit 1 = h, bit 2 = w)")
-    return int(flip)
-
-
-BLEND_KINDS = ("uniform", "gauss")
-
-
-def blend_weights_host(patch, kind: str = "uniform"):
-    """The per-axis window weights of the blend `kind` for the window extent `patch`, three fp32 numpy vectors whose
-    outer product weighs a window's voxels.  uniform: ones.  gauss: w(i) = exp(-0.5 ((i - (p - 1) / 2) / (p / 8))^2),
-    sigma = patch / 8 with the peak 1 at the centre, computed in fp64 and rounded once to fp32.  The least value of an
-    axis is exp(-0.5 (4 (p - 1) / p)^2) > exp(-8) = 3.4e-4 at any p, so the least product of three is above 3.7e-11:
-    thirty orders of magnitude from the fp32 denormals, and no floor is needed."""
-    import numpy as np
-    if kind not in BLEND_KINDS:
-        raise _lib.EffqError(f"blend {kind!r}, one of {', '.join(BLEND_KINDS)}")
-    out = []
-    for p in _triple(patch):
-        if p <= 0:
-            raise _lib.EffqError(f"window extent {p} must be positive")
-        if kind == "uniform":
-            out.append(np.ones(p, dtype=np.float32))
-        else:
-            i = np.arange(p, dtype=np.float64)
-            out.append(np.exp(-0.5 * ((i - (p - 1) / 2.0) / (p / 8.0)) ** 2).astype(np.float32))
-    return tuple(out)
 
 
 def make_geom(x_shape_ncdhw, c2: int, ksize, stride, padding) -> Geom:
@@ -129,84 +99,8 @@ def conv_i8s_plan_query(lib, geom: Geom, act_levels: int, w_levels: int) -> dict
     return dict(zip(("NJ", "CT", "T", "K", "aoff", "wmul", "grid"), (o.value for o in out)))
 
 
-class HipOps:
+class HipOps(WindowOps, SegOps, PrepOps):
     """Per-device handle: stream + library-owned workspaces (grown on demand, never shrunk)."""
-
-    def __init__(self, device: torch.device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.EffqError(f"efficientq_amd runs on a HIP device only, got {device} (no CPU fallback)")
-        self.lib = _lib.load()
-        self.device = device
-        self._red_ws = torch.zeros(self.lib.effq_reduce_ws_bytes(), dtype=torch.uint8, device=device)
-        self._ws = {}
-        self._att_cache = {}
-        self._ws_retired = []
-
-    # -- plumbing ---------------------------------------------------------------------------
-    @property
-    def stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def loss_stream(self):
-        """The stream the per-iteration loss evaluation runs on, one iteration behind the ADMM chain."""
-        if getattr(self, "_loss", None) is None:
-            self._loss = torch.cuda.Stream(self.device)
-        return self._loss
-
-    def side_stream(self):
-        """A second HIP stream of this device for work that is independent of the calibration stream."""
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(self.device)
-        return self._side
-
-    def side_stream2(self):
-        """A third stream: the later inverses of a layer alternate between the two side streams."""
-        if getattr(self, "_side2", None) is None:
-            self._side2 = torch.cuda.Stream(self.device)
-        return self._side2
-
-    def warm_streams(self):
-        """Create every stream the calibration uses NOW, in a fixed order: HIP hands out hardware queues in creation order
-        (4 by default), and streams that share one run their kernels one after the other.  Created lazily - after a
-        communicator had brought its own streams - the two side streams of the inverses landed on one queue (the later
-        inverses of the 256-channel layers 44 / 63 ms instead of 28 / 32, +5 % per calibration with a 1-rank RCCL group);
-        rccl.DirectComm calls this before ncclCommInitRank."""
-        if getattr(self, "_warm", False):
-            return
-        main = torch.cuda.current_stream(self.device)
-        # which streams get their helper, in which order, is empirical (per calibration with a 1-rank RCCL group, one box: none
-        # 693 ms, main / loss / side / side2 675, main / side / side2 - the order of a run without a communicator - 691; plain
-        # run 657; GPU_MAX_HW_QUEUES = 6 / 8: 766 / 753)
-        for st in (main, self.loss_stream(), self.side_stream(), self.side_stream2()):
-            check(self.lib.effq_spd_inverse_prepare(st.cuda_stream), "effq_spd_inverse_prepare")
-        self._warm = True
-
-    def _workspace(self, key: str, nbytes: int) -> torch.Tensor:
-        """Library workspace `key`, zero-filled on the current stream when (re)allocated.  A replaced buffer stays
-        referenced until release_retired() (kernels of another stream may still be reading it, and the caching
-        allocator only orders a block against the stream it was allocated on)."""
-        cur = self._ws.get(key)
-        if cur is None or cur.numel() < nbytes:
-            if cur is not None:
-                self._ws_retired.append(cur)
-            cur = torch.zeros(int(nbytes), dtype=torch.uint8, device=self.device)
-            self._ws[key] = cur
-        return cur
-
-    def release_retired(self):
-        """Drop replaced workspaces; call only where every stream of this handle has been joined."""
-        self._ws_retired.clear()
-
-    def _elsewhere(self, t: torch.Tensor) -> bool:
-        return t.device != self.device and not (t.device.type == "cuda" and self.device.index in (None, t.device.index))
-
-    def _f32(self, t: torch.Tensor) -> torch.Tensor:
-        if self._elsewhere(t):
-            raise _lib.EffqError(f"tensor on {t.device}, ops on {self.device}")
-        if t.dtype != torch.float32:
-            raise _lib.EffqError(f"expected float32, got {t.dtype}")
-        return t if t.is_contiguous() else t.contiguous()
 
     # -- a1/a3 --------------------------------------------------------------------------------
     def quant_dequant_f32(self, x: torch.Tensor, alpha: torch.Tensor, levels: int, lo: float, hi: float,
@@ -761,7 +655,6 @@ class HipOps:
         best iterate but synchronises with the host every iteration to do so.
         channel_wise: one weight scale per output channel (effq_fixed_point_channels_proj); the run then carries
         `alpha_ring` (iters x c2 doubles) and `w_iters_ring` (iters x c2 int32).  Loss kinds 0 and 4 only."""
-        from types import SimpleNamespace
         c2, n = (int(i) for i in B0.shape)
         has_b = b0 is not None
         # convert ONCE and keep the converted tensors alive with the run (the call only enqueues work on three streams:
@@ -1077,940 +970,6 @@ class HipOps:
                                                int(act_levels), _ptr(sqerr), _ptr(out), _ptr(ws), ws.numel(),
                                                self.stream), "conv3d_quant_calib_step")
         return out, sqerr
-
-    # -- validation on whole volumes (evaluate.validate_seg) ----------------------------------------------------
-    @staticmethod
-    def window_grid(dhw, patch, overlap) -> Tuple[int, int, int]:
-        """Windows per axis of evaluate.window_starts; raises on a window larger than the volume or an overlap that
-        is not smaller than the window."""
-        n = []
-        for s, p, o in zip(dhw, _triple(patch), _triple(overlap)):
-            if p <= 0 or p > s:
-                raise _lib.EffqError(f"window extent {p} outside 1..{s}")
-            if o < 0 or o >= p:
-                raise _lib.EffqError(f"overlap {o} must lie in 0..{p - 1}")
-            n.append(len(range(0, s - p, p - o)) + 1)
-        return tuple(n)
-
-    def _window_case(self, shape, patch, overlap):
-        """(N, C, D, H, W, patch, overlap, number of windows) of the N x C x D x H x W volume `shape`, window_grid's
-        refusals applied."""
-        N, Cc, D, H, W = (int(i) for i in shape)
-        p, o = _triple(patch), _triple(overlap)
-        return N, Cc, D, H, W, p, o, math.prod(self.window_grid((D, H, W), p, o))
-
-    @staticmethod
-    def _window_channels(what: str, Cc: int):
-        if not 0 < Cc <= 8:
-            raise _lib.EffqError(f"{what}: {Cc} channels, at most 8")
-
-    def window_gather(self, vol: torch.Tensor, patch, overlap, first: int = 0, count: Optional[int] = None,
-                      flip: int = 0):
-        """Windows first .. first+count-1 of the N x C x D x H x W volume as one (count*N, pd, ph, pw, C)
-        channels-last batch, window-major, the content of every window mirrored along the axes of the mask `flip`
-        (bit 0 = d, bit 1 = h, bit 2 = w; effq_window_gather)."""
-        x = self._f32(vol)
-        if x.dim() != 5:
-            raise _lib.EffqError(f"window_gather: expected N x C x D x H x W, got {tuple(x.shape)}")
-        flip = _flip_mask(flip, "window_gather")
-        N, Cc, D, H, W, p, o, nwin = self._window_case(x.shape, patch, overlap)
-        count = nwin - first if count is None else int(count)
-        if first < 0 or count <= 0 or first + count > nwin:
-            raise _lib.EffqError(f"windows {first}..{first + count - 1} of {nwin}")
-        out = torch.empty(count * N, p[0], p[1], p[2], Cc, dtype=torch.float32, device=self.device)
-        check(self.lib.effq_window_gather(_ptr(x), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], int(first), count,
-                                          flip, _ptr(out), self.stream), "effq_window_gather")
-        return out
-
-    def window_put(self, last: torch.Tensor, buf_slice: torch.Tensor, flip: int = 0, accumulate: bool = False) -> None:
-        """A network's last head `last` (M x C x pd x ph x pw, the windows of one batch mirrored by `flip`) into
-        `buf_slice`, the M x pd x ph x pw x C slice of the stitch's window buffer: transposed to channels-last,
-        un-mirrored, and stored (accumulate=False) or added onto what the slice holds (effq_window_put).  The slice is
-        written in place: it must be fp32, contiguous and on this device.  A head with channels-last strides (from_ndhwc:
-        what the convs of this package return) stored with flip 0 is in the slice's layout already, and the bits are
-        copied device to device as they lie; for any other pass such a head is first made contiguous, which allocates
-        a tensor of its size."""
-        if last.dim() != 5:
-            raise _lib.EffqError(f"window_put: expected M x C x pd x ph x pw, got {tuple(last.shape)}")
-        flip = _flip_mask(flip, "window_put")
-        M, Cc, pd, ph, pw = (int(i) for i in last.shape)
-        self._window_channels("window_put", Cc)
-        if tuple(buf_slice.shape) != (M, pd, ph, pw, Cc):
-            raise _lib.EffqError(f"window_put: buffer slice {tuple(buf_slice.shape)}, the head needs {(M, pd, ph, pw, Cc)}")
-        if self._f32(buf_slice) is not buf_slice:
-            raise _lib.EffqError("window_put: the buffer slice is written in place and must be contiguous")
-        if M * Cc * pd * ph * pw >= 1 << 31:
-            raise _lib.EffqError(f"window_put: {M * Cc * pd * ph * pw} elements, fewer than 2^31 per call")
-        as_stored = last.permute(0, 2, 3, 4, 1)
-        if flip == 0 and not accumulate and not last.is_contiguous() and as_stored.is_contiguous():
-            buf_slice.copy_(self._f32(as_stored))           # _f32: the checks of device and dtype, no copy
-            return
-        src = self._f32(last)
-        check(self.lib.effq_window_put(_ptr(src), M, Cc, pd, ph, pw, flip, int(bool(accumulate)), _ptr(buf_slice),
-                                       self.stream), "effq_window_put")
-
-    def window_stitch(self, win: torch.Tensor, shape, patch, overlap, weights=None, nflip: int = 1) -> torch.Tensor:
-        """The window buffer, (nwin*N, pd, ph, pw, C) channels-last and window-major and holding the sum of `nflip`
-        passes, stitched to the N x C x D x H x W volume `shape` (effq_window_stitch).  weights=None: each voxel is the
-        sum over its covering windows over (nflip * their count); with nflip = 1 evaluate.patch_to_image3d.  Otherwise
-        the separable per-axis `weights` (three fp32 device tensors of pd, ph, pw values: blend_weights): the weighted
-        sum over (nflip * the sum of the weights).  Ones give the bits of None."""
-        w = self._f32(win)
-        N, Cc, D, H, W, p, o, nwin = self._window_case(shape, patch, overlap)
-        if tuple(w.shape) != (nwin * N, p[0], p[1], p[2], Cc):
-            raise _lib.EffqError(f"window_stitch: windows {tuple(w.shape)}, geometry needs {(nwin * N, *p, Cc)}")
-        self._window_channels("window_stitch", Cc)
-        if int(nflip) != nflip or nflip < 1:
-            raise _lib.EffqError(f"window_stitch: nflip {nflip!r}, the number of passes summed, is at least 1")
-        ws = (None, None, None)
-        if weights is not None:
-            if len(weights) != 3:
-                raise _lib.EffqError(f"window_stitch: {len(weights)} weight tensors, one per axis d, h, w")
-            ws = [self._f32(t) for t in weights]
-            for t, n, ax in zip(ws, p, "dhw"):
-                if t.dim() != 1 or int(t.numel()) != n:
-                    raise _lib.EffqError(f"window_stitch: weights of axis {ax} have shape {tuple(t.shape)}, the window "
-                                         f"needs ({n},)")
-        out = torch.empty(N, Cc, D, H, W, dtype=torch.float32, device=self.device)
-        check(self.lib.effq_window_stitch(_ptr(w), N, Cc, D, H, W, p[0], p[1], p[2], o[0], o[1], o[2], _ptr(ws[0]),
-                                          _ptr(ws[1]), _ptr(ws[2]), int(nflip), _ptr(out), self.stream),
-              "effq_window_stitch")
-        return out
-
-    def blend_weights(self, patch, kind: str = "uniform"):
-        """The three per-axis fp32 weight tensors of window_stitch on this device (blend_weights_host)."""
-        return tuple(torch.from_numpy(w).to(self.device) for w in blend_weights_host(patch, kind))
-
-    def set_decision_threshold(self, logit: Optional[float]) -> None:
-        """The logit every sigmoid decision of these ops is taken at from now on (--thresh): sigmoid_threshold() returns
-        the fp32 nearest `logit`, so the tallies, the label maps, the lesions, the surfaces and the agreement follow it.
-        None: the default again.  seg_sweep and sweep_edges keep the default: the sweep does not depend on it."""
-        if logit is None:
-            self._decision_thresh = None
-            return
-        v = float(torch.tensor(float(logit), dtype=torch.float32).item())
-        if not math.isfinite(v):
-            raise _lib.EffqError(f"set_decision_threshold: {logit!r} is no finite fp32 logit")
-        self._decision_thresh = v
-
-    def sigmoid_threshold(self) -> float:
-        """The logit a sigmoid decision is taken at: the one set_decision_threshold set, or default_sigmoid_threshold()."""
-        if getattr(self, "_decision_thresh", None) is not None:
-            return self._decision_thresh
-        return self.default_sigmoid_threshold()
-
-    def default_sigmoid_threshold(self) -> float:
-        """The least fp32 x at which the framework's fp32 `torch.sigmoid(x) >= 0.5` holds on this device.  Near 0 it is
-        not 0: a small negative logit rounds to exactly 0.5.  Found by bisection over the bit patterns of -x, then
-        checked on the 2^17 floats around it; cached."""
-        if getattr(self, "_sig_thresh", None) is not None:
-            return self._sig_thresh
-
-        def decide(mags):       # magnitudes as int32 bit patterns -> decision of sigmoid(-mag) >= 0.5
-            x = -torch.tensor(mags, dtype=torch.int32).view(torch.float32).to(self.device)
-            return (torch.sigmoid(x) >= 0.5).cpu()
-
-        lo, hi = 0, 0x3F800000            # sigmoid(-0) = 0.5 holds, sigmoid(-1) < 0.5
-        while hi - lo > 1:
-            cand = sorted({lo + (hi - lo) * k // 4097 for k in range(1, 4097)} - {lo, hi})
-            ok = decide(cand)
-            bad = (~ok).nonzero()
-            first_bad = int(bad[0]) if len(bad) else len(cand)
-            lo = cand[first_bad - 1] if first_bad > 0 else lo
-            hi = cand[first_bad] if first_bad < len(cand) else hi
-        dense = list(range(max(0, lo - (1 << 16)), lo + (1 << 16)))
-        if not torch.equal(decide(dense), torch.tensor(dense) <= lo):
-            raise _lib.EffqError("torch.sigmoid(x) >= 0.5 is not monotone around its threshold")
-        self._sig_thresh = float(-torch.tensor([lo], dtype=torch.int32).view(torch.float32).item())
-        return self._sig_thresh
-
-    @staticmethod
-    def _fuse_code(what: str, fuse, argmax: bool, by: str, Cc: int, rule: Optional[str] = None) -> int:
-        """The code of the merge type `fuse`, checked for a decision by argmax or by sigmoid (named `by` in the refusal),
-        together with the class count and, for the label rule 'brats', its three channels."""
-        key = fuse.lower() if isinstance(fuse, str) else fuse
-        if key not in _lib.SEG_FUSE or (argmax and key is not None):
-            raise _lib.EffqError(f"{what}: merge type {fuse!r} for {by}")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"{what}: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if rule == "brats" and Cc < 3:
-            raise _lib.EffqError(f"{what}: the brats rule needs 3 channels or more, got {Cc}")
-        return _lib.SEG_FUSE[key]
-
-    def _seg_case(self, what: str, logits: torch.Tensor, label: torch.Tensor, task: str, fuse, spatial: bool):
-        """The arguments of one case that seg_tallies, seg_lesions, seg_surface and seg_surface_mm share, checked:
-        returns (x, lab, Cc, extents, mode, fuse code, thresh) - the fp32 logits, the contiguous label, the class count,
-        (D, H, W) when `spatial` requires C x D x H x W logits and the voxel count S otherwise, and the decision."""
-        x = self._f32(logits)
-        if spatial and x.dim() != 4:
-            raise _lib.EffqError(f"{what}: expected C x D x H x W logits, got {tuple(x.shape)}")
-        Cc = int(x.shape[0])
-        extents = tuple(int(i) for i in x.shape[1:]) if spatial else x[0].numel()
-        if task == "lits":
-            mode, lshape, thresh = _lib.SEG_ARGMAX, tuple(x.shape[1:]), 0.0
-        elif task == "brats":
-            mode, lshape, thresh = _lib.SEG_SIGMOID, tuple(x.shape), self.sigmoid_threshold()
-        else:
-            raise _lib.EffqError(f"Unknown task {task}")
-        fcode = self._fuse_code(what, fuse, mode == _lib.SEG_ARGMAX, f"task {task}", Cc)
-        if tuple(label.shape) != lshape or label.dtype != torch.uint8 or label.device != x.device:
-            raise _lib.EffqError(f"{what}: label {tuple(label.shape)} {label.dtype} on {label.device}, "
-                                 f"needs {lshape} torch.uint8 on {x.device}")
-        return x, label.contiguous(), Cc, extents, mode, fcode, thresh
-
-    def _mask_planes(self, what: str, mask: torch.Tensor):
-        """(m, P, D, H, W) of the masks cc_label, edt_sq and edt_sq_mm take: D x H x W or P x D x H x W uint8, not empty,
-        on the device of the ops; m is contiguous."""
-        if mask.dim() not in (3, 4) or mask.dtype != torch.uint8 or mask.numel() == 0:
-            raise _lib.EffqError(f"{what}: mask {tuple(mask.shape)} {mask.dtype}, needs (P x) D x H x W torch.uint8")
-        if self._elsewhere(mask):
-            raise _lib.EffqError(f"{what}: mask on {mask.device}, ops on {self.device}")
-        m = mask.contiguous()
-        D, H, W = (int(i) for i in m.shape[-3:])
-        return m, (int(m.shape[0]) if m.dim() == 4 else 1), D, H, W
-
-    def seg_tallies(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
-        """TP, FP, FN, TN per class (C x 4 int64) of one case's stitched logits (C x D x H x W) against its label
-        (effq_seg_tallies): lits = argmax over the channels vs class ids (D x H x W); brats = sigmoid >= 0.5 per channel,
-        merged by `fuse` (None / 'agg' / 'con'), vs a C x D x H x W 0/1 label."""
-        x, lab, Cc, S, mode, fcode, thresh = self._seg_case("seg_tallies", logits, label, task, fuse, False)
-        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
-        ws = self._workspace("seg_tallies", _lib.SEG_TALLIES_WS_BYTES)
-        check(self.lib.effq_seg_tallies(_ptr(x), _ptr(lab), Cc, S, mode, fcode, thresh, _ptr(counts), _ptr(ws), ws.numel(),
-                                        self.stream), "effq_seg_tallies")
-        return counts
-
-    def seg_sweep(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
-        """The threshold sweep of one case (effq_seg_sweep), arguments as seg_tallies: C x 2 x 4096 int64 on the device,
-        [c][g][b] = the voxels with truth g for class c whose score for class c falls in bin b of sweep_edges.  The
-        counts of the decision "score >= edge k" are the sums over the bins from k on; row 2048 is seg_tallies at the
-        default threshold, which is the pinned edge whatever set_decision_threshold set."""
-        x, lab, Cc, S, mode, fcode, _ = self._seg_case("seg_sweep", logits, label, task, fuse, False)
-        if not 0 < S < 2 ** 31:
-            raise _lib.EffqError(f"seg_sweep: {S} voxels, needs 1 to 2^31 - 1")
-        thresh = 0.0 if mode == _lib.SEG_ARGMAX else self.default_sigmoid_threshold()
-        hist = torch.empty(Cc, 2, _lib.SEG_SWEEP_BINS, dtype=torch.int64, device=self.device)
-        check(self.lib.effq_seg_sweep(_ptr(x), _ptr(lab), Cc, S, mode, fcode, thresh, _ptr(hist), self.stream),
-              "effq_seg_sweep")
-        return hist
-
-    def seg_sweep_plan(self, Cc: int, S: int, task: str) -> dict:
-        """The launch seg_sweep makes for Cc classes and S voxels (effq_seg_sweep_plan): grid, the workgroups, and trips,
-        the trips of each over its groups of four voxels."""
-        mode = {"lits": _lib.SEG_ARGMAX, "brats": _lib.SEG_SIGMOID}.get(task)
-        if mode is None:
-            raise _lib.EffqError(f"Unknown task {task}")
-        grid, trips = C.c_int(0), C.c_int(0)
-        check(self.lib.effq_seg_sweep_plan(int(Cc), int(S), mode, C.byref(grid), C.byref(trips)), "effq_seg_sweep_plan")
-        return {"grid": grid.value, "trips": trips.value}
-
-    def sweep_edges(self, kind: str) -> torch.Tensor:
-        """The 4096 fp32 edges of seg_sweep's bins on the host (effq_seg_sweep_edges), index 0 = -inf: kind 'lits' /
-        'argmax' (edge 2048 = 0) or 'brats' / 'sigmoid' (edge 2048 = the default sigmoid threshold)."""
-        mode = {"argmax": _lib.SEG_ARGMAX, "lits": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID,
-                "brats": _lib.SEG_SIGMOID}.get(kind)
-        if mode is None:
-            raise _lib.EffqError(f"sweep_edges: unknown kind {kind!r} (argmax or sigmoid)")
-        thresh = 0.0 if mode == _lib.SEG_ARGMAX else self.default_sigmoid_threshold()
-        edges = (C.c_float * _lib.SEG_SWEEP_BINS)()
-        check(self.lib.effq_seg_sweep_edges(mode, thresh, edges), "effq_seg_sweep_edges")
-        return torch.frombuffer(bytearray(edges), dtype=torch.float32).clone()
-
-    def seg_labels(self, logits: torch.Tensor, rule: str, fuse: Optional[str] = None, dtype=torch.uint8):
-        """Label maps of N cases' logits (N x C x spatial, fp32) from the decisions seg_tallies counts
-        (effq_seg_labels).  rule 'argmax': class ids of torch.max (fuse None); 'brats': merge_label_brats of the
-        sigmoid >= 0.5 channels merged by `fuse` (0 / 1 / 2 / 4, C >= 3); 'rank': i + 1 of the highest set merged
-        channel (fuse 'con': get_pred_brats_con_merge); 'planes': the merged 0/1 channels themselves.  Returns
-        N x spatial of `dtype` (torch.uint8 / torch.uint16), or N x C x spatial uint8 for 'planes'."""
-        x = self._f32(logits)
-        if x.dim() < 3:
-            raise _lib.EffqError(f"seg_labels: expected N x C x spatial logits, got {tuple(x.shape)}")
-        N, Cc, S = int(x.shape[0]), int(x.shape[1]), math.prod(x.shape[2:])
-        if rule not in _lib.SEG_LABEL_RULES:
-            raise _lib.EffqError(f"seg_labels: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
-        fcode = self._fuse_code("seg_labels", fuse, rule == "argmax", f"rule {rule}", Cc, rule)
-        if dtype not in (torch.uint8, torch.uint16) or (rule == "planes" and dtype != torch.uint8):
-            raise _lib.EffqError(f"seg_labels: output {dtype} for rule {rule}")
-        if N == 0 or S == 0 or N > 65535:
-            raise _lib.EffqError(f"seg_labels: {N} cases of {S} voxels")
-        shape = tuple(x.shape) if rule == "planes" else (N,) + tuple(x.shape[2:])
-        out = torch.empty(shape, dtype=dtype, device=self.device)
-        thresh = 0.0 if rule == "argmax" else self.sigmoid_threshold()
-        check(self.lib.effq_seg_labels(_ptr(x), N, Cc, S, _lib.SEG_LABEL_RULES[rule], fcode, thresh,
-                                       out.element_size(), _ptr(out), self.stream), "effq_seg_labels")
-        return out
-
-    def seg_labels_source(self, logits: torch.Tensor, pmin, grid, factors, source_shape, rule: str,
-                          fuse: Optional[str] = None) -> torch.Tensor:
-        """The label map of one subject on its SOURCE grid (effq_seg_labels_source): `logits` C x d x h x w fp32 are the
-        stitched logits on the box pmin : pmin + (d, h, w) of the working grid `grid`, which prep made from the source
-        grid `source_shape` with `factors` = target spacing / source spacing per axis (None: 1, no resampling).  Every
-        source voxel whose centre falls into the box gets the label of `rule` ('argmax', 'brats', 'rank'; 'planes' is
-        refused) and `fuse` from the trilinearly interpolated logits, every other voxel 0.  Returns uint8 of
-        `source_shape`."""
-        x = self._f32(logits)
-        if x.dim() != 4:
-            raise _lib.EffqError(f"seg_labels_source: expected C x d x h x w logits, got {tuple(x.shape)}")
-        Cc = int(x.shape[0])
-        if rule not in _lib.SEG_LABEL_RULES:
-            raise _lib.EffqError(f"seg_labels_source: unknown rule {rule!r} (one of {', '.join(_lib.SEG_LABEL_RULES)})")
-        fcode = self._fuse_code("seg_labels_source", fuse, rule == "argmax", f"rule {rule}", Cc, rule)
-        try:
-            lo, G, src = (tuple(int(v) for v in t) for t in (pmin, grid, source_shape))
-            f = (1.0, 1.0, 1.0) if factors is None else tuple(float(v) for v in factors)
-        except (TypeError, ValueError) as e:
-            raise _lib.EffqError(f"seg_labels_source: {e}") from e
-        if len(lo) != 3 or len(G) != 3 or len(src) != 3 or len(f) != 3 or x.numel() == 0:
-            raise _lib.EffqError(f"seg_labels_source: box at {lo} of {tuple(x.shape[1:])}, grid {G}, factors {f}, source "
-                                 f"{src}: three values each")
-        if min(src) < 1 or max(src) > 32767 or math.prod(src) >= 2 ** 31:     # the output is not allocated for these
-            raise _lib.EffqError(f"seg_labels_source: source grid {src}: 1 to 32767 along an axis, 2^31 - 1 voxels at most")
-        out = torch.empty(src, dtype=torch.uint8, device=self.device)
-        thresh = 0.0 if rule == "argmax" else self.sigmoid_threshold()
-        i3 = C.c_int * 3
-        check(self.lib.effq_seg_labels_source(_ptr(x), Cc, i3(*(int(v) for v in x.shape[1:])), i3(*lo), i3(*G),
-                                              (C.c_double * 3)(*f), i3(*src), _lib.SEG_LABEL_RULES[rule],
-                                              fcode, thresh, _ptr(out), self.stream), "effq_seg_labels_source")
-        return out
-
-    def seg_probs_source(self, logits: torch.Tensor, pmin, grid, factors, source_shape, mode: str,
-                         want_prob: bool = True, want_unc: bool = False):
-        """The probability planes and the uncertainty of one subject on its SOURCE grid (effq_seg_probs_source):
-        `logits`, `pmin`, `grid`, `factors` and `source_shape` as seg_labels_source, whose interpolated logits these are
-        computed from.  mode 'argmax' (class ids: softmax over the C channels, entropy as a share of ln C) or 'sigmoid'
-        (per raw channel; the largest binary entropy in bits).  Returns (probs, unc): C x source and source, uint8 levels
-        of 1 / 255, each None when not wanted; outside the box probs are 0 (argmax: channel 0 is 255) and unc is 0."""
-        x = self._f32(logits)
-        if x.dim() != 4:
-            raise _lib.EffqError(f"seg_probs_source: expected C x d x h x w logits, got {tuple(x.shape)}")
-        Cc = int(x.shape[0])
-        code = {"argmax": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID}.get(mode)
-        if code is None:
-            raise _lib.EffqError(f"seg_probs_source: unknown mode {mode!r} (argmax or sigmoid)")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"seg_probs_source: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if not (want_prob or want_unc):
-            raise _lib.EffqError("seg_probs_source: neither the probabilities nor the uncertainty is wanted")
-        try:
-            lo, G, src = (tuple(int(v) for v in t) for t in (pmin, grid, source_shape))
-            f = (1.0, 1.0, 1.0) if factors is None else tuple(float(v) for v in factors)
-        except (TypeError, ValueError) as e:
-            raise _lib.EffqError(f"seg_probs_source: {e}") from e
-        if len(lo) != 3 or len(G) != 3 or len(src) != 3 or len(f) != 3 or x.numel() == 0:
-            raise _lib.EffqError(f"seg_probs_source: box at {lo} of {tuple(x.shape[1:])}, grid {G}, factors {f}, source "
-                                 f"{src}: three values each")
-        planes = Cc if want_prob else 1
-        if min(src) < 1 or max(src) > 32767 or planes * math.prod(src) >= 2 ** 31:   # the outputs are not allocated for these
-            raise _lib.EffqError(f"seg_probs_source: source grid {src}, {planes} planes: 1 to 32767 along an axis, "
-                                 f"2^31 - 1 bytes at most")
-        probs = torch.empty((Cc,) + src, dtype=torch.uint8, device=self.device) if want_prob else None
-        unc = torch.empty(src, dtype=torch.uint8, device=self.device) if want_unc else None
-        i3 = C.c_int * 3
-        check(self.lib.effq_seg_probs_source(_ptr(x), Cc, i3(*(int(v) for v in x.shape[1:])), i3(*lo), i3(*G),
-                                             (C.c_double * 3)(*f), i3(*src), code, _ptr(probs), _ptr(unc), self.stream),
-              "effq_seg_probs_source")
-        return probs, unc
-
-    def seg_agreement(self, logits_q: torch.Tensor, logits_fp: torch.Tensor, mode: str, fuse: Optional[str] = None,
-                      want_map: bool = False):
-        """Where and how much two networks differ on one case (effq_seg_agreement): the stitched last-head logits of the
-        calibrated and of the FP network, C x spatial fp32 each.  mode 'argmax' (or the task 'lits') / 'sigmoid' ('brats')
-        and `fuse` as seg_tallies: both networks' voxels are decided by its rule.  Returns (counts, flips, stats, map):
-        counts C x 4 int64 = both, Q only, FP only, neither (TP, FP, FN, TN with the FP decision as the truth); flips (1)
-        int64, the voxels decided differently in any class; stats C x 4 float64 = sum (q - f)^2, sum f^2, max |q - f|,
-        sum |p_q - p_f| (p: sigmoid of the channel / softmax over the channels, in fp64); map: uint8 of the spatial
-        shape with bit c set where class c is decided differently, or None without `want_map`."""
-        if logits_q.dtype != torch.float32 or logits_fp.dtype != torch.float32:
-            raise _lib.EffqError(f"seg_agreement: expected float32 logits, got {logits_q.dtype} and {logits_fp.dtype}")
-        if logits_q.shape != logits_fp.shape or logits_q.dim() < 2 or logits_q.numel() == 0:
-            raise _lib.EffqError(f"seg_agreement: logits {tuple(logits_q.shape)} and {tuple(logits_fp.shape)}, needs the "
-                                 f"same C x spatial shape for both")
-        if logits_q.device != logits_fp.device:
-            raise _lib.EffqError(f"seg_agreement: logits on {logits_q.device} and on {logits_fp.device}")
-        if not (logits_q.is_contiguous() and logits_fp.is_contiguous()):
-            raise _lib.EffqError("seg_agreement: the logits must be contiguous")
-        q, f = self._f32(logits_q), self._f32(logits_fp)
-        Cc, S = int(q.shape[0]), q[0].numel()
-        key = {"argmax": _lib.SEG_ARGMAX, "lits": _lib.SEG_ARGMAX, "sigmoid": _lib.SEG_SIGMOID,
-               "brats": _lib.SEG_SIGMOID}.get(mode)
-        if key is None:
-            raise _lib.EffqError(f"seg_agreement: unknown mode {mode!r} (argmax or sigmoid)")
-        fcode = self._fuse_code("seg_agreement", fuse, key == _lib.SEG_ARGMAX, f"mode {mode}", Cc)
-        thresh = 0.0 if key == _lib.SEG_ARGMAX else self.sigmoid_threshold()
-        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
-        flips = torch.empty(1, dtype=torch.int64, device=self.device)
-        stats = torch.empty(Cc, 4, dtype=torch.float64, device=self.device)
-        vmap = torch.empty(tuple(q.shape[1:]), dtype=torch.uint8, device=self.device) if want_map else None
-        ws = self._workspace("seg_agreement", _lib.SEG_AGREEMENT_WS_BYTES)
-        check(self.lib.effq_seg_agreement(_ptr(q), _ptr(f), Cc, S, key, fcode, thresh, _ptr(counts),
-                                          _ptr(flips), _ptr(stats), _ptr(vmap), _ptr(ws), ws.numel(), self.stream),
-              "effq_seg_agreement")
-        return counts, flips, stats, vmap
-
-    def cc_label(self, mask: torch.Tensor, connectivity: int = 26):
-        """Connected components of 0/1 volumes (effq_cc_label; scipy.ndimage.label in metrics.py:69-73): `mask` D x H x W
-        or P x D x H x W uint8, non-zero = foreground.  Returns (labels, ncomp): int32 labels of the mask's shape, 0 for
-        background and 1 + the least linear index of the voxel's component otherwise, and the int64 component count of
-        each mask.  connectivity 26 (3 x 3 x 3 neighbourhood) or 6 (faces)."""
-        m, P, D, H, W = self._mask_planes("cc_label", mask)
-        if connectivity not in (6, 26):
-            raise _lib.EffqError(f"cc_label: connectivity {connectivity}, 6 or 26")
-        if P > 65535 or m.numel() >= 2 ** 31:
-            raise _lib.EffqError(f"cc_label: {P} masks of {D * H * W} voxels (at most 65535 masks, 2^31 - 1 voxels in all)")
-        labels = torch.empty(m.shape, dtype=torch.int32, device=self.device)
-        ncomp = torch.empty(P, dtype=torch.int64, device=self.device)
-        ws = self._workspace("cc", self.lib.effq_cc_ws_bytes(P, D, H, W))
-        check(self.lib.effq_cc_label(_ptr(m), P, D, H, W, int(connectivity), _ptr(labels), _ptr(ncomp), _ptr(ws),
-                                     ws.numel(), self.stream), "effq_cc_label")
-        return labels, (ncomp if m.dim() == 4 else ncomp[0])
-
-    def seg_lesions(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
-        """The lesion-level columns of one case (C x 4 int64: totall, predl, fnl, fpl - components of the label mask, of
-        the predicted mask, label components without a predicted voxel, predicted components without a labelled voxel;
-        metrics.py:69-94 with the 3 x 3 x 3 neighbourhood) from its stitched logits (C x D x H x W) and its label
-        (effq_seg_lesions).  Arguments and decisions as seg_tallies."""
-        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_lesions", logits, label, task, fuse, True)
-        if D * H * W == 0 or 2 * Cc * D * H * W >= 2 ** 31:
-            raise _lib.EffqError(f"seg_lesions: {2 * Cc} masks of {D * H * W} voxels (2^31 - 1 voxels in all at most)")
-        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
-        ws = self._workspace("cc", self.lib.effq_cc_ws_bytes(2 * Cc, D, H, W))
-        check(self.lib.effq_seg_lesions(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, _lib.LESION_CONNECTIVITY,
-                                        _ptr(counts), _ptr(ws), ws.numel(), self.stream), "effq_seg_lesions")
-        return counts
-
-    def _table_call(self, what: str, P: int, head: int, width: int, max_rows, call):
-        """The calls of cc_table and seg_lesion_table: one int32 buffer holds `head` int64 words (the counts), the P
-        int64 row counts and the P x capacity x width table, so one copy brings all of it to the host.  `call(cap, head
-        pointer, nrows pointer, rows pointer)` launches.  A plane with more components than the capacity: once more with
-        the capacity the row counts give.  Returns (head int64, nrows int64 (P), [rows of plane p, int32 n_p x width]),
-        all on the host."""
-        cap = _lib.LESION_TABLE_ROWS if max_rows is None else int(max_rows)
-        if cap <= 0:
-            raise _lib.EffqError(f"{what}: max_rows {max_rows}, needs a positive capacity")
-        while True:
-            if P * cap * width >= 2 ** 31:
-                raise _lib.EffqError(f"{what}: a table of {P} x {cap} rows")
-            front = 2 * (head + P)
-            buf = torch.empty(front + P * cap * width, dtype=torch.int32, device=self.device)
-            base = buf.data_ptr()
-            call(cap, C.c_void_p(base), C.c_void_p(base + 8 * head), C.c_void_p(base + 4 * front))
-            host = buf.cpu()
-            words = host[:front].view(torch.int64)
-            nrows = words[head:]
-            most = int(nrows.max())
-            if most <= cap:
-                table = host[front:].view(P, cap, width)
-                return words[:head], nrows, [table[q, :int(nrows[q])] for q in range(P)]
-            cap = most
-
-    def cc_table(self, mask: torch.Tensor, connectivity: int = 26, max_rows: Optional[int] = None):
-        """One record per connected component of 0/1 volumes (effq_cc_table; scipy.ndimage.label + numpy.bincount):
-        `mask` as cc_label.  Returns (rows, nrows) on the host: int32 rows n x 2 = first voxel (linear index), size in
-        voxels, in ascending order of the first voxel (row k is scipy's component k + 1) - one tensor for a D x H x W
-        mask, a list of P for P x D x H x W - and the int64 component count(s).  max_rows: the rows per mask asked for
-        first (default _lib.LESION_TABLE_ROWS); a mask with more components costs one more call, all rows are returned."""
-        m, P, D, H, W = self._mask_planes("cc_table", mask)
-        if connectivity not in (6, 26):
-            raise _lib.EffqError(f"cc_table: connectivity {connectivity}, 6 or 26")
-        if P > 65535 or m.numel() >= 2 ** 31:
-            raise _lib.EffqError(f"cc_table: {P} masks of {D * H * W} voxels (at most 65535 masks, 2^31 - 1 voxels in all)")
-
-        def call(cap, _head, nrows, rows):
-            ws = self._workspace("cc", self.lib.effq_cc_table_ws_bytes(P, D, H, W, cap))
-            check(self.lib.effq_cc_table(_ptr(m), P, D, H, W, int(connectivity), cap, rows, nrows, _ptr(ws), ws.numel(),
-                                         self.stream), "effq_cc_table")
-        _, nrows, rows = self._table_call("cc_table", P, 0, 2, max_rows, call)
-        return (rows, nrows) if m.dim() == 4 else (rows[0], nrows[0])
-
-    def seg_lesion_table(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None,
-                         max_rows: Optional[int] = None):
-        """The lesions of one case one by one (effq_seg_lesion_table), arguments and decisions as seg_lesions.  Returns
-        (counts, nrows, rows) on the host: counts C x 4 int64, bit for bit seg_lesions'; nrows (2 C) int64, the components
-        of plane q - the predicted mask of class q for q < C, the label mask of class q - C otherwise; rows, a list of
-        2 C int32 tensors n_q x 3 = first voxel (linear index), size, overlap (the voxels that the other mask of the
-        class holds too), in ascending order of the first voxel.  max_rows as cc_table."""
-        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_lesion_table", logits, label, task, fuse, True)
-        if D * H * W == 0 or 2 * Cc * D * H * W >= 2 ** 31:
-            raise _lib.EffqError(f"seg_lesion_table: {2 * Cc} masks of {D * H * W} voxels (2^31 - 1 voxels in all at most)")
-
-        def call(cap, counts, nrows, rows):
-            ws = self._workspace("cc", self.lib.effq_cc_table_ws_bytes(2 * Cc, D, H, W, cap))
-            check(self.lib.effq_seg_lesion_table(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh,
-                                                 _lib.LESION_CONNECTIVITY, cap, counts, nrows, rows, _ptr(ws), ws.numel(),
-                                                 self.stream), "effq_seg_lesion_table")
-        counts, nrows, rows = self._table_call("seg_lesion_table", 2 * Cc, 4 * Cc, 3, max_rows, call)
-        return counts.view(Cc, 4), nrows, rows
-
-    def label_clean(self, label_map: torch.Tensor, rules, connectivity: int = 26, out: Optional[torch.Tensor] = None):
-        """A predicted label map cleaned by connected components (effq_label_clean, --post): `label_map` D x H x W uint8;
-        `rules` a list of at most _lib.LABEL_CLEAN_MAX_RULES (labels, op, n, to) - config.PostRule - applied in order,
-        each to the map the previous one left: op 'largest' keeps the largest component of the voxels whose value is one
-        of `labels` (of equal sizes the one whose first voxel comes first) and gives every other component the value
-        `to`; op 'min' gives `to` to every component of fewer than `n` voxels.  Ops 'fill', 'close' and 'open'
-        (effq_label_post, called when a rule has one of them): 'fill' gives `to` to every hole of the mask (a component
-        of its complement, at the dual connectivity, that touches no face of the volume), 'close' to the voxels that
-        closing by a ball of `n` voxels (1 to _lib.LABEL_POST_MAX_RADIUS) adds - for both `to` is one of `labels` -
-        and 'open' to the voxels of the mask that opening by such a ball removes.  connectivity 26 or 6.  Returns (map,
-        stats): the cleaned map (a new tensor, or `out`, which may be `label_map` itself) and R x 2 int64 on the device:
-        per rule the components its mask had ('fill': the holes filled; 'close', 'open': the voxels of the mask before
-        the rule) and the voxels it relabelled."""
-        m, P, D, H, W = self._mask_planes("label_clean", label_map)
-        if m.dim() != 3:
-            raise _lib.EffqError(f"label_clean: map {tuple(m.shape)}, needs D x H x W")
-        if connectivity not in (6, 26):
-            raise _lib.EffqError(f"label_clean: connectivity {connectivity}, 6 or 26")
-        if m.numel() >= 2 ** 31:
-            raise _lib.EffqError(f"label_clean: a map of {m.numel()} voxels (2^31 - 1 at most)")
-        rules = list(rules)
-        R = len(rules)
-        if not 1 <= R <= _lib.LABEL_CLEAN_MAX_RULES:
-            raise _lib.EffqError(f"label_clean: {R} rules, 1 to {_lib.LABEL_CLEAN_MAX_RULES}")
-        sets = (C.c_uint8 * (256 * R))()
-        words = (C.c_longlong * (3 * R))()
-        morph, max_radius = False, 0
-        for r, rule in enumerate(rules):
-            try:
-                labels, op, n, to = rule
-                labels, n, to = [int(v) for v in labels], int(n), int(to)
-            except (TypeError, ValueError) as e:
-                raise _lib.EffqError(f"label_clean: rule {r}: {rule!r} is no (labels, op, n, to): {e}") from e
-            if op not in _lib.LABEL_CLEAN_OPS and op not in _lib.LABEL_POST_OPS:
-                raise _lib.EffqError(f"label_clean: rule {r}: unknown op {op!r} (one of "
-                                     f"{', '.join(list(_lib.LABEL_CLEAN_OPS) + list(_lib.LABEL_POST_OPS))})")
-            if not labels or min(labels) < 1 or max(labels) > 255:
-                raise _lib.EffqError(f"label_clean: rule {r}: labels {labels}, needs values of 1 to 255")
-            if op in ("fill", "close"):
-                if to not in labels:
-                    raise _lib.EffqError(f"label_clean: rule {r}: {op} adds voxels to the mask: the new label {to} is "
-                                         f"not one of {labels}")
-            elif not 0 <= to <= 255 or to in labels:
-                raise _lib.EffqError(f"label_clean: rule {r}: the new label {to} is outside 0..255 or one of {labels}")
-            if op == "min" and n < 1:
-                raise _lib.EffqError(f"label_clean: rule {r}: min {n}, needs 1 or more voxels")
-            if op in ("close", "open"):
-                if not 1 <= n <= _lib.LABEL_POST_MAX_RADIUS:
-                    raise _lib.EffqError(f"label_clean: rule {r}: {op} {n}, needs a radius of 1 to "
-                                         f"{_lib.LABEL_POST_MAX_RADIUS} voxels")
-                max_radius = max(max_radius, n)
-            for v in labels:
-                sets[256 * r + v] = 1
-            code = _lib.LABEL_CLEAN_OPS[op] if op in _lib.LABEL_CLEAN_OPS else _lib.LABEL_POST_OPS[op]
-            words[3 * r], words[3 * r + 1], words[3 * r + 2] = code, n, to
-            morph = morph or op in _lib.LABEL_POST_OPS
-        if out is None:
-            out = torch.empty_like(m)
-        elif out.shape != m.shape or out.dtype != torch.uint8 or out.device != m.device or not out.is_contiguous():
-            raise _lib.EffqError(f"label_clean: out {tuple(out.shape)} {out.dtype} on {out.device}, needs a contiguous "
-                                 f"{tuple(m.shape)} torch.uint8 on {m.device}")
-        elif out is label_map and m is not label_map:
-            raise _lib.EffqError("label_clean: a map cleaned in place must be contiguous")
-        stats = torch.empty(R, 2, dtype=torch.int64, device=self.device)
-        if not morph:
-            ws = self._workspace("label_clean", self.lib.effq_label_clean_ws_bytes(D, H, W))
-            check(self.lib.effq_label_clean(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
-                                            _ptr(ws), ws.numel(), self.stream), "effq_label_clean")
-            return out, stats
-        need = self.lib.effq_label_post_ws_bytes(D, H, W, max_radius)
-        if need == 0:
-            raise _lib.EffqError(f"label_clean: a map {D} x {H} x {W} padded by the radius {max_radius} is outside the "
-                                 f"distance transform's limits (fewer than 2^31 voxels, D and H at most "
-                                 f"{_lib.EDT_MAX_LINE})")
-        ws = self._workspace("label_clean", need)
-        check(self.lib.effq_label_post(_ptr(m), D, H, W, int(connectivity), R, sets, words, _ptr(out), _ptr(stats),
-                                       _ptr(ws), ws.numel(), self.stream), "effq_label_post")
-        return out, stats
-
-    def label_tallies(self, pred: torch.Tensor, truth: torch.Tensor, lut, C_: int):
-        """TP, FP, FN, TN per class (C x 4 int64, seg_tallies' layout) of a uint8 label map against the truth
-        (effq_label_tallies).  `lut`: 256 integers, bit c set = that label value belongs to class c; `truth`: a label map
-        of `pred`'s shape, read through `lut`, or C 0/1 planes (C x pred's shape)."""
-        Cc = int(C_)
-        if pred.dtype != torch.uint8 or truth.dtype != torch.uint8 or pred.numel() == 0:
-            raise _lib.EffqError(f"label_tallies: pred {tuple(pred.shape)} {pred.dtype}, truth {tuple(truth.shape)} "
-                                 f"{truth.dtype}: needs torch.uint8, not empty")
-        if not 0 < Cc <= _lib.SEG_TALLIES_MAX_CLASSES:
-            raise _lib.EffqError(f"label_tallies: {Cc} classes, at most {_lib.SEG_TALLIES_MAX_CLASSES}")
-        if tuple(truth.shape) == tuple(pred.shape):
-            planes = 0
-        elif tuple(truth.shape) == (Cc,) + tuple(pred.shape):
-            planes = 1
-        else:
-            raise _lib.EffqError(f"label_tallies: truth {tuple(truth.shape)} for a map {tuple(pred.shape)}: needs the "
-                                 f"map's shape, or {Cc} planes of it")
-        for t, who in ((pred, "pred"), (truth, "truth")):
-            if self._elsewhere(t):
-                raise _lib.EffqError(f"label_tallies: {who} on {t.device}, ops on {self.device}")
-        try:
-            table = [int(v) for v in lut]
-        except (TypeError, ValueError) as e:
-            raise _lib.EffqError(f"label_tallies: lut: {e}") from e
-        if len(table) != 256 or min(table) < 0 or max(table) >= 1 << Cc:
-            raise _lib.EffqError(f"label_tallies: lut of {len(table)} entries, needs 256 of {Cc} class bits each")
-        p, t = pred.contiguous(), truth.contiguous()
-        counts = torch.empty(Cc, 4, dtype=torch.int64, device=self.device)
-        ws = self._workspace("label_tallies", self.lib.effq_label_tallies_ws_bytes())
-        check(self.lib.effq_label_tallies(_ptr(p), _ptr(t), planes, Cc, p.numel(), (C.c_uint16 * 256)(*table),
-                                          _ptr(counts), _ptr(ws), ws.numel(), self.stream), "effq_label_tallies")
-        return counts
-
-    def edt_sq(self, mask: torch.Tensor):
-        """Exact squared Euclidean distance transform (effq_edt_sq): `mask` D x H x W or P x D x H x W uint8, non-zero =
-        site.  Returns an int32 tensor of the mask's shape: the squared distance (voxel units) of every voxel to the
-        nearest site of its own volume, 0 on a site, INT32_MAX throughout a volume without sites.  It is
-        rint(scipy.ndimage.distance_transform_edt(mask == 0) ** 2), voxel for voxel."""
-        m, P, D, H, W = self._mask_planes("edt_sq", mask)
-        need = self.lib.effq_surf_ws_bytes(P, D, H, W)
-        if need == 0:
-            raise _lib.EffqError(f"edt_sq: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels in "
-                                 f"all, D^2 + H^2 + W^2 < 2^31, D and H at most {_lib.EDT_MAX_LINE})")
-        sq = torch.empty(m.shape, dtype=torch.int32, device=self.device)
-        ws = self._workspace("surf", need)
-        check(self.lib.effq_edt_sq(_ptr(m), P, D, H, W, _ptr(sq), _ptr(ws), ws.numel(), self.stream), "effq_edt_sq")
-        return sq
-
-    def seg_surface(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None):
-        """What the surface distances of one case need (effq_seg_surface), from its stitched logits (C x D x H x W) and
-        its label, arguments and decisions as seg_tallies.  Returns (counts, sums): counts C x 6 int64 = nP, nL,
-        maxsq_PL, maxsq_LP, qlo_sq, qhi_sq and sums C x 2 float64 = the sums of the directed distances
-        (include/effq_hip.h); evaluate.surface_metrics turns them into hd, hd95 and assd."""
-        x, lab, Cc, (D, H, W), mode, fcode, thresh = self._seg_case("seg_surface", logits, label, task, fuse, True)
-        need = self.lib.effq_surf_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
-        if need == 0:
-            raise _lib.EffqError(f"seg_surface: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
-                                 f"most, D^2 + H^2 + W^2 < 2^31, D and H at most {_lib.EDT_MAX_LINE})")
-        counts = torch.empty(Cc, 6, dtype=torch.int64, device=self.device)
-        sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
-        ws = self._workspace("surf", need)
-        check(self.lib.effq_seg_surface(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, _ptr(counts), _ptr(sums),
-                                        _ptr(ws), ws.numel(), self.stream), "effq_seg_surface")
-        return counts, sums
-
-    @staticmethod
-    def _axis_weights(what: str, spacing):
-        """The fp32 weights of the three axes, float32(float64(spacing) ** 2), from a spacing of three finite positive
-        numbers (millimetres per voxel along D, H, W)."""
-        import numpy as np
-        try:
-            sp = [float(v) for v in spacing]
-        except (TypeError, ValueError):
-            sp = []
-        if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
-            raise _lib.EffqError(f"{what}: spacing {spacing!r}, needs three finite positive numbers (d, h, w)")
-        w = [float(np.float32(np.float64(v) ** 2)) for v in sp]
-        if not all(math.isfinite(v) and v > 0 for v in w):
-            raise _lib.EffqError(f"{what}: the square of spacing {spacing!r} is not a positive finite float32")
-        return w
-
-    def edt_sq_mm(self, mask: torch.Tensor, spacing):
-        """Squared Euclidean distance transform on a grid of spacing (d, h, w) (effq_edt_sq_mm): `mask` D x H x W or
-        P x D x H x W uint8, non-zero = site.  Returns a float32 tensor of the mask's shape: for every voxel the least
-        fl(fl(fl(ww dw^2) + fl(wh dh^2)) + fl(wd dd^2)) over the sites of its own volume, wa = float32(spacing_a ** 2) -
-        the bits of the brute force in fp32 -, 0 on a site, +inf throughout a volume without sites."""
-        m, P, D, H, W = self._mask_planes("edt_sq_mm", mask)
-        wd, wh, ww = self._axis_weights("edt_sq_mm", spacing)
-        need = self.lib.effq_surf_mm_ws_bytes(P, D, H, W)
-        if need == 0:
-            raise _lib.EffqError(f"edt_sq_mm: {P} masks of {D} x {H} x {W} voxels (at most 65535 masks, 2^31 - 1 voxels "
-                                 f"in all, every extent at most {_lib.EDT_MM_MAX_EXTENT})")
-        sq = torch.empty(m.shape, dtype=torch.float32, device=self.device)
-        ws = self._workspace("surf_mm", need)
-        check(self.lib.effq_edt_sq_mm(_ptr(m), P, D, H, W, wd, wh, ww, _ptr(sq), _ptr(ws), ws.numel(), self.stream),
-              "effq_edt_sq_mm")
-        return sq
-
-    def seg_surface_mm(self, logits: torch.Tensor, label: torch.Tensor, task: str, fuse: Optional[str] = None,
-                       spacing=(1.0, 1.0, 1.0)):
-        """What the surface distances of one case in millimetres need (effq_seg_surface_mm), from its stitched logits
-        (C x D x H x W), its label and the spacing (d, h, w) of its grid; arguments and decisions as seg_surface.
-        Returns (counts, sq, sums): counts C x 2 int64 = nP, nL, sq C x 4 float32 = max_PL, max_LP, qlo, qhi (squared
-        distances in mm^2) and sums C x 2 float64 = the sums of the directed distances in mm (include/effq_hip.h);
-        evaluate.surface_metrics_mm turns them into hd, hd95 and assd."""
-        case = self._seg_case("seg_surface_mm", logits, label, task, fuse, True)
-        x, lab, Cc, (D, H, W), mode, fcode, thresh = case
-        wd, wh, ww = self._axis_weights("seg_surface_mm", spacing)
-        need = self.lib.effq_surf_mm_ws_bytes(2 * Cc, D, H, W) if D * H * W else 0
-        if need == 0:
-            raise _lib.EffqError(f"seg_surface_mm: {2 * Cc} masks of {D} x {H} x {W} voxels (2^31 - 1 voxels in all at "
-                                 f"most, every extent at most {_lib.EDT_MM_MAX_EXTENT})")
-        counts = torch.empty(Cc, 2, dtype=torch.int64, device=self.device)
-        sq = torch.empty(Cc, 4, dtype=torch.float32, device=self.device)
-        sums = torch.empty(Cc, 2, dtype=torch.float64, device=self.device)
-        ws = self._workspace("surf_mm", need)
-        check(self.lib.effq_seg_surface_mm(_ptr(x), _ptr(lab), Cc, D, H, W, mode, fcode, thresh, wd, wh, ww, _ptr(counts),
-                                           _ptr(sq), _ptr(sums), _ptr(ws), ws.numel(), self.stream), "effq_seg_surface_mm")
-        return counts, sq, sums
-
-    # -- the prep mission (prep.py) ---------------------------------------------------------------------------------
-    def _prep_volumes(self, what: str, x: torch.Tensor, dtype=torch.float32, limit_c: bool = True):
-        """The checked (tensor, C, D, H, W) of a contiguous C x D x H x W device tensor of `dtype`."""
-        if x.dim() != 4 or x.dtype != dtype or x.numel() == 0 or not x.is_contiguous() or self._elsewhere(x):
-            raise _lib.EffqError(f"{what}: needs a contiguous C x D x H x W {dtype} tensor on {self.device}, got "
-                                 f"{tuple(x.shape)} {x.dtype} on {x.device}")
-        Cc, D, H, W = (int(n) for n in x.shape)
-        if (limit_c and Cc > _lib.PREP_MAX_MODALITIES) or x.numel() >= 2 ** 31 or max(D, H, W) > 32767:
-            raise _lib.EffqError(f"{what}: shape {tuple(x.shape)}: at most {_lib.PREP_MAX_MODALITIES} modalities, 2^31 - 1 "
-                                 f"voxels in all and 32767 along an axis")
-        return x, Cc, D, H, W
-
-    @staticmethod
-    def _prep_mask(what: str, mask: str) -> int:
-        if mask not in _lib.PREP_MASKS:
-            raise _lib.EffqError(f"{what}: unknown mask {mask!r} (one of {', '.join(_lib.PREP_MASKS)})")
-        return _lib.PREP_MASKS[mask]
-
-    @staticmethod
-    def _prep_box(what: str, shape, pmin, pmax):
-        lo, hi = tuple(int(v) for v in pmin), tuple(int(v) for v in pmax)
-        if len(lo) != 3 or len(hi) != 3 or not all(0 <= a < b <= n for a, b, n in zip(lo, hi, shape)):
-            raise _lib.EffqError(f"{what}: box {lo} : {hi} does not lie in a grid of {tuple(shape)}")
-        return lo, hi, (C.c_int * 3)(*lo), (C.c_int * 3)(*hi)
-
-    def _prep_stats(self, what: str, v, n: int) -> torch.Tensor:
-        t = torch.as_tensor(v, dtype=torch.float64).reshape(-1).to(self.device)
-        if t.numel() != n:
-            raise _lib.EffqError(f"{what}: {t.numel()} values for {n} modalities")
-        return t
-
-    def prep_window(self, x: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
-        """Clip the float32 tensor `x` to [lo, hi] in place (effq_prep_window: numpy.clip, a NaN stays)."""
-        if x.dtype != torch.float32 or not x.is_contiguous() or self._elsewhere(x) or x.numel() == 0:
-            raise _lib.EffqError(f"prep_window: needs a contiguous float32 tensor on {self.device}")
-        if not float(lo) <= float(hi):
-            raise _lib.EffqError(f"prep_window: bounds {lo}, {hi}")
-        check(self.lib.effq_prep_window(_ptr(x), x.numel(), float(lo), float(hi), self.stream), "effq_prep_window")
-        return x
-
-    def prep_quantiles(self, x: torch.Tensor, qs, mask: str = "nonzero"):
-        """The order statistics around the percentiles `qs` (1 to PREP_QUANTILE_MAX values in [0, 100]) of every
-        modality of x = C x S (or C x D x H x W) float32 over its own mask (effq_prep_quantiles; the rule of prep.py's
-        --prep_window pLO,pHI).  Returns (count int64[C], stats float32[C, len(qs), 2]) on the device: stats[c, r] =
-        sorted[k], sorted[min(k + 1, n - 1)] with k = floor((n - 1) qs[r] / 100); NaN where the mask is empty.
-        prep.percentile_value interpolates between the two."""
-        if x.dim() < 2 or x.dtype != torch.float32 or x.numel() == 0 or not x.is_contiguous() or self._elsewhere(x):
-            raise _lib.EffqError(f"prep_quantiles: needs a contiguous C x S float32 tensor on {self.device}, got "
-                                 f"{tuple(x.shape)} {x.dtype} on {x.device}")
-        Cc = int(x.shape[0])
-        if Cc > _lib.PREP_MAX_MODALITIES or x.numel() >= 2 ** 31:
-            raise _lib.EffqError(f"prep_quantiles: shape {tuple(x.shape)}: at most {_lib.PREP_MAX_MODALITIES} modalities and "
-                                 f"2^31 - 1 voxels in all")
-        mode = self._prep_mask("prep_quantiles", mask)
-        try:
-            q = [float(v) for v in qs]
-        except (TypeError, ValueError):
-            q = []
-        if not 1 <= len(q) <= _lib.PREP_QUANTILE_MAX or not all(0.0 <= v <= 100.0 for v in q):
-            raise _lib.EffqError(f"prep_quantiles: percentiles {qs!r}: needs 1 to {_lib.PREP_QUANTILE_MAX} values in "
-                                 f"[0, 100]")
-        count = torch.empty(Cc, dtype=torch.int64, device=self.device)
-        stats = torch.empty((Cc, len(q), 2), dtype=torch.float32, device=self.device)
-        need = C.c_size_t()
-        check(self.lib.effq_prep_quantile_ws_bytes(C.byref(need)), "effq_prep_quantile_ws_bytes")
-        ws = self._workspace("prep_quantile", need.value)
-        # the percentiles are host doubles, read before the call returns
-        check(self.lib.effq_prep_quantiles(_ptr(x), Cc, x.numel() // Cc, mode, (C.c_double * len(q))(*q), len(q),
-                                           _ptr(count), _ptr(stats), _ptr(ws), ws.numel(), self.stream),
-              "effq_prep_quantiles")
-        return count, stats
-
-    def prep_window_mask(self, x: torch.Tensor, lo: float, hi: float, mask: str = "nonzero") -> torch.Tensor:
-        """Clip the voxels of the float32 tensor `x` (one modality's plane) that lie inside the mask to [lo, hi] in place
-        and leave the others alone (effq_prep_mask_window: a NaN stays; with 'all' it is prep_window)."""
-        if x.dtype != torch.float32 or not x.is_contiguous() or self._elsewhere(x) or x.numel() == 0:
-            raise _lib.EffqError(f"prep_window_mask: needs a contiguous float32 tensor on {self.device}")
-        mode = self._prep_mask("prep_window_mask", mask)
-        if not float(lo) <= float(hi):
-            raise _lib.EffqError(f"prep_window_mask: bounds {lo}, {hi}")
-        check(self.lib.effq_prep_mask_window(_ptr(x), x.numel(), float(lo), float(hi), mode, self.stream),
-              "effq_prep_mask_window")
-        return x
-
-    def prep_resample(self, x: torch.Tensor, factors, out_shape, nearest: bool = False) -> torch.Tensor:
-        """N x D x H x W volumes on a grid of another spacing (effq_prep_resample): `factors` = target spacing / source
-        spacing per axis, `out_shape` the output extents (prep.resample_extent).  float32 volumes are interpolated
-        trilinearly; with `nearest` the volumes are uint8 labels and keep their values."""
-        x, N, D, H, W = self._prep_volumes("prep_resample", x, torch.uint8 if nearest else torch.float32, limit_c=False)
-        f = tuple(float(v) for v in factors)
-        o = tuple(int(v) for v in out_shape)
-        if len(f) != 3 or len(o) != 3 or not all(0.0 < v <= 1e6 for v in f) or min(o) < 1 or max(o) > 32767 or \
-                N * o[0] * o[1] * o[2] >= 2 ** 31:
-            raise _lib.EffqError(f"prep_resample: factors {f}, output extents {o}")
-        y = torch.empty((N,) + o, dtype=x.dtype, device=self.device)
-        check(self.lib.effq_prep_resample(_ptr(x), N, D, H, W, f[0], f[1], f[2],
-                                          _lib.PREP_NEAREST if nearest else _lib.PREP_LINEAR, _ptr(y), o[0], o[1], o[2],
-                                          self.stream), "effq_prep_resample")
-        return y
-
-    def prep_resample_cubic(self, x: torch.Tensor, factors, out_shape, keep_zero: bool = False) -> torch.Tensor:
-        """N x D x H x W float32 volumes on a grid of another spacing by cubic B-spline interpolation
-        (effq_prep_resample_cubic; the rule of prep.py's --prep_interp cubic): `factors` and `out_shape` as in
-        prep_resample.  `keep_zero`: an output voxel whose trilinear footprint in `x` is all exactly 0 is +0.0.  The
-        fp64 coefficients live in a workspace of 8 B per voxel of `x`; `x` is not modified.  A new tensor."""
-        x, N, D, H, W = self._prep_volumes("prep_resample_cubic", x, limit_c=False)
-        f = tuple(float(v) for v in factors)
-        o = tuple(int(v) for v in out_shape)
-        if len(f) != 3 or len(o) != 3 or not all(0.0 < v <= 1e6 for v in f) or min(o) < 1 or max(o) > 32767 or \
-                N * o[0] * o[1] * o[2] >= 2 ** 31:
-            raise _lib.EffqError(f"prep_resample_cubic: factors {f}, output extents {o}")
-        y = torch.empty((N,) + o, dtype=torch.float32, device=self.device)
-        need = C.c_size_t()
-        check(self.lib.effq_prep_cubic_ws_bytes(N, D, H, W, C.byref(need)), "effq_prep_cubic_ws_bytes")
-        ws = self._workspace("prep_cubic", need.value)
-        check(self.lib.effq_prep_resample_cubic(_ptr(x), N, D, H, W, f[0], f[1], f[2], int(bool(keep_zero)), _ptr(y),
-                                                o[0], o[1], o[2], _ptr(ws), ws.numel(), self.stream),
-              "effq_prep_resample_cubic")
-        return y
-
-    def prep_cubic_plan(self, shape, out_shape) -> dict:
-        """How prep_resample_cubic walks N x D x H x W volumes resampled to `out_shape` (effq_prep_cubic_plan; launches
-        nothing): chunk and tile_rows of the W prefilter pass, and per launch ('d', 'h', 'w', 'eval') its work items and
-        how many of them one trip of its grid covers."""
-        n, d, h, w = (int(v) for v in shape)
-        o = tuple(int(v) for v in out_shape)
-        chunk, rows = C.c_int(), C.c_int()
-        items, trip = (C.c_longlong * 4)(), (C.c_longlong * 4)()
-        check(self.lib.effq_prep_cubic_plan(n, d, h, w, o[0], o[1], o[2], C.addressof(chunk), C.addressof(rows),
-                                            C.addressof(items), C.addressof(trip)),
-              "effq_prep_cubic_plan")
-        names = ("d", "h", "w", "eval")
-        return dict(chunk=chunk.value, tile_rows=rows.value, items=dict(zip(names, (int(v) for v in items))),
-                    trip=dict(zip(names, (int(v) for v in trip))))
-
-    def prep_spline_prefilter(self, x: torch.Tensor, passes: str = "dhw", out: Optional[torch.Tensor] = None):
-        """The B-spline coefficients of N x D x H x W float32 volumes as a float64 tensor (effq_prep_spline_prefilter), or
-        some of the passes alone: 'd' reads `x` and writes `out` (a new tensor unless given), 'h' and 'w' filter `out` in
-        place, so without 'd' the caller passes the `out` of an earlier call (`x` gives the shape only)."""
-        x, N, D, H, W = self._prep_volumes("prep_spline_prefilter", x, limit_c=False)
-        mask = sum(_lib.PREP_SPLINE_PASSES.get(c, 8) for c in set(passes))
-        if not 0 < mask <= 7:
-            raise _lib.EffqError(f"prep_spline_prefilter: passes {passes!r}: letters of d, h, w")
-        if out is None:
-            if not mask & 1:
-                raise _lib.EffqError("prep_spline_prefilter: the passes h and w work in place: they need `out`")
-            out = torch.empty(x.shape, dtype=torch.float64, device=self.device)
-        elif out.dtype != torch.float64 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or \
-                self._elsewhere(out):
-            raise _lib.EffqError(f"prep_spline_prefilter: `out` must be a contiguous float64 tensor of {tuple(x.shape)}")
-        check(self.lib.effq_prep_spline_prefilter(_ptr(x), N, D, H, W, mask, _ptr(out), out.numel() * 8, self.stream),
-              "effq_prep_spline_prefilter")
-        return out
-
-    def prep_smooth(self, x: torch.Tensor, sigmas, keep_zero: bool = False) -> torch.Tensor:
-        """The anti-alias filter of --prep_antialias (effq_prep_smooth): N x D x H x W float32 volumes filtered along
-        D, H, W with Gaussians of `sigmas` (voxels; prep.antialias_sigma of the resampling factors), the taps and radii
-        from prep.antialias_taps, edges replicated.  `keep_zero`: a voxel that is exactly 0 in `x` is +0.0 in the result.
-        A new tensor; `x` itself when every radius is 0.  A NaN or an Inf spreads over its stencil."""
-        from . import prep
-        x, N, D, H, W = self._prep_volumes("prep_smooth", x, limit_c=False)
-        s = tuple(float(v) for v in sigmas)
-        if len(s) != 3 or not all(0.0 <= v < float("inf") for v in s):
-            raise _lib.EffqError(f"prep_smooth: sigmas {s}: needs three finite values >= 0 (d, h, w)")
-        taps = [prep.antialias_taps(v) for v in s]
-        radii = [len(t) - 1 for t in taps]
-        if max(radii) > _lib.PREP_SMOOTH_MAX_RADIUS:
-            raise _lib.EffqError(f"prep_smooth: sigmas {s} give the radii {radii}, at most {_lib.PREP_SMOOTH_MAX_RADIUS}")
-        if max(radii) == 0:
-            return x
-        y = torch.empty_like(x)
-        tmp = torch.empty_like(x) if sum(r > 0 for r in radii) > 1 else None
-        # the taps are contiguous float32 host arrays, r + 1 each, read before the call returns
-        check(self.lib.effq_prep_smooth(_ptr(x), N, D, H, W, taps[0].ctypes.data, radii[0], taps[1].ctypes.data, radii[1],
-                                        taps[2].ctypes.data, radii[2], int(bool(keep_zero)), _ptr(y), _ptr(tmp),
-                                        self.stream), "effq_prep_smooth")
-        return y
-
-    def prep_bbox_moments(self, x: torch.Tensor, mask: str = "nonzero"):
-        """Pass 1 over one subject (effq_prep_bbox_moments), x = C x D x H x W float32.  Returns (bbox, count, sum):
-        bbox int32[6] = the least d, h, w and the greatest d, h, w of the union of the modalities' masks (least > greatest
-        when it is empty), count int64[C] and sum float64[C] over each modality's own mask.  mask 'nonzero': x_c != 0;
-        'all': every voxel, the box is the grid."""
-        x, Cc, D, H, W = self._prep_volumes("prep_bbox_moments", x)
-        mode = self._prep_mask("prep_bbox_moments", mask)
-        bbox = torch.empty(6, dtype=torch.int32, device=self.device)
-        count = torch.empty(Cc, dtype=torch.int64, device=self.device)
-        total = torch.empty(Cc, dtype=torch.float64, device=self.device)
-        ws = self._workspace("prep", _lib.PREP_WS_BYTES)
-        check(self.lib.effq_prep_bbox_moments(_ptr(x), Cc, D, H, W, mode, _ptr(bbox), _ptr(count), _ptr(total), _ptr(ws),
-                                              ws.numel(), self.stream), "effq_prep_bbox_moments")
-        return bbox, count, total
-
-    def prep_sqdev(self, x: torch.Tensor, mean, mask: str = "nonzero") -> torch.Tensor:
-        """Pass 2 (effq_prep_sqdev): float64[C] = the sum over each modality's mask of (double(x) - mean[c])^2."""
-        x, Cc, D, H, W = self._prep_volumes("prep_sqdev", x)
-        mode = self._prep_mask("prep_sqdev", mask)
-        mu = self._prep_stats("prep_sqdev", mean, Cc)
-        out = torch.empty(Cc, dtype=torch.float64, device=self.device)
-        ws = self._workspace("prep", _lib.PREP_WS_BYTES)
-        check(self.lib.effq_prep_sqdev(_ptr(x), Cc, D * H * W, mode, _ptr(mu), _ptr(out), _ptr(ws), ws.numel(),
-                                       self.stream), "effq_prep_sqdev")
-        return out
-
-    def prep_standardise_crop(self, x: torch.Tensor, pmin, pmax, mean, std, mask: str = "nonzero") -> torch.Tensor:
-        """Pass 3 (effq_prep_standardise_crop): the box pmin <= (d, h, w) < pmax of every modality as
-        float((double(x) - mean[c]) / std[c]) inside the modality's mask and +0.0 outside it."""
-        x, Cc, D, H, W = self._prep_volumes("prep_standardise_crop", x)
-        mode = self._prep_mask("prep_standardise_crop", mask)
-        lo, hi, clo, chi = self._prep_box("prep_standardise_crop", (D, H, W), pmin, pmax)
-        mu, sd = self._prep_stats("prep_standardise_crop", mean, Cc), self._prep_stats("prep_standardise_crop", std, Cc)
-        y = torch.empty((Cc,) + tuple(b - a for a, b in zip(lo, hi)), dtype=torch.float32, device=self.device)
-        check(self.lib.effq_prep_standardise_crop(_ptr(x), Cc, D, H, W, mode, clo, chi, _ptr(mu), _ptr(sd), _ptr(y),
-                                                  self.stream), "effq_prep_standardise_crop")
-        return y
-
-    def prep_crop_u8(self, x: torch.Tensor, pmin, pmax) -> torch.Tensor:
-        """The box pmin <= (d, h, w) < pmax of C x D x H x W uint8 volumes (effq_prep_crop_u8: the label)."""
-        x, Cc, D, H, W = self._prep_volumes("prep_crop_u8", x, torch.uint8, limit_c=False)
-        lo, hi, clo, chi = self._prep_box("prep_crop_u8", (D, H, W), pmin, pmax)
-        y = torch.empty((Cc,) + tuple(b - a for a, b in zip(lo, hi)), dtype=torch.uint8, device=self.device)
-        check(self.lib.effq_prep_crop_u8(_ptr(x), Cc, D, H, W, clo, chi, _ptr(y), self.stream), "effq_prep_crop_u8")
-        return y
-
-    def prep_union_mask(self, x: torch.Tensor, mask: str = "nonzero") -> torch.Tensor:
-        """D x H x W uint8, 1 where the mask of any modality of x (C x D x H x W) holds (effq_prep_union_mask)."""
-        x, Cc, D, H, W = self._prep_volumes("prep_union_mask", x)
-        mode = self._prep_mask("prep_union_mask", mask)
-        m = torch.empty((D, H, W), dtype=torch.uint8, device=self.device)
-        check(self.lib.effq_prep_union_mask(_ptr(x), Cc, D * H * W, mode, _ptr(m), self.stream), "effq_prep_union_mask")
-        return m
-
-    @staticmethod
-    def _orient_plan(what: str, src_axis, flip):
-        """(ctypes int[3], flip mask) of a plan: `flip` is three truth values, one per output axis."""
-        try:
-            axes, fl = tuple(int(a) for a in src_axis), tuple(bool(f) for f in flip)
-        except (TypeError, ValueError):
-            axes, fl = (), ()
-        if sorted(axes) != [0, 1, 2] or len(fl) != 3:
-            raise _lib.EffqError(f"{what}: src_axis {src_axis!r} must be a permutation of 0, 1, 2 and flip {flip!r} three "
-                                 f"truth values")
-        return axes, (C.c_int * 3)(*axes), sum(1 << p for p in range(3) if fl[p])
-
-    def prep_reorient_variant(self, src_axis, flip, elem_bytes: int) -> int:
-        """The kernel effq_prep_reorient would launch for this plan (effq_prep_reorient_plan): 0 rows, 1 tiled transpose."""
-        _, cax, mask = self._orient_plan("prep_reorient_variant", src_axis, flip)
-        v = C.c_int(-1)
-        check(self.lib.effq_prep_reorient_plan(cax, mask, int(elem_bytes), C.byref(v)), "effq_prep_reorient_plan")
-        return int(v.value)
-
-    def prep_reorient(self, x: torch.Tensor, src_axis, flip) -> torch.Tensor:
-        """N x D x H x W (or D x H x W) float32 or uint8 volumes with their axes permuted and reversed
-        (effq_prep_reorient): output axis p is source axis src_axis[p], reversed iff flip[p]; a new tensor, bit for bit
-        numpy.flip(numpy.transpose(x)).  The tensor must be contiguous in its own storage; a uint8 one may start at any
-        byte of a larger buffer."""
-        if x.dim() not in (3, 4) or x.dtype not in (torch.float32, torch.uint8) or x.numel() == 0 or \
-                not x.is_contiguous() or self._elsewhere(x):
-            raise _lib.EffqError(f"prep_reorient: needs a contiguous [N x] D x H x W float32 or uint8 tensor on "
-                                 f"{self.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
-        axes, cax, mask = self._orient_plan("prep_reorient", src_axis, flip)
-        dims = tuple(int(n) for n in x.shape[-3:])
-        N = int(x.shape[0]) if x.dim() == 4 else 1
-        if x.numel() >= 2 ** 31 or max(dims) > 32767:
-            raise _lib.EffqError(f"prep_reorient: shape {tuple(x.shape)}: 2^31 - 1 voxels in all and 32767 along an axis "
-                                 f"at most")
-        out = tuple(dims[a] for a in axes)
-        y = torch.empty(((N,) if x.dim() == 4 else ()) + out, dtype=x.dtype, device=x.device)
-        check(self.lib.effq_prep_reorient(_ptr(x), N, dims[0], dims[1], dims[2], cax, mask, x.element_size(), _ptr(y),
-                                          self.stream), "effq_prep_reorient")
-        return y
 
 
 _OPS = {}

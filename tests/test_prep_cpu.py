@@ -157,7 +157,7 @@ def ref_resample_nearest(x, factors, out_shape):
 
 
 class NumpyOps:
-    """The prep_* methods of hip_ops.HipOps on host tensors, for the orchestration tests only."""
+    """The prep_* methods of ops_prep.PrepOps (hip_ops.HipOps) on host tensors, for the orchestration tests only."""
     device = torch.device("cpu")
 
     def prep_window(self, x, lo, hi):
