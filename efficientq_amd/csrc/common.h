@@ -30,6 +30,15 @@ void set_error(const char* fmt, ...);
 
 #define EFFQ_LAUNCH_CHECK() EFFQ_HIP(hipGetLastError())
 
+// the caller's workspace against what the entry point needs; the message names the entry point
+#define EFFQ_CHECK_WS(have, need)                                                                          \
+  do {                                                                                                     \
+    if ((have) < (need)) {                                                                                 \
+      effq::set_error("%s: workspace of %zu bytes, needs %zu", __func__, (size_t)(have), (size_t)(need)); \
+      return EFFQ_ERR_WORKSPACE;                                                                           \
+    }                                                                                                      \
+  } while (0)
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -106,7 +115,7 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// 64-lane wave sum of a double (all lanes end with lane 0's total valid).
+// 64-lane wave sum, __shfl_down: ONLY LANE 0 holds the total, lanes 1 to 63 end with partial sums.
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -116,6 +125,52 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// 64-lane wave sum, xor butterfly: every lane ends with the total; the same tree in every lane.
+__device__ __forceinline__ uint32_t wave_sum_all(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_sum_all(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Equal keys of a wave are added once: one key per valid lane, and the lanes that hold the same key as the first lane
+// still to do form a group (ballot, leader, popcount), for at most ROUNDS groups.  Returns what this lane must add at its
+// key: the group's count in the group's leader, 1 in a lane left over after the rounds (more distinct keys than rounds:
+// one add per lane), 0 elsewhere.  Every lane of the wave calls it (the ballots need them all).  group(m, leader) is
+// called once per round with the lane mask of the round's group and whether this lane leads it; false ends the rounds.
+struct WaveMatchEvery {
+  __device__ __forceinline__ bool operator()(unsigned long long, bool) const { return true; }
+};
+template <int ROUNDS, typename F = WaveMatchEvery>
+__device__ __forceinline__ uint32_t wave_match_count(bool valid, uint32_t key, int lane, F group = F{}) {
+  unsigned long long todo = __ballot(valid);
+  uint32_t add = 0;                                       // the leader of a group carries the group's count
+  for (int round = 0; round < ROUNDS && todo; ++round) {
+    const int lead = __ffsll((long long)todo) - 1;
+    const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
+    const unsigned long long m = __ballot(key == k) & todo;
+    if (lane == lead) add = (uint32_t)__popcll(m);
+    todo &= ~m;
+    if (!group(m, lane == lead)) break;
+  }
+  if ((todo >> lane) & 1ull) add = 1;
+  return add;
 }
 
 // ---- DPP reductions over groups of GS lanes (GS a power of two <= 64); every lane of a 16-lane row ends with the

@@ -113,12 +113,6 @@ static FbrWs fbr_carve(void* ws, size_t n) {
   return w;
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(FBR_T) void k_fbr_iter(const float* __restrict__ x, size_t n, FbrWs w,
                                                     const effq_fp_state* __restrict__ st, double lo, double hi,
                                                     double d, int vec_ok) {
@@ -222,7 +216,7 @@ __global__ __launch_bounds__(FBR_T) void k_fbr_iter(const float* __restrict__ x,
   long long acc[8] = {D0, D1, D2, D3, U0, U1, U2, U3};
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
-    acc[s] = wave_sum_i64(acc[s]);
+    acc[s] = wave_sum(acc[s]);
     if (lane == 0) s_red[s][wid] = acc[s];
   }
   __syncthreads();
@@ -341,7 +335,7 @@ __global__ __launch_bounds__(FBR_FT) void k_fbr_finish(FbrWs w, effq_fp_state* s
     }
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
-      a[s] = wave_sum_i64(a[s]);
+      a[s] = wave_sum(a[s]);
       if (lane == 0) s_red[s][wid] = a[s];
     }
     __syncthreads();
@@ -470,7 +464,7 @@ __global__ __launch_bounds__(FBR_FT) void k_fbr_export(FbrWs w, long long* __res
     for (int s = 0; s < 4; ++s) a[s] += w.DZ[g * 4 + s] + w.D[g * 4 + s];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    a[s] = wave_sum_i64(a[s]);
+    a[s] = wave_sum(a[s]);
     if (lane == 0) s_red[s][wid] = a[s];
   }
   __syncthreads();

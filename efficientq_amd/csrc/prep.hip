@@ -47,21 +47,6 @@ __device__ __forceinline__ int wave_max(int v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_xor(double v) {    // xor butterfly: the same tree in every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---- pass 1 ------------------------------------------------------------------------------------------------------------
 struct BoxAcc {
@@ -127,8 +112,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_bbox_moments(const float*
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const double s = wave_sum_xor(sum[c]);
-    const unsigned n = wave_sum_u32(cnt[c]);
+    const double s = wave_sum_all(sum[c]);
+    const unsigned n = wave_sum_all(cnt[c]);
     if (lane == 0) { rs[wave][c] = s; rc[wave][c] = n; }
   }
 #pragma unroll
@@ -170,8 +155,8 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_moments_final(PrepWs ws, 
       s += ws.sum[(size_t)blk * PREP_MAXC + c];
       if (count_out) n += ws.cnt[(size_t)blk * PREP_MAXC + c];
     }
-    s = wave_sum_xor(s);
-    const long long nn = wave_sum_i64(n);
+    s = wave_sum_all(s);
+    const long long nn = wave_sum_all(n);
     if (lane == 0) { rs[wave][c] = s; rc[wave][c] = nn; }
   }
   if (bbox_out) {
@@ -238,7 +223,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_prep_sqdev(const float* __rest
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const double s = wave_sum_xor(sum[c]);
+    const double s = wave_sum_all(sum[c]);
     if (lane == 0) rs[wave][c] = s;
   }
   __syncthreads();

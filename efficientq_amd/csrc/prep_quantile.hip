@@ -75,17 +75,9 @@ __device__ __forceinline__ float pq_value(uint32_t key) {
 
 // adds one to counter `k` of s_hist per valid lane; every lane of the wave calls it (the ballots need them all)
 __device__ __forceinline__ void pq_add(uint32_t* s_hist, bool valid, uint32_t k, int lane) {
-  unsigned long long todo = __ballot(valid);
-  uint32_t add = 0;                                       // the leader of a group carries the group's count
-  for (int round = 0; round < PQ_MATCH_ROUNDS && todo; ++round) {
-    const int lead = __ffsll((long long)todo) - 1;
-    const uint32_t kl = (uint32_t)__builtin_amdgcn_readlane((int)k, lead);
-    const unsigned long long m = __ballot(k == kl) & todo;
-    if (lane == lead) add = (uint32_t)__popcll(m);
-    todo &= ~m;
-    if (__popcll(m) < PQ_MATCH_MIN) break;                // the digits are spread (mantissa bits): ballots do not pay
-  }
-  if ((todo >> lane) & 1ull) add = 1;                     // counters left uncombined: one add per voxel
+  // a small group ends the rounds: the digits are spread (mantissa bits), ballots do not pay
+  const uint32_t add = wave_match_count<PQ_MATCH_ROUNDS>(
+      valid, k, lane, [](unsigned long long m, bool) { return __popcll(m) >= PQ_MATCH_MIN; });
   if (add) atomicAdd(&s_hist[k], add);
 }
 
@@ -184,10 +176,7 @@ __global__ __launch_bounds__(PREP_THREADS) void k_pq_select(PqWs ws, int C, int 
   const int T = 2 * R;
   uint32_t n, prefix[PQ_TARGETS], rank[PQ_TARGETS], slot[PQ_TARGETS];
   if (pass == 0) {
-    uint32_t s = hist[4 * lane] + hist[4 * lane + 1] + hist[4 * lane + 2] + hist[4 * lane + 3];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    n = s;
+    n = wave_sum_all(hist[4 * lane] + hist[4 * lane + 1] + hist[4 * lane + 2] + hist[4 * lane + 3]);
 #pragma unroll
     for (int t = 0; t < PQ_TARGETS; ++t) {
       uint32_t k = 0;

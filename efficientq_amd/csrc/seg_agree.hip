@@ -86,12 +86,6 @@ __device__ __forceinline__ uint32_t agree_voxel(const float* q, const float* f, 
   return x;
 }
 
-__device__ __forceinline__ uint32_t agree_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int MODE, int C>
 __global__ __launch_bounds__(AGREE_THREADS) void k_seg_agreement(AgreeParams p) {
   AgreeAcc<C> a;
@@ -137,16 +131,17 @@ __global__ __launch_bounds__(AGREE_THREADS) void k_seg_agreement(AgreeParams p) 
 #pragma unroll
   for (int k = 0; k < 4 * C; ++k) {
     double v = a.st[k];
+    if ((k & 3) == 2) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double w = __shfl_xor(v, o, 64);
-      v = (k & 3) == 2 ? fmax(v, w) : v + w;      // xor butterfly: the same tree in every lane
+      for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));      // the tree of wave_sum_all
+    } else {
+      v = wave_sum_all(v);
     }
     if (lane == 0) rs[wave][k] = v;
   }
 #pragma unroll
   for (int k = 0; k < 3 * C + 1; ++k) {
-    const uint32_t s = agree_wave_sum(a.cnt[k]);
+    const uint32_t s = wave_sum_all(a.cnt[k]);
     if (lane == 0) rc[wave][k] = s;
   }
   __syncthreads();

@@ -27,12 +27,6 @@ struct TallyParams {
   float thresh;
 };
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // C classes known at compile time: every per-class loop unrolls and each thread keeps 3 C counters
 template <int MODE, int VEC, int C>
 __global__ __launch_bounds__(TALLY_THREADS) void k_seg_tallies(TallyParams p) {
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_seg_tallies(TallyParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int q = 0; q < 3 * C; ++q) {
-    const uint32_t s = wave_sum(cnt[q]);
+    const uint32_t s = wave_sum_all(cnt[q]);
     if (lane == 0) red[wave][q] = s;
   }
   __syncthreads();
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(TALLY_THREADS) void k_label_tallies(LabelTallyParam
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int q = 0; q < 3 * C; ++q) {
-    const uint32_t s = wave_sum(cnt[q]);
+    const uint32_t s = wave_sum_all(cnt[q]);
     if (lane == 0) red[wave][q] = s;
   }
   __syncthreads();
@@ -356,10 +350,7 @@ int effq_label_tallies(const uint8_t* pred, const uint8_t* truth, int truth_plan
                        const uint16_t* lut, long long* counts, void* ws, size_t ws_bytes, void* stream) {
   EFFQ_CHECK_ARG(pred && truth && lut && counts && ws && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
   EFFQ_CHECK_ARG(S > 0 && S < (1ll << 40));            // a workgroup's partial counts are 32-bit
-  if (ws_bytes < effq_label_tallies_ws_bytes()) {
-    set_error("effq_label_tallies: workspace of %zu bytes, needs %zu", ws_bytes, effq_label_tallies_ws_bytes());
-    return EFFQ_ERR_WORKSPACE;
-  }
+  EFFQ_CHECK_WS(ws_bytes, effq_label_tallies_ws_bytes());
   LabelLut l;
   for (int v = 0; v < 256; ++v) l.v[v] = (uint16_t)(lut[v] & ((1u << C) - 1u));
   LabelTallyParams p;

@@ -108,7 +108,9 @@ __device__ __forceinline__ float sweep_score(const float* v, int c, int fuse) {
   }
 }
 
-// adds one key per valid lane to the LDS counters; every lane of the wave calls it (the ballots need them all)
+// adds one key per valid lane to the LDS counters; every lane of the wave calls it (the ballots need them all).
+// This is wave_match_count (common.h) written out: through the helper k_seg_sweep gets another register allocation, and
+// two of six timed cases were slower than the previous build by more than its spread (profiles/seg_cc_split_ab.txt).
 __device__ __forceinline__ void sweep_add(uint32_t* s_hist, bool valid, uint32_t key, int lane) {
   unsigned long long todo = __ballot(valid);
   uint32_t add = 0;                                       // the leader of a group carries the group's count
