@@ -208,6 +208,8 @@ SIGNATURES = {
     "effq_cc_table_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "effq_cc_table": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "effq_seg_lesion_table": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "effq_seg_lesion_match_ws_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "effq_seg_lesion_match": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_label_clean_ws_bytes": (_SZ, [_I, _I, _I]),
     "effq_label_clean": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_label_post_ws_bytes": (_SZ, [_I, _I, _I, _I]),
@@ -256,6 +258,8 @@ LESION_CONNECTIVITY = 26
 CC_TABLE_CHUNK = 2048
 # rows per plane that cc_table / seg_lesion_table ask for first; a plane with more components costs one more call
 LESION_TABLE_ROWS = 4096
+# pairs per class that ops_match.seg_lesion_match asks for first; a class with more is asked again with twice as many
+LESION_PAIR_ROWS = 4096
 # include/effq_hip.h: the rules of effq_label_clean (--post) and how many one call takes
 LABEL_CLEAN_MAX_RULES = 8
 LABEL_CLEAN_OPS = {"largest": 0, "min": 1}

@@ -328,6 +328,8 @@ def do_ptq(args, model_cube, data_cube, tester, snap_dir):
         cc['is_surf'] = True
     if getattr(args, 'lesion_table', False):
         cc['is_table'] = True
+    if getattr(args, 'lesion_match', False):
+        cc['is_match'] = True
     if args.test_fp:
         tester.test_as_is(folder='fp', is_save_nii=args.save_nii, **cc)
 

@@ -78,6 +78,10 @@ def build_parser():
     p.add_argument('--surf_dist', action='store_true', help='surface distances hd, hd95, assd (voxel units)')
     p.add_argument('--lesion_table', action='store_true',
                    help='one row per lesion (first voxel, size, overlap) in <snap>/{fp,ptq}/lesions.csv')
+    p.add_argument('--lesion_match', action='store_true',
+                   help='ptq: match label lesions and predicted lesions one to one at IoU > 0.5: lesion F1, panoptic '
+                        'quality and lesion-wise Dice in <snap>/{fp,ptq}/lesion_match.csv, the overlapping pairs in '
+                        'lesion_pairs.csv; refused combinations are named by match_switches')
     p.add_argument('--vs_fp', action='store_true',
                    help='validate the calibrated network against the FP network: <snap>/ptq/agreement.csv')
     p.add_argument('--unlabelled', action='store_true',
@@ -219,6 +223,25 @@ def thr_switches(args, mission=None):
             raise SystemExit(f'--thresh {given}: without --multi_label the classes are decided by argmax (class-id mode), '
                              f'which has no threshold: it needs --multi_label')
     return sweep, thresh
+
+
+def match_switches(args, mission=None):
+    """Whether --lesion_match (or the YAML key `lesion_match`) is set; the missions and combinations it cannot serve
+    are refused by name (SystemExit), host only."""
+    mission = mission or getattr(args, 'mission', None)
+    if not getattr(args, 'lesion_match', False):
+        return False
+    if mission in ('prep', 'predict'):
+        raise SystemExit(f'--lesion_match matches the lesions of a validation against labels: the {mission} mission '
+                         f'validates nothing, drop --lesion_match')
+    for switch in ('unlabelled', 'synthetic'):
+        if getattr(args, switch, False):
+            raise SystemExit(f'--lesion_match --{switch}: predicted lesions are matched to labelled ones, and there are '
+                             f'no labels: drop --lesion_match')
+    if getattr(args, 'no_test', False):
+        raise SystemExit('--lesion_match --no_test: the matching belongs to the validation that --no_test skips: drop '
+                         'one of them')
+    return True
 
 
 def prob_switches(args, mission=None):
@@ -410,7 +433,7 @@ TINY_NET = dict(task='lits', model='UResQ', nMod=1, nClass=3, multi_label=None, 
 
 def make_args(net: dict, qlvl_w: int, qlvl_a: int, **over):
     base = dict(pretrain=None, resume=None, device=0, round='1', suffix='', config=None, test_fp=False,
-                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, vs_fp=False, unlabelled=False, src_geom=False, spacing=None, post=None, post_conn=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
+                no_test=True, save_nii=False, is_cc=False, surf_dist=False, lesion_table=False, lesion_match=False, vs_fp=False, unlabelled=False, src_geom=False, spacing=None, post=None, post_conn=None, bin_label=None, lwq_dataid=0, lwq_batchsz=1, lwq_patchsz=None,
                 lwq_verbose=False, qlvl_w=qlvl_w, qlvl_a=qlvl_a)
     base.update(net)
     base.update(over)

@@ -19,27 +19,10 @@ namespace effq {
 //
 // Integer adds only: equal inputs give equal bits.  A workgroup reads and writes the label words of its own chunk only
 // (rank), and the accumulation runs in a launch of its own after it.
-constexpr int CC_CHUNK = EFFQ_CC_TABLE_CHUNK;
 constexpr int CC_CHUNK_ITERS = CC_CHUNK / CC_THREADS;  // ballots per wave: a wave owns CC_CHUNK / CC_WAVES voxels in a row
 constexpr int CC_SLOTS = 256;                          // accum: rows a workgroup keeps in LDS (direct-mapped)
 constexpr int CC_MATCH_ROUNDS = 4;                     // accum: distinct rows of a wave that are combined by ballot
 static_assert(CC_CHUNK % CC_THREADS == 0, "a chunk is a whole number of ballots per wave");
-
-struct CcTableWs {
-  CcWs cc;
-  uint32_t* chunks;    // (P, nchunks)
-  int nchunks;
-  size_t bytes;
-};
-
-static CcTableWs cc_table_ws(void* ws, int P, size_t S) {
-  CcTableWs r;
-  r.cc = cc_ws(ws, P, S);
-  r.nchunks = (int)((S + CC_CHUNK - 1) / CC_CHUNK);
-  r.chunks = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + r.cc.bytes);
-  r.bytes = r.cc.bytes + align16((size_t)P * r.nchunks * sizeof(uint32_t));
-  return r;
-}
 
 // WRITE false: chunks (P, gridDim.x) = the roots of each chunk.  WRITE true: chunks holds the exclusive scan; the roots
 // get their rows and their negative label words.  rows (P, max_rows, stride) int32.
@@ -141,7 +124,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_accum(const int* __restrict__
     if (i < S) {
       const int l = L[i];
       if (l != 0) {
-        r = l < 0 ? -l - 1 : -L[l - 1] - 1;
+        r = cc_row(L, l);
         if (r >= max_rows) r = -1;
         if (bits && r >= 0) {
           const uint32_t b = bits[i];
@@ -183,8 +166,8 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_accum(const int* __restrict__
 }
 
 // the four launches after cc_run; bits null: sizes only
-static int cc_table_run(const CcTableWs& t, const uint16_t* bits, int C, int P, int S, int max_rows, int stride,
-                        int32_t* rows, long long* nrows, hipStream_t st) {
+int cc_table_run(const CcTableWs& t, const uint16_t* bits, int C, int P, int S, int max_rows, int stride, int32_t* rows,
+                 long long* nrows, hipStream_t st) {
   const dim3 b(CC_THREADS), gc(t.nchunks, P);
   hipLaunchKernelGGL(k_cc_rank<false>, gc, b, 0, st, t.cc.labels, S, t.chunks, max_rows, stride, rows);
   EFFQ_LAUNCH_CHECK();

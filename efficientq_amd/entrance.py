@@ -12,6 +12,10 @@ the calibrated network on the val split (evaluate.validate_seg), writing ``<snap
 ``--surf_dist`` adds the surface distances ``hd, hd95, assd`` (voxel units) after them;
 ``--lesion_table`` writes ``<snap>/{fp,ptq}/lesions.csv``, one row per label lesion and per predicted lesion (first
 voxel, size, overlap; ``vol_mm3`` with ``--src_geom`` / ``--spacing``), and prints the detected lesions per size bin;
+``--lesion_match`` matches label lesions and predicted lesions one to one at IoU > 0.5 from the overlap of every pair of
+them (effq_seg_lesion_match): ``<snap>/{fp,ptq}/lesion_match.csv`` (per subject and class ``tp_l, fp_l, fn_l, f1_l, sq,
+pq, lw_dsc, groups``) and ``lesion_pairs.csv`` (every pair of overlapping lesions with its overlap and IoU), with
+``--lesion_table`` also the columns ``match, best_iou, partners`` of ``lesions.csv``; it needs labels and a validation;
 ``--src_geom`` reads every val subject's source image header (``data_dir/sn_fn.txt``, data.py): the distances become
 ``hd_mm, hd95_mm, assd_mm`` in millimetres and the val maps are written on the source grid with the source's geometry;
 ``--spacing d,h,w`` gives the distances in millimetres from one spacing for all subjects, without any file.
@@ -94,7 +98,8 @@ class _ValidationTester(_SnapshotWriter):
     """The reference's PTQTester on labelled data: test_as_is validates on the val split (rank 0 only) and writes
     <root>/<folder>/metrics.csv, with is_save_nii also every val subject's predicted map as
     <root>/<folder>/val/<subject>.nii.gz (trainer.validate_final), with is_cc also the lesion-level columns, with is_surf also the
-    surface distances, with is_table also <root>/<folder>/lesions.csv, with fp_model (--vs_fp) also
+    surface distances, with is_table also <root>/<folder>/lesions.csv, with is_match also lesion_match.csv and
+    lesion_pairs.csv there, with fp_model (--vs_fp) also
     <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
     labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written.
     With sweep (--thr_sweep) also <root>/<folder>/threshold.csv and threshold_curve.csv (_sweep)."""
@@ -119,7 +124,7 @@ class _ValidationTester(_SnapshotWriter):
         return {}
 
     def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False, is_table=False,
-                   fp_model=None):
+                   fp_model=None, is_match=False):
         if self.rank != 0:
             return
         if self.cube.valloader is None:
@@ -141,6 +146,7 @@ class _ValidationTester(_SnapshotWriter):
                                 if (self.blend, self.flips) != ('uniform', (0,)) else {}),
                              **({'post': self.post, 'post_conn': self.post_conn} if self.post else {}),
                              **({'sweep': True} if self.sweep and labelled else {}),
+                             **({'lesion_match': True} if is_match and labelled else {}),
                              **self._geometry(is_save_nii, is_surf, is_table))
         os.makedirs(out, exist_ok=True)
         if fp_model is not None:
@@ -152,6 +158,10 @@ class _ValidationTester(_SnapshotWriter):
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         if is_table:
             E.write_lesions_csv(os.path.join(out, 'lesions.csv'), res)
+        if is_match:
+            from . import lesion_match as LM
+            LM.write_lesion_match_csv(os.path.join(out, 'lesion_match.csv'), res)
+            LM.write_lesion_pairs_csv(os.path.join(out, 'lesion_pairs.csv'), res)
         means = E.metric_means(res)
         print(f'[entrance] {folder}: {len(res)} val cases in {time.time() - t0:.2f}s, per-class means:')
         tot = E.lesion_totals(res) if is_cc else None
@@ -170,6 +180,12 @@ class _ValidationTester(_SnapshotWriter):
             print(f'[entrance] {folder}: label lesions detected / all, by size in voxels:')
             for c in range(bins.shape[0]):
                 print(f'  class {c}: ' + ', '.join(f'{n}: {int(k[1])} / {int(k[0])}' for n, k in zip(names, bins[c])))
+        if is_match:
+            print(f'[entrance] {folder}: lesions matched one to one at IoU > 0.5, per class the mean f1_l, pq and lw_dsc '
+                  f'and the pooled tp_l / fp_l / fn_l:')
+            for c, m in enumerate(LM.match_summary(res)):
+                print(f'  class {c}: f1_l = {m["f1_l"]:.4f}, pq = {m["pq"]:.4f}, lw_dsc = {m["lw_dsc"]:.4f}, '
+                      f'tp_l / fp_l / fn_l = {m["tp_l"]} / {m["fp_l"]} / {m["fn_l"]}')
         if self.post:
             E.write_metrics_post_csv(os.path.join(out, 'metrics_post.csv'), res)
             after = E.post_means(res)
@@ -248,6 +264,7 @@ def check_switches(args):
     check_post(args)
     Cf.thr_switches(args)
     Cf.prob_switches(args)
+    Cf.match_switches(args)
     if not getattr(args, 'unlabelled', False):
         return
     if not getattr(args, 'vs_fp', False):
@@ -288,11 +305,13 @@ def main(argv=None):
         check_post(args)
         Cf.thr_switches(args)
         Cf.prob_switches(args)
+        Cf.match_switches(args)
         from . import prep
         prep.run(args)
         return
     if args.mission == 'predict':
         Cf.thr_switches(args)
+        Cf.match_switches(args)
         from . import predict
         predict.run(args)
         return
@@ -314,6 +333,9 @@ def main(argv=None):
         cleaning = dict(cleaning, sweep=True)
         print('[entrance] --thr_sweep: every labelled validation also sweeps the decision threshold (threshold.csv, '
               'threshold_curve.csv)')
+    if Cf.match_switches(args):
+        print('[entrance] --lesion_match: every labelled validation also matches its lesions one to one '
+              '(lesion_match.csv, lesion_pairs.csv)')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:

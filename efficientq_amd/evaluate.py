@@ -391,7 +391,7 @@ def stitched_window_logits(ops, nets, vol: torch.Tensor, patch, overlap, window_
 def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=None, fuse=None, names=None,
                  save_dir=None, label_dtype=np.uint16, multi_label=None, lesions=False, surface=False,
                  geometry=None, lesion_table=False, fp_model=None, blend="uniform", flips=(0,), post=None, post_conn=26,
-                 sweep=False):
+                 sweep=False, lesion_match=False):
     """Validate `model` (already on its HIP device, in the mode to be measured) on every case of `loader`
     ((image N x C x D x H x W, label) batches; label = class ids N x D x H x W for lits, N x C x D x H x W 0/1 for
     brats): the case's windows gathered into batches of `window_batch` (effq_window_gather), the network run on each
@@ -445,7 +445,11 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
     planes of --multi_label brats are read back from the map only when `fuse` nests them: both are a RuntimeError.
     sweep: each labelled case's dict also carries "sweep", the C x 2 x 4096 int64 histogram of the case's scores by truth
     on the host (effq_seg_sweep, one more call per case after the tallies), and "sweep_edges", the 4096 fp32 edges of its
-    bins (hip_ops.sweep_edges): what sweep_summary, write_threshold_csv and write_threshold_curve_csv take."""
+    bins (hip_ops.sweep_edges): what sweep_summary, write_threshold_csv and write_threshold_curve_csv take.
+    lesion_match: each labelled case's dict also carries "lesion_match", per class the dict of lesion_match.match_class
+    (one-to-one matching of label and predicted lesions at IoU > 0.5, lesion F1, panoptic quality, lesion-wise Dice, the
+    pairs of overlapping lesions) - from ops_match.seg_lesion_match (effq_seg_lesion_match), which takes the place of the
+    calls of lesions / lesion_table for the case and returns their results bit for bit with the pairs."""
     from .hip_ops import get_ops
     if task not in ("lits", "brats"):
         raise RuntimeError(f"Unknown task {task}")
@@ -514,13 +518,20 @@ def validate_seg(model, loader, task: str, patch_size, overlap, window_batch=Non
                         if kind not in sweep_edges:
                             sweep_edges[kind] = ops.sweep_edges(kind)
                         res["sweep_edges"] = sweep_edges[kind]
-                    if lesion_table:
-                        cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], kind, fz)
+                    if lesion_table or lesion_match:
+                        if lesion_match:
+                            from . import lesion_match as LM
+                            from .ops_match import seg_lesion_match
+                            cnt, _, rows, pairs = seg_lesion_match(ops, stitched[n], lab[n], kind, fz)
+                            res["lesion_match"] = LM.case_scores(rows, pairs)
+                        else:
+                            cnt, _, rows = ops.seg_lesion_table(stitched[n], lab[n], kind, fz)
                         ncls = int(cnt.shape[0])
-                        res["lesion_table"] = [(_lesion_rows(rows[ncls + c], vol.shape[-3:]),
-                                                _lesion_rows(rows[c], vol.shape[-3:])) for c in range(ncls)]
-                        if spacing is not None:
-                            res["spacing"] = spacing
+                        if lesion_table:
+                            res["lesion_table"] = [(_lesion_rows(rows[ncls + c], vol.shape[-3:]),
+                                                    _lesion_rows(rows[c], vol.shape[-3:])) for c in range(ncls)]
+                            if spacing is not None:
+                                res["spacing"] = spacing
                         if lesions:
                             res["lesions"] = cnt
                     elif lesions:
@@ -762,23 +773,34 @@ def write_lesions_csv(path: str, results) -> None:
     """One row per lesion of results that carry "lesion_table" (validate_seg(..., lesion_table=True)): subject, class,
     kind (label | pred), lesion (1-based, in raster order of the first voxel: scipy.ndimage.label's number), d, h, w of
     the first voxel, size in voxels, overlap; per subject and class the label lesions first.  When the results carry a
-    "spacing" a last column vol_mm3 = size x voxel volume; a file never mixes rows with and without it."""
+    "spacing" a last column vol_mm3 = size x voxel volume; a file never mixes rows with and without it.  When they carry
+    "lesion_match" (validate_seg(..., lesion_match=True)) three more columns after all others: match (the 1-based number
+    of the lesion of the other kind matched one to one at IoU > 0.5, or 0), best_iou (the largest IoU with any lesion of
+    the other kind, or 0) and partners (how many of them it shares voxels with); again a file never mixes the two."""
     import csv
     res = [r for r in results if "lesion_table" in r]
     mm = {"spacing" in r for r in res}
     if len(mm) > 1:
         raise RuntimeError("write_lesions_csv: cases with and without a spacing in one file")
     mm = mm == {True}
+    lm = {"lesion_match" in r for r in res}
+    if len(lm) > 1:
+        raise RuntimeError("write_lesions_csv: cases with and without a lesion matching in one file")
+    lm = lm == {True}
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(("subject", "class", "kind", "lesion") + LESION_TABLE_COLUMNS + (("vol_mm3",) if mm else ()))
+        wr.writerow(("subject", "class", "kind", "lesion") + LESION_TABLE_COLUMNS + (("vol_mm3",) if mm else ()) +
+                    (("match", "best_iou", "partners") if lm else ()))
         for r in res:
             vox = float(np.prod([float(v) for v in r["spacing"]])) if mm else None
             for c, pair in enumerate(r["lesion_table"]):
                 for kind, rows in zip(("label", "pred"), pair):
+                    side = r["lesion_match"][c][kind] if lm else None
                     for k, row in enumerate(np.asarray(rows, dtype=np.int64).reshape(-1, 5)):
                         wr.writerow([r["name"], c, kind, k + 1] + [int(v) for v in row] +
-                                    (["%.7g" % (int(row[3]) * vox)] if mm else []))
+                                    (["%.7g" % (int(row[3]) * vox)] if mm else []) +
+                                    ([int(side["match"][k]), "%.7g" % float(side["best_iou"][k]),
+                                      int(side["partners"][k])] if lm else []))
 
 
 def lesion_size_summary(results) -> np.ndarray:

@@ -795,6 +795,35 @@ int effq_seg_lesion_table(const float* logits, const uint8_t* label, int C, int 
                           float thresh, int connectivity, int max_rows, long long* counts, long long* nrows,
                           int32_t* rows, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the overlap of every (label lesion, predicted lesion) pair (validate_seg(..., lesion_match=True): one-to-one
+ * matching, lesion F1, panoptic quality and lesion-wise Dice need it; the overlap column of the lesion table says how
+ * many voxels of a lesion the other mask holds, not which lesion of it).  The launches of effq_seg_lesion_table and
+ * four more: the hash tables are emptied, one streaming pass per class counts the voxels of every pair (equal pairs of a
+ * wave combined, the sums of a workgroup kept in LDS, the rest into an open-addressing table of the class by a 64-bit
+ * compare-and-swap and an add), the occupied slots are gathered and then put in order by their rank.  All on `stream`,
+ * no read by the host, no workgroup that waits for another; integer adds only and an order that is the keys' own, so
+ * equal inputs give equal bits.
+ *
+ * effq_seg_lesion_match: arguments as effq_seg_lesion_table, and max_pairs -> counts, nrows, rows: bit for bit
+ *   effq_seg_lesion_table's (the same launches, the same truncation); npairs (C) int64 and pairs (C, max_pairs, 3)
+ *   int32 = label row, predicted row, the voxels both components hold: one record per pair of a component of the label
+ *   mask and a component of the predicted mask of class c that share a voxel.  A row is the 0-based row of the component
+ *   in its plane of effq_seg_lesion_table (scipy.ndimage.label's number - 1), valid whether or not it fits max_rows:
+ *   the pairs do not depend on max_rows.  Order: ascending in (label row, predicted row).
+ * A class with more than max_pairs pairs: npairs[c] = -1 and its records are unspecified; nothing is written past the
+ *   table and the other classes are what they would be.  Ask again with a larger max_pairs.
+ * ws: effq_seg_lesion_match_ws_bytes(C, D, H, W, max_rows, max_pairs) bytes: effq_cc_table_ws_bytes(2 C, ...) and per
+ *   class 16 B of words, 12 B for each of the T slots of the table (T = the least power of two >= 2 max_pairs, 256 or
+ *   more) and 12 B for each of the max_pairs gathered records: 3 x (16 + 12 x 8192 + 12 x 4096) B = 442 KB more for a
+ *   BraTS case at max_pairs 4096.  It may hold anything on entry.  0 for what the call refuses.
+ * Bad arguments (those of effq_seg_lesion_table, max_pairs <= 0, C * max_pairs * 3 >= 2^31) return EFFQ_ERR_ARG, a
+ *   short workspace EFFQ_ERR_WORKSPACE; both launch nothing and leave the outputs as they were. */
+size_t effq_seg_lesion_match_ws_bytes(int C, int D, int H, int W, int max_rows, int max_pairs);
+int effq_seg_lesion_match(const float* logits, const uint8_t* label, int C, int D, int H, int W, int mode, int fuse,
+                          float thresh, int connectivity, int max_rows, int max_pairs, long long* counts,
+                          long long* nrows, int32_t* rows, long long* npairs, int32_t* pairs, void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* ---- cleaning a predicted label map by connected components (--post: keep the largest liver, relabel small specks; the
  * reference's merge_label_brats_inference, utils/misc.py, is the need, not the specification).  in (D, H, W) uint8 label
  * values -> out (D, H, W), which may be `in` itself.  R rules, 1 <= R <= EFFQ_LABEL_CLEAN_MAX_RULES, apply in order, each
