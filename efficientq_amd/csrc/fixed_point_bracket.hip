@@ -42,7 +42,9 @@ constexpr int FBR_FT = 1024;                 // threads of the finish kernel: on
 constexpr size_t FBR_MIN_PER = 8192;      // values per workgroup below which fewer workgroups are used
 enum { FBR_X = 0, FBR_A = 1, FBR_B = 2, FBR_Z = 3 };      // sources: the tensor, the two working lists, the base list
 
-// header of the workspace; the first sixteen 8-byte words are read from Python (tests, diagnostics)
+// header of the workspace, read from Python as 8-byte words: ops.fp_bracket_diagnostics picks some of them, and
+// tests/test_fp_bracket_classes_gpu.py (class Header) reads the WHOLE layout by word index, the planning and import
+// fields (mono .. ext) included - whoever reorders or inserts a field changes both readers with it
 struct FbrHdr {
   double blo, bhi;              // bracket under which the current source list and the decided tallies are valid
   double nlo, nhi;              // plan of the next pass: narrowed bracket
@@ -72,7 +74,8 @@ static_assert(sizeof(FbrHdr) <= 256, "FbrHdr layout");
 struct FbrWs {
   FbrHdr* hdr;
   unsigned* segcnt;          // [3][FBR_MAXG]  length of segment w of list A / B / Z
-  long long* D;              // [FBR_MAXG][4]  decided since the base: sum l*u, sum l, sum l^2, sum u
+  long long* D;              // [FBR_MAXG][4]  decided since the base: sum l*u, sum l, sum l^2, sum u.  Restarted by every
+                             //                pass over the base, so STALE from an escape until that pass (hdr->src == base)
   long long* U;              // [FBR_MAXG][4]  the same sums over the undecided values of the last pass
   long long* DZ;             // [FBR_MAXG][4]  decided between the tensor and the base list
   float* L[3];               // A, B, Z: [G * per] each
@@ -451,6 +454,8 @@ __global__ __launch_bounds__(FBR_T) void k_fbr_init(FbrWs w, effq_fp_state* st, 
 // effq_fp_bracket_import sets up a fit over the gathered list with the summed tallies as its constant part, which every
 // rank then runs to the end ON ITS OWN - same integers, same order, same kernels: bit-identical iterates on every rank, no
 // further collective.  The imported fit is valid while its iterates stay inside [blo, bhi] (state.done = 4 otherwise).
+// The tallies handed out are always those of the bracket and the list handed out with them: right after an escape (source
+// = the base again, bracket = the base's) they are DZ alone, not the D of the bracket that was left.
 // out: [0..3] tallies, [4] list length (-1: no list yet, -2: horizon bracket, see below), [5], [6] bit patterns of the
 // bracket, [8 .. 8 + G] prefix offsets of the list segments (scratch for k_fbr_export_copy)
 __global__ __launch_bounds__(FBR_FT) void k_fbr_export(FbrWs w, long long* __restrict__ out) {
@@ -458,10 +463,15 @@ __global__ __launch_bounds__(FBR_FT) void k_fbr_export(FbrWs w, long long* __res
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const FbrHdr h = *w.hdr;
   const int G = (int)h.G;
+  // D counts only while the source is a working list.  With the base as the source nothing is decided since the base:
+  // either a pass over it has just restarted D (at zero, unless it narrowed - and then the source is its working list),
+  // or an escape / a rebase has sent the NEXT pass back to the base and D still holds the tallies of the bracket that
+  // was left.  Handing those out next to the whole base list would count their values twice on the receiving side.
+  const bool d_valid = h.src != h.base;
   long long a[4] = {0, 0, 0, 0};
   for (int g = tid; g < G; g += FBR_FT)
 #pragma unroll
-    for (int s = 0; s < 4; ++s) a[s] += w.DZ[g * 4 + s] + w.D[g * 4 + s];
+    for (int s = 0; s < 4; ++s) a[s] += w.DZ[g * 4 + s] + (d_valid ? w.D[g * 4 + s] : 0ll);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     a[s] = wave_sum(a[s]);
@@ -481,7 +491,10 @@ __global__ __launch_bounds__(FBR_FT) void k_fbr_export(FbrWs w, long long* __res
     }
     out[8 + G] = run;
     // -1: no list yet; -2: the list belongs to a HORIZON bracket (many levels: it only reaches as far as the next few
-    // iterations are expected to get, and the iterates leave it by design): not worth exchanging
+    // iterations are expected to get, and the iterates leave it by design): not worth exchanging.  fbr_plan sets
+    // `planned` with the plan, before the narrowing pass has run: right after an escape whose new plan is a horizon again
+    // the answer is -2 although the list at hand is the whole base list under the base's bracket - harmless (one more
+    // all-reduced iteration before the exchange), and what the many-level fits do for most of their length anyway
     out[4] = (h.src == FBR_X) ? -1 : ((h.planned != 0) ? -2 : run);
     out[5] = __double_as_longlong(h.blo);      // the bracket these tallies and this list are valid under: ranks plan on
     out[6] = __double_as_longlong(h.bhi);      // their own shard's density, so their brackets may differ

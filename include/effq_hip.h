@@ -181,7 +181,9 @@ int effq_fixed_point_coop_rec(const float* a, const float* b, float* v_out, size
  *   stats : one iteration pass, state.sums = this rank's [sum b*x, sum b*b]   } with data-parallel ranks the caller
  *   update: scalar update from state.sums + plan of the next pass              } all-reduces state.sums in between
  * ws: effq_fp_bracket_ws_bytes(n) bytes (three lists of n floats + tallies), owned by the fit between init and its end.
- * The first 128 bytes of ws are sixteen 8-byte words of diagnostics (bracket, plan, escapes, narrowings, values read). */
+ * The first 256 bytes of ws are the fit's header as 8-byte words (FbrHdr of fixed_point_bracket.hip): the first sixteen
+ * are diagnostics (bracket, plan, escapes, narrowings, values read), the planning and import state follows; the tests
+ * read all of them by word index. */
 size_t effq_fp_bracket_ws_bytes(size_t n);
 int effq_fp_bracket_init(effq_fp_state* state_dev, const double* abs_sums_dev, size_t n, int levels, int list_first,
                          void* ws, size_t ws_bytes, void* stream);
