@@ -72,6 +72,7 @@ from . import calibrate as K
 from . import config as Cf
 from . import data as D
 from . import evaluate as E
+from . import reports as R
 from . import synth
 
 
@@ -102,7 +103,8 @@ class _ValidationTester(_SnapshotWriter):
     lesion_pairs.csv there, with fp_model (--vs_fp) also
     <root>/<folder>/agreement.csv and, with is_save_nii, <root>/<folder>/val_vs_fp/<subject>.nii.gz.  On a cube without
     labels (--unlabelled, --synthetic --vs_fp) only the validation against fp_model runs and metrics.csv is not written.
-    With sweep (--thr_sweep) also <root>/<folder>/threshold.csv and threshold_curve.csv (_sweep)."""
+    With sweep (--thr_sweep) also <root>/<folder>/threshold.csv and threshold_curve.csv.  What it prints is
+    formatted by reports.py."""
 
     def __init__(self, model, root, data_cube, task, rank=0, blend='uniform', flips=(0,), post=(), post_conn=26,
                  sweep=False):
@@ -117,11 +119,9 @@ class _ValidationTester(_SnapshotWriter):
         lesion volumes and maps), or the one spacing of --spacing (distances and lesion volumes only)."""
         geom = getattr(self.cube, 'geometry', None)
         if geom is not None and (is_save_nii or is_surf or is_table):
-            return {'geometry': geom}
+            return geom
         spacing = getattr(self.cube, 'spacing', None)
-        if spacing is not None and (is_surf or is_table):
-            return {'geometry': spacing}
-        return {}
+        return spacing if spacing is not None and (is_surf or is_table) else None
 
     def test_as_is(self, folder='results', is_save_nii=False, is_cc=False, is_surf=False, is_table=False,
                    fp_model=None, is_match=False):
@@ -139,21 +139,17 @@ class _ValidationTester(_SnapshotWriter):
         res = E.validate_seg(self.model, self.cube.valloader, self.task, self.cube.patch_size, self.cube.overlap,
                              fuse=self.cube.multilabel_fusetype, names=self.cube.val_sn,
                              save_dir=os.path.join(out, 'val') if is_save_nii else None,
-                             multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc,
-                             surface=is_surf, **({'lesion_table': True} if is_table else {}),
-                             **({'fp_model': fp_model} if fp_model is not None else {}),
-                             **({'blend': self.blend, 'flips': self.flips}
-                                if (self.blend, self.flips) != ('uniform', (0,)) else {}),
-                             **({'post': self.post, 'post_conn': self.post_conn} if self.post else {}),
-                             **({'sweep': True} if self.sweep and labelled else {}),
-                             **({'lesion_match': True} if is_match and labelled else {}),
-                             **self._geometry(is_save_nii, is_surf, is_table))
+                             multi_label=getattr(self.cube, 'multi_label', None), lesions=is_cc, surface=is_surf,
+                             geometry=self._geometry(is_save_nii, is_surf, is_table), lesion_table=is_table,
+                             fp_model=fp_model, blend=self.blend, flips=self.flips, post=self.post,
+                             post_conn=self.post_conn, sweep=self.sweep and labelled,
+                             lesion_match=is_match and labelled)
         os.makedirs(out, exist_ok=True)
         if fp_model is not None:
             E.write_agreement_csv(os.path.join(out, 'agreement.csv'), res)
         if not labelled:
             print(f'[entrance] {folder}: {len(res)} unlabelled val cases in {time.time() - t0:.2f}s')
-            self._print_agreement(folder, res)
+            print('\n'.join(R.agreement_lines(folder, res)))
             return
         E.write_metrics_csv(os.path.join(out, 'metrics.csv'), res)
         if is_table:
@@ -162,72 +158,22 @@ class _ValidationTester(_SnapshotWriter):
             from . import lesion_match as LM
             LM.write_lesion_match_csv(os.path.join(out, 'lesion_match.csv'), res)
             LM.write_lesion_pairs_csv(os.path.join(out, 'lesion_pairs.csv'), res)
-        means = E.metric_means(res)
-        print(f'[entrance] {folder}: {len(res)} val cases in {time.time() - t0:.2f}s, per-class means:')
-        tot = E.lesion_totals(res) if is_cc else None
-        surf = E.surface_means(res) if is_surf else None
-        for c in range(len(means['dsc'])):
-            line = f'  class {c}: ' + ', '.join(f'{m} = {float(means[m][c]):.4f}' for m in E.METRICS)
-            if is_cc:
-                line += ', ' + ', '.join(f'{k} = {int(tot[c][j])}' for j, k in enumerate(E.LESION_COLUMNS))
-            if is_surf:
-                mm = ' mm' if res[0].get('surface_unit') == 'mm' else ''
-                line += ', ' + ', '.join(f'{k} = {float(surf[c][j]):.3f}{mm}' for j, k in enumerate(E.SURFACE_COLUMNS))
-            print(line)
+        lines = R.metric_lines(folder, res, time.time() - t0, is_cc, is_surf)
         if is_table:
-            bins = E.lesion_size_summary(res)
-            names = [f'{lo}-{hi}' if hi is not None else f'>= {lo}' for lo, hi in E.LESION_SIZE_BINS]
-            print(f'[entrance] {folder}: label lesions detected / all, by size in voxels:')
-            for c in range(bins.shape[0]):
-                print(f'  class {c}: ' + ', '.join(f'{n}: {int(k[1])} / {int(k[0])}' for n, k in zip(names, bins[c])))
+            lines += R.lesion_size_lines(folder, res)
         if is_match:
-            print(f'[entrance] {folder}: lesions matched one to one at IoU > 0.5, per class the mean f1_l, pq and lw_dsc '
-                  f'and the pooled tp_l / fp_l / fn_l:')
-            for c, m in enumerate(LM.match_summary(res)):
-                print(f'  class {c}: f1_l = {m["f1_l"]:.4f}, pq = {m["pq"]:.4f}, lw_dsc = {m["lw_dsc"]:.4f}, '
-                      f'tp_l / fp_l / fn_l = {m["tp_l"]} / {m["fp_l"]} / {m["fn_l"]}')
+            lines += R.lesion_match_lines(folder, res)
         if self.post:
             E.write_metrics_post_csv(os.path.join(out, 'metrics_post.csv'), res)
-            after = E.post_means(res)
-            changed = [sum(r['post']['changed'][k] for r in res) for k in range(len(self.post))]
-            print(f'[entrance] {folder}: --post {Cf.post_text(self.post, self.post_conn)}: '
-                  f'{" ".join(str(v) for v in changed)} voxels relabelled, per-class mean dsc before -> after:')
-            for c in range(len(means['dsc'])):
-                print(f'  class {c}: {float(means["dsc"][c]):.4f} -> {float(after["dsc"][c]):.4f}')
-        if self.sweep:
-            self._sweep(folder, out, res)
+            lines += R.post_lines(folder, res, Cf.post_text(self.post, self.post_conn), len(self.post))
+        if self.sweep:          # every network swept so far side by side
+            E.write_threshold_csv(os.path.join(out, 'threshold.csv'), res)
+            E.write_threshold_curve_csv(os.path.join(out, 'threshold_curve.csv'), res)
+            self.swept[folder] = R.sweep_means(res)
+            lines += R.sweep_lines(folder, self.swept, bool(getattr(self.cube, 'multi_label', None)))
         if fp_model is not None:
-            self._print_agreement(folder, res)
-
-    def _sweep(self, folder, out, res):
-        """--thr_sweep: threshold.csv and threshold_curve.csv of `folder`, and per class the mean AUC, the pooled best
-        threshold and the pooled Dice at the default threshold and at the best; every network swept so far side by side."""
-        E.write_threshold_csv(os.path.join(out, 'threshold.csv'), res)
-        E.write_threshold_curve_csv(os.path.join(out, 'threshold_curve.csv'), res)
-        per, pooled, _ = E.sweep_results(res)
-        ncls = len(pooled)
-        self.swept[folder] = ([sum(s[c]['auc'] for _, s in per) / len(per) for c in range(ncls)], pooled)
-        sigmoid = bool(getattr(self.cube, 'multi_label', None))
-
-        def said(name, c):
-            auc, pool = self.swept[name]
-            q = pool[c]
-            at = f'{E.logit_prob(q["best_thr"]):.4f} (logit {q["best_thr"]:.9g})' if sigmoid else f'margin {q["best_thr"]:.9g}'
-            return (f'{name.upper()}: AUC {auc[c]:.4f}, Dice {float(q["dsc_default"]):.4f} at '
-                    f'{"0.5" if sigmoid else "argmax"}, {float(q["dsc_best"]):.4f} at {at}')
-        print(f'[entrance] {folder}: --thr_sweep, per class the mean AUC and the pooled Dice at the default and at the '
-              f'best threshold:')
-        for c in range(ncls):
-            print(f'  class {c}: ' + '; '.join(said(name, c) for name in self.swept))
-
-    @staticmethod
-    def _print_agreement(folder, res):
-        m = E.agreement_means(res)
-        print(f'[entrance] {folder} against the FP network: {100 * m["flip_frac"]:.4f} % of the voxels decided '
-              f'differently, per-class means:')
-        for c in range(len(m['dsc'])):
-            print(f'  class {c}: dsc = {float(m["dsc"][c]):.4f}, logit_rel_mse = {float(m["logit_rel_mse"][c]):.4g}, '
-                  f'prob_mae = {float(m["prob_mae"][c]):.4g}')
+            lines += R.agreement_lines(folder, res)
+        print('\n'.join(lines))
 
 
 class _SyntheticCube:
@@ -257,24 +203,31 @@ class _SyntheticCube:
             self.multi_label, self.multilabel_fusetype = multi_label, None
 
 
+def _switches(args):
+    """The switch families of the ptq mission, each parsed and checked once, before anything touches the device (host
+    only: SystemExit naming the switches): ((blend, flips), (post rules, connectivity), (sweep, thresh), lesion_match)."""
+    sliding = Cf.blend_switches(args)
+    post = check_post(args)
+    thr = Cf.thr_switches(args)
+    Cf.prob_switches(args)
+    match = Cf.match_switches(args)
+    if getattr(args, 'unlabelled', False):
+        if not getattr(args, 'vs_fp', False):
+            raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add '
+                             '--vs_fp')
+        if getattr(args, 'test_fp', False):
+            raise SystemExit('--unlabelled --test_fp: the FP network cannot be validated against labels that are not '
+                             'there: drop --test_fp')
+        if getattr(args, 'lesion_table', False):
+            raise SystemExit('--unlabelled --lesion_table: the per-lesion table is written against labels only (--is_cc '
+                             'and --surf_dist are measured against the FP network): drop --lesion_table')
+    return sliding, post, thr, match
+
+
 def check_switches(args):
     """The combinations of --vs_fp / --unlabelled that cannot run and the values of --blend / --tta_mirror that are not
     understood, refused before anything touches the device (host only: SystemExit naming the switches)."""
-    Cf.blend_switches(args)
-    check_post(args)
-    Cf.thr_switches(args)
-    Cf.prob_switches(args)
-    Cf.match_switches(args)
-    if not getattr(args, 'unlabelled', False):
-        return
-    if not getattr(args, 'vs_fp', False):
-        raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add --vs_fp')
-    if getattr(args, 'test_fp', False):
-        raise SystemExit('--unlabelled --test_fp: the FP network cannot be validated against labels that are not there: '
-                         'drop --test_fp')
-    if getattr(args, 'lesion_table', False):
-        raise SystemExit('--unlabelled --lesion_table: the per-lesion table is written against labels only (--is_cc and '
-                         '--surf_dist are measured against the FP network): drop --lesion_table')
+    _switches(args)
 
 
 def check_post(args):
@@ -309,7 +262,7 @@ def main(argv=None):
         from . import prep
         prep.run(args)
         return
-    if args.mission == 'predict':
+    if args.mission == 'predict':       # refused ahead of predict.run's own checks, which hold for a direct caller too
         Cf.thr_switches(args)
         Cf.match_switches(args)
         from . import predict
@@ -317,25 +270,20 @@ def main(argv=None):
         return
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)
-    check_switches(args)
-    blend, flips = Cf.blend_switches(args)
-    sliding = {} if (blend, flips) == ('uniform', (0,)) else {'blend': blend, 'flips': flips}
-    if sliding:
+    (blend, flips), (post, post_conn), (sweep, thresh), match = _switches(args)
+    if (blend, flips) != ('uniform', (0,)):
         print(f'[entrance] sliding window: blend {blend}, {len(flips)} passes per window (flip masks '
               f'{" ".join(str(m) for m in flips)})')
-    post, post_conn = Cf.post_rules(args)
-    cleaning = {'post': post, 'post_conn': post_conn} if post else {}
     if post:
         print(f'[entrance] --post {Cf.post_text(post, post_conn)}: every labelled validation also scores the cleaned map '
               f'(metrics_post.csv)')
-    sweep, thresh = Cf.thr_switches(args)
     if sweep:
-        cleaning = dict(cleaning, sweep=True)
         print('[entrance] --thr_sweep: every labelled validation also sweeps the decision threshold (threshold.csv, '
               'threshold_curve.csv)')
-    if Cf.match_switches(args):
+    if match:
         print('[entrance] --lesion_match: every labelled validation also matches its lesions one to one '
               '(lesion_match.csv, lesion_pairs.csv)')
+    tester_kw = dict(blend=blend, flips=flips, post=post, post_conn=post_conn, sweep=sweep)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -347,20 +295,20 @@ def main(argv=None):
         dist.init_process_group('nccl')
         args.device = local
     if thresh is None:
-        return _ptq(args, sliding, cleaning)
+        return _ptq(args, tester_kw)
     from .hip_ops import get_ops
     ops = get_ops(torch.device('cuda', int(args.device)))
     print(f'[entrance] --thresh {args.thresh}: every channel is decided at logit >= {thresh:.9g} (sigmoid >= '
           f'{E.logit_prob(thresh):.6g}) in every validation and map of this run, for both networks alike')
     ops.set_decision_threshold(thresh)
     try:
-        return _ptq(args, sliding, cleaning)
+        return _ptq(args, tester_kw)
     finally:
         ops.set_decision_threshold(None)
 
 
-def _ptq(args, sliding, cleaning):
-    """The ptq mission after its switches are checked: `sliding` and `cleaning` are the tester's keywords."""
+def _ptq(args, tester_kw):
+    """The ptq mission after its switches are checked: `tester_kw` are the keywords of the _ValidationTester."""
     QConv, Qinfo, kwQ = Cf.get_conv_class(args)
     cube, info = Cf.get_model_cube(args, QConv, kwQ)
     model = cube['model']
@@ -372,7 +320,12 @@ def _ptq(args, sliding, cleaning):
         torch.save({'state_dict': model.state_dict()}, args.pretrain)
         cube['pretrain'] = args.pretrain
         print(f'[entrance] no --pretrain given: seeded random-init network saved to {args.pretrain}')
-    if not args.synthetic:
+    if args.synthetic:
+        size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
+        size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
+        data_cube = _SyntheticCube(args.task, args.lwq_batchsz, size, getattr(args, 'vs_fp', False),
+                                   getattr(args, 'multi_label', None))
+    else:
         if not (args.data_dir and args.split_dir):
             raise SystemExit('no dataset is shipped: pass --data_dir and --split_dir, or --synthetic')
         data_cube = D.get_data_cube(args)
@@ -381,24 +334,13 @@ def _ptq(args, sliding, cleaning):
             raise SystemExit(f'--save_nii --src_geom: the maps of --multi_label {data_cube.multi_label} hold one plane '
                              f'per class (C x D x H x W) and cannot be written on the source grid of '
                              f'{", ".join(data_cube.val_sn)}: drop --src_geom (or --save_nii)')
-        with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
-            f.write(' '.join(sys.argv) + '\n')
-        rank = int(os.environ.get('RANK', '0'))
-        tester = _ValidationTester(model, snap, data_cube, args.task, rank, **sliding, **cleaning)
-        K.do_ptq(args, cube, data_cube, tester, snap)
-        return
-    size = [int(v) for v in args.lwq_patchsz.split(',')] if args.lwq_patchsz else (128 if args.task == 'brats' else 160)
-    size = size[0] if isinstance(size, list) and len(set(size)) == 1 else size
-    data_cube = _SyntheticCube(args.task, args.lwq_batchsz, size, getattr(args, 'vs_fp', False),
-                               getattr(args, 'multi_label', None))
     with open(os.path.join(snap, 'cmd.txt'), 'w') as f:
         f.write(' '.join(sys.argv) + '\n')
-    if data_cube.valloader is not None:
-        rank = int(os.environ.get('RANK', '0'))
-        tester = _ValidationTester(model, snap, data_cube, args.task, rank, **sliding, **cleaning)
-        K.do_ptq(args, cube, data_cube, tester, snap)
-        return
-    K.do_ptq(args, cube, data_cube, _SnapshotWriter(model, snap), snap)
+    if args.synthetic and data_cube.valloader is None:      # nothing to validate: the snapshot files only
+        tester = _SnapshotWriter(model, snap)
+    else:
+        tester = _ValidationTester(model, snap, data_cube, args.task, int(os.environ.get('RANK', '0')), **tester_kw)
+    K.do_ptq(args, cube, data_cube, tester, snap)
 
 
 if __name__ == '__main__':

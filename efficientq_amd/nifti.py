@@ -14,12 +14,16 @@ float32 with the header's scaling applied.
 ``--src_geom`` the label maps are written with the geometry of the scan they belong to (``write_nifti(..., geometry=)``:
 the source's sform and qform fields, codes and ``pixdim``), so that a viewer overlays them, and the surface distances
 are measured with the source's spacing.
+
+``BackgroundWriter`` runs the writes of a mission on one background thread while the device goes on.
 """
 from __future__ import annotations
 
 import gzip
 import struct
 import zlib
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -181,6 +185,33 @@ def qform_affine(quatern, pixdim) -> np.ndarray:
     return aff
 
 
+def _header_fields(raw: bytes, path: str, who: str):
+    """(the fields of FIELDS, the byte order) of the header bytes of a single-file NIfTI-1 image, or `who`'s ValueError."""
+    for end in "<>":
+        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
+            break
+    else:
+        raise ValueError(f"{who}: {path}: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
+    f = {}
+    for name, fmt, off in FIELDS:
+        v = struct.unpack_from(end + fmt, raw, off)
+        f[name] = v[0] if len(v) == 1 else v
+    if f["magic"] != MAGIC:
+        raise ValueError(f"{who}: {path}: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    return f, end
+
+
+def _affine_and_spacing(f: dict):
+    """The affine in the order in which NIfTI readers choose it (read_geometry) and the norms of its first three columns."""
+    if f["sform_code"] > 0:
+        aff = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
+    elif f["qform_code"] > 0:
+        aff = qform_affine(f["quatern"], f["pixdim"])
+    else:
+        aff = np.diag([float(f["pixdim"][1]), float(f["pixdim"][2]), float(f["pixdim"][3]), 1.0])
+    return aff, tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
+
+
 def read_geometry(path: str) -> dict:
     """Where the voxels of a single-file NIfTI-1 image (``.nii`` / ``.nii.gz``, either byte order, any datatype) lie,
     from its header alone.  Returns `shape`, `pixdim` (8 values), `qform_code`, `sform_code`, `quatern` (b, c, d and the
@@ -193,31 +224,14 @@ def read_geometry(path: str) -> dict:
     raw = _read_head(path, VOX_OFFSET)
     if len(raw) < HEADER_BYTES:
         raise ValueError(f"read_geometry: {path}: {len(raw)} bytes, shorter than a NIfTI-1 header")
-    for end in "<>":
-        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
-            break
-    else:
-        raise ValueError(f"read_geometry: {path}: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
-    f = {}
-    for name, fmt, off in FIELDS:
-        v = struct.unpack_from(end + fmt, raw, off)
-        f[name] = v[0] if len(v) == 1 else v
-    if f["magic"] != MAGIC:
-        raise ValueError(f"read_geometry: {path}: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    f, _ = _header_fields(raw, path, "read_geometry")
     ndim = f["dim"][0]
     if not 3 <= ndim <= 7 or min(f["dim"][1:1 + ndim]) < 1:
         raise ValueError(f"read_geometry: {path}: dim = {f['dim']}, needs three axes or more")
     g = {k: f[k] for k in ("pixdim", "xyzt_units", "qform_code", "sform_code", "quatern", "srow_x", "srow_y", "srow_z",
                            "datatype")}
     g["shape"] = tuple(int(n) for n in f["dim"][1:1 + ndim])
-    if f["sform_code"] > 0:
-        aff = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
-    elif f["qform_code"] > 0:
-        aff = qform_affine(f["quatern"], f["pixdim"])
-    else:
-        aff = np.diag([float(f["pixdim"][1]), float(f["pixdim"][2]), float(f["pixdim"][3]), 1.0])
-    g["affine"] = aff
-    g["spacing"] = tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
+    g["affine"], g["spacing"] = _affine_and_spacing(f)
     return g
 
 
@@ -231,17 +245,7 @@ def decode_image(raw: bytes, path: str = "<bytes>"):
     """(float32 array, header fields) of the bytes of a single-file NIfTI-1 image; see read_image."""
     if len(raw) < VOX_OFFSET:
         raise ValueError(f"read_image: {path}: {len(raw)} bytes, shorter than a NIfTI-1 header")
-    for end in "<>":
-        if struct.unpack_from(end + "i", raw, 0)[0] == HEADER_BYTES:
-            break
-    else:
-        raise ValueError(f"read_image: {path}: sizeof_hdr is not {HEADER_BYTES}: not a NIfTI-1 file")
-    f = {}
-    for name, fmt, off in FIELDS:
-        v = struct.unpack_from(end + fmt, raw, off)
-        f[name] = v[0] if len(v) == 1 else v
-    if f["magic"] != MAGIC:
-        raise ValueError(f"read_image: {path}: magic {f['magic']!r}, only single-file NIfTI-1 ({MAGIC!r}) is read")
+    f, end = _header_fields(raw, path, "read_image")
     if f["datatype"] not in IMAGE_DATATYPES:
         raise ValueError(f"read_image: {path}: datatype {f['datatype']}, one of {sorted(IMAGE_DATATYPES)} is read")
     dt = IMAGE_DATATYPES[f["datatype"]].newbyteorder(end)
@@ -261,14 +265,7 @@ def decode_image(raw: bytes, path: str = "<bytes>"):
     slope, inter = float(f["scl_slope"]), float(f["scl_inter"])
     if slope != 0.0 and np.isfinite(slope) and np.isfinite(inter):     # nifti1.h: scaling applies when scl_slope != 0
         a = (a.astype(np.float64) * slope + inter).astype(np.float32)
-    if f["sform_code"] > 0:
-        aff = np.array([f["srow_x"], f["srow_y"], f["srow_z"], (0.0, 0.0, 0.0, 1.0)], dtype=np.float64)
-    elif f["qform_code"] > 0:
-        aff = qform_affine(f["quatern"], f["pixdim"])
-    else:
-        aff = np.diag([float(f["pixdim"][1]), float(f["pixdim"][2]), float(f["pixdim"][3]), 1.0])
-    f["affine"] = aff
-    f["spacing"] = tuple(float(np.sqrt((aff[:3, k] ** 2).sum())) for k in range(3))
+    f["affine"], f["spacing"] = _affine_and_spacing(f)
     f["shape"] = shape
     return np.ascontiguousarray(a, dtype=np.float32), f
 
@@ -284,3 +281,32 @@ def read_image(path: str):
     if raw[:2] == b"\x1f\x8b":
         raw = gzip.decompress(raw)
     return decode_image(raw, str(path))
+
+
+# ---- writing while the device goes on ------------------------------------------------------------------------------------
+class BackgroundWriter:
+    """One background thread that runs the writes of a mission in the order they are handed in (validate_seg's maps,
+    predict's maps), as a context manager.  `max_pending`: once that many jobs wait, submit first waits for the oldest
+    (gzip slower than the device: the host maps do not pile up), and re-raises it when it failed.  On exit every job has
+    run and the thread is gone, also when the body raised; the first failed job is re-raised unless the body raised."""
+
+    def __init__(self, thread_name_prefix: str, max_pending=None):
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=thread_name_prefix)
+        self._pending, self._max = deque(), max_pending
+
+    def submit(self, fn, *args):
+        while self._max is not None and len(self._pending) >= self._max:
+            self._pending.popleft().result()
+        job = self._pool.submit(fn, *args)
+        self._pending.append(job)
+        return job
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self._pool.shutdown(wait=True)
+        if exc_type is None:
+            for job in self._pending:
+                job.result()                    # re-raises a failed write
+        return False

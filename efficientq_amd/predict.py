@@ -11,11 +11,11 @@ defaults (``--prep_min_size``: the patch); they must be what the calibration dat
 are written into ``predict.csv``.  The network is exactly one of ``--resume`` (a snapshot of the ``ptq`` mission,
 calibrate.load_calibrated) and ``--pretrain`` with ``--qconv conv`` (the FP checkpoint, folded as do_ptq folds it).
 
-Per subject: the scans are read (the next subject's by one background thread), windowed, resampled, standardised and
-cropped in memory (prep.process_subject), the windows of the crop run through the network and the last head is stitched
-(evaluate.stitched_window_logits), and effq_seg_labels_source turns the stitched logits on the working grid into one
+Per subject: the scans are read (the next subject's by one background thread, prep.read_subjects), windowed, resampled,
+standardised and cropped in memory (prep.process_subject under prep.PrepOptions, the option set prep shares), the windows
+of the crop run through the network and the last head is stitched (window.stitched_window_logits), and effq_seg_labels_source turns the stitched logits on the working grid into one
 label per voxel of the scan's own grid: ``<out_dir>/<subject>.nii.gz``, uint8, with the header of the first modality,
-written by a background thread.  ``<out_dir>/predict.csv`` gets one row per subject: the source shape and spacing, the
+written by a background thread (nifti.BackgroundWriter).  ``<out_dir>/predict.csv`` gets one row per subject: the source shape and spacing, the
 grid, the box, the number of windows, the prep options used, and per label value present in the map its voxel count
 (counted on the device) and its volume in ml.
 
@@ -75,7 +75,8 @@ from __future__ import annotations
 import csv
 import os
 import os.path as P
-from concurrent.futures import ThreadPoolExecutor
+from contextlib import closing
+from types import SimpleNamespace
 from typing import List
 
 import numpy as np
@@ -148,18 +149,16 @@ def _write_csv(path: str, rows: List[dict], header=CSV_HEADER) -> None:
     prep._replace(path, dump)
 
 
-def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
-    """The `predict` mission of `args` (config.build_parser); returns the rows of predict.csv.  `ops`: the object whose
-    prep_*, window_*, seg_labels_source and (for --save_prob / --save_unc) seg_probs_source methods do the device work and whose `device` holds the tensors
-    (hip_ops.get_ops(args.device) by default); `model`: the network, already on that device and in its mode (by default
-    the one --resume / --pretrain name); `window_batch`: windows per forward (None: sized from the first window's peak
-    memory, as validate_seg sizes it)."""
+def _resolve(args, need_network: bool) -> SimpleNamespace:
+    """Everything `args`, the list and the headers decide, refused by name before anything touches the device or
+    out_dir; returns the mission's job: host values only (`overlap`: the validation's, half a patch at most; `sliding`:
+    --blend / --tta_mirror given, their columns are written; `used`: the columns that are the same in every row)."""
     task = (getattr(args, "task", None) or "").lower()
     if task not in D.MODALITIES:
         raise PrepError(f"predict: --task {getattr(args, 'task', None)!r}, one of {', '.join(D.MODALITIES)}")
     if not getattr(args, "src_list", None) or not getattr(args, "out_dir", None):
         raise PrepError("predict: needs --src_list and --out_dir")
-    if model is None:
+    if need_network:
         resume, pretrain = getattr(args, "resume", None), getattr(args, "pretrain", None)
         if bool(resume) == bool(pretrain):
             raise SystemExit(f"predict: needs exactly one of --resume (a calibrated snapshot of the ptq mission) and "
@@ -181,38 +180,107 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         raise PrepError(f"predict: the maps of --multi_label {multi_label} hold one plane per class (C x D x H x W); a "
                         f"NIfTI image has its spatial axes first, so they cannot be written on the source grid")
     fuse = getattr(args, "merge_type", None) if multi_label else None
-    mods = D.MODALITIES[task]
-    mask = getattr(args, "prep_mask", None) or prep.MASK_DEFAULT[task]
-    if mask not in ("nonzero", "all"):
-        raise PrepError(f"--prep_mask {mask!r}: nonzero or all")
-    window = prep.parse_window(getattr(args, "prep_window", None), task)
-    spacing = prep._triple(args.prep_spacing, "--prep_spacing") if getattr(args, "prep_spacing", None) else None
     try:
         patch = D.parse_patch(args.patch_size) if getattr(args, "patch_size", None) else D.PATCH_DEFAULT[task]
     except ValueError:
         patch = ()
     if len(patch) != 3 or min(patch) < 1:
         raise PrepError(f"--patch_size {args.patch_size!r}: needs one or three positive integers")
-    overlap = tuple(min(D.OVERLAP_DEFAULT, p // 2) for p in patch)      # the validation's overlap, half a patch at most
-    min_size = prep._triple(args.prep_min_size, "--prep_min_size", int) if getattr(args, "prep_min_size", None) else patch
-    if any(m < p for m, p in zip(min_size, patch)):
-        raise PrepError(f"--prep_min_size {tuple(min_size)} is smaller than --patch_size {tuple(patch)}: the sliding "
+    opts = prep.parse_options(args, task, patch)
+    if any(m < p for m, p in zip(opts.min_size, patch)):
+        raise PrepError(f"--prep_min_size {tuple(opts.min_size)} is smaller than --patch_size {tuple(patch)}: the sliding "
                         f"window needs one whole patch")
-    no_crop = bool(getattr(args, "prep_no_crop", False))
-    orient = prep.parse_orient(getattr(args, "prep_orient", None))
-    antialias = prep.antialias_switch(args, spacing)
-    interp = prep.interp_switch(args, spacing)
     from . import config as Cf
     blend, flips = Cf.blend_switches(args)
     sliding = (blend, flips) != ("uniform", (0,))
     post, post_conn = Cf.post_rules(args)
     _, thresh = Cf.thr_switches(args, 'predict')
     save_prob, save_unc = Cf.prob_switches(args, 'predict')
-    prob_mode = "argmax" if rule == "argmax" else "sigmoid"
+    mods = D.MODALITIES[task]
+    plans = [opts.plan(dict(e, seg=None), mods) for e in prep.read_src_list(args.src_list, task)]
+    window = opts.window
+    used = {"prep_mask": opts.mask, "prep_window": str(window) if isinstance(window, prep.PercentileWindow) else
+            prep._fmt(window) if window else "none",
+            "prep_spacing": prep._fmt(opts.spacing) if opts.spacing else "none",
+            "prep_min_size": prep._fmt(opts.min_size), "patch_size": prep._fmt(patch)}
+    if sliding:
+        used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
+    if thresh is not None:
+        used.update(thresh="%.9g" % thresh)
+    post_said = Cf.post_text(post, post_conn) if post else None
+    if post:
+        used.update(post=post_said)
+    return SimpleNamespace(mods=mods, opts=opts, patch=patch, overlap=tuple(min(D.OVERLAP_DEFAULT, p // 2) for p in patch),
+                           rule=rule, fuse=fuse, blend=blend, flips=flips, sliding=sliding, post=post, post_conn=post_conn,
+                           post_said=post_said, thresh=thresh, save_prob=save_prob, save_unc=save_unc,
+                           prob_mode="argmax" if rule == "argmax" else "sigmoid", used=used, plans=plans)
 
-    # everything the list and the headers decide, before anything touches the device or out_dir
-    entries = [dict(e, seg=None) for e in prep.read_src_list(args.src_list, task)]
-    plans = [prep._Plan(e, mods, spacing, min_size, orient, antialias, interp) for e in entries]
+
+def _on_scan_grid(ops, plan, t):
+    """A map `t` of the oriented source grid (D x H x W, or the C planes as N = C volumes; None stays None) back on the
+    scan's own grid: one effq_prep_reorient with the inverse plan, nothing when the scan was not turned."""
+    if t is None or plan.orient is None or prep.orient_is_identity(*plan.orient):
+        return t
+    return ops.prep_reorient(t, *prep.orient_inverse(*plan.orient))
+
+
+def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write):
+    """The device work of one subject: its label map and, for --save_prob / --save_unc, its probability and uncertainty
+    maps, handed to `write(path, host, geometry, scale=None)`.  Returns (what it leaves for the row and the line, the
+    window batch in use): box_of, the extent of the working arrays; counts, the voxels per label value of the map that was
+    written; changed, the voxels each --post rule relabelled; extra, what the line says of the probability files."""
+    sn = plan.subject
+    y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, imgs, None, job.mods, job.opts)
+    vol = torch.from_numpy(y)[None].to(ops.device)
+    outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, job.patch, job.overlap, bsz, job.blend, job.flips)
+    where = (pmin, plan.grid_shape, plan.factors, plan.oriented_shape)
+    labels = _on_scan_grid(ops, plan, ops.seg_labels_source(outs[0][0], *where, job.rule, job.fuse))
+    changed = None
+    if job.post:        # on the source grid, in place: the counts, the copy and the file are the cleaned map's
+        labels, stats = ops.label_clean(labels, job.post, job.post_conn, out=labels)
+        changed = prep._fmt(int(v) for v in stats.cpu()[:, 1])
+    counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
+    write(P.join(out_dir, f"{sn}.nii.gz"), labels.cpu().numpy(), plan.header)
+    extra = ""
+    if job.save_prob or job.save_unc:       # from the same stitched logits, on the same grid; --post does not enter
+        probs, unc = ops.seg_probs_source(outs[0][0], *where, job.prob_mode, job.save_prob, job.save_unc)
+        probs, unc = _on_scan_grid(ops, plan, probs), _on_scan_grid(ops, plan, unc)
+        if job.save_prob:       # (C, SD, SH, SW) -> the view (SD, SH, SW, C): a 4-D image, pixdim[4] = 1
+            geo = dict(plan.header, pixdim=tuple(plan.header["pixdim"][:4]) + (1.0,) + tuple(plan.header["pixdim"][5:]))
+            write(P.join(out_dir, PROB_DIR, f"{sn}.nii.gz"), np.moveaxis(probs.cpu().numpy(), 0, -1), geo, PROB_SCALE)
+            extra += f", {PROB_DIR}/{sn}.nii.gz ({probs.shape[0]} channels)"
+        if job.save_unc:
+            write(P.join(out_dir, UNC_DIR, f"{sn}.nii.gz"), unc.cpu().numpy(), plan.header, PROB_SCALE)
+            extra += f", {UNC_DIR}/{sn}.nii.gz"
+    return SimpleNamespace(box_of=tuple(y.shape[1:]), pmin=pmin, pmax=pmax, windows=nwin, counts=counts,
+                           changed=changed, extra=extra), bsz
+
+
+def _row(job, plan, done) -> dict:
+    """The row of predict.csv of one subject."""
+    present = [v for v, n in enumerate(done.counts) if n]
+    ml = float(np.prod(plan.source_spacing)) / 1000.0
+    row = {"subject": plan.subject, "source_shape": prep._fmt(plan.source_shape),
+           "source_spacing": prep._fmt(plan.source_spacing), "grid_shape": prep._fmt(plan.grid_shape),
+           "pmin": prep._fmt(done.pmin), "pmax": prep._fmt(done.pmax), "windows": str(done.windows),
+           "labels": prep._fmt(present), "voxels": prep._fmt(done.counts[v] for v in present),
+           "volume_ml": " ".join(f"{done.counts[v] * ml:.7g}" for v in present)}
+    row.update(job.used)
+    row.update(job.opts.row_values(plan))
+    if plan.window_bounds is not None:
+        row["window_bounds"] = ";".join(prep._fmt(b) for b in plan.window_bounds)
+    if job.post:
+        row["post_changed"] = done.changed
+    return row
+
+
+def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
+    """The `predict` mission of `args` (config.build_parser); returns the rows of predict.csv.  `ops`: the object whose
+    prep_*, window_*, seg_labels_source and (for --save_prob / --save_unc) seg_probs_source methods do the device work and whose `device` holds the tensors
+    (hip_ops.get_ops(args.device) by default); `model`: the network, already on that device and in its mode (by default
+    the one --resume / --pretrain name); `window_batch`: windows per forward (None: sized from the first window's peak
+    memory, as validate_seg sizes it)."""
+    job = _resolve(args, model is None)
     if ops is None:
         from .hip_ops import get_ops
         ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
@@ -222,124 +290,48 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
 
     out_dir = args.out_dir
     os.makedirs(out_dir, exist_ok=True)
-    pct = isinstance(window, prep.PercentileWindow)
-    used = {"prep_mask": mask, "prep_window": str(window) if pct else prep._fmt(window) if window else "none",
-            "prep_spacing": prep._fmt(spacing) if spacing else "none", "prep_min_size": prep._fmt(min_size),
-            "patch_size": prep._fmt(patch)}
-    if orient:
-        used.update(orient=orient)
-    if sliding:
-        used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
-    if thresh is not None:
-        used.update(thresh="%.9g" % thresh)
-        print(f"[predict] --thresh {args.thresh}: every channel is decided at logit >= {thresh:.9g} (sigmoid >= "
-              f"{E.logit_prob(thresh):.6g})")
-        ops.set_decision_threshold(thresh)
-    if save_prob or save_unc:
+    if job.thresh is not None:
+        print(f"[predict] --thresh {args.thresh}: every channel is decided at logit >= {job.thresh:.9g} (sigmoid >= "
+              f"{E.logit_prob(job.thresh):.6g})")
+        ops.set_decision_threshold(job.thresh)
+    if job.save_prob or job.save_unc:
         nc = getattr(args, "nClass", None)
-        what = " and ".join(w for w, on in ((f"{PROB_DIR}/<subject>.nii.gz (SD, SH, SW, C)", save_prob),
-                                            (f"{UNC_DIR}/<subject>.nii.gz", save_unc)) if on)
-        how = (f"softmax over {nc if nc else 'the'} classes, uncertainty = entropy / ln C" if prob_mode == "argmax" else
+        what = " and ".join(w for w, on in ((f"{PROB_DIR}/<subject>.nii.gz (SD, SH, SW, C)", job.save_prob),
+                                            (f"{UNC_DIR}/<subject>.nii.gz", job.save_unc)) if on)
+        how = (f"softmax over {nc if nc else 'the'} classes, uncertainty = entropy / ln C" if job.prob_mode == "argmax" else
                "sigmoid per channel, uncertainty = the largest binary entropy of a channel in bits")
         print(f"[predict] {what}: {how}, from the logits interpolated as for the label map; uint8 in steps of 1/255 "
               f"(scl_slope), --post does not touch them")
-        if save_prob and prob_mode == "sigmoid" and (fuse or thresh is not None):
-            given = " and ".join(w for w, on in ((f"--merge_type {fuse}", fuse), (f"--thresh {getattr(args, 'thresh', None)}",
-                                                                                 thresh is not None)) if on)
+        if job.save_prob and job.prob_mode == "sigmoid" and (job.fuse or job.thresh is not None):
+            given = " and ".join(w for w, on in ((f"--merge_type {job.fuse}", job.fuse),
+                                                 (f"--thresh {getattr(args, 'thresh', None)}", job.thresh is not None)) if on)
             print(f"[predict] --save_prob: {given} decide the label map only: the probabilities are the network's, per "
                   f"raw channel, not a decision's")
-        for on, sub in ((save_prob, PROB_DIR), (save_unc, UNC_DIR)):
+        for on, sub in ((job.save_prob, PROB_DIR), (job.save_unc, UNC_DIR)):
             if on:
                 os.makedirs(P.join(out_dir, sub), exist_ok=True)
-    post_said = Cf.post_text(post, post_conn) if post else None
-    if post:
-        used.update(post=post_said)
-    rows, writes = [], []
+    rows = []
     bsz = window_batch
-    reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-read")
-    writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-predict-write")
-
-    def write(path, host, geometry, scale=None):
-        while len(writes) >= MAX_PENDING_WRITES:       # gzip slower than the device: wait, do not pile maps up
-            writes.pop(0).result()
-        writes.append(writer.submit(nifti.write_nifti, path, host, None, geometry, scale))
-
     try:
-        nxt = reader.submit(prep._load, entries[0], mods)
-        for i, plan in enumerate(plans):
-            got = nxt.result()
-            nxt = reader.submit(prep._load, entries[i + 1], mods) if i + 1 < len(entries) else None
-            sn = plan.subject
-            if isinstance(got, Exception):
-                raise PrepError(f"subject {sn}: {got}") from got
-            y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, got[0], None, mods, mask, window, min_size,
-                                                                no_crop)
-            vol = torch.from_numpy(y)[None].to(ops.device)
-            outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, patch, overlap, bsz, blend, flips)
-            labels = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.oriented_shape, rule,
-                                           fuse)
-            if plan.orient is not None and not prep.orient_is_identity(*plan.orient):
-                labels = ops.prep_reorient(labels, *prep.orient_inverse(*plan.orient))     # back on the scan's own grid
-            cleaned = ""
-            if post:        # on the source grid, in place: the counts, the copy and the file are the cleaned map's
-                labels, stats = ops.label_clean(labels, post, post_conn, out=labels)
-                changed = prep._fmt(int(v) for v in stats.cpu()[:, 1])
-                cleaned = f", post {post_said}: {changed} voxels relabelled"
-            counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
-            host = labels.cpu().numpy()
-            write(P.join(out_dir, f"{sn}.nii.gz"), host, plan.header)
-            extra = ""
-            if save_prob or save_unc:       # from the same stitched logits, on the same grid; --post does not enter
-                probs, unc = ops.seg_probs_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.oriented_shape,
-                                                  prob_mode, save_prob, save_unc)
-                if plan.orient is not None and not prep.orient_is_identity(*plan.orient):
-                    back = prep.orient_inverse(*plan.orient)
-                    probs = ops.prep_reorient(probs, *back) if save_prob else None      # the C planes as N = C volumes
-                    unc = ops.prep_reorient(unc, *back) if save_unc else None
-                if save_prob:       # (C, SD, SH, SW) -> the view (SD, SH, SW, C): a 4-D image, pixdim[4] = 1
-                    geo = dict(plan.header, pixdim=tuple(plan.header["pixdim"][:4]) + (1.0,) +
-                               tuple(plan.header["pixdim"][5:]))
-                    write(P.join(out_dir, PROB_DIR, f"{sn}.nii.gz"), np.moveaxis(probs.cpu().numpy(), 0, -1), geo,
-                          PROB_SCALE)
-                    extra += f", {PROB_DIR}/{sn}.nii.gz ({probs.shape[0]} channels)"
-                if save_unc:
-                    write(P.join(out_dir, UNC_DIR, f"{sn}.nii.gz"), unc.cpu().numpy(), plan.header, PROB_SCALE)
-                    extra += f", {UNC_DIR}/{sn}.nii.gz"
-            present = [v for v, n in enumerate(counts) if n]
-            ml = float(np.prod(plan.source_spacing)) / 1000.0
-            row = {"subject": sn, "source_shape": prep._fmt(plan.source_shape),
-                   "source_spacing": prep._fmt(plan.source_spacing), "grid_shape": prep._fmt(plan.grid_shape),
-                   "pmin": prep._fmt(pmin), "pmax": prep._fmt(pmax), "windows": str(nwin),
-                   "labels": prep._fmt(present), "voxels": prep._fmt(counts[v] for v in present),
-                   "volume_ml": " ".join(f"{counts[v] * ml:.7g}" for v in present)}
-            row.update(used)
-            if orient:
-                row["source_orient"] = plan.orient_code
-            if antialias:
-                row["antialias"] = prep._fmt(plan.sigmas)
-            if interp == "cubic":
-                row["interp"] = interp
-            if pct:
-                row["window_bounds"] = ";".join(prep._fmt(b) for b in plan.window_bounds)
-            if post:
-                row["post_changed"] = changed
-            rows.append(row)
-            turned = f" ({plan.orient_code} -> {orient})" if orient and plan.orient_code != orient else ""
-            print(f"[predict] {sn}: {prep._fmt(plan.source_shape)}{turned}{prep.window_said(plan, mods)}{prep.antialias_said(plan)}{prep.interp_said(plan)} -> grid "
-                  f"{prep._fmt(plan.grid_shape)}, box at {prep._fmt(pmin)} of {prep._fmt(y.shape[1:])}, {nwin} windows"
-                  f"{f' x {len(flips)} passes, blend {blend}' if sliding else ''}, labels {row['labels']}: "
-                  f"{row['voxels']} voxels{cleaned}{extra}")
+        with nifti.BackgroundWriter("effq-predict-write", MAX_PENDING_WRITES) as writer, \
+                closing(prep.read_subjects(job.plans, job.mods, "effq-predict-read")) as subjects:
+            def write(path, host, geometry, scale=None):
+                writer.submit(nifti.write_nifti, path, host, None, geometry, scale)
+            for plan, imgs, _ in subjects:
+                done, bsz = _segment(ops, model, job, plan, imgs, out_dir, bsz, write)
+                rows.append(_row(job, plan, done))
+                cleaned = f", post {job.post_said}: {done.changed} voxels relabelled" if job.post else ""
+                print(f"[predict] {plan.subject}: {prep._fmt(plan.source_shape)}{job.opts.said(plan, job.mods)} -> grid "
+                      f"{prep._fmt(plan.grid_shape)}, box at {prep._fmt(done.pmin)} of {prep._fmt(done.box_of)}, "
+                      f"{done.windows} windows{f' x {len(job.flips)} passes, blend {job.blend}' if job.sliding else ''}, "
+                      f"labels {rows[-1]['labels']}: {rows[-1]['voxels']} voxels{cleaned}{done.extra}")
     finally:
-        reader.shutdown(wait=True, cancel_futures=True)
-        writer.shutdown(wait=True)
-        if thresh is not None:
+        if job.thresh is not None:
             ops.set_decision_threshold(None)
-    for w in writes:
-        w.result()                              # re-raises a failed write
+    pct = isinstance(job.opts.window, prep.PercentileWindow)
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
-               CSV_HEADER + (prep.ORIENT_COLUMNS if orient else []) + (prep.ANTIALIAS_COLUMNS if antialias else []) +
-               (prep.INTERP_COLUMNS if interp == "cubic" else []) + (CSV_WINDOW_COLUMNS if pct else []) +
-               (CSV_BLEND_COLUMNS if sliding else []) +
-               (CSV_THRESH_COLUMNS if thresh is not None else []) + (CSV_POST_COLUMNS if post else []))
+               CSV_HEADER + job.opts.columns() + (CSV_WINDOW_COLUMNS if pct else []) +
+               (CSV_BLEND_COLUMNS if job.sliding else []) +
+               (CSV_THRESH_COLUMNS if job.thresh is not None else []) + (CSV_POST_COLUMNS if job.post else []))
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

@@ -47,7 +47,8 @@ What the headers decide (the list itself, shapes and affines within a subject, a
 split that already exists) is checked for every subject before anything is written.  What only the voxels decide (an
 empty mask, a constant modality, a percentile bound that is not finite or, with the mask ``nonzero``, exactly 0) stops
 the run at that subject: none of its files and none of the files written at the end exist then.  The next subject's
-files are read and gunzipped by one background thread while the device works.
+files are read and gunzipped by one background thread while the device works (read_subjects).  The eight --prep_*
+options are one record, PrepOptions (parse_options), which the ``predict`` mission parses and uses the same way.
 There is no CPU path: `ops` is hip_ops.get_ops(device) unless a caller passes its own.
 """
 from __future__ import annotations
@@ -57,8 +58,10 @@ import math
 import os
 import os.path as P
 import pickle
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
-from typing import Dict, List, Optional, Sequence, Tuple
+from contextlib import closing
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -454,23 +457,6 @@ def interp_switch(args, spacing) -> str:
     return order
 
 
-def window_said(plan, mods: Sequence[str]) -> str:
-    """What the per-subject line says of a percentile window: every modality's bounds; nothing otherwise."""
-    if plan.window_bounds is None:
-        return ""
-    return ", window " + ", ".join(f"{m} {lo:.7g} {hi:.7g}" for m, (lo, hi) in zip(mods, plan.window_bounds))
-
-
-def interp_said(plan) -> str:
-    """What the per-subject line says of the interpolation: nothing for linear."""
-    return ", cubic" if plan.interp == "cubic" else ""
-
-
-def antialias_said(plan) -> str:
-    """What the per-subject line says of the filter: the sigmas when any is above 0, else nothing."""
-    return f", anti-alias sigma {_fmt(plan.sigmas)}" if any(s > 0 for s in plan.sigmas) else ""
-
-
 class _Plan:
     """What the headers of one subject decide."""
 
@@ -554,6 +540,82 @@ def _load(entry: dict, mods: Sequence[str]):
         return imgs, seg
     except Exception as e:        # handed to the main thread, which names the subject
         return e
+
+
+def read_subjects(plans: Sequence[_Plan], mods: Sequence[str], thread_name_prefix: str):
+    """(plan, {modality: array}, label or None) per plan, in order: one background thread reads and gunzips the next
+    subject's files while the caller works on this one.  A failed read is the PrepError naming its subject.  When the
+    generator ends or is closed early the pending read is cancelled and the thread is gone."""
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=thread_name_prefix)
+    try:
+        nxt = pool.submit(_load, plans[0].entry, mods)
+        for i, plan in enumerate(plans):
+            got = nxt.result()
+            nxt = pool.submit(_load, plans[i + 1].entry, mods) if i + 1 < len(plans) else None
+            if isinstance(got, Exception):
+                raise PrepError(f"subject {plan.subject}: {got}") from got
+            yield (plan,) + got
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)
+
+
+# ---- the options prep and predict share --------------------------------------------------------------------------------
+class PrepOptions(NamedTuple):
+    """The eight --prep_* options, as the ``prep`` and the ``predict`` mission both take them (parse_options)."""
+    mask: str                               # --prep_mask: nonzero | all
+    window: object                          # --prep_window: None, (lo, hi) or a PercentileWindow
+    spacing: Optional[tuple]                # --prep_spacing d,h,w
+    min_size: tuple                         # --prep_min_size d,h,w
+    no_crop: bool                           # --prep_no_crop
+    orient: Optional[str] = None            # --prep_orient CODE
+    antialias: bool = False                 # --prep_antialias
+    interp: str = "linear"                  # --prep_interp linear | cubic
+
+    def plan(self, entry: dict, mods: Sequence[str]) -> _Plan:
+        return _Plan(entry, mods, self.spacing, self.min_size, self.orient, self.antialias, self.interp)
+
+    def columns(self) -> List[str]:
+        """The optional columns of prep.csv and predict.csv that both missions write, in their order."""
+        return (ORIENT_COLUMNS if self.orient else []) + (ANTIALIAS_COLUMNS if self.antialias else []) + \
+            (INTERP_COLUMNS if self.interp == "cubic" else [])
+
+    def row_values(self, plan: _Plan) -> dict:
+        """One subject's values of columns()."""
+        row = {}
+        if self.orient:
+            row.update(source_orient=plan.orient_code, orient=self.orient)
+        if self.antialias:
+            row.update(antialias=_fmt(plan.sigmas))
+        if self.interp == "cubic":
+            row.update(interp=self.interp)
+        return row
+
+    def said(self, plan: _Plan, mods: Sequence[str]) -> str:
+        """What the per-subject line says after the source shape: "(LPS -> RAS)" when the scan was turned, every
+        modality's bounds of a percentile window, the filter's sigmas when any is above 0, "cubic"."""
+        said = f" ({plan.orient_code} -> {self.orient})" if self.orient and plan.orient_code != self.orient else ""
+        if plan.window_bounds is not None:
+            said += ", window " + ", ".join(f"{m} {lo:.7g} {hi:.7g}" for m, (lo, hi) in zip(mods, plan.window_bounds))
+        if any(s > 0 for s in plan.sigmas):
+            said += f", anti-alias sigma {_fmt(plan.sigmas)}"
+        return said + (", cubic" if plan.interp == "cubic" else "")
+
+
+def parse_options(args, task: str, default_min_size=None) -> PrepOptions:
+    """The PrepOptions of `args`, each value that is not understood refused by name in the order of the fields;
+    `default_min_size` stands for an absent --prep_min_size (None: the task's patch, data.PATCH_DEFAULT)."""
+    mask = getattr(args, "prep_mask", None) or MASK_DEFAULT[task]
+    if mask not in ("nonzero", "all"):
+        raise PrepError(f"--prep_mask {mask!r}: nonzero or all")
+    window = parse_window(getattr(args, "prep_window", None), task)
+    spacing = _triple(args.prep_spacing, "--prep_spacing") if getattr(args, "prep_spacing", None) else None
+    if getattr(args, "prep_min_size", None):
+        min_size = _triple(args.prep_min_size, "--prep_min_size", int)
+    else:
+        min_size = D.PATCH_DEFAULT[task] if default_min_size is None else default_min_size
+    return PrepOptions(mask, window, spacing, min_size, bool(getattr(args, "prep_no_crop", False)),
+                       parse_orient(getattr(args, "prep_orient", None)), antialias_switch(args, spacing),
+                       interp_switch(args, spacing))
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------
@@ -671,11 +733,16 @@ def _apply_window(ops, plan, x, window, mask: str) -> None:
         ops.prep_window(x, window[0], window[1])
 
 
+# what process_subject returns, host arrays: arrays C x d x h x w float32, the label or None, the union mask of the grid or
+# None, the box, and per modality the count, mean and std over its mask
+Subject = namedtuple("Subject", "arrays label union pmin pmax count mean std")
+
+
 def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str],
-                    mask: str, window, min_size, no_crop: bool):
-    """The device pipeline of one subject.  Returns (arrays C x d x h x w float32, label or None, union mask of the grid
-    or None, pmin, pmax, count, mean, std), host arrays."""
-    sn = plan.subject
+                    opts: PrepOptions) -> Subject:
+    """The device pipeline of one subject under `opts` (its mask, window, min_size and no_crop; the plan holds what the
+    other options decided)."""
+    sn, mask, window = plan.subject, opts.mask, opts.window
     for m in mods:
         if tuple(imgs[m].shape) != plan.source_shape:
             raise PrepError(f"subject {sn}: {m} holds an array of shape {tuple(imgs[m].shape)}, its header says "
@@ -716,15 +783,15 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
         if not s > 0.0 or not math.isfinite(s):
             raise PrepError(f"subject {sn}: modality {m}: standard deviation {s} over the mask: a constant (or "
                             f"non-finite) image cannot be standardised")
-    if no_crop:
+    if opts.no_crop:
         pmin, pmax = (0, 0, 0), tuple(plan.grid_shape)
     else:
-        pmin, pmax = widen_box(bbox[:3], [b + 1 for b in bbox[3:]], plan.grid_shape, min_size)
+        pmin, pmax = widen_box(bbox[:3], [b + 1 for b in bbox[3:]], plan.grid_shape, opts.min_size)
     y = ops.prep_standardise_crop(x, pmin, pmax, mean, std, mask)
     lab_out = ops.prep_crop_u8(lab, pmin, pmax)[0].cpu().numpy() if lab is not None else None
     on_new_grid = plan.factors is not None or plan.orient is not None        # the arrays left the scan's own axes
     union = ops.prep_union_mask(x, mask).cpu().numpy() if on_new_grid else None
-    return y.cpu().numpy(), lab_out, union, pmin, pmax, count, mean, std
+    return Subject(y.cpu().numpy(), lab_out, union, pmin, pmax, count, mean, std)
 
 
 # ---- the mission -------------------------------------------------------------------------------------------------------
@@ -738,25 +805,14 @@ def run(args, ops=None) -> List[dict]:
     if not getattr(args, "src_list", None) or not getattr(args, "data_dir", None):
         raise PrepError("prep: needs --src_list and --data_dir")
     mods = D.MODALITIES[task]
-    mask = getattr(args, "prep_mask", None) or MASK_DEFAULT[task]
-    if mask not in ("nonzero", "all"):
-        raise PrepError(f"--prep_mask {mask!r}: nonzero or all")
-    window = parse_window(getattr(args, "prep_window", None), task)
-    spacing = _triple(args.prep_spacing, "--prep_spacing") if getattr(args, "prep_spacing", None) else None
-    min_size = _triple(args.prep_min_size, "--prep_min_size", int) if getattr(args, "prep_min_size", None) \
-        else D.PATCH_DEFAULT[task]
-    no_crop = bool(getattr(args, "prep_no_crop", False))
-    orient = parse_orient(getattr(args, "prep_orient", None))
-    antialias = antialias_switch(args, spacing)
-    interp = interp_switch(args, spacing)
+    opts = parse_options(args, task)
     access = getattr(args, "access_type", None) or "npy"
     if access not in D.ACCESS_TYPES:
         raise PrepError(f"--access_type {access!r}: one of {', '.join(D.ACCESS_TYPES)}")
     data_dir = args.data_dir
 
     # everything the list and the headers decide, before anything is written
-    entries = read_src_list(args.src_list, task)
-    plans = [_Plan(e, mods, spacing, min_size, orient, antialias, interp) for e in entries]
+    plans = [opts.plan(e, mods) for e in read_src_list(args.src_list, task)]
     split = None
     if getattr(args, "split_dir", None):
         k = getattr(args, "val_every", None)
@@ -773,18 +829,10 @@ def run(args, ops=None) -> List[dict]:
 
     os.makedirs(data_dir, exist_ok=True)
     sn_fn, restore, rows = {}, {}, []
-    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="effq-prep-read")
-    try:
-        nxt = pool.submit(_load, entries[0], mods)
-        for i, plan in enumerate(plans):
-            got = nxt.result()
-            nxt = pool.submit(_load, entries[i + 1], mods) if i + 1 < len(entries) else None
+    with closing(read_subjects(plans, mods, "effq-prep-read")) as subjects:       # a subject that fails ends the reads
+        for plan, imgs, seg in subjects:
             sn = plan.subject
-            if isinstance(got, Exception):
-                raise PrepError(f"subject {sn}: {got}") from got
-            imgs, seg = got
-            y, lab, union, pmin, pmax, count, mean, std = process_subject(ops, plan, imgs, seg, mods, mask, window,
-                                                                          min_size, no_crop)
+            y, lab, union, pmin, pmax, count, mean, std = process_subject(ops, plan, imgs, seg, mods, opts)
             for c, m in enumerate(mods):
                 _save_array(data_dir, m, sn, access, y[c])
             if lab is not None:
@@ -803,25 +851,14 @@ def run(args, ops=None) -> List[dict]:
             for c, m in enumerate(mods):
                 row.update({f"{m}_count": str(int(count[c])), f"{m}_mean": repr(float(mean[c])),
                             f"{m}_std": repr(float(std[c]))})
-            turned = ""
-            if orient is not None:
-                row.update(source_orient=plan.orient_code, orient=orient)
-                turned = f" ({plan.orient_code} -> {orient})" if plan.orient_code != orient else ""
-            if antialias:
-                row.update(antialias=_fmt(plan.sigmas))
-            if interp == "cubic":
-                row.update(interp=interp)
+            row.update(opts.row_values(plan))
             if plan.window_bounds is not None:
                 for m, (lo, hi) in zip(mods, plan.window_bounds):
                     row.update({f"{m}_win_lo": repr(float(lo)), f"{m}_win_hi": repr(float(hi))})
             rows.append(row)
-            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{turned}{window_said(plan, mods)}{antialias_said(plan)}{interp_said(plan)} -> {_fmt(y.shape[1:])} at "
-                  f"{_fmt(pmin)}")
-    finally:
-        pool.shutdown(wait=True, cancel_futures=True)
-    write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods) + (ORIENT_COLUMNS if orient else []) +
-                      (ANTIALIAS_COLUMNS if antialias else []) + (INTERP_COLUMNS if interp == "cubic" else []) +
-                      (window_columns(mods) if isinstance(window, PercentileWindow) else []))
+            print(f"[prep] {sn}: {_fmt(plan.source_shape)}{opts.said(plan, mods)} -> {_fmt(y.shape[1:])} at {_fmt(pmin)}")
+    write_index_files(data_dir, sn_fn, restore, rows, prep_csv_header(mods) + opts.columns() +
+                      (window_columns(mods) if isinstance(opts.window, PercentileWindow) else []))
     if split is not None:
         names = [p.subject for p in plans]
         val = names[k - 1::k]

@@ -261,7 +261,8 @@ def _expected(ops, model, entry, spacing, patch, mask, wb):
     shared window function)."""
     plan = prep._Plan(dict(entry, seg=None), ("ct",), spacing, patch)
     imgs = {"ct": nifti.read_image(entry["images"]["ct"])[0]}
-    y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), mask, (-200.0, 250.0), patch, False)
+    y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",),
+                                                        prep.PrepOptions(mask, (-200.0, 250.0), spacing, patch, False))
     outs, nwin, _ = E.stitched_window_logits(ops, [model], torch.from_numpy(y)[None], patch, (4, 4, 4), wb)
     lab, _, inside = ref_labels_source(outs[0][0].numpy(), pmin, plan.grid_shape, plan.factors, plan.source_shape, "argmax")
     return lab, inside, plan, pmin, pmax, nwin

@@ -307,8 +307,8 @@ def test_mission_end_to_end(ops, snap_tensor, tmp_path, spacing):
         sn = r["subject"]
         plan = prep._Plan(entry, ("ct",), sp, patch)
         imgs = {"ct": nifti.read_image(entry["images"]["ct"])[0]}
-        y, _, _, pmin, pmax, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), "nonzero", (-200.0, 250.0),
-                                                            patch, False)
+        y, _, _, pmin, pmax, _, _, _ = prep.process_subject(
+            ops, plan, imgs, None, ("ct",), prep.PrepOptions("nonzero", (-200.0, 250.0), sp, patch, False))
         vol = torch.from_numpy(y)[None].to(DEV)
         outs, nwin, _ = E.stitched_window_logits(ops, [model], vol, patch, overlap, 1)
         want = ops.seg_labels_source(outs[0][0], pmin, plan.grid_shape, plan.factors, plan.source_shape, "argmax")

@@ -231,7 +231,8 @@ def test_prep_mission_filters_before_the_resample_and_records_the_sigmas(tmp_pat
     sm = S.ref_smooth(vols, (0.75, 0.2, 0.0), keep_zero=True).astype(np.float32)
     assert np.all(sm[vols == 0] == 0) and np.all(sm[vols != 0] != 0)
     want = prep.process_subject(NumpyOps(), prep._Plan(prep.read_src_list(lst, "brats")[0], mods, (2.5, 1.4, 1.0), (4, 4, 4)),
-                                dict(zip(mods, sm)), None, mods, "nonzero", None, (4, 4, 4), False)[0]
+                                dict(zip(mods, sm)), None, mods,
+                                prep.PrepOptions("nonzero", None, (2.5, 1.4, 1.0), (4, 4, 4), False))[0]
     assert np.array_equal(np.stack([np.load(os.path.join(on, m, "a.npy")) for m in mods]), want)
 
     # a second run into the same folder merges: a subject that is only kept or up-sampled gets 0 0 0, the op is not called

@@ -210,8 +210,9 @@ def _expected(ops, entry, kw, mode):
     spacing = prep._triple(kw["prep_spacing"], "spacing") if kw.get("prep_spacing") else None
     plan = prep._Plan(dict(entry, seg=None), ("ct",), spacing, (8, 8, 8), prep.parse_orient(kw.get("prep_orient")))
     imgs = {"ct": nifti.read_image(entry["images"]["ct"])[0]}
-    y, _, _, pmin, _, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), "nonzero", (-200.0, 250.0), (8, 8, 8),
-                                                     False)
+    y, _, _, pmin, _, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",),
+                                                     prep.PrepOptions("nonzero", (-200.0, 250.0), spacing, (8, 8, 8), False,
+                                                                      prep.parse_orient(kw.get("prep_orient"))))
     outs, _, _ = E.stitched_window_logits(ops, [PointNet()], torch.from_numpy(y)[None], (8, 8, 8), (4, 4, 4), 3)
     P, U, inside, _ = R.ref_probs_source(outs[0][0].numpy(), pmin, plan.grid_shape, plan.factors, plan.oriented_shape, mode)
     p, u = R.stored(P), R.stored(U)

@@ -252,8 +252,8 @@ def test_mission_end_to_end_on_a_turned_and_resampled_scan(ops, tmp_path, mode):
     entry = prep.read_src_list(lst, "lits")[0]
     plan = prep._Plan(dict(entry, seg=None), ("ct",), (2.0, 1.5, 2.5), (8, 8, 8), "RAS")
     imgs = {"ct": nifti.read_image(entry["images"]["ct"])[0]}
-    y, _, _, pmin, _, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), "nonzero", (-200.0, 250.0), (8, 8, 8),
-                                                     False)
+    y, _, _, pmin, _, _, _, _ = prep.process_subject(ops, plan, imgs, None, ("ct",), prep.PrepOptions(
+        "nonzero", (-200.0, 250.0), (2.0, 1.5, 2.5), (8, 8, 8), False, "RAS"))
     outs, _, _ = E.stitched_window_logits(ops, [model], torch.from_numpy(y)[None].to(DEV), (8, 8, 8), (4, 4, 4), 8)
     logits = outs[0][0]
     probs, unc = ops.seg_probs_source(logits, pmin, plan.grid_shape, plan.factors, plan.oriented_shape, mode, True, True)
