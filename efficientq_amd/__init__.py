@@ -9,6 +9,7 @@
     calibrate        do_ptq orchestrator, BN folding, attention-mask pyramid
     config           CLI / YAML surface, factories, the shipped BraTS / LiTS net definitions
     entrance         `python -m efficientq_amd.entrance ptq ...`
+    score, ops_score the `score` mission: finished label maps against labels on the scan's grid, and its two device calls
     mixed            per-layer mixed-precision search harness
     synth            seeded synthetic volumes / random-init networks
 """

@@ -222,6 +222,9 @@ SIGNATURES = {
     "effq_surf_mm_ws_bytes": (_SZ, [_I, _I, _I, _I]),
     "effq_edt_sq_mm": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _SZ, _P]),
     "effq_seg_surface_mm": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _SZ, _P]),
+    "effq_label_lesions": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
+    "effq_label_surface_mm_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "effq_label_surface_mm": (_I, [_P, _P, _I, _I, _I, _I, _P, _F, _F, _F, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_prep_window": (_I, [_P, _SZ, _F, _F, _P]),
     "effq_prep_resample": (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _I, _P, _I, _I, _I, _P]),
     "effq_prep_bbox_moments": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
@@ -270,6 +273,8 @@ LABEL_POST_MAX_RADIUS = 32
 EDT_MAX_LINE = 16382
 # include/effq_hip.h: the largest extent of the weighted distance transform ((i - j)^2 stays exact in fp32)
 EDT_MM_MAX_EXTENT = 4096
+# include/effq_hip.h (EFFQ_SURF_TOL_MAX): the most tolerances of one effq_label_surface_mm call
+SURF_TOL_MAX = 8
 # include/effq_hip.h: the prep kernels' most modalities, scratch, mask modes and resampling modes
 PREP_MAX_MODALITIES = 4
 PREP_WS_BYTES = 1024 * (2 * PREP_MAX_MODALITIES * 8 + 8 * 4)

@@ -1,4 +1,4 @@
-"""CLI / YAML surface of the missions (``prep``: prep.py, ``predict``: predict.py) and factories of the ``ptq`` mission, same flag names and semantics as the
+"""CLI / YAML surface of the missions (``prep``: prep.py, ``predict``: predict.py, ``score``: score.py) and factories of the ``ptq`` mission, same flag names and semantics as the
 reference (src/entrance.py:17-128, src/definer.py:130-248,286-329): YAML values override the
 command line for every non-null key (quirk Q15); ``qlvl_*`` are LEVEL counts (4 => 2-bit);
 ``q_first/q_last "W,A"`` with A=-1 => full-precision activations (quirk Q14); every ``lwq_*``
@@ -30,7 +30,7 @@ def merge_config(cfg: str, args: argparse.Namespace):
 
 def build_parser():
     p = argparse.ArgumentParser(description='EfficientQ PTQ calibration on MI355X')
-    p.add_argument('mission', choices=['ptq', 'prep', 'predict'])
+    p.add_argument('mission', choices=['ptq', 'prep', 'predict', 'score'])
     p.add_argument('--pretrain')
     p.add_argument('--resume')
     p.add_argument('--device', default=0, type=int, help='GPU ID.')
@@ -150,6 +150,15 @@ def build_parser():
     p.add_argument('--save_unc', action='store_true',
                    help='predict: also write <out_dir>/unc/<subject>.nii.gz, one uncertainty per voxel of the scan\'s grid '
                         '(entropy as a share of its maximum): uint8, scl_slope 1/255')
+    # the score mission (score.py): finished label maps against the labels of --src_list, on the scan's grid; the values
+    # are checked by score_switches, after the YAML has been merged in
+    p.add_argument('--pred_dir', default=None, help='score: the folder of the maps <subject>.nii.gz (or .nii) to score')
+    p.add_argument('--score_class', action='append', default=None, metavar='LABELS',
+                   help='score: one class per switch, repeatable (at most 8): the voxels whose value is one of LABELS '
+                        '(1 to 255, comma separated); brats: 1,2,4  1,4  4 (WT, TC, ET), lits: 1,2  2 (liver, tumour)')
+    p.add_argument('--score_tol', default=None, metavar='T[,T...]',
+                   help='score: the tolerances in mm of the normalised surface Dice (at most 8, default 1), one column '
+                        'nsd_<T>mm each; none: no such column')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
@@ -258,6 +267,104 @@ def prob_switches(args, mission=None):
                              f'working grid (--save_nii writes its label maps), it belongs to the predict mission: drop '
                              f'--{switch}')
     return got
+
+
+SCORE_MAX_CLASSES = 8        # effq_hip.h: EFFQ_SEG_TALLIES_MAX_CLASSES
+SCORE_MAX_TOLS = 8           # effq_hip.h: EFFQ_SURF_TOL_MAX
+SCORE_SWITCHES = ('pred_dir', 'score_class', 'score_tol')
+# the label values of every class of a task's maps (brats: WT, TC, ET - evaluate.post_class_lut('brats', 3); lits: the
+# liver with its tumours, the tumours)
+SCORE_CLASSES = {'brats': ((1, 2, 4), (1, 4), (4,)), 'lits': ((1, 2), (2,))}
+SCORE_TOL_DEFAULT = (1.0,)
+# switches of the other missions that decide, clean or write maps: (name, the value that means "not given")
+SCORE_FOREIGN = (('post', None), ('thresh', None), ('thr_sweep', False), ('save_prob', False), ('save_unc', False),
+                 ('lesion_match', False), ('lesion_table', False), ('blend', 'uniform'), ('tta_mirror', None),
+                 ('resume', None), ('pretrain', None), ('prep_mask', None), ('prep_window', None), ('prep_orient', None),
+                 ('prep_spacing', None), ('prep_antialias', False), ('prep_interp', 'linear'), ('prep_min_size', None),
+                 ('prep_no_crop', False))
+
+
+def parse_score_class(text) -> tuple:
+    """The label values of one --score_class LABELS (a comma separated string, or a YAML list or integer); what is not
+    understood is refused by name (SystemExit)."""
+    parts = [str(v) for v in text] if isinstance(text, (list, tuple)) else str(text).split(',')
+    labels = []
+    for v in parts:
+        if not re.fullmatch(r'\s*\d+\s*', v) or not 1 <= int(v) <= 255:
+            raise SystemExit(f'--score_class {text!r}: label {v.strip()!r}: the label values of a class are 1 to 255')
+        if int(v) in labels:
+            raise SystemExit(f'--score_class {text!r}: label {int(v)} is given twice')
+        labels.append(int(v))
+    return tuple(labels)
+
+
+def parse_score_tol(value) -> tuple:
+    """The tolerances in mm of --score_tol T[,T...] (or a YAML number or list), sorted ascending; () for `none`.  What is
+    not understood is refused by name (SystemExit)."""
+    import math
+    if value is None:
+        return SCORE_TOL_DEFAULT
+    if isinstance(value, str) and value.strip().lower() == 'none':
+        return ()
+    parts = list(value) if isinstance(value, (list, tuple)) else str(value).split(',')
+    tols = []
+    for v in parts:
+        try:
+            t = float(v)
+        except (TypeError, ValueError):
+            raise SystemExit(f'--score_tol {value!r}: {str(v).strip()!r} is no number: tolerances in mm, comma separated, '
+                             f'or none')
+        if not math.isfinite(t) or t < 0:
+            raise SystemExit(f'--score_tol {value!r}: {str(v).strip()}: a tolerance is finite and >= 0 (millimetres)')
+        if t in tols:
+            raise SystemExit(f'--score_tol {value!r}: {t:g} is given twice')
+        tols.append(t)
+    if not 1 <= len(tols) <= SCORE_MAX_TOLS:
+        raise SystemExit(f'--score_tol {value!r}: {len(tols)} tolerances, 1 to {SCORE_MAX_TOLS} (or none)')
+    if len({'%g' % t for t in tols}) != len(tols):
+        raise SystemExit(f'--score_tol {value!r}: two tolerances print alike (%g) and would share a column')
+    return tuple(sorted(tols))
+
+
+def score_class_lut(classes) -> list:
+    """The 256-entry class table of effq_label_tallies for `classes`: bit c set = the value is one of classes[c]."""
+    lut = [0] * 256
+    for c, labels in enumerate(classes):
+        for v in labels:
+            lut[v] |= 1 << c
+    return lut
+
+
+def score_switches(args, mission=None):
+    """(classes, tolerances) of --score_class / --score_tol (or the YAML keys `score_class`, a list, and `score_tol`) for
+    the score mission: a tuple of label-value tuples (the task's default without the switch) and the tolerances in mm,
+    ascending.  The other missions refuse --pred_dir, --score_class and --score_tol by name, and the score mission
+    refuses every switch that decides, cleans or writes maps (SystemExit), host only."""
+    mission = mission or getattr(args, 'mission', None)
+    if mission != 'score':
+        for switch in SCORE_SWITCHES:
+            if getattr(args, switch, None) is not None:
+                raise SystemExit(f'--{switch} belongs to the score mission, which scores finished maps against labels: '
+                                 f'the {mission} mission scores nothing with it, drop --{switch}')
+        return None
+    for switch, unset in SCORE_FOREIGN:
+        got = getattr(args, switch, unset)
+        if got is not None and got != unset and got != []:
+            raise SystemExit(f'--{switch} decides, cleans or writes maps: the score mission reads finished maps as they '
+                             f'are (--pred_dir) and changes none, drop --{switch}')
+    task = (getattr(args, 'task', None) or '').lower()
+    given = getattr(args, 'score_class', None)
+    if given is None or given == []:
+        if task not in SCORE_CLASSES:
+            raise SystemExit(f'score: --task {getattr(args, "task", None)!r}, one of {", ".join(SCORE_CLASSES)}')
+        classes = SCORE_CLASSES[task]
+    else:
+        if isinstance(given, (str, int)):
+            given = [given]
+        if len(given) > SCORE_MAX_CLASSES:
+            raise SystemExit(f'--score_class: {len(given)} classes, at most {SCORE_MAX_CLASSES}')
+        classes = tuple(parse_score_class(t) for t in given)
+    return classes, parse_score_tol(getattr(args, 'score_tol', None))
 
 
 POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES

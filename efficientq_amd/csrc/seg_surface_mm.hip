@@ -5,9 +5,13 @@
 //   masks, surface   the decision bits (seg_masks.h) and the 6-neighbour stencil (seg_surf.h), as effq_seg_surface
 //   rows, lines      the three separable passes of seg_surf.h with the metric EdtMm: fl(g(j) + fl(wa (i - j)^2)) in fp32
 //   reduce           k_mm_scan, then k_mm_select / k_mm_hist over 8 + 8 + 8 + 8 bits of the pattern, k_mm_next, k_mm_final
+// effq_label_surface_mm takes its decision bits from two label maps (label_bits.h) and runs the same launches after them
+// (mm_surface_run); with tolerances it then counts the surface voxels within each: k_surf_within, k_surf_within_final
+// (DESIGN section 26).
 #include <cmath>
 
 #include "common.h"
+#include "label_bits.h"
 #include "seg_decide.h"
 #include "seg_masks.h"
 #include "seg_surf.h"
@@ -276,6 +280,58 @@ __global__ __launch_bounds__(MM_THREADS) void k_mm_final(MmRed r, int nblocks, l
   }
 }
 
+// ---- surface voxels within a tolerance (effq_label_surface_mm) --------------------------------------------------------
+constexpr int MM_TOLS = EFFQ_SURF_TOL_MAX;
+constexpr int MM_WITHIN = 2 * MM_CLASSES * (MM_TOLS + 1);              // counters: (row 2 c + dir, first tolerance)
+static_assert(MM_WITHIN == 144, "the LDS counters of k_surf_within");
+
+struct MmTols {
+  float sq[MM_TOLS];             // ascending; entries n .. are unused
+  int n;
+};
+
+// A surface voxel of row 2 c + dir adds 1 at the first tolerance that holds its stored distance (fp32 <=), at n when
+// none does (+inf among them): the tolerances ascend, so that is the number of tolerances it exceeds.  LDS counters per
+// workgroup, then integer adds into the workspace.  One voxel per lane, as k_mm_scan walks the surface bits: the
+// distances of neighbouring surface voxels of a row are then read by neighbouring lanes.
+__global__ __launch_bounds__(MM_THREADS) void k_surf_within(const uint16_t* __restrict__ surf,
+                                                            const float* __restrict__ sq, int C, int S, MmTols tol,
+                                                            unsigned long long* __restrict__ within) {
+  __shared__ uint32_t s_cnt[MM_WITHIN];
+  for (int k = threadIdx.x; k < MM_WITHIN; k += MM_THREADS) s_cnt[k] = 0;
+  __syncthreads();
+  for (long long i = (long long)blockIdx.x * MM_THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * MM_THREADS) {
+    const uint32_t b = surf[i];
+    if (!b) continue;
+    for (int c = 0; c < C; ++c) {
+#pragma unroll
+      for (int dir = 0; dir < 2; ++dir) {
+        if (!((b >> (dir ? 8 + c : c)) & 1)) continue;
+        const float e = __uint_as_float(mm_value(sq, C, (size_t)S, c, dir, (size_t)i));
+        int first = 0;
+#pragma unroll
+        for (int k = 0; k < MM_TOLS; ++k) first += (k < tol.n && !(e <= tol.sq[k])) ? 1 : 0;
+        atomicAdd(&s_cnt[(2 * c + dir) * (MM_TOLS + 1) + first], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < MM_WITHIN; k += MM_THREADS)
+    if (s_cnt[k]) atomicAdd(&within[k], (unsigned long long)s_cnt[k]);
+}
+
+// out (C, 2, n): the prefix sums over the tolerances of the counters of row 2 c + dir, one thread per row
+__global__ __launch_bounds__(64) void k_surf_within_final(const unsigned long long* __restrict__ within, int C, int n,
+                                                          long long* __restrict__ out) {
+  const int row = threadIdx.x;
+  if (row >= 2 * C) return;
+  unsigned long long run = 0;
+  for (int k = 0; k < n; ++k) {
+    run += within[row * (MM_TOLS + 1) + k];
+    out[(size_t)row * n + k] = (long long)run;
+  }
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------
 static bool mm_dims_ok(int P, int D, int H, int W) {
   return P > 0 && P <= 65535 && D > 0 && H > 0 && W > 0 && D <= EFFQ_EDT_MM_MAX_EXTENT && H <= EFFQ_EDT_MM_MAX_EXTENT &&
@@ -287,6 +343,57 @@ static bool mm_weight_ok(float w) { return std::isfinite(w) && w > 0.0f; }
 template <int C>
 static void launch_scan(dim3 g, hipStream_t st, const uint16_t* surf, const float* sq, int S, const MmRed& r) {
   hipLaunchKernelGGL((k_mm_scan<C>), g, dim3(MM_THREADS), 0, st, surf, sq, S, r);
+}
+
+// Everything after the decision bits in s.bits (the counters of s already cleared): surface stencil, the three passes,
+// scan, select / hist, next, final.  One sequence for the bits of logits and of label maps.
+static int mm_surface_run(const MmWs& s, int C, int D, int H, int W, float wd, float wh, float ww, long long* counts,
+                          float* sq, double* sums, hipStream_t st) {
+  const int P = 2 * C;
+  const size_t S = (size_t)D * H * W;
+  const dim3 gs(cc_grid(S, CC_STREAM_BLOCKS)), b(CC_THREADS);
+  hipLaunchKernelGGL(k_surf_bits, gs, b, 0, st, s.bits, s.surf, D, H, W);
+  EFFQ_LAUNCH_CHECK();
+  EdtSrc src;
+  src.masks = nullptr; src.surf = s.surf; src.C = C;
+  const int rc = edt_run<EdtMm>(src, P, D, H, W, wd, wh, ww, s.sq, st);
+  if (rc != EFFQ_OK) return rc;
+  const dim3 g(cc_grid(S, MM_SCAN_BLOCKS)), t(MM_THREADS);
+  switch (C) {
+    case 1: launch_scan<1>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 2: launch_scan<2>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 3: launch_scan<3>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 4: launch_scan<4>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 5: launch_scan<5>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 6: launch_scan<6>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    case 7: launch_scan<7>(g, st, s.surf, s.sq, (int)S, s.red); break;
+    default: launch_scan<8>(g, st, s.surf, s.sq, (int)S, s.red); break;
+  }
+  EFFQ_LAUNCH_CHECK();
+  for (int stage = 0; stage < MM_STAGES; ++stage) {
+    if (stage > 0) {
+      hipLaunchKernelGGL(k_mm_hist, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red, stage);
+      EFFQ_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_mm_select, dim3(C), dim3(MM_BINS), 0, st, s.red, stage);
+    EFFQ_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_mm_next, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red);
+  EFFQ_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mm_final, dim3(C), t, 0, st, s.red, (int)g.x, counts, sq, sums);
+  EFFQ_LAUNCH_CHECK();
+  return EFFQ_OK;
+}
+
+// the workspace of effq_label_surface_mm: that of effq_seg_surface_mm, then the counters of k_surf_within
+static size_t mm_within_offset(int C, int D, int H, int W) { return mm_align16(mm_ws(nullptr, 2 * C, D, H, W).bytes); }
+constexpr size_t MM_WITHIN_BYTES = MM_WITHIN * sizeof(unsigned long long);
+
+static bool mm_tols_ok(const float* tol_sq, int ntol) {
+  if (ntol < 0 || ntol > MM_TOLS || (ntol > 0 && !tol_sq)) return false;
+  for (int k = 0; k < ntol; ++k)
+    if (!std::isfinite(tol_sq[k]) || tol_sq[k] < 0.0f || (k > 0 && !(tol_sq[k] > tol_sq[k - 1]))) return false;
+  return true;
 }
 
 }  // namespace effq
@@ -324,38 +431,44 @@ int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D,
   EFFQ_CHECK_ARG(ws_bytes >= s.bytes);
   const hipStream_t st = as_stream(stream);
   EFFQ_HIP(hipMemsetAsync(s.zeroed, 0, s.zeroed_bytes, st));
-  int rc = cc_decision_bits(logits, label, C, S, mode, fuse, thresh, s.bits, st);
+  const int rc = cc_decision_bits(logits, label, C, S, mode, fuse, thresh, s.bits, st);
   if (rc != EFFQ_OK) return rc;
-  const dim3 gs(cc_grid(S, CC_STREAM_BLOCKS)), b(CC_THREADS);
-  hipLaunchKernelGGL(k_surf_bits, gs, b, 0, st, s.bits, s.surf, D, H, W);
-  EFFQ_LAUNCH_CHECK();
-  EdtSrc src;
-  src.masks = nullptr; src.surf = s.surf; src.C = C;
-  rc = edt_run<EdtMm>(src, P, D, H, W, wd, wh, ww, s.sq, st);
+  return mm_surface_run(s, C, D, H, W, wd, wh, ww, counts, sq, sums, st);
+}
+
+size_t effq_label_surface_mm_ws_bytes(int C, int D, int H, int W, int ntol) {
+  if (C <= 0 || C > EFFQ_SEG_TALLIES_MAX_CLASSES || ntol < 0 || ntol > MM_TOLS || !mm_dims_ok(2 * C, D, H, W)) return 0;
+  return mm_within_offset(C, D, H, W) + MM_WITHIN_BYTES;
+}
+
+int effq_label_surface_mm(const uint8_t* pred, const uint8_t* truth, int C, int D, int H, int W, const uint16_t* lut,
+                          float wd, float wh, float ww, const float* tol_sq, int ntol, long long* counts, float* sq,
+                          double* sums, long long* within, void* ws, size_t ws_bytes, void* stream) {
+  EFFQ_CHECK_ARG(pred && truth && lut && counts && sq && sums && ws && C > 0 && C <= EFFQ_SEG_TALLIES_MAX_CLASSES);
+  EFFQ_CHECK_ARG(mm_dims_ok(2 * C, D, H, W));
+  EFFQ_CHECK_ARG(mm_weight_ok(wd) && mm_weight_ok(wh) && mm_weight_ok(ww));
+  EFFQ_CHECK_ARG(mm_tols_ok(tol_sq, ntol) && (ntol == 0 || within));
+  EFFQ_CHECK_ARG(label_lut_ok(lut, C));
+  EFFQ_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 15) == 0);          // 8-B loads of the surface bits, 8-B counters
+  EFFQ_CHECK_ARG(ws_bytes >= effq_label_surface_mm_ws_bytes(C, D, H, W, ntol));
+  const size_t S = (size_t)D * H * W;
+  const MmWs s = mm_ws(ws, 2 * C, D, H, W);
+  const hipStream_t st = as_stream(stream);
+  EFFQ_HIP(hipMemsetAsync(s.zeroed, 0, s.zeroed_bytes, st));
+  int rc = label_decision_bits(pred, truth, lut, S, s.bits, st);
   if (rc != EFFQ_OK) return rc;
-  const dim3 g(cc_grid(S, MM_SCAN_BLOCKS)), t(MM_THREADS);
-  switch (C) {
-    case 1: launch_scan<1>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 2: launch_scan<2>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 3: launch_scan<3>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 4: launch_scan<4>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 5: launch_scan<5>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 6: launch_scan<6>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    case 7: launch_scan<7>(g, st, s.surf, s.sq, (int)S, s.red); break;
-    default: launch_scan<8>(g, st, s.surf, s.sq, (int)S, s.red); break;
-  }
+  rc = mm_surface_run(s, C, D, H, W, wd, wh, ww, counts, sq, sums, st);
+  if (rc != EFFQ_OK || ntol == 0) return rc;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + mm_within_offset(C, D, H, W));
+  EFFQ_HIP(hipMemsetAsync(cnt, 0, MM_WITHIN_BYTES, st));
+  MmTols tol;
+  tol.n = ntol;
+  for (int k = 0; k < MM_TOLS; ++k) tol.sq[k] = k < ntol ? tol_sq[k] : 0.0f;
+  // the grid of the scans: every workgroup ends with up to 2 C (ntol + 1) adds on the same few words
+  hipLaunchKernelGGL(k_surf_within, dim3(cc_grid(S, MM_SCAN_BLOCKS)), dim3(MM_THREADS), 0, st, s.surf, s.sq, C, (int)S,
+                     tol, cnt);
   EFFQ_LAUNCH_CHECK();
-  for (int stage = 0; stage < MM_STAGES; ++stage) {
-    if (stage > 0) {
-      hipLaunchKernelGGL(k_mm_hist, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red, stage);
-      EFFQ_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_mm_select, dim3(C), dim3(MM_BINS), 0, st, s.red, stage);
-    EFFQ_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_mm_next, g, t, 0, st, s.surf, s.sq, C, (int)S, s.red);
-  EFFQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_mm_final, dim3(C), t, 0, st, s.red, (int)g.x, counts, sq, sums);
+  hipLaunchKernelGGL(k_surf_within_final, dim3(1), dim3(64), 0, st, cnt, C, ntol, within);
   EFFQ_LAUNCH_CHECK();
   return EFFQ_OK;
 }

@@ -58,6 +58,13 @@ subject on the scan's own grid, with the scan's header, and ``predict.csv``:
 
     python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/
+
+The ``score`` mission (score.py) scores finished label maps - those of ``predict``, or of any other tool - against the
+``seg`` column of the same list, on the scan's own grid: Dice, lesion counts, surface distances in millimetres and the
+normalised surface Dice at ``--score_tol`` per subject and class in ``score/scores.csv``, the means in ``summary.csv``:
+
+    python -m efficientq_amd.entrance score --task lits --src_list cases.csv --pred_dir seg/ --out_dir score/ \
+        --score_tol 1,3
 """
 from __future__ import annotations
 
@@ -211,6 +218,7 @@ def _switches(args):
     thr = Cf.thr_switches(args)
     Cf.prob_switches(args)
     match = Cf.match_switches(args)
+    Cf.score_switches(args, 'ptq')
     if getattr(args, 'unlabelled', False):
         if not getattr(args, 'vs_fp', False):
             raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add '
@@ -259,14 +267,20 @@ def main(argv=None):
         Cf.thr_switches(args)
         Cf.prob_switches(args)
         Cf.match_switches(args)
+        Cf.score_switches(args)
         from . import prep
         prep.run(args)
         return
     if args.mission == 'predict':       # refused ahead of predict.run's own checks, which hold for a direct caller too
         Cf.thr_switches(args)
         Cf.match_switches(args)
+        Cf.score_switches(args)
         from . import predict
         predict.run(args)
+        return
+    if args.mission == 'score':         # score.run refuses the switches of the other missions itself (score_switches)
+        from . import score
+        score.run(args)
         return
     if args.mission != 'ptq':
         raise NotImplementedError(args.mission)

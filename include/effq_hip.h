@@ -975,6 +975,41 @@ int effq_seg_surface_mm(const float* logits, const uint8_t* label, int C, int D,
                         float thresh, float wd, float wh, float ww, long long* counts, float* sq, double* sums, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- scoring a finished label map against a label map on one grid (the `score` mission).  pred and
+ * truth (D, H, W) uint8 label values; lut: 256 uint16 on the host, read before the call returns, bit c set = that label
+ * value belongs to class c (effq_label_tallies' table; a voxel may sit in several classes), every entry < 1 << C.  One
+ * launch makes the decision bits of seg_masks.h from the two maps, bits[v] = (lut[pred[v]] & 0xff) | (lut[truth[v]] & 0xff)
+ * << 8 (4-B loads and one 8-B store when both maps are 4-B aligned, the last S % 4 voxels one by one); everything after
+ * it is the launches of the entry point that takes logits, on those bits.  1 <= C <= EFFQ_SEG_TALLIES_MAX_CLASSES.  The
+ * Dice tallies of the same maps are effq_label_tallies'.
+ *
+ * effq_label_lesions: counts (C, 4) int64 = totall, predl, fnl, fpl, meaning and layout of effq_seg_lesions.  ws:
+ *   effq_cc_ws_bytes(2 C, D, H, W).  Bad arguments (those of effq_seg_lesions, a table entry with a bit at or above C)
+ *   return EFFQ_ERR_ARG, a short workspace EFFQ_ERR_WORKSPACE; both launch nothing and leave counts as it was.
+ * effq_label_surface_mm: P, L, S(M), E_M, the weights and counts (C, 2), sq (C, 4), sums (C, 2) as effq_seg_surface_mm:
+ *   for equal decision bits the same launches and the same bits.  tol_sq: ntol fp32 squared tolerances in mm^2 on the
+ *   host, read before the call returns, float32(float64(tol_mm) ** 2); 0 <= ntol <= EFFQ_SURF_TOL_MAX, each finite and
+ *   >= 0, strictly ascending.  within (C, 2, ntol) int64: within[c][0][k] = the voxels of S(P) of class c with E_L(v) <=
+ *   tol_sq[k], within[c][1][k] = those of S(L) with E_P(v) <= tol_sq[k]; the comparison is in fp32 on the stored
+ *   distance, and a +inf distance (the target has no surface) is never within.  The normalised surface Dice at
+ *   tolerance k is (within[c][0][k] + within[c][1][k]) / (nP + nL) on the host.  ntol == 0 launches nothing for it and
+ *   leaves within untouched; it may then be null.  Two more launches: every surface voxel adds 1 at the first tolerance
+ *   that holds it in LDS counters of its workgroup, which are added to int64 counters of the workspace; one small launch
+ *   takes the prefix sums.  Integer adds only: equal inputs give equal bits.  No read by the host, no workgroup that
+ *   waits for another.
+ *   ws: effq_label_surface_mm_ws_bytes(C, D, H, W, ntol) bytes, 16-B aligned: effq_surf_mm_ws_bytes(2 C, D, H, W) and
+ *   1152 B of counters; 0 for what the call refuses.  It may hold anything on entry.  Bad arguments (those of
+ *   effq_seg_surface_mm, a table entry with a bit at or above C, ntol out of range, a tolerance that is negative, NaN,
+ *   infinite or not above the one before it) and a short workspace return EFFQ_ERR_ARG, launch nothing and leave every
+ *   output as it was. */
+#define EFFQ_SURF_TOL_MAX 8
+int effq_label_lesions(const uint8_t* pred, const uint8_t* truth, int C, int D, int H, int W, const uint16_t* lut,
+                       int connectivity, long long* counts, void* ws, size_t ws_bytes, void* stream);
+size_t effq_label_surface_mm_ws_bytes(int C, int D, int H, int W, int ntol);
+int effq_label_surface_mm(const uint8_t* pred, const uint8_t* truth, int C, int D, int H, int W, const uint16_t* lut,
+                          float wd, float wh, float ww, const float* tol_sq, int ntol, long long* counts, float* sq,
+                          double* sums, long long* within, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the `prep` mission (prep.py): source scans to the standardised, cropped arrays the `ptq` mission reads.  One
  * subject at a time: x (C, D, H, W) fp32, contiguous, S = D H W voxels per modality, C <= EFFQ_PREP_MAX_MODALITIES,
  * C S < 2^31, every extent <= 32767.  mask_mode EFFQ_PREP_MASK_NONZERO: the mask of modality c is x_c != 0 (a NaN is
