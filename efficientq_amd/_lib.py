@@ -242,6 +242,7 @@ SIGNATURES = {
     "effq_prep_resample_cubic": (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _I, _P, _I, _I, _I, _P, _SZ, _P]),
     "effq_prep_reorient": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "effq_prep_reorient_plan": (_I, [_P, _I, _I, _P]),
+    "effq_prep_align": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges

@@ -112,6 +112,10 @@ def build_parser():
                    help='prep, predict: linear (trilinear, the default) or cubic (with --prep_spacing): the images are '
                         'resampled by cubic B-spline interpolation, as scipy and skimage do at order=3 with mode mirror; '
                         'the label stays nearest')
+    p.add_argument('--prep_align', default=None, metavar='MODALITY',
+                   help='prep, predict: the reference modality; every other modality (and the label) whose header lies '
+                        'on another grid is resampled onto the reference\'s grid by the affines as they stand '
+                        '(trilinear, the label nearest); no registration')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
     # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint
@@ -282,6 +286,8 @@ SCORE_FOREIGN = (('post', None), ('thresh', None), ('thr_sweep', False), ('save_
                  ('resume', None), ('pretrain', None), ('prep_mask', None), ('prep_window', None), ('prep_orient', None),
                  ('prep_spacing', None), ('prep_antialias', False), ('prep_interp', 'linear'), ('prep_min_size', None),
                  ('prep_no_crop', False))
+# refused like those; kept apart because tests/test_score_cpu.py pins the members of SCORE_FOREIGN
+SCORE_FOREIGN_ALIGN = (('prep_align', None),)
 
 
 def parse_score_class(text) -> tuple:
@@ -347,7 +353,7 @@ def score_switches(args, mission=None):
                 raise SystemExit(f'--{switch} belongs to the score mission, which scores finished maps against labels: '
                                  f'the {mission} mission scores nothing with it, drop --{switch}')
         return None
-    for switch, unset in SCORE_FOREIGN:
+    for switch, unset in SCORE_FOREIGN + SCORE_FOREIGN_ALIGN:
         got = getattr(args, switch, unset)
         if got is not None and got != unset and got != []:
             raise SystemExit(f'--{switch} decides, cleans or writes maps: the score mission reads finished maps as they '

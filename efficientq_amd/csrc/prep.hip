@@ -22,8 +22,6 @@ constexpr int PREP_MAXC = EFFQ_PREP_MAX_MODALITIES;
 // per workgroup: PREP_MAXC sums, PREP_MAXC counts, the six box values
 static_assert((size_t)PREP_MAX_BLOCKS * (PREP_MAXC * 8 + PREP_MAXC * 8 + 8 * 4) <= EFFQ_PREP_WS_BYTES, "workspace");
 
-struct __attribute__((packed, aligned(1))) PByte4 { uint8_t x, y, z, w; };
-
 struct PrepWs {
   double* sum;        // (PREP_MAX_BLOCKS, PREP_MAXC)
   long long* cnt;     // (PREP_MAX_BLOCKS, PREP_MAXC)

@@ -1,5 +1,5 @@
-// What the prep kernels share (prep.hip, prep_smooth.hip, prep_quantile.hip): the launch shape, the 16-B vector of 4-B
-// alignment, the mask, the item of four consecutive w of one row, and the argument checks of the extents and the pointers.
+// What the prep kernels share (prep.hip, prep_smooth.hip, prep_quantile.hip, prep_align.hip): the launch shape, the 16-B
+// vector of 4-B alignment, the mask, the item of four consecutive w of one row, and the argument checks of the extents and the pointers.
 #pragma once
 #include "common.h"
 
@@ -10,6 +10,7 @@ constexpr int PREP_WAVES = PREP_THREADS / 64;
 constexpr int PREP_MAX_BLOCKS = 1024;
 
 struct __attribute__((packed, aligned(4))) PFloat4 { float x, y, z, w; };    // 16 B at any 4-B boundary
+struct __attribute__((packed, aligned(1))) PByte4 { uint8_t x, y, z, w; };    // four labels at any byte
 
 static inline unsigned prep_grid(size_t groups) {
   size_t nb = (groups + PREP_THREADS - 1) / PREP_THREADS;

@@ -3,7 +3,8 @@
     python -m efficientq_amd.entrance predict --config config/lits_ptq.yaml --qlvl_w 4 --qlvl_a 4 \
         --resume out/state_in_fp.pkl --src_list new_cases.csv --out_dir seg/ \
         [--prep_window -200,250 --prep_spacing 1,1,2.5 --prep_mask all --prep_min_size d,h,w --patch_size d,h,w]
-        [--prep_orient RAS] [--prep_antialias] [--prep_interp cubic] [--blend gauss --tta_mirror hw]
+        [--prep_align MODALITY] [--prep_orient RAS] [--prep_antialias] [--prep_interp cubic]
+        [--blend gauss --tta_mirror hw]
 
 ``--src_list`` is the CSV of the ``prep`` mission (prep.read_src_list; a ``seg`` column is allowed and ignored).  The
 ``--prep_*`` switches and ``--patch_size`` mean what they mean in ``prep`` and ``ptq`` and have the same per-task
@@ -14,7 +15,8 @@ calibrate.load_calibrated) and ``--pretrain`` with ``--qconv conv`` (the FP chec
 Per subject: the scans are read (the next subject's by one background thread, prep.read_subjects), windowed, resampled,
 standardised and cropped in memory (prep.process_subject under prep.PrepOptions, the option set prep shares), the windows
 of the crop run through the network and the last head is stitched (window.stitched_window_logits), and effq_seg_labels_source turns the stitched logits on the working grid into one
-label per voxel of the scan's own grid: ``<out_dir>/<subject>.nii.gz``, uint8, with the header of the first modality,
+label per voxel of the scan's own grid: ``<out_dir>/<subject>.nii.gz``, uint8, with the header of the first modality
+(of the reference under ``--prep_align``),
 written by a background thread (nifti.BackgroundWriter).  ``<out_dir>/predict.csv`` gets one row per subject: the source shape and spacing, the
 grid, the box, the number of windows, the prep options used, and per label value present in the map its voxel count
 (counted on the device) and its volume in ml.
@@ -35,6 +37,12 @@ three array axes, ``0 0 0`` for a subject with nothing to filter) after the orie
 the ``antialias`` column's place and before those of ``--blend``; the step back to the scan's grid stays trilinear on
 the logits.  ``linear``, the default, changes nothing; another value, or cubic without ``--prep_spacing``, is refused by
 name.
+
+``--prep_align MODALITY`` names the reference modality as in ``prep``: every other modality whose header lies on another
+grid is resampled onto the reference's grid by the affines as they stand (effq_prep_align; no registration), before
+everything else.  The map is written on the reference's grid with the reference's header.  ``predict.csv`` then gains
+the columns ``align`` and ``align_inside`` (per modality the voxels of the grid inside that scan's field of view) after
+the ``interp`` column's place and before ``window_bounds`` and those of ``--blend``.
 
 ``--prep_window pLO,pHI`` (``p0.5,p99.5``) clips every modality of every scan to a pair of its own percentiles over its
 own mask as ``prep`` does (pass what the calibration data was prepared with).  The column ``prep_window`` then reads

@@ -2,13 +2,18 @@
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
         [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|pLO,pHI|none] \
-        [--prep_orient RAS] [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
+        [--prep_align MODALITY] [--prep_orient RAS] \
+        [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
         [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
 ``--src_list`` is a CSV with the header ``subject,<modality>,...[,seg]`` (the task's modalities, data.MODALITIES, in any
 order) and one row per subject with one NIfTI path per column, relative to the CSV unless absolute; an empty ``seg``
 cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
 
+    align      --prep_align MODALITY: every other modality, and the label, whose header does not lie on the grid of
+               MODALITY (the reference) is resampled onto it by the two affines as they stand, trilinear for the images,
+               nearest for the label, 0 outside the scan's field of view (the rule below at ALIGN_COLUMNS;
+               csrc/prep_align.hip); no registration, and no filter when the reference is the coarser grid
     reorient   --prep_orient CODE: the axes permuted and reversed (csrc/reorient.hip) so that array axis 0, 1, 2 runs
                towards the three letters of CODE (one each of R/L, A/P, S/I: RAS, LPS, SAR, ...), whatever orientation
                the scan's affine gives it; --prep_spacing and --prep_min_size then refer to the oriented axes
@@ -38,8 +43,12 @@ also one that was oriented as asked already), and prep.csv gains the columns ``s
 With ``--prep_antialias`` prep.csv gains the column ``antialias`` after all others: the sigmas of the three array axes
 in voxels of the source grid, ``0 0 0`` for a subject no axis of which is down-sampled far enough to be filtered.
 With ``--prep_interp cubic`` prep.csv gains the column ``interp`` (``cubic``) after all others, the anti-alias column
-included.  With ``--prep_window pLO,pHI`` prep.csv gains ``<modality>_win_lo`` and ``<modality>_win_hi`` per modality
-(``repr(float)``) after all others, ``interp`` included.  A NaN or an Inf in a scan is carried along whole lines by the
+included.  With ``--prep_align`` prep.csv gains the columns ``align`` (the reference) and ``align_inside`` (per modality
+in the task's order, then the label: the voxels of the reference grid inside that scan's field of view, the whole grid
+for one that was not resampled) after ``interp``, and "the first modality" above is the reference: its shape, spacing,
+affine and header are the subject's, and sn_fn.txt names its scan.  With ``--prep_window pLO,pHI`` prep.csv gains
+``<modality>_win_lo`` and ``<modality>_win_hi`` per modality (``repr(float)``) after all others, ``interp`` and the
+align columns included.  A NaN or an Inf in a scan is carried along whole lines by the
 spline's recursions; the check of the standard deviation then stops the run at that subject.
 ``--split_dir --val_every K`` also writes ``split_dir/round<R>/{train,val}.txt``.
 
@@ -47,7 +56,7 @@ What the headers decide (the list itself, shapes and affines within a subject, a
 split that already exists) is checked for every subject before anything is written.  What only the voxels decide (an
 empty mask, a constant modality, a percentile bound that is not finite or, with the mask ``nonzero``, exactly 0) stops
 the run at that subject: none of its files and none of the files written at the end exist then.  The next subject's
-files are read and gunzipped by one background thread while the device works (read_subjects).  The eight --prep_*
+files are read and gunzipped by one background thread while the device works (read_subjects).  The nine --prep_*
 options are one record, PrepOptions (parse_options), which the ``predict`` mission parses and uses the same way.
 There is no CPU path: `ops` is hip_ops.get_ops(device) unless a caller passes its own.
 """
@@ -61,6 +70,7 @@ import pickle
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 from contextlib import closing
+from functools import partial
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -68,6 +78,7 @@ import torch
 
 from . import data as D
 from . import nifti
+from . import ops_align
 
 GRID_DIR = "grid"
 PREP_CSV = "prep.csv"
@@ -370,6 +381,60 @@ def orient_affine(affine, src_axis: Sequence[int], flip: Sequence[bool], shape: 
     return np.asarray(affine, dtype=np.float64) @ t
 
 
+# ---- alignment by the headers (host, no device) -------------------------------------------------------------------------
+# The one definition of the rule of --prep_align MODALITY; include/effq_hip.h (effq_prep_align) restates the device half.
+# 1 MODALITY names the reference.  A modality, or the label, whose header passes check_same_grid against the reference's is
+#   used as it is, bit for bit.  For any other the plan holds M = inv(A_src) A_ref (align_matrix: 3 x 4, fp64), which maps
+#   a voxel index (d, h, w, 1) of the reference grid to voxel coordinates of the source.  The affines are believed as
+#   they stand: this is no registration.
+# 2 The step comes first, on the scans' own axes, before --prep_orient; everything after it sees one grid.
+# 3 Per voxel of the reference grid and source axis a, in fp64 and in this order:
+#   s_a = ((M[a][0] d + M[a][1] h) + M[a][2] w) + M[a][3].  The voxel is inside the source's field of view when
+#   -0.5 <= s_a < n_a - 0.5 on all three axes (n the source extent); outside it the result is +0.0, the background of
+#   --prep_mask nonzero, or label 0.  `<` at the upper end: every source voxel owns the half voxel on either side of its
+#   centre, the lower end included and the upper excluded, so the nearest index floor(s_a + 0.5) never reaches n_a.
+# 4 Inside, an image is trilinear: c = clamp(s_a, 0, n_a - 1) (the edge replicated over the outer half voxel), i0 =
+#   floor(c), i1 = min(i0 + 1, n_a - 1), l1 = float32(c - i0), l0 = 1 - l1 in fp32, the eight neighbours combined in fp32 in
+#   the order of --prep_spacing's trilinear step.  The label takes the voxel floor(s_a + 0.5), at most n_a - 1.
+# 5 Nothing is filtered when the reference grid is the coarser one, and --prep_interp cubic and --prep_antialias keep
+#   their meaning: the --prep_spacing step only.
+# 6 The run stops before anything is written at an A_src with an entry that is not finite or a 3 x 3 part of determinant
+#   0, and at an M with an entry that is not finite; it stops at the subject when no voxel of the reference grid lies
+#   inside a resampled scan.
+ALIGN_COLUMNS = ["align", "align_inside"]      # prep.csv and predict.csv, only with --prep_align
+
+
+def align_switch(args, task: str) -> Optional[str]:
+    """--prep_align of `args` (or the YAML key): the reference modality, None when the switch is absent; anything but one
+    of the task's modalities is refused by name."""
+    ref = getattr(args, "prep_align", None)
+    if ref is None:
+        return None
+    if not isinstance(ref, str) or ref.strip() not in D.MODALITIES[task]:
+        raise PrepError(f"--prep_align {ref!r}: one of {', '.join(D.MODALITIES[task])}")
+    return ref.strip()
+
+
+def align_matrix(subject: str, name: str, a_src, a_ref) -> np.ndarray:
+    """M = inv(A_src) A_ref as 3 x 4 fp64 (numpy.linalg.solve(A_src, A_ref)[:3]): reference voxel indices (d, h, w, 1) to
+    voxel coordinates of the source `name`; step 6 of the rule refuses by subject and modality."""
+    who = f"subject {subject}: --prep_align: {name}"
+    a, r = np.asarray(a_src, dtype=np.float64), np.asarray(a_ref, dtype=np.float64)
+    if not np.all(np.isfinite(a)):
+        raise PrepError(f"{who}: its affine holds an entry that is not finite")
+    with np.errstate(all="ignore"):
+        if np.linalg.det(a[:3, :3]) == 0.0:
+            raise PrepError(f"{who}: the 3 x 3 part of its affine has determinant 0: its voxels have no place in the "
+                            f"world")
+        try:
+            m = np.linalg.solve(a, r)[:3]
+        except np.linalg.LinAlgError as e:
+            raise PrepError(f"{who}: its affine cannot be inverted: {e}") from e
+    if not np.all(np.isfinite(m)):
+        raise PrepError(f"{who}: the matrix from the reference's grid to its own holds an entry that is not finite")
+    return np.ascontiguousarray(m)
+
+
 # ---- the source list ---------------------------------------------------------------------------------------------------
 def read_src_list(path: str, task: str) -> List[dict]:
     """The rows of --src_list, sorted by subject: {subject, images: {modality: path}, seg: path or None}.  Everything the
@@ -461,7 +526,7 @@ class _Plan:
     """What the headers of one subject decide."""
 
     def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size, orient: Optional[str] = None,
-                 antialias: bool = False, interp: str = "linear"):
+                 antialias: bool = False, interp: str = "linear", align: Optional[str] = None):
         sn = self.subject = entry["subject"]
         self.interp = interp if spacing is not None else "linear"      # how the images are resampled (--prep_interp)
         self.window_bounds = None       # --prep_window pLO,pHI: (lo, hi) per modality, set by process_subject
@@ -478,14 +543,28 @@ class _Plan:
                 raise PrepError(f"subject {sn}: {name}: {path} has datatype {h['datatype']}, one of "
                                 f"{sorted(nifti.IMAGE_DATATYPES)} is read")
             heads[name] = h
-        first = heads[mods[0]]
+        # --prep_align: the reference stands where the first modality stands without the switch; a header on another grid is
+        # no refusal then but a matrix (align_matrix) and the source's own shape
+        self.ref = align if align is not None else mods[0]
+        self.align = {}                 # name -> (M, source shape) of what is resampled; empty without --prep_align
+        self.align_inside = None        # per modality, then the label: set by process_subject under --prep_align
+        self.shapes = {name: tuple(int(n) for n in h["shape"][:3]) for name, h in heads.items()}
+        first = heads[self.ref]
         for name, h in heads.items():
-            if name != mods[0]:
+            if name == self.ref:
+                continue
+            if align is None:
                 check_same_grid(sn, first, h, name)
+                continue
+            m = align_matrix(sn, name, h["affine"], first["affine"])      # refused here also when the grids would pass
+            try:
+                check_same_grid(sn, first, h, name)
+            except PrepError:
+                self.align[name] = (m, self.shapes[name])
         self.source_shape = tuple(int(n) for n in first["shape"][:3])
         self.source_spacing = tuple(first["spacing"])
         self.affine = first["affine"]
-        self.header = first             # nifti.read_geometry of the first modality: write_nifti(..., geometry=header)
+        self.header = first             # nifti.read_geometry of that modality: write_nifti(..., geometry=header)
         # --prep_orient: the scan's own code and the plan (src_axis, flip) that turns it into the target's; without the
         # switch the affine is not looked at (orient_code None) and the oriented values are the scan's own
         self.orient_code, self.orient = None, None
@@ -561,7 +640,7 @@ def read_subjects(plans: Sequence[_Plan], mods: Sequence[str], thread_name_prefi
 
 # ---- the options prep and predict share --------------------------------------------------------------------------------
 class PrepOptions(NamedTuple):
-    """The eight --prep_* options, as the ``prep`` and the ``predict`` mission both take them (parse_options)."""
+    """The nine --prep_* options, as the ``prep`` and the ``predict`` mission both take them (parse_options)."""
     mask: str                               # --prep_mask: nonzero | all
     window: object                          # --prep_window: None, (lo, hi) or a PercentileWindow
     spacing: Optional[tuple]                # --prep_spacing d,h,w
@@ -570,14 +649,15 @@ class PrepOptions(NamedTuple):
     orient: Optional[str] = None            # --prep_orient CODE
     antialias: bool = False                 # --prep_antialias
     interp: str = "linear"                  # --prep_interp linear | cubic
+    align: Optional[str] = None             # --prep_align MODALITY
 
     def plan(self, entry: dict, mods: Sequence[str]) -> _Plan:
-        return _Plan(entry, mods, self.spacing, self.min_size, self.orient, self.antialias, self.interp)
+        return _Plan(entry, mods, self.spacing, self.min_size, self.orient, self.antialias, self.interp, self.align)
 
     def columns(self) -> List[str]:
         """The optional columns of prep.csv and predict.csv that both missions write, in their order."""
         return (ORIENT_COLUMNS if self.orient else []) + (ANTIALIAS_COLUMNS if self.antialias else []) + \
-            (INTERP_COLUMNS if self.interp == "cubic" else [])
+            (INTERP_COLUMNS if self.interp == "cubic" else []) + (ALIGN_COLUMNS if self.align else [])
 
     def row_values(self, plan: _Plan) -> dict:
         """One subject's values of columns()."""
@@ -588,17 +668,26 @@ class PrepOptions(NamedTuple):
             row.update(antialias=_fmt(plan.sigmas))
         if self.interp == "cubic":
             row.update(interp=self.interp)
+        if self.align:
+            row.update(align=self.align, align_inside=_fmt(plan.align_inside))
         return row
 
     def said(self, plan: _Plan, mods: Sequence[str]) -> str:
         """What the per-subject line says after the source shape: "(LPS -> RAS)" when the scan was turned, every
-        modality's bounds of a percentile window, the filter's sigmas when any is above 0, "cubic"."""
+        modality's bounds of a percentile window, the filter's sigmas when any is above 0, "cubic", and what --prep_align
+        resampled with its share of the reference grid."""
         said = f" ({plan.orient_code} -> {self.orient})" if self.orient and plan.orient_code != self.orient else ""
         if plan.window_bounds is not None:
             said += ", window " + ", ".join(f"{m} {lo:.7g} {hi:.7g}" for m, (lo, hi) in zip(mods, plan.window_bounds))
         if any(s > 0 for s in plan.sigmas):
             said += f", anti-alias sigma {_fmt(plan.sigmas)}"
-        return said + (", cubic" if plan.interp == "cubic" else "")
+        said += ", cubic" if plan.interp == "cubic" else ""
+        if plan.align:
+            names = list(mods) + [D.LABEL_MODALITY]
+            voxels = float(np.prod(plan.source_shape))
+            said += f", aligned to {self.align}: " + ", ".join(
+                f"{m} {n / voxels:.2f}" for m, n in zip(names, plan.align_inside) if m in plan.align)
+        return said
 
 
 def parse_options(args, task: str, default_min_size=None) -> PrepOptions:
@@ -615,7 +704,7 @@ def parse_options(args, task: str, default_min_size=None) -> PrepOptions:
         min_size = D.PATCH_DEFAULT[task] if default_min_size is None else default_min_size
     return PrepOptions(mask, window, spacing, min_size, bool(getattr(args, "prep_no_crop", False)),
                        parse_orient(getattr(args, "prep_orient", None)), antialias_switch(args, spacing),
-                       interp_switch(args, spacing))
+                       interp_switch(args, spacing), align_switch(args, task))
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------
@@ -733,6 +822,31 @@ def _apply_window(ops, plan, x, window, mask: str) -> None:
         ops.prep_window(x, window[0], window[1])
 
 
+def _aligned(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str]):
+    """--prep_align: (x, lab) on the reference's grid.  Each modality goes to the device alone and is copied, or aligned by
+    its matrix, into its plane of the C x D x H x W tensor, the label likewise; plan.align_inside gets the voxels of the
+    grid inside each one's field of view, and a resampled scan that covers none of them stops the run."""
+    align = getattr(ops, "prep_align", None) or partial(ops_align.prep_align, ops)
+    dev, grid = ops.device, plan.source_shape
+    full = int(np.prod(grid))
+    x = torch.empty((len(mods),) + grid, dtype=torch.float32, device=dev)
+    lab = torch.empty((1,) + grid, dtype=torch.uint8, device=dev) if seg is not None else None
+    names = list(mods) + ([D.LABEL_MODALITY] if seg is not None else [])
+    counted = {}        # name -> the one-element device tensor of effq_prep_align; read once, after the last launch
+    for name, host, plane in zip(names, [imgs[m] for m in mods] + [seg], list(x) + [lab[0] if lab is not None else None]):
+        t = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+        if name in plan.align:
+            t, counted[name] = align(t, plan.align[name][0], grid, nearest=name == D.LABEL_MODALITY)
+        plane.copy_(t)
+    got = dict(zip(counted, torch.cat([n.reshape(1) for n in counted.values()]).cpu().tolist())) if counted else {}
+    plan.align_inside = [int(got.get(name, full)) for name in names]
+    for name in names:
+        if got.get(name, full) == 0:
+            raise PrepError(f"subject {plan.subject}: --prep_align {plan.ref}: {name}: no voxel of the reference grid lies "
+                            f"inside it; do the headers share a world?")
+    return x, lab
+
+
 # what process_subject returns, host arrays: arrays C x d x h x w float32, the label or None, the union mask of the grid or
 # None, the box, and per modality the count, mean and std over its mask
 Subject = namedtuple("Subject", "arrays label union pmin pmax count mean std")
@@ -743,15 +857,19 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
     """The device pipeline of one subject under `opts` (its mask, window, min_size and no_crop; the plan holds what the
     other options decided)."""
     sn, mask, window = plan.subject, opts.mask, opts.window
-    for m in mods:
-        if tuple(imgs[m].shape) != plan.source_shape:
+    for m in mods:          # every array against its own header; without --prep_align they all say plan.source_shape
+        if tuple(imgs[m].shape) != plan.shapes[m]:
             raise PrepError(f"subject {sn}: {m} holds an array of shape {tuple(imgs[m].shape)}, its header says "
-                            f"{plan.source_shape}")
-    if seg is not None and tuple(seg.shape) != plan.source_shape:
-        raise PrepError(f"subject {sn}: the label holds an array of shape {tuple(seg.shape)}, not {plan.source_shape}")
+                            f"{plan.shapes[m]}")
+    if seg is not None and tuple(seg.shape) != plan.shapes[D.LABEL_MODALITY]:
+        raise PrepError(f"subject {sn}: the label holds an array of shape {tuple(seg.shape)}, not "
+                        f"{plan.shapes[D.LABEL_MODALITY]}")
     dev = ops.device
-    x = torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
-    lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
+    if opts.align is None:
+        x = torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
+        lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
+    else:
+        x, lab = _aligned(ops, plan, imgs, seg, mods)
     if plan.orient is not None and not orient_is_identity(*plan.orient):
         x = ops.prep_reorient(x, *plan.orient)
         if lab is not None:
@@ -842,7 +960,7 @@ def run(args, ops=None) -> List[dict]:
                 nifti.write_nifti(P.join(data_dir, GRID_DIR, f"{sn}.nii.gz"), union, plan.grid_affine)
                 sn_fn[sn] = f"{GRID_DIR}/{sn}.nii.gz"
             else:
-                sn_fn[sn] = P.abspath(plan.entry["images"][mods[0]])
+                sn_fn[sn] = P.abspath(plan.entry["images"][plan.ref])
             cropped = tuple(y.shape[1:]) != tuple(plan.grid_shape)
             restore[sn] = {"pmin": pmin, "pmax": pmax, "shape": plan.grid_shape} if cropped else None
             row = {"subject": sn, "source_shape": _fmt(plan.source_shape), "source_spacing": _fmt(plan.source_spacing),

@@ -1169,6 +1169,28 @@ int effq_prep_reorient(const void* x, int N, int D, int H, int W, const int* src
                        void* y, void* stream);
 int effq_prep_reorient_plan(const int* src_axis, int flip_mask, int elem_bytes, int* variant);
 
+/* ---- alignment (csrc/prep_align.hip; prep.py --prep_align, where the rule is defined): one volume x (D, H, W) resampled
+ * onto another grid y (OD, OH, OW) through a general affine.  m: 12 HOST doubles, a row-major 3 x 4 matrix that maps an
+ * output voxel index (d, h, w, 1) to source voxel coordinates, read before the call returns.  Per output voxel and axis a,
+ * in fp64 and in exactly this order, nothing fused:  s_a = ((m[a][0] d + m[a][1] h) + m[a][2] w) + m[a][3].
+ * Field of view: the voxel is inside when -0.5 <= s_a < n_a - 0.5 on all three axes (n the source extent; `<` at the upper
+ * end so that nearest never indexes n_a and the half voxel around every source voxel belongs to it alone); outside it
+ * the output is +0.0f, or 0 for a label, and nothing is read.
+ *   EFFQ_PREP_LINEAR (fp32 in and out), inside: c = clamp(s_a, 0, n_a - 1) (the edge replicated over the outer half
+ *     voxel), i0 = floor(c), i1 = i0 + (i0 < n_a - 1), l1 = float(c - floor(c)), l0 = 1.0f - l1; the eight neighbours are
+ *     combined in fp32 in the order of effq_prep_resample: l0d (l0h (l0w v000 + l1w v001) + l1h (...)) + l1d (...).  A
+ *     NaN or an Inf among the eight reaches the output even at weight 0.
+ *   EFFQ_PREP_NEAREST (uint8 in and out), inside: the index floor(s_a + 0.5), kept at n_a - 1 at most (the fp64 sum can
+ *     round up to n_a only when n_a = 1).
+ * inside (device, one int64, 8-B aligned): the number of output voxels inside the field of view.  The call zeroes it with
+ * a memset on the stream; every workgroup sums its count in LDS and adds it once with an integer atomic: equal inputs give
+ * equal bits, there is no floating-point atomic and no workgroup waits for another.  One launch; a thread makes four
+ * consecutive w of an output row.  Refused with EFFQ_ERR_ARG before the memset and before any launch: a null pointer,
+ * extents outside 1 ... 32767 or D H W >= 2^31 or OD OH OW >= 2^31, another mode, a matrix entry that is not finite, for
+ * EFFQ_PREP_LINEAR an x or y that is not 4-B aligned, an `inside` that is not 8-B aligned. */
+int effq_prep_align(const void* x, int D, int H, int W, const double* m, int mode, void* y, int OD, int OH, int OW,
+                    long long* inside, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
