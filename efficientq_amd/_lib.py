@@ -225,6 +225,8 @@ SIGNATURES = {
     "effq_label_lesions": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
     "effq_label_surface_mm_ws_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "effq_label_surface_mm": (_I, [_P, _P, _I, _I, _I, _I, _P, _F, _F, _F, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "effq_label_lesion_measures_ws_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
+    "effq_label_lesion_measures": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_prep_window": (_I, [_P, _SZ, _F, _F, _P]),
     "effq_prep_resample": (_I, [_P, _I, _I, _I, _I, _D, _D, _D, _I, _P, _I, _I, _I, _P]),
     "effq_prep_bbox_moments": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
@@ -276,6 +278,10 @@ EDT_MAX_LINE = 16382
 EDT_MM_MAX_EXTENT = 4096
 # include/effq_hip.h (EFFQ_SURF_TOL_MAX): the most tolerances of one effq_label_surface_mm call
 SURF_TOL_MAX = 8
+# include/effq_hip.h (EFFQ_LESION_MEASURE_WORDS): the int64 words of one record of effq_label_lesion_measures
+LESION_MEASURE_WORDS = 13
+# include/effq_hip.h (EFFQ_LESION_MEASURE_MAX_TILE_PAIRS): the tile pairs of a call above which the diameters are not searched
+LESION_MEASURE_MAX_TILE_PAIRS = 1 << 26
 # include/effq_hip.h: the prep kernels' most modalities, scratch, mask modes and resampling modes
 PREP_MAX_MODALITIES = 4
 PREP_WS_BYTES = 1024 * (2 * PREP_MAX_MODALITIES * 8 + 8 * 4)

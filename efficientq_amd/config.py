@@ -163,6 +163,18 @@ def build_parser():
     p.add_argument('--score_tol', default=None, metavar='T[,T...]',
                    help='score: the tolerances in mm of the normalised surface Dice (at most 8, default 1), one column '
                         'nsd_<T>mm each; none: no such column')
+    # one record per lesion of the maps of score and predict; the values and the missions are checked by measure_switches,
+    # after the YAML has been merged in
+    p.add_argument('--lesion_measures', action='store_true',
+                   help='score, predict: one row per lesion in <out_dir>/lesions.csv: place, volume in ml, centroid in '
+                        'scanner coordinates, box, the longest diameter in mm in 3-D and inside one slice; score also '
+                        'writes the detection rate by diameter in <out_dir>/lesion_detect.csv')
+    p.add_argument('--measure_class', action='append', default=None, metavar='LABELS',
+                   help='predict, with --lesion_measures: one class per switch as --score_class (at most 8; default the '
+                        'classes of the task); score measures the classes of --score_class')
+    p.add_argument('--measure_plane', default=None, metavar='axial|d|h|w',
+                   help='with --lesion_measures: the slices of the in-plane diameter: axial (default; the array axis '
+                        'nearest to world z by the header) or the array axis they are stacked along')
     # `--prep_window -200,250`: argparse takes a value that starts with `-` for a switch unless it looks like a negative
     # number, and its own pattern knows no comma
     p._negative_number_matcher = re.compile(r'^-\d[\d.,eE+-]*$')
@@ -371,6 +383,48 @@ def score_switches(args, mission=None):
             raise SystemExit(f'--score_class: {len(given)} classes, at most {SCORE_MAX_CLASSES}')
         classes = tuple(parse_score_class(t) for t in given)
     return classes, parse_score_tol(getattr(args, 'score_tol', None))
+
+
+MEASURE_SWITCHES = ('lesion_measures', 'measure_class', 'measure_plane')
+MEASURE_PLANES = ('axial', 'd', 'h', 'w')
+
+
+def measure_switches(args, mission=None):
+    """None without --lesion_measures, else (classes, plane) of --measure_class / --measure_plane (or the YAML keys
+    `lesion_measures`, `measure_class`, a list, and `measure_plane`): a tuple of label-value tuples, or None for the
+    mission's own classes (score: those of --score_class; predict: the task's), and one of MEASURE_PLANES.  ptq and prep
+    refuse all three by name, score refuses --measure_class, and the two that only qualify the first are refused without
+    it (SystemExit), host only."""
+    mission = mission or getattr(args, 'mission', None)
+    given = {k: getattr(args, k, None) for k in MEASURE_SWITCHES}
+    given = {k: v for k, v in given.items() if v not in (None, False, [])}
+    if mission in ('ptq', 'prep'):
+        for switch in given:
+            raise SystemExit(f'--{switch} measures the lesions of finished maps on the grid of their scan: the {mission} '
+                             f'mission writes none, it belongs to the score and predict missions: drop --{switch}')
+        return None
+    if mission == 'score' and 'measure_class' in given:
+        raise SystemExit('--measure_class: the score mission measures the classes it scores, those of --score_class: '
+                         'drop --measure_class')
+    if 'lesion_measures' not in given:
+        for switch in given:
+            raise SystemExit(f'--{switch} qualifies --lesion_measures, which is not given: add --lesion_measures or drop '
+                             f'--{switch}')
+        return None
+    plane = given.get('measure_plane', 'axial')
+    if plane not in MEASURE_PLANES:
+        raise SystemExit(f'--measure_plane {plane!r}: one of {", ".join(MEASURE_PLANES)}')
+    classes = given.get('measure_class')
+    if classes is not None:
+        if isinstance(classes, (str, int)):
+            classes = [classes]
+        if len(classes) > SCORE_MAX_CLASSES:
+            raise SystemExit(f'--measure_class: {len(classes)} classes, at most {SCORE_MAX_CLASSES}')
+        try:
+            classes = tuple(parse_score_class(t) for t in classes)
+        except SystemExit as e:
+            raise SystemExit(str(e).replace('--score_class', '--measure_class'))
+    return classes, plane
 
 
 POST_MAX_RULES = 8           # effq_hip.h: EFFQ_LABEL_CLEAN_MAX_RULES

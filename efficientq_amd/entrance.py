@@ -219,6 +219,7 @@ def _switches(args):
     Cf.prob_switches(args)
     match = Cf.match_switches(args)
     Cf.score_switches(args, 'ptq')
+    Cf.measure_switches(args, 'ptq')
     if getattr(args, 'unlabelled', False):
         if not getattr(args, 'vs_fp', False):
             raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add '
@@ -268,6 +269,7 @@ def main(argv=None):
         Cf.prob_switches(args)
         Cf.match_switches(args)
         Cf.score_switches(args)
+        Cf.measure_switches(args)
         from . import prep
         prep.run(args)
         return

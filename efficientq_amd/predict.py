@@ -75,6 +75,11 @@ channel in bits.  Outside the box the probabilities are the background's (class-
 and the uncertainty is 0.  ``--blend`` and ``--tta_mirror`` act through the logits, ``--post`` does not touch these
 files, ``predict.csv`` is unchanged, and without the switches nothing changes.
 
+``--lesion_measures`` (``--measure_class LABELS``, ``--measure_plane axial|d|h|w``) measures the uint8 map that is
+written, after ``--post`` and on the scan's own grid (ops_measure.label_lesion_measures without a truth map), and writes
+``<out_dir>/lesions.csv``: the columns of ``score --lesion_measures`` without ``overlap``, ``kind`` ``pred`` throughout.
+The per-subject line gains the lesion count per class; ``predict.csv`` and the maps are unchanged.
+
 Everything the list and the headers decide, a ``--thresh`` that is not understood or given without ``--multi_label``, a ``--post`` rule that is not understood, a ``--blend`` or ``--tta_mirror`` that is not understood, ``--multi_label lits`` (one plane per class has no place on a source grid)
 and the choice of the network are refused before anything touches the device or ``out_dir``, in prep's wording.
 """
@@ -90,8 +95,10 @@ from typing import List
 import numpy as np
 import torch
 
+from . import _lib
 from . import data as D
 from . import evaluate as E
+from . import lesion_measures as LM
 from . import nifti
 from . import prep
 from .prep import PrepError
@@ -204,8 +211,21 @@ def _resolve(args, need_network: bool) -> SimpleNamespace:
     post, post_conn = Cf.post_rules(args)
     _, thresh = Cf.thr_switches(args, 'predict')
     save_prob, save_unc = Cf.prob_switches(args, 'predict')
+    measures = Cf.measure_switches(args, 'predict')
     mods = D.MODALITIES[task]
     plans = [opts.plan(dict(e, seg=None), mods) for e in prep.read_src_list(args.src_list, task)]
+    measure = None
+    if measures:        # the classes, and per subject the slice axis; the limits of the device call are refused here
+        classes = measures[0] or Cf.SCORE_CLASSES[task]
+        axes = {}
+        for plan in plans:
+            shape = tuple(int(n) for n in plan.source_shape)
+            if len(classes) * int(np.prod(shape)) >= 2 ** 31 or max(shape) > _lib.EDT_MM_MAX_EXTENT:
+                raise PrepError(f"subject {plan.subject}: --lesion_measures: {len(classes)} masks of {prep._fmt(shape)} "
+                                f"voxels are outside the limits of the device call (2^31 - 1 voxels in all, every extent "
+                                f"at most {_lib.EDT_MM_MAX_EXTENT})")
+            axes[plan.subject] = LM.slice_axis(measures[1], plan.affine, plan.subject)
+        measure = SimpleNamespace(classes=classes, lut=Cf.score_class_lut(classes), axes=axes)
     window = opts.window
     used = {"prep_mask": opts.mask, "prep_window": str(window) if isinstance(window, prep.PercentileWindow) else
             prep._fmt(window) if window else "none",
@@ -220,7 +240,7 @@ def _resolve(args, need_network: bool) -> SimpleNamespace:
         used.update(post=post_said)
     return SimpleNamespace(mods=mods, opts=opts, patch=patch, overlap=tuple(min(D.OVERLAP_DEFAULT, p // 2) for p in patch),
                            rule=rule, fuse=fuse, blend=blend, flips=flips, sliding=sliding, post=post, post_conn=post_conn,
-                           post_said=post_said, thresh=thresh, save_prob=save_prob, save_unc=save_unc,
+                           post_said=post_said, thresh=thresh, save_prob=save_prob, save_unc=save_unc, measure=measure,
                            prob_mode="argmax" if rule == "argmax" else "sigmoid", used=used, plans=plans)
 
 
@@ -232,7 +252,7 @@ def _on_scan_grid(ops, plan, t):
     return ops.prep_reorient(t, *prep.orient_inverse(*plan.orient))
 
 
-def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write):
+def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write, measures=None):
     """The device work of one subject: its label map and, for --save_prob / --save_unc, its probability and uncertainty
     maps, handed to `write(path, host, geometry, scale=None)`.  Returns (what it leaves for the row and the line, the
     window batch in use): box_of, the extent of the working arrays; counts, the voxels per label value of the map that was
@@ -248,6 +268,15 @@ def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write):
         labels, stats = ops.label_clean(labels, job.post, job.post_conn, out=labels)
         changed = prep._fmt(int(v) for v in stats.cpu()[:, 1])
     counts = torch.bincount(labels.reshape(-1)).cpu().tolist()      # on the uint8 map itself, before the copy
+    lesions = None
+    if job.measure:     # of the map that is written: after --post, on the scan's own grid
+        m = job.measure
+        try:
+            _, _, table, meas = measures(labels, None, m.lut, len(m.classes), plan.source_spacing, m.axes[sn])
+        except _lib.EffqError as e:
+            raise PrepError(f"subject {sn}: --lesion_measures: {e}")
+        lesions = LM.lesion_rows(sn, m.classes, False, table, meas, tuple(labels.shape), plan.source_spacing, plan.affine,
+                                 m.axes[sn])
     write(P.join(out_dir, f"{sn}.nii.gz"), labels.cpu().numpy(), plan.header)
     extra = ""
     if job.save_prob or job.save_unc:       # from the same stitched logits, on the same grid; --post does not enter
@@ -261,7 +290,7 @@ def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write):
             write(P.join(out_dir, UNC_DIR, f"{sn}.nii.gz"), unc.cpu().numpy(), plan.header, PROB_SCALE)
             extra += f", {UNC_DIR}/{sn}.nii.gz"
     return SimpleNamespace(box_of=tuple(y.shape[1:]), pmin=pmin, pmax=pmax, windows=nwin, counts=counts,
-                           changed=changed, extra=extra), bsz
+                           changed=changed, extra=extra, lesions=lesions), bsz
 
 
 def _row(job, plan, done) -> dict:
@@ -282,16 +311,21 @@ def _row(job, plan, done) -> dict:
     return row
 
 
-def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
+def run(args, ops=None, model=None, window_batch=None, measures=None) -> List[dict]:
     """The `predict` mission of `args` (config.build_parser); returns the rows of predict.csv.  `ops`: the object whose
     prep_*, window_*, seg_labels_source and (for --save_prob / --save_unc) seg_probs_source methods do the device work and whose `device` holds the tensors
     (hip_ops.get_ops(args.device) by default); `model`: the network, already on that device and in its mode (by default
     the one --resume / --pretrain name); `window_batch`: windows per forward (None: sized from the first window's peak
-    memory, as validate_seg sizes it)."""
+    memory, as validate_seg sizes it); `measures`: the device call of --lesion_measures (ops_measure.label_lesion_measures
+    over `ops` by default)."""
     job = _resolve(args, model is None)
     if ops is None:
         from .hip_ops import get_ops
         ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
+    if job.measure and measures is None:
+        from functools import partial
+        from . import ops_measure as OM
+        measures = partial(OM.label_lesion_measures, ops)
     if model is None:
         model = _network(args, ops.device)
     model.eval()
@@ -318,7 +352,7 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
         for on, sub in ((job.save_prob, PROB_DIR), (job.save_unc, UNC_DIR)):
             if on:
                 os.makedirs(P.join(out_dir, sub), exist_ok=True)
-    rows = []
+    rows, lesions = [], []
     bsz = window_batch
     try:
         with nifti.BackgroundWriter("effq-predict-write", MAX_PENDING_WRITES) as writer, \
@@ -326,9 +360,14 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
             def write(path, host, geometry, scale=None):
                 writer.submit(nifti.write_nifti, path, host, None, geometry, scale)
             for plan, imgs, _ in subjects:
-                done, bsz = _segment(ops, model, job, plan, imgs, out_dir, bsz, write)
+                done, bsz = _segment(ops, model, job, plan, imgs, out_dir, bsz, write, measures)
                 rows.append(_row(job, plan, done))
                 cleaned = f", post {job.post_said}: {done.changed} voxels relabelled" if job.post else ""
+                if job.measure:
+                    lesions += done.lesions
+                    cleaned += ", lesions " + ", ".join(
+                        f"class {c} ({prep._fmt(labels)}): {sum(1 for r in done.lesions if r['class'] == c)}"
+                        for c, labels in enumerate(job.measure.classes))
                 print(f"[predict] {plan.subject}: {prep._fmt(plan.source_shape)}{job.opts.said(plan, job.mods)} -> grid "
                       f"{prep._fmt(plan.grid_shape)}, box at {prep._fmt(done.pmin)} of {prep._fmt(done.box_of)}, "
                       f"{done.windows} windows{f' x {len(job.flips)} passes, blend {job.blend}' if job.sliding else ''}, "
@@ -341,5 +380,8 @@ def run(args, ops=None, model=None, window_batch=None) -> List[dict]:
                CSV_HEADER + job.opts.columns() + (CSV_WINDOW_COLUMNS if pct else []) +
                (CSV_BLEND_COLUMNS if job.sliding else []) +
                (CSV_THRESH_COLUMNS if job.thresh is not None else []) + (CSV_POST_COLUMNS if job.post else []))
+    if job.measure:
+        LM.write_csv(P.join(out_dir, LM.LESIONS_CSV), [k for k in LM.LESION_COLUMNS if k != "overlap"], lesions)
+        print(f"[predict] {len(lesions)} lesions measured: {P.join(out_dir, LM.LESIONS_CSV)}")
     print(f"[predict] {len(rows)} maps written to {out_dir}")
     return rows

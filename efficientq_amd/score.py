@@ -25,6 +25,13 @@ the surface voxels of both masks that lie within T mm of the other surface; 1 wh
 exactly one is.  ``<out_dir>/summary.csv``: one row per class - the cases, the means of ``dsc``, ``hd95_mm``, ``assd_mm``
 and every ``nsd_*``, the summed lesion counts, ``lesion_sens = 1 - fnl / totall`` and ``lesion_prec = 1 - fpl / predl``
 (each 1 when its denominator is 0).  Floats are printed as metrics.csv prints them (``%.7g``).
+
+``--lesion_measures`` (``--measure_plane axial|d|h|w``): one more device call per subject on the same two maps,
+``ops_measure.label_lesion_measures``, and two more files, lesion_measures.py's: ``<out_dir>/lesions.csv``, one row per
+connected component of every class (place, size, overlap, volume in ml, centroid in voxels and in scanner coordinates, box,
+the longest diameter in mm in 3-D and inside one slice with their end points), and ``<out_dir>/lesion_detect.csv``, the
+label lesions, the detected ones and the invented ones per class and bin of the diameter.  The slice axis of every
+subject is resolved from its header before the device is touched; the other two files are what they are without it.
 """
 from __future__ import annotations
 
@@ -41,6 +48,7 @@ import torch
 from . import _lib
 from . import config as Cf
 from . import data as D
+from . import lesion_measures as LM
 from . import metrics as M
 from . import nifti
 from . import prep
@@ -84,6 +92,7 @@ def _resolve(args) -> SimpleNamespace:
     """Everything `args`, the list and the headers decide, refused by name before anything touches the device or out_dir;
     returns the mission's job: host values only."""
     classes, tols = Cf.score_switches(args, "score")
+    measures = Cf.measure_switches(args, "score")
     task = (getattr(args, "task", None) or "").lower()
     if task not in D.MODALITIES:
         raise PrepError(f"score: --task {getattr(args, 'task', None)!r}, one of {', '.join(D.MODALITIES)}")
@@ -126,8 +135,11 @@ def _resolve(args) -> SimpleNamespace:
         c.shape, c.spacing = shape, tuple(float(v) for v in gp["spacing"])
         if not all(np.isfinite(v) and v > 0 for v in c.spacing):
             raise PrepError(f"subject {c.subject}: {c.pred}: spacing {c.spacing}: needs three finite positive numbers")
+        if measures:
+            c.affine = np.asarray(gp["affine"], dtype=np.float64)
+            c.slice_axis = LM.slice_axis(measures[1], c.affine, c.subject)
     return SimpleNamespace(task=task, classes=classes, tols=tols, lut=Cf.score_class_lut(classes), cases=cases,
-                           skipped=skipped)
+                           skipped=skipped, measures=bool(measures))
 
 
 def read_labels(subject: str, path: str) -> np.ndarray:
@@ -147,20 +159,29 @@ def read_labels(subject: str, path: str) -> np.ndarray:
 
 
 def device_calls(ops) -> SimpleNamespace:
-    """The three device calls of a subject over `ops` (a HipOps)."""
+    """The three device calls of a subject over `ops` (a HipOps), and the fourth of --lesion_measures."""
+    from . import ops_measure as OM
     from . import ops_score as OS
     return SimpleNamespace(tallies=ops.label_tallies, lesions=partial(OS.label_lesions, ops),
-                           surface=partial(OS.label_surface_mm, ops))
+                           surface=partial(OS.label_surface_mm, ops), measures=partial(OM.label_lesion_measures, ops))
 
 
-def score_case(calls, device, job, case) -> List[dict]:
-    """The rows of scores.csv of one subject, unformatted: one dict per class."""
+def score_case(calls, device, job, case, measured=None) -> List[dict]:
+    """The rows of scores.csv of one subject, unformatted: one dict per class.  `measured` (a list, with
+    --lesion_measures): the subject's rows of lesions.csv are added to it, from one more call on the same two maps."""
     pred = torch.from_numpy(read_labels(case.subject, case.pred)).to(device)
     truth = torch.from_numpy(read_labels(case.subject, case.seg)).to(device)
     C = len(job.classes)
     counts = calls.tallies(pred, truth, job.lut, C).cpu()
     lesions = calls.lesions(pred, truth, job.lut, C).cpu()
     n, sq, sums, within = (t.cpu() for t in calls.surface(pred, truth, job.lut, C, case.spacing, job.tols))
+    if measured is not None:
+        try:
+            _, _, table, meas = calls.measures(pred, truth, job.lut, C, case.spacing, case.slice_axis)
+        except _lib.EffqError as e:
+            raise PrepError(f"subject {case.subject}: --lesion_measures: {e}")
+        measured += LM.lesion_rows(case.subject, job.classes, True, table, meas, case.shape, case.spacing, case.affine,
+                                  case.slice_axis)
     ratios = M.metrics_from_counts(counts)
     surface = M.surface_metrics_mm(n, sq, sums, case.shape, case.spacing)
     ml = float(np.prod(case.spacing)) / 1000.0
@@ -228,9 +249,9 @@ def run(args, ops=None, calls=None) -> List[dict]:
     os.makedirs(args.out_dir, exist_ok=True)
     if job.skipped:
         print(f"[score] {len(job.skipped)} subjects without a {D.LABEL_MODALITY} cell are skipped: {' '.join(job.skipped)}")
-    rows = []
+    rows, lesions = [], [] if job.measures else None
     for case in job.cases:
-        mine = score_case(calls, device, job, case)
+        mine = score_case(calls, device, job, case, lesions)
         rows += mine
         print(f"[score] {case.subject}: {prep._fmt(case.shape)} at {prep._fmt(case.spacing)} mm: " +
               "; ".join(f"class {r['class']} {_means_said(job, r)} lesions {r['totall']}/{r['predl']} missed "
@@ -241,6 +262,15 @@ def run(args, ops=None, calls=None) -> List[dict]:
     for r in summary:
         print(f"[score] class {r['class']} (labels {r['labels']}), {r['cases']} cases: mean {_means_said(job, r)}, "
               f"lesion_sens {r['lesion_sens']:.4g} lesion_prec {r['lesion_prec']:.4g}")
+    if job.measures:
+        detect = LM.detect_rows(job.classes, lesions)
+        LM.write_csv(P.join(args.out_dir, LM.LESIONS_CSV), LM.LESION_COLUMNS, lesions)
+        LM.write_csv(P.join(args.out_dir, LM.DETECT_CSV), LM.DETECT_COLUMNS, detect)
+        for c, labels in enumerate(job.classes):
+            print(f"[score] class {c} (labels {prep._fmt(labels)}), detected / labelled +invented by diameter: "
+                  f"{LM.detect_said(detect, c)}")
+        print(f"[score] {len(lesions)} lesions measured: {P.join(args.out_dir, LM.LESIONS_CSV)}, "
+              f"{P.join(args.out_dir, LM.DETECT_CSV)}")
     print(f"[score] {len(job.cases)} subjects scored: {P.join(args.out_dir, SCORES_CSV)}, "
           f"{P.join(args.out_dir, SUMMARY_CSV)}")
     return rows

@@ -1010,6 +1010,50 @@ int effq_label_surface_mm(const uint8_t* pred, const uint8_t* truth, int C, int 
                           float wd, float wh, float ww, const float* tol_sq, int ntol, long long* counts, float* sq,
                           double* sums, long long* within, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- one geometric record per lesion of finished label maps (`score --lesion_measures`, `predict --lesion_measures`;
+ * DESIGN section 28).  pred, truth, lut, C and connectivity as effq_label_lesions.  With truth there are P = 2 C planes,
+ * plane q < C the predicted mask of class q and plane C + q its label mask, and counts (C, 4) is bit for bit
+ * effq_label_lesions'.  With truth null only the P = C predicted planes exist, counts may be null and every overlap is 0.
+ * wd, wh, ww: the fp32 axis weights float32(float64(spacing) ** 2), finite and > 0.  slice_axis 0, 1 or 2: the array
+ * axis the slices are stacked along.  Every extent <= EFFQ_EDT_MM_MAX_EXTENT, P D H W < 2^31, P max_rows < 2^31.
+ *
+ * nrows (P) int64 and rows (P, max_rows, 3) int32 = first voxel, size, overlap: the contract of effq_seg_lesion_table
+ *   (row k is the component whose first voxel has the k-th smallest linear index, nrows is the true count, of a plane
+ *   with more rows than fit the first max_rows are complete, rows past nrows are untouched).
+ * meas (P, max_rows, EFFQ_LESION_MEASURE_WORDS) int64, one record per row that fits, nothing else written:
+ *   0..2   the sums of d, h and w over the voxels of the component (integer adds)
+ *   3..8   its box: the least d, h, w, then the greatest d, h, w (inclusive)
+ *   9, 10  the linear indices a <= b of two voxels of the component that attain the greatest
+ *          E = (wd * f(dd^2) + wh * f(dh^2)) + ww * f(dw^2) over all its pairs of voxels: (dd, dh, dw) the integer
+ *          offsets, f the exact conversion of the square to fp32, every product and sum rounded to fp32
+ *   11, 12 the same over the pairs that share the coordinate along slice_axis
+ *   A component of one voxel has a = b = that voxel (distances run between voxel centres).  The diameters in mm follow
+ *   on the host from the end points and the spacing.
+ * Only the voxels that end a line of the component along w (along h when slice_axis is 2) enter the search: E is
+ *   strictly convex along a line and rounding is monotone, so the fp32 maximum over them is the one over all voxels.
+ *   Among the pairs of line ends of the greatest E, a is the least index any of them holds and b the least partner of
+ *   a at that E (an inner voxel of a line may reach the same fp32 E after rounding; it is never returned).
+ *   Integer atomics only, their winners decided by value: equal inputs give equal bits, whatever the workspace holds
+ *   on entry.  A fixed number of launches on `stream`, no read by the host, no workgroup that waits for another.
+ * The search walks the line ends of a component in tiles of 256 and costs 65536 pairs per pair of tiles (i <= j): it
+ *   grows with the square of the line ends of one component.  A call whose rows that fit have more than
+ *   EFFQ_LESION_MEASURE_MAX_TILE_PAIRS tile pairs in all (4.4e12 voxel pairs; one solid component of 512^3 has 2.1e6, a
+ *   map of noise that hangs together has more) does not run it: slots 9..12 of every record are then -1 and the rest
+ *   of the call's outputs is complete.  The bound is on the work of one launch, not on the volume.
+ * ws: effq_label_lesion_measures_ws_bytes(C, planes, D, H, W, max_rows) bytes, planes = P, 16-B aligned:
+ *   effq_cc_table_ws_bytes(P, D, H, W, max_rows), 4 B per plane and voxel for the compacted line ends and 36 B per
+ *   plane and row; 0 for what the call refuses.  Bad arguments (those of effq_label_lesions, a slice_axis other than 0,
+ *   1, 2, a weight that is 0, negative, NaN or infinite, an extent above the limit, max_rows <= 0, a null meas, rows or
+ *   nrows, a null counts with a truth map) return EFFQ_ERR_ARG, a short workspace EFFQ_ERR_WORKSPACE; both launch
+ *   nothing and leave every output as it was. */
+#define EFFQ_LESION_MEASURE_WORDS 13
+#define EFFQ_LESION_MEASURE_MAX_TILE_PAIRS (1ll << 26)
+size_t effq_label_lesion_measures_ws_bytes(int C, int planes, int D, int H, int W, int max_rows);
+int effq_label_lesion_measures(const uint8_t* pred, const uint8_t* truth, int C, int D, int H, int W,
+                               const uint16_t* lut, int connectivity, float wd, float wh, float ww, int slice_axis,
+                               int max_rows, long long* counts, long long* nrows, int32_t* rows, long long* meas,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the `prep` mission (prep.py): source scans to the standardised, cropped arrays the `ptq` mission reads.  One
  * subject at a time: x (C, D, H, W) fp32, contiguous, S = D H W voxels per modality, C <= EFFQ_PREP_MAX_MODALITIES,
  * C S < 2^31, every extent <= 32767.  mask_mode EFFQ_PREP_MASK_NONZERO: the mask of modality c is x_c != 0 (a NaN is
