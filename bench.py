@@ -8,7 +8,14 @@ volumes, inputs resident in HBM.  With N GPUs the calibration set is vols*N volu
 (data-parallel, Gram / statistics all-reduced over RCCL) => weak scaling; value = total volumes / s.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--vols V] [--size S] [--levels L]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps (with the roofline
+figures their own HIP events give), the dump if asked for, the result line.  ``--full`` adds, after the timed steps and
+on one GPU, the measurements that take runs of their own and puts them into the same line: ``conv_path`` (the same
+calibration with every per-iteration loss by a conv pass), ``f32_only`` (every loss and Gram system on the f32 matrix
+cores) and ``cpu_baseline`` (the oracle timed on the host cores, the BraTS net only); ``--no-conv-subrun``,
+``--no-f32-subrun`` and ``--no-cpu-baseline`` leave one of them out of a full run.
 
 ``--gpus N`` with N > 1 starts its own N ranks (``python -m torch.distributed.run --nproc-per-node N``,
 one rank per GPU over RCCL) when it was not itself started by a launcher (WORLD_SIZE unset); under a
@@ -45,9 +52,11 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--levels", type=int, default=None)
     ap.add_argument("--net", choices=["brats", "lits"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-subrun", action="store_true")
-    ap.add_argument("--no-conv-subrun", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the conv_path and f32_only sub-runs and time the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-f32-subrun", action="store_true", help="with --full: leave the f32_only sub-run out")
+    ap.add_argument("--no-conv-subrun", action="store_true", help="with --full: leave the conv_path sub-run out")
     ap.add_argument("--f32-only", action="store_true",
                     help="evaluate every per-iteration loss on the f32 matrix cores (no exact-integer path)")
     ap.add_argument("--spawn-check", action="store_true",
@@ -546,6 +555,23 @@ def spawn_check(a, world, rank, local):
         print(json.dumps({"metric": "spawn_check", "n_gpus": world, "rccl_ranks": ranks, "backend": backend}), flush=True)
 
 
+def extra_runs(a, solo, exact, gram_loss):
+    """What the run measures after its timed steps, as a tuple of the result line's keys: nothing without --full; with
+    it, on one GPU (`solo`: rank 0 of a world of one), `conv_path` where the default path is the exact-integer one
+    (`exact`) with the losses from the Gram system (`gram_loss`), `f32_only` where it is exact, `cpu_baseline` for the
+    BraTS net, each unless its --no-... flag is given."""
+    if not (a.full and solo):
+        return ()
+    runs = []
+    if exact and gram_loss and not a.no_conv_subrun:
+        runs.append("conv_path")
+    if exact and not a.no_f32_subrun:
+        runs.append("f32_only")
+    if a.net == "brats" and not a.no_cpu_baseline:
+        runs.append("cpu_baseline")
+    return tuple(runs)
+
+
 def main():
     a = parse_args()
     if a.f32_only:
@@ -709,9 +735,10 @@ def main():
                       if dp_forced else None),
         "main_queue_wait": {"ms_per_step": round(getattr(timer, "wait_ms", 0.0) / a.steps, 2),
                             "frac_of_step": round(getattr(timer, "wait_ms", 0.0) * 1e-3 / dt, 4)},
+        "full": bool(a.full),
     }
-    solo = rank == 0 and world == 1
-    if solo and exact and not a.no_conv_subrun and _Q.GRAM_LOSS_DEFAULT:
+    extra = extra_runs(a, rank == 0 and world == 1, exact, bool(_Q.GRAM_LOSS_DEFAULT))
+    if "conv_path" in extra:
         # north_star's named kernel (conv3d_quant_calib_step, here its exact-integer form k_conv3d_i8l2e) stays in view:
         # the same calibration with the per-iteration losses by conv passes over the voxels (EFFQ_GRAM_LOSS=0)
         _Q.GRAM_LOSS_DEFAULT = False
@@ -733,7 +760,7 @@ def main():
                                 "roofline": (conv_rows[0] if conv_rows else None)}
         finally:
             _Q.GRAM_LOSS_DEFAULT = True
-    if solo and exact and not a.no_f32_subrun:
+    if "f32_only" in extra:
         # like-for-like dtype: the same calibration with every loss and Gram system on the f32 matrix cores
         for m in model.modules():
             if hasattr(m, "lwq_exact_int"):
@@ -749,7 +776,7 @@ def main():
         for m in model.modules():
             if hasattr(m, "lwq_exact_int"):
                 m.lwq_exact_int = True
-    if solo and not a.no_cpu_baseline and a.net == "brats":
+    if "cpu_baseline" in extra:
         log("[rank 0] timing the CPU baseline components ...")
         out["cpu_baseline"] = cpu_baseline(a.levels, a.vols, a.size)
     elif rank == 0:

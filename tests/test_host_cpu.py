@@ -728,6 +728,32 @@ def test_bench_config_presets():
     assert (a.net, a.levels, a.vols, a.size) == ("lits", 4, 2, 160)                    # configs[3], flag override
 
 
+def test_bench_runs_its_sub_runs_and_the_cpu_baseline_only_with_full():
+    """A plain run measures nothing after its timed steps; --full adds the three extra measurements on one GPU, each
+    where it applies (exact-integer default path, losses from the Gram system, BraTS net) and unless its flag drops it."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    every = ("conv_path", "f32_only", "cpu_baseline")
+
+    def runs(flags, solo=True, exact=True, gram_loss=True):
+        return bench.extra_runs(bench.parse_args(flags), solo, exact, gram_loss)
+
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    assert runs([]) == () and runs(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "d"]) == ()
+    # the flags that leave one out do not bring the others in
+    assert runs(["--no-cpu-baseline"]) == () and runs(["--no-f32-subrun", "--no-conv-subrun"]) == ()
+    assert runs(["--full"]) == every
+    assert runs(["--full", "--no-conv-subrun"]) == every[1:]
+    assert runs(["--full", "--no-f32-subrun"]) == (every[0], every[2])
+    assert runs(["--full", "--no-cpu-baseline"]) == every[:2]
+    assert runs(["--full", "--no-cpu-baseline", "--no-f32-subrun", "--no-conv-subrun"]) == ()
+    assert runs(["--full"], solo=False) == ()                          # one rank of several, or not rank 0
+    assert runs(["--full"], exact=False) == ("cpu_baseline",)          # the f32 path is already the like-for-like dtype
+    assert runs(["--full"], gram_loss=False) == every[1:]              # the losses already come from conv passes
+    assert runs(["--full", "--config", "4"]) == every[:2]              # the CPU baseline models the BraTS net only
+
+
 @pytest.mark.parametrize("tag,psz,ov", [("a", 6, 2), ("b", (6, 12, 6), (2, 0, 3)), ("c", 7, 3)])
 def test_sliding_window_helpers_match_reference(gold, tag, psz, ov):
     """Row f1 host logic (efficientq_amd/evaluate.py) against the reference's split / stitch / Dice goldens."""
