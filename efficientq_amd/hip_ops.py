@@ -300,8 +300,8 @@ class HipOps(WindowOps, SegOps, PrepOps):
         return it
 
     def fixed_point_bucket(self, a, b, v, levels: int, state, lo: float = -1.0, hi: float = 1.0):
-        """project_by_iter of v = a + b (b may be None) on the bucketed copy: one workgroup, one launch
-        (effq_fixed_point_bucket)."""
+        """project_by_iter of v = a + b (b may be None) on the bucketed copy: one workgroup and one launch up to
+        32768 values, four launches over many workgroups above (effq_fixed_point_bucket)."""
         n = a.numel()
         ws = self._workspace("fp_bucket", self.lib.effq_fp_bucket_ws_bytes(n))
         check(self.lib.effq_fixed_point_bucket(_ptr(a), _ptr(b), _ptr(v), n, levels, lo, hi, ADMM_TOL, 100 * levels,
