@@ -13,7 +13,10 @@ class-name substring (src/models/model_blk.py:26-34).
 from __future__ import annotations
 
 import math
-from typing import Optional
+import os
+import time
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -23,10 +26,9 @@ from .hip_ops import from_ndhwc, make_geom, to_ndhwc
 
 # ADMM constants are constructor constants in the reference (EfficientQConv.py:23-26)
 LWQ_ITER, LWQ_RHO, LWQ_RHO_MAX, LWQ_ETA, RHO_PERIOD = 200, 10.0, 1000.0, 1.0, 50
-import os as _os
-EXACT_INT_DEFAULT = _os.environ.get("EFFQ_EXACT_INT", "1") != "0"
+EXACT_INT_DEFAULT = os.environ.get("EFFQ_EXACT_INT", "1") != "0"
 # per-iteration losses from the unweighted Gram system (effq_gram_loss) for layers with n = k^3 c1 + 1 up to this size
-GRAM_LOSS_DEFAULT = _os.environ.get("EFFQ_GRAM_LOSS", "1") != "0"
+GRAM_LOSS_DEFAULT = os.environ.get("EFFQ_GRAM_LOSS", "1") != "0"
 GRAM_LOSS_MAX_N = 1729
 # wide layers: the quadratic form on the i8 matrix cores up to this system size: measured per calibration, BraTS
 # (n = 3457, 6913) 674 -> 657 ms with it; LiTS with its 512-channel layers (n = 13825) included 2110 -> 2169 ms (5.4 ms
@@ -40,6 +42,79 @@ def get_ops(device):
     return hip_ops.get_ops(device)
 
 
+def _call_if(ops, name, *args):
+    """ops.<name>(*args) where the backend has that entry point, else False (the CPU stand-ins of the tests lack the
+    optional kernels and the questions about them)."""
+    fn = getattr(ops, name, None)
+    return fn(*args) if fn is not None else False
+
+
+class LayerPaths(NamedTuple):
+    """The kernels one layer's calibration takes: layer_paths() chooses them, after() applies what only a call tells."""
+    conv: Optional[str]      # integer family of the loss conv: None (the fp32 conv), "i8", "i8s" (direct gather)
+    gram_i8: bool            # the Gram system from exact integer sums (else ops.gram)
+    losses: Optional[str]    # the 200 losses: None (the loss conv), "gram_f64", "gram_i8" or "gram_f64_fp_input"
+    want_idx: bool           # the level ids of the quantised input are needed
+    fwd_i8: bool             # the final forward runs on the i8 matrix cores
+
+    @property
+    def loss_kind(self) -> int:
+        return {None: 0, "i8": 1, "i8s": 2}[self.conv]
+
+    def after(self, att_classes_ok: bool = True, planes_ok: bool = True) -> "LayerPaths":
+        """att_classes() returned None (more distinct weights than the integer Gram kernel takes): the fp32 Gram system,
+        no losses from it, level ids - and with them the i8 forward - only for an integer conv.  gram_loss_i8_planes()
+        returned None (entries beyond its planes): the losses come from the loss conv again, nothing else changes."""
+        p = self
+        if p.gram_i8 and not att_classes_ok:
+            p = p._replace(gram_i8=False, losses=None, want_idx=p.conv is not None,
+                           fwd_i8=p.fwd_i8 and p.conv is not None)
+        return p._replace(losses=None) if p.losses == "gram_i8" and not planes_ok else p
+
+
+def layer_paths(ops, geom, act_levels, w_levels, has_bias, c2, n_sys, voxels, *, q_act, act_inited, exact_int,
+                channel_wise, gram_loss_enabled, gram_loss_max_n, gram_loss_i8_max_n) -> LayerPaths:
+    """The paths of a layer with n_sys = k^3 c1 (+ 1) unknowns and `voxels` output voxels per output channel, from its
+    arguments alone; `ops` only answers what it supports."""
+    int_ok = bool(q_act and not act_inited and exact_int)      # the level ids of an input quantised by a scale fitted here
+    conv = None
+    # channel mode: the integer conv losses and the i8 forward fold ONE weight scale into their arithmetic - off; the
+    # integer Gram accumulation and the fp64 Gram loss (kind 4) take G as fp32 values and stay
+    if int_ok and not channel_wise:
+        # exact-integer evaluation of the 200 per-iteration losses (north_star's "int-simulated" forward)
+        if _call_if(ops, "conv_i8_supported", geom, act_levels, w_levels):
+            conv = "i8"
+        # ... through the direct-gather kernel for short-K layers and the 256-level first/last layers
+        elif _call_if(ops, "conv_i8s_supported", geom, act_levels, w_levels):
+            conv = "i8s"
+    # exact-integer evaluation of the Gram system too (exact integer sums, weights applied per attention class)
+    gram_i8 = bool(int_ok and _call_if(ops, "gram_i8_supported", geom, act_levels))
+    # Losses of the 200 iterates from the unweighted Gram system of the same integer pass (effq_gram_loss) instead of
+    # 200 passes over the voxels, where the voxel count is far above n = k^3 c1 + 1 (the conv is cheaper on the small
+    # volumes of the wide layers)
+    many_voxels = n_sys <= gram_loss_max_n and voxels >= 8 * n_sys
+    losses = None
+    if gram_i8 and gram_loss_enabled:
+        if many_voxels and hasattr(ops, "gram_loss"):
+            losses = "gram_f64"
+        # ... and on the wide layers (n above GRAM_LOSS_MAX_N: the fp64 evaluation would cost more than the conv pass)
+        # with the quadratic form on the i8 matrix cores: both of its factors are small integers there (effq_gram_loss_i8)
+        elif (not channel_wise and gram_loss_max_n < n_sys <= gram_loss_i8_max_n and
+              _call_if(ops, "gram_loss_i8_supported", c2, n_sys, has_bias, w_levels)):
+            losses = "gram_i8"
+    # full-precision input (first conv, classifier: quirk Q14): the same 200 losses from an fp64 Gram system
+    elif (not q_act and gram_loss_enabled and exact_int and many_voxels and
+          _call_if(ops, "gram_f64_supported", geom, has_bias)):
+        losses = "gram_f64_fp_input"
+    want_idx = conv is not None or gram_i8
+    # the final forward on the i8 matrix cores where the level ids of the input are at hand and the shape has a kernel
+    # (32 -> 32 and 64 -> 64 channels at 3^3: the layers with the most voxels): an exact integer contraction + one
+    # multiply-add per output, HBM-bound, instead of the f32 conv (2.6 -> 0.3 ms at 16 x 64^3 voxels)
+    fwd_i8 = bool(int_ok and want_idx and not channel_wise and
+                  _call_if(ops, "conv_i8_out_supported", geom, act_levels, w_levels))
+    return LayerPaths(conv, gram_i8, losses, want_idx, fwd_i8)
+
+
 class SumReducer:
     """Data-parallel SUM over calibration-volume shards (RCCL all-reduce; identity on one rank)."""
 
@@ -49,7 +124,7 @@ class SumReducer:
         import torch.distributed as dist
         self.dist = dist
         # EFFQ_DP_FORCE=1: run the collectives even on one rank (exercises the RCCL path on a single GPU)
-        force = _os.environ.get("EFFQ_DP_FORCE", "0") == "1"
+        force = os.environ.get("EFFQ_DP_FORCE", "0") == "1"
         self.on = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force)
         self.group = group
         self.direct = None
@@ -372,37 +447,78 @@ class EfficientQConvHIP(PTQConv):
         return math.sqrt(max(ss - s * s / n, 0.0) / (n - 1))
 
     def ptq(self, x):
-        ops = get_ops(x.device)
-        red = SumReducer()
-        dev = x.device
+        c = self._layer_inputs(x)
+        ops, red = c.ops, c.red
+        rho_scale, y_dim, att, sx, syy_local = self._statistics(c)
+        paths = layer_paths(ops, c.geom, self.qlvl_act, self.qlvl_w, c.has_b, c.c2, c.n_sys, c.voxels, q_act=self.q_act,
+                            act_inited=self._act_inited, exact_int=self.lwq_exact_int, channel_wise=self.channel_wise,
+                            gram_loss_enabled=GRAM_LOSS_DEFAULT, gram_loss_max_n=GRAM_LOSS_MAX_N,
+                            gram_loss_i8_max_n=GRAM_LOSS_I8_MAX_N)
+        att_cls = ops.att_classes(att) if paths.gram_i8 else None
+        paths = paths.after(att_classes_ok=att_cls is not None)
+        xq, xidx, act_iters = self._quantise_input(c, sx, paths.want_idx)
+        rho = self.lwq_rho * rho_scale                                    # (:74-76)
+        rho_m = self.lwq_rho_max * rho_scale
+        eta = self.lwq_eta * rho_scale
+        A0, B0, loss_gram, paths = self._gram_system(c, paths, xq, xidx, att, att_cls, syy_local)
+        t_loop0 = time.perf_counter()
+        run = self._admm_run(c, paths, A0, B0, xq, xidx, loss_gram, rho, rho_m, eta)
+        t_enq = time.perf_counter() - t_loop0     # host time to enqueue the 200 iterations (diagnostic)
+        red(run.hist)
+        best_G, best_b, best = ops.admm_select_best(run)
+        fin = self._final_forward(c, paths, run, best, best_G, best_b, xq, xidx, att)
+        red(fin)
+        info = ops.admm_read(run, best, extra=fin)                         # ONE host sync for the loop and the final loss
+        t_loop = time.perf_counter() - t_loop0
+        self._print_progress(run, info["hist"], rho, rho_m, eta, y_dim)
+        self._raise_on_error(ops, info)
+        _call_if(ops, "release_retired")     # every stream was joined and the host has synchronised
+        self._commit(c, best_G, best_b, info["alpha_w"])
+        fin_h, best_h, numel = info["extra"], info["best"], y_dim * 1.0
+        lossf = (fin_h[1] if att is not None else fin_h[0]) / numel
+        if self.layer_loss is not None:
+            self.layer_loss.append(f'{self.name:45s}:{lossf}')
+        self.last_trace = dict(rho_scale=rho_scale, best_iter=int(best_h[1]), best_mse=best_h[0] / numel,
+                               final_mse=fin_h[0] / numel, layer_loss=lossf, act_iters=act_iters,
+                               w_iters=info["w_iters"], alpha_w=info["alpha_w"],
+                               loss_history=[h / numel for h in info["hist"]],
+                               exact_int=paths.conv is not None or paths.losses is not None, exact_gram=paths.gram_i8,
+                               gram_loss=paths.losses is not None, host_enqueue_s=t_enq, admm_loop_s=t_loop,
+                               channel_wise=self.channel_wise, paths=paths._asdict())
+
+    def _layer_inputs(self, x):
+        """What the steps of ptq read and none of them changes; n_sys = k^3 c1 (+ 1) unknowns per output channel."""
+        ops, red, dev, c2, has_b = get_ops(x.device), SumReducer(), x.device, self.out_channels, self.bias is not None
         xn = to_ndhwc(x.detach())
         yn = to_ndhwc(self.output_fp.detach().to(dev))
         geom = self._geom(x)
         W0 = self.weight.data.contiguous()
-        has_b = self.bias is not None
         b0 = self.bias.data.contiguous() if has_b else None
-        c2 = self.out_channels
-        nw = W0.numel() // c2
+        return SimpleNamespace(ops=ops, red=red, dev=dev, x=x, xn=xn, yn=yn, geom=geom, W0=W0, b0=b0, has_b=has_b, c2=c2,
+                               n_sys=W0.numel() // c2 + int(has_b), voxels=yn.numel() // c2)
 
+    def _statistics(self, c):
+        """(rho_scale, y_dim, att, sx, syy_local): the layer's moments, packed into one all-reduce and one host read."""
+        ops, red = c.ops, c.red
         # rho_scale = max(numel(y)*std(y) / (numel(W)*std(W)), 1) [* mean(att)]     (EfficientQConv.py:43-49, :51-62)
         # the three moment triples are enqueued first and read by ONE device->host copy (each read empties the queue:
         # the device idles for the round trip)
-        my = ops.moments(yn)
+        my = ops.moments(c.yn)
         syy_local = my[1:2].clone()           # sum y^2 over THIS rank's voxels (the loss from the Gram system adds it)
-        mw = ops.moments(W0)
+        mw = ops.moments(c.W0)
         att = None
         if self.lwq_verbose:
             print(f'Calibrating {self.name}')
         if self.mask_pyramid:
             for mask in self.mask_pyramid:
                 if tuple(mask.shape[1:]) == tuple(self.output_fp.shape[2:]):
-                    att = mask.to(dev).contiguous()
+                    att = mask.to(c.dev).contiguous()
                     break
         ma = ops.moments(att) if att is not None else None
         # data-parallel: the layer's three statistics triples - targets, attention weights, sum|x| of the input for the
         # start of its scale fit - travel as ONE message (they were three)
         fit_here = bool(self.q_act and not self._act_inited)
-        sx = ops.abs_sum(xn) if (fit_here and red and hasattr(ops, "abs_sum")) else None
+        sx = ops.abs_sum(c.xn) if (fit_here and red and hasattr(ops, "abs_sum")) else None
         if red:
             parts = [t for t in (my, ma, sx) if t is not None]
             pack = red(torch.cat(parts))
@@ -412,174 +528,126 @@ class EfficientQConvHIP(PTQConv):
                 off += t.numel()
         mh = torch.cat([my, mw] + ([ma] if ma is not None else [])).tolist()
         y_dim = mh[2]
-        rho_scale = max(y_dim * self._std(mh[0:3]) / (W0.numel() * self._std(mh[3:6])), 1.0)
+        rho_scale = max(y_dim * self._std(mh[0:3]) / (c.W0.numel() * self._std(mh[3:6])), 1.0)
         if ma is not None:
             rho_scale *= mh[6] / mh[8]
+        return rho_scale, y_dim, att, sx, syy_local
 
-        act_iters = 0
-        xidx = None
-        # exact-integer evaluation of the 200 per-iteration losses (north_star's "int-simulated" forward)
-        use_i8 = bool(self.q_act and not self._act_inited and self.lwq_exact_int and
-                      getattr(ops, "conv_i8_supported", lambda *a: False)(geom, self.qlvl_act, self.qlvl_w))
-        # ... through the direct-gather kernel for short-K layers and the 256-level first/last layers
-        use_i8s = bool((not use_i8) and self.q_act and not self._act_inited and self.lwq_exact_int and
-                       getattr(ops, "conv_i8s_supported", lambda *a: False)(geom, self.qlvl_act, self.qlvl_w))
-        int_conv = use_i8 or use_i8s
-        # ... and of the Gram system (exact integer sums, weights applied per attention class)
-        use_gi8 = bool(self.q_act and not self._act_inited and self.lwq_exact_int and
-                       getattr(ops, "gram_i8_supported", lambda *a: False)(geom, self.qlvl_act))
-        # channel mode: the integer conv losses and the i8 forward fold ONE weight scale into their arithmetic - off; the
-        # integer Gram accumulation and the fp64 Gram loss (kind 4) take G as fp32 values and stay
-        chan = self.channel_wise
-        if chan:
-            use_i8 = use_i8s = int_conv = False
-        att_cls = ops.att_classes(att) if use_gi8 else None
-        use_gi8 = att_cls is not None
-        if self.q_act:                                                     # (:64-72)
-            if self._act_inited:
-                xq = to_ndhwc(self._quantize_act(x))
-            else:
-                kw_fit = dict(abs_sums=sx) if sx is not None else {}
-                a_act, act_iters, st = ops.fit_scale(xn, self.qlvl_act, 0.0, 1.0, reducer=red or None,
-                                                     guess_iters=12 * self.qlvl_act, **kw_fit)
-                self.alpha_act.data = torch.tensor(a_act, dtype=x.dtype, device=dev)
-                xq, _, xidx = ops.quant_dequant_f64path(xn, st, self.qlvl_act, 0.0, 1.0, want_idx=int_conv or use_gi8)
-        else:
-            xq = xn
+    def _quantise_input(self, c, sx, want_idx):
+        """(xq, xidx, act_iters): the input as the loop sees it (:64-72); fits alpha_act where it is not initialised."""
+        if not self.q_act:
+            return c.xn, None, 0
+        if self._act_inited:
+            return to_ndhwc(self._quantize_act(c.x)), None, 0
+        kw_fit = dict(abs_sums=sx) if sx is not None else {}
+        a_act, act_iters, st = c.ops.fit_scale(c.xn, self.qlvl_act, 0.0, 1.0, reducer=c.red or None,
+                                               guess_iters=12 * self.qlvl_act, **kw_fit)
+        self.alpha_act.data = torch.tensor(a_act, dtype=c.x.dtype, device=c.dev)
+        xq, _, xidx = c.ops.quant_dequant_f64path(c.xn, st, self.qlvl_act, 0.0, 1.0, want_idx=want_idx)
+        return xq, xidx, act_iters
 
-        rho = self.lwq_rho * rho_scale                                    # (:74-76)
-        rho_m = self.lwq_rho_max * rho_scale
-        eta = self.lwq_eta * rho_scale
-
-        # Losses of the 200 iterates from the unweighted Gram system of the same integer pass (effq_gram_loss) instead of
-        # 200 passes over the voxels, where the voxel count is far above n = k^3 c1 + 1 (the conv is cheaper on the small
-        # volumes of the wide layers)
-        n_sys = nw + int(has_b)
-        loss_gram = None
-        use_gl = bool(use_gi8 and GRAM_LOSS_DEFAULT and hasattr(ops, "gram_loss") and n_sys <= GRAM_LOSS_MAX_N and
-                      yn.numel() // c2 >= 8 * n_sys)
-        # ... and on the wide layers (n above GRAM_LOSS_MAX_N: the fp64 evaluation would cost more than the conv pass) with
-        # the quadratic form on the i8 matrix cores: both of its factors are small integers there (effq_gram_loss_i8)
-        use_gl8 = bool(use_gi8 and GRAM_LOSS_DEFAULT and not use_gl and not chan and
-                       GRAM_LOSS_MAX_N < n_sys <= GRAM_LOSS_I8_MAX_N and
-                       getattr(ops, "gram_loss_i8_supported", lambda *a: False)(c2, n_sys, has_b, self.qlvl_w))
-        if use_gi8 and (use_gl or use_gl8):
-            A0, B0, Au, Bu = ops.gram_i8(xidx, att_cls, yn, geom, has_b, self.alpha_act.data, self.qlvl_act,
-                                         unweighted=True)
+    def _gram_system(self, c, paths, xq, xidx, att, att_cls, syy_local):
+        """(A0, B0, loss_gram, paths): the Gram system, summed over the ranks, and the operands of the Gram losses."""
+        ops, a_act, loss_gram = c.ops, self.alpha_act.data, None
+        if paths.gram_i8 and paths.losses:
+            A0, B0, Au, Bu = ops.gram_i8(xidx, att_cls, c.yn, c.geom, c.has_b, a_act, self.qlvl_act, unweighted=True)
             loss_gram = (Au, Bu, syy_local)
-            if use_gl8:
-                planes = ops.gram_loss_i8_planes(Au, has_b, self.alpha_act.data, self.qlvl_act, yn.numel() // c2)
+            if paths.losses == "gram_i8":
+                planes = ops.gram_loss_i8_planes(Au, c.has_b, a_act, self.qlvl_act, c.voxels)
+                paths = paths.after(planes_ok=planes is not None)
                 loss_gram = (Au, Bu, syy_local, planes) if planes is not None else None
-        elif use_gi8:                                                      # (:87-91, solver.py:282-314)
-            A0, B0 = ops.gram_i8(xidx, att_cls, yn, geom, has_b, self.alpha_act.data, self.qlvl_act)
+        elif paths.gram_i8:                                                # (:87-91, solver.py:282-314)
+            A0, B0 = ops.gram_i8(xidx, att_cls, c.yn, c.geom, c.has_b, a_act, self.qlvl_act)
         else:
-            A0, B0 = ops.gram(xq, att, yn, geom, has_b)
-            # full-precision input (first conv, classifier: quirk Q14): the same 200 losses from an fp64 Gram system
-            if (not self.q_act and GRAM_LOSS_DEFAULT and self.lwq_exact_int and n_sys <= GRAM_LOSS_MAX_N and
-                    yn.numel() // c2 >= 8 * n_sys and
-                    getattr(ops, "gram_f64_supported", lambda *a: False)(geom, has_b)):
-                Au, Bu = ops.gram_f64(xq, yn, geom, has_b)
+            A0, B0 = ops.gram(xq, att, c.yn, c.geom, c.has_b)
+            if paths.losses:                                               # "gram_f64_fp_input"
+                Au, Bu = ops.gram_f64(xq, c.yn, c.geom, c.has_b)
                 loss_gram = (Au, Bu, syy_local)
-        if red:                      # one message per layer: upper triangle of A0 + B0
+        if c.red:                    # one message per layer: upper triangle of A0 + B0
             if hasattr(ops, "gram_reduce"):
-                ops.gram_reduce(A0, B0, red)
+                ops.gram_reduce(A0, B0, c.red)
             else:
-                red(A0)
-                red(B0)
+                c.red(A0)
+                c.red(B0)
+        return A0, B0, loss_gram, paths
 
+    def _admm_run(self, c, paths, A0, B0, xq, xidx, loss_gram, rho, rho_m, eta):
         # The 200 iterations (:99-144) are enqueued by ONE library call (effq_admm_run): the serial chain prox ->
         # scale fixed point -> projection/dual on this stream, the loss of iteration i (conv + MSE, used only to pick
         # the best iterate) on a second stream while the chain computes i+1, the inverses of A(rho) for the later rho
         # values (A changes only with rho: 4 inverses per layer, not 200 LU solves) on a third.  Per-iteration results
         # stay in rings, the squared errors in `hist`; the best iterate is selected afterwards - so the data-parallel
         # reduction of the 200 losses is ONE collective per layer.
-        import time as _time
-        t_loop0 = _time.perf_counter()
-        loss_kind = 1 if use_i8 else (2 if use_i8s else 0)
         kw = dict(loss_gram=loss_gram) if loss_gram is not None else {}
-        if chan:
+        if self.channel_wise:
             kw['channel_wise'] = True     # effq_fixed_point_channels_proj: one scale per output row
         if self.lwq_verbose:
             kw['residuals'] = True        # the per-iteration residual norms of the reference's progress line (:114-127)
-        run = ops.admm_run(A0, B0, W0, b0, geom, yn, xq=xq, xidx=xidx, act_alpha=self.alpha_act.data,
-                           act_levels=self.qlvl_act, loss_kind=loss_kind, rho=rho, rho_max=rho_m, eta=eta,
-                           iters=self.lwq_iter, period=RHO_PERIOD, levels=self.qlvl_w,
-                           overlap=self.lwq_overlap_loss, **kw)
-        t_enq = _time.perf_counter() - t_loop0     # host time to enqueue the 200 iterations (diagnostic)
-        red(run.hist)
-        best_G, best_b, best = ops.admm_select_best(run)
+        return c.ops.admm_run(A0, B0, c.W0, c.b0, c.geom, c.yn, xq=xq, xidx=xidx, act_alpha=self.alpha_act.data,
+                              act_levels=self.qlvl_act, loss_kind=paths.loss_kind, rho=rho, rho_max=rho_m, eta=eta,
+                              iters=self.lwq_iter, period=RHO_PERIOD, levels=self.qlvl_w,
+                              overlap=self.lwq_overlap_loss, **kw)
+
+    def _final_forward(self, c, paths, run, best, best_G, best_b, xq, xidx, att):
         # (:161-166) the final loss - and, from the same pass, the layer's quantised output, which forward() hands to the
         # next layer right after this call (PTQConv.py:160-163 runs the same conv a second time): the fp32 activation
         # quant-dequant is fused into the tile load, exactly as in the quantised forward.  Enqueued BEFORE the layer's
         # one device->host read, which then carries its two sums as well.
         fuse = self.q_act and not self._act_inited
-        # ... on the i8 matrix cores where the level ids of the input are at hand and the shape has a kernel (32 -> 32 and
-        # 64 -> 64 channels at 3^3: the layers with the most voxels): an exact integer contraction + one multiply-add per
-        # output, HBM-bound, instead of the f32 conv (2.6 -> 0.3 ms at 16 x 64^3 voxels)
-        fwd_i8 = bool(fuse and xidx is not None and self.lwq_exact_int and not chan and
-                      getattr(ops, "conv_i8_out_supported", lambda *a: False)(geom, self.qlvl_act, self.qlvl_w))
-        if fwd_i8:
+        if paths.fwd_i8:
             st_best = run.state_ring.index_select(0, best[1:2].to(torch.long)).reshape(-1)    # the best iterate's scale
-            out, fin = ops.conv_forward_i8(xidx, best_G, best_b, geom, yn, att, self.alpha_act.data, self.qlvl_act,
-                                           st_best, self.qlvl_w)
+            out, fin = c.ops.conv_forward_i8(xidx, best_G, best_b, c.geom, c.yn, att, self.alpha_act.data, self.qlvl_act,
+                                             st_best, self.qlvl_w)
         else:
-            out, fin = ops.conv_step(xn if fuse else xq, best_G, best_b, geom, yn, att,
-                                     act_alpha=self.alpha_act.data if fuse else None,
-                                     act_levels=self.qlvl_act if fuse else 0, want_out=True)
+            out, fin = c.ops.conv_step(c.xn if fuse else xq, best_G, best_b, c.geom, c.yn, att,
+                                       act_alpha=self.alpha_act.data if fuse else None,
+                                       act_levels=self.qlvl_act if fuse else 0, want_out=True)
         self._ptq_out = out if (fuse or not self.q_act) else None
-        red(fin)
-        info = ops.admm_read(run, best, extra=fin)                         # ONE host sync for the loop and the final loss
-        t_loop = _time.perf_counter() - t_loop0
-        a_w, w_iters, hist, best_h = info["alpha_w"], info["w_iters"], info["hist"], info["best"]
-        if self.lwq_verbose and getattr(run, "res", None) is not None:
-            # "print every 10 admm iters" (EfficientQConv.py:124-127), after the loop: the iterations are enqueued as a whole
-            res, r_i = run.res.cpu(), rho
-            for i in range(self.lwq_iter):
-                if i % 10 == 0:
-                    print(f'ADMM iter {i + 1}: primal residual = {float(res[i, 0]) ** 0.5:.4f}, '
-                          f'dual residual = {r_i * float(res[i, 1]) ** 0.5:.4f}, rho = {r_i:.4f}, eta = {eta:.4f}, '
-                          f'loss = {hist[i] / (y_dim * 1.0):.7f}.')
-                if i % RHO_PERIOD == 0:
-                    r_i = r_i * 2 if r_i * 2 <= rho_m else rho_m
+        return fin
+
+    def _print_progress(self, run, hist, rho, rho_m, eta, y_dim):
+        if not (self.lwq_verbose and getattr(run, "res", None) is not None):
+            return
+        # "print every 10 admm iters" (EfficientQConv.py:124-127), after the loop: the iterations are enqueued as a whole
+        res, r_i = run.res.cpu(), rho
+        for i in range(self.lwq_iter):
+            if i % 10 == 0:
+                print(f'ADMM iter {i + 1}: primal residual = {float(res[i, 0]) ** 0.5:.4f}, '
+                      f'dual residual = {r_i * float(res[i, 1]) ** 0.5:.4f}, rho = {r_i:.4f}, eta = {eta:.4f}, '
+                      f'loss = {hist[i] / (y_dim * 1.0):.7f}.')
+            if i % RHO_PERIOD == 0:
+                r_i = r_i * 2 if r_i * 2 <= rho_m else rho_m
+
+    def _raise_on_error(self, ops, info):
         if info["err"] >= 1000:
             raise RuntimeError(f'{self.name}: the unweighted Gram system is not the integer system effq_gram_loss_i8 '
                                f'expects (flag {info["err"] // 1000})')
-        if info["err"] != 0:                                               # layer_helper.py:62-64
-            if info["err"] == 2:
-                where = ''
-                if chan:
-                    i_cap = next((i for i, w in enumerate(w_iters) if w >= 100 * self.qlvl_w), None)
-                    if i_cap is not None:
-                        where = f' (output channel {info["w_iters_rows"][i_cap]}, ADMM iteration {i_cap})'
-                raise RuntimeWarning(f'Exceed maximum iteration ({100 * self.qlvl_w}) for alpha optimization{where}')
-            # state 3 = the grid barrier of the cooperative fixed point timed out (its workgroups were not co-resident):
-            # its barrier words in the reduction workspace are left non-zero - clear them before reporting
-            if hasattr(ops, "_red_ws"):
-                ops._red_ws.zero_()
-            raise RuntimeError(f'weight-scale fixed point did not finish (device state {info["err"]}: grid barrier '
-                               f'time-out of the cooperative kernel)')
-        if hasattr(ops, "release_retired"):
-            ops.release_retired()        # every stream was joined and the host has synchronised
+        if info["err"] == 0:
+            return
+        if info["err"] == 2:                                               # layer_helper.py:62-64
+            where = ''
+            if self.channel_wise:
+                i_cap = next((i for i, w in enumerate(info["w_iters"]) if w >= 100 * self.qlvl_w), None)
+                if i_cap is not None:
+                    where = f' (output channel {info["w_iters_rows"][i_cap]}, ADMM iteration {i_cap})'
+            raise RuntimeWarning(f'Exceed maximum iteration ({100 * self.qlvl_w}) for alpha optimization{where}')
+        # state 3 = the grid barrier of the cooperative fixed point timed out (its workgroups were not co-resident):
+        # its barrier words in the reduction workspace are left non-zero - clear them before reporting
+        if hasattr(ops, "_red_ws"):
+            ops._red_ws.zero_()
+        raise RuntimeError(f'weight-scale fixed point did not finish (device state {info["err"]}: grid barrier '
+                           f'time-out of the cooperative kernel)')
+
+    def _commit(self, c, best_G, best_b, a_w):
         self.weight.data = best_G.reshape(self.weight.shape)               # (:147-158)
-        if has_b:
+        if c.has_b:
             self.bias.data = best_b
-        if chan:
+        if self.channel_wise:
             # the BEST iterate's scales (not the last iterate's as in the per-tensor quirk Q6): the saved weights then lie
             # exactly on alpha_w's grids, and store_int_weight is exact
-            self.alpha_w.data = torch.tensor(a_w, dtype=x.dtype, device=dev).reshape(c2, 1, 1, 1)
+            self.alpha_w.data = torch.tensor(a_w, dtype=c.x.dtype, device=c.dev).reshape(c.c2, 1, 1, 1)
         else:
-            self.alpha_w.data = torch.tensor(a_w, dtype=x.dtype, device=dev)   # LAST iterate's scale (quirk Q6)
-        fin_h = info["extra"]
-        numel = y_dim * 1.0
-        lossf = (fin_h[1] if att is not None else fin_h[0]) / numel
-        if self.layer_loss is not None:
-            self.layer_loss.append(f'{self.name:45s}:{lossf}')
-        self.last_trace = dict(rho_scale=rho_scale, best_iter=int(best_h[1]), best_mse=best_h[0] / numel,
-                               final_mse=fin_h[0] / numel, layer_loss=lossf, act_iters=act_iters,
-                               w_iters=w_iters, alpha_w=a_w, loss_history=[h / numel for h in hist],
-                               exact_int=int_conv or loss_gram is not None, exact_gram=use_gi8,
-                               gram_loss=loss_gram is not None, host_enqueue_s=t_enq, admm_loop_s=t_loop,
-                               channel_wise=chan)
+            self.alpha_w.data = torch.tensor(a_w, dtype=c.x.dtype, device=c.dev)   # LAST iterate's scale (quirk Q6)
 
     def compute_quant_error(self, output_fp, Qw, Qact):
         """EfficientQConv.py:168-172."""

@@ -99,9 +99,9 @@ def calib(reps=2, nvol=16, size=128):
     print(f"{'layer':45s} {'loss path (tensor -> channel)':34s} {'layer_loss tensor':>18s} {'channel':>12s} {'ratio':>7s}")
 
     def kind(tr):            # gram: loss kinds 4 / 5 (Gram system), int-conv: 1 / 2, f32-conv: 0
-        if tr["gram_loss"]:
+        if tr["paths"]["losses"]:
             return "gram"
-        return "int-conv" if tr["exact_int"] else "f32-conv"
+        return "int-conv" if tr["paths"]["conv"] else "f32-conv"
     tot = {False: 0.0, True: 0.0}
     for (name, tr_t), (_, tr_c) in zip(last[False][1], last[True][1]):
         lt, lc = tr_t["layer_loss"], tr_c["layer_loss"]
