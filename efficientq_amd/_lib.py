@@ -245,6 +245,8 @@ SIGNATURES = {
     "effq_prep_reorient": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "effq_prep_reorient_plan": (_I, [_P, _I, _I, _P]),
     "effq_prep_align": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "effq_prep_bins": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P]),
+    "effq_prep_joint_hist": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _F, _F, _I, _I, _I, _P, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -293,6 +295,9 @@ PREP_QUANTILE_MAX = 4
 PREP_SMOOTH_MAX_RADIUS = 32
 # include/effq_hip.h (EFFQ_PREP_SPLINE_PASS_*): the prefilter passes of effq_prep_spline_prefilter
 PREP_SPLINE_PASSES = {"d": 1, "h": 2, "w": 4}
+# include/effq_hip.h (EFFQ_PREP_REGISTER_BINS, EFFQ_PREP_REGISTER_MAX_K): the intensity bins of effq_prep_bins and
+# effq_prep_joint_hist, 255 for a voxel that is not sampled, and the most candidate matrices of one call
+PREP_REGISTER_BINS, PREP_REGISTER_SKIP, PREP_REGISTER_MAX_K = 32, 255, 16
 
 _lib = None
 

@@ -20,6 +20,7 @@
 #include <math.h>
 #include <type_traits>
 #include "common.h"
+#include "prep_geom.h"
 #include "prep_rows.h"
 
 namespace effq {
@@ -33,19 +34,7 @@ struct AlignParams {
   double m[12];
 };
 
-// the field of view of one axis; false for a NaN
-__device__ __forceinline__ bool in_fov(double s, unsigned n) { return s >= -0.5 && s < (double)n - 0.5; }
-
-// the trilinear footprint of one axis at a coordinate inside the field of view
-__device__ __forceinline__ void align_axis(double s, unsigned n, unsigned& i0, unsigned& i1, float& l0, float& l1) {
-  const double top = (double)(n - 1);
-  const double c = s < 0.0 ? 0.0 : (s > top ? top : s);
-  const double fl = floor(c);
-  i0 = (unsigned)fl;
-  i1 = i0 + (i0 < n - 1 ? 1u : 0u);
-  l1 = (float)(c - fl);
-  l0 = 1.0f - l1;
-}
+// in_fov and align_axis, the field of view and the trilinear footprint of one axis, live in prep_geom.h
 __device__ __forceinline__ unsigned align_near(double s, unsigned n) {
   const unsigned i = (unsigned)floor(s + 0.5);
   return i < n - 1 ? i : n - 1;

@@ -44,6 +44,10 @@ everything else.  The map is written on the reference's grid with the reference'
 the columns ``align`` and ``align_inside`` (per modality the voxels of the grid inside that scan's field of view) after
 the ``interp`` column's place and before ``window_bounds`` and those of ``--blend``.
 
+``--prep_register rigid`` (with ``--prep_align``) registers every other modality onto the reference before it is
+resampled, as ``prep`` does (register.py; pass what the calibration data was prepared with).  ``predict.csv`` then gains
+the columns ``register``, ``register_params``, ``register_nmi`` and ``register_evals`` directly after the align columns.
+
 ``--prep_window pLO,pHI`` (``p0.5,p99.5``) clips every modality of every scan to a pair of its own percentiles over its
 own mask as ``prep`` does (pass what the calibration data was prepared with).  The column ``prep_window`` then reads
 ``p0.5 p99.5`` and ``predict.csv`` gains the column ``window_bounds`` (``lo hi`` per modality, joined by ``;``) after the

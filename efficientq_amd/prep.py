@@ -2,7 +2,7 @@
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
         [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|pLO,pHI|none] \
-        [--prep_align MODALITY] [--prep_orient RAS] \
+        [--prep_align MODALITY [--prep_register rigid]] [--prep_orient RAS] \
         [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
         [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
@@ -14,6 +14,10 @@ cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
                MODALITY (the reference) is resampled onto it by the two affines as they stand, trilinear for the images,
                nearest for the label, 0 outside the scan's field of view (the rule below at ALIGN_COLUMNS;
                csrc/prep_align.hip); no registration, and no filter when the reference is the coarser grid
+    register   --prep_register rigid (with --prep_align): every other modality, one on the reference's grid included,
+               is first registered to the reference rigidly by normalised mutual information (register.py, where the
+               rule stands; csrc/prep_register.hip) and then resampled once, through the matrix that was found; the
+               label is never registered and stays aligned by its header
     reorient   --prep_orient CODE: the axes permuted and reversed (csrc/reorient.hip) so that array axis 0, 1, 2 runs
                towards the three letters of CODE (one each of R/L, A/P, S/I: RAS, LPS, SAR, ...), whatever orientation
                the scan's affine gives it; --prep_spacing and --prep_min_size then refer to the oriented axes
@@ -46,7 +50,10 @@ With ``--prep_interp cubic`` prep.csv gains the column ``interp`` (``cubic``) af
 included.  With ``--prep_align`` prep.csv gains the columns ``align`` (the reference) and ``align_inside`` (per modality
 in the task's order, then the label: the voxels of the reference grid inside that scan's field of view, the whole grid
 for one that was not resampled) after ``interp``, and "the first modality" above is the reference: its shape, spacing,
-affine and header are the subject's, and sn_fn.txt names its scan.  With ``--prep_window pLO,pHI`` prep.csv gains
+affine and header are the subject's, and sn_fn.txt names its scan.  With ``--prep_register rigid`` the columns ``register``
+(``rigid``), ``register_params`` (per registered modality ``tx ty tz`` in mm and ``rx ry rz`` in degrees, ``repr(float)``,
+the modalities joined by ``;``), ``register_nmi`` (``before after``) and ``register_evals`` (``launches converged``)
+follow the align columns.  With ``--prep_window pLO,pHI`` prep.csv gains
 ``<modality>_win_lo`` and ``<modality>_win_hi`` per modality (``repr(float)``) after all others, ``interp`` and the
 align columns included.  A NaN or an Inf in a scan is carried along whole lines by the
 spline's recursions; the check of the standard deviation then stops the run at that subject.
@@ -526,7 +533,8 @@ class _Plan:
     """What the headers of one subject decide."""
 
     def __init__(self, entry: dict, mods: Sequence[str], spacing, min_size, orient: Optional[str] = None,
-                 antialias: bool = False, interp: str = "linear", align: Optional[str] = None):
+                 antialias: bool = False, interp: str = "linear", align: Optional[str] = None,
+                 register: Optional[str] = None):
         sn = self.subject = entry["subject"]
         self.interp = interp if spacing is not None else "linear"      # how the images are resampled (--prep_interp)
         self.window_bounds = None       # --prep_window pLO,pHI: (lo, hi) per modality, set by process_subject
@@ -548,6 +556,9 @@ class _Plan:
         self.ref = align if align is not None else mods[0]
         self.align = {}                 # name -> (M, source shape) of what is resampled; empty without --prep_align
         self.align_inside = None        # per modality, then the label: set by process_subject under --prep_align
+        self.register = register if align is not None else None       # --prep_register: 'rigid' or None
+        self.registered = {}            # modality -> register.Registered, set by process_subject under --prep_register
+        self.affines = {name: h["affine"] for name, h in heads.items()}
         self.shapes = {name: tuple(int(n) for n in h["shape"][:3]) for name, h in heads.items()}
         first = heads[self.ref]
         for name, h in heads.items():
@@ -559,7 +570,11 @@ class _Plan:
             m = align_matrix(sn, name, h["affine"], first["affine"])      # refused here also when the grids would pass
             try:
                 check_same_grid(sn, first, h, name)
+                same = True
             except PrepError:
+                same = False
+            # --prep_register: an image is resampled also from the reference's own grid, the label is not
+            if not same or (self.register and name != D.LABEL_MODALITY):
                 self.align[name] = (m, self.shapes[name])
         self.source_shape = tuple(int(n) for n in first["shape"][:3])
         self.source_spacing = tuple(first["spacing"])
@@ -640,7 +655,7 @@ def read_subjects(plans: Sequence[_Plan], mods: Sequence[str], thread_name_prefi
 
 # ---- the options prep and predict share --------------------------------------------------------------------------------
 class PrepOptions(NamedTuple):
-    """The nine --prep_* options, as the ``prep`` and the ``predict`` mission both take them (parse_options)."""
+    """The --prep_* options, as the ``prep`` and the ``predict`` mission both take them (parse_options)."""
     mask: str                               # --prep_mask: nonzero | all
     window: object                          # --prep_window: None, (lo, hi) or a PercentileWindow
     spacing: Optional[tuple]                # --prep_spacing d,h,w
@@ -649,15 +664,18 @@ class PrepOptions(NamedTuple):
     orient: Optional[str] = None            # --prep_orient CODE
     antialias: bool = False                 # --prep_antialias
     interp: str = "linear"                  # --prep_interp linear | cubic
+    register: Optional[str] = None          # --prep_register rigid; a qualifier of the switch below
     align: Optional[str] = None             # --prep_align MODALITY
 
     def plan(self, entry: dict, mods: Sequence[str]) -> _Plan:
-        return _Plan(entry, mods, self.spacing, self.min_size, self.orient, self.antialias, self.interp, self.align)
+        return _Plan(entry, mods, self.spacing, self.min_size, self.orient, self.antialias, self.interp, self.align,
+                     self.register)
 
     def columns(self) -> List[str]:
         """The optional columns of prep.csv and predict.csv that both missions write, in their order."""
         return (ORIENT_COLUMNS if self.orient else []) + (ANTIALIAS_COLUMNS if self.antialias else []) + \
-            (INTERP_COLUMNS if self.interp == "cubic" else []) + (ALIGN_COLUMNS if self.align else [])
+            (INTERP_COLUMNS if self.interp == "cubic" else []) + (ALIGN_COLUMNS if self.align else []) + \
+            (REGISTER_COLUMNS if self.register else [])
 
     def row_values(self, plan: _Plan) -> dict:
         """One subject's values of columns()."""
@@ -670,6 +688,12 @@ class PrepOptions(NamedTuple):
             row.update(interp=self.interp)
         if self.align:
             row.update(align=self.align, align_inside=_fmt(plan.align_inside))
+        if self.register:
+            from . import register as G
+            done = plan.registered.values()
+            row.update(register=self.register, register_params=";".join(G.params_text(r.theta) for r in done),
+                       register_nmi=";".join(f"{r.nmi_before!r} {r.nmi_after!r}" for r in done),
+                       register_evals=";".join(f"{r.evals} {int(r.converged)}" for r in done))
         return row
 
     def said(self, plan: _Plan, mods: Sequence[str]) -> str:
@@ -687,6 +711,11 @@ class PrepOptions(NamedTuple):
             voxels = float(np.prod(plan.source_shape))
             said += f", aligned to {self.align}: " + ", ".join(
                 f"{m} {n / voxels:.2f}" for m, n in zip(names, plan.align_inside) if m in plan.align)
+        if plan.registered:
+            from . import register as G
+            said += "".join(f", registered {m}: {math.sqrt(sum(v * v for v in r.theta[:3])):.1f} mm "
+                            f"{G.rotation_degrees(r.theta):.1f} deg, NMI {r.nmi_before:.3f} -> {r.nmi_after:.3f}"
+                            for m, r in plan.registered.items())
         return said
 
 
@@ -702,9 +731,12 @@ def parse_options(args, task: str, default_min_size=None) -> PrepOptions:
         min_size = _triple(args.prep_min_size, "--prep_min_size", int)
     else:
         min_size = D.PATCH_DEFAULT[task] if default_min_size is None else default_min_size
-    return PrepOptions(mask, window, spacing, min_size, bool(getattr(args, "prep_no_crop", False)),
-                       parse_orient(getattr(args, "prep_orient", None)), antialias_switch(args, spacing),
-                       interp_switch(args, spacing), align_switch(args, task))
+    from . import register as G
+    orient, antialias, interp = parse_orient(getattr(args, "prep_orient", None)), antialias_switch(args, spacing), \
+        interp_switch(args, spacing)
+    align = align_switch(args, task)
+    return PrepOptions(mask, window, spacing, min_size, bool(getattr(args, "prep_no_crop", False)), orient, antialias,
+                       interp, G.register_switch(args, align), align)
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------
@@ -783,6 +815,8 @@ def prep_csv_header(mods: Sequence[str]) -> List[str]:
 
 
 ORIENT_COLUMNS = ["source_orient", "orient"]      # prep.csv and predict.csv, only with --prep_orient
+# prep.csv and predict.csv, only with --prep_register, directly after ALIGN_COLUMNS
+REGISTER_COLUMNS = ["register", "register_params", "register_nmi", "register_evals"]
 
 
 def _fmt(v) -> str:
@@ -822,12 +856,20 @@ def _apply_window(ops, plan, x, window, mask: str) -> None:
         ops.prep_window(x, window[0], window[1])
 
 
-def _aligned(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str]):
+def _aligned(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.ndarray], mods: Sequence[str],
+             mask: str = "nonzero"):
     """--prep_align: (x, lab) on the reference's grid.  Each modality goes to the device alone and is copied, or aligned by
     its matrix, into its plane of the C x D x H x W tensor, the label likewise; plan.align_inside gets the voxels of the
-    grid inside each one's field of view, and a resampled scan that covers none of them stops the run."""
+    grid inside each one's field of view, and a resampled scan that covers none of them stops the run.  With
+    --prep_register the matrix of an image is the one the registration finds (plan.registered), formed again from the
+    values the tables record, and the image is still resampled once; the label keeps its header's matrix."""
     align = getattr(ops, "prep_align", None) or partial(ops_align.prep_align, ops)
     dev, grid = ops.device, plan.source_shape
+    plan.registered, ref = {}, None
+    if plan.register:
+        from . import register as G
+        ref = G.Reference(ops, plan.subject, plan.ref, torch.from_numpy(np.ascontiguousarray(imgs[plan.ref])).to(dev),
+                          plan.affines[plan.ref], mask)
     full = int(np.prod(grid))
     x = torch.empty((len(mods),) + grid, dtype=torch.float32, device=dev)
     lab = torch.empty((1,) + grid, dtype=torch.uint8, device=dev) if seg is not None else None
@@ -836,7 +878,12 @@ def _aligned(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional[np.nda
     for name, host, plane in zip(names, [imgs[m] for m in mods] + [seg], list(x) + [lab[0] if lab is not None else None]):
         t = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
         if name in plan.align:
-            t, counted[name] = align(t, plan.align[name][0], grid, nearest=name == D.LABEL_MODALITY)
+            m = plan.align[name][0]
+            if ref is not None and name != D.LABEL_MODALITY:
+                done = plan.registered[name] = G.register_rigid(ops, ref, name, t, plan.affines[name])
+                m = G.rigid_matrix(plan.subject, name, plan.affines[name], ref.affine, ref.shape,
+                                   G.params_theta(G.params_text(done.theta)))
+            t, counted[name] = align(t, m, grid, nearest=name == D.LABEL_MODALITY)
         plane.copy_(t)
     got = dict(zip(counted, torch.cat([n.reshape(1) for n in counted.values()]).cpu().tolist())) if counted else {}
     plan.align_inside = [int(got.get(name, full)) for name in names]
@@ -869,7 +916,7 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
         x = torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
         lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
     else:
-        x, lab = _aligned(ops, plan, imgs, seg, mods)
+        x, lab = _aligned(ops, plan, imgs, seg, mods, mask)
     if plan.orient is not None and not orient_is_identity(*plan.orient):
         x = ops.prep_reorient(x, *plan.orient)
         if lab is not None:
@@ -946,6 +993,9 @@ def run(args, ops=None) -> List[dict]:
         ops = get_ops(torch.device("cuda", int(getattr(args, "device", 0) or 0)))
 
     os.makedirs(data_dir, exist_ok=True)
+    if opts.register:
+        print(f"[prep] --prep_register {opts.register}: every modality but {opts.align} is registered to it; the label is "
+              f"never registered, it stays aligned by its header")
     sn_fn, restore, rows = {}, {}, []
     with closing(read_subjects(plans, mods, "effq-prep-read")) as subjects:       # a subject that fails ends the reads
         for plan, imgs, seg in subjects:

@@ -1235,6 +1235,36 @@ int effq_prep_reorient_plan(const int* src_axis, int flip_mask, int elem_bytes, 
 int effq_prep_align(const void* x, int D, int H, int W, const double* m, int mode, void* y, int OD, int OH, int OW,
                     long long* inside, void* stream);
 
+/* ---- rigid registration by mutual information (csrc/prep_register.hip; register.py and prep.py --prep_register, where
+ * the search is defined): the two device halves of the objective.
+ * The bin rule, all fp32 and nothing fused, with B = EFFQ_PREP_REGISTER_BINS:  t = (v - lo) * scale;  a NaN t is "not
+ * sampled";  t < 0 is bin 0,  t >= B is bin B - 1 (so -Inf and +Inf fall into the outer bins),  otherwise the bin is (int)t.
+ * effq_prep_bins: x (D, H, W) fp32 -> y (D, H, W) uint8, a voxel's bin 0 .. B - 1 or 255 for "not sampled"; with
+ *   mask_nonzero = 1 a voxel that is exactly 0 (either sign) is not sampled: the background of --prep_mask nonzero.  One
+ *   launch, four voxels and one 4-byte store per thread, no atomics.
+ * effq_prep_joint_hist: fbin (D, H, W) uint8 on the reference grid (a value of B or more is "not sampled"), mov
+ *   (MD, MH, MW) fp32, m: K row-major 3 x 4 matrices of HOST doubles, 1 <= K <= EFFQ_PREP_REGISTER_MAX_K, read before the
+ *   call returns, each mapping a reference voxel index (d, h, w, 1) to voxel coordinates of mov as effq_prep_align's does;
+ *   lo, scale: the bin range of mov; (sd, sh, sw) >= 1: the sample stride.  hist (device, uint64 [K][B][B], 8-B aligned) is
+ *   cleared by the call on the stream; hist[k][bf][bm] is then the number of sampled reference voxels (i sd, j sh, l sw)
+ *   inside the grid whose fbin is bf (not "not sampled"), whose coordinates under matrix k lie inside the field of view of
+ *   mov, and whose trilinear sample is not NaN and falls into bin bm.  Coordinates, field of view, clamp, weights and the
+ *   order of the eight products are those of EFFQ_PREP_LINEAR above, to the bit.  Two launches (the clear and the count); a
+ *   thread owns four consecutive sampled w of a row, reads their bins once and walks the K candidates; every workgroup
+ *   counts in K x B x B uint32 of LDS by integer atomics and adds its non-zero counters to hist with 64-bit integer
+ *   atomics: equal inputs give equal bits, there is no floating-point atomic, no workgroup waits for another, and the host
+ *   reads nothing inside the call.
+ * Refused with EFFQ_ERR_ARG before any launch: a null pointer, extents outside 1 ... 32767 or 2^31 voxels or more in either
+ * volume, K out of range, a stride below 1, a float pointer not 4-B aligned, hist not 8-B aligned, a matrix entry, lo or
+ * scale that is not finite, scale <= 0, mask_nonzero other than 0 and 1. */
+#define EFFQ_PREP_REGISTER_BINS 32
+#define EFFQ_PREP_REGISTER_MAX_K 16
+int effq_prep_bins(const float* x, int D, int H, int W, float lo, float scale, int mask_nonzero, unsigned char* y,
+                   void* stream);
+int effq_prep_joint_hist(const unsigned char* fbin, int D, int H, int W, const float* mov, int MD, int MH, int MW,
+                         const double* m, int K, float lo, float scale, int sd, int sh, int sw, unsigned long long* hist,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
