@@ -247,6 +247,11 @@ SIGNATURES = {
     "effq_prep_align": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P]),
     "effq_prep_bins": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P]),
     "effq_prep_joint_hist": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _F, _F, _I, _I, _I, _P, _P]),
+    "effq_prep_bias_log": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "effq_prep_bias_hist": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "effq_bias_fit_ws_bytes": (_SZ, [_I, _I, _I, _P, _P]),
+    "effq_prep_bias_fit": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _SZ, _P]),
+    "effq_prep_bias_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -298,6 +303,9 @@ PREP_SPLINE_PASSES = {"d": 1, "h": 2, "w": 4}
 # include/effq_hip.h (EFFQ_PREP_REGISTER_BINS, EFFQ_PREP_REGISTER_MAX_K): the intensity bins of effq_prep_bins and
 # effq_prep_joint_hist, 255 for a voxel that is not sampled, and the most candidate matrices of one call
 PREP_REGISTER_BINS, PREP_REGISTER_SKIP, PREP_REGISTER_MAX_K = 32, 255, 16
+# include/effq_hip.h (EFFQ_PREP_BIAS_BINS, EFFQ_PREP_BIAS_LEVELS, EFFQ_PREP_BIAS_LATTICE): the histogram bins of
+# effq_prep_bias_hist, the spline levels, and the doubles of the four lattices of effq_prep_bias_apply
+PREP_BIAS_BINS, PREP_BIAS_LEVELS, PREP_BIAS_LATTICE = 200, 4, 1863
 
 _lib = None
 

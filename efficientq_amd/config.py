@@ -119,6 +119,9 @@ def build_parser():
     p.add_argument('--prep_register', default=None, metavar='rigid',
                    help='prep, predict, with --prep_align: every other modality is first registered to the reference '
                         'rigidly by normalised mutual information, then resampled once; the label is not registered')
+    p.add_argument('--prep_bias', default=None, metavar='n4',
+                   help='prep, predict: before anything else every modality is divided by the smooth multiplicative bias '
+                        'field of an N4-style fit on the device; the label is not touched')
     p.add_argument('--prep_min_size', default=None, help='prep: d,h,w, the least extent of a crop (the task\'s patch)')
     p.add_argument('--prep_no_crop', action='store_true', help='prep: keep the whole grid')
     # the predict mission (predict.py): label maps of new scans from a snapshot (--resume) or the FP checkpoint
@@ -302,7 +305,7 @@ SCORE_FOREIGN = (('post', None), ('thresh', None), ('thr_sweep', False), ('save_
                  ('prep_spacing', None), ('prep_antialias', False), ('prep_interp', 'linear'), ('prep_min_size', None),
                  ('prep_no_crop', False))
 # refused like those; kept apart because tests/test_score_cpu.py pins the members of SCORE_FOREIGN
-SCORE_FOREIGN_ALIGN = (('prep_align', None), ('prep_register', None))
+SCORE_FOREIGN_ALIGN = (('prep_align', None), ('prep_register', None), ('prep_bias', None))
 
 
 def parse_score_class(text) -> tuple:

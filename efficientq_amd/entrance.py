@@ -223,6 +223,9 @@ def _switches(args):
     if getattr(args, 'prep_register', None) is not None:
         raise SystemExit('--prep_register registers source scans in the prep and predict missions: the ptq mission reads '
                          'prepared data (--data_dir) as it is, drop --prep_register')
+    if getattr(args, 'prep_bias', None) is not None:
+        raise SystemExit('--prep_bias corrects source scans in the prep and predict missions: the ptq mission reads '
+                         'prepared data (--data_dir) as it is, drop --prep_bias')
     if getattr(args, 'unlabelled', False):
         if not getattr(args, 'vs_fp', False):
             raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add '

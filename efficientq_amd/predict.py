@@ -44,6 +44,10 @@ everything else.  The map is written on the reference's grid with the reference'
 the columns ``align`` and ``align_inside`` (per modality the voxels of the grid inside that scan's field of view) after
 the ``interp`` column's place and before ``window_bounds`` and those of ``--blend``.
 
+``--prep_bias n4`` corrects the bias field of every modality before anything else, as ``prep`` does (bias.py).
+``predict.csv`` then gains the columns ``bias``, ``bias_iters``, ``bias_cv`` and ``bias_field`` directly before the place of
+the align columns.
+
 ``--prep_register rigid`` (with ``--prep_align``) registers every other modality onto the reference before it is
 resampled, as ``prep`` does (register.py; pass what the calibration data was prepared with).  ``predict.csv`` then gains
 the columns ``register``, ``register_params``, ``register_nmi`` and ``register_evals`` directly after the align columns.

@@ -1265,6 +1265,49 @@ int effq_prep_joint_hist(const unsigned char* fbin, int D, int H, int W, const f
                          const double* m, int K, float lo, float scale, int sd, int sh, int sw, unsigned long long* hist,
                          void* stream);
 
+/* ---- bias field correction (csrc/prep_bias.hip; bias.py and prep.py --prep_bias n4, where the rule is defined): the
+ * device steps of one N4-style correction of one scan.
+ * Samples: every call takes stride (sd, sh, sw) >= 1 and offset (od, oh, ow), 0 <= o < extent, as two HOST arrays of three
+ * ints; sample q of an axis is the full-grid index x = s q + o < X.  f is a dense fp32 array over the samples only.
+ * Spline: level l has n = 2^l spans and n + 3 control points per axis; for index x, t = (x + 0.5) / X * n, span k =
+ * floor(t), and the four uniform cubic B-spline weights at t - k lie on control points k .. k + 3.  A lattice of level l
+ * is (n + 3)^3 doubles, the last axis fastest.
+ * effq_prep_bias_log: v (D, H, W) fp32 -> m = 1 where v lies in its mask (mask_mode as above), is finite and > 0, else
+ *   0; u = fp32(log((double)v)) there, else 0.
+ * effq_prep_bias_hist: r = u - f (fp32) over the samples with m != 0.  hist (device, uint64, EFFQ_PREP_BIAS_BINS + 2,
+ *   8-B aligned) is cleared by the call on the stream.  hist[B] receives min r and max r as two uint32 (low word the min) in
+ *   the order-preserving code  c = bits ^ 0xffffffff for a negative float, bits | 0x80000000 otherwise;  hist[B + 1] the
+ *   number of samples.  With max > min, and with inv = 199 / ((double)max - (double)min), every sample adds, all in fp64,
+ *   t = ((double)r - min) * inv, k = min(floor(t), B - 2), a = min(t - k, 1), q = floor(a * 65536 + 0.5):  65536 - q to
+ *   hist[k] and q to hist[k + 1].  With max == min or no sample the counters stay 0.  Three launches; the counters are
+ *   64-bit integers in LDS per workgroup, then 64-bit integer atomics: equal inputs give equal bits.
+ * effq_prep_bias_fit: one iteration at `level` (0 .. EFFQ_PREP_BIAS_LEVELS - 1) with the sharpened table E (HOST, B
+ *   doubles, read before the call returns) over [lo, hi], the min and max effq_prep_bias_hist reported: per sample in m,
+ *   e = fp32(r - (E[k] (1 - a) + E[k + 1] a)) with t, k, a as above in fp64 (a not quantised); the lattice
+ *   phi_c = sum w_c^3 e / S / sum w_c^2 (S the sum of the 64 squared weights of the sample), 0 where the denominator is
+ *   0, all sums fp64 in a fixed order; phi is written, Phi += phi; on every sample f = f + fp32(eval(phi)); sums[0], sums[1]
+ *   (device doubles) receive the sums of exp(eval(phi)) and of its square over the samples in m.  Three launches, no
+ *   floating-point atomic, no workgroup waits for another; ws of effq_bias_fit_ws_bytes (0 for arguments that would
+ *   be refused) needs no initialisation.
+ * effq_prep_bias_apply: y = fp32((double)v / exp(f)) on the full grid, f the sum over the four levels, in their order, of
+ *   the lattices in Phi (device, EFFQ_PREP_BIAS_LATTICE doubles, level after level).  m and range (device, two uint32)
+ *   are given together or both null: range receives min and max of fp32(exp(f)) over m != 0 in the code above.
+ * Refused with EFFQ_ERR_ARG before any launch: a null pointer, extents outside 1 ... 32767 or 2^31 voxels or more, a
+ * stride below 1, an offset outside the axis, a level out of range, lo, hi or an entry of E that is not finite, hi <= lo,
+ * a pointer that is not aligned to its element; EFFQ_ERR_WORKSPACE for a workspace that is too small. */
+#define EFFQ_PREP_BIAS_BINS 200
+#define EFFQ_PREP_BIAS_LEVELS 4
+#define EFFQ_PREP_BIAS_LATTICE 1863
+int effq_prep_bias_log(const float* v, int D, int H, int W, int mask_mode, float* u, unsigned char* m, void* stream);
+int effq_prep_bias_hist(const float* u, const unsigned char* m, const float* f, int D, int H, int W, const int* stride,
+                        const int* offset, unsigned long long* hist, void* stream);
+size_t effq_bias_fit_ws_bytes(int D, int H, int W, const int* stride, const int* offset);
+int effq_prep_bias_fit(const float* u, const unsigned char* m, float* f, int D, int H, int W, const int* stride,
+                       const int* offset, int level, float lo, float hi, const double* E, double* phi, double* Phi,
+                       double* sums, void* ws, size_t ws_bytes, void* stream);
+int effq_prep_bias_apply(const float* v, const unsigned char* m, int D, int H, int W, const double* Phi, float* y,
+                         unsigned* range, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
