@@ -252,6 +252,9 @@ SIGNATURES = {
     "effq_bias_fit_ws_bytes": (_SZ, [_I, _I, _I, _P, _P]),
     "effq_prep_bias_fit": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _SZ, _P]),
     "effq_prep_bias_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "effq_prep_denoise_residual": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "effq_prep_denoise_ws_bytes": (_I, [_I, _I, _I, _P]),
+    "effq_prep_denoise_nlm": (_I, [_P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -306,6 +309,10 @@ PREP_REGISTER_BINS, PREP_REGISTER_SKIP, PREP_REGISTER_MAX_K = 32, 255, 16
 # include/effq_hip.h (EFFQ_PREP_BIAS_BINS, EFFQ_PREP_BIAS_LEVELS, EFFQ_PREP_BIAS_LATTICE): the histogram bins of
 # effq_prep_bias_hist, the spline levels, and the doubles of the four lattices of effq_prep_bias_apply
 PREP_BIAS_BINS, PREP_BIAS_LEVELS, PREP_BIAS_LATTICE = 200, 4, 1863
+# include/effq_hip.h (EFFQ_PREP_DENOISE_TILE_D, _H, _W): the output tile of one workgroup of effq_prep_denoise_nlm, and
+# the search radii it takes
+PREP_DENOISE_TILE = (8, 8, 62)
+PREP_DENOISE_MAX_RADIUS = 5
 
 _lib = None
 

@@ -119,6 +119,10 @@ def build_parser():
     p.add_argument('--prep_register', default=None, metavar='rigid',
                    help='prep, predict, with --prep_align: every other modality is first registered to the reference '
                         'rigidly by normalised mutual information, then resampled once; the label is not registered')
+    p.add_argument('--prep_denoise', default=None, metavar='nlm|nlmM',
+                   help='prep, predict: before anything else every modality is filtered by non-local means on the device '
+                        '(3^3 patches, search radius M = 1 ... 5, nlm is nlm3) at a noise level found from the scan; the '
+                        'label is not touched')
     p.add_argument('--prep_bias', default=None, metavar='n4',
                    help='prep, predict: before anything else every modality is divided by the smooth multiplicative bias '
                         'field of an N4-style fit on the device; the label is not touched')
@@ -305,7 +309,7 @@ SCORE_FOREIGN = (('post', None), ('thresh', None), ('thr_sweep', False), ('save_
                  ('prep_spacing', None), ('prep_antialias', False), ('prep_interp', 'linear'), ('prep_min_size', None),
                  ('prep_no_crop', False))
 # refused like those; kept apart because tests/test_score_cpu.py pins the members of SCORE_FOREIGN
-SCORE_FOREIGN_ALIGN = (('prep_align', None), ('prep_register', None), ('prep_bias', None))
+SCORE_FOREIGN_ALIGN = (('prep_align', None), ('prep_register', None), ('prep_bias', None), ('prep_denoise', None))
 
 
 def parse_score_class(text) -> tuple:

@@ -226,6 +226,9 @@ def _switches(args):
     if getattr(args, 'prep_bias', None) is not None:
         raise SystemExit('--prep_bias corrects source scans in the prep and predict missions: the ptq mission reads '
                          'prepared data (--data_dir) as it is, drop --prep_bias')
+    if getattr(args, 'prep_denoise', None) is not None:
+        raise SystemExit('--prep_denoise filters source scans in the prep and predict missions: the ptq mission reads '
+                         'prepared data (--data_dir) as it is, drop --prep_denoise')
     if getattr(args, 'unlabelled', False):
         if not getattr(args, 'vs_fp', False):
             raise SystemExit('--unlabelled: without labels only the validation against the FP network can run: add '

@@ -44,7 +44,12 @@ everything else.  The map is written on the reference's grid with the reference'
 the columns ``align`` and ``align_inside`` (per modality the voxels of the grid inside that scan's field of view) after
 the ``interp`` column's place and before ``window_bounds`` and those of ``--blend``.
 
-``--prep_bias n4`` corrects the bias field of every modality before anything else, as ``prep`` does (bias.py).
+``--prep_denoise nlmM`` filters every modality by non-local means before anything else, the bias field included, as
+``prep`` does (denoise.py; pass what the calibration data was prepared with).  ``predict.csv`` then gains the columns
+``denoise``, ``denoise_sigma``, ``denoise_samples`` and ``denoise_rms`` directly before the place of the bias columns.
+
+``--prep_bias n4`` corrects the bias field of every modality before anything else but the denoiser, as ``prep`` does
+(bias.py).
 ``predict.csv`` then gains the columns ``bias``, ``bias_iters``, ``bias_cv`` and ``bias_field`` directly before the place of
 the align columns.
 

@@ -2,7 +2,7 @@
 
     python -m efficientq_amd.entrance prep --task brats --src_list cases.csv --data_dir out/data \
         [--split_dir out/split --round 1 --val_every 5] [--prep_mask nonzero|all] [--prep_window lo,hi|pLO,pHI|none] \
-        [--prep_bias n4] [--prep_align MODALITY [--prep_register rigid]] [--prep_orient RAS] \
+        [--prep_denoise nlm|nlmM] [--prep_bias n4] [--prep_align MODALITY [--prep_register rigid]] [--prep_orient RAS] \
         [--prep_spacing d,h,w [--prep_antialias] [--prep_interp linear|cubic]] \
         [--prep_min_size d,h,w] [--prep_no_crop] [--access_type npy|npz]
 
@@ -14,8 +14,12 @@ cell is a subject without a label.  Per subject, on the device (csrc/prep.hip):
                MODALITY (the reference) is resampled onto it by the two affines as they stand, trilinear for the images,
                nearest for the label, 0 outside the scan's field of view (the rule below at ALIGN_COLUMNS;
                csrc/prep_align.hip); no registration, and no filter when the reference is the coarser grid
-    bias       --prep_bias n4: every modality, on its own grid and before anything else, is divided by the smooth
-               multiplicative field that an N4-style fit finds in it (bias.py, where the rule stands;
+    denoise    --prep_denoise nlm | nlmM (M = 1 ... 5, nlm is nlm3): every modality, on its own grid and before anything
+               else, the bias field included, is filtered by non-local means with 3^3 patches and a search window of
+               (2M + 1)^3 voxels at a noise level found from the scan itself (denoise.py, where the rule stands;
+               csrc/prep_denoise.hip); voxels outside the modality's mask keep their bits; the label is never touched
+    bias       --prep_bias n4: every modality, on its own grid and before anything else but the denoiser, is divided by
+               the smooth multiplicative field that an N4-style fit finds in it (bias.py, where the rule stands;
                csrc/prep_bias.hip); the label is never touched
     register   --prep_register rigid (with --prep_align): every other modality, one on the reference's grid included,
                is first registered to the reference rigidly by normalised mutual information (register.py, where the
@@ -59,6 +63,9 @@ the modalities joined by ``;``), ``register_nmi`` (``before after``) and ``regis
 follow the align columns.  With ``--prep_bias n4`` the columns ``bias`` (``n4``), ``bias_iters`` (per modality the
 iterations of the four levels, the modalities joined by ``;``), ``bias_cv`` (the last cv per modality) and ``bias_field``
 (``min max`` of exp(f) over the fit mask per modality) stand directly before the align columns' place, after ``interp``.
+With ``--prep_denoise nlmM`` the columns ``denoise`` (``nlmM``), ``denoise_sigma`` (the noise level per modality, the
+modalities joined by ``;``), ``denoise_samples`` (the residuals it was found from) and ``denoise_rms`` (the rms of what the
+filter removed over the mask) stand directly before the bias columns' place.
 With ``--prep_window pLO,pHI`` prep.csv gains
 ``<modality>_win_lo`` and ``<modality>_win_hi`` per modality (``repr(float)``) after all others, ``interp`` and the
 align columns included.  A NaN or an Inf in a scan is carried along whole lines by the
@@ -565,6 +572,7 @@ class _Plan:
         self.register = register if align is not None else None       # --prep_register: 'rigid' or None
         self.registered = {}            # modality -> register.Registered, set by process_subject under --prep_register
         self.bias = {}                  # modality -> bias.Corrected, set by process_subject under --prep_bias
+        self.denoise = {}               # modality -> denoise.Denoised, set by process_subject under --prep_denoise
         self.affines = {name: h["affine"] for name, h in heads.items()}
         self.shapes = {name: tuple(int(n) for n in h["shape"][:3]) for name, h in heads.items()}
         first = heads[self.ref]
@@ -671,6 +679,7 @@ class PrepOptions(NamedTuple):
     orient: Optional[str] = None            # --prep_orient CODE
     antialias: bool = False                 # --prep_antialias
     interp: str = "linear"                  # --prep_interp linear | cubic
+    denoise: Optional[int] = None           # --prep_denoise nlmM: the search radius M
     bias: Optional[str] = None              # --prep_bias n4
     register: Optional[str] = None          # --prep_register rigid; a qualifier of the switch below
     align: Optional[str] = None             # --prep_align MODALITY
@@ -682,7 +691,8 @@ class PrepOptions(NamedTuple):
     def columns(self) -> List[str]:
         """The optional columns of prep.csv and predict.csv that both missions write, in their order."""
         return (ORIENT_COLUMNS if self.orient else []) + (ANTIALIAS_COLUMNS if self.antialias else []) + \
-            (INTERP_COLUMNS if self.interp == "cubic" else []) + (BIAS_COLUMNS if self.bias else []) + \
+            (INTERP_COLUMNS if self.interp == "cubic" else []) + (DENOISE_COLUMNS if self.denoise else []) + \
+            (BIAS_COLUMNS if self.bias else []) + \
             (ALIGN_COLUMNS if self.align else []) + \
             (REGISTER_COLUMNS if self.register else [])
 
@@ -695,6 +705,11 @@ class PrepOptions(NamedTuple):
             row.update(antialias=_fmt(plan.sigmas))
         if self.interp == "cubic":
             row.update(interp=self.interp)
+        if self.denoise:
+            done = plan.denoise.values()
+            row.update(denoise=f"nlm{self.denoise}", denoise_sigma=";".join(repr(float(d.sigma)) for d in done),
+                       denoise_samples=";".join(str(int(d.samples)) for d in done),
+                       denoise_rms=";".join(repr(float(d.rms)) for d in done))
         if self.bias:
             done = plan.bias.values()
             row.update(bias=self.bias, bias_iters=";".join(_fmt(b.iters) for b in done),
@@ -730,6 +745,7 @@ class PrepOptions(NamedTuple):
             said += "".join(f", registered {m}: {math.sqrt(sum(v * v for v in r.theta[:3])):.1f} mm "
                             f"{G.rotation_degrees(r.theta):.1f} deg, NMI {r.nmi_before:.3f} -> {r.nmi_after:.3f}"
                             for m, r in plan.registered.items())
+        said += "".join(f", denoise {m} sigma {d.sigma:.1f} (rms {d.rms:.1f})" for m, d in plan.denoise.items())
         said += "".join(f", bias {m} {b.field_min:.2f}-{b.field_max:.2f} ({_fmt(b.iters)} it)" for m, b in plan.bias.items())
         return said
 
@@ -746,12 +762,12 @@ def parse_options(args, task: str, default_min_size=None) -> PrepOptions:
         min_size = _triple(args.prep_min_size, "--prep_min_size", int)
     else:
         min_size = D.PATCH_DEFAULT[task] if default_min_size is None else default_min_size
-    from . import bias as B, register as G
+    from . import bias as B, denoise as N, register as G
     orient, antialias, interp = parse_orient(getattr(args, "prep_orient", None)), antialias_switch(args, spacing), \
         interp_switch(args, spacing)
     align = align_switch(args, task)
     return PrepOptions(mask, window, spacing, min_size, bool(getattr(args, "prep_no_crop", False)), orient, antialias,
-                       interp, B.bias_switch(args), G.register_switch(args, align), align)
+                       interp, N.denoise_switch(args), B.bias_switch(args), G.register_switch(args, align), align)
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------
@@ -830,6 +846,8 @@ def prep_csv_header(mods: Sequence[str]) -> List[str]:
 
 
 ORIENT_COLUMNS = ["source_orient", "orient"]      # prep.csv and predict.csv, only with --prep_orient
+# prep.csv and predict.csv, only with --prep_denoise, directly before the place of BIAS_COLUMNS
+DENOISE_COLUMNS = ["denoise", "denoise_sigma", "denoise_samples", "denoise_rms"]
 # prep.csv and predict.csv, only with --prep_bias, directly before the place of ALIGN_COLUMNS
 BIAS_COLUMNS = ["bias", "bias_iters", "bias_cv", "bias_field"]
 # prep.csv and predict.csv, only with --prep_register, directly after ALIGN_COLUMNS
@@ -874,7 +892,8 @@ def _apply_window(ops, plan, x, window, mask: str) -> None:
 
 
 def _on_device(a, dev):
-    """A scan as a device tensor: a host array is uploaded, what --prep_bias left on the device is taken as it is."""
+    """A scan as a device tensor: a host array is uploaded, what --prep_denoise or --prep_bias left on the device is taken
+    as it is."""
     return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
@@ -934,14 +953,22 @@ def process_subject(ops, plan: _Plan, imgs: Dict[str, np.ndarray], seg: Optional
         raise PrepError(f"subject {sn}: the label holds an array of shape {tuple(seg.shape)}, not "
                         f"{plan.shapes[D.LABEL_MODALITY]}")
     dev = ops.device
-    plan.bias = {}
+    plan.denoise, plan.bias = {}, {}
+    if opts.denoise:      # --prep_denoise nlmM: every modality alone, on its own grid, before the bias field and all else
+        from . import denoise as N
+        imgs = dict(imgs)         # the filtered scans stay on the device: the steps below take them from there
+        for m in mods:
+            imgs[m], plan.denoise[m] = N.denoise(ops, sn, m, _on_device(np.asarray(imgs[m], dtype=np.float32), dev), mask,
+                                                 opts.denoise)
     if opts.bias:         # --prep_bias n4: every modality alone, on its own grid, before anything else sees it
         from . import bias as B
         imgs = dict(imgs)         # the corrected scans stay on the device: the steps below take them from there
         for m in mods:
-            imgs[m], plan.bias[m] = B.correct(ops, sn, m, _on_device(np.asarray(imgs[m], dtype=np.float32), dev), mask)
+            scan = imgs[m] if opts.denoise else np.asarray(imgs[m], dtype=np.float32)
+            imgs[m], plan.bias[m] = B.correct(ops, sn, m, _on_device(scan, dev), mask)
     if opts.align is None:
-        x = torch.stack([imgs[m] for m in mods]) if opts.bias else torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
+        x = torch.stack([imgs[m] for m in mods]) if opts.bias or opts.denoise else \
+            torch.from_numpy(np.stack([imgs[m] for m in mods])).to(dev)
         lab = torch.from_numpy(seg[None]).to(dev) if seg is not None else None
     else:
         x, lab = _aligned(ops, plan, imgs, seg, mods, mask)

@@ -1308,6 +1308,34 @@ int effq_prep_bias_fit(const float* u, const unsigned char* m, float* f, int D, 
 int effq_prep_bias_apply(const float* v, const unsigned char* m, int D, int H, int W, const double* Phi, float* y,
                          unsigned* range, void* stream);
 
+/* ---- non-local means denoising (csrc/prep_denoise.hip; denoise.py and prep.py --prep_denoise nlmM, where the rule is
+ * defined): one scan v (D, H, W) fp32 on its own grid.  Omega: the voxels that are finite and, with
+ * EFFQ_PREP_MASK_NONZERO, not exactly 0; with EFFQ_PREP_MASK_ALL every finite voxel.
+ * effq_prep_denoise_residual: for a voxel of Omega whose six face neighbours are inside the volume and in Omega,
+ *   r = |fp32((double)v - ((((((d-) + (d+)) + (h-)) + (h+)) + (w-)) + (w+)) / 6)|, the sum in fp64 in that order; every
+ *   other voxel gets r = +0.  The median of the non-zero r gives the noise level (effq_prep_quantiles).
+ * effq_prep_denoise_nlm: patch radius 1, search radius M = 1 ... 5, patch reads outside the volume clamped to the edge.
+ *   For i in Omega and every j = i + t, t != 0, |t|inf <= M, j inside the volume and in Omega:
+ *     d2 = (1 / 27) sum over o in {-1, 0, 1}^3 of (v[clamp(i + o)] - v[clamp(j + o)])^2,
+ *     w = exp(-max(d2 - 2 sigma2, 0) / (H2 sigma2)), H2 = 1, w = 0 for a d2 that is not finite,
+ *     wmax = max w, or 1 when no candidate has w > 0,  y_i = (sum w_j v_j + wmax v_i) / (sum w_j + wmax).
+ *   A voxel outside Omega is copied bit for bit.  change (device, two doubles) receives the sum over Omega of (y - v)^2
+ *   and |Omega|.  fp32 weights through exp2 while wmax >= 2^-16, else the voxel is done again in fp64, where a candidate
+ *   counts while fp64 exp gives w > 0.  A workgroup owns a tile of EFFQ_PREP_DENOISE_TILE_D x _H x _W outputs; per
+ *   workgroup fp64 partials in ws (effq_prep_denoise_ws_bytes, no initialisation needed) and one finishing workgroup in
+ *   block order; no floating-point atomic, the grid depends on the extents alone: equal inputs give equal bits.
+ * Refused with EFFQ_ERR_ARG before any launch: a null pointer, extents outside 1 ... 32767 or 2^31 voxels or more, a
+ * mask_mode that is neither, M outside 1 ... 5, a sigma2 that is not finite and positive or whose folded constant
+ * log2(e) / (27 sigma2) is not a finite fp32 number, v and y (v and r) overlapping, an fp32 pointer off 4 B, change or
+ * ws off 8 B; EFFQ_ERR_WORKSPACE for a workspace that is too small. */
+#define EFFQ_PREP_DENOISE_TILE_D 8
+#define EFFQ_PREP_DENOISE_TILE_H 8
+#define EFFQ_PREP_DENOISE_TILE_W 62
+int effq_prep_denoise_residual(const float* v, int D, int H, int W, int mask_mode, float* r, void* stream);
+int effq_prep_denoise_ws_bytes(int D, int H, int W, size_t* bytes);
+int effq_prep_denoise_nlm(const float* v, int D, int H, int W, int mask_mode, int M, double sigma2, float* y,
+                          double* change, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
