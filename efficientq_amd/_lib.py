@@ -255,6 +255,8 @@ SIGNATURES = {
     "effq_prep_denoise_residual": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "effq_prep_denoise_ws_bytes": (_I, [_I, _I, _I, _P]),
     "effq_prep_denoise_nlm": (_I, [_P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _SZ, _P]),
+    "effq_seg_crf_ws_bytes": (_I, [_I, _I, _I, _I, _P]),
+    "effq_seg_crf": (_I, [_P, _I, _P, _I, _I, _I, _I, _D, _D, _D, _I, _D, _D, _D, _D, _D, _I, _F, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -313,6 +315,12 @@ PREP_BIAS_BINS, PREP_BIAS_LEVELS, PREP_BIAS_LATTICE = 200, 4, 1863
 # the search radii it takes
 PREP_DENOISE_TILE = (8, 8, 62)
 PREP_DENOISE_MAX_RADIUS = 5
+# include/effq_hip.h (EFFQ_SEG_CRF_TILE_D, _H, _W, EFFQ_SEG_CRF_MAX_*): the output tile of one workgroup of effq_seg_crf, the
+# largest radius of an axis, the most classes, modalities and iterations, the largest w_a + w_s, and the range of a width
+SEG_CRF_TILE = (16, 8, 16)
+SEG_CRF_MAX_RADIUS = 3
+SEG_CRF_MAX_CLASSES, SEG_CRF_MAX_MODALITIES, SEG_CRF_MAX_ITERS, SEG_CRF_MAX_WEIGHT = 8, 4, 20, 64
+SEG_CRF_THETA_RANGE = (1e-18, 1e18)
 
 _lib = None
 

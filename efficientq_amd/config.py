@@ -164,6 +164,18 @@ def build_parser():
     p.add_argument('--save_unc', action='store_true',
                    help='predict: also write <out_dir>/unc/<subject>.nii.gz, one uncertainty per voxel of the scan\'s grid '
                         '(entropy as a share of its maximum): uint8, scl_slope 1/255')
+    # the local conditional random field of predict (crf.py, where the values are checked after the YAML has been merged
+    # in); refused by name in the other missions (crf.crf_switches)
+    p.add_argument('--crf', action='store_true',
+                   help='predict: refine the stitched logits by mean-field iterations of a local conditional random field '
+                        'whose pair weights come from the standardised scans, before the map is decided (the defaults '
+                        'are not tuned on data: measure with the score mission)')
+    p.add_argument('--crf_w', default=None, metavar='WA,WS',
+                   help='with --crf: the appearance and smoothness weights in logit units, >= 0, WA + WS <= 64 (4,1)')
+    p.add_argument('--crf_theta', default=None, metavar='P,I,S',
+                   help='with --crf: the widths of the appearance kernel in mm and in standard deviations of the '
+                        'standardised scans, and of the smoothness kernel in mm, each > 0 and within 1e-18 ... 1e18 (3,0.5,1)')
+    p.add_argument('--crf_iters', default=None, metavar='T', help='with --crf: the iterations, 1 ... 20 (5)')
     # the score mission (score.py): finished label maps against the labels of --src_list, on the scan's grid; the values
     # are checked by score_switches, after the YAML has been merged in
     p.add_argument('--pred_dir', default=None, help='score: the folder of the maps <subject>.nii.gz (or .nii) to score')
@@ -375,6 +387,8 @@ def score_switches(args, mission=None):
                 raise SystemExit(f'--{switch} belongs to the score mission, which scores finished maps against labels: '
                                  f'the {mission} mission scores nothing with it, drop --{switch}')
         return None
+    from . import crf
+    crf.crf_switches(args, 'score')
     for switch, unset in SCORE_FOREIGN + SCORE_FOREIGN_ALIGN:
         got = getattr(args, switch, unset)
         if got is not None and got != unset and got != []:

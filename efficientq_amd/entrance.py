@@ -77,6 +77,7 @@ import torch
 
 from . import calibrate as K
 from . import config as Cf
+from . import crf
 from . import data as D
 from . import evaluate as E
 from . import reports as R
@@ -220,6 +221,7 @@ def _switches(args):
     match = Cf.match_switches(args)
     Cf.score_switches(args, 'ptq')
     Cf.measure_switches(args, 'ptq')
+    crf.crf_switches(args, 'ptq')
     if getattr(args, 'prep_register', None) is not None:
         raise SystemExit('--prep_register registers source scans in the prep and predict missions: the ptq mission reads '
                          'prepared data (--data_dir) as it is, drop --prep_register')
@@ -279,6 +281,7 @@ def main(argv=None):
         Cf.match_switches(args)
         Cf.score_switches(args)
         Cf.measure_switches(args)
+        crf.crf_switches(args)
         from . import prep
         prep.run(args)
         return
@@ -286,6 +289,7 @@ def main(argv=None):
         Cf.thr_switches(args)
         Cf.match_switches(args)
         Cf.score_switches(args)
+        crf.crf_switches(args)
         from . import predict
         predict.run(args)
         return

@@ -79,6 +79,15 @@ after all others, and ``labels``, ``voxels`` and ``volume_ml`` are the cleaned m
 at that threshold instead of sigmoid >= 0.5.  ``predict.csv`` then gains the column ``thresh`` (the fp32 logit, ``%.9g``)
 after the blend columns and before the post columns; ``0.5`` and ``logit:0`` are the default and change nothing.
 
+``--crf`` (``--crf_w WA,WS``, ``--crf_theta P,I,S``, ``--crf_iters T``; crf.py, where the rule stands) refines the stitched
+logits by mean-field iterations of a local conditional random field whose pair weights come from the standardised working
+arrays, on the working grid at the plan's spacing (effq_seg_crf, one call per subject).  The refined logits stand in for
+the network's in everything after: the label map, hence ``--thresh``, ``--post`` and ``--lesion_measures``, and the files
+of ``--save_prob`` and ``--save_unc``.  ``predict.csv`` then gains the columns ``crf`` (``w_a w_s theta_p theta_i theta_s
+T``) and ``crf_changed`` (the voxels of the working grid whose decision the field changed) after the ``thresh`` column's
+place and before the post columns, and the subject's line says ``crf N voxels changed (r R_D R_H R_W)``.  The defaults are
+not tuned on data; without ``--crf`` nothing changes.
+
 ``--save_prob`` also writes ``<out_dir>/prob/<subject>.nii.gz``, uint8 ``(SD, SH, SW, C)`` on the scan's grid with the
 scan's header and ``scl_slope`` 1/255: the softmax over the C classes (class-id mode) or the sigmoid of every raw channel
 (``--multi_label``; ``--merge_type`` and ``--thresh`` do not enter) of the logits interpolated exactly as for the label
@@ -109,6 +118,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import crf as Crf
 from . import data as D
 from . import evaluate as E
 from . import lesion_measures as LM
@@ -165,6 +175,7 @@ def _network(args, dev):
 CSV_WINDOW_COLUMNS = ["window_bounds"]            # after the interp column's place, only with --prep_window pLO,pHI
 CSV_BLEND_COLUMNS = ["blend", "tta_mirror"]       # after CSV_HEADER, only when --blend / --tta_mirror is given
 CSV_THRESH_COLUMNS = ["thresh"]                   # after those, only when --thresh is given (and is not the default)
+CSV_CRF_COLUMNS = Crf.CSV_COLUMNS                  # after those, only when --crf is given
 CSV_POST_COLUMNS = ["post", "post_changed"]       # after those, only when --post is given
 
 
@@ -225,8 +236,11 @@ def _resolve(args, need_network: bool) -> SimpleNamespace:
     _, thresh = Cf.thr_switches(args, 'predict')
     save_prob, save_unc = Cf.prob_switches(args, 'predict')
     measures = Cf.measure_switches(args, 'predict')
+    crf = Crf.crf_switches(args, 'predict')
     mods = D.MODALITIES[task]
     plans = [opts.plan(dict(e, seg=None), mods) for e in prep.read_src_list(args.src_list, task)]
+    for plan in plans if crf is not None else ():       # a grid with no linked axis, from the headers
+        Crf.linked_radii(plan.subject, plan.grid_spacing, crf)
     measure = None
     if measures:        # the classes, and per subject the slice axis; the limits of the device call are refused here
         classes = measures[0] or Cf.SCORE_CLASSES[task]
@@ -248,12 +262,14 @@ def _resolve(args, need_network: bool) -> SimpleNamespace:
         used.update(blend=blend, tta_mirror=getattr(args, "tta_mirror", None) or "none")
     if thresh is not None:
         used.update(thresh="%.9g" % thresh)
+    if crf is not None:
+        used.update(crf=Crf.column_text(crf))
     post_said = Cf.post_text(post, post_conn) if post else None
     if post:
         used.update(post=post_said)
     return SimpleNamespace(mods=mods, opts=opts, patch=patch, overlap=tuple(min(D.OVERLAP_DEFAULT, p // 2) for p in patch),
                            rule=rule, fuse=fuse, blend=blend, flips=flips, sliding=sliding, post=post, post_conn=post_conn,
-                           post_said=post_said, thresh=thresh, save_prob=save_prob, save_unc=save_unc, measure=measure,
+                           post_said=post_said, thresh=thresh, save_prob=save_prob, save_unc=save_unc, measure=measure, crf=crf,
                            prob_mode="argmax" if rule == "argmax" else "sigmoid", used=used, plans=plans)
 
 
@@ -275,7 +291,16 @@ def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write, measures=Non
     vol = torch.from_numpy(y)[None].to(ops.device)
     outs, nwin, bsz = E.stitched_window_logits(ops, [model], vol, job.patch, job.overlap, bsz, job.blend, job.flips)
     where = (pmin, plan.grid_shape, plan.factors, plan.oriented_shape)
-    labels = _on_scan_grid(ops, plan, ops.seg_labels_source(outs[0][0], *where, job.rule, job.fuse))
+    logits, crf_done = outs[0][0], None
+    if job.crf is not None:     # on the working grid, from the arrays the windows were cut from; H stands in for the logits
+        try:
+            logits, n, radii = Crf.refine(ops, sn, logits, vol[0], plan.grid_spacing,
+                                          "softmax" if job.rule == "argmax" else "sigmoid", job.crf,
+                                          ops.sigmoid_threshold())
+        except _lib.EffqError as e:
+            raise PrepError(f"subject {sn}: --crf: {e}")
+        crf_done = (n, radii)
+    labels = _on_scan_grid(ops, plan, ops.seg_labels_source(logits, *where, job.rule, job.fuse))
     changed = None
     if job.post:        # on the source grid, in place: the counts, the copy and the file are the cleaned map's
         labels, stats = ops.label_clean(labels, job.post, job.post_conn, out=labels)
@@ -293,7 +318,7 @@ def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write, measures=Non
     write(P.join(out_dir, f"{sn}.nii.gz"), labels.cpu().numpy(), plan.header)
     extra = ""
     if job.save_prob or job.save_unc:       # from the same stitched logits, on the same grid; --post does not enter
-        probs, unc = ops.seg_probs_source(outs[0][0], *where, job.prob_mode, job.save_prob, job.save_unc)
+        probs, unc = ops.seg_probs_source(logits, *where, job.prob_mode, job.save_prob, job.save_unc)
         probs, unc = _on_scan_grid(ops, plan, probs), _on_scan_grid(ops, plan, unc)
         if job.save_prob:       # (C, SD, SH, SW) -> the view (SD, SH, SW, C): a 4-D image, pixdim[4] = 1
             geo = dict(plan.header, pixdim=tuple(plan.header["pixdim"][:4]) + (1.0,) + tuple(plan.header["pixdim"][5:]))
@@ -303,7 +328,7 @@ def _segment(ops, model, job, plan, imgs, out_dir: str, bsz, write, measures=Non
             write(P.join(out_dir, UNC_DIR, f"{sn}.nii.gz"), unc.cpu().numpy(), plan.header, PROB_SCALE)
             extra += f", {UNC_DIR}/{sn}.nii.gz"
     return SimpleNamespace(box_of=tuple(y.shape[1:]), pmin=pmin, pmax=pmax, windows=nwin, counts=counts,
-                           changed=changed, extra=extra, lesions=lesions), bsz
+                           changed=changed, extra=extra, lesions=lesions, crf=crf_done), bsz
 
 
 def _row(job, plan, done) -> dict:
@@ -319,6 +344,8 @@ def _row(job, plan, done) -> dict:
     row.update(job.opts.row_values(plan))
     if plan.window_bounds is not None:
         row["window_bounds"] = ";".join(prep._fmt(b) for b in plan.window_bounds)
+    if job.crf is not None:
+        row["crf_changed"] = str(done.crf[0])
     if job.post:
         row["post_changed"] = done.changed
     return row
@@ -349,6 +376,8 @@ def run(args, ops=None, model=None, window_batch=None, measures=None) -> List[di
         print(f"[predict] --thresh {args.thresh}: every channel is decided at logit >= {job.thresh:.9g} (sigmoid >= "
               f"{E.logit_prob(job.thresh):.6g})")
         ops.set_decision_threshold(job.thresh)
+    if job.crf is not None:
+        print(f"[predict] {Crf.said(job.crf)}")
     if job.save_prob or job.save_unc:
         nc = getattr(args, "nClass", None)
         what = " and ".join(w for w, on in ((f"{PROB_DIR}/<subject>.nii.gz (SD, SH, SW, C)", job.save_prob),
@@ -375,7 +404,8 @@ def run(args, ops=None, model=None, window_batch=None, measures=None) -> List[di
             for plan, imgs, _ in subjects:
                 done, bsz = _segment(ops, model, job, plan, imgs, out_dir, bsz, write, measures)
                 rows.append(_row(job, plan, done))
-                cleaned = f", post {job.post_said}: {done.changed} voxels relabelled" if job.post else ""
+                cleaned = f", crf {done.crf[0]} voxels changed (r {prep._fmt(done.crf[1])})" if job.crf is not None else ""
+                cleaned += f", post {job.post_said}: {done.changed} voxels relabelled" if job.post else ""
                 if job.measure:
                     lesions += done.lesions
                     cleaned += ", lesions " + ", ".join(
@@ -392,7 +422,8 @@ def run(args, ops=None, model=None, window_batch=None, measures=None) -> List[di
     _write_csv(P.join(out_dir, PREDICT_CSV), rows,
                CSV_HEADER + job.opts.columns() + (CSV_WINDOW_COLUMNS if pct else []) +
                (CSV_BLEND_COLUMNS if job.sliding else []) +
-               (CSV_THRESH_COLUMNS if job.thresh is not None else []) + (CSV_POST_COLUMNS if job.post else []))
+               (CSV_THRESH_COLUMNS if job.thresh is not None else []) + (CSV_CRF_COLUMNS if job.crf is not None else []) +
+               (CSV_POST_COLUMNS if job.post else []))
     if job.measure:
         LM.write_csv(P.join(out_dir, LM.LESIONS_CSV), [k for k in LM.LESION_COLUMNS if k != "overlap"], lesions)
         print(f"[predict] {len(lesions)} lesions measured: {P.join(out_dir, LM.LESIONS_CSV)}")

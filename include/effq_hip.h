@@ -1336,6 +1336,44 @@ int effq_prep_denoise_ws_bytes(int D, int H, int W, size_t* bytes);
 int effq_prep_denoise_nlm(const float* v, int D, int H, int W, int mask_mode, int M, double sigma2, float* y,
                           double* change, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the local conditional random field of predict --crf (csrc/seg_crf.hip; crf.py, where the rule is defined): the
+ * stitched logits v (C, D, H, W) fp32 of one subject refined by `iters` mean-field iterations whose pair weights come
+ * from the standardised images x (M, D, H, W) fp32 of the same working grid with spacing (s_d, s_h, s_w) mm.
+ *   Neighbourhood: the offsets t != 0 with |t_a| <= r_a = min(EFFQ_SEG_CRF_MAX_RADIUS, floor(2 max(theta_p, theta_s) /
+ *   s_a)); neighbours outside the volume contribute nothing.  With d2 = sum_a (s_a t_a)^2:
+ *     g_p(t) = exp(-d2 / 2 theta_p^2) / Z_p,  g_s(t) = exp(-d2 / 2 theta_s^2) / Z_s,  Z the sum over the neighbourhood,
+ *     k(i, j) = w_a g_p(t) exp(-sum_m (x_m(i) - x_m(j))^2 / 2 theta_i^2) + w_s g_s(t).
+ *   EFFQ_SEG_ARGMAX:   H0 = v,  H'_i(c) = v_i(c) + sum_j k(i, j) softmax_c(H_j)(c)          (C >= 2)
+ *   EFFQ_SEG_SIGMOID:  H0 = v,  H'_i(c) = v_i(c) + sum_j k(i, j) (2 sigmoid(H_j(c)) - 1)    per channel
+ *   A voxel whose C logits and M intensities are not all finite sends no message and keeps H = v bit for bit.
+ *   out (C, D, H, W) receives H after `iters` iterations; changed (device, one unsigned) the number of voxels whose
+ *   decision differs between v and out: the first largest channel, or any channel's side of `thresh_logit` (v >= thresh).
+ * One launch per iteration, ping-pong between two (C, D, H, W) buffers of ws (effq_seg_crf_ws_bytes; no initialisation
+ * needed); a workgroup owns EFFQ_SEG_CRF_TILE_D x _H x _W outputs and marches along D over a ring of planes in LDS.  No
+ * floating-point atomic: equal inputs give equal bits.
+ * Refused with EFFQ_ERR_ARG before any launch: a null pointer, a mode that is neither, C outside 1 ... 8 (ARGMAX: 2 ... 8),
+ * M outside 1 ... 4, an extent below 1, max(C, M) D H W above 2^31 - 1, a spacing that is not finite and positive,
+ * a theta outside EFFQ_SEG_CRF_THETA_MIN ... EFFQ_SEG_CRF_THETA_MAX (inside it every folded constant is a normal number,
+ * and Z is taken relative to the nearest neighbour, so no width vanishes against the spacing), w_a or w_s negative or not
+ * finite, w_a + w_s above EFFQ_SEG_CRF_MAX_WEIGHT, iters outside 1 ... EFFQ_SEG_CRF_MAX_ITERS, a thresh_logit that is not
+ * finite, all three radii 0, out, changed or ws overlapping an input or each other, a pointer off 4 B;
+ * EFFQ_ERR_WORKSPACE for a workspace that is too small.  effq_seg_crf_ws_bytes knows C alone: it answers for every shape
+ * with C D H W <= 2^31 - 1, and the call still refuses such a shape when M > C and M D H W is above that. */
+#define EFFQ_SEG_CRF_TILE_D 16
+#define EFFQ_SEG_CRF_TILE_H 8
+#define EFFQ_SEG_CRF_TILE_W 16
+#define EFFQ_SEG_CRF_MAX_RADIUS 3
+#define EFFQ_SEG_CRF_MAX_CLASSES 8
+#define EFFQ_SEG_CRF_MAX_MODALITIES 4
+#define EFFQ_SEG_CRF_MAX_ITERS 20
+#define EFFQ_SEG_CRF_MAX_WEIGHT 64
+#define EFFQ_SEG_CRF_THETA_MIN 1e-18
+#define EFFQ_SEG_CRF_THETA_MAX 1e18
+int effq_seg_crf_ws_bytes(int C, int D, int H, int W, size_t* need);
+int effq_seg_crf(const float* logits, int C, const float* images, int M, int D, int H, int W, double s_d, double s_h,
+                 double s_w, int mode, double w_a, double w_s, double theta_p, double theta_i, double theta_s, int iters,
+                 float thresh_logit, float* out, unsigned* changed, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
