@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libeffq_hip.so")
 
 EFFQ_OK = 0
 _ERR_NAMES = {1: "EFFQ_ERR_ARG", 2: "EFFQ_ERR_HIP", 3: "EFFQ_ERR_WORKSPACE", 4: "EFFQ_ERR_NO_DEVICE",
-              5: "EFFQ_ERR_NOT_CONVERGED"}
+              5: "EFFQ_ERR_NOT_CONVERGED", 6: "EFFQ_ERR_NOT_SPD"}
 
 
 class EffqError(RuntimeError):
@@ -257,6 +257,12 @@ SIGNATURES = {
     "effq_prep_denoise_nlm": (_I, [_P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _SZ, _P]),
     "effq_seg_crf_ws_bytes": (_I, [_I, _I, _I, _I, _P]),
     "effq_seg_crf": (_I, [_P, _I, _P, _I, _I, _I, _I, _D, _D, _D, _I, _D, _D, _D, _D, _D, _I, _F, _P, _P, _P, _SZ, _P]),
+    "effq_gptq_factor_bytes": (_SZ, [_I]),
+    "effq_gptq_chol_ws_bytes": (_SZ, [_I]),
+    "effq_gptq_ws_bytes": (_SZ, [_I, _I]),
+    "effq_gptq_plan_query": (_I, [_I, _I, _IP, _IP, _IP, _IP, _IP, _IP]),
+    "effq_gptq_chol": (_I, [_P, _D, _I, _P, _SZ, _P, _SZ, _I, _P]),
+    "effq_gptq_sweep": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges
@@ -321,6 +327,8 @@ SEG_CRF_TILE = (16, 8, 16)
 SEG_CRF_MAX_RADIUS = 3
 SEG_CRF_MAX_CLASSES, SEG_CRF_MAX_MODALITIES, SEG_CRF_MAX_ITERS, SEG_CRF_MAX_WEIGHT = 8, 4, 20, 64
 SEG_CRF_THETA_RANGE = (1e-18, 1e18)
+# include/effq_hip.h: the error effq_gptq_chol returns for a matrix that is not positive definite
+EFFQ_ERR_NOT_SPD = 6
 
 _lib = None
 

@@ -13,10 +13,11 @@ import re
 import torch.nn as nn
 import yaml
 
+from .gptq import GPTQConvHIP
 from .qconv import EfficientQConvHIP
 from .unet import UResQ
 
-QCONV_REGISTRY = {'conv': nn.Conv3d, 'effq': EfficientQConvHIP, 'effq_hip': EfficientQConvHIP}
+QCONV_REGISTRY = {'conv': nn.Conv3d, 'effq': EfficientQConvHIP, 'effq_hip': EfficientQConvHIP, 'gptq': GPTQConvHIP}
 
 
 def merge_config(cfg: str, args: argparse.Namespace):

@@ -1,0 +1,163 @@
+"""One-pass layer calibration by sequential rounding with error feedback (OBQ / GPTQ, Babai's nearest plane):
+``--qconv gptq``, the cheap companion of the 200-iteration ADMM calibrator of qconv.py.
+
+The rule, per layer with n = k^3 c1 (+ 1) unknowns per output row, weights in the reference's layout, the bias last:
+
+1. H = A0 + eta I, eta = lwq_eta * rho_scale: the Hessian of  ||Y - [W|b] X||^2_att + eta ||[W|b] - [W0|b0]||^2.
+   Its minimiser is u* = (B0 + eta [W0|b0]) H^-1 (effq_spd_inverse and effq_prox_solve at rho = 0).
+2. The weight scale is project_by_iter on the weight part of u* (per tensor, or per row with lwq_channel_wise) and stays fixed.
+3. H = P P^T with P upper triangular: the Cholesky factor of the index-reversed matrix, fp64.
+4. Per output row, with s = 0, for j = 0 .. n-1:
+       t_j = u*_j - s_j / P_jj
+       q_j = alpha * disc64(t_j, alpha, -1, 1, 2 / (L - 1))   for a weight,   q_j = t_j   for the bias
+       s_k += (q_j - u*_j) P_jk  for k > j,     err += (P_jj (q_j - t_j))^2
+   t_j minimises the quadratic form over column j with the earlier columns at their rounded values and the later ones
+   free; err ends as (q - u*) H (q - u*)^T.  Only P is needed, not the factor of H^-1.
+5. The rounded weights, the bias and the scale go through the calibrator's own final forward and commit.
+
+``factor_host`` / ``sweep_host`` state 3 and 4 in numpy the way the kernels of csrc/gptq.hip walk them - reversed indices,
+64-column blocks, the later columns' s updated once per block - for the tests and for reading; ``GPTQConvHIP`` is the layer.
+"""
+from __future__ import annotations
+
+import time
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import ops_gptq
+from .qconv import (GRAM_LOSS_DEFAULT, GRAM_LOSS_I8_MAX_N, GRAM_LOSS_MAX_N, EfficientQConvHIP, _call_if, layer_paths)
+
+
+def disc64(t, alpha, levels: int):
+    """(value, level id) of t on the grid alpha * (2 i / (L - 1) - 1): layer_helper.py:25-37 in fp64."""
+    d = 2.0 / (levels - 1)
+    idx = np.rint((np.clip(t / alpha, -1.0, 1.0) + 1.0) / d)
+    return idx * d - 1.0, idx
+
+
+def factor_host(H: np.ndarray) -> np.ndarray:
+    """P upper triangular with H = P P^T."""
+    return np.linalg.cholesky(H[::-1, ::-1])[::-1, ::-1]
+
+
+def sweep_host(P: np.ndarray, u: np.ndarray, alpha, levels: int, has_bias: bool, block: int = ops_gptq.BLOCK):
+    """(q, ids, err) of the rule for u (c2, n) and alpha (a scalar or c2 scales), walked as the device walks it."""
+    c2, n = u.shape
+    npad = -(-n // block) * block
+    L = np.eye(npad)
+    L[:n, :n] = P[::-1, ::-1]
+    ur = np.zeros((c2, npad))
+    ur[:, :n] = u[:, ::-1]
+    a = np.broadcast_to(np.asarray(alpha, dtype=np.float64).reshape(-1), (c2,))
+    S, q, ids, err = np.zeros((c2, npad)), np.zeros((c2, npad)), np.zeros((c2, npad)), np.zeros(c2)
+    for B in range(npad // block - 1, -1, -1):
+        kb = B * block
+        delta = np.zeros((c2, block))
+        for jj in range(min(block, n - kb) - 1, -1, -1):
+            j = kb + jj
+            t = ur[:, j] - S[:, j] / L[j, j]
+            if has_bias and j == 0:
+                qj = t
+            else:
+                v, ids[:, j] = disc64(t, a, levels)
+                qj = a * v
+            err += (L[j, j] * (qj - t)) ** 2
+            delta[:, jj] = qj - ur[:, j]
+            S[:, kb:j] += np.outer(delta[:, jj], L[j, kb:j])
+            q[:, j] = qj
+        S[:, :kb] += delta @ L[kb:kb + block, :kb]
+    return q[:, :n][:, ::-1], ids[:, :n][:, ::-1], err
+
+
+class GPTQConvHIP(EfficientQConvHIP):
+    """The layer of ``--qconv gptq``: the statistics, input quantisation, Gram system, final forward and commit of
+    EfficientQConvHIP around the rule above instead of the ADMM run.  One host synchronisation per layer.  ``alpha_w`` is the
+    one fitted scale (per tensor or per row): the committed weights lie exactly on its grid."""
+
+    def ptq(self, x):
+        c = self._layer_inputs(x)
+        ops, red = c.ops, c.red
+        rho_scale, y_dim, att, sx, syy_local = self._statistics(c)
+        # (no per-iteration losses: the unweighted Gram system behind them is not formed)
+        paths = layer_paths(ops, c.geom, self.qlvl_act, self.qlvl_w, c.has_b, c.c2, c.n_sys, c.voxels, q_act=self.q_act,
+                            act_inited=self._act_inited, exact_int=self.lwq_exact_int, channel_wise=self.channel_wise,
+                            gram_loss_enabled=GRAM_LOSS_DEFAULT, gram_loss_max_n=GRAM_LOSS_MAX_N,
+                            gram_loss_i8_max_n=GRAM_LOSS_I8_MAX_N)._replace(losses=None)
+        att_cls = ops.att_classes(att) if paths.gram_i8 else None
+        paths = paths.after(att_classes_ok=att_cls is not None)
+        xq, xidx, act_iters = self._quantise_input(c, sx, paths.want_idx)
+        eta = self.lwq_eta * rho_scale
+        A0, B0, _, paths = self._gram_system(c, paths, xq, xidx, att, att_cls, syy_local)
+        t0 = time.perf_counter()
+        fit = self._gptq_run(c, A0, B0, eta)
+        fin = self._final_forward(c, paths, fit.run, fit.best, fit.G, fit.b, xq, xidx, att)
+        red(fin)
+        info = self._gptq_read(fit, fin)                                    # ONE host sync for the layer
+        t_fit = time.perf_counter() - t0
+        _call_if(ops, "release_retired")
+        self._commit(c, fit.G, fit.b, info["alpha_w"])
+        numel = y_dim * 1.0
+        lossf = (info["fin"][1] if att is not None else info["fin"][0]) / numel
+        if self.lwq_verbose:
+            print(f'GPTQ {self.name}: n = {c.n_sys}, eta = {eta:.4f}, scale fit {info["w_iters"]} iterations, '
+                  f'err = {info["gptq_err"]:.6g}, loss = {lossf:.7f}.')
+        if self.layer_loss is not None:
+            self.layer_loss.append(f'{self.name:45s}:{lossf}')
+        self.last_trace = dict(method='gptq', rho_scale=rho_scale, gptq_err=info["gptq_err"],
+                               final_mse=info["fin"][0] / numel, layer_loss=lossf, act_iters=act_iters,
+                               w_iters=info["w_iters"], alpha_w=info["alpha_w"], loss_history=[],
+                               exact_gram=paths.gram_i8, gptq_s=t_fit, channel_wise=self.channel_wise,
+                               paths=paths._asdict())
+
+    def _gptq_run(self, c, A0, B0, eta):
+        """Steps 1 - 4, enqueued on the current stream; nothing is read back."""
+        ops, dev, c2, L = c.ops, c.dev, c.c2, self.qlvl_w
+        nw = c.n_sys - int(c.has_b)
+        Ainv = ops.spd_inverse(A0, c.has_b, 0.0, eta)
+        zero = torch.zeros(c2 * nw, dtype=torch.float32, device=dev)      # G - dual of the prox right-hand side
+        u_w = torch.empty(c2, nw, dtype=torch.float32, device=dev)
+        u_b = torch.empty(c2, dtype=torch.float32, device=dev) if c.has_b else None
+        ops.prox_solve(B0, Ainv, c.W0, c.b0, zero, zero, 0.0, eta, u_w, u_b)
+        fp_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.channel_wise:
+            alpha = torch.empty(c2, dtype=torch.float64, device=dev)
+            iters = torch.zeros(c2, dtype=torch.int32, device=dev)
+            ops.fixed_point_channels(u_w, None, None, L, alpha, iters, fp_err)
+            state = None
+        else:
+            state = ops.new_fp_state()
+            ops.fixed_point_bucket(u_w, None, None, L, state)
+            ops.fp_check(state, fp_err)
+            alpha, iters = state[:1], state[4:5].view(torch.int32)[:1]
+        P = ops_gptq.gptq_chol(ops, A0, eta)
+        G, b, _, err, row_flag = ops_gptq.gptq_sweep(ops, P, c.n_sys, u_w, u_b, alpha, L, per_row=self.channel_wise)
+        # what _final_forward reads of an ADMM run: the scale state of the chosen iterate (the i8 forward folds it in)
+        run = SimpleNamespace(state_ring=state.reshape(1, 5)) if state is not None else None
+        best = torch.zeros(2, dtype=torch.float64, device=dev)
+        return SimpleNamespace(G=G.reshape(-1), b=b, err=err, alpha=alpha, iters=iters, fp_err=fp_err, row_flag=row_flag,
+                               pd_flag=ops_gptq.gptq_flag(P, c.n_sys), run=run, best=best, keep=(P, u_w, u_b, Ainv, zero))
+
+    def _gptq_read(self, fit, fin):
+        """The layer's one device->host copy; raises naming the layer on what the device flagged."""
+        c2 = fit.err.numel()
+        f64 = torch.float64
+        pack = torch.cat([fin.to(f64).reshape(-1), fit.err, fit.alpha.reshape(-1), fit.iters.to(f64), fit.fp_err.to(f64),
+                          fit.pd_flag.to(f64), fit.row_flag.to(f64)]).cpu().tolist()
+        na, ni = fit.alpha.numel(), fit.iters.numel()
+        o = 2 + c2
+        alpha, iters = pack[o:o + na], pack[o + na:o + na + ni]
+        fp_err, pd_flag = (int(v) for v in pack[o + na + ni:o + na + ni + 2])
+        rows = [r for r, v in enumerate(pack[o + na + ni + 2:]) if v]
+        if pd_flag:
+            raise RuntimeError(f'{self.name}: the Gram system A0 + eta I is not positive definite (a pivot of its fp64 '
+                               f'Cholesky factorisation was <= 0 or not finite)')
+        if fp_err == 2:                                                     # layer_helper.py:62-64
+            raise RuntimeWarning(f'{self.name}: Exceed maximum iteration ({100 * self.qlvl_w}) for alpha optimization')
+        if fp_err:
+            raise RuntimeError(f'{self.name}: weight-scale fixed point did not finish (device state {fp_err})')
+        if rows:
+            raise RuntimeError(f'{self.name}: the weight scale of output channel(s) {rows[:8]} is not finite and positive')
+        return dict(fin=pack[:2], gptq_err=float(sum(pack[2:o])), alpha_w=alpha if self.channel_wise else alpha[0],
+                    w_iters=[int(max(iters))])

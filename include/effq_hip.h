@@ -32,7 +32,8 @@ enum {
   EFFQ_ERR_HIP = 2,        /* a HIP runtime call failed; see effq_last_error() */
   EFFQ_ERR_WORKSPACE = 3,  /* workspace too small; query the *_ws_bytes function */
   EFFQ_ERR_NO_DEVICE = 4,
-  EFFQ_ERR_NOT_CONVERGED = 5
+  EFFQ_ERR_NOT_CONVERGED = 5,
+  EFFQ_ERR_NOT_SPD = 6     /* effq_gptq_chol: a pivot of the factorisation was <= 0 or not finite */
 };
 
 /* Conv geometry.  Dilation and groups are 1 (the reference's solver ignores
@@ -1373,6 +1374,43 @@ int effq_seg_crf_ws_bytes(int C, int D, int H, int W, size_t* need);
 int effq_seg_crf(const float* logits, int C, const float* images, int M, int D, int H, int W, double s_d, double s_h,
                  double s_w, int mode, double w_a, double w_s, double theta_p, double theta_i, double theta_s, int iters,
                  float thresh_logit, float* out, unsigned* changed, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- One-pass sequential rounding with error feedback (OBQ / GPTQ; the rule: efficientq_amd/gptq.py, kernels: gptq.hip) ----
+ * effq_gptq_chol factors H = A0 + eta I (A0: n x n fp32 as effq_gram_finish leaves it, its upper triangle is read) as
+ * H = P P^T, P upper triangular, in fp64: a blocked right-looking Cholesky factorisation of the index-reversed matrix on
+ * v_mfma_f64_16x16x4_f64.  P is kept in the layout the sweep walks: with npad = n rounded up to 64, npad x npad doubles
+ * row-major holding L with P[i][j] = L[n-1-i][n-1-j] (lower triangular, identity on the padding, zeros above the
+ * diagonal), then 32 doubles of header whose first 32-bit word is the flag; effq_gptq_factor_bytes(n) in all.  A pivot that
+ * is <= 0 or not finite sets the flag: every later workgroup and launch of the call, and every launch of a sweep on that
+ * factor, reads it and does nothing.  read_flag != 0: the call copies the flag back, synchronises the stream once and
+ * returns EFFQ_ERR_NOT_SPD when it is set; read_flag == 0: nothing is read, the caller reads the flag word with its own copy.
+ * ws: effq_gptq_chol_ws_bytes(n), no initialisation needed.  1 + 3 ceil(n / 64) - 2 launches.
+ * effq_gptq_sweep rounds the columns j = 0 .. n-1 of every output row r one after the other, with s = 0:
+ *   t_j = u_j - s_j / P_jj;  q_j = alpha_r * disc64(t_j, alpha_r, -1, 1, 2 / (levels - 1)) for a weight, q_j = t_j for the
+ *   bias (the last column, has_bias != 0);  s_k += (q_j - u_j) P_jk for k > j;  err_r += (P_jj (q_j - t_j))^2,
+ * which leaves err_r = (q - u) H (q - u)^T.  u: the continuous optimum as effq_prox_solve splits it, u_w [c2][n - has_bias]
+ * and u_b [c2] (NULL without a bias), fp32; alpha: 1 (per_row == 0) or c2 device doubles.  Outputs: G [c2][n - has_bias] =
+ * f32(alpha_r) * f32(level value), b [c2] (NULL without a bias), ids (uint8 level ids like G, may be NULL), err [c2]
+ * doubles, row_flag [c2] = 1 for a row whose scale is not finite and positive (nothing else of that row is written), else
+ * 0.  Per 64-column block one kernel of one wave per row (the block of P in LDS, delta_j broadcast across the lanes) and
+ * one matrix-core update of the later columns' s, enqueued back to back: 2 ceil(n / 64) launches, no host read.
+ * ws: effq_gptq_ws_bytes(c2, n), no initialisation needed.
+ * Refused with EFFQ_ERR_ARG before any launch, outputs untouched: a null pointer (but ids; u_b and b without a bias),
+ * n < 1 or above 32768, c2 < 1, levels outside 2 .. 256, eta that is not finite and positive, a factor buffer shorter
+ * than effq_gptq_factor_bytes(n); EFFQ_ERR_WORKSPACE for a short workspace.
+ * effq_gptq_plan_query launches nothing: *nblk 64-blocks, the launches of the two calls, *chol_tiles tiles in the first
+ * trailing update of the factorisation, *block_grid workgroups of the in-block kernel, *trail_gy row groups of the sweep's
+ * matrix-core update. */
+size_t effq_gptq_factor_bytes(int n);
+size_t effq_gptq_chol_ws_bytes(int n);
+size_t effq_gptq_ws_bytes(int c2, int n);
+int effq_gptq_plan_query(int c2, int n, int* nblk, int* chol_launches, int* chol_tiles, int* sweep_launches,
+                         int* block_grid, int* trail_gy);
+int effq_gptq_chol(const float* A0, double eta, int n, double* P, size_t p_bytes, void* ws, size_t ws_bytes,
+                   int read_flag, void* stream);
+int effq_gptq_sweep(const double* P, int n, const float* u_w, const float* u_b, int c2, int has_bias, const double* alpha,
+                    int per_row, int levels, float* G, float* b, uint8_t* ids, double* err, int32_t* row_flag, void* ws,
+                    size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

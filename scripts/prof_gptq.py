@@ -1,0 +1,110 @@
+"""--qconv gptq beside --qconv effq: seconds per calibration and the summed layer_loss on the benchmark's BraTS
+configuration (alternating the two in one process), and effq_gptq_chol / effq_gptq_sweep alone at a few system sizes.
+
+    python scripts/prof_gptq.py calib [--vols 16] [--size 128] [--levels 4] [--steps 3] [--only effq|gptq]
+    python scripts/prof_gptq.py kernels [n ...]
+One JSON line per result."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+PEAK_F64_MFMA_TFLOPS = 78.6       # MI355X fp64 matrix peak (vendor)
+DEV = "cuda:0"
+
+
+def calib(a):
+    from efficientq_amd import calibrate as K, config as Cf, synth
+    vols = synth.calib_batch("brats", range(a.vols), a.size).to(DEV)
+    nets = {}
+    for name in ([a.only] if a.only else ["effq", "gptq"]):
+        args = Cf.make_args(dict(Cf.BRATS_NET, qconv=name), a.levels, a.levels)
+        QConv, _, kwQ = Cf.get_conv_class(args)
+        model = Cf.get_model_cube(args, QConv, kwQ)[0]["model"]
+        synth.randomise_network(model, 0)
+        model.eval()
+        K.search_fold_and_remove_bn(model)
+        model.to(DEV)
+        K.set_name(model)
+        nets[name] = (args, model, {k: v.clone() for k, v in model.state_dict().items()})
+
+    def step(name):
+        args, model, pristine = nets[name]
+        model.load_state_dict(pristine, strict=True)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        res = K.calibrate_model(model, vols, "brats", args.init_stride)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, sum(float(l.split(":")[1]) for l in res["layer_loss"])
+
+    for name in nets:
+        step(name)                                     # warm-up: code objects, workspaces
+    times, loss = {name: [] for name in nets}, {}
+    for _ in range(a.steps):
+        for name in nets:                              # alternating: both see the same state of the machine
+            dt, loss[name] = step(name)
+            times[name].append(round(dt, 4))
+    for name in nets:
+        t = sorted(times[name])
+        print(json.dumps(dict(metric="calibration", qconv=name, vols=a.vols, size=a.size, levels=a.levels,
+                              layer_loss_sum=loss[name], seconds=times[name], median_s=t[len(t) // 2])), flush=True)
+
+
+def kernels(a):
+    from efficientq_amd import ops_gptq as OG
+    from efficientq_amd.hip_ops import get_ops
+    ops = get_ops(DEV)
+
+    def timed(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for n in a.n or (865, 1729, 6913):
+        g = torch.Generator().manual_seed(n)
+        X = torch.randint(-3, 4, (2 * n, n), generator=g).float().to(DEV)
+        A0 = (2 * X.T @ X).contiguous()
+        del X
+        reps = 10 if n < 4000 else 3
+        ms = timed(lambda: OG.gptq_chol(ops, A0, 8.0), reps)
+        P = OG.gptq_chol(ops, A0, 8.0, read_flag=True)
+        flop = n ** 3 / 3.0
+        print(json.dumps(dict(metric="gptq_chol", n=n, ms=round(ms, 3), flop=flop, tflops=round(flop / ms / 1e9, 2),
+                              frac_f64_matrix_peak=round(flop / ms / 1e9 / PEAK_F64_MFMA_TFLOPS, 4),
+                              launches=OG.gptq_plan(ops, 1, n)["chol_launches"])), flush=True)
+        for c2 in (32, 64, 256):
+            u = ((torch.rand(c2, n, generator=g) - 0.5)).to(DEV)
+            alpha = torch.tensor([0.4], dtype=torch.float64, device=DEV)
+            u_w, u_b = u[:, :-1].contiguous(), u[:, -1].contiguous()
+            ms = timed(lambda: OG.gptq_sweep(ops, P, n, u_w, u_b, alpha, 4), reps)
+            flop = 1.0 * c2 * n * n
+            print(json.dumps(dict(metric="gptq_sweep", n=n, c2=c2, ms=round(ms, 3), flop=flop,
+                                  tflops=round(flop / ms / 1e9, 3),
+                                  frac_f64_matrix_peak=round(flop / ms / 1e9 / PEAK_F64_MFMA_TFLOPS, 5),
+                                  launches=OG.gptq_plan(ops, c2, n)["sweep_launches"])), flush=True)
+        del A0, P
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="mode", required=True)
+    c = sub.add_parser("calib")
+    c.add_argument("--vols", type=int, default=16)
+    c.add_argument("--size", type=int, default=128)
+    c.add_argument("--levels", type=int, default=4)
+    c.add_argument("--steps", type=int, default=3)
+    c.add_argument("--only", choices=["effq", "gptq"], default=None)
+    k = sub.add_parser("kernels")
+    k.add_argument("n", type=int, nargs="*")
+    a = ap.parse_args()
+    calib(a) if a.mode == "calib" else kernels(a)
