@@ -74,6 +74,13 @@ def build_parser():
     p.add_argument('--lwq_verbose', action='store_true')
     # new in this build: one weight scale per output channel (the reference's alpha_w is one scalar per layer)
     p.add_argument('--lwq_channel_wise', action='store_true')
+    # the two optional steps of --qconv gptq (gptq.py); the values and the calibrator are checked by gptq_switches, after the
+    # YAML has been merged in
+    p.add_argument('--gptq_refine', default=0, type=int, metavar='K',
+                   help='with --qconv gptq: K coordinate-descent passes behind the sweep, 0 ... 16 (0)')
+    p.add_argument('--gptq_order', default='natural', metavar='natural|act',
+                   help='with --qconv gptq: the order the columns are rounded in: natural (default) or act, by '
+                        'descending diag(A0), the bias last')
     p.add_argument('--save_nii', action='store_true')
     p.add_argument('--is_cc', action='store_true', help='lesion-level metrics from connected components')
     p.add_argument('--surf_dist', action='store_true', help='surface distances hd, hd95, assd (voxel units)')
@@ -545,6 +552,27 @@ def post_rules(args):
     return rules, int(conn)
 
 
+def gptq_switches(args) -> dict:
+    """{gptq_refine, gptq_order} of --gptq_refine / --gptq_order (or the YAML keys, or the attributes of a namespace made by
+    hand): the constructor keywords of GPTQConvHIP, {} where neither is given.  With any --qconv other than gptq both are
+    refused by name, and so is a value outside 0 ... 16 or an unknown order (SystemExit), host only."""
+    from .gptq import check_options
+    refine, order = getattr(args, 'gptq_refine', 0), getattr(args, 'gptq_order', 'natural')
+    refine, order = 0 if refine is None else refine, 'natural' if order is None else order
+    if (refine, order) == (0, 'natural'):
+        return {}
+    qconv = str(getattr(args, 'qconv', 'conv')).lower()
+    for switch, given, unset in (('gptq_refine', refine, 0), ('gptq_order', order, 'natural')):
+        if given != unset and qconv != 'gptq':
+            raise SystemExit(f'--{switch} {given}: a step of the one-pass calibrator, and --qconv is {qconv}: it needs '
+                             f'--qconv gptq, or drop --{switch}')
+    try:
+        refine, order = check_options(refine, order)
+    except ValueError as e:
+        raise SystemExit(f'--{e}')
+    return dict(gptq_refine=refine, gptq_order=order)
+
+
 def _pair(s):
     return [int(x) for x in s.split(',')] if s else None
 
@@ -554,11 +582,13 @@ def get_conv_class(args):
     name = args.qconv.lower()
     if name not in QCONV_REGISTRY:
         raise RuntimeError('Unknown QConv name: %s' % args.qconv)
+    gptq_kw = gptq_switches(args)
     if name == 'conv':
         return nn.Conv3d, 'FP', {}
     q_weight, q_act = args.qlvl_w > 0, args.qlvl_a > 0
     qlvl, qlvl_act = args.qlvl_w, (args.qlvl_a if q_act else 256)
     kwQ = {a: getattr(args, a) for a in dir(args) if a[:4] == 'lwq_'}
+    kwQ.update(gptq_kw)
     if q_act and q_weight:
         info = 'bothQw{}a{}'.format(qlvl, qlvl_act)
     elif q_act:

@@ -23,23 +23,13 @@
 #include <math.h>
 #include "common.h"
 #include "fp_level.h"
+#include "gptq.h"
 
 namespace effq {
 
-typedef double gq_f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GQ_B = 64;          // block size of the factor and of the sweep
 constexpr int GQ_LDA = 66;        // LDS leading dimension (doubles) of the matrix-core operands
 constexpr int GQ_HDR = 32;        // doubles behind L: [0] = the flag (int32)
 constexpr int GQ_LDT = 65;        // LDS leading dimension of the diagonal block while it is factored
-constexpr int GQ_MAX_N = 32768;
-constexpr int GQ_ROWS = 4;        // output rows (waves) per workgroup of k_gq_block
-
-__device__ __forceinline__ double gq_readlane(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
 
 // L (reversed indices) = the lower triangle of A0 + eta I, identity on the padding, zeros above the diagonal; flag = 0
 __global__ __launch_bounds__(256) void k_gq_build(const float* __restrict__ A0, int n, int npad, double eta,
@@ -271,11 +261,7 @@ __global__ __launch_bounds__(64 * GQ_ROWS) void k_gq_block(const GqSweep p, int 
     if (is_bias) {
       p.b[r] = (float)q_mine;
     } else {
-      // f32(alpha) times the level value in the arithmetic that restores a stored weight, so that the round trip through
-      // the level ids gives these bits back: per row PTQConv._channel_weight (the value rounded from fp64), per tensor
-      // restore_fp_weight (id * f32(d) - 1 in fp32; the file is compiled without contraction)
-      const float bv = p.per_row ? (float)(idx_mine * d - 1.0) : (float)idx_mine * (float)d - 1.0f;
-      p.G[(size_t)r * p.nw + j] = (float)a * bv;
+      p.G[(size_t)r * p.nw + j] = gq_weight_f32(a, idx_mine, d, p.per_row);      // (gptq.h: the restore arithmetic)
       if (p.ids != nullptr) p.ids[(size_t)r * p.nw + j] = (uint8_t)idx_mine;
     }
   }

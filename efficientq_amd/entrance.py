@@ -274,6 +274,7 @@ def main(argv=None):
     args = Cf.build_parser().parse_args(argv)
     if args.config:
         args = Cf.merge_config(args.config, args)
+    Cf.gptq_switches(args)              # in every mission: refused by name before anything runs
     if args.mission == 'prep':
         check_post(args)
         Cf.thr_switches(args)

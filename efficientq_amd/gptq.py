@@ -17,6 +17,18 @@ The rule, per layer with n = k^3 c1 (+ 1) unknowns per output row, weights in th
 
 ``factor_host`` / ``sweep_host`` state 3 and 4 in numpy the way the kernels of csrc/gptq.hip walk them - reversed indices,
 64-column blocks, the later columns' s updated once per block - for the tests and for reading; ``GPTQConvHIP`` is the layer.
+
+Two optional steps around 4 (``--gptq_refine K``, ``--gptq_order act``; both off by default):
+
+4a. Activation ordering: the weight columns are visited by descending diag(A0) (``order_host``), the bias still last: A0
+    and u* are permuted, factor, sweep and passes run on the permuted system, G and the ids are scattered back.  The scale
+    of 2 is fitted before and does not depend on the order.
+4b. K passes of coordinate descent on the same quadratic form (``refine_host``, csrc/gptq_refine.hip), from the sweep's
+    result q, with g = (q - u*) H.  A pass visits j = 0 .. n-1:
+        t = q_j - g_j / H_jj
+        q' = alpha * disc64(t)  for a weight,   q' = t  for the bias
+        a weight moves only if (q' - t)^2 < (q_j - t)^2, the bias always;  on a move  g += (q' - q_j) H[j, :],  q_j = q'
+    A move lowers the row's error by H_jj ((q_j - t)^2 - (q' - t)^2), so no pass raises it; err = sum_j g_j (q_j - u*_j).
 """
 from __future__ import annotations
 
@@ -71,10 +83,102 @@ def sweep_host(P: np.ndarray, u: np.ndarray, alpha, levels: int, has_bias: bool,
     return q[:, :n][:, ::-1], ids[:, :n][:, ::-1], err
 
 
+def refine_host(H: np.ndarray, u: np.ndarray, ids, b, alpha, levels: int, has_bias: bool, passes: int,
+                block: int = ops_gptq.BLOCK):
+    """(q, ids, moves, err, margin) after `passes` passes of rule 4b over the sweep's state - the level ids (c2, n - has_bias)
+    and the bias b (c2) - walked as the device walks it: 64-column blocks in natural order, g step by step inside a
+    block, the columns outside it once per block.  err: (passes, c2), the error after every pass.  margin: per row the
+    smallest margin of a decision, as a difference of squared distances in units of alpha^2: of an acceptance whose grid
+    value differs from the current one, |(q' - t)^2 - (q_j - t)^2|, and of the rounding of an unclipped t, 2 d times its
+    distance from the boundary between two levels."""
+    c2, n = u.shape
+    nw = n - int(has_bias)
+    a = np.broadcast_to(np.asarray(alpha, dtype=np.float64).reshape(-1), (c2,))
+    d = 2.0 / (levels - 1)
+    ids = np.array(ids, dtype=np.float64).reshape(c2, nw)
+    q = np.empty((c2, n))
+    q[:, :nw] = a[:, None] * (ids * d - 1.0)
+    if has_bias:
+        q[:, -1] = np.asarray(b, dtype=np.float64)
+    g = (q - u) @ H
+    moves, margin, errs = np.zeros(c2, dtype=np.int64), np.full(c2, np.inf), []
+    for _ in range(passes):
+        for kb in range(0, n, block):
+            ke = min(kb + block, n)
+            delta = np.zeros((c2, ke - kb))
+            for j in range(kb, ke):
+                t = q[:, j] - g[:, j] / H[j, j]
+                if has_bias and j == n - 1:
+                    dl, q[:, j] = t - q[:, j], t
+                else:
+                    v, idx = disc64(t, a, levels)
+                    qn = a * v
+                    gain = (q[:, j] - t) ** 2 - (qn - t) ** 2
+                    take = gain > 0.0
+                    x = (t / a + 1.0) / d
+                    edge = np.where((x > 0.0) & (x < levels - 1), 2.0 * d * d * np.abs(np.abs(x - np.floor(x)) - 0.5), np.inf)
+                    margin = np.minimum(margin, np.minimum(edge, np.where(idx != ids[:, j], np.abs(gain) / a ** 2, np.inf)))
+                    dl = np.where(take, qn - q[:, j], 0.0)
+                    q[:, j] = np.where(take, qn, q[:, j])
+                    ids[:, j] = np.where(take, idx, ids[:, j])
+                    moves += take
+                delta[:, j - kb] = dl
+                g[:, kb:ke] += np.outer(dl, H[j, kb:ke])
+            g[:, :kb] += delta @ H[kb:ke, :kb]
+            g[:, ke:] += delta @ H[kb:ke, ke:]
+        errs.append(np.einsum("rj,rj->r", g, q - u))
+    return q, ids, moves, np.array(errs), margin
+
+
+def order_host(diag_a0, has_bias: bool) -> np.ndarray:
+    """The visiting order of ``--gptq_order act``: the weight columns by descending diag(A0), ties in their own order,
+    the bias last."""
+    diag_a0 = np.asarray(diag_a0)
+    nw = diag_a0.shape[0] - int(has_bias)
+    perm = np.argsort(-diag_a0[:nw], kind="stable")
+    return np.concatenate([perm, [nw]]) if has_bias else perm
+
+
+def round_columns(ops, A0, eta, u_w, u_b, alpha, levels, per_row, refine=0, order="natural"):
+    """Steps 3, 4, 4a and 4b on the device, nothing read back: (G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P).
+    err_sweep is the sweep's error and err the final one (the same tensor without passes); moves is None without passes;
+    ids is None unless passes ran."""
+    n = int(A0.shape[0])
+    perm = None
+    if order == "act":
+        perm = ops_gptq.gptq_order(A0, u_b is not None)
+        up = torch.triu(A0)                                   # the triangle the kernels read, mirrored: a full matrix to permute
+        A0 = (up + torch.triu(A0, 1).T)[perm][:, perm].contiguous()
+        u_w = u_w[:, perm[:u_w.shape[1]]].contiguous()
+    P = ops_gptq.gptq_chol(ops, A0, eta)
+    pd_flag = ops_gptq.gptq_flag(P, n)
+    if refine:
+        G, b, ids, err_sweep, row_flag = ops_gptq.gptq_sweep(ops, P, n, u_w, u_b, alpha, levels, want_ids=True, per_row=per_row)
+        err, moves = ops_gptq.gptq_refine(ops, A0, eta, u_w, u_b, alpha, levels, refine, G, b, ids, row_flag, pd_flag,
+                                          per_row=per_row)
+    else:
+        G, b, ids, err, row_flag = ops_gptq.gptq_sweep(ops, P, n, u_w, u_b, alpha, levels, per_row=per_row)
+        err_sweep, moves = err, None
+    if perm is not None:
+        back = torch.empty_like(perm[:G.shape[1]])
+        back[perm[:G.shape[1]]] = torch.arange(G.shape[1], device=perm.device)
+        G = G[:, back].contiguous()
+        ids = ids[:, back].contiguous() if ids is not None else None
+    return G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P
+
+
+GPTQ_ORDERS = ("natural", "act")
+
+
 class GPTQConvHIP(EfficientQConvHIP):
     """The layer of ``--qconv gptq``: the statistics, input quantisation, Gram system, final forward and commit of
     EfficientQConvHIP around the rule above instead of the ADMM run.  One host synchronisation per layer.  ``alpha_w`` is the
-    one fitted scale (per tensor or per row): the committed weights lie exactly on its grid."""
+    one fitted scale (per tensor or per row): the committed weights lie exactly on its grid.  ``gptq_refine=K`` (0 .. 16)
+    adds K coordinate-descent passes behind the sweep, ``gptq_order='act'`` visits the columns by descending diag(A0)."""
+
+    def __init__(self, *args, **kwQ):
+        super().__init__(*args, **kwQ)
+        self.gptq_refine, self.gptq_order = check_options(kwQ.get('gptq_refine', 0), kwQ.get('gptq_order', 'natural'))
 
     def ptq(self, x):
         c = self._layer_inputs(x)
@@ -101,15 +205,19 @@ class GPTQConvHIP(EfficientQConvHIP):
         numel = y_dim * 1.0
         lossf = (info["fin"][1] if att is not None else info["fin"][0]) / numel
         if self.lwq_verbose:
+            passes = (f'err after the sweep = {info["gptq_err_sweep"]:.6g}, after {self.gptq_refine} passes '
+                      f'({info["gptq_moves"]} moves) = {info["gptq_err"]:.6g}' if self.gptq_refine else
+                      f'err = {info["gptq_err"]:.6g}')
             print(f'GPTQ {self.name}: n = {c.n_sys}, eta = {eta:.4f}, scale fit {info["w_iters"]} iterations, '
-                  f'err = {info["gptq_err"]:.6g}, loss = {lossf:.7f}.')
+                  f'{passes}, loss = {lossf:.7f}.')
         if self.layer_loss is not None:
             self.layer_loss.append(f'{self.name:45s}:{lossf}')
         self.last_trace = dict(method='gptq', rho_scale=rho_scale, gptq_err=info["gptq_err"],
                                final_mse=info["fin"][0] / numel, layer_loss=lossf, act_iters=act_iters,
                                w_iters=info["w_iters"], alpha_w=info["alpha_w"], loss_history=[],
                                exact_gram=paths.gram_i8, gptq_s=t_fit, channel_wise=self.channel_wise,
-                               paths=paths._asdict())
+                               paths=paths._asdict(), gptq_refine=self.gptq_refine, gptq_order=self.gptq_order,
+                               gptq_err_sweep=info["gptq_err_sweep"], gptq_moves=info["gptq_moves"])
 
     def _gptq_run(self, c, A0, B0, eta):
         """Steps 1 - 4, enqueued on the current stream; nothing is read back."""
@@ -131,25 +239,28 @@ class GPTQConvHIP(EfficientQConvHIP):
             ops.fixed_point_bucket(u_w, None, None, L, state)
             ops.fp_check(state, fp_err)
             alpha, iters = state[:1], state[4:5].view(torch.int32)[:1]
-        P = ops_gptq.gptq_chol(ops, A0, eta)
-        G, b, _, err, row_flag = ops_gptq.gptq_sweep(ops, P, c.n_sys, u_w, u_b, alpha, L, per_row=self.channel_wise)
+        G, b, _, err, err_sweep, moves, row_flag, pd_flag, P = round_columns(
+            ops, A0, eta, u_w, u_b, alpha, L, self.channel_wise, self.gptq_refine, self.gptq_order)
         # what _final_forward reads of an ADMM run: the scale state of the chosen iterate (the i8 forward folds it in)
         run = SimpleNamespace(state_ring=state.reshape(1, 5)) if state is not None else None
         best = torch.zeros(2, dtype=torch.float64, device=dev)
-        return SimpleNamespace(G=G.reshape(-1), b=b, err=err, alpha=alpha, iters=iters, fp_err=fp_err, row_flag=row_flag,
-                               pd_flag=ops_gptq.gptq_flag(P, c.n_sys), run=run, best=best, keep=(P, u_w, u_b, Ainv, zero))
+        return SimpleNamespace(G=G.reshape(-1), b=b, err=err, err_sweep=err_sweep, moves=moves, alpha=alpha, iters=iters,
+                               fp_err=fp_err, row_flag=row_flag, pd_flag=pd_flag, run=run, best=best,
+                               keep=(P, u_w, u_b, Ainv, zero))
 
     def _gptq_read(self, fit, fin):
         """The layer's one device->host copy; raises naming the layer on what the device flagged."""
         c2 = fit.err.numel()
         f64 = torch.float64
         pack = torch.cat([fin.to(f64).reshape(-1), fit.err, fit.alpha.reshape(-1), fit.iters.to(f64), fit.fp_err.to(f64),
-                          fit.pd_flag.to(f64), fit.row_flag.to(f64)]).cpu().tolist()
+                          fit.pd_flag.to(f64), fit.row_flag.to(f64)] +
+                         ([fit.err_sweep, fit.moves.to(f64)] if fit.moves is not None else [])).cpu().tolist()
         na, ni = fit.alpha.numel(), fit.iters.numel()
         o = 2 + c2
         alpha, iters = pack[o:o + na], pack[o + na:o + na + ni]
         fp_err, pd_flag = (int(v) for v in pack[o + na + ni:o + na + ni + 2])
-        rows = [r for r, v in enumerate(pack[o + na + ni + 2:]) if v]
+        rows = [r for r, v in enumerate(pack[o + na + ni + 2:o + na + ni + 2 + c2]) if v]
+        tail = pack[o + na + ni + 2 + c2:]                                  # with passes: the sweep's errors, the moves
         if pd_flag:
             raise RuntimeError(f'{self.name}: the Gram system A0 + eta I is not positive definite (a pivot of its fp64 '
                                f'Cholesky factorisation was <= 0 or not finite)')
@@ -159,5 +270,19 @@ class GPTQConvHIP(EfficientQConvHIP):
             raise RuntimeError(f'{self.name}: weight-scale fixed point did not finish (device state {fp_err})')
         if rows:
             raise RuntimeError(f'{self.name}: the weight scale of output channel(s) {rows[:8]} is not finite and positive')
-        return dict(fin=pack[:2], gptq_err=float(sum(pack[2:o])), alpha_w=alpha if self.channel_wise else alpha[0],
-                    w_iters=[int(max(iters))])
+        err = float(sum(pack[2:o]))
+        return dict(fin=pack[:2], gptq_err=err, alpha_w=alpha if self.channel_wise else alpha[0], w_iters=[int(max(iters))],
+                    gptq_err_sweep=float(sum(tail[:c2])) if tail else err, gptq_moves=int(sum(tail[c2:])))
+
+
+def check_options(refine, order):
+    """(passes, order) of ``gptq_refine`` / ``gptq_order``; a value outside 0 .. 16 or an unknown order is refused by name."""
+    try:
+        ok = not isinstance(refine, bool) and int(refine) == refine and 0 <= int(refine) <= ops_gptq.REFINE_MAX_PASSES
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'gptq_refine {refine!r}: the passes behind the sweep, 0 to {ops_gptq.REFINE_MAX_PASSES}')
+    if order not in GPTQ_ORDERS:
+        raise ValueError(f'gptq_order {order!r}: one of {", ".join(GPTQ_ORDERS)}')
+    return int(refine), order

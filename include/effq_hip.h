@@ -1412,6 +1412,28 @@ int effq_gptq_sweep(const double* P, int n, const float* u_w, const float* u_b, 
                     int per_row, int levels, float* G, float* b, uint8_t* ids, double* err, int32_t* row_flag, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- Coordinate-descent passes behind the sweep (the rule: refine_host of efficientq_amd/gptq.py, kernels: gptq_refine.hip) ----
+ * The state is what the sweep left: the level ids (q_j = alpha_r * (id_j d - 1) in fp64, d = 2 / (levels - 1)) and the
+ * fp32 bias.  With H = A0 + eta I read from A0's upper triangle as the factorisation reads it, u the optimum u_w | u_b and
+ * g = (q - u) H, one pass visits j = 0 .. n-1 (the bias last):  t = q_j - g_j / H_jj;  q' = alpha_r * disc64(t) for a
+ * weight, q' = t for the bias;  a weight moves only if (q' - t)^2 < (q_j - t)^2, the bias always;  on a move q_j = q' and
+ * g += (q' - q_j) H[j, :].  No move raises (q - u) H (q - u)^T.  After `passes` passes (1 .. 16) err_r = sum_j g_j (q_j - u_j),
+ * and G, ids and b hold the new state, G in the arithmetic of the sweep; moves_r counts the weight moves of row r.
+ * The device works in 64-column blocks: inside a block g follows step by step, the other columns take Delta * H[block, :]
+ * once per block on v_mfma_f64_16x16x4_f64, H converted from the fp32 A0 in registers (the mirrored tiles through LDS).
+ * row_flag: that of the sweep; a row whose flag is set (or whose scale is not finite and positive) writes nothing.
+ * pd_flag: the flag word of the factor the sweep ran on; when it is set no launch writes anything.  Nothing is read back.
+ * ws: effq_gptq_refine_ws_bytes(c2, n), no initialisation needed.  Refused as effq_gptq_sweep refuses (ids may not be
+ * NULL here), and for passes outside 1 .. 16 or an eta that is not finite and positive.
+ * effq_gptq_refine_plan_query launches nothing: *nblk 64-blocks, the launches of the call, *block_grid workgroups of the
+ * in-block kernel, *update_gx x *update_gy workgroups of the matrix-core update. */
+size_t effq_gptq_refine_ws_bytes(int c2, int n);
+int effq_gptq_refine_plan_query(int c2, int n, int passes, int* nblk, int* launches, int* block_grid, int* update_gx,
+                                int* update_gy);
+int effq_gptq_refine(const float* A0, double eta, int n, const float* u_w, const float* u_b, int c2, int has_bias,
+                     const double* alpha, int per_row, int levels, int passes, float* G, float* b, uint8_t* ids, double* err,
+                     int32_t* moves, const int32_t* row_flag, const int* pd_flag, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

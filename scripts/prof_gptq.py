@@ -1,7 +1,8 @@
 """--qconv gptq beside --qconv effq: seconds per calibration and the summed layer_loss on the benchmark's BraTS
-configuration (alternating the two in one process), and effq_gptq_chol / effq_gptq_sweep alone at a few system sizes.
+configuration (alternating the two in one process; --variants adds gptq with 1 / 2 / 4 refinement passes and with
+activation ordering), and effq_gptq_chol / effq_gptq_sweep / a pass of effq_gptq_refine alone at a few system sizes.
 
-    python scripts/prof_gptq.py calib [--vols 16] [--size 128] [--levels 4] [--steps 3] [--only effq|gptq]
+    python scripts/prof_gptq.py calib [--vols 16] [--size 128] [--levels 4] [--steps 3] [--only effq|gptq] [--variants]
     python scripts/prof_gptq.py kernels [n ...]
 One JSON line per result."""
 import argparse
@@ -21,8 +22,14 @@ def calib(a):
     from efficientq_amd import calibrate as K, config as Cf, synth
     vols = synth.calib_batch("brats", range(a.vols), a.size).to(DEV)
     nets = {}
-    for name in ([a.only] if a.only else ["effq", "gptq"]):
-        args = Cf.make_args(dict(Cf.BRATS_NET, qconv=name), a.levels, a.levels)
+    # name: (qconv, passes, order)
+    variants = {"effq": ("effq", 0, "natural"), "gptq": ("gptq", 0, "natural")}
+    if a.variants:
+        variants.update({"gptq+r1": ("gptq", 1, "natural"), "gptq+r2": ("gptq", 2, "natural"),
+                         "gptq+r4": ("gptq", 4, "natural"), "gptq+act": ("gptq", 0, "act"), "gptq+act+r2": ("gptq", 2, "act")})
+    for name in ([a.only] if a.only else variants):
+        qconv, passes, order = variants[name]
+        args = Cf.make_args(dict(Cf.BRATS_NET, qconv=qconv), a.levels, a.levels, gptq_refine=passes, gptq_order=order)
         QConv, _, kwQ = Cf.get_conv_class(args)
         model = Cf.get_model_cube(args, QConv, kwQ)[0]["model"]
         synth.randomise_network(model, 0)
@@ -92,6 +99,19 @@ def kernels(a):
                                   tflops=round(flop / ms / 1e9, 3),
                                   frac_f64_matrix_peak=round(flop / ms / 1e9 / PEAK_F64_MFMA_TFLOPS, 5),
                                   launches=OG.gptq_plan(ops, c2, n)["sweep_launches"])), flush=True)
+            # a pass alone: the difference of 3 passes and 1 pass over the same sweep state (the moves differ, the launches not)
+            G, b, ids, _, row_flag = OG.gptq_sweep(ops, P, n, u_w, u_b, alpha, 4, want_ids=True)
+            state, flag = (G.clone(), b.clone(), ids.clone()), OG.gptq_flag(P, n)
+
+            def refine(k):
+                for t, t0 in zip((G, b, ids), state):
+                    t.copy_(t0)
+                OG.gptq_refine(ops, A0, 8.0, u_w, u_b, alpha, 4, k, G, b, ids, row_flag, flag)
+            ms1, ms3 = timed(lambda: refine(1), reps), timed(lambda: refine(3), reps)
+            print(json.dumps(dict(metric="gptq_refine_pass", n=n, c2=c2, ms=round((ms3 - ms1) / 2, 3),
+                                  ms_one_pass_call=round(ms1, 3), flop=2.0 * c2 * n * n,
+                                  launches_per_pass=(OG.gptq_refine_plan(ops, c2, n, 2)["launches"] -
+                                                     OG.gptq_refine_plan(ops, c2, n, 1)["launches"]))), flush=True)
         del A0, P
 
 
@@ -104,6 +124,7 @@ if __name__ == "__main__":
     c.add_argument("--levels", type=int, default=4)
     c.add_argument("--steps", type=int, default=3)
     c.add_argument("--only", choices=["effq", "gptq"], default=None)
+    c.add_argument("--variants", action="store_true")
     k = sub.add_parser("kernels")
     k.add_argument("n", type=int, nargs="*")
     a = ap.parse_args()
