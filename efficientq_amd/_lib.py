@@ -266,6 +266,9 @@ SIGNATURES = {
     "effq_gptq_refine_ws_bytes": (_SZ, [_I, _I]),
     "effq_gptq_refine_plan_query": (_I, [_I, _I, _I, _IP, _IP, _IP, _IP, _IP]),
     "effq_gptq_refine": (_I, [_P, _D, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "effq_gptq_rescale_ws_bytes": (_SZ, [_I, _I]),
+    "effq_gptq_rescale_plan_query": (_I, [_I, _I, _IP, _IP, _IP, _IP, _IP, _IP]),
+    "effq_gptq_rescale": (_I, [_P, _D, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 # include/effq_hip.h: scratch of effq_seg_tallies, the most classes it counts, its modes and label merges

@@ -81,6 +81,9 @@ def build_parser():
     p.add_argument('--gptq_order', default='natural', metavar='natural|act',
                    help='with --qconv gptq: the order the columns are rounded in: natural (default) or act, by '
                         'descending diag(A0), the bias last')
+    p.add_argument('--gptq_rescale', default=0, type=int, metavar='R',
+                   help='with --qconv gptq: R rounds of [weight scale (and bias) refitted on the layer\'s quadratic form, '
+                        'then the K passes of --gptq_refine], 0 ... 8 (0); more than 1 needs K > 0')
     p.add_argument('--save_nii', action='store_true')
     p.add_argument('--is_cc', action='store_true', help='lesion-level metrics from connected components')
     p.add_argument('--surf_dist', action='store_true', help='surface distances hd, hd95, assd (voxel units)')
@@ -553,24 +556,27 @@ def post_rules(args):
 
 
 def gptq_switches(args) -> dict:
-    """{gptq_refine, gptq_order} of --gptq_refine / --gptq_order (or the YAML keys, or the attributes of a namespace made by
-    hand): the constructor keywords of GPTQConvHIP, {} where neither is given.  With any --qconv other than gptq both are
-    refused by name, and so is a value outside 0 ... 16 or an unknown order (SystemExit), host only."""
+    """{gptq_refine, gptq_order, gptq_rescale} of --gptq_refine / --gptq_order / --gptq_rescale (or the YAML keys, or the
+    attributes of a namespace made by hand): the constructor keywords of GPTQConvHIP, {} where none is given.  With any
+    --qconv other than gptq they are refused by name, and so is a value outside 0 ... 16 (passes) or 0 ... 8 (rounds), an
+    unknown order, or more than one round without passes (SystemExit), host only."""
     from .gptq import check_options
     refine, order = getattr(args, 'gptq_refine', 0), getattr(args, 'gptq_order', 'natural')
     refine, order = 0 if refine is None else refine, 'natural' if order is None else order
-    if (refine, order) == (0, 'natural'):
+    rescale = getattr(args, 'gptq_rescale', 0)
+    rescale = 0 if rescale is None else rescale
+    if (refine, order, rescale) == (0, 'natural', 0):
         return {}
     qconv = str(getattr(args, 'qconv', 'conv')).lower()
-    for switch, given, unset in (('gptq_refine', refine, 0), ('gptq_order', order, 'natural')):
+    for switch, given, unset in (('gptq_refine', refine, 0), ('gptq_order', order, 'natural'), ('gptq_rescale', rescale, 0)):
         if given != unset and qconv != 'gptq':
             raise SystemExit(f'--{switch} {given}: a step of the one-pass calibrator, and --qconv is {qconv}: it needs '
                              f'--qconv gptq, or drop --{switch}')
     try:
-        refine, order = check_options(refine, order)
+        refine, order, rescale = check_options(refine, order, rescale)
     except ValueError as e:
         raise SystemExit(f'--{e}')
-    return dict(gptq_refine=refine, gptq_order=order)
+    return dict(gptq_refine=refine, gptq_order=order, **(dict(gptq_rescale=rescale) if rescale else {}))
 
 
 def _pair(s):

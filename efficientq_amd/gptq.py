@@ -29,6 +29,14 @@ Two optional steps around 4 (``--gptq_refine K``, ``--gptq_order act``; both off
         q' = alpha * disc64(t)  for a weight,   q' = t  for the bias
         a weight moves only if (q' - t)^2 < (q_j - t)^2, the bias always;  on a move  g += (q' - q_j) H[j, :],  q_j = q'
     A move lowers the row's error by H_jj ((q_j - t)^2 - (q' - t)^2), so no pass raises it; err = sum_j g_j (q_j - u*_j).
+
+And one around 2 (``--gptq_rescale R``, off by default): the scale of 2 is an unweighted fit and never sees H.
+4c. R rounds of [refit, then the K passes of 4b on the new grid]: with the level ids fixed, v_j = id_j d - 1, a row is
+    q = [alpha v | beta] and its error  f(alpha, beta) = alpha^2 a11 + 2 alpha beta a12 + beta^2 a22 - 2 alpha c1 - 2 beta c2 + c0
+    with a11 = v H_ww v^T, a12 = v . H_wb, a22 = H_bb, c1 = v . (H u*^T)_w, c2 = (H u*^T)_b, c0 = u* H u*^T.  The refit
+    (``rescale_host``, csrc/gptq_rescale.hip) is the minimiser of f: per row the 2 x 2 solve, per tensor one alpha for the
+    summed f and every row's own beta.  It is taken only where it is a finite positive scale from a positive denominator,
+    so neither a refit nor a pass raises the error: a block-coordinate descent on the layer's own objective.
 """
 from __future__ import annotations
 
@@ -130,6 +138,48 @@ def refine_host(H: np.ndarray, u: np.ndarray, ids, b, alpha, levels: int, has_bi
     return q, ids, moves, np.array(errs), margin
 
 
+def rescale_host(H: np.ndarray, u: np.ndarray, ids, b, alpha, levels: int, has_bias: bool, per_row: bool, row_flag=None):
+    """(alpha, b, err, kept) of rule 4c for the level ids (c2, n - has_bias), the bias b (c2, or None) and the scale(s)
+    alpha the rows stand on.  With the bias eliminated, num_r = c1 - a12 c2 / a22 and den_r = a11 - a12^2 / a22 (c1 and a11
+    without a bias): alpha_r = num_r / den_r per row, alpha = sum_r num_r / sum_r den_r per tensor (the rows added in row
+    order), beta_r = (c2 - a12 alpha) / a22.  A refit is taken only if its denominator is positive, alpha finite and
+    positive, beta finite and the row not flagged (row_flag, or a present scale that is not finite and positive); per
+    tensor every row must pass.  Where it is not taken the row keeps alpha and b, and kept counts it (rows, or 1 for the
+    tensor).  err: f at the point every row stands on afterwards (without meaning for a flagged row)."""
+    c2, n = u.shape
+    nw = n - int(has_bias)
+    v = np.zeros((c2, n))
+    v[:, :nw] = np.asarray(ids, dtype=np.float64).reshape(c2, nw) * (2.0 / (levels - 1)) - 1.0
+    a_old = np.broadcast_to(np.asarray(alpha, dtype=np.float64).reshape(-1), (c2,))
+    b_old = np.asarray(b, dtype=np.float64).reshape(c2) if has_bias else np.zeros(c2)
+    vH, uH = v @ H, u @ H
+    a11, c1, c0 = (np.einsum("rj,rj->r", x, y) for x, y in ((vH, v), (vH, u), (uH, u)))
+    if has_bias:
+        a12, cb, a22 = vH[:, -1], uH[:, -1], H[-1, -1]
+        num, den = c1 - a12 * cb / a22, a11 - a12 * a12 / a22
+    else:
+        a12, cb, a22, num, den = np.zeros(c2), np.zeros(c2), 0.0, c1, a11
+    live = np.isfinite(a_old) & (a_old > 0.0)
+    if row_flag is not None:
+        live &= np.asarray(row_flag).reshape(c2) == 0
+    with np.errstate(all="ignore"):
+        if per_row:
+            a_new = num / den
+        else:
+            N = D = 0.0
+            for r in range(c2):
+                N, D = N + num[r], D + den[r]
+            a_new, den = np.full(c2, N / D), np.full(c2, D)
+        beta_new = (cb - a12 * a_new) / a22 if has_bias else np.zeros(c2)
+        take = live & (den > 0.0) & np.isfinite(a_new) & (a_new > 0.0) & np.isfinite(beta_new)
+    if not per_row:
+        take = np.full(c2, bool(take.all()))
+    a, beta = np.where(take, a_new, a_old), np.where(take, beta_new, b_old)
+    err = a * a * a11 + 2.0 * a * beta * a12 + beta * beta * a22 - 2.0 * a * c1 - 2.0 * beta * cb + c0
+    kept = int((~take).sum()) if per_row else int(not take[0])
+    return (a if per_row else a[:1]), (beta if has_bias else None), err, kept
+
+
 def order_host(diag_a0, has_bias: bool) -> np.ndarray:
     """The visiting order of ``--gptq_order act``: the weight columns by descending diag(A0), ties in their own order,
     the bias last."""
@@ -139,10 +189,12 @@ def order_host(diag_a0, has_bias: bool) -> np.ndarray:
     return np.concatenate([perm, [nw]]) if has_bias else perm
 
 
-def round_columns(ops, A0, eta, u_w, u_b, alpha, levels, per_row, refine=0, order="natural"):
-    """Steps 3, 4, 4a and 4b on the device, nothing read back: (G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P).
-    err_sweep is the sweep's error and err the final one (the same tensor without passes); moves is None without passes;
-    ids is None unless passes ran."""
+def round_columns(ops, A0, eta, u_w, u_b, alpha, levels, per_row, refine=0, order="natural", rescale=0):
+    """Steps 3, 4 and 4a to 4c on the device, nothing read back: (G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P,
+    err_rescaled, kept).  err_sweep is the sweep's error and err the final one (the same tensor without passes or
+    refits); moves is None without passes; ids is None unless passes or refits ran.  rescale = R: R rounds of [refit,
+    `refine` passes]; alpha is then updated in place, err_rescaled is the error after the last refit and kept counts the
+    refits not taken (both None without)."""
     n = int(A0.shape[0])
     perm = None
     if order == "act":
@@ -152,7 +204,19 @@ def round_columns(ops, A0, eta, u_w, u_b, alpha, levels, per_row, refine=0, orde
         u_w = u_w[:, perm[:u_w.shape[1]]].contiguous()
     P = ops_gptq.gptq_chol(ops, A0, eta)
     pd_flag = ops_gptq.gptq_flag(P, n)
-    if refine:
+    err_rescaled = kept = None
+    if rescale:
+        G, b, ids, err_sweep, row_flag = ops_gptq.gptq_sweep(ops, P, n, u_w, u_b, alpha, levels, want_ids=True, per_row=per_row)
+        err, moves, kept = err_sweep, None, torch.zeros(1, dtype=torch.int32, device=G.device)
+        for _ in range(rescale):
+            err_rescaled, _ = ops_gptq.gptq_rescale(ops, A0, eta, u_w, u_b, alpha, levels, G, b, ids, row_flag, pd_flag,
+                                                    per_row=per_row, out=(torch.empty_like(err_sweep), kept))
+            err = err_rescaled
+            if refine:
+                err, m = ops_gptq.gptq_refine(ops, A0, eta, u_w, u_b, alpha, levels, refine, G, b, ids, row_flag, pd_flag,
+                                              per_row=per_row)
+                moves = m if moves is None else moves + m
+    elif refine:
         G, b, ids, err_sweep, row_flag = ops_gptq.gptq_sweep(ops, P, n, u_w, u_b, alpha, levels, want_ids=True, per_row=per_row)
         err, moves = ops_gptq.gptq_refine(ops, A0, eta, u_w, u_b, alpha, levels, refine, G, b, ids, row_flag, pd_flag,
                                           per_row=per_row)
@@ -164,7 +228,7 @@ def round_columns(ops, A0, eta, u_w, u_b, alpha, levels, per_row, refine=0, orde
         back[perm[:G.shape[1]]] = torch.arange(G.shape[1], device=perm.device)
         G = G[:, back].contiguous()
         ids = ids[:, back].contiguous() if ids is not None else None
-    return G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P
+    return G, b, ids, err, err_sweep, moves, row_flag, pd_flag, P, err_rescaled, kept
 
 
 GPTQ_ORDERS = ("natural", "act")
@@ -174,11 +238,14 @@ class GPTQConvHIP(EfficientQConvHIP):
     """The layer of ``--qconv gptq``: the statistics, input quantisation, Gram system, final forward and commit of
     EfficientQConvHIP around the rule above instead of the ADMM run.  One host synchronisation per layer.  ``alpha_w`` is the
     one fitted scale (per tensor or per row): the committed weights lie exactly on its grid.  ``gptq_refine=K`` (0 .. 16)
-    adds K coordinate-descent passes behind the sweep, ``gptq_order='act'`` visits the columns by descending diag(A0)."""
+    adds K coordinate-descent passes behind the sweep, ``gptq_order='act'`` visits the columns by descending diag(A0),
+    ``gptq_rescale=R`` (0 .. 8) runs R rounds of [scale refit on the quadratic form, the K passes]; ``alpha_w`` is then the
+    last refitted scale."""
 
     def __init__(self, *args, **kwQ):
         super().__init__(*args, **kwQ)
-        self.gptq_refine, self.gptq_order = check_options(kwQ.get('gptq_refine', 0), kwQ.get('gptq_order', 'natural'))
+        self.gptq_refine, self.gptq_order, self.gptq_rescale = check_options(
+            kwQ.get('gptq_refine', 0), kwQ.get('gptq_order', 'natural'), kwQ.get('gptq_rescale', 0))
 
     def ptq(self, x):
         c = self._layer_inputs(x)
@@ -208,6 +275,10 @@ class GPTQConvHIP(EfficientQConvHIP):
             passes = (f'err after the sweep = {info["gptq_err_sweep"]:.6g}, after {self.gptq_refine} passes '
                       f'({info["gptq_moves"]} moves) = {info["gptq_err"]:.6g}' if self.gptq_refine else
                       f'err = {info["gptq_err"]:.6g}')
+            if self.gptq_rescale:
+                passes = (f'err after the sweep = {info["gptq_err_sweep"]:.6g}, after the last of {self.gptq_rescale} scale '
+                          f'refits ({info["gptq_kept"]} not taken) = {info["gptq_err_rescaled"]:.6g}, after its '
+                          f'{self.gptq_refine} passes ({info["gptq_moves"]} moves in all) = {info["gptq_err"]:.6g}')
             print(f'GPTQ {self.name}: n = {c.n_sys}, eta = {eta:.4f}, scale fit {info["w_iters"]} iterations, '
                   f'{passes}, loss = {lossf:.7f}.')
         if self.layer_loss is not None:
@@ -217,7 +288,9 @@ class GPTQConvHIP(EfficientQConvHIP):
                                w_iters=info["w_iters"], alpha_w=info["alpha_w"], loss_history=[],
                                exact_gram=paths.gram_i8, gptq_s=t_fit, channel_wise=self.channel_wise,
                                paths=paths._asdict(), gptq_refine=self.gptq_refine, gptq_order=self.gptq_order,
-                               gptq_err_sweep=info["gptq_err_sweep"], gptq_moves=info["gptq_moves"])
+                               gptq_err_sweep=info["gptq_err_sweep"], gptq_moves=info["gptq_moves"],
+                               gptq_rescale=self.gptq_rescale, gptq_err_rescaled=info["gptq_err_rescaled"],
+                               gptq_kept=info["gptq_kept"])
 
     def _gptq_run(self, c, A0, B0, eta):
         """Steps 1 - 4, enqueued on the current stream; nothing is read back."""
@@ -239,14 +312,15 @@ class GPTQConvHIP(EfficientQConvHIP):
             ops.fixed_point_bucket(u_w, None, None, L, state)
             ops.fp_check(state, fp_err)
             alpha, iters = state[:1], state[4:5].view(torch.int32)[:1]
-        G, b, _, err, err_sweep, moves, row_flag, pd_flag, P = round_columns(
-            ops, A0, eta, u_w, u_b, alpha, L, self.channel_wise, self.gptq_refine, self.gptq_order)
+        # (a refit writes the new scale into alpha, i.e. into the state the final forward reads)
+        G, b, _, err, err_sweep, moves, row_flag, pd_flag, P, err_rescaled, kept = round_columns(
+            ops, A0, eta, u_w, u_b, alpha, L, self.channel_wise, self.gptq_refine, self.gptq_order, self.gptq_rescale)
         # what _final_forward reads of an ADMM run: the scale state of the chosen iterate (the i8 forward folds it in)
         run = SimpleNamespace(state_ring=state.reshape(1, 5)) if state is not None else None
         best = torch.zeros(2, dtype=torch.float64, device=dev)
         return SimpleNamespace(G=G.reshape(-1), b=b, err=err, err_sweep=err_sweep, moves=moves, alpha=alpha, iters=iters,
                                fp_err=fp_err, row_flag=row_flag, pd_flag=pd_flag, run=run, best=best,
-                               keep=(P, u_w, u_b, Ainv, zero))
+                               err_rescaled=err_rescaled, kept=kept, keep=(P, u_w, u_b, Ainv, zero))
 
     def _gptq_read(self, fit, fin):
         """The layer's one device->host copy; raises naming the layer on what the device flagged."""
@@ -254,13 +328,16 @@ class GPTQConvHIP(EfficientQConvHIP):
         f64 = torch.float64
         pack = torch.cat([fin.to(f64).reshape(-1), fit.err, fit.alpha.reshape(-1), fit.iters.to(f64), fit.fp_err.to(f64),
                           fit.pd_flag.to(f64), fit.row_flag.to(f64)] +
-                         ([fit.err_sweep, fit.moves.to(f64)] if fit.moves is not None else [])).cpu().tolist()
+                         ([fit.err_sweep, fit.moves.to(f64) if fit.moves is not None else torch.zeros_like(fit.err)]
+                          if fit.moves is not None or fit.kept is not None else []) +
+                         ([fit.err_rescaled, fit.kept.to(f64)] if fit.kept is not None else [])).cpu().tolist()
         na, ni = fit.alpha.numel(), fit.iters.numel()
         o = 2 + c2
         alpha, iters = pack[o:o + na], pack[o + na:o + na + ni]
         fp_err, pd_flag = (int(v) for v in pack[o + na + ni:o + na + ni + 2])
         rows = [r for r, v in enumerate(pack[o + na + ni + 2:o + na + ni + 2 + c2]) if v]
-        tail = pack[o + na + ni + 2 + c2:]                                  # with passes: the sweep's errors, the moves
+        # with passes or refits: the sweep's errors, the moves; with refits: the errors after the last one, the count not taken
+        tail = pack[o + na + ni + 2 + c2:]
         if pd_flag:
             raise RuntimeError(f'{self.name}: the Gram system A0 + eta I is not positive definite (a pivot of its fp64 '
                                f'Cholesky factorisation was <= 0 or not finite)')
@@ -272,17 +349,28 @@ class GPTQConvHIP(EfficientQConvHIP):
             raise RuntimeError(f'{self.name}: the weight scale of output channel(s) {rows[:8]} is not finite and positive')
         err = float(sum(pack[2:o]))
         return dict(fin=pack[:2], gptq_err=err, alpha_w=alpha if self.channel_wise else alpha[0], w_iters=[int(max(iters))],
-                    gptq_err_sweep=float(sum(tail[:c2])) if tail else err, gptq_moves=int(sum(tail[c2:])))
+                    gptq_err_sweep=float(sum(tail[:c2])) if tail else err, gptq_moves=int(sum(tail[c2:2 * c2])),
+                    gptq_err_rescaled=float(sum(tail[2 * c2:3 * c2])) if fit.kept is not None else err,
+                    gptq_kept=int(tail[3 * c2]) if fit.kept is not None else 0)
 
 
-def check_options(refine, order):
-    """(passes, order) of ``gptq_refine`` / ``gptq_order``; a value outside 0 .. 16 or an unknown order is refused by name."""
+def _count(value, top: int) -> bool:
     try:
-        ok = not isinstance(refine, bool) and int(refine) == refine and 0 <= int(refine) <= ops_gptq.REFINE_MAX_PASSES
+        return not isinstance(value, bool) and int(value) == value and 0 <= int(value) <= top
     except (TypeError, ValueError):
-        ok = False
-    if not ok:
+        return False
+
+
+def check_options(refine, order, rescale=0):
+    """(passes, order, rounds) of ``gptq_refine`` / ``gptq_order`` / ``gptq_rescale``; passes outside 0 .. 16, an unknown
+    order, rounds outside 0 .. 8 or more than one round without passes are refused by name."""
+    if not _count(refine, ops_gptq.REFINE_MAX_PASSES):
         raise ValueError(f'gptq_refine {refine!r}: the passes behind the sweep, 0 to {ops_gptq.REFINE_MAX_PASSES}')
     if order not in GPTQ_ORDERS:
         raise ValueError(f'gptq_order {order!r}: one of {", ".join(GPTQ_ORDERS)}')
-    return int(refine), order
+    if not _count(rescale, ops_gptq.RESCALE_MAX_ROUNDS):
+        raise ValueError(f'gptq_rescale {rescale!r}: the rounds of [scale refit, passes], 0 to {ops_gptq.RESCALE_MAX_ROUNDS}')
+    if int(rescale) > 1 and int(refine) == 0:
+        raise ValueError(f'gptq_rescale {rescale!r} with gptq_refine 0: a second refit of unchanged ids changes nothing, '
+                         f'give 1 round or passes between the refits')
+    return int(refine), order, int(rescale)

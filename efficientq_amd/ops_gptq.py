@@ -163,6 +163,62 @@ def gptq_refine(ops, A0: torch.Tensor, eta: float, u_w: torch.Tensor, u_b: Optio
     return err, moves
 
 
+RESCALE_MAX_ROUNDS = 8  # gptq.py: rounds of [refit, passes]
+
+
+def gptq_rescale_plan(ops, c2: int, n: int) -> dict:
+    """The launches gptq_rescale makes for c2 rows of n unknowns (effq_gptq_rescale_plan_query; launches nothing)."""
+    out = [C.c_int() for _ in range(6)]
+    check(ops.lib.effq_gptq_rescale_plan_query(int(c2), int(n), *[C.byref(o) for o in out]), "effq_gptq_rescale_plan_query")
+    return dict(zip(("nblk", "tiles", "tiles_per_run", "runs", "forms_grid", "launches"), (o.value for o in out)))
+
+
+def gptq_rescale(ops, A0: torch.Tensor, eta: float, u_w: torch.Tensor, u_b: Optional[torch.Tensor], alpha: torch.Tensor,
+                 levels: int, G: torch.Tensor, b: Optional[torch.Tensor], ids: torch.Tensor, row_flag: torch.Tensor,
+                 pd_flag: torch.Tensor, per_row: Optional[bool] = None, out=None):
+    """(err, kept): the scale (and the bias) refitted on H = A0 + eta I with the ids fixed, the rule of gptq.rescale_host,
+    over what gptq_sweep or gptq_refine left: alpha (1 or c2 device doubles), G and b are updated in place, ids only read.
+    err (c2) doubles: f at the point every row now stands on; kept (1) int32: incremented for every refit not taken.
+    out: (err, kept) to write into (kept is not cleared).  Nothing is read back; a set flag leaves every output as it is."""
+    what = "gptq_rescale"
+    has_b = u_b is not None
+    if not isinstance(A0, torch.Tensor) or A0.dim() != 2 or A0.shape[0] != A0.shape[1] or A0.numel() == 0:
+        raise _lib.EffqError(f"{what}: A0 needs a square matrix, got {tuple(getattr(A0, 'shape', ()))}")
+    A0 = ops._f32(A0)
+    n = int(A0.shape[0])
+    nw = n - int(has_b)
+    if not isinstance(u_w, torch.Tensor) or u_w.dim() != 2 or u_w.shape[1] != nw or u_w.shape[0] < 1:
+        raise _lib.EffqError(f"{what}: u_w needs (c2, {nw}), got {tuple(getattr(u_w, 'shape', ()))}")
+    c2 = int(u_w.shape[0])
+    u_w = ops._f32(u_w)
+    if has_b:
+        u_b = ops._f32(u_b)
+        if u_b.numel() != c2:
+            raise _lib.EffqError(f"{what}: u_b has {u_b.numel()} elements for {c2} rows")
+    if per_row is None:
+        per_row = alpha.numel() == c2 and c2 > 1
+    if alpha.dtype != torch.float64 or ops._elsewhere(alpha) or alpha.numel() != (c2 if per_row else 1) or not alpha.is_contiguous():
+        raise _lib.EffqError(f"{what}: alpha needs {c2 if per_row else 1} device double(s)")
+    if not 2 <= int(levels) <= LEVELS_MAX:
+        raise _lib.EffqError(f"{what}: {levels} levels, takes 2 .. {LEVELS_MAX}")
+    dev = ops.device
+    if out is None:
+        out = (torch.empty(c2, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+    err, kept = out
+    for name, t, dt, m in (("G", G, torch.float32, c2 * nw), ("b", b, torch.float32, c2), ("ids", ids, torch.uint8, c2 * nw),
+                           ("err", err, torch.float64, c2), ("kept", kept, torch.int32, 1),
+                           ("row_flag", row_flag, torch.int32, c2), ("pd_flag", pd_flag, torch.int32, 1)):
+        if t is None and name == "b" and not has_b:
+            continue
+        if t is None or t.dtype != dt or t.numel() != m or not t.is_contiguous() or ops._elsewhere(t):
+            raise _lib.EffqError(f"{what}: {name} needs {m} contiguous {dt} values on {ops.device}")
+    ws = ops._workspace("gptq_rescale", ops.lib.effq_gptq_rescale_ws_bytes(c2, n))
+    check(ops.lib.effq_gptq_rescale(_ptr(A0), float(eta), n, _ptr(u_w), _ptr(u_b), c2, int(has_b), _ptr(ids), int(levels),
+                                    int(bool(per_row)), _ptr(row_flag), _ptr(pd_flag), _ptr(alpha), _ptr(G), _ptr(b),
+                                    _ptr(err), _ptr(kept), _ptr(ws), ws.numel(), ops.stream), "effq_gptq_rescale")
+    return err, kept
+
+
 def gptq_order(A0: torch.Tensor, has_bias: bool) -> torch.Tensor:
     """The permutation of gptq.order_host on the device, nothing read back: the weight columns by descending diag(A0),
     ties in their own order, the bias last."""

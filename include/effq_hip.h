@@ -1434,6 +1434,33 @@ int effq_gptq_refine(const float* A0, double eta, int n, const float* u_w, const
                      const double* alpha, int per_row, int levels, int passes, float* G, float* b, uint8_t* ids, double* err,
                      int32_t* moves, const int32_t* row_flag, const int* pd_flag, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- The weight scale refitted on the quadratic form (the rule: rescale_host of efficientq_amd/gptq.py, kernels: gptq_rescale.hip) ----
+ * With the level ids fixed, v_j = id_j d - 1 (d = 2 / (levels - 1)), v' = [v | 0], H and u as effq_gptq_refine reads them, a
+ * row's error is  f(alpha, beta) = alpha^2 a11 + 2 alpha beta a12 + beta^2 a22 - 2 alpha c1 - 2 beta c2 + c0  with
+ * a11 = v H v^T, a12 = (v' H)_bias, a22 = H_bias,bias, c1 = v' H u^T, c2 = (u H)_bias, c0 = u H u^T, all fp64.  With the bias
+ * eliminated, num_r = c1 - a12 c2 / a22 and den_r = a11 - a12^2 / a22 (c1 and a11 without a bias):
+ *   per_row != 0: alpha_r = num_r / den_r;   per_row == 0: alpha = sum_r num_r / sum_r den_r, the rows added in row order;
+ *   beta_r = (c2 - a12 alpha) / a22.
+ * A refit is taken only if the denominator is positive, alpha finite and positive, beta finite, and the row is not flagged
+ * (row_flag, or a present scale that is not finite and positive); per tensor every row must pass.  Taken: alpha (in/out, 1
+ * or c2 doubles) gets the new scale, b = f32(beta), G = f32(alpha) * level value in the arithmetic of the sweep, err_r =
+ * f(alpha, beta_r).  Not taken: alpha, b and G keep their bits, *kept is incremented (once per row, or once for the
+ * tensor), and an unflagged row's err_r is f at the point it keeps; a flagged row writes nothing.  ids are only read.
+ * The forms come from one fused kernel on v_mfma_f64_16x16x4_f64 over the 64 x 64 tiles of A0's upper triangle: each tile is
+ * read once, converted in registers and serves both halves of H; neither H, nor the fp64 operands, nor the product is
+ * stored.  Per-run partials in the workspace are added in a fixed order: no floating-point atomics, equal bits from equal
+ * inputs.  Three launches, nothing is read back; when *pd_flag is set no launch writes anything.
+ * ws: effq_gptq_rescale_ws_bytes(c2, n), no initialisation needed.  Refused as effq_gptq_refine refuses.
+ * effq_gptq_rescale_plan_query launches nothing: *nblk 64-blocks, *tiles tiles of the triangle, *tiles_per_run of them per
+ * workgroup, *runs partials per row, *forms_grid workgroups of the forms kernel, the launches of the call. */
+size_t effq_gptq_rescale_ws_bytes(int c2, int n);
+int effq_gptq_rescale_plan_query(int c2, int n, int* nblk, int* tiles, int* tiles_per_run, int* runs, int* forms_grid,
+                                 int* launches);
+int effq_gptq_rescale(const float* A0, double eta, int n, const float* u_w, const float* u_b, int c2, int has_bias,
+                      const uint8_t* ids, int levels, int per_row, const int32_t* row_flag, const int* pd_flag,
+                      double* alpha, float* G, float* b, double* err, int32_t* kept, void* ws, size_t ws_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

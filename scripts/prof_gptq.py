@@ -1,8 +1,10 @@
 """--qconv gptq beside --qconv effq: seconds per calibration and the summed layer_loss on the benchmark's BraTS
-configuration (alternating the two in one process; --variants adds gptq with 1 / 2 / 4 refinement passes and with
-activation ordering), and effq_gptq_chol / effq_gptq_sweep / a pass of effq_gptq_refine alone at a few system sizes.
+configuration (alternating the two in one process; --variants adds gptq with 1 / 2 / 4 refinement passes, with
+activation ordering and with R rounds of scale refit and K passes, --channel_wise runs them with one scale per row), and
+effq_gptq_chol / effq_gptq_sweep / a pass of effq_gptq_refine / effq_gptq_rescale alone at a few system sizes.
 
     python scripts/prof_gptq.py calib [--vols 16] [--size 128] [--levels 4] [--steps 3] [--only effq|gptq] [--variants]
+                                       [--channel_wise]
     python scripts/prof_gptq.py kernels [n ...]
 One JSON line per result."""
 import argparse
@@ -15,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 PEAK_F64_MFMA_TFLOPS = 78.6       # MI355X fp64 matrix peak (vendor)
+PEAK_HBM_GBS = 8000.0             # MI355X HBM3E bandwidth (vendor)
 DEV = "cuda:0"
 
 
@@ -22,14 +25,17 @@ def calib(a):
     from efficientq_amd import calibrate as K, config as Cf, synth
     vols = synth.calib_batch("brats", range(a.vols), a.size).to(DEV)
     nets = {}
-    # name: (qconv, passes, order)
-    variants = {"effq": ("effq", 0, "natural"), "gptq": ("gptq", 0, "natural")}
+    # name: (qconv, passes, order, rounds of scale refit)
+    variants = {"effq": ("effq", 0, "natural", 0), "gptq": ("gptq", 0, "natural", 0)}
     if a.variants:
-        variants.update({"gptq+r1": ("gptq", 1, "natural"), "gptq+r2": ("gptq", 2, "natural"),
-                         "gptq+r4": ("gptq", 4, "natural"), "gptq+act": ("gptq", 0, "act"), "gptq+act+r2": ("gptq", 2, "act")})
+        variants.update({"gptq+r1": ("gptq", 1, "natural", 0), "gptq+r2": ("gptq", 2, "natural", 0),
+                         "gptq+r4": ("gptq", 4, "natural", 0), "gptq+act": ("gptq", 0, "act", 0),
+                         "gptq+act+r2": ("gptq", 2, "act", 0), "gptq+s1": ("gptq", 0, "natural", 1),
+                         "gptq+s1r2": ("gptq", 2, "natural", 1), "gptq+s2r2": ("gptq", 2, "natural", 2)})
     for name in ([a.only] if a.only else variants):
-        qconv, passes, order = variants[name]
-        args = Cf.make_args(dict(Cf.BRATS_NET, qconv=qconv), a.levels, a.levels, gptq_refine=passes, gptq_order=order)
+        qconv, passes, order, rounds = variants[name]
+        args = Cf.make_args(dict(Cf.BRATS_NET, qconv=qconv), a.levels, a.levels, gptq_refine=passes, gptq_order=order,
+                            gptq_rescale=rounds, lwq_channel_wise=a.channel_wise)
         QConv, _, kwQ = Cf.get_conv_class(args)
         model = Cf.get_model_cube(args, QConv, kwQ)[0]["model"]
         synth.randomise_network(model, 0)
@@ -57,7 +63,7 @@ def calib(a):
             times[name].append(round(dt, 4))
     for name in nets:
         t = sorted(times[name])
-        print(json.dumps(dict(metric="calibration", qconv=name, vols=a.vols, size=a.size, levels=a.levels,
+        print(json.dumps(dict(metric="calibration", qconv=name, channel_wise=a.channel_wise, vols=a.vols, size=a.size, levels=a.levels,
                               layer_loss_sum=loss[name], seconds=times[name], median_s=t[len(t) // 2])), flush=True)
 
 
@@ -112,6 +118,19 @@ def kernels(a):
                                   ms_one_pass_call=round(ms1, 3), flop=2.0 * c2 * n * n,
                                   launches_per_pass=(OG.gptq_refine_plan(ops, c2, n, 2)["launches"] -
                                                      OG.gptq_refine_plan(ops, c2, n, 1)["launches"]))), flush=True)
+            # the scale refit: half of the (2 c2) x n x n product (the mirrored half is not multiplied), one read of the
+            # triangle of A0
+            refine(1)
+            a_fit, kept = alpha.clone(), torch.zeros(1, dtype=torch.int32, device=DEV)
+            err = torch.empty(c2, dtype=torch.float64, device=DEV)
+            ms = timed(lambda: OG.gptq_rescale(ops, A0, 8.0, u_w, u_b, a_fit, 4, G, b, ids, row_flag, flag, out=(err, kept)),
+                       reps)
+            flop, tri = 2.0 * c2 * n * n, 2.0 * n * (n + 1)
+            print(json.dumps(dict(metric="gptq_rescale", n=n, c2=c2, ms=round(ms, 3), flop=flop,
+                                  tflops=round(flop / ms / 1e9, 3),
+                                  frac_f64_matrix_peak=round(flop / ms / 1e9 / PEAK_F64_MFMA_TFLOPS, 5),
+                                  triangle_bytes=tri, frac_hbm_peak=round(tri / ms / 1e6 / PEAK_HBM_GBS, 5),
+                                  kept=int(kept.item()), **OG.gptq_rescale_plan(ops, c2, n))), flush=True)
         del A0, P
 
 
@@ -125,6 +144,7 @@ if __name__ == "__main__":
     c.add_argument("--steps", type=int, default=3)
     c.add_argument("--only", choices=["effq", "gptq"], default=None)
     c.add_argument("--variants", action="store_true")
+    c.add_argument("--channel_wise", action="store_true")
     k = sub.add_parser("kernels")
     k.add_argument("n", type=int, nargs="*")
     a = ap.parse_args()
